@@ -7,7 +7,15 @@ synthetic chips (6 bands, T=1, 224x224, 2 classes, class weights [1,3], ignore_i
 ``--batch`` (weak scaling).  A step = K0 normalise of a resident int16 batch -> forward -> loss/metrics -> backward ->
 (gradient all-reduce) -> AdamW.
 
-The line is kept COMPACT (< 2000 characters: the driver's record keeps only a tail of stdout).  On it, besides the contract keys:
+A plain run does only what the headline needs: set up, W warm-up steps, K timed steps, the outputs of the last timed step
+(``--dump-outputs DIR``), and a line with the contract keys plus the cheap ``config`` fields (workload, batch, launch mode,
+final loss, whole_step_mfma_frac).  ``--dump-outputs DIR`` writes DIR/<name>.npy: ``stats`` (float64: the step's return value,
+weighted-NLL sum and valid pixels), ``loss``, and fixed seeded samples (float32, at most 4 Mi elements each) of the updated fp32
+master weights (``params``), the step's weight gradients (``grads``) and its logits gradient (``dlogits``).  The inputs, the
+initial weights and the dropout stream are seeded, so the same arguments give the same arrays from run to run.
+
+``--full`` adds every other leg and check below (as the default run did before the option existed).  The line is kept COMPACT
+(< 2000 characters: the driver's record keeps only a tail of stdout).  On it, besides the contract keys:
   config             workload + the other legs' headline numbers: encoder_fwd_mfma_frac / encoder_fwd_ms (the encoder forward
                      alone: patch embed + L blocks + final LayerNorm -- the north-star target is stated on it),
                      inference_chips_per_s (K0 + forward + argmax int8), parity_mode_chips_per_s / _inference (the SAME workload
@@ -70,6 +78,30 @@ HBM_OPS = ["ig_normalize_chips", "ig_layernorm_fwd", "ig_layernorm_bwd", "ig_col
            "ig_classifier_fwd", "ig_classifier_bwd", "ig_classifier_bn_fwd", "ig_classifier_bn_bwd", "ig_ce_loss", "ig_adamw_step"]
 GEMM_OPS.append("ig_linear_wgrad_group")
 TIMED_OPS = ["ig_linear_fwd", "ig_linear_residual_fwd", "ig_linear_dgrad", "ig_linear_wgrad", "ig_linear_wgrad_group"]
+DUMP_SAMPLE = 4 << 20  # elements per sampled array of --dump-outputs: 3 x 16 MiB, under the 64 MB cap
+
+
+def dump_outputs(path: str, mod, stats: torch.Tensor) -> None:
+    """--dump-outputs: what the last timed train step computed, as DIR/<name>.npy (see the module docstring).  Arrays longer than
+    DUMP_SAMPLE are sampled at fixed positions (seeded, sorted), the same for every run with the same arguments."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    torch.cuda.synchronize()
+    eng, store = mod.net.engine, mod.net.store
+    arrays = {"stats": stats.double(), "loss": (stats[0] / stats[1]).double().reshape(1)}
+    ws = eng._last["ws"] if eng._last is not None else {}
+    for name, t in (("params", store.flat), ("grads", store.grad), ("dlogits", ws.get("dlogits"))):
+        if t is None:
+            continue
+        flat = t.detach().reshape(-1)
+        if flat.numel() > DUMP_SAMPLE:
+            g = torch.Generator().manual_seed(1042)
+            idx = torch.randint(0, flat.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+            flat = flat[idx.to(flat.device)]
+        arrays[name] = flat.float()
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
 
 
 def cpu_baseline(target_s: float = 10.0) -> dict:
@@ -223,6 +255,10 @@ def main() -> None:
     ap.add_argument("--model", default="prithvi_eo_v1_100", help="variant (other BASELINE configs: prithvi_eo_v2_300)")
     ap.add_argument("--temporal", type=int, default=1, help="T: 1 = configs[1] (default), 3 = configs[2] multi-temporal crop")
     ap.add_argument("--classes", type=int, default=2)
+    ap.add_argument("--full", action="store_true", help="also run every other leg and check: inference, encoder forward, per-kernel rooflines, "
+                    "PCIe input, bf16x3 parity, tile, YAML-batch and N > 1 T = 3 legs, CPU baseline, data-parallel pre-flight, detail file; "
+                    "the --no-* options below select among them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity-leg", action="store_true", help="skip the bf16x3 (1e-3-parity) leg")
     ap.add_argument("--no-tile", action="store_true", help="skip the configs[3] sliding-window leg")
@@ -305,8 +341,9 @@ def main() -> None:
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return t.item()
 
-    def run_mode(precision: str, profile: bool, graph: bool, wl: dict = None):
-        """Train + inference (+ encoder-forward) legs of one precision mode on workload ``wl``; returns a dict of raw measurements."""
+    def run_mode(precision: str, profile: bool, graph: bool, wl: dict = None, legs: bool = True, dump: str = None):
+        """Train + inference (+ encoder-forward) legs of one precision mode on workload ``wl``; returns a dict of raw measurements.
+        ``legs=False``: the timed train steps only.  ``dump``: write the last timed step's outputs there before anything else runs."""
         wl = wl or main_wl
         B, T, NCLS, raws, labels, xbuf, cw = wl["B"], wl["T"], wl["NCLS"], wl["raws"], wl["labels"], wl["xbuf"], wl["cw"]
         mod = PrithviSegmentationModule(image_size=224, learning_rate=1e-4, freeze_backbone=False, load_pretrained_weights=False,
@@ -340,6 +377,11 @@ def main() -> None:
         barrier()
         dt_own = time.perf_counter() - t0
         dt = max_over_ranks(dt_own)
+        if dump is not None and rank == 0:
+            dump_outputs(dump, mod, stats)
+        if not legs:
+            return {"mod": mod, "dt": dt, "graphed": graphed is not None, "loss": (stats[0] / stats[1]).item(),
+                    "dp_mode": None if sync is None else ("zero1" if isinstance(sync, D.ShardedGradSync) else "allreduce")}
         per_rank = None
         if dp and dist.is_initialized():  # every rank's own clock around the same K steps (the barrier makes them nearly equal: a straggler shows)
             mine = torch.tensor([dt_own], dtype=torch.float64, device=dev)
@@ -449,12 +491,52 @@ def main() -> None:
         torch.cuda.empty_cache()
         return info
 
-    preflight = dp_preflight() if dp and dist.is_initialized() else None
-    main_res = run_mode(args.precision, not args.no_profile and not args.graph, args.graph)
+    preflight = dp_preflight() if args.full and dp and dist.is_initialized() else None
+    main_res = run_mode(args.precision, args.full and not args.no_profile and not args.graph, args.graph, legs=args.full, dump=args.dump_outputs)
     hbm_peak_gib = round(torch.cuda.max_memory_allocated() / 2**30, 2) if torch.cuda.is_available() else None  # the main legs (train + inference)
     mod = main_res["mod"]
     cfgm = mod.net.cfg
     fpc, fpc_enc = flop_per_chip_fwd(cfgm.embed_dim, cfgm.depth, T, NCLS)
+    headline = (T, NCLS, args.model) == (1, 2, "prithvi_eo_v1_100")
+
+    def contract_line(res: dict) -> dict:
+        """The contract keys and the config fields that need no extra run (a plain run prints exactly this)."""
+        value = world * B * args.steps / res["dt"]
+        cfg_out = {"workload": "BASELINE.json configs[1]: Prithvi-100M fine-tune, Sen1Floods11-shaped synthetic int16 chips (6 bands, T=1, "
+                               "224x224, 2 classes, weights [1,3], ignore -1, dropout 0.1)" if headline else
+                               f"{args.model} T={T} {NCLS} classes, synthetic int16 chips, dropout 0.1, random init",
+                   "per_gpu_batch": B, "global_batch": B * world, "parallelism": f"dp{world}",
+                   "launch": "hipGraph" if res["graphed"] else "eager",
+                   "deterministic": os.environ.get("IG_DETERMINISTIC", "1") != "0",  # bit-reproducible reductions (reference: Trainer(deterministic=True))
+                   "final_loss": round(res["loss"], 5),
+                   "whole_step_mfma_frac": round(value / world * 3 * fpc / (PEAK_BF16_TFLOPS * 1e12), 4)}  # fmt: skip
+        return {
+            "metric": f"HLS chips/sec (train fwd+bwd+AdamW), {args.model} 224x224x6 T={T}",
+            "value": round(value, 2),
+            "unit": "chips/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(1e3 * res["dt"] / args.steps, 3),
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": args.precision,
+            "data": "synthetic",
+            "config": cfg_out,
+        }
+
+    if not args.full:
+        if rank == 0:
+            out = contract_line(main_res)
+            if dp:
+                out["dist"] = {"ranks": world, "backend": dist.get_backend(), "mode": main_res["dp_mode"]}
+            if args.dump_outputs is not None:
+                out["outputs"] = args.dump_outputs
+            print(json.dumps(out))
+        if dp:
+            dist.destroy_process_group()
+        return
 
     # PCIe-inclusive view (never ``value``): one batch of raw int16 chips + float labels from PINNED host memory, (i) copied
     # serially in front of every step, (ii) copied on a side stream into the other half of a double buffer while the step runs.
@@ -607,20 +689,13 @@ def main() -> None:
 
     dt, dti = main_res["dt"], main_res["dti"]
     value = world * B * args.steps / dt
-    headline = (T, NCLS, args.model) == (1, 2, "prithvi_eo_v1_100")
     enc_tflops = B * fpc_enc / (main_res["enc_ms"] * 1e-3) / 1e12
-    cfg_out = {"workload": "BASELINE.json configs[1]: Prithvi-100M fine-tune, Sen1Floods11-shaped synthetic int16 chips (6 bands, T=1, "
-                           "224x224, 2 classes, weights [1,3], ignore -1, dropout 0.1)" if headline else
-                           f"{args.model} T={T} {NCLS} classes, synthetic int16 chips, dropout 0.1, random init",
-               "per_gpu_batch": B, "global_batch": B * world, "parallelism": f"dp{world}",
-               "launch": "hipGraph" if main_res["graphed"] else "eager",
-               "deterministic": os.environ.get("IG_DETERMINISTIC", "1") != "0",  # bit-reproducible reductions (reference: Trainer(deterministic=True))
-               "final_loss": round(main_res["loss"], 5),
-               "whole_step_mfma_frac": round(value / world * 3 * fpc / (PEAK_BF16_TFLOPS * 1e12), 4),
-               "encoder_fwd_ms": round(main_res["enc_ms"], 3), "encoder_fwd_tflops": round(enc_tflops, 1),
-               "encoder_fwd_mfma_frac": round(enc_tflops / PEAK_BF16_TFLOPS, 4),
-               "inference_chips_per_s": round(world * B * args.steps / dti, 1),
-               "inference_mfma_frac": round(B * args.steps / dti * fpc / (PEAK_BF16_TFLOPS * 1e12), 4)}  # fmt: skip
+    out = contract_line(main_res)
+    cfg_out = out["config"]
+    cfg_out.update({"encoder_fwd_ms": round(main_res["enc_ms"], 3), "encoder_fwd_tflops": round(enc_tflops, 1),
+                    "encoder_fwd_mfma_frac": round(enc_tflops / PEAK_BF16_TFLOPS, 4),
+                    "inference_chips_per_s": round(world * B * args.steps / dti, 1),
+                    "inference_mfma_frac": round(B * args.steps / dti * fpc / (PEAK_BF16_TFLOPS * 1e12), 4)})  # fmt: skip
     detail = {"gflop_per_chip_fwd": round(fpc / 1e9, 2), "gflop_per_chip_encoder_fwd": round(fpc_enc / 1e9, 2),
               "inference_ms_per_step": round(1e3 * dti / args.steps, 3), "optimizer": "AdamW lr 1e-4 wd 1e-2",
               "hbm_peak_gib_torch_allocator": hbm_peak_gib}  # (the library's own scratch -- slabs, packed weights -- is outside the allocator: < 1 GiB)
@@ -647,21 +722,8 @@ def main() -> None:
     if host_leg is not None:
         cfg_out["train_chips_per_s_pcie_overlapped"] = host_leg["train_chips_per_s_overlapped_copy"]
         detail["host_input"] = host_leg
-    out = {
-        "metric": f"HLS chips/sec (train fwd+bwd+AdamW), {args.model} 224x224x6 T={T}",
-        "value": round(value, 2),
-        "unit": "chips/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(1e3 * dt / args.steps, 3),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": args.precision,
-        "data": "synthetic",
-        "config": cfg_out,
-    }
+    if args.dump_outputs is not None:
+        out["outputs"] = args.dump_outputs
     prof, prof_all = main_res["prof"], main_res["prof_all"]
     if prof is not None:
         def table(p, per_step):

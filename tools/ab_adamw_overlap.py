@@ -11,6 +11,6 @@ import instageo_amd.segmentation as seg  # noqa: E402
 seg._ADAMW_OVERLAP = sys.argv[1] == "1"
 import bench  # noqa: E402
 
-sys.argv = ["bench.py", "--steps", "60", "--warmup", "10", "--no-parity-leg", "--no-tile", "--no-yaml-legs", "--no-cpu-baseline", "--no-profile",
+sys.argv = ["bench.py", "--full", "--steps", "60", "--warmup", "10", "--no-parity-leg", "--no-tile", "--no-yaml-legs", "--no-cpu-baseline", "--no-profile",
             "--detail-file", "/tmp/ab_adamw.json"] + sys.argv[2:]
 bench.main()

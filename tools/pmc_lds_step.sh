@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 case $OUT in /*) ;; *) OUT=$R/$OUT;; esac
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-timeout 300 rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE --kernel-trace --output-format csv -d $OUT/lds -o pmc -- python3 $R/bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-parity-leg --no-tile --no-yaml-legs --no-profile --detail-file /tmp/d.json "$@" > $OUT/lds.log 2>&1
+timeout 300 rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE --kernel-trace --output-format csv -d $OUT/lds -o pmc -- python3 $R/bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-parity-leg --no-tile --no-yaml-legs --no-profile --detail-file /dev/null "$@" > $OUT/lds.log 2>&1
 python3 - <<PY
 import csv,glob,collections
 agg=collections.defaultdict(lambda: collections.defaultdict(float)); n=collections.Counter()
