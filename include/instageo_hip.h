@@ -261,6 +261,21 @@ int ig_kd_mse_loss(const float* pred, const float* teacher, const float* labels,
 int ig_auc_update(const float* logits, const void* labels, int label_dtype, long ignore_index, unsigned long long* hist, int B,
                   long HW, int ncls, int nbins, float min_score, float max_score, void* stream);
 int ig_softmax_prob(const float* logits, float* out, int B, long HW, int ncls, int cls, void* stream);
+/* Probability-blended tile inference (tile_blend.hip).  The windows of a tile form the row-major grid tops[n_rows] x lefts[n_cols]
+ * (DEVICE int32, each ascending: process_test's rule, dataloader.py:655-664, optionally with a last origin at size - crop).
+ * ig_window_blend_accumulate adds windows [w0, w0 + n) of that grid, logits (n, ncls, crop, crop) f32, to a canvas band:
+ * acc (ncls, Hb, W) and wsum (Hb, W) hold canvas rows [y0, y0 + Hb) of the H x W tile; only rows [ylo, yhi) of it are visited (the
+ * rows the batch covers).  Per covered pixel and window, w = wvec[y - top] * wvec[x - left]: wsum += w, acc[c] += w * softmax(logits)[c]
+ * (max-subtracted, as predict_step's probability, segmentation.py:202-213; the raw value when ncls == 1).  No atomics: a pixel's terms
+ * are added in row-major window order, so the canvas is bit-identical however the windows are split into batches.
+ * ig_window_blend_finalize, per pixel of the full canvas (HW = H * W): where wsum == 0 or (nodata_enabled) any band of tile
+ * (TC, H, W), tile_dtype 0 = int16 / 1 = f32, equals no_data_value: classmap = fill, prob = NaN; else p_c = acc_c / wsum, classmap =
+ * the first argmax (ig_argmax_i8), prob (ncls, H, W) optional.  ncls == 1: classmap NULL, prob = the blended regression value. */
+int ig_window_blend_accumulate(const float* logits, const int* tops, const int* lefts, int n_rows, int n_cols, long w0, int n,
+                               const float* wvec, float* acc, float* wsum, int ncls, int crop, int H, int W, int y0, int Hb, int ylo,
+                               int yhi, void* stream);
+int ig_window_blend_finalize(const float* acc, const float* wsum, const void* tile, int tile_dtype, int TC, double no_data_value,
+                             int nodata_enabled, signed char* classmap, float* prob, int ncls, long HW, int fill, void* stream);
 int ig_confusion_update(const long long* y_true, const long long* y_pred, unsigned long long* confusion, long n, int k,
                         long ignore_index, int has_ignore, void* stream);
 /* torch.optim.AdamW step on a flat buffer (+ clip_weights, + bf16 shadow refresh)        base.py:103-126 */

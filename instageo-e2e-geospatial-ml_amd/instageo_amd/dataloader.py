@@ -73,6 +73,25 @@ def window_origins(img_size: int, crop_size: int, stride: int) -> List[Tuple[int
     ]
 
 
+def window_grid(height: int, width: int, crop_size: int, stride: int, cover_edges: bool = False) -> Tuple[List[int], List[int]]:
+    """Window origins of an H x W tile as two ascending lists (tops, lefts); the windows are their row-major product.
+
+    ``cover_edges=False`` is :func:`window_origins`' rule per axis (a square tile gives exactly its list); ``cover_edges=True`` adds a
+    last origin at ``size - crop`` on an axis that lacks it, so every pixel is covered."""
+    if stride <= 0:
+        raise ValueError(f"stride must be positive (got {stride})")
+    if crop_size <= 0 or crop_size > height or crop_size > width:
+        raise ValueError(f"crop_size {crop_size} does not fit a {height} x {width} tile")
+
+    def axis(size: int) -> List[int]:
+        o = list(range(0, size - crop_size + 1, stride))
+        if cover_edges and o[-1] != size - crop_size:
+            o.append(size - crop_size)
+        return o
+
+    return axis(height), axis(width)
+
+
 def extract_windows(tile: torch.Tensor, origins: Sequence[Tuple[int, int]], crop_size: int) -> torch.Tensor:
     """tile (T*C,S,S) [or label (S,S)] -> stacked windows (n, T*C, crop, crop) [(n, crop, crop)]: pure copies."""
     if tile.dim() == 2:

@@ -542,3 +542,34 @@ def gather_class_maps(local: torch.Tensor, counts: Sequence[int], dst: int = 0) 
     if rank != dst:
         return None
     return torch.cat([o[: counts[r]] for r, o in enumerate(outs)], dim=0)
+
+
+def reduce_row_bands(local: torch.Tensor, bands: Sequence[Tuple[int, int]], height: int, dst: int = 0) -> Optional[torch.Tensor]:
+    """Sum per-rank canvas bands onto one (K, height, W) canvas on ``dst`` (blended tile inference).
+
+    ``local`` (K, Hb_r, W) holds canvas rows [y0_r, y0_r + Hb_r) of this rank; ``bands[r]`` = (y0_r, Hb_r) for every rank (known
+    to all of them from the window partition, so only the data travels).  The bands are added to a zeroed canvas in rank order:
+    the sum equals the one-rank canvas to fp32 rounding (partial sums are added), not bit for bit.  The gloo backend moves the
+    bands through host memory; without a process group the band is placed on the canvas as it is."""
+    K, _, W = local.shape
+    if not dp_active():
+        y0, hb = bands[0]
+        if y0 == 0 and hb == height:
+            return local
+        full = torch.zeros((K, height, W), dtype=local.dtype, device=local.device)
+        full[:, y0 : y0 + hb] = local
+        return full
+    world, rank = world_size(), dist.get_rank()
+    hmax = max(max(hb for _, hb in bands), 1)
+    on_host = dist.get_backend() == "gloo"
+    pad = torch.zeros((K, hmax, W), dtype=local.dtype, device="cpu" if on_host else local.device)
+    pad[:, : local.shape[1]] = local
+    outs = [torch.empty_like(pad) for _ in range(world)] if rank == dst else None
+    dist.gather(pad, outs, dst=dst)
+    if rank != dst:
+        return None
+    full = torch.zeros((K, height, W), dtype=local.dtype, device=local.device)
+    for (y0, hb), o in zip(bands, outs):
+        if hb:
+            full[:, y0 : y0 + hb] += o[:, :hb].to(local.device)
+    return full

@@ -8,6 +8,11 @@ structure (``save_prediction``, infer_utils.py:37-54, through :mod:`instageo_amd
 ``process_test``, dataloader.py:655-664), gathered + normalised by ONE kernel launch per batch (``ig_normalize_windows``),
 windows partitioned contiguously over ranks, final gather; ``stitch_windows`` puts the class maps back on the tile canvas
 (overlapping windows: every pixel takes the window whose centre is nearest), ``tile_inference`` does file -> file.
+
+``blended_window_inference`` is the second tile path (``tile_inference(blend="mean" | "gaussian")``): any H x W tile, optionally a
+last window row / column at the edge (``cover_edges``), per-window class probabilities averaged on the canvas with a separable
+window weight (``ig_window_blend_accumulate``: gather form, no atomics, bit-identical for any batch size), then one
+``ig_window_blend_finalize`` -> class map + optional probability raster.
 """
 from __future__ import annotations
 
@@ -20,14 +25,16 @@ import torch
 
 from . import distributed as D
 from . import ops, tiff
-from .dataloader import gather_windows, origins_tensor, window_origins
+from .dataloader import gather_windows, origins_tensor, window_grid, window_origins
 
 
-def save_prediction(prediction: np.ndarray, file_name: str, output_folder: str, profile: Optional[Dict[str, Any]] = None) -> str:
+def save_prediction(prediction: np.ndarray, file_name: str, output_folder: str, profile: Optional[Dict[str, Any]] = None,
+                    kind: str = "prediction") -> str:
     """Save one prediction as a TIFF next to the reference's naming (``chip`` -> ``prediction`` in the base name,
-    infer_utils.py:51-54); ``profile`` = the source chip's profile (georeferencing tags are copied, count = 1)."""
+    infer_utils.py:51-54); ``profile`` = the source chip's profile (georeferencing tags are copied, count = 1).  ``kind`` replaces
+    "prediction" in the name (``probability`` rasters of the blended tile path)."""
     base = os.path.basename(str(file_name))
-    out = base.replace("chip", "prediction") if "chip" in base else "prediction_" + base
+    out = base.replace("chip", kind) if "chip" in base else f"{kind}_" + base
     if not out.lower().endswith((".tif", ".tiff")):
         out = os.path.splitext(out)[0] + ".tif"
     path = os.path.join(output_folder, out)
@@ -148,13 +155,80 @@ def stitch_windows(maps: torch.Tensor, origins: Sequence[Tuple[int, int]], size,
 
 
 @torch.no_grad()
+def blended_window_inference(tile: torch.Tensor, model, mean: Sequence[float], std: Sequence[float], temporal_size: int = 1,
+                             crop_size: int = 224, stride: int = 224, batch_size: int = 64, constant_multiplier: Optional[float] = None,
+                             blend: str = "gaussian", sigma_scale: float = 0.125, cover_edges: bool = True,
+                             no_data_value: Optional[float] = None, fill: int = -1, probabilities: bool = False
+                             ) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """tile (T*C, H, W) int16|f32 on the device, any H, W >= crop -> (class map (H, W) int8, probabilities (ncls, H, W) f32 or None)
+    on rank 0, (None, None) elsewhere.  A regression head (one output channel) gives (None, the blended value (1, H, W)).
+
+    Windows: the row-major grid of :func:`window_grid` (``cover_edges``: a last row / column of windows at the tile edge).  Every
+    window's softmax probabilities are added to the canvas with the weight ``wvec[dy] * wvec[dx]`` (:func:`ops.blend_weights`) and
+    divided by the summed weight at the end.  Pixels no window covers, or with any band == ``no_data_value``, get ``fill`` / NaN.
+    The canvas is bit-identical for any ``batch_size`` given the same window logits.  Ranks take contiguous blocks of the window
+    list (as :func:`sliding_window_inference`) and accumulate only the canvas rows their windows cover; rank 0 adds the bands in
+    rank order (:func:`distributed.reduce_row_bands`), which equals the one-rank canvas to fp32 rounding."""
+    net, eng = _engine_of(model)
+    net.eval()
+    TC, H, W = tile.shape
+    ncls = net.cfg.num_classes
+    tops, lefts = window_grid(H, W, crop_size, stride, cover_edges)
+    ncol = len(lefts)
+    world = D.world_size()
+    rank = torch.distributed.get_rank() if world > 1 else 0
+    lo, hi = D.shard_range(len(tops) * ncol, rank, world)
+
+    def rows_of(a: int, b: int) -> Tuple[int, int]:  # canvas rows covered by windows [a, b)
+        return (tops[a // ncol], tops[(b - 1) // ncol] + crop_size) if b > a else (0, 0)
+
+    if D.dp_active():
+        bands = [(y0, y1 - y0) for y0, y1 in (rows_of(*D.shard_range(len(tops) * ncol, r, world)) for r in range(world))]
+    else:
+        bands = [(0, H)]
+    y0, hb = bands[rank]
+    dev = tile.device
+    canvas = torch.zeros((ncls + 1, hb, W), dtype=torch.float32, device=dev)  # acc (ncls planes) + wsum
+    wvec = ops.blend_weights(crop_size, blend, sigma_scale).to(dev)
+    tops_d = torch.tensor(tops, dtype=torch.int32).to(dev)
+    lefts_d = torch.tensor(lefts, dtype=torch.int32).to(dev)
+    mine = origins_tensor([(tops[w // ncol], lefts[w % ncol]) for w in range(lo, hi)], dev)
+    n = hi - lo
+    C = TC // temporal_size
+    nbatch = max(1, -(-n // batch_size))  # balanced batches (sliding_window_inference)
+    bs = -(-n // nbatch) if n else 1
+    xbuf = torch.empty((max(bs, 1), C, temporal_size, crop_size, crop_size), dtype=torch.float32, device=dev)
+    for i in range(0, n, bs):
+        k = min(bs, n - i)
+        x, _ = gather_windows(tile, mine[i : i + k], mean, std, temporal_size, crop_size, constant_multiplier, out=xbuf[:k])
+        logits = eng.forward(x, training=False, save=False)
+        ops.window_blend_accumulate(logits, tops_d, lefts_d, lo + i, wvec, canvas[:ncls], canvas[ncls], H, y0, rows_of(lo + i, lo + i + k))
+    full = D.reduce_row_bands(canvas, bands, H, dst=0)
+    if full is None:
+        return None, None
+    return ops.window_blend_finalize(full[:ncls], full[ncls], tile, no_data_value, fill, probabilities)
+
+
+@torch.no_grad()
 def tile_inference(tile_path: str, output_folder: str, model, mean: Sequence[float], std: Sequence[float], temporal_size: int = 1,
                    crop_size: int = 224, stride: int = 224, batch_size: int = 64, constant_multiplier: Optional[float] = None,
-                   no_data_value: Optional[float] = -9999, fill: int = -1, device: str = "cuda") -> Optional[str]:
+                   no_data_value: Optional[float] = -9999, fill: int = -1, device: str = "cuda", blend: str = "nearest",
+                   cover_edges: bool = False, sigma_scale: float = 0.125, save_probabilities: bool = False) -> Optional[str]:
     """GeoTIFF tile -> ``prediction_*.tif`` class map of the same georeferencing: read the (T*C, H, W)
     tile, sliding-window inference over all ranks, stitch, blank NODATA pixels (any band == ``no_data_value``) and uncovered
-    border pixels with ``fill``, write on rank 0.  Returns the output path on rank 0, None elsewhere."""
+    border pixels with ``fill``, write on rank 0.  Returns the output path on rank 0, None elsewhere.
+
+    ``blend="nearest"`` (default): square tiles, nearest-centre stitch (:func:`stitch_windows`).  ``blend="mean" | "gaussian"``:
+    :func:`blended_window_inference` on any H x W tile, optionally with ``cover_edges``; a regression head writes its blended value
+    as float32.  ``save_probabilities`` also writes ``probability_*.tif`` (float32, one band per class, NaN = NODATA)."""
+    if blend not in ("nearest", "mean", "gaussian"):
+        raise ValueError(f"blend must be 'nearest', 'mean' or 'gaussian' (got {blend!r})")
+    if blend == "nearest" and (cover_edges or save_probabilities):
+        raise ValueError("cover_edges and save_probabilities need blend='mean' or 'gaussian' (the nearest-centre stitch has neither)")
     arr, profile = tiff.read(tile_path)
+    if blend != "nearest":
+        return _blended_tile_file(arr, profile, tile_path, output_folder, model, mean, std, temporal_size, crop_size, stride, batch_size,
+                                  constant_multiplier, no_data_value, fill, device, blend, cover_edges, sigma_scale, save_probabilities)
     if arr.shape[1] != arr.shape[2]:
         raise ValueError("tile_inference expects a square tile (the window rule of process_test uses one img_size)")
     t = torch.from_numpy(arr if arr.dtype in (np.int16, np.float32) else arr.astype(np.float32)).to(device)
@@ -169,3 +243,21 @@ def tile_inference(tile_path: str, output_folder: str, model, mean: Sequence[flo
     prof.update(count=1, dtype="int8", nodata=fill)
     prof["tags"] = {k: v for k, v in profile["tags"].items() if k != 42113}
     return save_prediction(canvas.cpu().numpy(), tile_path, output_folder, prof)
+
+
+def _blended_tile_file(arr, profile, tile_path, output_folder, model, mean, std, temporal_size, crop_size, stride, batch_size,
+                       constant_multiplier, no_data_value, fill, device, blend, cover_edges, sigma_scale, save_probabilities) -> Optional[str]:
+    t = torch.from_numpy(arr if arr.dtype in (np.int16, np.float32) else arr.astype(np.float32)).to(device)
+    classmap, prob = blended_window_inference(t, model, mean, std, temporal_size, crop_size, stride, batch_size, constant_multiplier,
+                                              blend, sigma_scale, cover_edges, no_data_value, fill, save_probabilities)
+    if classmap is None and prob is None:
+        return None
+    os.makedirs(output_folder, exist_ok=True)
+    tags = {k: v for k, v in profile["tags"].items() if k != 42113}
+    float_prof = dict(profile, count=1, dtype="float32", nodata=None, tags={**tags, 42113: (2, "nan")})
+    if classmap is None:  # regression head: the blended value is the prediction
+        return save_prediction(prob[0].cpu().numpy(), tile_path, output_folder, float_prof)
+    out = save_prediction(classmap.cpu().numpy(), tile_path, output_folder, dict(profile, count=1, dtype="int8", nodata=fill, tags=tags))
+    if save_probabilities:
+        save_prediction(prob.cpu().numpy(), tile_path, output_folder, dict(float_prof, count=prob.shape[0]), kind="probability")
+    return out

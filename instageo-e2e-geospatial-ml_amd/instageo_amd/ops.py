@@ -697,6 +697,54 @@ def argmax_i8(logits, out=None):
     return out
 
 
+def blend_weights(crop: int, blend: str, sigma_scale: float = 0.125) -> torch.Tensor:
+    """(crop,) f32 window weight of one axis (the 2-D weight is the outer product): "mean" = ones; "gaussian" =
+    exp(-(i - (crop-1)/2)^2 / (2 sigma^2)), sigma = sigma_scale * crop, clamped to >= 1e-3, computed in float64 and rounded once."""
+    if blend == "mean":
+        return torch.ones(crop, dtype=torch.float32)
+    if blend != "gaussian":
+        raise ValueError(f"blend must be 'mean' or 'gaussian' (got {blend!r})")
+    if not sigma_scale > 0:
+        raise ValueError(f"sigma_scale must be positive (got {sigma_scale})")
+    i = torch.arange(crop, dtype=torch.float64) - (crop - 1) / 2.0
+    sigma = float(sigma_scale) * crop
+    return torch.exp(-(i * i) / (2.0 * sigma * sigma)).clamp_min(1e-3).to(torch.float32)
+
+
+def window_blend_accumulate(logits, tops, lefts, w0: int, wvec, acc, wsum, H: int, y0: int = 0, rows: Optional[Tuple[int, int]] = None) -> None:
+    """Add windows [w0, w0 + n) of the row-major grid tops x lefts (int32 device tensors) to a canvas band (include/instageo_hip.h):
+    logits (n, ncls, crop, crop) f32, acc (ncls, Hb, W) / wsum (Hb, W) f32 = canvas rows [y0, y0 + Hb) of an H x W tile.  ``rows`` =
+    (ylo, yhi), the canvas rows the batch covers (default: the whole band)."""
+    n, ncls, crop = logits.shape[0], logits.shape[1], logits.shape[-1]
+    Hb, W = wsum.shape
+    assert acc.shape == (ncls, Hb, W) and wvec.numel() == crop and tops.dtype == torch.int32 and lefts.dtype == torch.int32
+    ylo, yhi = rows if rows is not None else (y0, y0 + Hb)
+    # HBM bytes: the logits once + one read and write of the canvas rows the batch covers ((ncls + 1) f32 per pixel)
+    work = float(logits.numel()) * 4 + float(max(0, min(yhi, y0 + Hb) - max(ylo, y0))) * W * (ncls + 1) * 8
+    _call("ig_window_blend_accumulate", work, _p(_f32(logits)), _p(tops), _p(lefts), tops.numel(), lefts.numel(), int(w0), n,
+          _p(_f32(wvec)), _p(_f32(acc)), _p(_f32(wsum)), ncls, crop, int(H), W, int(y0), Hb, int(ylo), int(yhi), _stream())
+
+
+def window_blend_finalize(acc, wsum, tile: Optional[torch.Tensor] = None, no_data_value: Optional[float] = None, fill: int = -1,
+                          probabilities: bool = False):
+    """acc (ncls, H, W) / wsum (H, W) -> (classmap (H, W) int8, prob (ncls, H, W) f32 or None); ncls == 1 (regression): (None, the
+    blended value (1, H, W)).  Pixels with wsum == 0 or any band of ``tile`` (T*C, H, W) int16|f32 == ``no_data_value``: fill / NaN."""
+    ncls, H, W = acc.shape
+    assert wsum.shape == (H, W)
+    classmap = torch.empty((H, W), dtype=torch.int8, device=acc.device) if ncls > 1 else None
+    prob = torch.empty((ncls, H, W), dtype=torch.float32, device=acc.device) if (probabilities or ncls == 1) else None
+    check = tile is not None and no_data_value is not None
+    if check:
+        assert tile.shape[1:] == (H, W)
+    dt = {torch.int16: 0, torch.float32: 1}[tile.dtype] if check else 0
+    work = float(H) * W * ((ncls + 1) * 4 + (tile.shape[0] * tile.element_size() if check else 0) + (1 if classmap is not None else 0)
+                           + (ncls * 4 if prob is not None else 0))
+    _call("ig_window_blend_finalize", work, _p(_f32(acc)), _p(_f32(wsum)), _p(tile.contiguous()) if check else None, dt,
+          tile.shape[0] if check else 0, float(no_data_value) if check else 0.0, int(check), _p(classmap), _p(prob), ncls, H * W, int(fill),
+          _stream())
+    return classmap, prob
+
+
 def confusion_update(y_true, y_pred, confusion, k: int, ignore_index: Optional[int]) -> None:
     assert y_true.dtype == torch.int64 and y_pred.dtype == torch.int64 and confusion.dtype == torch.int64
     _lib.call("ig_confusion_update", _p(y_true), _p(y_pred), _p(confusion), y_true.numel(), k,

@@ -2,7 +2,8 @@
 
     python -m instageo_amd.run [--config-name sen1floods11] [--config-path DIR] key=value ...
 
-Modes ``stats | train | eval | chip_inference`` and every config key are those of the reference.  Hydra,
+Modes ``stats | train | eval | chip_inference`` and every config key are those of the reference; ``tile_inference``
+(whole GeoTIFF tiles -> maps, ``test.blend`` / ``cover_edges`` / ``sigma_scale`` / ``save_probabilities``) is this project's.  Hydra,
 Lightning and Neptune are replaced by :mod:`instageo_amd.config` and the explicit loop below, which logs the
 same metric names and writes ``instageo_best_checkpoint.ckpt`` (``{"state_dict": ...}``) on the best
 ``val_IoU`` (pipeline_utils.py:347-355).  Data: ``*_filepath`` may be ``synthetic:<n>`` (on-device HLS-shaped
@@ -190,6 +191,33 @@ def evaluate(cfg: Dict[str, Any], model, rank: int, world: int) -> Dict[str, flo
     return {k: float(v) for k, v in model.logged.items() if k.startswith("test_") and not isinstance(v, (list, tuple))}
 
 
+def tile_paths(cfg: Dict[str, Any]) -> List[str]:
+    """mode=tile_inference input: ``test_filepath`` is one GeoTIFF tile or a CSV whose ``Input`` column lists tiles (paths relative
+    to ``root_dir`` unless absolute)."""
+    spec = str(cfg["test_filepath"])
+    root = cfg.get("root_dir")
+    rel = lambda p: p if os.path.isabs(p) or root in (None, "None") else os.path.join(root, p)  # noqa: E731
+    path = rel(spec)
+    if not path.lower().endswith(".csv"):
+        return [path]
+    import pandas as pd
+
+    return [rel(str(p)) for p in pd.read_csv(path)["Input"]]
+
+
+def run_tile_inference(cfg: Dict[str, Any], model, tile: str, output_dir: str, dev: str) -> Optional[str]:
+    """One tile -> ``prediction_*.tif`` (+ ``probability_*.tif``) with the ``test.*`` window keys; windows shard over ranks."""
+    from .infer_utils import tile_inference
+
+    d, t = cfg["dataloader"], cfg["test"]
+    mult = d.get("constant_multiplier", 1.0)
+    mult = None if mult in (None, 1, 1.0) else float(mult)
+    return tile_inference(tile, output_dir, model, d["mean"], d["std"], d["temporal_dim"], t["crop_size"], t["stride"],
+                          cfg["train"]["batch_size"], mult, d.get("no_data_value", -9999), device=dev, blend=t.get("blend", "nearest"),
+                          cover_edges=bool(t.get("cover_edges", False)), sigma_scale=float(t.get("sigma_scale", 0.125)),
+                          save_probabilities=bool(t.get("save_probabilities", False)))
+
+
 def main(argv: Optional[List[str]] = None) -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--config-name", default="config")
@@ -251,6 +279,12 @@ def main(argv: Optional[List[str]] = None) -> int:
         info = chip_inference(loader, output_dir, model, device="gpu")
         if rank == 0:
             print(f"Carbon tracking information: {info}")
+    elif cfg["mode"] == "tile_inference":
+        check_required_flags(["root_dir", "test_filepath", "checkpoint_path"], cfg)
+        for tile in tile_paths(cfg):
+            out = run_tile_inference(cfg, model, tile, os.path.join(cfg["root_dir"], "predictions"), dev)
+            if rank == 0:
+                print(json.dumps({"tile": tile, "prediction": out}))
     else:
         raise ValueError(f"unknown mode {cfg['mode']!r}")
     if D.dp_active():
