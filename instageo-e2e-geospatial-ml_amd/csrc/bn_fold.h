@@ -6,8 +6,10 @@
 namespace {
 // deterministic mode: sums[i] = sum over the workgroups of the reduce pass of part[wg][i], in a fixed order (strided subsets
 // per column in wg order, folded in subset order) -- the float atomics of the default mode arrive in any order, and a fixed-point
-// integer sum has no range for both the forward moments (up to 1e10) and the backward ones (down to 1e-9)
-__global__ __launch_bounds__(1024) void bn_part_fold_kernel(const float* __restrict__ part, double* __restrict__ sums, int nwg, int n) {
+// integer sum has no range for both the forward moments (up to 1e10) and the backward ones (down to 1e-9).  T = double: the forward
+// statistics, whose partials are raw sums formed in fp64 from centred fp32 ones (ig_bn_relu_fwd, the fused convolution epilogues).
+template <typename T>
+__global__ __launch_bounds__(1024) void bn_part_fold_kernel(const T* __restrict__ part, double* __restrict__ sums, int nwg, int n) {
     // 64 columns x 16 row subsets per workgroup; every thread keeps four independent partial sums so that its loads overlap
     __shared__ double sub[16][64];
     const int c = blockIdx.x * 64 + (threadIdx.x & 63), g = threadIdx.x >> 6;

@@ -258,6 +258,9 @@ __global__ __launch_bounds__(TPB) void layernorm_fwd_kernel(const float* __restr
     if (row >= M) return;
     const int nv = D / 4;  // float4 chunks per row
     const float* xr = x + (size_t)row * D;
+    // the sum is centred on the row's first element: a row's DC offset does not round its mean (a constant row gets its value exactly,
+    // where (D x)/D misses it by an ulp that rstd = eps^-1/2 turns into an output error of 300 ulps)
+    const float x0 = xr[0];
     float4 v[MAXV];
     float s = 0.f;
 #pragma unroll
@@ -265,10 +268,10 @@ __global__ __launch_bounds__(TPB) void layernorm_fwd_kernel(const float* __restr
         int c = lane + i * 64;
         if (c < nv) {
             v[i] = *reinterpret_cast<const float4*>(xr + c * 4);
-            s += v[i].x + v[i].y + v[i].z + v[i].w;
+            s += ((v[i].x - x0) + (v[i].y - x0)) + ((v[i].z - x0) + (v[i].w - x0));
         }
     }
-    float mu = wave_sum(s) / D;
+    float mu = x0 + wave_sum(s) / D;
     float q = 0.f;
 #pragma unroll
     for (int i = 0; i < MAXV; ++i) {
@@ -678,9 +681,10 @@ __global__ __launch_bounds__(TPB) void patch_grad_prep_kernel(const float* __res
 // K13: BatchNorm2d (+ReLU) on NHWC bf16/split tensors [M][C]   (model.py:376-377; eps 1e-5, momentum 0.1)
 // ----------------------------------------------------------------------------------------------
 // pass 1: per-channel sum / sum of squares: fp32 partials per thread, LDS reduction per block, one fp64
-// atomic per (block, channel, statistic)
+// atomic per (block, channel, statistic).  The fp32 partials are centred on a pivot, the block's first row, and turned back
+// into the raw sums in fp64: raw fp32 sums of squares lose (mean / std)^2 ulps of the variance to E[x^2] - E[x]^2.
 __global__ __launch_bounds__(TPB) void bn_stats_kernel(const bf16_t* __restrict__ hi, const bf16_t* __restrict__ lo,
-                                                       double* __restrict__ sums, long M, int C, int rows_per_block, float* __restrict__ part) {
+                                                       double* __restrict__ sums, long M, int C, int rows_per_block, double* __restrict__ part) {
     extern __shared__ float red[];  // [2C]
     const int units = C / 8;
     const int tu = min(units, TPB), nslice = TPB / tu;
@@ -694,7 +698,8 @@ __global__ __launch_bounds__(TPB) void bn_stats_kernel(const bf16_t* __restrict_
     }
     if (sl < nslice) {
         for (int ub = u; ub < units; ub += tu) {
-            float s[8] = {0, 0, 0, 0, 0, 0, 0, 0}, q[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+            float s[8] = {0, 0, 0, 0, 0, 0, 0, 0}, q[8] = {0, 0, 0, 0, 0, 0, 0, 0}, pv[8];
+            load8_split(hi, lo, (size_t)r0 * C + ub * 8, pv);
             long r = r0 + sl;
             for (; r + 3L * nslice < r1; r += 4L * nslice) {  // four rows in flight per thread
                 float f[4][8];
@@ -703,13 +708,19 @@ __global__ __launch_bounds__(TPB) void bn_stats_kernel(const bf16_t* __restrict_
 #pragma unroll
                 for (int k = 0; k < 4; ++k)
 #pragma unroll
-                    for (int j = 0; j < 8; ++j) s[j] += f[k][j], q[j] = fmaf(f[k][j], f[k][j], q[j]);
+                    for (int j = 0; j < 8; ++j) {
+                        const float d = f[k][j] - pv[j];
+                        s[j] += d, q[j] = fmaf(d, d, q[j]);
+                    }
             }
             for (; r < r1; r += nslice) {
                 float f[8];
                 load8_split(hi, lo, (size_t)r * C + ub * 8, f);
 #pragma unroll
-                for (int j = 0; j < 8; ++j) s[j] += f[j], q[j] = fmaf(f[j], f[j], q[j]);
+                for (int j = 0; j < 8; ++j) {
+                    const float d = f[j] - pv[j];
+                    s[j] += d, q[j] = fmaf(d, d, q[j]);
+                }
             }
             if (direct) {  // slab per row slice: plain stores (LDS float atomics retire a few lanes per cycle)
 #pragma unroll
@@ -724,12 +735,20 @@ __global__ __launch_bounds__(TPB) void bn_stats_kernel(const bf16_t* __restrict_
         }
     }
     __syncthreads();
-    for (int i = threadIdx.x; i < 2 * C; i += TPB) {
-        float t = red[i];
+    for (int c = threadIdx.x; c < C; c += TPB) {
+        float ts = red[c], tq = red[C + c];
         if (direct)
-            for (int q2 = 1; q2 < nslice; ++q2) t += red[(size_t)q2 * 2 * C + i];
-        if (part) part[(size_t)blockIdx.x * 2 * C + i] = t;  // deterministic mode: bn_part_fold_kernel sums the workgroups in index order
-        else atomicAdd(sums + i, (double)t);
+            for (int q2 = 1; q2 < nslice; ++q2) ts += red[(size_t)q2 * 2 * C + c], tq += red[(size_t)q2 * 2 * C + C + c];
+        // un-shift in fp64: sum x = ts + n p, sum x^2 = tq + 2 p ts + n p^2
+        const double p = (double)(bf2f(hi[(size_t)r0 * C + c]) + (lo ? bf2f(lo[(size_t)r0 * C + c]) : 0.f)), n = (double)(r1 - r0);
+        const double S = (double)ts + n * p, Q = (double)tq + p * (2.0 * (double)ts + n * p);
+        if (part) {  // deterministic mode: bn_part_fold_kernel sums the workgroups in index order
+            part[(size_t)blockIdx.x * 2 * C + c] = S;
+            part[(size_t)blockIdx.x * 2 * C + C + c] = Q;
+        } else {
+            atomicAdd(sums + c, S);
+            atomicAdd(sums + C + c, Q);
+        }
     }
 }
 // finalize: train -> batch statistics (+ running update), eval -> running statistics
@@ -1290,16 +1309,16 @@ int ig_bn_relu_fwd(const void* x_hi, const void* x_lo, const float* gamma, const
     if (M == 0) return IG_OK;
     if (training == 1) {  // (training == 2: a producer has already left the statistics in sums -- ig_conv3x3_fwd_stats)
         const int rpb = bn_reduce_rows(M), nwg = ig_cdiv(M, rpb);
-        float* part = nullptr;
+        double* part = nullptr;
         if (ig_deterministic()) {
-            part = (float*)ig_scratch(0, (size_t)nwg * 2 * C * sizeof(float), ST(stream));
+            part = (double*)ig_scratch(0, (size_t)nwg * 2 * C * sizeof(double), ST(stream));
             IG_REQUIRE(part, "ig_bn_relu_fwd: scratch allocation failed");
         } else {
             (void)hipMemsetAsync(sums, 0, 2 * (size_t)C * sizeof(double), ST(stream));
         }
         hipLaunchKernelGGL(bn_stats_kernel, dim3(nwg), dim3(TPB), bn_red_bytes(C), ST(stream), (const bf16_t*)x_hi, (const bf16_t*)x_lo,
                            sums, M, C, rpb, part);
-        if (part) hipLaunchKernelGGL(bn_part_fold_kernel, dim3(ig_cdiv(2 * C, 64)), dim3(1024), 0, ST(stream), part, sums, nwg, 2 * C);
+        if (part) hipLaunchKernelGGL((bn_part_fold_kernel<double>), dim3(ig_cdiv(2 * C, 64)), dim3(1024), 0, ST(stream), part, sums, nwg, 2 * C);
     }
     hipLaunchKernelGGL(bn_finalize_kernel, dim3(ig_cdiv(C, TPB)), dim3(TPB), 0, ST(stream), sums, gamma, beta, running_mean,
                        running_var, scale, shift, mean, rstd, (double)M, C, eps, momentum, training, update_running);
@@ -1338,7 +1357,7 @@ int ig_bn_relu_bwd(const void* x_hi, const void* x_lo, const void* dy_hi, const 
     }
     hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(nwg), dim3(TPB), bn_red_bytes(C), ST(stream), (const bf16_t*)x_hi, (const bf16_t*)x_lo,
                        (const bf16_t*)dy_hi, (const bf16_t*)dy_lo, scale, shift, mean, rstd, sums, M, C, rpb, part);
-    if (part) hipLaunchKernelGGL(bn_part_fold_kernel, dim3(ig_cdiv(2 * C, 64)), dim3(1024), 0, ST(stream), part, sums, nwg, 2 * C);
+    if (part) hipLaunchKernelGGL((bn_part_fold_kernel<float>), dim3(ig_cdiv(2 * C, 64)), dim3(1024), 0, ST(stream), part, sums, nwg, 2 * C);
     const int arpb = bn_apply_rows(C);
     hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(ig_cdiv(M, arpb)), dim3(TPB), 0, ST(stream), (const bf16_t*)x_hi,
                        (const bf16_t*)x_lo, (const bf16_t*)dy_hi, (const bf16_t*)dy_lo, scale, shift, mean, rstd, sums, (bf16_t*)dx_hi,

@@ -542,20 +542,23 @@ __global__ __launch_bounds__(TPB) void ce_loss_kernel(const float* __restrict__ 
 #pragma unroll
             for (int n = 0; n < NCB; ++n)
                 if (n < ncls && z[n][e] > mx) mx = z[n][e], am = n;
-            float se = 0.f;
+            const long y = (long)lab[e];
+            float se = 0.f, zy = 0.f;
 #pragma unroll
             for (int n = 0; n < NCB; ++n)
-                if (n < ncls) se += __expf(z[n][e] - mx);
-            const float lse = mx + __logf(se);
-            const long y = (long)lab[e];
+                if (n < ncls) {
+                    if (n == (int)y) zy = z[n][e];
+                    z[n][e] = expf(z[n][e] - mx);  // z now holds exp(z - max)
+                    se += z[n][e];
+                }
+            // loss = (max - z_y) + log(se), probabilities exp(z - max) / se, as torch's log_softmax: max + log(se) would round the small
+            // loss of a confident pixel away at ulp(|max|).  expf / logf, not __expf / __logf: those lose ~|x| ulps of the argument and
+            // ~2^-22 absolute at se ~ 1, the whole loss of a confident pixel.
+            const float lse0 = logf(se), rse = 1.f / se;
             const bool valid = (y != ignore_index) && y >= 0 && y < ncls;
             const float wy = valid ? (cw ? cw[y] : 1.f) : 0.f;
             if (valid) {
-                float zy = 0.f;
-#pragma unroll
-                for (int n = 0; n < NCB; ++n)
-                    if (n == (int)y) zy = z[n][e];
-                my_loss += wy * (lse - zy);
+                my_loss += wy * ((mx - zy) + lse0);
                 my_cnt += 1.f;
                 if constexpr (NCB == 2) {
                     const int ci = (int)y * ncls + am;
@@ -567,7 +570,7 @@ __global__ __launch_bounds__(TPB) void ce_loss_kernel(const float* __restrict__ 
             }
 #pragma unroll
             for (int n = 0; n < NCB; ++n)
-                if (n < ncls) z[n][e] = wy * (__expf(z[n][e] - lse) - (n == (int)y ? 1.f : 0.f));  // z now holds dlogits
+                if (n < ncls) z[n][e] = wy * (z[n][e] * rse - (n == (int)y ? 1.f : 0.f));  // z now holds dlogits
             amv[e] = am;
         }
         if (dlogits) {
@@ -672,16 +675,20 @@ __global__ __launch_bounds__(TPB) void kd_loss_kernel(const float* __restrict__ 
         float ses = 0.f, set = 0.f;
 #pragma unroll
         for (int n = 0; n < MAXC; ++n)
-            if (n < ncls) ses += __expf(zs[n] - ms), set += __expf(zt[n] - mt);
-        const float lses = ms + __logf(ses), lset = mt + __logf(set);
+            if (n < ncls) {
+                zs[n] -= ms, zt[n] -= mt;  // in place: the exponentials are recomputed below rather than held (register budget)
+                ses += expf(zs[n]), set += expf(zt[n]);
+            }
+        // log-softmax as (z - max) - log(sum), with expf / logf: see ce_loss_kernel
+        const float lses = logf(ses), lset = logf(set), rses = 1.f / ses, rset = 1.f / set;
         float kl = 0.f;
 #pragma unroll
         for (int n = 0; n < MAXC; ++n)
             if (n < ncls) {
                 const float lt = zt[n] - lset, ls = zs[n] - lses;
-                const float t = __expf(lt);
+                const float t = expf(zt[n]) * rset;
                 kl += t * (lt - ls);
-                if (dlogits) dlogits[(b * ncls + n) * HW + pix] += __expf(ls) - t;
+                if (dlogits) dlogits[(b * ncls + n) * HW + pix] += expf(zs[n]) * rses - t;
             }
         my += (double)kl;
     }
@@ -1024,7 +1031,7 @@ int ig_classifier_bn_bwd(const float* dlogits, const void* x_hi, const void* x_l
                              drop_seed_dev, drop_p, stream);
     if (rc != IG_OK) return rc;
     if (bn.part)
-        hipLaunchKernelGGL(bn_part_fold_kernel, dim3(ig_cdiv(2 * C, 64)), dim3(1024), 0, (hipStream_t)stream, bn.part, sums, nwg, 2 * C);
+        hipLaunchKernelGGL((bn_part_fold_kernel<float>), dim3(ig_cdiv(2 * C, 64)), dim3(1024), 0, (hipStream_t)stream, bn.part, sums, nwg, 2 * C);
     return classifier_bwd_impl(2, bn, nullptr, dlogits, x_hi, x_lo, w, dx_hi, dx_lo, nullptr, nullptr, count, B, HW, C, ncls, drop_seed,
                                drop_seed_dev, drop_p, stream);
 }
