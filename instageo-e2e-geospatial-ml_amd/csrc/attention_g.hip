@@ -557,7 +557,7 @@ __global__ __launch_bounds__(AGL_WPB * 64) void attng_bwd_dq_lds_kernel(const bf
     }
 }
 
-constexpr bool agl_enabled() { return true; }  // plain bf16: the LDS-staged kernels (round 4: backward 587 -> 252 us); split mode: the register / L2 kernels above
+// plain bf16: the LDS-staged kernels (round 4: backward 587 -> 252 us); split mode: the register / L2 kernels above
 template <class K>
 inline bool agl_attr(K kern, int bytes) {
     return hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess;
@@ -567,7 +567,7 @@ template <int HD>
 int attng_fwd(const void* qkv_hi, const void* qkv_lo, void* out_hi, void* out_lo, float* lse, int B, int N, int H, hipStream_t st) {
     const dim3 grid(ig_cdiv(ig_cdiv(N, 16), AG_WPB), H, B), block(AG_WPB * 64);
     const float scale = 1.0f / sqrtf((float)HD);
-    if (!qkv_lo && agl_enabled()) {
+    if (!qkv_lo) {
         constexpr int smem = AGL_CH * (2 * HD + 16) + AGL_CH * 2 * HD;
         static bool attr = false;
         if (!attr) attr = agl_attr(attng_fwd_lds_kernel<HD>, smem);
@@ -594,7 +594,7 @@ int attng_bwd(const void* qkv_hi, const void* qkv_lo, const void* out_hi, const 
     const dim3 grid(ig_cdiv(ig_cdiv(N, 16), AG_WPB), H, B), block(AG_WPB * 64);
     const float scale = 1.0f / sqrtf((float)HD);
     const long total = (long)B * N * H;
-    if (!qkv_lo && agl_enabled()) {
+    if (!qkv_lo) {
         constexpr int smem_kv = 2 * AGL_CH * (2 * HD + 16) + 2 * AGL_CH * 4, smem_q = 2 * AGL_CH * (2 * HD + 16);
         static bool attr = false;
         if (!attr) attr = agl_attr(attng_bwd_dkv_lds_kernel<HD>, smem_kv) && agl_attr(attng_bwd_dq_lds_kernel<HD>, smem_q);

@@ -1,7 +1,11 @@
-// Generic bf16 MFMA "gather-GEMM" for gfx950 and every matmul-shaped op of the Prithvi path.
+// Generic bf16 MFMA "gather-GEMM" for gfx950 and the C-ABI entry points of every linear and convolution of the Prithvi path.
 //
 //   C[m][n] = sum_seg sum_k A_seg(m,k) * B_seg(n,k)           (fp32 accumulate)
 //
+// Two engines run what the specialised kernels (gemm4 / gemm8 / gemm8w / conv8 / conv_direct) decline:
+//   v1 gemm_kernel   128x128-class register-staged tiles: every gathered (convolution) operand, small plain-matrix problems;
+//   v2 gemm2_kernel  256x128 tile, LDS-DMA ring: plain matrices with enough tiles to fill the chip, and the fused column sums.
+// v1 in detail:
 // * 128x128 output tile, BK=64, 256 threads = 4 waves (2x2), each wave 64x64 = 4x4 MFMA 16x16x32 bf16.
 // * Operands are fetched in 16-byte units (8 bf16) through *loader functors* that return a global
 //   pointer or NULL (zero fill): plain row-major matrices, NHWC convolution gathers (3x3 conv, stride-2
@@ -67,8 +71,10 @@ __device__ __forceinline__ bf16x8_t read_frag(const char* tile, int row0, int s,
     }
 }
 
-// 64-byte-row K-contiguous image (BK = 32): physical chunk of logical chunk c in row r (conflict-free for ds_read_b128)
-__device__ __forceinline__ int kc32_off(int r, int c) { return r * 64 + ((c ^ ((0x1230 >> (4 * ((r >> 2) & 3))) & 3)) << 4); }
+// 64-byte-row K-contiguous image (BK = 32): physical chunk of logical chunk c in row r, an involution in c
+// (f = {0,3,2,1}: conflict-free for ds_read_b128), and its byte offset
+__device__ __forceinline__ int kc32_swz(int r, int c) { return c ^ ((0x1230 >> (4 * ((r >> 2) & 3))) & 3); }
+__device__ __forceinline__ int kc32_off(int r, int c) { return r * 64 + (kc32_swz(r, c) << 4); }
 
 // v1: 4 waves laid out WM x WN (2 x 2, 4 x 1 or 1 x 4), each owning MT x NT MFMA tiles of 16 x 16 => block tile
 // (16 WM MT) x (16 WN NT).  The decode head's channel counts are multiples of 48 (48, 96, 192, 384): 48-, 96- and
@@ -280,20 +286,19 @@ __global__ __launch_bounds__(NTHR) void gemm_kernel(AL al, BL bl, EP ep, int M, 
 constexpr int BM2 = 256, NTHR2 = 512;
 typedef __attribute__((address_space(3))) char* lds_char_ptr;
 
-// Geometry of one ring stage for K-step BKT (64: 48 KiB/stage, 1 workgroup/CU -- used by the LDS-staged wgrad epilogue;
-// 32: 24 KiB/stage, 72 KiB ring => 2 workgroups (16 waves) per CU so one workgroup's barrier / DMA waits are covered by
-// the other's MFMAs)
-template <int BKT>
+// Geometry of one ring stage at K-step 32: 24 KiB/stage, 72 KiB ring => 2 workgroups (16 waves) per CU so one workgroup's
+// barrier / DMA waits are covered by the other's MFMAs
 struct G2 {
-    static constexpr int UPR = BKT / 8;                // 16-byte units per K-contiguous row
+    static constexpr int BK = 32;
+    static constexpr int UPR = BK / 8;                 // 16-byte units per K-contiguous row
     static constexpr int RPI = 64 / UPR;               // rows per 1-KiB wave-instruction (K-contiguous image)
-    static constexpr int A_BYTES = BM2 * BKT * 2;
-    static constexpr int B_BYTES = BN * BKT * 2;
+    static constexpr int A_BYTES = BM2 * BK * 2;
+    static constexpr int B_BYTES = BN * BK * 2;
     static constexpr int STAGE = A_BYTES + B_BYTES;
     static constexpr int NA = A_BYTES / 1024, NB = B_BYTES / 1024;  // wave-instructions per stage
     static constexpr int PER_WAVE = (NA + NB) / 8;
     static constexpr int SMEM = 3 * STAGE;
-    static constexpr int TRH = BKT * 256;              // bytes of one 128-column half of a TR image
+    static constexpr int TRH = BK * 256;               // bytes of one 128-column half of a TR image
 };
 
 __device__ __forceinline__ void glds16(const void* gsrc, unsigned lds_dst) {
@@ -305,21 +310,10 @@ __device__ __forceinline__ void glds16(const void* gsrc, unsigned lds_dst) {
                  : "memory");
 }
 __device__ __forceinline__ int tr_key(int k) { return (k & 3) | (((k >> 3) & 1) << 2); }
-// K-contiguous image swizzle: physical 16-byte chunk of logical chunk c in row r (an involution in c)
-template <int BKT>
-__device__ __forceinline__ int kc_swz(int r, int c) {
-    if constexpr (BKT == 64) return c ^ (r & 7);
-    else return c ^ ((0x1230 >> (4 * ((r >> 2) & 3))) & 3);  // f = {0,3,2,1}: conflict-free for ds_read_b128 on 64-byte rows
-}
-template <int BKT, bool TR>
-__device__ __forceinline__ bf16x8_t read_frag2(const char* tile, int row0, int s, int lane) {
-    if constexpr (!TR) {
-        const int r = row0 + (lane & 15);
-        const int c = s * 4 + (lane >> 4);
-        return *reinterpret_cast<const bf16x8_t*>(tile + r * (BKT * 2) + (kc_swz<BKT>(r, c) << 4));
-    } else {
-        return read_frag<true>(tile, row0, s, lane);
-    }
+template <bool TR>
+__device__ __forceinline__ bf16x8_t read_frag2(const char* tile, int row0, int lane) {
+    if constexpr (!TR) return *reinterpret_cast<const bf16x8_t*>(tile + kc32_off(row0 + (lane & 15), lane >> 4));
+    else return read_frag<true>(tile, row0, 0, lane);
 }
 
 // DUALK = 2 (staged-atomic weight gradients only): ONE 16-wave workgroup per CU instead of two 8-wave ones.  Its two wave
@@ -327,11 +321,12 @@ __device__ __forceinline__ bf16x8_t read_frag2(const char* tile, int row0, int s
 // barriers, so both execute the same number of K-steps; the shorter half idles through its last one) and fold their two fp32
 // tiles through LDS before the atomic pass: the split-K atomic volume (#workgroups x tile) is halved -- with the adds
 // switched off the weight gradient ran at 890-990 TFLOP/s against 675-785.
-template <class AL, class BL, class EP, bool A_TR, bool B_TR, int NSEG, int BKT, int DUALK = 1>
-__global__ __launch_bounds__(NTHR2 * DUALK, (BKT == 32 ? 4 : 2)) void gemm2_kernel(AL al, BL bl, EP ep, int M, int N, int K, int tiles_n,
-                                                                               int ntiles, int kchunk, const bf16_t* zero_page) {
-    using G = G2<BKT>;
-    static_assert(DUALK == 1 || (DUALK == 2 && EP::kStagedAtomic && BKT == 32), "the dual-group form exists for the staged-atomic epilogue");
+template <class AL, class BL, class EP, bool A_TR, bool B_TR, int NSEG, int DUALK = 1>
+__global__ __launch_bounds__(NTHR2 * DUALK, 4) void gemm2_kernel(AL al, BL bl, EP ep, int M, int N, int K, int tiles_n, int ntiles, int kchunk,
+                                                                 const bf16_t* zero_page) {
+    using G = G2;
+    static_assert(AL::kLinearK && BL::kLinearK, "v2 reads plain matrices only");
+    static_assert(DUALK == 1 || (DUALK == 2 && EP::kStagedAtomic), "the dual-group form exists for the staged-atomic epilogue");
     extern __shared__ __attribute__((aligned(16))) char smem_all[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave16 = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -370,7 +365,7 @@ __global__ __launch_bounds__(NTHR2 * DUALK, (BKT == 32 ? 4 : 2)) void gemm2_kern
     bl.init(blockIdx.z);
     ep.init(blockIdx.z);
     if (al.kdim() >= 0) K = al.kdim();
-    const int nk_all = (K + BKT - 1) / BKT;
+    const int nk_all = (K + G::BK - 1) / G::BK;
     int kt0 = ysplit * kchunk;
     int nk = min(kchunk, nk_all - kt0);
     if (nk <= 0 || my_tiles <= 0) return;
@@ -395,30 +390,29 @@ __global__ __launch_bounds__(NTHR2 * DUALK, (BKT == 32 ? 4 : 2)) void gemm2_kern
     // one stage = NA + NB wave-instructions ("pieces") of 1 KiB (ids 0..NA-1 -> A, then B); wave w issues ids i*8 + w.
     // The source pointer of a piece advances by a constant per K-step, so it is decoded once per (tile, segment) and
     // then stepped with one 64-bit add: recomputing row*ld + bounds for every piece and K-step cost more issue cycles
-    // than the 16 MFMAs of the step (MI355X_MICROARCH.md, 'vector-instruction ISSUE cost').  Needs K % BKT == 0 and a
-    // loader whose address is linear in k (kLinearK); otherwise the generic per-step decode below is used.
+    // than the 16 MFMAs of the step (MI355X_MICROARCH.md, 'vector-instruction ISSUE cost').  A K tail (K % 32 != 0) takes the
+    // generic per-step decode below for that step only.
 #define GEMM2_PIECE_PTR(SEG, KT, BM_, BN_, ID, P, OK)                                                       \
     {                                                                                                       \
         if ((ID) < G::NA) {                                                                                 \
             if constexpr (!A_TR) {                                                                          \
                 const int row = (ID)*G::RPI + lane / G::UPR;                                                \
-                P = al.ptr(SEG, (BM_)*BM2 + row, (KT)*G::UPR + kc_swz<BKT>(row, lane % G::UPR), OK);        \
+                P = al.ptr(SEG, (BM_)*BM2 + row, (KT)*G::UPR + kc32_swz(row, lane % G::UPR), OK);           \
             } else {                                                                                        \
-                const int k = ((ID) % (BKT / 4)) * 4 + (lane >> 4);                                         \
-                P = al.ptr(SEG, (KT)*BKT + k, (BM_)*32 + ((ID) / (BKT / 4)) * 16 + ((lane & 15) ^ (tr_key(k) << 1)), OK); \
+                const int k = ((ID) % (G::BK / 4)) * 4 + (lane >> 4);                                       \
+                P = al.ptr(SEG, (KT)*G::BK + k, (BM_)*32 + ((ID) / (G::BK / 4)) * 16 + ((lane & 15) ^ (tr_key(k) << 1)), OK); \
             }                                                                                               \
         } else {                                                                                            \
             const int id2 = (ID)-G::NA;                                                                     \
             if constexpr (!B_TR) {                                                                          \
                 const int row = id2 * G::RPI + lane / G::UPR;                                               \
-                P = bl.ptr(SEG, (BN_)*BN + row, (KT)*G::UPR + kc_swz<BKT>(row, lane % G::UPR), OK);         \
+                P = bl.ptr(SEG, (BN_)*BN + row, (KT)*G::UPR + kc32_swz(row, lane % G::UPR), OK);            \
             } else {                                                                                        \
                 const int k = id2 * 4 + (lane >> 4);                                                        \
-                P = bl.ptr(SEG, (KT)*BKT + k, (BN_)*16 + ((lane & 15) ^ (tr_key(k) << 1)), OK);             \
+                P = bl.ptr(SEG, (KT)*G::BK + k, (BN_)*16 + ((lane & 15) ^ (tr_key(k) << 1)), OK);           \
             }                                                                                               \
         }                                                                                                   \
     }
-    constexpr bool kFast = AL::kLinearK && BL::kLinearK;  // a K tail (K % BKT != 0) takes the generic decode for that step only
     const char* pp[G::PER_WAVE];   // fast path: current source of this wave's pieces
     long pstep[G::PER_WAVE];       // bytes per K-step (0 for out-of-range rows, which read the zero page)
 #define GEMM2_SETUP(IT, BM_, BN_)                                                                           \
@@ -433,7 +427,7 @@ __global__ __launch_bounds__(NTHR2 * DUALK, (BKT == 32 ? 4 : 2)) void gemm2_kern
             pp[i] = ok ? (const char*)p : (const char*)zero_page;                                           \
             const bool tr_ = id < G::NA ? A_TR : B_TR;                                                      \
             const long ld_ = id < G::NA ? al.kstride() : bl.kstride();                                      \
-            pstep[i] = !ok ? 0L : tr_ ? (long)BKT * ld_ * 2 : (long)BKT * 2;                                \
+            pstep[i] = !ok ? 0L : tr_ ? (long)G::BK * ld_ * 2 : (long)G::BK * 2;                            \
         }                                                                                                   \
     }
     // Issue of one K-step's pieces: BEGIN decodes the step (and re-seeds the piece pointers at a tile/segment start),
@@ -445,7 +439,7 @@ __global__ __launch_bounds__(NTHR2 * DUALK, (BKT == 32 ? 4 : 2)) void gemm2_kern
     const int seg_ = (NSEG == 1) ? 0 : (IT) / nk;                                                           \
     const int kt_ = kt0 + (IT)-seg_ * nk;                                                                   \
     const int ibm_ = (BM_), ibn_ = (BN_);                                                                   \
-    const bool fast_ = kFast && (kt_ + 1) * BKT <= K;                                                       \
+    const bool fast_ = (kt_ + 1) * G::BK <= K;                                                              \
     if (fast_ && (IT) == seg_ * nk) GEMM2_SETUP(IT, BM_, BN_);
 #define GEMM2_ISSUE_ONE(I)                                                                                  \
     {                                                                                                       \
@@ -492,9 +486,9 @@ __global__ __launch_bounds__(NTHR2 * DUALK, (BKT == 32 ? 4 : 2)) void gemm2_kern
         // K-step g landed for THIS wave once at most the DMAs of step g+1 are outstanding (vmcnt also counts the
         // epilogue's stores, which only makes the wait at a tile boundary conservative); the barrier then covers
         // the other waves' pieces (RAW) and everybody's reads of the slot that is refilled next (WAR)
+        static_assert(G::PER_WAVE == 3, "the counted wait below retires all but one K-step of pieces");
         if (g + 1 < G_) {
-            if constexpr (G::PER_WAVE == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
+            asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
         } else {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
@@ -516,26 +510,23 @@ __global__ __launch_bounds__(NTHR2 * DUALK, (BKT == 32 ? 4 : 2)) void gemm2_kern
         }
         const char* ta = smem + slot * G::STAGE;
         const char* tb = ta + G::A_BYTES;
+        bf16x8_t af[4], bf[4];
 #pragma unroll
-        for (int s = 0; s < BKT / 32; ++s) {
-            bf16x8_t af[4], bf[4];
+        for (int t = 0; t < 4; ++t) {
+            if constexpr (!A_TR) af[t] = read_frag2<false>(ta, wm * 64 + t * 16, lane);
+            else af[t] = read_frag2<true>(ta + (wm >> 1) * G::TRH, (wm & 1) * 64 + t * 16, lane);
+        }
 #pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                if constexpr (!A_TR) af[t] = read_frag2<BKT, false>(ta, wm * 64 + t * 16, s, lane);
-                else af[t] = read_frag2<BKT, true>(ta + (wm >> 1) * G::TRH, (wm & 1) * 64 + t * 16, s, lane);
-            }
+        for (int t = 0; t < 4; ++t) bf[t] = read_frag2<B_TR>(tb, wn * 64 + t * 16, lane);
 #pragma unroll
-            for (int t = 0; t < 4; ++t) bf[t] = read_frag2<BKT, B_TR>(tb, wn * 64 + t * 16, s, lane);
+        for (int tn = 0; tn < 4; ++tn) {
 #pragma unroll
-            for (int tn = 0; tn < 4; ++tn) {
-#pragma unroll
-                for (int tm = 0; tm < 4; ++tm)
-                    acc[tn][tm] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[tn], af[tm], acc[tn][tm], 0, 0, 0);
-                if (kSpread && s * 4 + tn < G::PER_WAVE) {
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (do_issue) GEMM2_ISSUE_ONE(s * 4 + tn)
-                    __builtin_amdgcn_sched_barrier(0);
-                }
+            for (int tm = 0; tm < 4; ++tm)
+                acc[tn][tm] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[tn], af[tm], acc[tn][tm], 0, 0, 0);
+            if (kSpread && tn < G::PER_WAVE) {
+                __builtin_amdgcn_sched_barrier(0);
+                if (do_issue) GEMM2_ISSUE_ONE(tn)
+                __builtin_amdgcn_sched_barrier(0);
             }
         }
         if (do_issue) GEMM2_ADVANCE_ISSUE();
@@ -657,247 +648,6 @@ __global__ __launch_bounds__(NTHR2 * DUALK, (BKT == 32 ? 4 : 2)) void gemm2_kern
 #undef GEMM2_ADVANCE_ISSUE
 }
 
-// ==============================================================================================
-// v5: "ping-pong" 256x256 tile.  8 waves = 2 row groups (wr) x 4 column waves (wc); a wave owns 128 x 64
-// (acc[4][8], 128 accumulator registers, one workgroup per CU => 256 registers per wave).  BK = 32, LDS-DMA into a
-// 4-stage ring (4 x 32 KiB), two K-steps in flight.  Every K-step is two PHASES (the two 64-row halves of the wave's
-// rows); a phase = [fragment ds_reads + 2 DMA pieces] s_barrier [16 MFMAs under s_setprio 1] s_barrier.  The two row
-// groups run ONE barrier apart (group 1 executes an extra barrier first): between two barriers one group issues
-// memory instructions while the other group's waves -- one per SIMD -- own the matrix pipe, so the ~100-cycle DMA
-// issues and the fragment-read latency of one group are hidden under the MFMAs of the other (the structure of the
-// CDNA guide's 8-phase template; here with BK = 32 phases and the loaders / epilogues of v2).
-//   RAW: a wave retires its own pieces of step g+1 with vmcnt(4) in phase (g,1) before that phase's first barrier;
-//        step g+1 is first read two barriers later.      WAR: slot (g+2)%4 was last read during step g-2.
-// ==============================================================================================
-constexpr int NTHR5 = 512;
-constexpr int G5_OP = 256 * 32 * 2;     // one operand image: 16 KiB
-constexpr int G5_STAGE = 2 * G5_OP;     // A + B
-constexpr int G5_SMEM = 4 * G5_STAGE;   // 128 KiB
-
-template <class AL, class BL, class EP, bool A_TR, bool B_TR, int NSEG>
-__global__ __launch_bounds__(NTHR5, 2) void gemm5_kernel(AL al, BL bl, EP ep, int M, int N, int K, int tiles_n, int ntiles,
-                                                         int kchunk, const bf16_t* zero_page) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wr = wave >> 2, wc = wave & 3;
-    const int nb = gridDim.x, xcd = blockIdx.x & 7, jx = blockIdx.x >> 3;
-    const int nbx = (nb >> 3) + (xcd < (nb & 7) ? 1 : 0);
-    const int qT = ntiles >> 3, rT = ntiles & 7;
-    const int tlo = xcd * qT + min(xcd, rT), tcnt = qT + (xcd < rT ? 1 : 0);
-    const int my_tiles = tcnt > jx ? (tcnt - jx + nbx - 1) / nbx : 0;
-    al.init(blockIdx.z);
-    bl.init(blockIdx.z);
-    ep.init(blockIdx.z);
-    const int nk_all = (K + 31) / 32;  // a K tail takes the generic per-piece decode for that step
-    const int kt0 = blockIdx.y * kchunk;
-    const int nk = min(kchunk, nk_all - kt0);
-    if (nk <= 0 || my_tiles <= 0) return;
-    const int total = nk * NSEG;
-    const int G_ = my_tiles * total;
-    const unsigned lds_base = (unsigned)(uintptr_t)(lds_char_ptr)smem;
-
-    f32x4 acc[4][8];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    // 32 pieces of 1 KiB per stage: ids 0..15 -> A, 16..31 -> B; wave w owns ids i*8 + w (i = 0, 1: A; 2, 3: B)
-    const char* pp[4];
-    long pstep[4];
-    int kpos_i = 0, seg_i = 0, tile_i = tlo + jx;  // issue cursor: K-step inside the segment, segment, tile
-    int bm_i = tile_i / tiles_n, bn_i = tile_i - bm_i * tiles_n;
-    const bool has_tail = (K & 31) != 0 && kt0 + nk == nk_all;  // this workgroup's last K-step of a segment is partial
-    int kb[4];  // this lane's k offset inside a K-step for each piece (K-tail predicate)
-#define GEMM5_SETUP(SEG, KT)                                                                                \
-    {                                                                                                       \
-        _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                     \
-            const int id = (i & 1) * 8 + wave;                                                              \
-            bool ok;                                                                                        \
-            const bf16_t* p;                                                                                \
-            if (i < 2) {                                                                                    \
-                if constexpr (!A_TR) {                                                                      \
-                    const int row = id * 16 + (lane >> 2), ch = kc_swz<32>(row, lane & 3);                  \
-                    p = al.ptr(SEG, bm_i * 256 + row, (KT)*4 + ch, ok);                                     \
-                    ok = bm_i * 256 + row < M;                                                              \
-                    kb[i] = ch * 8;                                                                         \
-                } else {                                                                                    \
-                    const int k = (id & 7) * 4 + (lane >> 4), cu = bm_i * 32 + (id >> 3) * 16 + ((lane & 15) ^ (tr_key(k) << 1)); \
-                    p = al.ptr(SEG, (KT)*32 + k, cu, ok);                                                   \
-                    ok = cu * 8 < M;                                                                        \
-                    kb[i] = k;                                                                              \
-                }                                                                                           \
-                pstep[i] = !ok ? 0L : A_TR ? 64L * al.kstride() : 64L;                                      \
-            } else {                                                                                        \
-                if constexpr (!B_TR) {                                                                      \
-                    const int row = id * 16 + (lane >> 2), ch = kc_swz<32>(row, lane & 3);                  \
-                    p = bl.ptr(SEG, bn_i * 256 + row, (KT)*4 + ch, ok);                                     \
-                    ok = bn_i * 256 + row < N;                                                              \
-                    kb[i] = ch * 8;                                                                         \
-                } else {                                                                                    \
-                    const int k = (id & 7) * 4 + (lane >> 4), cu = bn_i * 32 + (id >> 3) * 16 + ((lane & 15) ^ (tr_key(k) << 1)); \
-                    p = bl.ptr(SEG, (KT)*32 + k, cu, ok);                                                   \
-                    ok = cu * 8 < N;                                                                        \
-                    kb[i] = k;                                                                              \
-                }                                                                                           \
-                pstep[i] = !ok ? 0L : B_TR ? 64L * bl.kstride() : 64L;                                      \
-            }                                                                                               \
-            pp[i] = ok ? (const char*)p : (const char*)zero_page;                                           \
-        }                                                                                                   \
-    }
-    // pieces 2h, 2h+1 of the stage for the issue cursor's K-step go out in phase h.  The piece pointers are stepped for
-    // every K-step; only the (wave-uniform, rare) last partial step masks the lanes whose k index is beyond K.
-#define GEMM5_ISSUE_HALF(SLOT, H)                                                                           \
-    {                                                                                                       \
-        const unsigned sb_ = lds_base + (SLOT)*G5_STAGE + ((H) ? G5_OP : 0);                                \
-        if ((H) == 0 && kpos_i == 0) GEMM5_SETUP(seg_i, kt0);                                               \
-        const char *q0 = pp[2 * (H)], *q1 = pp[2 * (H) + 1];                                                \
-        if (has_tail && kpos_i == nk - 1) {                                                                 \
-            const int k0_ = (kt0 + kpos_i) * 32;                                                            \
-            q0 = (k0_ + kb[2 * (H)] < K) ? q0 : (const char*)zero_page;                                     \
-            q1 = (k0_ + kb[2 * (H) + 1] < K) ? q1 : (const char*)zero_page;                                 \
-        }                                                                                                   \
-        glds16(q0, sb_ + (0 * 8 + wave) * 1024);                                                            \
-        glds16(q1, sb_ + (1 * 8 + wave) * 1024);                                                            \
-        pp[2 * (H)] += pstep[2 * (H)], pp[2 * (H) + 1] += pstep[2 * (H) + 1];                               \
-        if ((H) == 1 && ++kpos_i == nk) {                                                                   \
-            kpos_i = 0;                                                                                     \
-            if (NSEG == 1 || ++seg_i == NSEG) {                                                             \
-                seg_i = 0;                                                                                  \
-                tile_i += nbx;                                                                              \
-                bm_i = tile_i / tiles_n, bn_i = tile_i - bm_i * tiles_n;                                    \
-            }                                                                                               \
-        }                                                                                                   \
-    }
-    // prologue: two stages in flight, the first one landed for everybody
-    GEMM5_ISSUE_HALF(0, 0);
-    GEMM5_ISSUE_HALF(0, 1);
-    if (G_ > 1) {
-        GEMM5_ISSUE_HALF(1, 0);
-        GEMM5_ISSUE_HALF(1, 1);
-        asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    } else {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    asm volatile("s_barrier" ::: "memory");
-    if (wr == 1) asm volatile("s_barrier" ::: "memory");  // stagger: group 1 runs one barrier behind group 0
-
-    int it_c = 0, tile_c = tlo + jx;
-    bf16x8_t bf[4];
-    for (int g = 0; g < G_; ++g) {
-        const int slot = g & 3;
-        const char* ta = smem + slot * G5_STAGE;
-        const char* tb = ta + G5_OP;
-        const bool do_issue = g + 2 < G_;
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            bf16x8_t af[4];
-            if (h == 0) {
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    if constexpr (!B_TR) bf[t] = read_frag2<32, false>(tb, wc * 64 + t * 16, 0, lane);
-                    else bf[t] = read_frag2<32, true>(tb + (wc >> 1) * 8192, (wc & 1) * 64 + t * 16, 0, lane);
-                }
-            }
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                if constexpr (!A_TR) af[t] = read_frag2<32, false>(ta, wr * 128 + h * 64 + t * 16, 0, lane);
-                else af[t] = read_frag2<32, true>(ta + wr * 8192, h * 64 + t * 16, 0, lane);
-            }
-            if (do_issue) GEMM5_ISSUE_HALF((g + 2) & 3, h);
-            if (h == 1 && g + 1 < G_) {
-                if (do_issue) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-                else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            }
-            asm volatile("s_barrier" ::: "memory");
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-            for (int tn = 0; tn < 4; ++tn)
-#pragma unroll
-                for (int tm = 0; tm < 4; ++tm)
-                    acc[tn][h * 4 + tm] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[tn], af[tm], acc[tn][h * 4 + tm], 0, 0, 0);
-            __builtin_amdgcn_s_setprio(0);
-            asm volatile("s_barrier" ::: "memory");
-        }
-        if (++it_c < total) continue;
-        it_c = 0;
-        if constexpr (EP::kStagedAtomic) break;  // one tile per workgroup: staged epilogue after the loop
-        const int bm = tile_c / tiles_n, bn = tile_c - bm * tiles_n;
-        tile_c += nbx;
-        f32x4 cs[4];
-#pragma unroll
-        for (int tn = 0; tn < 4; ++tn) cs[tn] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int tm = 0; tm < 8; ++tm) {
-            const int m = bm * 256 + wr * 128 + tm * 16 + (lane & 15);
-#pragma unroll
-            for (int tn = 0; tn < 4; ++tn) {
-                const int n = bn * 256 + wc * 64 + tn * 16 + 4 * (lane >> 4);
-                if (m < M && n < N) {
-                    if constexpr (EP::kColSum) cs[tn] += ep.store_ret(m, n, acc[tn][tm]);
-                    else ep.store(m, n, acc[tn][tm]);
-                }
-                acc[tn][tm] = f32x4{0.f, 0.f, 0.f, 0.f};
-            }
-            asm volatile("" ::: "memory");
-        }
-        if constexpr (EP::kColSum) {
-            if (ep.colsum) {
-#pragma unroll
-                for (int tn = 0; tn < 4; ++tn) {
-                    const int n = bn * 256 + wc * 64 + tn * 16 + 4 * (lane >> 4);
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) {
-                        float v = cs[tn][c];
-                        v += __shfl_xor(v, 1, 64);
-                        v += __shfl_xor(v, 2, 64);
-                        v += __shfl_xor(v, 4, 64);
-                        v += __shfl_xor(v, 8, 64);
-                        if ((lane & 15) == 0 && n + c < N) ig_red_add(ep.colsum + n + c, v);
-                    }
-                }
-            }
-        }
-    }
-    if (wr == 0) asm volatile("s_barrier" ::: "memory");  // balance group 1's extra barrier: the groups are aligned again
-    if constexpr (EP::kStagedAtomic) {
-        // weight gradient (one tile per workgroup, split-K over blockIdx.y): the fp32 tile goes through the idle ring in two
-        // 128-row passes (128 KiB each) and is added with row-contiguous 256-byte atomic wave-instructions
-        const int bm = tile_c / tiles_n, bn = tile_c - bm * tiles_n;
-        float* st = reinterpret_cast<float*>(smem);
-#pragma unroll
-        for (int pass = 0; pass < 2; ++pass) {
-            __syncthreads();
-            if (wr == pass) {
-#pragma unroll
-                for (int tm = 0; tm < 8; ++tm) {
-                    const int ml = tm * 16 + (lane & 15);
-#pragma unroll
-                    for (int tn = 0; tn < 4; ++tn) {
-                        const int c4 = (wc * 64 + tn * 16 + 4 * (lane >> 4)) >> 2;
-                        *reinterpret_cast<f32x4*>(st + ml * 256 + ((c4 ^ (ml & 7)) << 2)) = acc[tn][tm];
-                    }
-                }
-            }
-            __syncthreads();
-            for (int rr = wave; rr < 128; rr += NTHR5 / 64) {
-                const int m = bm * 256 + pass * 128 + rr;
-                if (m >= M) break;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int nl = q * 64 + lane;
-                    const int n = bn * 256 + nl;
-                    if (n < N) ep.add(m, n, st[rr * 256 + ((((nl >> 2) ^ (rr & 7)) << 2) | (nl & 3))]);
-                }
-            }
-        }
-    }
-#undef GEMM5_ISSUE_HALF
-#undef GEMM5_SETUP
-}
-
 // FDiv / make_fdiv (division by a launch-time constant as multiply-high + shift): common.h
 
 // ------------------------------------------------------------------------------------ loaders
@@ -906,7 +656,7 @@ __global__ __launch_bounds__(NTHR5, 2) void gemm5_kernel(AL al, BL bl, EP ep, in
 __device__ __forceinline__ const bf16_t* bsel(const bf16_t* const (&b)[3], int seg) { return seg == 0 ? b[0] : seg == 1 ? b[1] : b[2]; }
 struct PlainLoader {
     static constexpr const char* kName = "PlainLoader";  // row-major [R][ld], logical width C (multiple of 8)
-    static constexpr bool kLinearK = true;  // ptr() is affine in the K index (v2 steps piece pointers instead of re-decoding)
+    static constexpr bool kLinearK = true;  // ptr() is affine in the K index: a plain matrix, which v2 reads (stepping piece pointers)
     const bf16_t* base[3];
     int R, C;
     long ld;
@@ -938,7 +688,6 @@ struct PlainLoader {
 struct Conv3Loader {
     static constexpr const char* kName = "Conv3Loader";
     static constexpr bool kLinearK = false;
-    __device__ long kstride() const { return 0; }
     const bf16_t* base[3];
     int Mtot, H, W, C, sign;
     FDiv f_hw, f_w, f_c;  // set by finish()
@@ -987,7 +736,6 @@ struct Conv3Loader {
         ok = cl.ok & (r < Mtot) & ((unsigned)(y + cl.dy) < (unsigned)H) & ((unsigned)(x + cl.dx) < (unsigned)W);
         return bsel(base, seg) + (ok ? (long)r * C + cl.delta : 0L);
     }
-    __device__ const bf16_t* ptr(int seg, int r, int c8, bool& ok) const { return ptr_tr(seg, r, col(c8), ok); }
 };
 
 // NHWC KS x KS convolution with padding 1 (nn.Conv2d(kernel_size=KS, padding=1), model.py:370-375 with the 600M variants'
@@ -998,7 +746,6 @@ struct Conv3Loader {
 struct ConvKLoader {
     static constexpr const char* kName = "ConvKLoader";
     static constexpr bool kLinearK = false;
-    __device__ long kstride() const { return 0; }
     const bf16_t* base[3];
     int Mtot, Hr, Wr, Hs, Ws, C, KS, sign;
     FDiv f_hw, f_w, f_c, f_ks;
@@ -1024,7 +771,6 @@ struct ConvKLoader {
         return bsel(base, seg) + (ok ? rw.off + ((long)ys * Ws + xs) * C + cl.c : 0L);
     }
     __device__ const bf16_t* ptr_tr(int seg, int r, const Col& cl, bool& ok) const { return at(seg, row(r), cl, ok); }
-    __device__ const bf16_t* ptr(int seg, int r, int c8, bool& ok) const { return at(seg, row(r), col(c8), ok); }
 };
 
 // ConvTranspose2d(k3,s2,p1,op1) forward, sub-pixel phase z=(py,px): output (2iy+py, 2ix+px) reads taps
@@ -1032,7 +778,6 @@ struct ConvKLoader {
 struct ConvTFwdALoader {
     static constexpr const char* kName = "ConvTFwdALoader";
     static constexpr bool kLinearK = false;
-    __device__ long kstride() const { return 0; }
     const bf16_t* base[3];
     int Mtot, H, W, C;
     FDiv f_hw, f_w, f_c;
@@ -1067,13 +812,11 @@ struct ConvTFwdALoader {
         return bsel(base, seg) + (ok ? rw.off + cl.delta : 0L);
     }
     __device__ const bf16_t* ptr_tr(int seg, int r, const Col& cl, bool& ok) const { return at(seg, row(r), cl, ok); }
-    __device__ const bf16_t* ptr(int seg, int r, int c8, bool& ok) const { return at(seg, row(r), col(c8), ok); }
 };
 // matching weight view: n = co, k = (local tap, ci) of storage Wc[co][tap][ci]
 struct ConvTFwdBLoader {
     static constexpr const char* kName = "ConvTFwdBLoader";
     static constexpr bool kLinearK = false;
-    __device__ long kstride() const { return 0; }
     const bf16_t* base[3];
     int Cout, C;
     FDiv f_c;  // set by finish(): multiply-high division by C (a runtime division per 16-byte unit sat in every K-step)
@@ -1108,7 +851,6 @@ struct ConvTFwdBLoader {
 struct ConvWgtTRLoader {
     static constexpr const char* kName = "ConvWgtTRLoader";
     static constexpr bool kLinearK = false;
-    __device__ long kstride() const { return 0; }
     const bf16_t* base[3];
     int Cout, Cin;
     int ntaps = 9;  // 3 x 3; 25 / 49 for the 5 x 5 / 7 x 7 convolutions of the 600M head (ig_convk_*)
@@ -1136,7 +878,6 @@ struct ConvWgtTRLoader {
 struct ConvTGradLoader {
     static constexpr const char* kName = "ConvTGradLoader";
     static constexpr bool kLinearK = false;
-    __device__ long kstride() const { return 0; }
     const bf16_t* base[3];
     int Mtot, H, W, Cout;  // H,W = input resolution; dOut is (2H,2W)
     int fixed_tap;         // -1: k=(tap,co); -2: take tap from blockIdx.z
@@ -1184,7 +925,6 @@ struct ConvTGradLoader {
         ok = cl.ok & (r < Mtot) & ((unsigned)(2 * y - 1 + cl.ky) < (unsigned)(2 * H)) & ((unsigned)(2 * x - 1 + cl.kx) < (unsigned)(2 * W));
         return bsel(base, seg) + (ok ? (((long)(b * 2 * H + 2 * y)) * (2 * W) + 2 * x) * Cout + cl.delta : 0L);
     }
-    __device__ const bf16_t* ptr(int seg, int r, int c8, bool& ok) const { return ptr_tr(seg, r, col(c8), ok); }
 };
 
 // ---------------------------------------------------------------------------------- epilogues
@@ -1390,18 +1130,8 @@ inline float* splitk_workspace(size_t bytes, hipStream_t st) {
     const bool capturing = hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
     return (float*)ig_scratch2(5, bytes, !capturing, st);
 }
-constexpr bool splitk_partial_enabled() { return true; }  // split-K partials + ordered fold (the float-atomic form was an A/B arm)
 
 // ------------------------------------------------------------------------------------ launch
-// Engine choice for the plain-matrix GEMMs that the 8-phase / 4-wave engines do not cover: v2 everywhere except the shapes where the
-// ping-pong v5 measured faster on the same box (tools/gemm_bench.py): dgrad without an elementwise factor (+8-9 %) and the residual
-// GEMM with a long reduction (fc2, K = 4D: +9 %).  (The IG_GEMM switch that forced one engine was an A/B arm and is gone.)
-inline int gemm_version() { return 2; }
-inline int gemm_version_prefer5(bool prefer) { return prefer ? 5 : 2; }
-inline int conv_version(int n_out) {
-    (void)n_out;
-    return 1;  // measured: v1 is faster for every conv stage (gather address math per LDS-DMA issue)
-}
 inline const bf16_t* zero_page() {
     static void* z = nullptr;
     if (!z) {
@@ -1413,9 +1143,12 @@ inline const bf16_t* zero_page() {
 
 constexpr int tr_pitch(int upr) { return upr <= 8 ? 8 : upr <= 12 ? 12 : 16; }
 
+// `engine`: 2 = v2, 1 = v1, for plain-matrix operands.  Gathered operands always run v1 (measured faster on every convolution
+// stage: v2 would redo the gather address math per LDS-DMA issue).
 template <class AL, class BL, class EP, bool A_TR, bool B_TR>
 int launch_gemm(const AL& al, const BL& bl, const EP& ep_in, int M, int N, int K, int Z, bool split, hipStream_t st,
-                const char* what, bool allow_ksplit = false, int force_ver = 0) {
+                const char* what, bool allow_ksplit = false, int engine = 2) {
+    constexpr bool kPlain = AL::kLinearK && BL::kLinearK;
     if (M <= 0 || N <= 0 || K <= 0) return IG_OK;
     EP ep = ep_in;
     // Split-K weight gradients (atomic epilogue): `ks` splits store their tiles into workspace slabs and one reduce launch adds them
@@ -1427,7 +1160,7 @@ int launch_gemm(const AL& al, const BL& bl, const EP& ep_in, int M, int N, int K
             // Z > 1 (the taps of the ConvTranspose weight gradient in blockIdx.z): the z slices must tile the rows of `out` exactly,
             // because the reduce adds WHOLE slabs -- an element no workgroup stored would be garbage
             const bool z_ok = Z == 1 || ((long)Z * ep.zstride == ep.ldo && (long)N == ep.zstride);
-            if (ks > 1 && z_ok && splitk_partial_enabled() && ((long)M * ep.ldo) % 4 == 0 && (((uintptr_t)ep.out) & 15) == 0) {
+            if (ks > 1 && z_ok && ((long)M * ep.ldo) % 4 == 0 && (((uintptr_t)ep.out) & 15) == 0) {
                 float* ws = splitk_workspace((size_t)ks * M * ep.ldo * sizeof(float), st);
                 if (ws) {  // (no workspace -- allocation failed or a capture is active: the atomic form, still correct)
                     ep.partial = ws, ep.slab = (long)M * ep.ldo;
@@ -1449,56 +1182,21 @@ int launch_gemm(const AL& al, const BL& bl, const EP& ep_in, int M, int N, int K
     };
     // v2 (256x128, LDS-DMA ring) wins on the encoder linears; the head convolutions (Cout 48..384, huge M) are
     // better served by the 128x128 register-staged tile at 2 workgroups/CU until a narrow-N tile exists
-    int ver = force_ver ? force_ver : gemm_version();
-    if (!EP::kStagedAtomic && AL::kLinearK && BL::kLinearK) {
-        // small problems (e.g. the YAML's batch 16: M = 3152 rows): the big tiles leave most CUs idle -- a 256x256 tile
-        // needs >= 192 tiles to be worth one workgroup per CU, a 256x128 tile >= 256; below that the 128x128 engine's
-        // 2-4x larger tile count wins (measured at B = 16: fc2 94.9 us on v5)
-        if (ver == 5 && (long)ig_cdiv(M, 256) * ig_cdiv(N, 256) < 192) ver = 2;
+    int ver = kPlain ? engine : 1;
+    if (!EP::kStagedAtomic && kPlain) {
+        // small problems (e.g. the YAML's batch 16: M = 3152 rows): the big tiles leave most CUs idle -- a 256x128 tile
+        // needs >= 256 tiles to be worth its place; below that the 128x128 engine's 2-4x larger tile count wins
         if (ver == 2 && (long)ig_cdiv(M, 256) * ig_cdiv(N, 128) < 256) ver = 1;
     }
     if constexpr (EP::kColSum) {
-        if (ver == 1 && ep.colsum) ver = 2;  // the fused column sums live in the v2 / v5 epilogues only
-    }
-    if constexpr (AL::kLinearK && BL::kLinearK) {
-        if (ver == 5) {
-            const int tm5 = ig_cdiv(M, 256), tn5 = ig_cdiv(N, 256), ntiles = tm5 * tn5;
-            dim3 grid5(ig_tile_grid(ntiles, 1), 1, Z);  // persistent: one workgroup per CU
-            int kchunk5 = ig_cdiv(K, 32);
-            if constexpr (EP::kStagedAtomic) {  // one tile per workgroup, split-K over blockIdx.y, one workgroup per CU
-                grid5.x = ntiles;
-                const int nk32 = kchunk5;
-                int ks = 256 / (ntiles * Z);
-                if (ks > nk32 / 16) ks = nk32 / 16;
-                if (ks < 1) ks = 1;
-                kchunk5 = ig_cdiv(nk32, ks);
-                grid5.y = ig_cdiv(nk32, kchunk5);
+        if (ver == 1 && ep.colsum) {  // the fused column sums live in the v2 epilogue only
+            if constexpr (!kPlain) {
+                ig_set_error("%s: fused column sums need plain-matrix operands", what);
+                return IG_ERR_ARG;
             }
-            const bf16_t* zp5 = zero_page();
-            if (!zp5) {
-                ig_set_error("%s: could not allocate the zero page", what);
-                return IG_ERR_HIP;
-            }
-#define IG_LAUNCH_V5(NSEG_)                                                                                           \
-    {                                                                                                                  \
-        auto kern = gemm5_kernel<AL, BL, EP, A_TR, B_TR, NSEG_>;                                                       \
-        static bool attr_done = false;                                                                                 \
-        if (!attr_done) {                                                                                              \
-            (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, G5_SMEM);         \
-            attr_done = true;                                                                                          \
-        }                                                                                                              \
-        ig_note_kernel("gemm5_kernel<%s,%s,%s,%s,%s,%d>", AL::kName, BL::kName, EP::kName, A_TR ? "true" : "false", B_TR ? "true" : "false", NSEG_); \
-        ig_note_grid((int)grid5.x);                                                                                    \
-        hipLaunchKernelGGL(kern, grid5, dim3(NTHR5), G5_SMEM, st, al, bl, ep, M, N, K, tn5, ntiles, kchunk5, zp5);     \
-    }
-            if (prep_partial((int)grid5.y) != IG_OK) return IG_ERR_HIP;
-            if (split) IG_LAUNCH_V5(3) else IG_LAUNCH_V5(1)
-#undef IG_LAUNCH_V5
-            finish_partial();
-            return ig_check_launch(what);
+            ver = 2;
         }
     }
-    if (ver == 5) ver = 2;  // shapes / epilogues v5 does not cover
     // v1 tile shape: the candidate with the fewest padded rows/columns, ties to the larger tile.  Weight gradients
     // (atomic epilogue) vary the tile height (M = Cout), everything else the width (N = Cout).  Code 1 = 48.
     int mt = 4, nt = 4;
@@ -1538,40 +1236,40 @@ int launch_gemm(const AL& al, const BL& bl, const EP& ep_in, int M, int N, int K
     int kchunk = ig_cdiv(nk_all, ksplit);
     ksplit = ig_cdiv(nk_all, kchunk);
     dim3 grid(tm * tn, ksplit, Z);
-    if (ver == 2) {
-        const int ntiles = tm * tn;
-        const bf16_t* zp = zero_page();
-        if (!zp) {
-            ig_set_error("%s: could not allocate the zero page", what);
-            return IG_ERR_HIP;
-        }
-#define IG_LAUNCH_V2(NSEG_, BKT_)                                                                                        \
+    if constexpr (kPlain) {
+        if (ver == 2) {
+            const int ntiles = tm * tn;
+            const bf16_t* zp = zero_page();
+            if (!zp) {
+                ig_set_error("%s: could not allocate the zero page", what);
+                return IG_ERR_HIP;
+            }
+#define IG_LAUNCH_V2(NSEG_)                                                                                              \
     {                                                                                                                     \
-        auto kern = gemm2_kernel<AL, BL, EP, A_TR, B_TR, NSEG_, BKT_>;                                                    \
+        auto kern = gemm2_kernel<AL, BL, EP, A_TR, B_TR, NSEG_>;                                                          \
         static bool attr_done = false;                                                                                    \
         if (!attr_done) {                                                                                                 \
-            (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, G2<BKT_>::SMEM);     \
+            (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, G2::SMEM);          \
             attr_done = true;                                                                                             \
         }                                                                                                                 \
-        ig_note_kernel("gemm2_kernel<%s,%s,%s,%s,%s,%d,%d,1>", AL::kName, BL::kName, EP::kName, A_TR ? "true" : "false", B_TR ? "true" : "false", NSEG_, BKT_); \
+        ig_note_kernel("gemm2_kernel<%s,%s,%s,%s,%s,%d,32,1>", AL::kName, BL::kName, EP::kName, A_TR ? "true" : "false", B_TR ? "true" : "false", NSEG_); \
         ig_note_grid((int)grid.x);                                                                                        \
-        hipLaunchKernelGGL(kern, grid, dim3(NTHR2), G2<BKT_>::SMEM, st, al, bl, ep, M, N, K, tn, ntiles, kchunk, zp);     \
+        hipLaunchKernelGGL(kern, grid, dim3(NTHR2), G2::SMEM, st, al, bl, ep, M, N, K, tn, ntiles, kchunk, zp);          \
     }
-        if constexpr (EP::kStagedAtomic) {
-            // one tile per workgroup (split-K over blockIdx.y); the fp32 tile is staged through the ring in two halves
-            const int nk32 = ig_cdiv(K, 32);
-            const bool dual = !split && AL::kLinearK && BL::kLinearK && nk32 >= 64;
-            int ks = (dual ? 256 : 512) / (tm * tn * Z);  // two 8-wave workgroups per CU, or one 16-wave workgroup (two K halves)
-            if (ks > nk32 / (dual ? 32 : 16)) ks = nk32 / (dual ? 32 : 16);
-            if (ks < 1) ks = 1;
-            kchunk = ig_cdiv(nk32, ks);
-            grid.y = ig_cdiv(nk32, kchunk);
-            if constexpr (AL::kLinearK && BL::kLinearK) {
+            if constexpr (EP::kStagedAtomic) {
+                // one tile per workgroup (split-K over blockIdx.y); the fp32 tile is staged through the ring in two halves
+                const int nk32 = ig_cdiv(K, 32);
+                const bool dual = !split && nk32 >= 64;
+                int ks = (dual ? 256 : 512) / (tm * tn * Z);  // two 8-wave workgroups per CU, or one 16-wave workgroup (two K halves)
+                if (ks > nk32 / (dual ? 32 : 16)) ks = nk32 / (dual ? 32 : 16);
+                if (ks < 1) ks = 1;
+                kchunk = ig_cdiv(nk32, ks);
+                grid.y = ig_cdiv(nk32, kchunk);
                 if (dual) {
-                    auto kern = gemm2_kernel<AL, BL, EP, A_TR, B_TR, 1, 32, 2>;
+                    auto kern = gemm2_kernel<AL, BL, EP, A_TR, B_TR, 1, 2>;
                     static bool attr_dual = false;
                     if (!attr_dual) {
-                        (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * G2<32>::SMEM);
+                        (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * G2::SMEM);
                         attr_dual = true;
                     }
                     ig_note_kernel("gemm2_kernel<%s,%s,%s,%s,%s,1,32,2>", AL::kName, BL::kName, EP::kName, A_TR ? "true" : "false", B_TR ? "true" : "false");
@@ -1580,28 +1278,26 @@ int launch_gemm(const AL& al, const BL& bl, const EP& ep_in, int M, int N, int K
                         ep.pairs = (int)grid.y;
                         grid.x = grid.x * grid.y, grid.y = 1;
                     }
-                    hipLaunchKernelGGL(kern, grid, dim3(2 * NTHR2), 2 * G2<32>::SMEM, st, al, bl, ep, M, N, K, tn, ntiles, kchunk, zp);
+                    hipLaunchKernelGGL(kern, grid, dim3(2 * NTHR2), 2 * G2::SMEM, st, al, bl, ep, M, N, K, tn, ntiles, kchunk, zp);
                     finish_partial();
                     return ig_check_launch(what);
                 }
-            }
-            if (prep_partial((int)grid.y) != IG_OK) return IG_ERR_HIP;
-            {
+                if (prep_partial((int)grid.y) != IG_OK) return IG_ERR_HIP;
                 if (grid.y > 1) {
                     ep.pairs = (int)grid.y;
                     grid.x = grid.x * grid.y, grid.y = 1;
                 }
+                if (split) IG_LAUNCH_V2(3) else IG_LAUNCH_V2(1)
+                finish_partial();
+            } else {
+                // persistent: two workgroups per CU walk the tile list; BK = 32 keeps the ring at 72 KiB
+                grid.x = ig_tile_grid((int)grid.x, 2);  // persistent: two workgroups per CU
+                kchunk = ig_cdiv(K, 32);
+                if (split) IG_LAUNCH_V2(3) else IG_LAUNCH_V2(1)
             }
-            if (split) IG_LAUNCH_V2(3, 32) else IG_LAUNCH_V2(1, 32)
-            finish_partial();
-        } else {
-            // persistent: two workgroups per CU walk the tile list; BK = 32 keeps the ring at 72 KiB
-            grid.x = ig_tile_grid((int)grid.x, 2);  // persistent: two workgroups per CU
-            kchunk = ig_cdiv(K, 32);
-            if (split) IG_LAUNCH_V2(3, 32) else IG_LAUNCH_V2(1, 32)
-        }
 #undef IG_LAUNCH_V2
-        return ig_check_launch(what);
+            return ig_check_launch(what);
+        }
     }
     dim3 block(NTHR);
 #define IG_LAUNCH_V1K(NSEG_, MT_, NT_, WM_, BKT_)                                                                      \
@@ -1730,7 +1426,7 @@ int ig_linear_residual_fwd(const void* x_hi, const void* x_lo, const void* w_hi,
     EpResidual ep{out, resid, bias, (long)N};
     return launch_gemm<PlainLoader, PlainLoader, EpResidual, false, false>(
         plain_a(x_hi, x_lo, M, K, K), plain_b(w_hi, w_lo, N, K, K), ep, M, N, K, 1, x_lo != nullptr, (hipStream_t)stream,
-        "ig_linear_residual_fwd", false, gemm_version_prefer5(K >= 2048 && x_lo == nullptr));
+        "ig_linear_residual_fwd");
 }
 
 // dx[M][K] = dy[M][N] @ w[N][K]       mode 0: plain store, 1: * gelu'(pre[M][K])
@@ -1747,7 +1443,7 @@ int ig_linear_dgrad(const void* dy_hi, const void* dy_lo, const void* w_hi, cons
     // C[m][k] = sum_n dy[m][n] * w[n][k]: reduce dim = N; B operand is TR (rows n, contiguous k)
     return launch_gemm<PlainLoader, PlainLoader, EpGradStore, false, true>(
         plain_a(dy_hi, dy_lo, M, N, N), plain_b(w_hi, w_lo, N, K, K), ep, M, K, N, 1, dy_lo != nullptr, (hipStream_t)stream,
-        "ig_linear_dgrad", false, gemm_version_prefer5(mode == 0 && dx_colsum == nullptr && dy_lo == nullptr));
+        "ig_linear_dgrad");
 }
 
 // ig_linear_dgrad with the weight given TRANSPOSED: wt[K][N] = w^T.  Both operands are then contiguous in the reduce dimension N
@@ -1869,11 +1565,10 @@ int ig_conv3x3_fwd(const void* x_hi, const void* x_lo, const void* w_hi, const v
     al.finish();
     EpStore ep{};
     ep.out_hi = (bf16_t*)y_hi, ep.out_lo = (bf16_t*)y_lo, ep.bias = bias, ep.ldo = Cout;
-    IG_REQUIRE((bn_scale == nullptr) == (bn_shift == nullptr), "ig_conv3x3_fwd: bn_scale and bn_shift go together");
     ep.col_scale = bn_scale, ep.col_shift = bn_shift;  // eval-mode BatchNorm + ReLU folded into the epilogue
     return launch_gemm<Conv3Loader, PlainLoader, EpStore, false, false>(
         al, plain_b(w_hi, w_lo, Cout, 9 * Cin, 9L * Cin), ep, al.Mtot, Cout, 9 * Cin, 1, x_lo != nullptr,
-        (hipStream_t)stream, "ig_conv3x3_fwd", false, conv_version(Cout));
+        (hipStream_t)stream, "ig_conv3x3_fwd");
 }
 
 // The same convolution in front of a training-mode BatchNorm: where the direct kernel runs (the 48-channel last stage) it also
@@ -1941,17 +1636,13 @@ int ig_conv3x3_dgrad(const void* dy_hi, const void* dy_lo, const void* w_hi, con
     bl.Cout = Cout, bl.Cin = Cin;
     bl.finish();
     EpGradStore ep{};
-    IG_REQUIRE(drop_p <= 0.f || (double)B * H * W * Cin < 4294967296.0, "ig_conv3x3_dgrad: dropout needs < 2^32 elements");
     ep.out_hi = (bf16_t*)dx_hi, ep.out_lo = (bf16_t*)dx_lo, ep.ldo = Cin, ep.mode = 2;
     ep.drop_seed = drop_seed, ep.drop_seed_dev = drop_seed_dev;
     ep.drop_thresh = ig_drop_thresh16(drop_p);
     ep.drop_inv = drop_p > 0.f ? 1.0f / (1.0f - drop_p) : 1.0f;
     return launch_gemm<Conv3Loader, ConvWgtTRLoader, EpGradStore, false, true>(
-        al, bl, ep, al.Mtot, Cin, 9 * Cout, 1, dy_lo != nullptr, (hipStream_t)stream, "ig_conv3x3_dgrad", false, conv_version(Cin));
+        al, bl, ep, al.Mtot, Cin, 9 * Cout, 1, dy_lo != nullptr, (hipStream_t)stream, "ig_conv3x3_dgrad");
 }
-
-// split-operand weight gradients of the narrow stages: three launches of the bf16 direct kernels (round 4: +6.6 % on the bf16x3 step)
-static constexpr bool direct_x3_env() { return true; }
 
 // dWc[Cout][9][Cin] += sum_pixels dy[p][co] * x[shift_tap(p)][ci]
 int ig_conv3x3_wgrad(const void* dy_hi, const void* dy_lo, const void* x_hi, const void* x_lo, float* dw, float* dbias, int B,
@@ -1975,7 +1666,7 @@ int ig_conv3x3_wgrad(const void* dy_hi, const void* dy_lo, const void* x_hi, con
             if (rc == IG_OK && dbias && !fused) return ig_colsum(dy_hi, dy_lo, dbias, (long)B * H * W, Cout, stream);
             return rc;
         }
-    } else if (direct_x3_env()) {
+    } else {
         // split operands on the narrow stages: the bf16x3 product dy^T x = dy_hi^T x_hi + dy_hi^T x_lo + dy_lo^T x_hi (lo x lo dropped, as in
         // every split GEMM here) is a SUM of three bf16 products accumulated in fp32 -- and the direct kernel accumulates into dw: three
         // launches on the operand pairs (1.7 ms at 48 channels, B = 216, against 4.4 ms on the gather GEMM, whose 128 x 128 tiles fit a 48-row
@@ -2001,7 +1692,7 @@ int ig_conv3x3_wgrad(const void* dy_hi, const void* dy_lo, const void* x_hi, con
     EpAtomic ep{dw, 9L * Cin, 0, 0, nullptr, 0};
     return launch_gemm<PlainLoader, Conv3Loader, EpAtomic, true, true>(
         plain_a(dy_hi, dy_lo, Mtot, Cout, Cout), bl, ep, Cout, 9 * Cin, Mtot, 1, dy_lo != nullptr, (hipStream_t)stream,
-        "ig_conv3x3_wgrad", true, 1);
+        "ig_conv3x3_wgrad", true);
 }
 
 // ---- nn.Conv2d(kernel_size=KS, padding=1), KS odd >= 3, NHWC, weight storage Wc[Cout][KS*KS][Cin]: the 5 x 5 / 7 x 7 convolutions of
@@ -2024,7 +1715,7 @@ int ig_convk_fwd(const void* x_hi, const void* x_lo, const void* w_hi, const voi
     ep.col_scale = bn_scale, ep.col_shift = bn_shift;
     return launch_gemm<ConvKLoader, PlainLoader, EpStore, false, false>(
         al, plain_b(w_hi, w_lo, Cout, KS * KS * Cin, (long)KS * KS * Cin), ep, al.Mtot, Cout, KS * KS * Cin, 1, x_lo != nullptr,
-        (hipStream_t)stream, "ig_convk_fwd", false, 1);
+        (hipStream_t)stream, "ig_convk_fwd");
 }
 
 // dx (B,H,W,Cin) = conv_dgrad(dy (B,Ho,Wo,Cout), w) [* dropout mask of the conv input when drop_p > 0]
@@ -2050,7 +1741,7 @@ int ig_convk_dgrad(const void* dy_hi, const void* dy_lo, const void* w_hi, const
     ep.drop_thresh = ig_drop_thresh16(drop_p);
     ep.drop_inv = drop_p > 0.f ? 1.0f / (1.0f - drop_p) : 1.0f;
     return launch_gemm<ConvKLoader, ConvWgtTRLoader, EpGradStore, false, true>(
-        al, bl, ep, al.Mtot, Cin, KS * KS * Cout, 1, dy_lo != nullptr, (hipStream_t)stream, "ig_convk_dgrad", false, 1);
+        al, bl, ep, al.Mtot, Cin, KS * KS * Cout, 1, dy_lo != nullptr, (hipStream_t)stream, "ig_convk_dgrad");
 }
 
 // dWc[Cout][KS*KS][Cin] += sum over output pixels of dy[p][co] * x[shift_tap(p)][ci];  dbias[co] += sum_p dy[p][co] (optional)
@@ -2072,7 +1763,7 @@ int ig_convk_wgrad(const void* dy_hi, const void* dy_lo, const void* x_hi, const
     EpAtomic ep{dw, (long)KS * KS * Cin, 0, 0, nullptr, 0};
     return launch_gemm<PlainLoader, ConvKLoader, EpAtomic, true, true>(
         plain_a(dy_hi, dy_lo, Mo, Cout, Cout), bl, ep, Cout, KS * KS * Cin, Mo, 1, dy_lo != nullptr, (hipStream_t)stream,
-        "ig_convk_wgrad", true, 1);
+        "ig_convk_wgrad", true);
 }
 
 // ---- ConvTranspose2d(k=3,s=2,p=1,op=1), NHWC, weight storage Wc[Cout][9][Cin]  (model.py:361-368) ----
@@ -2103,14 +1794,13 @@ int ig_convT_fwd(const void* x_hi, const void* x_lo, const void* w_hi, const voi
     bl.finish();
     EpStore ep{};
     ep.out_hi = (bf16_t*)y_hi, ep.out_lo = (bf16_t*)y_lo, ep.bias = bias, ep.ldo = Cout;
-    IG_REQUIRE(drop_p <= 0.f || (double)B * 4 * H * W * Cout < 4294967296.0, "ig_convT_fwd: dropout needs < 2^32 elements");
     ep.phase_map = 1, ep.H = H, ep.W = W;
     ep.f_hw = make_fdiv(H * W), ep.f_w = make_fdiv(W);
     ep.drop_seed = drop_seed, ep.drop_seed_dev = drop_seed_dev;
     ep.drop_thresh = ig_drop_thresh16(drop_p);
     ep.drop_inv = drop_p > 0.f ? 1.0f / (1.0f - drop_p) : 1.0f;
     return launch_gemm<ConvTFwdALoader, ConvTFwdBLoader, EpStore, false, false>(
-        al, bl, ep, al.Mtot, Cout, 4 * Cin, 4, x_lo != nullptr, (hipStream_t)stream, "ig_convT_fwd", false, conv_version(Cout));
+        al, bl, ep, al.Mtot, Cout, 4 * Cin, 4, x_lo != nullptr, (hipStream_t)stream, "ig_convT_fwd");
 }
 
 // dx (H,W,Cin) = stride-2 gather of dy (2H,2W,Cout) against Wc
@@ -2138,7 +1828,7 @@ int ig_convT_dgrad(const void* dy_hi, const void* dy_lo, const void* w_hi, const
     EpGradStore ep{};
     ep.out_hi = (bf16_t*)dx_hi, ep.out_lo = (bf16_t*)dx_lo, ep.ldo = Cin, ep.mode = 0;
     return launch_gemm<ConvTGradLoader, ConvWgtTRLoader, EpGradStore, false, true>(
-        al, bl, ep, al.Mtot, Cin, 9 * Cout, 1, dy_lo != nullptr, (hipStream_t)stream, "ig_convT_dgrad", false, conv_version(Cin));
+        al, bl, ep, al.Mtot, Cin, 9 * Cout, 1, dy_lo != nullptr, (hipStream_t)stream, "ig_convT_dgrad");
 }
 
 // dWc[Cout][tap][Cin] += sum_{input pixels} dy[shift_tap(p)][co] * x[p][ci]     (blockIdx.z = tap)
@@ -2163,7 +1853,7 @@ int ig_convT_wgrad(const void* dy_hi, const void* dy_lo, const void* x_hi, const
             if (rc == IG_OK && dbias && !fused) return ig_colsum(dy_hi, dy_lo, dbias, 4L * B * H * W, Cout, stream);
             return rc;
         }
-    } else if (direct_x3_env()) {  // split operands: three launches of the bf16 kernel on (hi, hi), (hi, lo), (lo, hi) -- see ig_conv3x3_wgrad
+    } else {  // split operands: three launches of the bf16 kernel on (hi, hi), (hi, lo), (lo, hi) -- see ig_conv3x3_wgrad
         int fused = 0, f2 = 0;
         int rc = ig_convT_wgrad_direct(dy_hi, x_hi, dw, dbias, &fused, B, H, W, Cin, Cout, stream);
         if (rc != IG_ERR_UNSUPPORTED) {
@@ -2185,7 +1875,7 @@ int ig_convT_wgrad(const void* dy_hi, const void* dy_lo, const void* x_hi, const
     EpAtomic ep{dw, 9L * Cin, (long)Cin, 0, nullptr, 0};
     return launch_gemm<ConvTGradLoader, PlainLoader, EpAtomic, true, true>(
         al, plain_b(x_hi, x_lo, Mtot, Cin, Cin), ep, Cout, Cin, Mtot, 9, dy_lo != nullptr, (hipStream_t)stream,
-        "ig_convT_wgrad", true, 1);
+        "ig_convT_wgrad", true);
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 // v8: the forward ("NT", both operands K-contiguous) linear GEMM of the timm Block (pritvhi.py:446-456: qkv / proj /
-// fc1 / fc2) and of the patch embedding as a 256 x 256 x 64 "8-phase" ping-pong kernel for gfx950.
+// fc1 / fc2) and of the patch embedding as a 256 x 256 x 64 "8-phase" kernel for gfx950.
 //
 //   C[m][n] = sum_seg sum_k A_seg[m][k] * B_seg[n][k]      A = activations [M][K], B = nn.Linear weight [N][K]
 //
@@ -50,16 +50,11 @@ namespace {
 
 // Epilogue stores.  Non-temporal stores drain the write burst of 256 CUs faster in isolation (round 4, same-box A/B of two builds at
 // M = 42552: proj 87 -> 72 us, fc1 + gelu' 256 -> 239, d_fc1 164 -> 157, qkv / fc2 unchanged) but over the whole step the gain is gone
-// (44.36 -> 44.28 ms): the consumer of the tile then misses in L2 / MALL.  -DIG_G8_NT builds them all non-temporal (A/B builds); by
-// default only the tensor nobody reads before the backward pass -- gelu' saved by fc1 -- takes the non-temporal path.
+// (44.36 -> 44.28 ms): the consumer of the tile then misses in L2 / MALL.  So only the tensor nobody reads before the backward pass --
+// gelu' saved by fc1 -- takes the non-temporal path.
 template <bool NT = false, typename T>
 __device__ __forceinline__ void g8_store(T* ptr, const T& v) {
-#ifdef IG_G8_NT
-    constexpr bool nt = true;
-#else
-    constexpr bool nt = NT;
-#endif
-    if constexpr (nt) {
+    if constexpr (NT) {
         static_assert(sizeof(T) == 16, "16-byte stores");
         typedef __attribute__((ext_vector_type(4))) unsigned u32x4_t;
         __builtin_nontemporal_store(__builtin_bit_cast(u32x4_t, v), reinterpret_cast<u32x4_t*>(ptr));

@@ -588,9 +588,6 @@ inline int wg8_env() {  // IG_WGRAD8: 0 = off (the BK = 32 ring engine of gemm.h
     const char* e = getenv("IG_WGRAD8");
     return e ? atoi(e) : 1;
 }
-constexpr int wg8_rem_env() { return 1; }  // ragged token splits (uniform-only splits were an A/B arm)
-constexpr int w_rem_aligned_env() { return 1; }  // remainder workgroups in step (the walking remainder was the A/B arm: profiles/r06_gemm8w_xcd_rectangles.txt)
-constexpr int IG_W_DEAL_ENV() { return 1; }  // per-XCD rectangles (the round-3 dealing was the A/B arm: profiles/r06_gemm8w_xcd_rectangles.txt)
 
 struct TileRef {  // one output tile of the launch
     int g;         // GEMM (pointer set)
@@ -668,7 +665,7 @@ int w_run(const WKey& key, const std::vector<TileRef>& tl, int M, int lda2_of_g[
             // * uniform: every tile is cut into ks = C / T token ranges; the (split, tile) pairs are listed split-major and each XCD
             //   (workgroup id % 8) takes a contiguous run, so the workgroups that share an L2 stream the SAME token range of
             //   neighbouring tiles (tiles of one GEMM row share the dy column block).  108 tiles (one Block at D = 768): 216 of 256 CUs.
-            // * with remainder (IG_WGRAD8_REM, default on): the ks main ranges are shortened to c = ceil(T P / C) pairs -- the length
+            // * with remainder: the ks main ranges are shortened to c = ceil(T P / C) pairs -- the length
             //   that balances all C workgroups -- and the last r = P - ks c pairs of every tile go to the R = C - T ks workgroups
             //   left over, which walk the tiles' remainders in tile order (3-4 short segments each, again in step with one another).
             //   Makespan 84 -> 71 pairs at T = 108; the price is one more slab per tile in the fold.
@@ -682,7 +679,7 @@ int w_run(const WKey& key, const std::vector<TileRef>& tl, int M, int lda2_of_g[
             if (ks > P) ks = P;
             bool rem = false;
             int c = 0, r = 0, R = 0, q = 0;
-            if (T <= ncu && wg8_rem_env()) {
+            if (T <= ncu) {
                 c = (int)(((long)T * P + ncu - 1) / ncu);
                 r = P - ks * c, R = ncu - T * ks;
                 if (r > 0 && R > 0) {
@@ -698,7 +695,7 @@ int w_run(const WKey& key, const std::vector<TileRef>& tl, int M, int lda2_of_g[
             // all starting at the same token -- tiles that are neighbours in the (rectangle-ordered) list, so each time step's nr tiles share
             // their operand slabs in step.  r is chosen so that d remainders weigh about one main segment: P = ks c + r with d r ~ c.
             bool aligned = false;
-            if (rem && ((long)T * ks) % 8 == 0 && R % 8 == 0 && w_rem_aligned_env()) {
+            if (rem && ((long)T * ks) % 8 == 0 && R % 8 == 0) {
                 const int nr = R / 8, share = (T + 7) / 8, d = (share + nr - 1) / nr;
                 if (d >= 1 && d <= W_MAXSEG && (long)nr * d * 8 >= T) {
                     int r2 = (int)((P + (ks * d + 1) / 2) / (ks * d + 1));
@@ -752,7 +749,7 @@ int w_run(const WKey& key, const std::vector<TileRef>& tl, int M, int lda2_of_g[
             // XCD x owns a contiguous eighth of the logical workgroup list.  With the remainder workgroups at the END of the list the eighths
             // straddle the token splits (XCD 3: the last 12 tiles of split 0 + the first 20 of split 1 -- nothing shared between them); when the
             // counts divide, every XCD gets an equal run of main segments of ONE split and an equal share of the remainder workgroups instead.
-            if (rem && ((long)T * ks) % 8 == 0 && (wl.size() - (size_t)T * ks) % 8 == 0 && IG_W_DEAL_ENV()) {
+            if (rem && ((long)T * ks) % 8 == 0 && (wl.size() - (size_t)T * ks) % 8 == 0) {
                 const size_t nm = (size_t)T * ks / 8, nr = (wl.size() - (size_t)T * ks) / 8;
                 std::vector<std::vector<SegRef>> w2;
                 for (int x = 0; x < 8; ++x) {
@@ -867,7 +864,7 @@ int ig_wgrad8_group(int n, const void* const* dy_hi, const void* const* dy_lo, c
         // compact rectangle: 27 tiles of fc1's 12 x 3 grid = 9 rows x 3 columns share 9 + 3 operand slabs, 27 of fc2's 3 x 12 grid in
         // row-major order 3 + 12 (round 6; a model of the plan, DESIGN 9: 1.32 -> 1.20 x the algorithmic bytes under ideal L2 sharing)
         const int tR = N[g] >> 8, tC = K[g] >> 8;
-        const bool rows_outer = tR >= tC || !IG_W_DEAL_ENV();
+        const bool rows_outer = tR >= tC;
         for (int o = 0; o < (rows_outer ? tR : tC); ++o)
             for (int i = 0; i < (rows_outer ? tC : tR); ++i) {
                 const int tm = rows_outer ? o : i, tn = rows_outer ? i : o;
@@ -878,7 +875,7 @@ int ig_wgrad8_group(int n, const void* const* dy_hi, const void* const* dy_lo, c
     if (ncu < 8) ncu = 8;
     int dev_ = 0;
     (void)hipGetDevice(&dev_);
-    WKey key = {0, n, M, ncu, split, wg8_rem_env() + 2 * IG_W_DEAL_ENV() + 4 * w_rem_aligned_env(), dev_};
+    WKey key = {0, n, M, ncu, split, dev_};
     for (int g = 0; g < n; ++g) key.push_back(N[g]), key.push_back(K[g]);
     WConv cv{};
     return w_run<0, 4, 2>(key, tl, M, lda2, ldb2, split, args, cv, dws, overwrite, (hipStream_t)stream, "ig_linear_wgrad_group");
@@ -966,7 +963,7 @@ int ig_wgrad8_conv(int kind, const void* dy_hi, const void* dy_lo, const void* x
     cv.f_hw = make_fdiv(H * W), cv.f_w = make_fdiv(W), cv.f_c = make_fdiv(cv.Cg);
     int dev_ = 0;
     (void)hipGetDevice(&dev_);
-    const WKey key = {1 + kind + (swap ? 2 : 0), (long)M, ncu, split, wg8_rem_env(), dev_, H, W, Cin, Cout, BMt, BNt};
+    const WKey key = {1 + kind + (swap ? 2 : 0), (long)M, ncu, split, dev_, H, W, Cin, Cout, BMt, BNt};
     hipStream_t st = (hipStream_t)stream;
     const int M_ = (int)M;
 #define IG_W8C(MODE, TRANS, WHAT)                                                                                                  \

@@ -250,7 +250,7 @@ def rel_l2(a, b):
 def test_train_step_gradients(name, precision):
     """forward(train-mode BN, dropout p=0) + loss + backward: loss, logits and gradients vs the fp64 fixture that
     oracle/gen_golden.py computed with the REFERENCE network (tiny, the model-size Prithvi-100M cases -- D = 768 runs the
-    8-phase / ping-pong / dual-K GEMM engines end to end against reference-generated gradients -- Prithvi-V2-300M:
+    8-phase / dual-K GEMM engines end to end against reference-generated gradients -- Prithvi-V2-300M:
     D = 1024, 24 blocks, 16 heads, the 64-channel head of BASELINE configs[4] -- and the 600M shape family at depth 2:
     D = 1280, 16 heads of 80, patch 14 / 257 tokens, head kernels [5, 5, 5, 7], model.py:154-177)."""
     cfg, sd, net, img, lab = build(name, precision)

@@ -65,7 +65,7 @@ def test_linear_fwd(split, M, N, K):
 
 
 def test_linear_big_shapes_repeatable():
-    """Model-sized GEMMs (the shapes routed to the ping-pong v5 engine): repeated launches are bit-identical (race screen:
+    """Model-sized GEMMs on the generic engines (untransposed dgrad, residual GEMM): repeated launches are bit-identical (race screen:
     an LDS-DMA / barrier ordering bug shows up as rare differing tiles) and agree with an fp32 matmul of the bf16 inputs."""
     M, D = 4300, 768
     # dgrad without elementwise factor: dx[M, K] = dy[M, N] @ w[N, K]

@@ -3,7 +3,7 @@
 // writes) exactly BYTES bytes of a buffer much larger than L2 + Infinity Cache, once:
 //   k_ld16     global_load_dwordx4, 16 B per lane, fully coalesced                      (the documented x2 case)
 //   k_dma128   global_load_lds_dwordx4, one instruction = 8 rows x 128 B  (gemm8: BK = 64 K-contiguous pieces, full lines)
-//   k_dma64    global_load_lds_dwordx4, one instruction = 16 rows x 64 B  (gemm2 / gemm5 at BK = 32: half lines)
+//   k_dma64    global_load_lds_dwordx4, one instruction = 16 rows x 64 B  (gemm2 at BK = 32: half lines)
 //   k_dma256   global_load_lds_dwordx4, one instruction = 4 rows x 256 B  (TR operands: dgrad / wgrad pieces)
 //   k_st16     global_store_dwordx4, 16 B per lane
 // Build + run: hipcc --offload-arch=gfx950 -O3 tools/fetch_calib.hip -o /tmp/fetch_calib ; rocprofv3 --pmc FETCH_SIZE ... -- /tmp/fetch_calib
