@@ -496,7 +496,7 @@ __global__ __launch_bounds__(256) void conv4_kernel(C8Params p) {
     const unsigned dA = PAIR ? (unsigned)((const char*)p.a[1] - (const char*)p.a[0]) : 0u;  // one descriptor spans hi and lo (the host checks)
     const unsigned abytes = p.a_bytes + dA;
     const char* abase = (const char*)p.a[0];
-    // lane constants of the asm blocks (gen_gemm4.py: c_setup / cp_setup)
+    // lane constants of the asm blocks (gen_gemm4.py: Cv.setup)
     const unsigned sc = (lane & 7) ^ ((lane >> 3) & 7);  // source chunk of this lane's LDS chunk; paired: chunks 0-3 = hi, 4-7 = lo of the same 32 elements
     const unsigned c16 = PAIR ? ((sc & 3) << 4) + (sc >= 4 ? (unsigned)((const char*)p.b[1] - (const char*)p.b[0]) : 0u) : sc << 4;
     const unsigned aloadd = PAIR && sc >= 4 ? dA : 0u;

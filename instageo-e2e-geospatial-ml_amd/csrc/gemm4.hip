@@ -38,7 +38,7 @@ __device__ __forceinline__ void g4_store(T* ptr, const T& v) {
     }
 }
 
-// NSEG = 1: plain bf16 operands.  NSEG = 2: the split precision mode (bf16x3) on PAIRED K-tiles (gen_gemm4.py, second half): operands are
+// NSEG = 1: plain bf16 operands.  NSEG = 2: the split precision mode (bf16x3) on PAIRED K-tiles (gen_gemm4.py: the paired shape): operands are
 // (hi, lo) pairs with lo a 32-bit distance above hi, a K-tile covers 32 reduction elements with hi and lo side by side in the LDS row, three
 // products of 64 MFMAs per K-tile (hi hi, hi(B) lo(A), lo(B) hi(A)); outputs are split again (kinds 0, 2) or fp32 (kind 1).
 template <int KIND, int ACT, bool DACT, int NSEG = 1>
@@ -62,7 +62,7 @@ __global__ __launch_bounds__(256) void gemm4_kernel(G8Params p) {
     const int lda2 = (int)(p.lda * 2), ldb2 = (int)(p.ldb * 2);
     const int nk = PAIR ? p.K >> 5 : p.K >> 6, npair = (nk >> 1) - 2;
 
-    // lane constants of the asm blocks (gen_gemm4.py: setup): DMA row and source chunk, fragment read bases, DMA destination of this wave
+    // lane constants of the asm blocks (gen_gemm4.py: Lin.setup): DMA row and source chunk, fragment read bases, DMA destination of this wave
     const unsigned rowv = wave * 64 + (lane >> 3);
     const unsigned sc = (lane & 7) ^ ((lane >> 3) & 7);  // source chunk of this lane's LDS chunk; paired: chunks 0-3 = hi, 4-7 = lo of the same 32 elements
     const unsigned c16 = sc << 4;

@@ -432,7 +432,7 @@ __global__ __launch_bounds__(256) void gemm4w_kernel(const WSeg* __restrict__ se
     const WSeg* __restrict__ my = segs + (size_t)blockIdx.x * W_MAXSEG;
     if (my[0].nkt <= 0) return;
     const unsigned lds_base = (unsigned)(uintptr_t)(lds_char_ptr)smem;
-    // lane constants of the asm blocks (gen_gemm4.py: w_setup): fragment reads as in gemm8w_kernel (16 lanes read 4 tokens x 16 columns)
+    // lane constants of the asm blocks (gen_gemm4.py: Wg.setup): fragment reads as in gemm8w_kernel (16 lanes read 4 tokens x 16 columns)
     const unsigned g4 = lane >> 4, li = lane & 15, qq = li >> 2, pp = li & 3;
     const unsigned rkey5 = (qq | ((g4 & 1) << 2)) << 5;
     const unsigned tbase = lds_base + (8 * g4 + qq) * 256 + pp * 8;

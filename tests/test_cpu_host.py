@@ -347,6 +347,93 @@ def test_m0_is_only_written_by_the_lds_dma_helpers():
             assert not bad, (name, bad[:5])
 
 
+# ---- csrc/gen_gemm4.py: helpers of the generator tests below
+_G4_MF = "v_mfma_f32_16x16x32_bf16"
+_G4_MF_OPERANDS = _G4_MF + r" a\[\d+:\d+\], v\[(\d+):\d+\], v\[(\d+):\d+\]"
+
+
+def _g4_run(out, *args):
+    """run the generator the way the Makefile does: output path, then key=value arguments"""
+    return subprocess.run([sys.executable, os.path.join(PKG, "csrc", "gen_gemm4.py"), str(out), *args], capture_output=True, text=True)
+
+
+def _g4_generate(tmp_path, *args):
+    out = tmp_path / "g4.inc"
+    r = _g4_run(out, *args)
+    assert r.returncode == 0, r.stderr
+    return out.read_text()
+
+
+def _g4_macros(text):
+    """macro name -> body (everything behind the name, continuation lines included); "readout" -> the C++ helpers behind the last macro"""
+    m = dict(re.findall(r"^#define (G4\w+)((?:.*\\\n)*.*)$", text, re.M))
+    m["readout"] = text[text.index("__device__"):]
+    return m
+
+
+def _g4_block(text, name):
+    """the instructions of an asm macro"""
+    return re.findall(r'"([^"]*?)\\n\\t"', _g4_macros(text)[name])
+
+
+def _g4_check_regs(ins, clob):
+    """every VGPR / SGPR the instructions name lies inside the clobber list, which declares all AGPRs, M0, SCC and memory; returns the VGPRs"""
+    cv = {int(x) for x in re.findall(r'"v(\d+)"', clob)}
+    cs = {int(x) for x in re.findall(r'"s(\d+)"', clob)}
+    assert {int(x) for x in re.findall(r'"a(\d+)"', clob)} == set(range(256)) and '"m0"' in clob and '"scc"' in clob and '"memory"' in clob
+    for i in ins:
+        body = re.sub(r"%\[[a-z0-9_]+\]", "", i)
+        for lo, hi in re.findall(r"\bv\[(\d+):(\d+)\]", body):
+            assert set(range(int(lo), int(hi) + 1)) <= cv, i
+        for r in re.findall(r"\bv(\d+)\b", body):
+            assert int(r) in cv, i
+        for lo, hi in re.findall(r"\bs\[(\d+):(\d+)\]", body):
+            assert set(range(int(lo), int(hi) + 1)) <= cs, i
+        for r in re.findall(r"\bs(\d+)\b", body):
+            assert int(r) in cs, i
+    return cv
+
+
+def _g4_check_m0_spacing(ins, prefix):
+    """every LDS-DMA issue (mnemonic prefix) has its own M0 write two instructions earlier and something else in between (the wait state M0
+    needs); returns the issues' positions"""
+    dma = [k for k, i in enumerate(ins) if i.startswith(prefix)]
+    for k in dma:
+        assert ins[k - 2].startswith("s_add_u32 m0, ") and not ins[k - 1].startswith(("s_add_u32 m0", "buffer_load", "global_load")), ins[k - 2:k + 1]
+    return dma
+
+
+def _g4_halves(ins):
+    """the stream split behind the waits that end a half"""
+    out, half = [], []
+    for i in ins:
+        half.append(i)
+        if i == "s_waitcnt lgkmcnt(0)":
+            out.append(half)
+            half = []
+    return out
+
+
+def _g4_products(ins, per):
+    """the stream from the first to the last MFMA of every run of `per` MFMAs"""
+    mfk = [k for k, i in enumerate(ins) if i.startswith(_G4_MF)]
+    return [ins[mfk[b]:mfk[b + per - 1] + 1] for b in range(0, len(mfk), per)]
+
+
+def _g4_check_reads_spare_consumed_sets(groups, rd):
+    """in every group (a half or a product) no read (mnemonic rd) writes a fragment block that the group's own MFMAs consume"""
+    for n, g in enumerate(groups):
+        used = set()
+        for i in g:
+            m = re.match(_G4_MF_OPERANDS, i)
+            if m:
+                used |= {int(m.group(1)), int(m.group(2))}
+        for i in g:
+            m = re.match(rd + r" v\[(\d+):", i)
+            if m:
+                assert int(m.group(1)) // 4 * 4 not in used, (i, n)
+
+
 def test_gemm4w_generator_emits_a_consistent_instruction_stream(tmp_path):
     """The weight-gradient forms of csrc/gen_gemm4.py (gemm4w_kernel in gemm8w.hip: plain, short-segment and paired blocks).  Structural
     invariants of the generated text:
@@ -357,42 +444,14 @@ def test_gemm4w_generator_emits_a_consistent_instruction_stream(tmp_path):
     * paired block: 6 iterations of 192 MFMAs in three products, 64 reads per iteration (+ 48 at entry), 16 DMA issues, and no product's reads
       write a quarter set its own MFMAs consume;
     * every named register lies inside the clobber list; the clobbered VGPR range leaves the low registers to the compiler."""
-    import re
-    import subprocess
-
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = tmp_path / "g4.inc"
-    subprocess.run([sys.executable, os.path.join(root, "instageo-e2e-geospatial-ml_amd", "csrc", "gen_gemm4.py"), str(out)], check=True)
-    text = out.read_text()
-
-    def block(name, end):
-        return re.findall(r'"([^"]*?)\\n\\t"', text[text.index("#define " + name):text.index("#define " + end)])
-
-    def check_regs(ins, clob):
-        cv = {int(x) for x in re.findall(r'"v(\d+)"', clob)}
-        cs = {int(x) for x in re.findall(r'"s(\d+)"', clob)}
-        assert {int(x) for x in re.findall(r'"a(\d+)"', clob)} == set(range(256)) and '"m0"' in clob and '"scc"' in clob and '"memory"' in clob
-        for i in ins:
-            body = re.sub(r"%\[[a-z0-9_]+\]", "", i)
-            for lo, hi in re.findall(r"\bv\[(\d+):(\d+)\]", body):
-                assert set(range(int(lo), int(hi) + 1)) <= cv, i
-            for r in re.findall(r"\bv(\d+)\b", body):
-                assert int(r) in cv, i
-            for lo, hi in re.findall(r"\bs\[(\d+):(\d+)\]", body):
-                assert set(range(int(lo), int(hi) + 1)) <= cs, i
-            for r in re.findall(r"\bs(\d+)\b", body):
-                assert int(r) in cs, i
-        return cv
+    text = _g4_generate(tmp_path)
 
     def check_dma(ins, n):
-        dma = [k for k, i in enumerate(ins) if i.startswith("buffer_load_dwordx4")]
-        assert len(dma) == n
-        for k in dma:
-            assert ins[k].endswith("offen lds") and ins[k - 2].startswith("s_add_u32 m0, ") and not ins[k - 1].startswith(("s_add_u32 m0", "buffer_load")), ins[k - 2:k + 1]
+        dma = _g4_check_m0_spacing(ins, "buffer_load_dwordx4")
+        assert len(dma) == n and all(ins[k].endswith("offen lds") for k in dma)
 
-    MF, RD = "v_mfma_f32_16x16x32_bf16", "ds_read_b64_tr_b16"
-    wclob = text[text.index("#define G4W_CLOBBERS"):].split("\n", 1)[0]
-    seg, short, pro = block("G4W_ASM_SEG", "G4W_ASM_SEG_SHORT"), block("G4W_ASM_SEG_SHORT", "G4W_CLOBBERS"), block("G4W_ASM_PROLOGUE", "G4W_ASM_SEG")
+    MF, RD = _G4_MF, "ds_read_b64_tr_b16"
+    seg, short, pro = _g4_block(text, "G4W_ASM_SEG"), _g4_block(text, "G4W_ASM_SEG_SHORT"), _g4_block(text, "G4W_ASM_PROLOGUE")
     for ins, iters in ((seg, 6), (short, 2)):
         mf = [i for i in ins if i.startswith(MF)]
         assert len(mf) == iters * 128 and all(i.endswith(", 0") for i in mf[:64]) and sum(1 for i in mf if i.endswith(", 0")) == 64
@@ -409,43 +468,20 @@ def test_gemm4w_generator_emits_a_consistent_instruction_stream(tmp_path):
         mfk = [k for k, i in enumerate(ins) if i.startswith(MF)]
         assert flags[1] < mfk[0] and mfk[(iters - 2) * 128 - 1] < flags[2] < flags[3] < mfk[(iters - 2) * 128] if iters > 2 else flags[3] < mfk[0]
     check_dma(pro, 32)
-    cv = check_regs(seg + short + pro, wclob)
+    cv = _g4_check_regs(seg + short + pro, _g4_macros(text)["G4W_CLOBBERS"])
     assert min(cv) >= 48  # the compiler keeps v0 .. v47 at least
-    # a half's reads never write the fragment set its own MFMAs consume
-    half = []
-    for i in seg:
-        half.append(i)
-        if i == "s_waitcnt lgkmcnt(0)":
-            used = set()
-            for j in half:
-                m = re.match(MF + r" a\[\d+:\d+\], v\[(\d+):\d+\], v\[(\d+):\d+\]", j)
-                if m:
-                    used |= {int(m.group(1)), int(m.group(2))}
-            for j in half:
-                m = re.match(RD + r" v\[(\d+):(\d+)\]", j)
-                if m and used:
-                    assert int(m.group(1)) // 4 * 4 not in used, j
-            half = []
+    _g4_check_reads_spare_consumed_sets(_g4_halves(seg), RD)  # a half's reads never write the fragment set its own MFMAs consume
     # ---- paired form
-    pclob = text[text.index("#define G4WP_CLOBBERS"):].split("\n", 1)[0]
-    pseg, ppro = block("G4WP_ASM_SEG", "G4WP_CLOBBERS"), block("G4WP_ASM_PROLOGUE", "G4WP_ASM_SEG")
+    pseg, ppro = _g4_block(text, "G4WP_ASM_SEG"), _g4_block(text, "G4WP_ASM_PROLOGUE")
     pmf = [k for k, i in enumerate(pseg) if i.startswith(MF)]
     assert len(pmf) == 6 * 192 and all(pseg[k].endswith(", 0") for k in pmf[:64]) and sum(1 for k in pmf if pseg[k].endswith(", 0")) == 64
     assert sum(1 for i in pseg if i.startswith(RD)) == 48 + 6 * 64
     check_dma(pseg, 6 * 16)
     check_dma(ppro, 32)
     assert sum(1 for i in pseg if i == "s_waitcnt vmcnt(8)") == 6 and sum(1 for i in pseg if i == "s_barrier") == 7
-    pcv = check_regs(pseg + ppro, pclob)
+    pcv = _g4_check_regs(pseg + ppro, _g4_macros(text)["G4WP_CLOBBERS"])
     assert min(pcv) >= 32
-    for b in range(0, len(pmf), 64):
-        used = set()
-        for k in pmf[b:b + 64]:
-            m = re.match(MF + r" a\[\d+:\d+\], v\[(\d+):\d+\], v\[(\d+):\d+\]", pseg[k])
-            used |= {int(m.group(1)), int(m.group(2))}
-        for i in pseg[pmf[b]:pmf[b + 63] + 1]:
-            m = re.match(RD + r" v\[(\d+):", i)
-            if m:
-                assert int(m.group(1)) // 4 * 4 not in used, (i, b // 64)
+    _g4_check_reads_spare_consumed_sets(_g4_products(pseg, 64), RD)
 
 
 def test_conv4_generator_emits_a_consistent_instruction_stream(tmp_path):
@@ -454,50 +490,23 @@ def test_conv4_generator_emits_a_consistent_instruction_stream(tmp_path):
     three instructions that build its offset from the row offset, the row's inverted tap mask and this K-tile's table entry -- and NI plain B
     pieces; one table read per iteration, behind the decode of the previous entry; the last pair takes the NEXT tile's rows; every named
     register lies inside the clobber list."""
-    import re
-    import subprocess
-
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = tmp_path / "g4.inc"
-    subprocess.run([sys.executable, os.path.join(root, "instageo-e2e-geospatial-ml_amd", "csrc", "gen_gemm4.py"), str(out)], check=True)
-    text = out.read_text()
+    text = _g4_generate(tmp_path)
     for NI in (6, 3):
         _check_conv4_blocks(text, NI)
     # ---- the paired split form (256 x 192 tile): three products of 48 MFMAs per 32-element K-tile on five quarter sets
-    import re as _re
-    pt = _re.findall(r'"([^"]*?)\\n\\t"', text[text.index("#define G4CP6_ASM_TILE"):text.index("#define G4CP6_CLOBBERS")])
-    pclob = text[text.index("#define G4CP6_CLOBBERS"):].split("\n", 1)[0]
-    MF = "v_mfma_f32_16x16x32_bf16"
-    pmf = [k for k, i in enumerate(pt) if i.startswith(MF)]
+    pt = _g4_block(text, "G4CP6_ASM_TILE")
+    pmf = [k for k, i in enumerate(pt) if i.startswith(_G4_MF)]
     assert len(pmf) == 6 * 3 * 48 and all(pt[k].endswith(", 0") for k in pmf[:48]) and sum(1 for k in pmf if pt[k].endswith(", 0")) == 48
     assert sum(1 for i in pt if i.startswith("ds_read_b128")) == (8 + 8 + 6) + 6 * (6 + 8 + 6 + 8)
     assert sum(1 for i in pt if i.startswith("buffer_load_dwordx4")) == 6 * 8 and sum(1 for i in pt if i.startswith("global_load_lds_dwordx4")) == 6 * 6
     assert sum(1 for i in pt if i.startswith("ds_read_b32")) == 7 and sum(1 for i in pt if i == "s_barrier") == 7
-    pcv = {int(x) for x in _re.findall(r'"v(\d+)"', pclob)}
-    for i in pt:
-        body = _re.sub(r"%\[[a-z0-9_]+\]", "", i)
-        for lo, hi in _re.findall(r"\bv\[(\d+):(\d+)\]", body):
-            assert set(range(int(lo), int(hi) + 1)) <= pcv, i
-        for r in _re.findall(r"\bv(\d+)\b", body):
-            assert int(r) in pcv, i
-    for b in range(0, len(pmf), 48):  # a product's reads never write a quarter set its own MFMAs consume
-        used = set()
-        for k in pmf[b:b + 48]:
-            m = _re.match(MF + r" a\[\d+:\d+\], v\[(\d+):\d+\], v\[(\d+):\d+\]", pt[k])
-            used |= {int(m.group(1)), int(m.group(2))}
-        for i in pt[pmf[b]:pmf[b + 47] + 1]:
-            m = _re.match(r"ds_read_b128 v\[(\d+):", i)
-            if m:
-                assert int(m.group(1)) not in used, (i, b // 48)
+    _g4_check_regs(pt, _g4_macros(text)["G4CP6_CLOBBERS"])
+    _g4_check_reads_spare_consumed_sets(_g4_products(pt, 48), "ds_read_b128")  # a product's reads never write a quarter set its own MFMAs consume
 
 
 def _check_conv4_blocks(text, NI):
-    import re
-
-    tile = re.findall(r'"([^"]*?)\\n\\t"', text[text.index("#define G4C%d_ASM_TILE" % NI):text.index("#define G4C%d_CLOBBERS" % NI)])
-    pro = re.findall(r'"([^"]*?)\\n\\t"', text[text.index("#define G4C%d_ASM_PROLOGUE" % NI):text.index("#define G4C%d_ASM_TILE" % NI)])
-    clob = text[text.index("#define G4C%d_CLOBBERS" % NI):].split("\n", 1)[0]
-    MF = "v_mfma_f32_16x16x32_bf16"
+    tile, pro = _g4_block(text, "G4C%d_ASM_TILE" % NI), _g4_block(text, "G4C%d_ASM_PROLOGUE" % NI)
+    MF = _G4_MF
     mf = [i for i in tile if i.startswith(MF)]
     H = 8 * NI
     assert len(mf) == 6 * 2 * H and all(i.endswith(", 0") for i in mf[:H]) and sum(1 for i in mf if i.endswith(", 0")) == H
@@ -506,11 +515,9 @@ def _check_conv4_blocks(text, NI):
         assert dst == sorted([(mi * 8 + ni) * 4 for mi in range(8) for ni in range(NI)] * 2)
     assert sum(1 for i in tile if i.startswith("ds_read_b128")) == (8 + NI) + 6 * 2 * (8 + NI)
     assert sum(1 for i in tile if i.startswith("ds_read_b32")) == 1 + 6 and sum(1 for i in pro if i.startswith("ds_read_b32")) == 2
-    ga = [k for k, i in enumerate(tile) if i.startswith("buffer_load_dwordx4")]
-    gb = [k for k, i in enumerate(tile) if i.startswith("global_load_lds_dwordx4")]
+    ga = _g4_check_m0_spacing(tile, "buffer_load_dwordx4")
+    gb = _g4_check_m0_spacing(tile, "global_load_lds_dwordx4")
     assert len(ga) == 6 * 8 and len(gb) == 6 * NI
-    for k in ga + gb:
-        assert tile[k - 2].startswith("s_add_u32 m0, ") and not tile[k - 1].startswith(("s_add_u32 m0", "buffer_load", "global_load")), tile[k - 2:k + 1]
     for n, k in enumerate(ga):  # the piece's offset register is written by bfe -> lshl_add -> add, in that order, before the issue
         reg = re.match(r"buffer_load_dwordx4 (v\d+),", tile[k]).group(1)
         ops3 = [i for i in tile[:k] if re.match(r"v_(bfe_u32|lshl_add_u32|add_u32) " + reg + ",", i)][-3:]
@@ -518,19 +525,7 @@ def _check_conv4_blocks(text, NI):
         nxt = n >= 4 * 8  # the last pair gathers the next tile's rows
         assert ("%[imn" in ops3[0]) == nxt and ("%[ron" in ops3[2]) == nxt, ops3
     assert sum(1 for i in tile if i == "s_waitcnt vmcnt(8)") == 6 and sum(1 for i in tile if i == "s_barrier") == 7
-    cv = {int(x) for x in re.findall(r'"v(\d+)"', clob)}
-    cs = {int(x) for x in re.findall(r'"s(\d+)"', clob)}
-    assert {int(x) for x in re.findall(r'"a(\d+)"', clob)} == set(range(256)) and '"m0"' in clob and '"scc"' in clob
-    for i in tile + pro:
-        body = re.sub(r"%\[[a-z0-9_]+\]", "", i)
-        for lo, hi in re.findall(r"\bv\[(\d+):(\d+)\]", body):
-            assert set(range(int(lo), int(hi) + 1)) <= cv, i
-        for r in re.findall(r"\bv(\d+)\b", body):
-            assert int(r) in cv, i
-        for lo, hi in re.findall(r"\bs\[(\d+):(\d+)\]", body):
-            assert set(range(int(lo), int(hi) + 1)) <= cs, i
-        for r in re.findall(r"\bs(\d+)\b", body):
-            assert int(r) in cs, i
+    _g4_check_regs(tile + pro, _g4_macros(text)["G4C%d_CLOBBERS" % NI])
 
 
 def test_split_tensors_are_one_allocation_with_lo_above_hi():
@@ -584,85 +579,99 @@ def test_gemm4_generator_emits_a_consistent_instruction_stream(tmp_path):
       between them, one `vmcnt(8)` + one `s_barrier` (+ the entry's `vmcnt(0)` + barrier);
     * every explicitly named VGPR / SGPR / AGPR lies inside the clobber list, M0 and SCC are declared, and a fragment register is never the
       destination of a read in the half whose MFMAs consume it."""
-    import re
-    import subprocess
-
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = tmp_path / "g4.inc"
-    subprocess.run([sys.executable, os.path.join(root, "instageo-e2e-geospatial-ml_amd", "csrc", "gen_gemm4.py"), str(out)], check=True)
-    text = out.read_text()
-    tile = text[text.index("#define G4_ASM_TILE"):text.index("#define G4_CLOBBERS")]
-    pro = text[text.index("#define G4_ASM_PROLOGUE"):text.index("#define G4_ASM_TILE")]
-    clob = text[text.index("#define G4_CLOBBERS"):].split("\n", 1)[0]
-    ins = re.findall(r'"([^"]*?)\\n\\t"', tile)
-    mf = [i for i in ins if i.startswith("v_mfma_f32_16x16x32_bf16")]
+    text = _g4_generate(tmp_path)
+    ins, pins = _g4_block(text, "G4_ASM_TILE"), _g4_block(text, "G4_ASM_PROLOGUE")
+    mf = [i for i in ins if i.startswith(_G4_MF)]
     assert len(mf) == 6 * 128
     assert sum(1 for i in mf if i.endswith(", 0")) == 64 and all(i.endswith(", 0") for i in mf[:64])
     for it in range(6):
-        dst = [re.match(r"v_mfma_f32_16x16x32_bf16 a\[(\d+):(\d+)\]", i).group(1) for i in mf[it * 128:(it + 1) * 128]]
+        dst = [re.match(_G4_MF + r" a\[(\d+):(\d+)\]", i).group(1) for i in mf[it * 128:(it + 1) * 128]]
         assert sorted(map(int, dst)) == sorted([4 * b for b in range(64)] * 2)
     assert sum(1 for i in ins if i.startswith("ds_read_b128")) == 16 + 6 * 32
-    dma = [k for k, i in enumerate(ins) if i.startswith("global_load_lds_dwordx4")]
-    assert len(dma) == 6 * 16
-    for k in dma:  # M0 write two instructions earlier, something else in between (the wait state M0 needs)
-        assert ins[k - 2].startswith("s_add_u32 m0, ") and not ins[k - 1].startswith(("s_add_u32 m0", "global_load_lds")), ins[k - 2:k + 1]
+    assert len(_g4_check_m0_spacing(ins, "global_load_lds_dwordx4")) == 6 * 16
     assert sum(1 for i in ins if i == "s_waitcnt vmcnt(8)") == 6 and sum(1 for i in ins if i == "s_waitcnt vmcnt(0)") == 1
     assert sum(1 for i in ins if i == "s_barrier") == 7
-    pins = re.findall(r'"([^"]*?)\\n\\t"', pro)
     assert sum(1 for i in pins if i.startswith("global_load_lds_dwordx4")) == 32  # K-tiles 0 and 1 of the workgroup's first tile
-    cv = {int(x) for x in re.findall(r'"v(\d+)"', clob)}
-    cs = {int(x) for x in re.findall(r'"s(\d+)"', clob)}
-    ca = {int(x) for x in re.findall(r'"a(\d+)"', clob)}
-    assert ca == set(range(256)) and '"m0"' in clob and '"scc"' in clob and '"memory"' in clob
-    for i in ins + pins:
-        body = re.sub(r"%\[[a-z0-9_]+\]", "", i)
-        for lo, hi in re.findall(r"\bv\[(\d+):(\d+)\]", body):
-            assert set(range(int(lo), int(hi) + 1)) <= cv, i
-        for r in re.findall(r"\bv(\d+)\b", body):
-            assert int(r) in cv, i
-        for lo, hi in re.findall(r"\bs\[(\d+):(\d+)\]", body):
-            assert set(range(int(lo), int(hi) + 1)) <= cs, i
-        for r in re.findall(r"\bs(\d+)\b", body):
-            assert int(r) in cs, i
+    _g4_check_regs(ins + pins, _g4_macros(text)["G4_CLOBBERS"])
     # ---- the paired form (split precision mode): three products per K-tile, five quarter sets
-    ptile = text[text.index("#define G4P_ASM_TILE"):text.index("#define G4P_CLOBBERS")]
-    pclob = text[text.index("#define G4P_CLOBBERS"):].split("\n", 1)[0]
-    pin = re.findall(r'"([^"]*?)\\n\\t"', ptile)
-    pmf = [k for k, i in enumerate(pin) if i.startswith("v_mfma_f32_16x16x32_bf16")]
+    pin = _g4_block(text, "G4P_ASM_TILE")
+    pmf = [k for k, i in enumerate(pin) if i.startswith(_G4_MF)]
     assert len(pmf) == 6 * 192 and all(pin[k].endswith(", 0") for k in pmf[:64]) and sum(1 for k in pmf if pin[k].endswith(", 0")) == 64
     assert sum(1 for i in pin if i.startswith("ds_read_b128")) == 24 + 6 * 32 and sum(1 for i in pin if i.startswith("global_load_lds_dwordx4")) == 6 * 16
     assert sum(1 for i in pin if i == "s_waitcnt vmcnt(8)") == 6 and sum(1 for i in pin if i == "s_barrier") == 7
-    pcv = {int(x) for x in re.findall(r'"v(\d+)"', pclob)}
-    for i in pin:
-        body = re.sub(r"%\[[a-z0-9_]+\]", "", i)
-        for lo, hi in re.findall(r"\bv\[(\d+):(\d+)\]", body):
-            assert set(range(int(lo), int(hi) + 1)) <= pcv, i
-        for r in re.findall(r"\bv(\d+)\b", body):
-            assert int(r) in pcv, i
-    for b in range(0, len(pmf), 64):  # a product's reads never write a quarter set its own MFMAs consume
-        lo_k, hi_k = pmf[b], pmf[b + 63]
-        used = set()
-        for k in pmf[b:b + 64]:
-            m = re.match(r"v_mfma_f32_16x16x32_bf16 a\[\d+:\d+\], v\[(\d+):\d+\], v\[(\d+):\d+\]", pin[k])
-            used |= {int(m.group(1)), int(m.group(2))}
-        for i in pin[lo_k:hi_k + 1]:
-            m = re.match(r"ds_read_b128 v\[(\d+):\d+\]", i)
-            if m:
-                assert int(m.group(1)) not in used, (i, b // 64)
-    # a half's reads never write the fragment set its MFMAs consume: split the stream at the waits that end a half
-    half, halves = [], []
-    for i in ins:
-        half.append(i)
-        if i == "s_waitcnt lgkmcnt(0)":
-            halves.append(half)
-            half = []
-    for h in halves:
-        used = set()
-        for i in h:
-            m = re.match(r"v_mfma_f32_16x16x32_bf16 a\[\d+:\d+\], v\[(\d+):\d+\], v\[(\d+):\d+\]", i)
-            if m:
-                used |= {int(m.group(1)), int(m.group(2))}
-        for i in h:
-            m = re.match(r"ds_read_b128 v\[(\d+):\d+\]", i)
-            if m and used:
-                assert int(m.group(1)) not in used, (i, sorted(used)[:4])
+    _g4_check_regs(pin, _g4_macros(text)["G4P_CLOBBERS"])
+    _g4_check_reads_spare_consumed_sets(_g4_products(pin, 64), "ds_read_b128")  # a product's reads never write a quarter set its own MFMAs consume
+    _g4_check_reads_spare_consumed_sets(_g4_halves(ins), "ds_read_b128")        # a half's reads never write the fragment set its MFMAs consume
+
+
+# SHA-256 of every macro body of the DEFAULT configuration (and of the accumulator read-out helpers), recorded from the generator as it stood
+# before its skeleton was folded into one weaver and one loop builder.
+_G4_DEFAULT_DIGESTS = {
+    "G4_ASM_PROLOGUE": "0c3900fc2351b5abb73c50c952ef5906847624b835c2542911d6ecdf8bf47c78",
+    "G4_ASM_TILE": "388366dab4735d6c8dcb6235b680ed67bcaeb285ece758f0fcce235fab981e98",
+    "G4_CLOBBERS": "e3c2048ae4a9f916dd90a790adea04361d4807e190699bed6ebc055b30945de1",
+    "G4P_ASM_PROLOGUE": "ec266d47e2a1f6d81d8319e8f147d61bb800b01028c69b3012875d1b45cf4afe",
+    "G4P_ASM_TILE": "e5cef16095b057b4433e5e9c7f9714fd7a2ba881fb7df898cd5eb9d77e1173de",
+    "G4P_CLOBBERS": "50639c1b4bbf8e40c059d5688bd1ca6f3a338caf8d1e77b2fd5190f8ad007ddd",
+    "G4W_ASM_PROLOGUE": "1a615b233a53c819a23a016879593cd120d9095793bf8adf3316077947077332",
+    "G4W_ASM_SEG": "9affd143f25fb478f5459f2a2b073214e195cc5b6e89697105943c68ab9a14cc",
+    "G4W_ASM_SEG_SHORT": "8be5c51f5e09de79212be07d5f323852cb457f3d1700c3aafa56836ea0d672ee",
+    "G4W_CLOBBERS": "321a3d6f9b005404f5504a74425ccfe320a6c72f3ad66912e238a9e28788eaea",
+    "G4WP_ASM_PROLOGUE": "df70daee55af66cbb19bee160b5214eacf3c8a715f84f067977745682c8212c1",
+    "G4WP_ASM_SEG": "45a24078015173dbf9ce4bc651763d425e587d62b6237df113db41cda2fc9929",
+    "G4WP_CLOBBERS": "95b0b9a3e0f409b8001cbdf6bf71b33e7c80b9d59b2ee236f7f4a47fd3fa495b",
+    "G4C6_ASM_PROLOGUE": "d8f6e17da763e6fecf014d3c3f215537e6f379200693032c4e545c2329c49f7e",
+    "G4C6_ASM_TILE": "ba37dbae0603bfe70fb72952072998be2a4240f0ff63ce9f1e9997725ea29825",
+    "G4C6_CLOBBERS": "a284efeba757f2dcc28eb59f988b8cc951a1daa381d7629046309e4eefea6acb",
+    "G4C3_ASM_PROLOGUE": "074f311f7bb51734f42e983d39b3b5ca9a473bdd7d0f01997c6e1c3616bdef5f",
+    "G4C3_ASM_TILE": "6c998deb6ce5503f606f74d7c55280f0633d3c85d547ca90be83d2f22525e37b",
+    "G4C3_CLOBBERS": "e46c4fe36239dd60f912cffc95faaec6f7684cd50b78a6a40622e830d2a7c369",
+    "G4CP6_ASM_PROLOGUE": "29b1eef00fb0a7e581fb48d7a72e775456ed90526e481876ad3b9fe22b615da4",
+    "G4CP6_ASM_TILE": "48252b6337af9dc920b89009e2091d9d20e7ee9cf57a5ac80a9fd2d1ef2d35c6",
+    "G4CP6_CLOBBERS": "745a1c99db68b6ec16f555d3b117e7f58335d4fa0d021c9f6d869ce5dd114bba",
+    "G4CP3_ASM_PROLOGUE": "844a599c318b1532d1b22657399900fe0dd9374ec12b98b32e35cad862865355",
+    "G4CP3_ASM_TILE": "c2bd80f2d79abb728f5337c9cfa37d7cdbdcf59cc146f20a3057457aab773d11",
+    "G4CP3_CLOBBERS": "6926fdebb67ce4147779761cd33c8460e17ec62e4da8204a88c1c89e633cf216",
+    "readout": "e8c0d5c79d23e481ca505130322d4d18eb172367db3e00b7e70701ba15ea60fc",
+}
+
+
+def test_gemm4_generator_default_output_is_pinned(tmp_path):
+    """The default output of csrc/gen_gemm4.py is the schedule every measurement in profiles/ and DESIGN.md was taken with: the same macros, in
+    the same order, each with the recorded body.  A wrong weave position or a register missing from a clobber list is silent corruption, so a
+    change of the emitted text must be deliberate: a digest in `_G4_DEFAULT_DIGESTS` is updated ONLY together with a measurement of the new
+    schedule (and the GPU tests of the engine it belongs to), never to make this test pass after an edit of the generator."""
+    import hashlib
+
+    macros = _g4_macros(_g4_generate(tmp_path))
+    assert list(macros) == list(_G4_DEFAULT_DIGESTS)
+    changed = [k for k, v in macros.items() if hashlib.sha256(v.encode()).hexdigest() != _G4_DEFAULT_DIGESTS[k]]
+    assert not changed, changed
+
+
+def test_gemm4_generator_configuration_keys(tmp_path):
+    """`key=value` arguments of csrc/gen_gemm4.py (tools/gemm4_sweep.sh, tools/gemm4w_sweep.sh): an unknown key is an error that names the key
+    (a typo in a sweep would otherwise measure the default schedule); every documented key changes the body of at least one macro; and the
+    timing ablations hold in EVERY form: with abl_dma + abl_rd a tile / segment block keeps all its MFMAs and has no fragment read and no
+    LDS-DMA issue behind its entry reads, with abl_vmw + abl_bar only the entry's barrier is left and no counted vmcnt wait."""
+    r = _g4_run(tmp_path / "typo.inc", "rd_evry=2")
+    assert r.returncode != 0 and "rd_evry" in r.stderr
+    base_text = _g4_generate(tmp_path)
+    base = _g4_macros(base_text)
+    for arg in ("rd_every=2", "rd_at=1", "dm_every=7", "dm_at=4", "w_rd_at=16", "w_rd_num=1", "w_rd_den=2", "w_dm_at=2", "w_dm_every=4",
+                "wp_rd_num=3", "wp_rd_den=2", "abl_rd=1", "abl_dma=1", "abl_vmw=1", "abl_bar=1"):
+        m = _g4_macros(_g4_generate(tmp_path, arg))
+        assert list(m) == list(base) and any(m[k] != base[k] for k in base), arg
+    loops = [k for k in base if k.endswith(("_ASM_TILE", "_ASM_SEG", "_ASM_SEG_SHORT"))]
+    assert len(loops) == 9
+    idle = _g4_generate(tmp_path, "abl_dma=1", "abl_rd=1")
+    free = _g4_generate(tmp_path, "abl_vmw=1", "abl_bar=1")
+    fetch = ("ds_read_b128", "ds_read_b64_tr_b16", "buffer_load_dwordx4", "global_load_lds_dwordx4")
+    for name in loops:
+        ref, ins = _g4_block(base_text, name), _g4_block(idle, name)
+        entry, ref_entry = [next(k for k, i in enumerate(x) if i.startswith(_G4_MF)) for x in (ins, ref)]
+        assert ins[:entry] == ref[:ref_entry], name  # the entry (setup, waits, entry reads) is untouched
+        assert sum(1 for i in ins if i.startswith(_G4_MF)) == sum(1 for i in ref if i.startswith(_G4_MF)), name
+        assert not [i for i in ins[entry:] if i.startswith(fetch)], name
+        ins = _g4_block(free, name)
+        assert sum(1 for i in ins if i == "s_barrier") == 1 and [i for i in ins if i.startswith("s_waitcnt vmcnt")] == ["s_waitcnt vmcnt(0)"], name
