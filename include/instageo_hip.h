@@ -237,6 +237,21 @@ int ig_classifier_bn_bwd(const float* dlogits, const void* x_hi, const void* x_l
 int ig_ce_loss(const float* logits, const void* labels, int label_dtype, const float* class_weights, long ignore_index,
                double* stats, float* dlogits, long long* preds, signed char* preds_i8, unsigned long long* confusion, int B,
                long HW, int ncls, void* stream);
+/* Focal + region (Dice / Tversky) segmentation loss for class-imbalanced maps (not in the reference).  Same inputs, outputs and validity
+ * predicate (label != ignore_index and 0 <= label < ncls) as ig_ce_loss; p = softmax(logits), pt = p[y]:
+ *   pixel term  sum_valid w_y (1 - pt)^gamma (-log pt); focal_gamma = 0 is the cross-entropy of ig_ce_loss (bit for bit when
+ *               region_weight = 0 as well), otherwise 1 <= focal_gamma <= 8; pixel_term = 0 drops the term (loss = region term alone)
+ *               while the count, argmax and confusion matrix still run
+ *   region term region_weight * (1 / K_p) sum_{c present} (1 - T_c),  T_c = (I_c + s) / (I_c + alpha (P_c - I_c) + beta (G_c - I_c) + s)
+ *               over the valid pixels of the whole launch (I_c = sum p_c [y == c], P_c = sum p_c, G_c = #{y == c}, K_p = classes present,
+ *               s = region_smooth >= 0; alpha = beta = 0.5 is Dice); class weights do not enter it; off when region_weight = 0
+ * stats double[2] += (pixel-term sum + #valid * region term, #valid): loss = stats[0] / stats[1] (NaN when nothing is valid); dlogits is the
+ * gradient of stats[0], UN-normalised like ig_ce_loss's (divide by stats[1] downstream; ig_kd_loss stacks on top unchanged).  parts
+ * (optional, needs stats) double[2] += (pixel-term sum, #valid * region term) for logging.  All sums are folded in a fixed order or as
+ * integers: results are bit-identical from run to run.  The region term costs a second pass over logits, labels and dlogits. */
+int ig_seg_loss(const float* logits, const void* labels, int label_dtype, const float* class_weights, long ignore_index, float focal_gamma,
+                int pixel_term, float region_weight, float region_smooth, float tversky_alpha, float tversky_beta, double* stats, double* parts,
+                float* dlogits, long long* preds, signed char* preds_i8, unsigned long long* confusion, int B, long HW, int ncls, void* stream);
 /* torch.argmax(dim=1) -> int8                                                           infer_utils.py:99-101 */
 int ig_argmax_i8(const float* logits, signed char* out, int B, long HW, int ncls, void* stream);
 /* RunningConfusionMatrix.update                                                         metrics.py:86-108 */

@@ -500,12 +500,27 @@ __global__ __launch_bounds__(TPB, VEC == 8 ? 1 : 2) void cls_bwd_kernel(const fl
 // NCB: class bucket (2: the two-class flood task -- straight-line class loops and the confusion counts in four registers per thread:
 // the LDS histogram has only four counters there, and 256 threads x 4 pixels of same-address LDS atomics per iteration were the kernel;
 // 16: everything else)
-template <typename LABEL, int VEC, int NCB>
+// SEG: the focal / region-loss form (ig_seg_loss); everything it adds sits under `if constexpr (SEG)`, so the SEG = false kernel is the
+// cross-entropy kernel unchanged.  Pixel term: w_y (1 - pt)^gamma (-log pt) with 1 - pt = (sum of the OTHER classes' exponentials) / se
+// where pt >= 1/2 (1.f - pt would round a confident pixel's whole factor away) and -log pt = (max - z_y) + log(se); un-normalised gradient
+// w_y (1 - pt)^(gamma - 1) ((1 - pt) - gamma pt log pt) (p_n - [n == y]).  Region term (Dice / Tversky): this pass only collects the
+// per-class sums P_c = sum p_c, I_c = sum p_c [y == c], G_c = #{y == c} over the valid pixels of the workgroup -- fp32 per thread, one
+// double per workgroup and class in part[workgroup][3][MAXC]; G_c comes from the rows of the LDS confusion histogram, which then
+// counts whether or not a confusion matrix was asked for.  seg_region_finalize_kernel folds them in workgroup order.
+struct SegArgs {
+    float gamma;    // focal exponent; 0 = plain cross-entropy
+    int pixel_on;   // 0: the pixel term is dropped (loss = region term alone); count, argmax and confusion still run
+    double* parts;  // optional [2]: parts[0] += the pixel-term sum of the launch
+    double* part;   // region term: the per-workgroup class sums; NULL = no region term
+};
+
+template <typename LABEL, int VEC, int NCB, bool SEG>
 __global__ __launch_bounds__(TPB) void ce_loss_kernel(const float* __restrict__ logits, const LABEL* __restrict__ labels,
                                                       const float* __restrict__ cw, long ignore_index, double* __restrict__ stats,
                                                       float* __restrict__ dlogits, long long* __restrict__ preds,
                                                       signed char* __restrict__ preds_i8, unsigned long long* __restrict__ confusion,
-                                                      long M, long HW, int ncls, unsigned long long* __restrict__ acc, unsigned* __restrict__ arrived) {
+                                                      long M, long HW, int ncls, unsigned long long* __restrict__ acc, unsigned* __restrict__ arrived,
+                                                      SegArgs seg) {
     extern __shared__ unsigned int hist[];  // [ncls*ncls]
     for (int i = threadIdx.x; i < ncls * ncls; i += TPB) hist[i] = 0u;
     __syncthreads();
@@ -515,6 +530,13 @@ __global__ __launch_bounds__(TPB) void ce_loss_kernel(const float* __restrict__ 
     // flight per CU to cover the HBM latency.
     float my_loss = 0.f, my_cnt = 0.f;
     unsigned cnt4[4] = {0u, 0u, 0u, 0u};  // NCB == 2: confusion counts [y][argmax] of this thread
+    float sP[SEG ? NCB : 1], sI[SEG ? NCB : 1];  // SEG: this thread's P_c, I_c
+    bool count_hist = confusion != nullptr;
+    if constexpr (SEG) {
+#pragma unroll
+        for (int n = 0; n < NCB; ++n) sP[n] = 0.f, sI[n] = 0.f;
+        count_hist = count_hist || seg.part != nullptr;
+    }
     for (long m0 = (blockIdx.x * (long)TPB + threadIdx.x) * VEC; m0 < M; m0 += (long)gridDim.x * TPB * VEC) {
         long b, pix;
         split_pixel(m0, HW, b, pix);
@@ -544,28 +566,59 @@ __global__ __launch_bounds__(TPB) void ce_loss_kernel(const float* __restrict__ 
                 if (n < ncls && z[n][e] > mx) mx = z[n][e], am = n;
             const long y = (long)lab[e];
             float se = 0.f, zy = 0.f;
+            [[maybe_unused]] float ey = 0.f, so = 0.f;  // SEG: the label class's exponential, the sum of the others
 #pragma unroll
             for (int n = 0; n < NCB; ++n)
                 if (n < ncls) {
                     if (n == (int)y) zy = z[n][e];
                     z[n][e] = expf(z[n][e] - mx);  // z now holds exp(z - max)
                     se += z[n][e];
+                    if constexpr (SEG) {
+                        if (n == (int)y) ey = z[n][e];
+                        else so += z[n][e];
+                    }
                 }
             // loss = (max - z_y) + log(se), probabilities exp(z - max) / se, as torch's log_softmax: max + log(se) would round the small
             // loss of a confident pixel away at ulp(|max|).  expf / logf, not __expf / __logf: those lose ~|x| ulps of the argument and
             // ~2^-22 absolute at se ~ 1, the whole loss of a confident pixel.
             const float lse0 = logf(se), rse = 1.f / se;
             const bool valid = (y != ignore_index) && y >= 0 && y < ncls;
-            const float wy = valid ? (cw ? cw[y] : 1.f) : 0.f;
+            const float w0 = valid ? (cw ? cw[y] : 1.f) : 0.f;
+            float wy = w0, wl = w0;  // weights of the gradient and of the loss term
+            if constexpr (SEG) {
+                if (valid) {
+                    if (seg.part) {
+#pragma unroll
+                        for (int n = 0; n < NCB; ++n)
+                            if (n < ncls) {
+                                const float p = z[n][e] * rse;
+                                sP[n] += p;
+                                sI[n] += n == (int)y ? p : 0.f;
+                            }
+                    }
+                    if (!seg.pixel_on) {
+                        wy = 0.f, wl = 0.f;
+                    } else if (seg.gamma != 0.f) {
+                        // 1 - pt: from the other classes' exponentials where pt >= 1/2 (1.f - pt would round a confident pixel's whole factor
+                        // away), as 1.f - pt below (there the subtraction is the accurate form: it damps the rounding of se by pt, while the
+                        // quotient carries the rounding of both sums in full, and (1 - pt)^gamma multiplies it by gamma)
+                        const float pt = ey * rse, nll = (mx - zy) + lse0;
+                        const float omp = 2.f * ey < se ? 1.f - pt : so * rse;
+                        const float pw = seg.gamma == 1.f ? 1.f : (seg.gamma == 2.f ? omp : powf(omp, seg.gamma - 1.f));  // (1 - pt)^(gamma - 1)
+                        wl = w0 * (pw * omp);
+                        wy = w0 * (pw * (omp + seg.gamma * pt * nll));
+                    }
+                }
+            }
             if (valid) {
-                my_loss += wy * ((mx - zy) + lse0);
+                my_loss += wl * ((mx - zy) + lse0);
                 my_cnt += 1.f;
                 if constexpr (NCB == 2) {
                     const int ci = (int)y * ncls + am;
 #pragma unroll
                     for (int q = 0; q < 4; ++q) cnt4[q] += ci == q ? 1u : 0u;
                 } else {
-                    if (confusion) atomicAdd(hist + (int)y * ncls + am, 1u);
+                    if (count_hist) atomicAdd(hist + (int)y * ncls + am, 1u);
                 }
             }
 #pragma unroll
@@ -604,7 +657,7 @@ __global__ __launch_bounds__(TPB) void ce_loss_kernel(const float* __restrict__ 
     // the reported loss is bit-identical from run to run whatever order the workgroups finish in; the workgroup that arrives last
     // converts the totals, adds them to stats and re-arms the scratch.  Waves are folded in index order.
     if constexpr (NCB == 2) {
-        if (confusion) {
+        if (count_hist) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 unsigned c = cnt4[q];
@@ -618,7 +671,35 @@ __global__ __launch_bounds__(TPB) void ce_loss_kernel(const float* __restrict__ 
     my_loss = wave_sum(my_loss);
     my_cnt = wave_sum(my_cnt);
     if ((threadIdx.x & 63) == 0) wred[threadIdx.x >> 6][0] = my_loss, wred[threadIdx.x >> 6][1] = my_cnt;
+    __shared__ float sred[SEG ? TPB / 64 : 1][2 * MAXC];
+    if constexpr (SEG) {
+        if (seg.part) {
+#pragma unroll
+            for (int n = 0; n < NCB; ++n) {
+                const float a = wave_sum(sP[n]), b = wave_sum(sI[n]);
+                if ((threadIdx.x & 63) == 0) sred[threadIdx.x >> 6][n] = a, sred[threadIdx.x >> 6][MAXC + n] = b;
+            }
+        }
+    }
     __syncthreads();
+    if constexpr (SEG) {  // this workgroup's class sums, waves folded in index order; the histogram is complete after the barrier
+        if (seg.part && threadIdx.x < 3 * MAXC) {
+            const int k = threadIdx.x / MAXC, c = threadIdx.x % MAXC;
+            double v = 0.0;
+            if (c < ncls) {
+                if (k < 2) {
+                    float t = 0.f;
+                    for (int w = 0; w < TPB / 64; ++w) t += sred[w][k * MAXC + c];
+                    v = (double)t;
+                } else {
+                    unsigned g = 0u;
+                    for (int a = 0; a < ncls; ++a) g += hist[c * ncls + a];
+                    v = (double)g;
+                }
+            }
+            seg.part[(size_t)blockIdx.x * 3 * MAXC + threadIdx.x] = v;
+        }
+    }
     if (stats && threadIdx.x == 0) {
         float l = 0.f, c = 0.f;
         for (int w = 0; w < TPB / 64; ++w) l += wred[w][0], c += wred[w][1];
@@ -639,11 +720,143 @@ __global__ __launch_bounds__(TPB) void ce_loss_kernel(const float* __restrict__ 
             double tot = (double)tl * (1.0 / 268435456.0);
             if (pz) tot = ((pz & 1u) || (pz & 6u) == 6u) ? __longlong_as_double(0x7ff8000000000000LL) : ((pz & 2u) ? 1.0 : -1.0) * __longlong_as_double(0x7ff0000000000000LL);
             stats[0] += tot, stats[1] += (double)tc;
+            if constexpr (SEG) {
+                if (seg.parts) seg.parts[0] += tot;
+            }
         }
     }
     if (confusion)
         for (int i = threadIdx.x; i < ncls * ncls; i += TPB)
             if (hist[i]) atomicAdd(confusion + i, (unsigned long long)hist[i]);
+}
+
+// Region term, second pass (ig_seg_loss).  One workgroup folds the per-workgroup class sums of the first pass in a fixed order (16
+// strided subsets per value, in double, subsets folded in index order: bit-identical from run to run) and turns them into
+//   N_c = I_c + s,  D_c = I_c + alpha (P_c - I_c) + beta (G_c - I_c) + s,  L_reg = (1 / K_p) sum_{G_c > 0} (1 - N_c / D_c)
+//   dL_reg / dp[i, c] = A_c [y_i == c] + B_c,  A_c = -(D_c - N_c (1 - alpha - beta)) / (K_p D_c^2),  B_c = N_c alpha / (K_p D_c^2)
+// (K_p = classes present among the valid labels, |V| = sum_c G_c; A_c = B_c = 0 for an absent class).  Everything downstream divides by
+// |V| (stats[1]), so the term is handed on pre-multiplied: stats[0], parts[1] += |V| lambda L_reg; coef[c], coef[MAXC + c] =
+// |V| lambda A_c, |V| lambda B_c.  |V| = 0: K_p = 0 and the loss term is 0 / 0 = NaN, like the cross-entropy of an empty selection.
+constexpr int SEG_FOLD = 16;  // strided subsets of the fold: 16 x 48 threads
+__global__ __launch_bounds__(SEG_FOLD * 3 * MAXC) void seg_region_finalize_kernel(const double* __restrict__ part, int nwg, int ncls, float lambda,
+                                                                                  float smooth, float alpha, float beta, float* __restrict__ coef,
+                                                                                  double* __restrict__ stats, double* __restrict__ parts) {
+    __shared__ double sub[SEG_FOLD][3 * MAXC];
+    __shared__ double tot[3 * MAXC];
+    const int i = threadIdx.x % (3 * MAXC), g = threadIdx.x / (3 * MAXC);
+    double a = 0.0;
+    for (int b = g; b < nwg; b += SEG_FOLD) a += part[(size_t)b * 3 * MAXC + i];
+    sub[g][i] = a;
+    __syncthreads();
+    if (threadIdx.x < 3 * MAXC) {
+        double s = 0.0;
+#pragma unroll
+        for (int q = 0; q < SEG_FOLD; ++q) s += sub[q][threadIdx.x];
+        tot[threadIdx.x] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double V = 0.0, L = 0.0;
+        int kp = 0;
+        for (int c = 0; c < ncls; ++c) V += tot[2 * MAXC + c], kp += tot[2 * MAXC + c] > 0.0 ? 1 : 0;
+        for (int c = 0; c < MAXC; ++c) {
+            double A = 0.0, B = 0.0;
+            if (c < ncls && tot[2 * MAXC + c] > 0.0) {
+                const double P = tot[c], I = tot[MAXC + c], G = tot[2 * MAXC + c];
+                const double N = I + (double)smooth, D = I + (double)alpha * (P - I) + (double)beta * (G - I) + (double)smooth;
+                const double sc = V * (double)lambda / ((double)kp * D * D);
+                L += 1.0 - N / D;
+                A = -(D - N * (1.0 - (double)alpha - (double)beta)) * sc;
+                B = N * (double)alpha * sc;
+            }
+            coef[c] = (float)A, coef[MAXC + c] = (float)B;
+        }
+        const double lr = V * (double)lambda * (L / (double)kp);
+        if (stats) stats[0] += lr;
+        if (parts) parts[1] += lr;
+    }
+}
+
+// dlogits[i, n] += |V| lambda dL_reg / dz[i, n] = p_n (g_n - sum_c p_c g_c), g_c = A'_c [y_i == c] + B'_c, on the valid pixels: one more
+// read of logits and labels (the softmax is recomputed, not stored) and a read-modify-write of dlogits, in the vector forms and class
+// buckets of ce_loss_kernel.
+template <typename LABEL, int VEC, int NCB>
+__global__ __launch_bounds__(TPB) void seg_region_grad_kernel(const float* __restrict__ logits, const LABEL* __restrict__ labels, long ignore_index,
+                                                              const float* __restrict__ coef, float* __restrict__ dlogits, long M, long HW, int ncls) {
+    float cA[NCB], cB[NCB];
+#pragma unroll
+    for (int n = 0; n < NCB; ++n) cA[n] = n < ncls ? coef[n] : 0.f, cB[n] = n < ncls ? coef[MAXC + n] : 0.f;
+    for (long m0 = (blockIdx.x * (long)TPB + threadIdx.x) * VEC; m0 < M; m0 += (long)gridDim.x * TPB * VEC) {
+        long b, pix;
+        split_pixel(m0, HW, b, pix);
+        long y[VEC];
+        bool any = false;
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) {
+            y[e] = (long)labels[m0 + e];
+            if (y[e] == ignore_index || y[e] < 0 || y[e] >= ncls) y[e] = -1;  // the validity predicate of ce_loss_kernel
+            any = any || y[e] >= 0;
+        }
+        if (!any) continue;
+        float z[NCB][VEC];
+#pragma unroll
+        for (int n = 0; n < NCB; ++n) {
+            if (n < ncls) {
+                const float* src = logits + (b * ncls + n) * HW + pix;
+                if constexpr (VEC == 4) {
+                    const float4 v = *reinterpret_cast<const float4*>(src);
+                    z[n][0] = v.x, z[n][1] = v.y, z[n][2] = v.z, z[n][3] = v.w;
+                } else {
+                    z[n][0] = *src;
+                }
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) {
+            float mx = -INFINITY;
+            int am = 0;
+#pragma unroll
+            for (int n = 0; n < NCB; ++n)
+                if (n < ncls && z[n][e] > mx) mx = z[n][e], am = n;
+            float se = 0.f;
+#pragma unroll
+            for (int n = 0; n < NCB; ++n)
+                if (n < ncls) z[n][e] = expf(z[n][e] - mx), se += z[n][e];
+            const float rse = y[e] >= 0 ? 1.f / se : 0.f;  // p = 0, and so no gradient, on a pixel that is not valid
+            // g_n - sum_c p_c g_c with g taken relative to the top class's (sum_c p_c = 1): on a confident pixel the sum is then made of
+            // the small terms alone, where g_top - sum_c p_c g_c would cancel to the rounding of g
+            float h[NCB], gtop = 0.f;
+#pragma unroll
+            for (int n = 0; n < NCB; ++n) {
+                h[n] = cB[n] + (n == (int)y[e] ? cA[n] : 0.f);
+                gtop = n == am ? h[n] : gtop;
+            }
+            float dot = 0.f;
+#pragma unroll
+            for (int n = 0; n < NCB; ++n)
+                if (n < ncls) {
+                    z[n][e] *= rse;  // z now holds p
+                    h[n] -= gtop;
+                    dot += z[n][e] * h[n];
+                }
+#pragma unroll
+            for (int n = 0; n < NCB; ++n)
+                if (n < ncls) z[n][e] *= h[n] - dot;  // z now holds the region gradient
+        }
+#pragma unroll
+        for (int n = 0; n < NCB; ++n) {
+            if (n < ncls) {
+                float* dst = dlogits + (b * ncls + n) * HW + pix;
+                if constexpr (VEC == 4) {
+                    float4 v = *reinterpret_cast<const float4*>(dst);
+                    v.x += z[n][0], v.y += z[n][1], v.z += z[n][2], v.w += z[n][3];
+                    *reinterpret_cast<float4*>(dst) = v;
+                } else {
+                    *dst += z[n][0];
+                }
+            }
+        }
+    }
 }
 
 // Knowledge-distillation term (segmentation.py:352-378): KLDivLoss(batchmean)(log_softmax(student), softmax(teacher)) over
@@ -1046,14 +1259,12 @@ static double* loss_scratch(unsigned** ticket, hipStream_t st) {
     return buf;
 }
 
-// label_dtype: 0 = int64, 1 = int32, 2 = float32 (reference labels are float tensors cast with .long())
-int ig_ce_loss(const float* logits, const void* labels, int label_dtype, const float* class_weights, long ignore_index,
-               double* stats, float* dlogits, long long* preds, signed char* preds_i8, unsigned long long* confusion, int B,
-               long HW, int ncls, void* stream) {
-    IG_REQUIRE(logits && labels, "ig_ce_loss: null pointer");
-    IG_REQUIRE(ncls >= 1 && ncls <= MAXC, "ig_ce_loss: 1 <= ncls <= %d (got %d)", MAXC, ncls);
-    long M = (long)B * HW;
-    if (M == 0) return IG_OK;
+// ig_ce_loss and the first pass of ig_seg_loss: one launch of ce_loss_kernel<.., SEG> on nblk workgroups
+extern "C++" {
+template <bool SEG>
+static int ce_loss_launch(const char* who, const float* logits, const void* labels, int label_dtype, const float* class_weights, long ignore_index,
+                          double* stats, float* dlogits, long long* preds, signed char* preds_i8, unsigned long long* confusion, long M, long HW,
+                          int ncls, SegArgs seg, bool vec4, int nblk, void* stream) {
     size_t sm = (size_t)ncls * ncls * sizeof(unsigned);
     // scratch of the order-independent (loss, count) sums: two 64-bit accumulators + the arrival counter, per (device, stream) (ig_scratch
     // slot 3, zero-filled when it is made; the kernel re-arms it); never made during a graph capture (the first call on a stream is a warm-up)
@@ -1061,30 +1272,25 @@ int ig_ce_loss(const float* logits, const void* labels, int label_dtype, const f
     if (stats) {
         acc_stream = (unsigned long long*)ig_scratch(3, 4 * sizeof(unsigned long long), (hipStream_t)stream);
         if (!acc_stream) {
-            ig_set_error("ig_ce_loss: scratch allocation failed");
+            ig_set_error("%s: scratch allocation failed", who);
             return IG_ERR_HIP;
         }
     }
     unsigned long long* acc = acc_stream;
     unsigned* arrived = acc ? reinterpret_cast<unsigned*>(acc + 2) : nullptr;
-    const bool vec4 = HW % 4 == 0 && (reinterpret_cast<uintptr_t>(logits) | reinterpret_cast<uintptr_t>(dlogits) |
-                                      reinterpret_cast<uintptr_t>(preds) | reinterpret_cast<uintptr_t>(preds_i8)) % 16 == 0;
-    const int vec = vec4 ? 4 : 1;
-    long nblk = (M + (long)TPB * vec - 1) / ((long)TPB * vec);
-    if (nblk > 1024) nblk = 1024;  // grid-stride: one round of global atomics per workgroup
     dim3 grid((unsigned)nblk), block(TPB);
     hipStream_t st = (hipStream_t)stream;
-#define IG_CE(LT)                                                                                                              \
-    {                                                                                                                          \
-        if (vec4 && ncls <= 2)                                                                                                 \
-            hipLaunchKernelGGL((ce_loss_kernel<LT, 4, 2>), grid, block, sm, st, logits, (const LT*)labels, class_weights,      \
-                               ignore_index, stats, dlogits, preds, preds_i8, confusion, M, HW, ncls, acc, arrived); \
-        else if (vec4)                                                                                                         \
-            hipLaunchKernelGGL((ce_loss_kernel<LT, 4, 16>), grid, block, sm, st, logits, (const LT*)labels, class_weights,     \
-                               ignore_index, stats, dlogits, preds, preds_i8, confusion, M, HW, ncls, acc, arrived); \
-        else                                                                                                                   \
-            hipLaunchKernelGGL((ce_loss_kernel<LT, 1, 16>), grid, block, sm, st, logits, (const LT*)labels, class_weights,     \
-                               ignore_index, stats, dlogits, preds, preds_i8, confusion, M, HW, ncls, acc, arrived); \
+#define IG_CE(LT)                                                                                                                   \
+    {                                                                                                                               \
+        if (vec4 && ncls <= 2)                                                                                                      \
+            hipLaunchKernelGGL((ce_loss_kernel<LT, 4, 2, SEG>), grid, block, sm, st, logits, (const LT*)labels, class_weights,      \
+                               ignore_index, stats, dlogits, preds, preds_i8, confusion, M, HW, ncls, acc, arrived, seg);          \
+        else if (vec4)                                                                                                              \
+            hipLaunchKernelGGL((ce_loss_kernel<LT, 4, 16, SEG>), grid, block, sm, st, logits, (const LT*)labels, class_weights,     \
+                               ignore_index, stats, dlogits, preds, preds_i8, confusion, M, HW, ncls, acc, arrived, seg);          \
+        else                                                                                                                        \
+            hipLaunchKernelGGL((ce_loss_kernel<LT, 1, 16, SEG>), grid, block, sm, st, logits, (const LT*)labels, class_weights,     \
+                               ignore_index, stats, dlogits, preds, preds_i8, confusion, M, HW, ncls, acc, arrived, seg);          \
     }
     if (label_dtype == 0)
         IG_CE(long long)
@@ -1093,11 +1299,99 @@ int ig_ce_loss(const float* logits, const void* labels, int label_dtype, const f
     else if (label_dtype == 2)
         IG_CE(float)
     else {
-        ig_set_error("ig_ce_loss: unsupported label dtype %d", label_dtype);
+        ig_set_error("%s: unsupported label dtype %d", who, label_dtype);
         return IG_ERR_UNSUPPORTED;
     }
 #undef IG_CE
-    return ig_check_launch("ig_ce_loss");
+    return ig_check_launch(who);
+}
+}  // extern "C++"
+
+// the vector form and the grid of ce_loss_kernel (and of seg_region_grad_kernel, which walks the same pixels)
+static int ce_loss_grid(const float* logits, const float* dlogits, const long long* preds, const signed char* preds_i8, long M, long HW, bool* vec4) {
+    *vec4 = HW % 4 == 0 && (reinterpret_cast<uintptr_t>(logits) | reinterpret_cast<uintptr_t>(dlogits) | reinterpret_cast<uintptr_t>(preds) |
+                            reinterpret_cast<uintptr_t>(preds_i8)) % 16 == 0;
+    const int vec = *vec4 ? 4 : 1;
+    long nblk = (M + (long)TPB * vec - 1) / ((long)TPB * vec);
+    if (nblk > 1024) nblk = 1024;  // grid-stride: one round of global atomics per workgroup
+    return (int)nblk;
+}
+
+// label_dtype: 0 = int64, 1 = int32, 2 = float32 (reference labels are float tensors cast with .long())
+int ig_ce_loss(const float* logits, const void* labels, int label_dtype, const float* class_weights, long ignore_index,
+               double* stats, float* dlogits, long long* preds, signed char* preds_i8, unsigned long long* confusion, int B,
+               long HW, int ncls, void* stream) {
+    IG_REQUIRE(logits && labels, "ig_ce_loss: null pointer");
+    IG_REQUIRE(ncls >= 1 && ncls <= MAXC, "ig_ce_loss: 1 <= ncls <= %d (got %d)", MAXC, ncls);
+    long M = (long)B * HW;
+    if (M == 0) return IG_OK;
+    bool vec4;
+    const int nblk = ce_loss_grid(logits, dlogits, preds, preds_i8, M, HW, &vec4);
+    return ce_loss_launch<false>("ig_ce_loss", logits, labels, label_dtype, class_weights, ignore_index, stats, dlogits, preds, preds_i8, confusion,
+                                 M, HW, ncls, SegArgs{0.f, 1, nullptr, nullptr}, vec4, nblk, stream);
+}
+
+// Focal + region (Dice / Tversky) loss; see the header.  Pass 1 is ce_loss_kernel<.., SEG = true>; with region_weight > 0 the class sums
+// go through scratch slot 6 (1024 workgroups x 48 doubles + the 32 gradient coefficients, per (device, stream); not to be made during a
+// graph capture: the first call on a stream is a warm-up call) to seg_region_finalize_kernel and, with dlogits, seg_region_grad_kernel.
+int ig_seg_loss(const float* logits, const void* labels, int label_dtype, const float* class_weights, long ignore_index, float focal_gamma,
+                int pixel_term, float region_weight, float region_smooth, float tversky_alpha, float tversky_beta, double* stats, double* parts,
+                float* dlogits, long long* preds, signed char* preds_i8, unsigned long long* confusion, int B, long HW, int ncls, void* stream) {
+    IG_REQUIRE(logits && labels, "ig_seg_loss: null pointer");
+    IG_REQUIRE(ncls >= 1 && ncls <= MAXC, "ig_seg_loss: 1 <= ncls <= %d (got %d)", MAXC, ncls);
+    IG_REQUIRE(focal_gamma == 0.f || (focal_gamma >= 1.f && focal_gamma <= 8.f),
+               "ig_seg_loss: focal_gamma must be 0 or in [1, 8] (got %g): (1 - pt)^(gamma - 1) of the gradient is singular at pt = 1 for 0 < gamma < 1",
+               (double)focal_gamma);
+    IG_REQUIRE(region_weight >= 0.f && region_smooth >= 0.f, "ig_seg_loss: region_weight >= 0 and region_smooth >= 0 (got %g, %g)",
+               (double)region_weight, (double)region_smooth);
+    IG_REQUIRE(tversky_alpha > 0.f && tversky_beta > 0.f, "ig_seg_loss: tversky_alpha > 0 and tversky_beta > 0 (got %g, %g)", (double)tversky_alpha,
+               (double)tversky_beta);
+    IG_REQUIRE(!parts || stats, "ig_seg_loss: parts needs stats");
+    IG_REQUIRE(B >= 0 && HW >= 0, "ig_seg_loss: negative size");
+    const long M = (long)B * HW;
+    if (M == 0) return IG_OK;
+    bool vec4;
+    const int nblk = ce_loss_grid(logits, dlogits, preds, preds_i8, M, HW, &vec4);
+    const bool region = region_weight > 0.f;
+    hipStream_t st = (hipStream_t)stream;
+    double* part = nullptr;
+    float* coef = nullptr;
+    if (region) {
+        part = (double*)ig_scratch(6, (size_t)1024 * 3 * MAXC * sizeof(double) + 2 * MAXC * sizeof(float), st);
+        if (!part) {
+            ig_set_error("ig_seg_loss: scratch allocation failed");
+            return IG_ERR_HIP;
+        }
+        coef = reinterpret_cast<float*>(part + (size_t)1024 * 3 * MAXC);
+    }
+    int rc = ce_loss_launch<true>("ig_seg_loss", logits, labels, label_dtype, class_weights, ignore_index, stats, dlogits, preds, preds_i8, confusion,
+                                  M, HW, ncls, SegArgs{focal_gamma, pixel_term != 0, parts, part}, vec4, nblk, stream);
+    if (rc != IG_OK || !region) return rc;
+    hipLaunchKernelGGL(seg_region_finalize_kernel, dim3(1), dim3(SEG_FOLD * 3 * MAXC), 0, st, part, nblk, ncls, region_weight, region_smooth,
+                       tversky_alpha, tversky_beta, coef, stats, parts);
+    if (dlogits) {
+        dim3 grid((unsigned)nblk), block(TPB);
+#define IG_RG(LT)                                                                                                                              \
+    {                                                                                                                                          \
+        if (vec4 && ncls <= 2)                                                                                                                 \
+            hipLaunchKernelGGL((seg_region_grad_kernel<LT, 4, 2>), grid, block, 0, st, logits, (const LT*)labels, ignore_index, coef, dlogits, \
+                               M, HW, ncls);                                                                                                   \
+        else if (vec4)                                                                                                                         \
+            hipLaunchKernelGGL((seg_region_grad_kernel<LT, 4, 16>), grid, block, 0, st, logits, (const LT*)labels, ignore_index, coef,         \
+                               dlogits, M, HW, ncls);                                                                                          \
+        else                                                                                                                                   \
+            hipLaunchKernelGGL((seg_region_grad_kernel<LT, 1, 16>), grid, block, 0, st, logits, (const LT*)labels, ignore_index, coef,         \
+                               dlogits, M, HW, ncls);                                                                                          \
+    }
+        if (label_dtype == 0)
+            IG_RG(long long)
+        else if (label_dtype == 1)
+            IG_RG(int)
+        else
+            IG_RG(float)
+#undef IG_RG
+    }
+    return ig_check_launch("ig_seg_loss");
 }
 
 // kl_sum: device double += KL sum over valid pixels; dlogits (optional) += softmax(student) - softmax(teacher) on valid pixels

@@ -24,7 +24,13 @@ DEFAULTS: Dict[str, Any] = {'root_dir': None,
            'weight_decay': 0.01,
            'scheduler': False,
            'distillation': False,
-           'teacher_ckpt_path': None},
+           'teacher_ckpt_path': None,
+           # segmentation objective (not in the reference): ce | focal | dice | ce_dice | focal_dice (segmentation.loss_spec)
+           'loss': 'ce',
+           'focal_gamma': 2.0,
+           'region_weight': 1.0,
+           'region_smooth': 1.0,
+           'tversky': [0.5, 0.5]},
  'model': {'model_name': 'prithvi_eo_tiny',
            'freeze_backbone': False,
            'load_pretrained_weights': True,

@@ -6,7 +6,7 @@ from typing import Any, Dict
 import torch
 
 from .regression import PrithviDistillationRegressionModule, PrithviRegressionModule
-from .segmentation import PrithviDistillationSegmentationModule, PrithviSegmentationModule
+from .segmentation import LOSS_CHOICES, PrithviDistillationSegmentationModule, PrithviSegmentationModule
 
 
 def create_model(cfg: Dict[str, Any], precision: str = "bf16", device=None) -> PrithviSegmentationModule:
@@ -29,6 +29,13 @@ def create_model(cfg: Dict[str, Any], precision: str = "bf16", device=None) -> P
         precision=precision,
         device=device,
     )
+    loss = t.get("loss", "ce")
+    if loss not in LOSS_CHOICES:
+        raise ValueError(f"train.loss={loss!r}: choose one of {', '.join(LOSS_CHOICES)}")
+    if cfg.get("is_reg_task", False) and loss != "ce":
+        raise ValueError(f"train.loss={loss!r} is a segmentation objective: a regression task (is_reg_task) trains on its masked MSE")
+    seg_loss = dict(loss=loss, focal_gamma=t.get("focal_gamma", 2.0), region_weight=t.get("region_weight", 1.0),
+                    region_smooth=t.get("region_smooth", 1.0), tversky=tuple(t.get("tversky", (0.5, 0.5))))
     distill = bool(t.get("distillation", False)) and train_mode
     if distill and cfg.get("is_reg_task", False):  # factory.py:61-69
         common_d = {k: v for k, v in common.items() if k != "depth"}
@@ -40,12 +47,12 @@ def create_model(cfg: Dict[str, Any], precision: str = "bf16", device=None) -> P
         common_d = {k: v for k, v in common.items() if k != "depth"}
         model = PrithviDistillationSegmentationModule(teacher_ckpt_path=t["teacher_ckpt_path"], num_classes=m["num_classes"],
                                                       class_weights=t["class_weights"], depth=t.get("teacher_depth", -1),
-                                                      student_depth=m.get("depth", -1), **common_d)
+                                                      student_depth=m.get("depth", -1), **seg_loss, **common_d)
     elif cfg.get("is_reg_task", False):  # factory.py:58-76, 97-104
         model = PrithviRegressionModule(use_log_scale=m.get("use_log_scale", False), plot_reg_results=m.get("plot_reg_results", False),
                                         include_ee=m.get("include_ee_metric", False), **common)
     else:
-        model = PrithviSegmentationModule(num_classes=m["num_classes"], class_weights=t["class_weights"], **common)
+        model = PrithviSegmentationModule(num_classes=m["num_classes"], class_weights=t["class_weights"], **seg_loss, **common)
     if not train_mode:
         ckpt = cfg.get("checkpoint_path")
         if not ckpt or str(ckpt) == "None":

@@ -639,6 +639,24 @@ def ce_loss(logits, labels, class_weights, ignore_index: int, stats, dlogits=Non
           _p(dlogits), _p(preds), _p(preds_i8), _p(confusion), B, HW, ncls, _stream())
 
 
+def seg_loss(logits, labels, class_weights, ignore_index: int, stats, dlogits=None, preds=None, preds_i8=None, confusion=None, *,
+             focal_gamma: float = 0.0, pixel_term: bool = True, region_weight: float = 0.0, region_smooth: float = 1.0,
+             tversky=(0.5, 0.5), parts=None) -> None:
+    """Focal + region (Dice / Tversky) loss, the arguments of :func:`ce_loss` first: ``stats`` (f64 [2]) += (pixel-term sum + #valid * region
+    term, #valid), ``dlogits`` = the un-normalised gradient of ``stats[0]``, ``parts`` (f64 [2], optional) += the two summands.  The class
+    sums of the region term run over the tensors given -- the local batch of a data-parallel rank, like the loss count."""
+    B, ncls = logits.shape[0], logits.shape[1]
+    HW = logits.numel() // (B * ncls)
+    assert stats is None or stats.dtype == torch.float64
+    assert parts is None or (parts.dtype == torch.float64 and parts.numel() >= 2)
+    passes = 2 if region_weight > 0 and dlogits is not None else 1  # the region gradient re-reads logits, labels and dlogits
+    work = float(B) * HW * (passes * (ncls * 4 + labels.element_size()) + (ncls * 4 * (2 * passes - 1) if dlogits is not None else 0)
+                            + (8 if preds is not None else 0) + (1 if preds_i8 is not None else 0))
+    _call("ig_seg_loss", work, _p(_f32(logits)), _p(labels), _LABEL_DT[labels.dtype], _p(class_weights), int(ignore_index), float(focal_gamma),
+          int(bool(pixel_term)), float(region_weight), float(region_smooth), float(tversky[0]), float(tversky[1]), _p(stats), _p(parts), _p(dlogits),
+          _p(preds), _p(preds_i8), _p(confusion), B, HW, ncls, _stream())
+
+
 def kd_loss(student_logits, teacher_logits, labels, ignore_index: Optional[int], kl_sum, dlogits=None) -> None:
     """KLDivLoss(batchmean) numerator over the valid pixels into ``kl_sum`` (f64 [1]); ``dlogits`` += softmax(s) - softmax(t)."""
     B, ncls = student_logits.shape[0], student_logits.shape[1]

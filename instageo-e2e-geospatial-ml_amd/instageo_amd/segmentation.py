@@ -13,7 +13,7 @@ from __future__ import annotations
 
 import math
 import os
-from typing import Any, Callable, Dict, List, Optional, Tuple
+from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple
 
 import torch
 import torch.nn as nn
@@ -231,28 +231,67 @@ class FusedAdamW(torch.optim.Optimizer):
 # --------------------------------------------------------------------------------------------------
 # loss bridge: CrossEntropyLoss(weight, ignore_index, 'none') + loss[mask].mean()  (segmentation.py:85-87,117-122)
 # --------------------------------------------------------------------------------------------------
+LOSS_CHOICES = ("ce", "focal", "dice", "ce_dice", "focal_dice")
+
+
+def loss_spec(loss: str = "ce", focal_gamma: float = 2.0, region_weight: float = 1.0, region_smooth: float = 1.0,
+              tversky: Sequence[float] = (0.5, 0.5)) -> Optional[Dict[str, Any]]:
+    """The training objective as keyword arguments of :func:`ops.seg_loss`; ``None`` for ``"ce"``, which stays ``ig_ce_loss``.
+
+    ``focal``: sum_valid w_y (1 - pt)^gamma (-log pt) / #valid.  ``dice``: the Tversky region loss (``tversky = (alpha, beta)``; (0.5, 0.5)
+    is Dice) averaged over the classes present in the batch, times ``region_weight``; the pixel term is dropped.  ``ce_dice`` /
+    ``focal_dice``: pixel term + ``region_weight`` x region term.  The class sums of the region term are those of the local batch: under
+    data parallelism each rank forms its own, like the loss count, and no collective is added."""
+    if loss not in LOSS_CHOICES:
+        raise ValueError(f"unknown loss {loss!r}: choose one of {', '.join(LOSS_CHOICES)}")
+    if loss == "ce":
+        return None
+    gamma = float(focal_gamma) if loss.startswith("focal") else 0.0
+    if gamma != 0.0 and not 1.0 <= gamma <= 8.0:
+        raise ValueError(f"focal_gamma must be 0 or in [1, 8] (got {focal_gamma})")
+    region = float(region_weight) if loss.endswith("dice") else 0.0
+    alpha, beta = (float(v) for v in tversky)
+    if loss.endswith("dice") and not (region > 0 and region_smooth >= 0 and alpha > 0 and beta > 0):
+        raise ValueError("the region term needs region_weight > 0, region_smooth >= 0 and tversky alpha, beta > 0")
+    return dict(focal_gamma=gamma, pixel_term=loss != "dice", region_weight=region, region_smooth=float(region_smooth), tversky=(alpha, beta))
+
+
+def _loss_call(spec, logits, labels, weight, ignore_index, stats, dlog, preds, confusion, parts=None) -> None:
+    """``ig_ce_loss`` (``spec`` None) or ``ig_seg_loss``; ``parts`` (f64 [3], zeroed by the caller, optional): (pixel-term sum,
+    #valid x region term, #valid) of the call, for logging."""
+    if spec is None:
+        ops.ce_loss(logits, labels, weight, ignore_index, stats, dlog, preds, None, confusion)
+        return
+    before = stats[1].clone() if parts is not None else None
+    ops.seg_loss(logits, labels, weight, ignore_index, stats, dlog, preds, None, confusion, parts=parts, **spec)
+    if parts is not None:
+        parts[2] = stats[1] - before
+
+
 class _SegLoss(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, logits, labels, weight, ignore_index, confusion, preds):
+    def forward(ctx, logits, labels, weight, ignore_index, confusion, preds, spec=None, parts=None):
         stats = torch.zeros(2, dtype=torch.float64, device=logits.device)
         dlog = torch.empty_like(logits)
-        ops.ce_loss(logits.contiguous(), labels.contiguous(), weight, ignore_index, stats, dlog, preds, None, confusion)
+        _loss_call(spec, logits.contiguous(), labels.contiguous(), weight, ignore_index, stats, dlog, preds, confusion, parts)
         ctx.save_for_backward(dlog, stats)
         return (stats[0] / stats[1]).float()
 
     @staticmethod
     def backward(ctx, g):
         dlog, stats = ctx.saved_tensors
-        return dlog * (g / stats[1].float()), None, None, None, None, None
+        return dlog * (g / stats[1].float()), None, None, None, None, None, None, None
 
 
 def segmentation_loss(logits: torch.Tensor, labels: torch.Tensor, class_weights: Optional[torch.Tensor], ignore_index: int,
-                      confusion: Optional[torch.Tensor] = None, preds: Optional[torch.Tensor] = None) -> torch.Tensor:
+                      confusion: Optional[torch.Tensor] = None, preds: Optional[torch.Tensor] = None,
+                      spec: Optional[Dict[str, Any]] = None, parts: Optional[torch.Tensor] = None) -> torch.Tensor:
     """sum_valid(w_y * nll) / #valid -- NOT torch's weighted mean.  NaN when nothing is valid,
-    exactly like ``loss[mask].mean()`` of an empty selection."""
+    exactly like ``loss[mask].mean()`` of an empty selection.  ``spec`` (:func:`loss_spec`): the focal / region objective instead;
+    ``parts`` (f64 [3], zeroed by the caller) then receives (pixel-term sum, #valid x region term, #valid)."""
     if labels.dtype not in (torch.int64, torch.int32, torch.float32):
         labels = labels.long()
-    return _SegLoss.apply(logits, labels, class_weights, ignore_index, confusion, preds)
+    return _SegLoss.apply(logits, labels, class_weights, ignore_index, confusion, preds, spec, parts)
 
 
 class _SegKDLoss(torch.autograd.Function):
@@ -260,11 +299,11 @@ class _SegKDLoss(torch.autograd.Function):
     (segmentation.py:352-378): total, and the two parts for logging."""
 
     @staticmethod
-    def forward(ctx, logits, t_logits, labels, weight, ignore_index, confusion):
+    def forward(ctx, logits, t_logits, labels, weight, ignore_index, confusion, spec=None, parts=None):
         stats = torch.zeros(2, dtype=torch.float64, device=logits.device)
         kl = torch.zeros(1, dtype=torch.float64, device=logits.device)
         dlog = torch.empty_like(logits)
-        ops.ce_loss(logits.contiguous(), labels.contiguous(), weight, ignore_index, stats, dlog, None, None, confusion)
+        _loss_call(spec, logits.contiguous(), labels.contiguous(), weight, ignore_index, stats, dlog, None, confusion, parts)
         ops.kd_loss(logits.contiguous(), t_logits.contiguous(), labels.contiguous(), ignore_index, kl, dlog)
         ctx.save_for_backward(dlog, stats)
         return ((stats[0] + kl[0]) / stats[1]).float(), (stats[0] / stats[1]).float().detach(), (kl[0] / stats[1]).float().detach()
@@ -272,7 +311,7 @@ class _SegKDLoss(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g, _g_ce, _g_kl):
         dlog, stats = ctx.saved_tensors
-        return dlog * (g / stats[1].float()), None, None, None, None, None
+        return dlog * (g / stats[1].float()), None, None, None, None, None, None, None
 
 
 # --------------------------------------------------------------------------------------------------
@@ -296,8 +335,17 @@ class PrithviSegmentationModule(_Base):
         depth: int = -1,
         precision: str = "bf16",
         device: Optional[Any] = None,
+        loss: str = "ce",
+        focal_gamma: float = 2.0,
+        region_weight: float = 1.0,
+        region_smooth: float = 1.0,
+        tversky: Sequence[float] = (0.5, 0.5),
     ) -> None:
         super().__init__()
+        # training, validation and test objective (not in the reference): "ce" is the reference's weighted cross-entropy through ig_ce_loss
+        self.loss = loss
+        self._loss_spec = loss_spec(loss, focal_gamma, region_weight, region_smooth, tversky)
+        self._loss_parts: Optional[torch.Tensor] = None  # f64 [3]: (pixel-term sum, #valid x region term, #valid) of the latest step
         self._num_classes = num_classes
         self.net = PrithviSeg(
             image_size=image_size, temporal_step=temporal_step, freeze_backbone=freeze_backbone, variant=model_name,
@@ -362,11 +410,35 @@ class PrithviSegmentationModule(_Base):
         inputs, labels = batch
         outputs = self.forward(inputs)
         metrics: RunningConfusionMatrix = getattr(self, f"{step_type}_metrics")
-        loss = segmentation_loss(outputs, labels, self._weights(), self.ignore_index, confusion=metrics.device_matrix(outputs.device))
+        loss = segmentation_loss(outputs, labels, self._weights(), self.ignore_index, confusion=metrics.device_matrix(outputs.device),
+                                 spec=self._loss_spec, parts=self._zeroed_loss_parts(outputs.device))
         if step_type == "test":  # ROC-AUC is a test-time metric (segmentation.py:153-156)
             self.test_auc.update_from_logits(outputs.detach(), labels)
+        self._log_region_parts(step_type)
         self._accumulate_loss(step_type, loss.detach())
         return loss
+
+    def _region_on(self) -> bool:
+        return self._loss_spec is not None and self._loss_spec["region_weight"] > 0
+
+    def _zeroed_loss_parts(self, device) -> Optional[torch.Tensor]:
+        """The device double[3] that receives (pixel-term sum, #valid x region term, #valid) of the step; None for plain CE."""
+        if self._loss_spec is None:
+            return None
+        if self._loss_parts is None:
+            self._loss_parts = torch.zeros(3, dtype=torch.float64, device=device)
+        else:
+            self._loss_parts.zero_()
+        return self._loss_parts
+
+    def _log_region_parts(self, step_type: str) -> None:
+        """``<step>_pixel_loss`` / ``<step>_dice_loss`` of the latest step when the region term is on: device scalars, no host sync.
+        pixel + dice = the step's loss (before a distillation term)."""
+        if not self._region_on() or torch.cuda.is_current_stream_capturing():
+            return
+        pixel, region, n = self._loss_parts.unbind()
+        self.log(f"{step_type}_pixel_loss", (pixel / n).float())
+        self.log(f"{step_type}_dice_loss", (region / n).float())
 
     def _accumulate_loss(self, step_type: str, loss: torch.Tensor) -> None:
         acc = self._loss_sums.get(step_type)
@@ -482,6 +554,7 @@ class PrithviSegmentationModule(_Base):
             self._loss_sums["train"] = acc
         acc[0] += stats[0] / stats[1]
         acc[1] += 1
+        self._log_region_parts("train")
         return stats
 
     def make_graphed_train_step(self, inputs: torch.Tensor, labels: torch.Tensor):
@@ -549,6 +622,7 @@ class PrithviSegmentationModule(_Base):
                 self._loss_sums["train"] = loss_acc
             graph.replay()
             opt._host_step += 1
+            self._log_region_parts("train")
             return stats
 
         run.graph = graph
@@ -565,6 +639,7 @@ class PrithviSegmentationModule(_Base):
             labels = labels.long()
         self._fused_loss(logits, labels, stats, None, step_type)
         self._accumulate_loss(step_type, (stats[0] / stats[1]).float())
+        self._log_region_parts(step_type)
         return stats
 
     def _fused_loss(self, logits: torch.Tensor, labels: torch.Tensor, stats: torch.Tensor, dlogits: Optional[torch.Tensor],
@@ -572,8 +647,8 @@ class PrithviSegmentationModule(_Base):
         """Loss statistics (+ un-normalised dlogits when training) and the step's streaming metrics, all on the device.
         Overridden by the regression module."""
         metrics: RunningConfusionMatrix = getattr(self, f"{step_type}_metrics")
-        ops.ce_loss(logits, labels.contiguous(), self._weights(), self.ignore_index, stats, dlogits, None, None,
-                    metrics.device_matrix(logits.device))
+        _loss_call(self._loss_spec, logits, labels.contiguous(), self._weights(), self.ignore_index, stats, dlogits, None,
+                   metrics.device_matrix(logits.device), self._zeroed_loss_parts(logits.device))
         if step_type == "test":
             self.test_auc.update_from_logits(logits, labels)
 
@@ -623,12 +698,15 @@ class PrithviDistillationSegmentationModule(PrithviSegmentationModule):
                  temporal_step: int = 1, class_weights: Optional[List[float]] = None, ignore_index: int = -100,
                  weight_decay: float = 1e-2, model_name: str = "prithvi_eo_v1_100", depth: int = -1, student_depth: int = -1,
                  load_pretrained_weights: bool = True, scheduler: bool = True, weight_clip_range: Optional[List[float]] = None,
-                 freeze_backbone: bool = False, precision: str = "bf16", device: Optional[Any] = None, **kwargs: Any) -> None:
+                 freeze_backbone: bool = False, precision: str = "bf16", device: Optional[Any] = None, loss: str = "ce",
+                 focal_gamma: float = 2.0, region_weight: float = 1.0, region_smooth: float = 1.0, tversky: Sequence[float] = (0.5, 0.5),
+                 **kwargs: Any) -> None:
         super().__init__(image_size=image_size, learning_rate=learning_rate, freeze_backbone=freeze_backbone,
                          load_pretrained_weights=False, num_classes=num_classes, temporal_step=temporal_step,
                          class_weights=class_weights, ignore_index=ignore_index, weight_decay=weight_decay, scheduler=scheduler,
                          model_name=model_name, weight_clip_range=weight_clip_range, depth=student_depth, precision=precision,
-                         device=device)
+                         device=device, loss=loss, focal_gamma=focal_gamma, region_weight=region_weight, region_smooth=region_smooth,
+                         tversky=tversky)
         self.teacher = PrithviSegmentationModule(image_size=image_size, learning_rate=learning_rate, freeze_backbone=True,
                                                  load_pretrained_weights=False, num_classes=num_classes, temporal_step=temporal_step,
                                                  class_weights=class_weights, ignore_index=ignore_index, weight_decay=weight_decay,
@@ -659,9 +737,13 @@ class PrithviDistillationSegmentationModule(PrithviSegmentationModule):
         if labels.dtype not in (torch.int64, torch.int32, torch.float32):
             labels = labels.long()
         metrics: RunningConfusionMatrix = getattr(self, f"{step_type}_metrics")
-        loss, ce, kl = _SegKDLoss.apply(outputs, t_logits, labels, self._weights(), self.ignore_index, metrics.device_matrix(outputs.device))
+        loss, ce, kl = _SegKDLoss.apply(outputs, t_logits, labels, self._weights(), self.ignore_index, metrics.device_matrix(outputs.device),
+                                        self._loss_spec, self._zeroed_loss_parts(outputs.device))
         if step_type == "test":
             self.test_auc.update_from_logits(outputs.detach(), labels)
+        if self._region_on():  # <step>_ce_loss names the pixel term; the region term is logged beside it
+            ce = (self._loss_parts[0] / self._loss_parts[2]).float()
+            self.log(f"{step_type}_dice_loss", (self._loss_parts[1] / self._loss_parts[2]).float().item())
         self.log(f"{step_type}_ce_loss", ce.item())
         self.log(f"{step_type}_distill_loss", kl.item())
         self._accumulate_loss(step_type, loss.detach())
@@ -674,7 +756,9 @@ class PrithviDistillationSegmentationModule(PrithviSegmentationModule):
         self._kl.zero_()
         ops.kd_loss(logits, t_logits, labels.contiguous(), self.ignore_index, self._kl, dlogits)
         # total = (ce_sum + kl_sum) / #valid: fold the KL numerator into the loss statistic; keep the parts for logging
-        self._parts = (stats[0].clone(), self._kl[0].clone(), stats[1].clone())
+        # (with a region term, stats[0] = pixel + region: <step>_ce_loss names the pixel term and <step>_dice_loss the region term)
+        region = self._loss_parts[1].clone() if self._region_on() else None
+        self._parts = (stats[0].clone() if region is None else self._loss_parts[0].clone(), self._kl[0].clone(), stats[1].clone(), region)
         stats[0] += self._kl[0]
 
     def fused_train_step(self, inputs, labels, stats=None, grad_scale_world: int = 1):
@@ -689,7 +773,13 @@ class PrithviDistillationSegmentationModule(PrithviSegmentationModule):
         self._log_parts(step_type)
         return out
 
+    def _log_region_parts(self, step_type: str) -> None:
+        """Nothing: this module logs its parts itself, as ``<step>_ce_loss`` (the pixel term), ``<step>_dice_loss`` and
+        ``<step>_distill_loss`` (``_shared_step`` / ``_log_parts``)."""
+
     def _log_parts(self, step_type: str) -> None:
-        ce, kl, n = self._parts
+        ce, kl, n, region = self._parts
+        if region is not None:
+            self.log(f"{step_type}_dice_loss", (region / n).item())
         self.log(f"{step_type}_ce_loss", (ce / n).item())
         self.log(f"{step_type}_distill_loss", (kl / n).item())
