@@ -291,6 +291,27 @@ int ig_window_blend_accumulate(const float* logits, const int* tops, const int* 
                                int yhi, void* stream);
 int ig_window_blend_finalize(const float* acc, const float* wsum, const void* tile, int tile_dtype, int TC, double no_data_value,
                              int nodata_enabled, signed char* classmap, float* prob, int ncls, long HW, int fill, void* stream);
+/* D4 test-time augmentation and uncertainty rasters on the blend canvas (tile_blend.hip).
+ * The eight transforms of an S x S plane a: code k in 0..7 has bits h = k & 1, v = (k >> 1) & 1, t = (k >> 2) & 1 and
+ *   G_k(a)[y][x] = a[sy][sx],  (y1, x1) = t ? (x, y) : (y, x),  sy = v ? S-1-y1 : y1,  sx = h ? S-1-x1 : x1
+ * (0 identity, 1 fliplr, 2 flipud, 3 rot180, 4 transpose, 5 rot90 counter-clockwise, 6 rot90 clockwise, 7 anti-transpose; the inverse of k
+ * is k when t = 0, else 4 | v | (h << 1): dataloader.d4_inverse).
+ * ig_d4_apply: codes = HOST array of K codes (1 <= K <= 8), f32 planes, src != dst, bits are copied.  expand = 1: src (m, P, S, S) ->
+ * dst (m*K, P, S, S), dst[i*K + j] = G_codes[j](src[i]); expand = 0: both (m*K, P, S, S), dst[i*K + j] = G_codes[j](src[i*K + j]).
+ * ig_window_blend_accumulate_tta: ig_window_blend_accumulate with K (1 <= K <= 8) logit sets per window, logits (n, K, ncls, crop, crop)
+ * already in the canvas frame; a pixel's terms are added in row-major window order and, inside a window, in order j = 0..K-1 (for K > 1
+ * a window's K fp32 terms are summed in fp64 and added to the fp32 canvas with one rounding, acc[c] += w * sum_j softmax(logits[j])[c],
+ * wsum += K * w), so the canvas is bit-identical for any split of the windows into batches; K = 1 is ig_window_blend_accumulate bit
+ * for bit.
+ * ig_window_blend_uncertainty, per pixel of the finished canvas with ig_window_blend_finalize's validity rule (NaN where wsum == 0 or a
+ * band is NODATA): p_c = acc_c / wsum, entropy = -sum_c p_c ln p_c / ln(ncls) (0 ln 0 = 0), margin = largest p - second largest p;
+ * entropy or margin may be NULL (not both); 2 <= ncls <= 127. */
+int ig_d4_apply(const float* src, float* dst, const int* codes, int K, int m, int P, int S, int expand, void* stream);
+int ig_window_blend_accumulate_tta(const float* logits, const int* tops, const int* lefts, int n_rows, int n_cols, long w0, int n, int K,
+                                   const float* wvec, float* acc, float* wsum, int ncls, int crop, int H, int W, int y0, int Hb, int ylo,
+                                   int yhi, void* stream);
+int ig_window_blend_uncertainty(const float* acc, const float* wsum, const void* tile, int tile_dtype, int TC, double no_data_value,
+                                int nodata_enabled, float* entropy, float* margin, int ncls, long HW, void* stream);
 int ig_confusion_update(const long long* y_true, const long long* y_pred, unsigned long long* confusion, long n, int k,
                         long ignore_index, int has_ignore, void* stream);
 /* torch.optim.AdamW step on a flat buffer (+ clip_weights, + bf16 shadow refresh)        base.py:103-126 */

@@ -62,7 +62,9 @@ DEFAULTS: Dict[str, Any] = {'root_dir': None,
                                   'noise': {'use': True, 'p': 0.5, 'noise_std': 0.05}}},
  'test': {'img_size': 224, 'crop_size': 224, 'stride': 224, 'mask_cloud': False,
           # mode=tile_inference (not in the reference): window blending of the tile path; the defaults are the nearest-centre stitch
-          'blend': 'nearest', 'cover_edges': False, 'sigma_scale': 0.125, 'save_probabilities': False}}
+          'blend': 'nearest', 'cover_edges': False, 'sigma_scale': 0.125, 'save_probabilities': False,
+          # blended modes only: test-time augmentation over the flips ('flips') or all of D4 ('d4'), entropy / margin raster
+          'tta': 'none', 'save_uncertainty': False}}
 
 PRESETS: Dict[str, Dict[str, Any]] = {'sen1floods11': {'train': {'batch_size': 16, 'class_weights': [1, 3], 'ignore_index': -1},
                   'model': {'model_name': 'prithvi_eo_v1_100'},

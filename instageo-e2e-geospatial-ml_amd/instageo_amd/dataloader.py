@@ -92,6 +92,31 @@ def window_grid(height: int, width: int, crop_size: int, stride: int, cover_edge
     return axis(height), axis(width)
 
 
+D4_SETS = {"none": [0], "flips": [0, 1, 2, 3], "d4": [0, 1, 2, 3, 4, 5, 6, 7]}
+
+
+def d4_codes(tta: str) -> List[int]:
+    """Transform codes of a test-time-augmentation set.  A code k in 0..7 has bits h = k & 1, v = (k >> 1) & 1, t = (k >> 2) & 1 and
+    maps an S x S plane a to ``G_k(a)[y][x] = a[sy][sx]`` with ``(y1, x1) = (x, y) if t else (y, x)``, ``sy = S-1-y1 if v else y1``,
+    ``sx = S-1-x1 if h else x1``: 0 identity, 1 fliplr, 2 flipud, 3 rot180, 4 transpose, 5 rot90 counter-clockwise, 6 rot90 clockwise,
+    7 anti-transpose (``ig_d4_apply``).  "none" -> [0], "flips" -> [0, 1, 2, 3], "d4" -> all eight."""
+    if tta not in D4_SETS:
+        raise ValueError(f"tta must be 'none', 'flips' or 'd4' (got {tta!r})")
+    return list(D4_SETS[tta])
+
+
+def d4_inverse(codes: Sequence[int]) -> List[int]:
+    """The code of each transform's inverse: the flips and rot180 (t = 0) are their own, a transposing code swaps its h and v bits
+    ([0, 1, 2, 3, 4, 6, 5, 7])."""
+    out = []
+    for k in codes:
+        if not 0 <= int(k) <= 7:
+            raise ValueError(f"D4 codes are 0..7 (got {k})")
+        k = int(k)
+        out.append(k if not k & 4 else 4 | ((k >> 1) & 1) | ((k & 1) << 1))
+    return out
+
+
 def extract_windows(tile: torch.Tensor, origins: Sequence[Tuple[int, int]], crop_size: int) -> torch.Tensor:
     """tile (T*C,S,S) [or label (S,S)] -> stacked windows (n, T*C, crop, crop) [(n, crop, crop)]: pure copies."""
     if tile.dim() == 2:

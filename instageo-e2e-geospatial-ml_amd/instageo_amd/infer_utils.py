@@ -12,7 +12,9 @@ windows partitioned contiguously over ranks, final gather; ``stitch_windows`` pu
 ``blended_window_inference`` is the second tile path (``tile_inference(blend="mean" | "gaussian")``): any H x W tile, optionally a
 last window row / column at the edge (``cover_edges``), per-window class probabilities averaged on the canvas with a separable
 window weight (``ig_window_blend_accumulate``: gather form, no atomics, bit-identical for any batch size), then one
-``ig_window_blend_finalize`` -> class map + optional probability raster.
+``ig_window_blend_finalize`` -> class map + optional probability raster.  ``tta="flips" | "d4"`` runs every window under the flips /
+all eight transforms of the square (``ig_d4_apply`` before and after the forward pass) and averages them on the same canvas
+(``ig_window_blend_accumulate_tta``); ``uncertainty`` adds the entropy / top-two-margin raster (``ig_window_blend_uncertainty``).
 """
 from __future__ import annotations
 
@@ -25,14 +27,14 @@ import torch
 
 from . import distributed as D
 from . import ops, tiff
-from .dataloader import gather_windows, origins_tensor, window_grid, window_origins
+from .dataloader import d4_codes, d4_inverse, gather_windows, origins_tensor, window_grid, window_origins
 
 
 def save_prediction(prediction: np.ndarray, file_name: str, output_folder: str, profile: Optional[Dict[str, Any]] = None,
                     kind: str = "prediction") -> str:
     """Save one prediction as a TIFF next to the reference's naming (``chip`` -> ``prediction`` in the base name,
     infer_utils.py:51-54); ``profile`` = the source chip's profile (georeferencing tags are copied, count = 1).  ``kind`` replaces
-    "prediction" in the name (``probability`` rasters of the blended tile path)."""
+    "prediction" in the name (``probability`` and ``uncertainty`` rasters of the blended tile path)."""
     base = os.path.basename(str(file_name))
     out = base.replace("chip", kind) if "chip" in base else f"{kind}_" + base
     if not out.lower().endswith((".tif", ".tiff")):
@@ -158,8 +160,8 @@ def stitch_windows(maps: torch.Tensor, origins: Sequence[Tuple[int, int]], size,
 def blended_window_inference(tile: torch.Tensor, model, mean: Sequence[float], std: Sequence[float], temporal_size: int = 1,
                              crop_size: int = 224, stride: int = 224, batch_size: int = 64, constant_multiplier: Optional[float] = None,
                              blend: str = "gaussian", sigma_scale: float = 0.125, cover_edges: bool = True,
-                             no_data_value: Optional[float] = None, fill: int = -1, probabilities: bool = False
-                             ) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
+                             no_data_value: Optional[float] = None, fill: int = -1, probabilities: bool = False, tta: str = "none",
+                             uncertainty: bool = False) -> Tuple[Optional[torch.Tensor], ...]:
     """tile (T*C, H, W) int16|f32 on the device, any H, W >= crop -> (class map (H, W) int8, probabilities (ncls, H, W) f32 or None)
     on rank 0, (None, None) elsewhere.  A regression head (one output channel) gives (None, the blended value (1, H, W)).
 
@@ -168,11 +170,20 @@ def blended_window_inference(tile: torch.Tensor, model, mean: Sequence[float], s
     divided by the summed weight at the end.  Pixels no window covers, or with any band == ``no_data_value``, get ``fill`` / NaN.
     The canvas is bit-identical for any ``batch_size`` given the same window logits.  Ranks take contiguous blocks of the window
     list (as :func:`sliding_window_inference`) and accumulate only the canvas rows their windows cover; rank 0 adds the bands in
-    rank order (:func:`distributed.reduce_row_bands`), which equals the one-rank canvas to fp32 rounding."""
+    rank order (:func:`distributed.reduce_row_bands`), which equals the one-rank canvas to fp32 rounding.
+
+    ``tta`` ("none" | "flips" | "d4", :func:`dataloader.d4_codes`): every window is run under K transforms of the square, the logits are
+    mapped back and all K enter the canvas with the window's weight.  A forward batch holds whole windows (``max(1, batch_size // K)``
+    of them, x K images), so all transforms of a window stay on one rank.  ``uncertainty=True`` returns a third tensor (2, H, W) =
+    [normalised entropy, top-two margin] of the blended probabilities on rank 0 (NaN where the class map is ``fill``); a regression
+    head has neither and raises ValueError."""
+    codes = d4_codes(tta)
     net, eng = _engine_of(model)
     net.eval()
     TC, H, W = tile.shape
     ncls = net.cfg.num_classes
+    if uncertainty and ncls == 1:
+        raise ValueError("uncertainty rasters need class probabilities (a regression head has one output channel)")
     tops, lefts = window_grid(H, W, crop_size, stride, cover_edges)
     ncol = len(lefts)
     world = D.world_size()
@@ -195,40 +206,64 @@ def blended_window_inference(tile: torch.Tensor, model, mean: Sequence[float], s
     mine = origins_tensor([(tops[w // ncol], lefts[w % ncol]) for w in range(lo, hi)], dev)
     n = hi - lo
     C = TC // temporal_size
-    nbatch = max(1, -(-n // batch_size))  # balanced batches (sliding_window_inference)
+    K = len(codes)
+    per = batch_size if tta == "none" else max(1, batch_size // K)  # windows per forward batch
+    nbatch = max(1, -(-n // per))  # balanced batches (sliding_window_inference)
     bs = -(-n // nbatch) if n else 1
     xbuf = torch.empty((max(bs, 1), C, temporal_size, crop_size, crop_size), dtype=torch.float32, device=dev)
+    if tta != "none":
+        inverse = d4_inverse(codes)
+        xk = torch.empty((max(bs, 1) * K, C, temporal_size, crop_size, crop_size), dtype=torch.float32, device=dev)
+        back = torch.empty((max(bs, 1) * K, ncls, crop_size, crop_size), dtype=torch.float32, device=dev)
     for i in range(0, n, bs):
         k = min(bs, n - i)
         x, _ = gather_windows(tile, mine[i : i + k], mean, std, temporal_size, crop_size, constant_multiplier, out=xbuf[:k])
-        logits = eng.forward(x, training=False, save=False)
-        ops.window_blend_accumulate(logits, tops_d, lefts_d, lo + i, wvec, canvas[:ncls], canvas[ncls], H, y0, rows_of(lo + i, lo + i + k))
+        if tta == "none":
+            logits = eng.forward(x, training=False, save=False)
+            ops.window_blend_accumulate(logits, tops_d, lefts_d, lo + i, wvec, canvas[:ncls], canvas[ncls], H, y0, rows_of(lo + i, lo + i + k))
+            continue
+        logits = eng.forward(ops.d4_apply(x, codes, True, out=xk[: k * K]), training=False, save=False)
+        ops.d4_apply(logits, inverse, False, out=back[: k * K])
+        ops.window_blend_accumulate_tta(back[: k * K].view(k, K, ncls, crop_size, crop_size), tops_d, lefts_d, lo + i, wvec, canvas[:ncls],
+                                        canvas[ncls], H, y0, rows_of(lo + i, lo + i + k))
     full = D.reduce_row_bands(canvas, bands, H, dst=0)
     if full is None:
-        return None, None
-    return ops.window_blend_finalize(full[:ncls], full[ncls], tile, no_data_value, fill, probabilities)
+        return (None, None, None) if uncertainty else (None, None)
+    out = ops.window_blend_finalize(full[:ncls], full[ncls], tile, no_data_value, fill, probabilities)
+    if not uncertainty:
+        return out
+    unc = torch.empty((2, H, W), dtype=torch.float32, device=dev)
+    ops.window_blend_uncertainty(full[:ncls], full[ncls], tile, no_data_value, out=unc)
+    return out + (unc,)
 
 
 @torch.no_grad()
 def tile_inference(tile_path: str, output_folder: str, model, mean: Sequence[float], std: Sequence[float], temporal_size: int = 1,
                    crop_size: int = 224, stride: int = 224, batch_size: int = 64, constant_multiplier: Optional[float] = None,
                    no_data_value: Optional[float] = -9999, fill: int = -1, device: str = "cuda", blend: str = "nearest",
-                   cover_edges: bool = False, sigma_scale: float = 0.125, save_probabilities: bool = False) -> Optional[str]:
+                   cover_edges: bool = False, sigma_scale: float = 0.125, save_probabilities: bool = False, tta: str = "none",
+                   save_uncertainty: bool = False) -> Optional[str]:
     """GeoTIFF tile -> ``prediction_*.tif`` class map of the same georeferencing: read the (T*C, H, W)
     tile, sliding-window inference over all ranks, stitch, blank NODATA pixels (any band == ``no_data_value``) and uncovered
     border pixels with ``fill``, write on rank 0.  Returns the output path on rank 0, None elsewhere.
 
     ``blend="nearest"`` (default): square tiles, nearest-centre stitch (:func:`stitch_windows`).  ``blend="mean" | "gaussian"``:
     :func:`blended_window_inference` on any H x W tile, optionally with ``cover_edges``; a regression head writes its blended value
-    as float32.  ``save_probabilities`` also writes ``probability_*.tif`` (float32, one band per class, NaN = NODATA)."""
+    as float32.  ``save_probabilities`` also writes ``probability_*.tif`` (float32, one band per class, NaN = NODATA); ``tta`` =
+    "flips" | "d4" averages every window over its transforms; ``save_uncertainty`` writes ``uncertainty_*.tif`` (float32, band 1 the
+    normalised entropy, band 2 the top-two margin of the blended probabilities, NaN = NODATA)."""
     if blend not in ("nearest", "mean", "gaussian"):
         raise ValueError(f"blend must be 'nearest', 'mean' or 'gaussian' (got {blend!r})")
     if blend == "nearest" and (cover_edges or save_probabilities):
         raise ValueError("cover_edges and save_probabilities need blend='mean' or 'gaussian' (the nearest-centre stitch has neither)")
+    d4_codes(tta)  # an unknown set raises here
+    if blend == "nearest" and (tta != "none" or save_uncertainty):
+        raise ValueError("tta and save_uncertainty need blend='mean' or 'gaussian' (they work on the probability canvas)")
     arr, profile = tiff.read(tile_path)
     if blend != "nearest":
         return _blended_tile_file(arr, profile, tile_path, output_folder, model, mean, std, temporal_size, crop_size, stride, batch_size,
-                                  constant_multiplier, no_data_value, fill, device, blend, cover_edges, sigma_scale, save_probabilities)
+                                  constant_multiplier, no_data_value, fill, device, blend, cover_edges, sigma_scale, save_probabilities,
+                                  tta, save_uncertainty)
     if arr.shape[1] != arr.shape[2]:
         raise ValueError("tile_inference expects a square tile (the window rule of process_test uses one img_size)")
     t = torch.from_numpy(arr if arr.dtype in (np.int16, np.float32) else arr.astype(np.float32)).to(device)
@@ -246,10 +281,12 @@ def tile_inference(tile_path: str, output_folder: str, model, mean: Sequence[flo
 
 
 def _blended_tile_file(arr, profile, tile_path, output_folder, model, mean, std, temporal_size, crop_size, stride, batch_size,
-                       constant_multiplier, no_data_value, fill, device, blend, cover_edges, sigma_scale, save_probabilities) -> Optional[str]:
+                       constant_multiplier, no_data_value, fill, device, blend, cover_edges, sigma_scale, save_probabilities,
+                       tta="none", save_uncertainty=False) -> Optional[str]:
     t = torch.from_numpy(arr if arr.dtype in (np.int16, np.float32) else arr.astype(np.float32)).to(device)
-    classmap, prob = blended_window_inference(t, model, mean, std, temporal_size, crop_size, stride, batch_size, constant_multiplier,
-                                              blend, sigma_scale, cover_edges, no_data_value, fill, save_probabilities)
+    res = blended_window_inference(t, model, mean, std, temporal_size, crop_size, stride, batch_size, constant_multiplier, blend,
+                                   sigma_scale, cover_edges, no_data_value, fill, save_probabilities, tta, save_uncertainty)
+    classmap, prob = res[0], res[1]
     if classmap is None and prob is None:
         return None
     os.makedirs(output_folder, exist_ok=True)
@@ -260,4 +297,6 @@ def _blended_tile_file(arr, profile, tile_path, output_folder, model, mean, std,
     out = save_prediction(classmap.cpu().numpy(), tile_path, output_folder, dict(profile, count=1, dtype="int8", nodata=fill, tags=tags))
     if save_probabilities:
         save_prediction(prob.cpu().numpy(), tile_path, output_folder, dict(float_prof, count=prob.shape[0]), kind="probability")
+    if save_uncertainty:
+        save_prediction(res[2].cpu().numpy(), tile_path, output_folder, dict(float_prof, count=2), kind="uncertainty")
     return out

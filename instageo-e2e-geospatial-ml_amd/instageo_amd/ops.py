@@ -763,6 +763,65 @@ def window_blend_finalize(acc, wsum, tile: Optional[torch.Tensor] = None, no_dat
     return classmap, prob
 
 
+def d4_apply(src, codes, expand: bool, out=None):
+    """The D4 transforms ``codes`` (host ints 0..7, K of them; :func:`dataloader.d4_codes`) of S x S f32 planes, bits copied.  ``expand``:
+    src (m, ..., S, S) -> (m * K, ..., S, S) with out[i * K + j] = G_codes[j](src[i]); otherwise src is (m * K, ..., S, S) and
+    out[i * K + j] = G_codes[j](src[i * K + j]) (the logits back in the canvas frame, with the inverse codes)."""
+    import ctypes
+
+    codes = [int(k) for k in codes]
+    K, S = len(codes), src.shape[-1]
+    assert src.dim() >= 3 and src.shape[-2] == S and src.dtype == torch.float32
+    if not expand and src.shape[0] % max(K, 1):
+        raise ValueError(f"d4_apply: {src.shape[0]} images are not whole groups of {K} transforms")
+    m = src.shape[0] if expand else src.shape[0] // max(K, 1)
+    P = src.numel() // (src.shape[0] * S * S) if src.shape[0] else 1
+    shape = (m * K,) + tuple(src.shape[1:])
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=src.device)
+    assert tuple(out.shape) == shape and out.dtype == torch.float32
+    # HBM bytes: every destination element is read once and written once
+    _call("ig_d4_apply", float(out.numel()) * 8, _p(src), _p(out), (ctypes.c_int * max(K, 1))(*codes), K, m, P, S, int(bool(expand)), _stream())
+    return out
+
+
+def window_blend_accumulate_tta(logits, tops, lefts, w0: int, wvec, acc, wsum, H: int, y0: int = 0,
+                                rows: Optional[Tuple[int, int]] = None) -> None:
+    """:func:`window_blend_accumulate` with K logit sets per window: logits (n, K, ncls, crop, crop) f32 in the canvas frame, a window's
+    sets added in order j = 0..K-1 (bit-identical for any batching; K = 1 is :func:`window_blend_accumulate` bit for bit)."""
+    n, K, ncls, crop = logits.shape[0], logits.shape[1], logits.shape[2], logits.shape[-1]
+    Hb, W = wsum.shape
+    assert logits.dim() == 5 and acc.shape == (ncls, Hb, W) and wvec.numel() == crop and tops.dtype == torch.int32 and lefts.dtype == torch.int32
+    ylo, yhi = rows if rows is not None else (y0, y0 + Hb)
+    # HBM bytes: the K logit sets once + one read and write of the canvas rows the batch covers ((ncls + 1) f32 per pixel)
+    work = float(logits.numel()) * 4 + float(max(0, min(yhi, y0 + Hb) - max(ylo, y0))) * W * (ncls + 1) * 8
+    _call("ig_window_blend_accumulate_tta", work, _p(_f32(logits)), _p(tops), _p(lefts), tops.numel(), lefts.numel(), int(w0), n, K,
+          _p(_f32(wvec)), _p(_f32(acc)), _p(_f32(wsum)), ncls, crop, int(H), W, int(y0), Hb, int(ylo), int(yhi), _stream())
+
+
+def window_blend_uncertainty(acc, wsum, tile: Optional[torch.Tensor] = None, no_data_value: Optional[float] = None, entropy: bool = True,
+                             margin: bool = True, out: Optional[torch.Tensor] = None):
+    """acc (ncls, H, W) / wsum (H, W) of a finished canvas -> (entropy (H, W) f32 or None, margin (H, W) f32 or None): the entropy of
+    p = acc / wsum normalised by ln(ncls) and the gap between the two largest p; NaN where :func:`window_blend_finalize` writes fill.
+    ``out`` (2, H, W) f32 receives [entropy, margin] (both are computed)."""
+    ncls, H, W = acc.shape
+    assert wsum.shape == (H, W)
+    if out is not None:
+        assert out.shape == (2, H, W) and out.dtype == torch.float32 and out.is_contiguous() and entropy and margin
+        ent, mar = out[0], out[1]
+    else:
+        ent = torch.empty((H, W), dtype=torch.float32, device=acc.device) if entropy else None
+        mar = torch.empty((H, W), dtype=torch.float32, device=acc.device) if margin else None
+    check = tile is not None and no_data_value is not None
+    if check:
+        assert tile.shape[1:] == (H, W)
+    dt = {torch.int16: 0, torch.float32: 1}[tile.dtype] if check else 0
+    work = float(H) * W * ((ncls + 1) * 4 + (tile.shape[0] * tile.element_size() if check else 0) + 4 * (int(entropy) + int(margin)))
+    _call("ig_window_blend_uncertainty", work, _p(_f32(acc)), _p(_f32(wsum)), _p(tile.contiguous()) if check else None, dt,
+          tile.shape[0] if check else 0, float(no_data_value) if check else 0.0, int(check), _p(ent), _p(mar), ncls, H * W, _stream())
+    return ent, mar
+
+
 def confusion_update(y_true, y_pred, confusion, k: int, ignore_index: Optional[int]) -> None:
     assert y_true.dtype == torch.int64 and y_pred.dtype == torch.int64 and confusion.dtype == torch.int64
     _lib.call("ig_confusion_update", _p(y_true), _p(y_pred), _p(confusion), y_true.numel(), k,

@@ -3,8 +3,8 @@
     python -m instageo_amd.run [--config-name sen1floods11] [--config-path DIR] key=value ...
 
 Modes ``stats | train | eval | chip_inference`` and every config key are those of the reference; ``tile_inference``
-(whole GeoTIFF tiles -> maps, ``test.blend`` / ``cover_edges`` / ``sigma_scale`` / ``save_probabilities``) is this project's.  Hydra,
-Lightning and Neptune are replaced by :mod:`instageo_amd.config` and the explicit loop below, which logs the
+(whole GeoTIFF tiles -> maps, ``test.blend`` / ``cover_edges`` / ``sigma_scale`` / ``save_probabilities`` / ``tta`` /
+``save_uncertainty``) is this project's.  Hydra, Lightning and Neptune are replaced by :mod:`instageo_amd.config` and the explicit loop below, which logs the
 same metric names and writes ``instageo_best_checkpoint.ckpt`` (``{"state_dict": ...}``) on the best
 ``val_IoU`` (pipeline_utils.py:347-355).  Data: ``*_filepath`` may be ``synthetic:<n>`` (on-device HLS-shaped
 chips), an ``.npz`` with ``chips (N,T*C,H,W)`` and ``labels (N,H,W)``, or the reference's own CSV of chip / label GeoTIFF paths
@@ -215,7 +215,8 @@ def run_tile_inference(cfg: Dict[str, Any], model, tile: str, output_dir: str, d
     return tile_inference(tile, output_dir, model, d["mean"], d["std"], d["temporal_dim"], t["crop_size"], t["stride"],
                           cfg["train"]["batch_size"], mult, d.get("no_data_value", -9999), device=dev, blend=t.get("blend", "nearest"),
                           cover_edges=bool(t.get("cover_edges", False)), sigma_scale=float(t.get("sigma_scale", 0.125)),
-                          save_probabilities=bool(t.get("save_probabilities", False)))
+                          save_probabilities=bool(t.get("save_probabilities", False)), tta=str(t.get("tta", "none")),
+                          save_uncertainty=bool(t.get("save_uncertainty", False)))
 
 
 def main(argv: Optional[List[str]] = None) -> int:
