@@ -312,6 +312,24 @@ int ig_window_blend_accumulate_tta(const float* logits, const int* tops, const i
                                    int yhi, void* stream);
 int ig_window_blend_uncertainty(const float* acc, const float* wsum, const void* tile, int tile_dtype, int TC, double no_data_value,
                                 int nodata_enabled, float* entropy, float* margin, int ncls, long HW, void* stream);
+/* Region post-processing of class maps (regions.hip; not in the reference).  A class map is (n, H, W) int8, contiguous; `fill` (any int8
+ * value) marks invalid pixels, every other value is a class; H * W <= 2^31 - 1; images are independent; connectivity is 4 or 8.  All
+ * results are integers and unique: bit-identical from run to run.  n = 0 returns IG_OK without touching a pointer.
+ * ig_ccl_label: labels (n, H, W) int32 = the smallest row-major index y * W + x among the pixels of the pixel's component (same class,
+ *   connected under `connectivity`), -1 at fill pixels.  status: device int, zeroed by the caller; nonzero afterwards means a capped
+ *   union-find loop gave up (the labels are then not valid): the caller must check it.
+ * ig_region_area: area (n, HW) int32 = the pixel count at root positions (labels[p] == p), 0 elsewhere.
+ * ig_sieve_pass: one pass of the minimum-mapping-unit sieve on cls, IN PLACE, given its labels and areas.  Regions with area <
+ *   min_region are small, the others kept.  A small region R takes the class of the kept region S that shares a 4-neighbour edge with
+ *   it and has the largest area (ties: the smaller label): best (n, HW) uint64 scratch receives max((area(S) << 32) | (0xFFFFFFFF - S))
+ *   at R.  Small regions without a kept neighbour stay; fill never counts.  *changed (device int) += the small regions reassigned.
+ * ig_region_stats: stats (n_regions, 7) int64 = {area, row_min, row_max, col_min, col_max, row_sum, col_sum} of every region;
+ *   rid (n, HW) int32 holds at root positions the region's row in stats (dense, from area != 0; other positions are not read). */
+int ig_ccl_label(const signed char* cls, int* labels, int n, int H, int W, int connectivity, int fill, int* status, void* stream);
+int ig_region_area(const int* labels, int* area, int n, long HW, void* stream);
+int ig_sieve_pass(signed char* cls, const int* labels, const int* area, int min_region, int n, int H, int W, int fill,
+                  unsigned long long* best, int* changed, void* stream);
+int ig_region_stats(const int* labels, const int* rid, long long* stats, long n_regions, int n, int H, int W, void* stream);
 int ig_confusion_update(const long long* y_true, const long long* y_pred, unsigned long long* confusion, long n, int k,
                         long ignore_index, int has_ignore, void* stream);
 /* torch.optim.AdamW step on a flat buffer (+ clip_weights, + bf16 shadow refresh)        base.py:103-126 */

@@ -64,7 +64,10 @@ DEFAULTS: Dict[str, Any] = {'root_dir': None,
           # mode=tile_inference (not in the reference): window blending of the tile path; the defaults are the nearest-centre stitch
           'blend': 'nearest', 'cover_edges': False, 'sigma_scale': 0.125, 'save_probabilities': False,
           # blended modes only: test-time augmentation over the flips ('flips') or all of D4 ('d4'), entropy / margin raster
-          'tta': 'none', 'save_uncertainty': False}}
+          'tta': 'none', 'save_uncertainty': False,
+          # chip / tile inference (not in the reference): sieve of regions below min_region pixels (0 = off) under 4- or 8-connectivity
+          # with at most sieve_passes passes, and the region table regions_*.csv (postprocess.py)
+          'min_region': 0, 'connectivity': 4, 'sieve_passes': 8, 'save_regions': False}}
 
 PRESETS: Dict[str, Dict[str, Any]] = {'sen1floods11': {'train': {'batch_size': 16, 'class_weights': [1, 3], 'ignore_index': -1},
                   'model': {'model_name': 'prithvi_eo_v1_100'},

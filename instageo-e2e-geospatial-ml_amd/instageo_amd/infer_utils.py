@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from . import distributed as D
-from . import ops, tiff
+from . import ops, postprocess, tiff
 from .dataloader import d4_codes, d4_inverse, gather_windows, origins_tensor, window_grid, window_origins
 
 
@@ -35,13 +35,31 @@ def save_prediction(prediction: np.ndarray, file_name: str, output_folder: str, 
     """Save one prediction as a TIFF next to the reference's naming (``chip`` -> ``prediction`` in the base name,
     infer_utils.py:51-54); ``profile`` = the source chip's profile (georeferencing tags are copied, count = 1).  ``kind`` replaces
     "prediction" in the name (``probability`` and ``uncertainty`` rasters of the blended tile path)."""
-    base = os.path.basename(str(file_name))
-    out = base.replace("chip", kind) if "chip" in base else f"{kind}_" + base
-    if not out.lower().endswith((".tif", ".tiff")):
-        out = os.path.splitext(out)[0] + ".tif"
-    path = os.path.join(output_folder, out)
+    path = _output_path(file_name, output_folder, kind)
     tiff.write(path, prediction, profile)
     return path
+
+
+def _output_path(file_name: str, output_folder: str, kind: str, ext: Optional[str] = None) -> str:
+    """``save_prediction``'s naming; ``ext`` replaces the extension (the region table is ``regions_*.csv``)."""
+    base = os.path.basename(str(file_name))
+    out = base.replace("chip", kind) if "chip" in base else f"{kind}_" + base
+    if ext is not None:
+        out = os.path.splitext(out)[0] + ext
+    elif not out.lower().endswith((".tif", ".tiff")):
+        out = os.path.splitext(out)[0] + ".tif"
+    return os.path.join(output_folder, out)
+
+
+def save_regions_csv(table: Dict[str, np.ndarray], file_name: str, output_folder: str, profile: Optional[Dict[str, Any]] = None) -> str:
+    """Write a region table (:func:`postprocess.region_table`) as ``regions_*.csv`` beside the prediction of ``file_name``."""
+    return postprocess.write_region_csv(_output_path(file_name, output_folder, "regions", ".csv"), table, profile)
+
+
+def _is_regression(model) -> bool:
+    """A single output channel, read from the module's configuration (no device work); False when there is no model to ask."""
+    cfg = getattr(getattr(model, "net", model), "cfg", None)
+    return getattr(cfg, "num_classes", None) == 1
 
 
 def _engine_of(model):
@@ -62,9 +80,15 @@ def _profile_of(file_name: str, dtype: np.dtype) -> Optional[Dict[str, Any]]:
 
 
 @torch.no_grad()
-def chip_inference(dataloader, output_folder: str, model, device: str = "gpu", num_workers: int = 4) -> Dict:
+def chip_inference(dataloader, output_folder: str, model, device: str = "gpu", num_workers: int = 4, min_region: int = 0,
+                   connectivity: int = 4, sieve_passes: int = 8, save_regions: bool = False) -> Dict:
     """Run inference on chips and save one int8 class map (float32 for single-channel regression heads) per chip as
-    ``prediction_*.tif``.  Returns {} (the reference returns CodeCarbon numbers; there is no tracker here)."""
+    ``prediction_*.tif``.  Returns {} (the reference returns CodeCarbon numbers; there is no tracker here).
+
+    ``min_region`` > 0 sieves every class map on the device before it is written (:func:`postprocess.sieve_class_map` with
+    ``connectivity`` and at most ``sieve_passes`` passes); ``save_regions`` writes the region table of the written map as
+    ``regions_*.csv`` beside it.  With the defaults neither runs."""
+    postprocess.check_region_options(min_region, connectivity, sieve_passes, save_regions, _is_regression(model))
     os.makedirs(output_folder, exist_ok=True)
     net, eng = _engine_of(model)
     net.eval()
@@ -75,9 +99,16 @@ def chip_inference(dataloader, output_folder: str, model, device: str = "gpu", n
             if logits.shape[1] == 1:  # regression (single output channel)
                 pred = logits.squeeze(1).cpu().numpy()
             else:
-                pred = ops.argmax_i8(logits).cpu().numpy()
+                maps = ops.argmax_i8(logits)
+                if min_region > 0:
+                    maps, _ = postprocess.sieve_class_map(maps, min_region, connectivity, -1, sieve_passes)
+                table = postprocess.region_table(maps, connectivity, -1) if save_regions else None
+                pred = maps.cpu().numpy()
             profiles = [_profile_of(f, pred.dtype) for f in file_names]
             futures = [executor.submit(save_prediction, p, f, output_folder, prof) for p, f, prof in zip(pred, file_names, profiles)]
+            if save_regions:
+                futures += [executor.submit(save_regions_csv, postprocess.table_of_image(table, i), f, output_folder, prof)
+                            for i, (f, prof) in enumerate(zip(file_names, profiles))]
             for fut in futures:
                 fut.result()
     return {}
@@ -242,7 +273,8 @@ def tile_inference(tile_path: str, output_folder: str, model, mean: Sequence[flo
                    crop_size: int = 224, stride: int = 224, batch_size: int = 64, constant_multiplier: Optional[float] = None,
                    no_data_value: Optional[float] = -9999, fill: int = -1, device: str = "cuda", blend: str = "nearest",
                    cover_edges: bool = False, sigma_scale: float = 0.125, save_probabilities: bool = False, tta: str = "none",
-                   save_uncertainty: bool = False) -> Optional[str]:
+                   save_uncertainty: bool = False, min_region: int = 0, connectivity: int = 4, sieve_passes: int = 8,
+                   save_regions: bool = False) -> Optional[str]:
     """GeoTIFF tile -> ``prediction_*.tif`` class map of the same georeferencing: read the (T*C, H, W)
     tile, sliding-window inference over all ranks, stitch, blank NODATA pixels (any band == ``no_data_value``) and uncovered
     border pixels with ``fill``, write on rank 0.  Returns the output path on rank 0, None elsewhere.
@@ -251,7 +283,14 @@ def tile_inference(tile_path: str, output_folder: str, model, mean: Sequence[flo
     :func:`blended_window_inference` on any H x W tile, optionally with ``cover_edges``; a regression head writes its blended value
     as float32.  ``save_probabilities`` also writes ``probability_*.tif`` (float32, one band per class, NaN = NODATA); ``tta`` =
     "flips" | "d4" averages every window over its transforms; ``save_uncertainty`` writes ``uncertainty_*.tif`` (float32, band 1 the
-    normalised entropy, band 2 the top-two margin of the blended probabilities, NaN = NODATA)."""
+    normalised entropy, band 2 the top-two margin of the blended probabilities, NaN = NODATA).
+
+    Region post-processing of the finished class map, on either path and on rank 0: ``min_region`` > 0 writes the sieved map as
+    ``prediction_*.tif`` (regions below the minimum mapping unit take the class of their largest kept 4-neighbour,
+    :func:`postprocess.sieve_class_map` with ``connectivity`` and at most ``sieve_passes`` passes); ``save_regions`` writes
+    ``regions_*.csv``, the region table of the written map (map coordinates when the tile is georeferenced).  The probability and
+    uncertainty rasters are unchanged by either: they describe the blend BEFORE the sieve.  With the defaults nothing of this runs."""
+    postprocess.check_region_options(min_region, connectivity, sieve_passes, save_regions, _is_regression(model))
     if blend not in ("nearest", "mean", "gaussian"):
         raise ValueError(f"blend must be 'nearest', 'mean' or 'gaussian' (got {blend!r})")
     if blend == "nearest" and (cover_edges or save_probabilities):
@@ -263,7 +302,7 @@ def tile_inference(tile_path: str, output_folder: str, model, mean: Sequence[flo
     if blend != "nearest":
         return _blended_tile_file(arr, profile, tile_path, output_folder, model, mean, std, temporal_size, crop_size, stride, batch_size,
                                   constant_multiplier, no_data_value, fill, device, blend, cover_edges, sigma_scale, save_probabilities,
-                                  tta, save_uncertainty)
+                                  tta, save_uncertainty, min_region, connectivity, sieve_passes, save_regions)
     if arr.shape[1] != arr.shape[2]:
         raise ValueError("tile_inference expects a square tile (the window rule of process_test uses one img_size)")
     t = torch.from_numpy(arr if arr.dtype in (np.int16, np.float32) else arr.astype(np.float32)).to(device)
@@ -277,12 +316,24 @@ def tile_inference(tile_path: str, output_folder: str, model, mean: Sequence[flo
     prof = dict(profile)
     prof.update(count=1, dtype="int8", nodata=fill)
     prof["tags"] = {k: v for k, v in profile["tags"].items() if k != 42113}
+    canvas = _region_outputs(canvas, tile_path, output_folder, prof, fill, min_region, connectivity, sieve_passes, save_regions)
     return save_prediction(canvas.cpu().numpy(), tile_path, output_folder, prof)
+
+
+def _region_outputs(classmap: torch.Tensor, tile_path: str, output_folder: str, profile, fill: int, min_region: int, connectivity: int,
+                    sieve_passes: int, save_regions: bool) -> torch.Tensor:
+    """The class map to write: sieved when ``min_region`` > 0; ``save_regions`` writes its region table.  The defaults return the map
+    untouched without a launch."""
+    if min_region > 0:
+        classmap, _ = postprocess.sieve_class_map(classmap, min_region, connectivity, fill, sieve_passes)
+    if save_regions:
+        save_regions_csv(postprocess.region_table(classmap, connectivity, fill), tile_path, output_folder, profile)
+    return classmap
 
 
 def _blended_tile_file(arr, profile, tile_path, output_folder, model, mean, std, temporal_size, crop_size, stride, batch_size,
                        constant_multiplier, no_data_value, fill, device, blend, cover_edges, sigma_scale, save_probabilities,
-                       tta="none", save_uncertainty=False) -> Optional[str]:
+                       tta="none", save_uncertainty=False, min_region=0, connectivity=4, sieve_passes=8, save_regions=False) -> Optional[str]:
     t = torch.from_numpy(arr if arr.dtype in (np.int16, np.float32) else arr.astype(np.float32)).to(device)
     res = blended_window_inference(t, model, mean, std, temporal_size, crop_size, stride, batch_size, constant_multiplier, blend,
                                    sigma_scale, cover_edges, no_data_value, fill, save_probabilities, tta, save_uncertainty)
@@ -294,7 +345,9 @@ def _blended_tile_file(arr, profile, tile_path, output_folder, model, mean, std,
     float_prof = dict(profile, count=1, dtype="float32", nodata=None, tags={**tags, 42113: (2, "nan")})
     if classmap is None:  # regression head: the blended value is the prediction
         return save_prediction(prob[0].cpu().numpy(), tile_path, output_folder, float_prof)
-    out = save_prediction(classmap.cpu().numpy(), tile_path, output_folder, dict(profile, count=1, dtype="int8", nodata=fill, tags=tags))
+    int_prof = dict(profile, count=1, dtype="int8", nodata=fill, tags=tags)
+    classmap = _region_outputs(classmap, tile_path, output_folder, int_prof, fill, min_region, connectivity, sieve_passes, save_regions)
+    out = save_prediction(classmap.cpu().numpy(), tile_path, output_folder, int_prof)
     if save_probabilities:
         save_prediction(prob.cpu().numpy(), tile_path, output_folder, dict(float_prof, count=prob.shape[0]), kind="probability")
     if save_uncertainty:

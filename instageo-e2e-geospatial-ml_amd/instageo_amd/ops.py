@@ -822,6 +822,59 @@ def window_blend_uncertainty(acc, wsum, tile: Optional[torch.Tensor] = None, no_
     return ent, mar
 
 
+def _class_maps(classmap) -> Tuple[int, int, int]:
+    assert classmap.dtype == torch.int8 and classmap.dim() in (2, 3), "a class map is (H, W) or (n, H, W) int8"
+    H, W = classmap.shape[-2:]
+    return (classmap.shape[0] if classmap.dim() == 3 else 1), H, W
+
+
+def ccl_label(classmap, connectivity: int = 4, fill: int = -1, out=None):
+    """Connected-component labels of (n, H, W) | (H, W) int8 class maps -> int32 of the same shape: the smallest row-major index of the
+    pixel's component, -1 at ``fill`` (include/instageo_hip.h).  Raises when a capped union-find loop of the kernels gave up."""
+    n, H, W = _class_maps(classmap)
+    if out is None:
+        out = torch.empty(classmap.shape, dtype=torch.int32, device=classmap.device)
+    assert out.shape == classmap.shape and out.dtype == torch.int32
+    status = torch.zeros(1, dtype=torch.int32, device=classmap.device)
+    # HBM bytes: the map twice (tiles, borders) + labels written, then read and written by the flatten pass
+    _call("ig_ccl_label", float(n) * H * W * 14, _p(classmap), _p(out), n, H, W, int(connectivity), int(fill), _p(status), _stream())
+    if n and int(status.item()):
+        raise _lib.HipLibraryError(f"ig_ccl_label: a union-find loop reached its iteration cap (status {int(status.item())}); labels are not valid")
+    return out
+
+
+def region_area(labels, out=None):
+    """labels (n, H, W) | (H, W) int32 of :func:`ccl_label` -> int32 of the same shape: the pixel count at root positions, 0 elsewhere."""
+    assert labels.dtype == torch.int32 and labels.dim() in (2, 3)
+    n = labels.shape[0] if labels.dim() == 3 else 1
+    if out is None:
+        out = torch.empty(labels.shape, dtype=torch.int32, device=labels.device)
+    assert out.shape == labels.shape and out.dtype == torch.int32
+    _call("ig_region_area", float(labels.numel()) * 8, _p(labels), _p(out), n, labels.shape[-2] * labels.shape[-1], _stream())
+    return out
+
+
+def sieve_pass(classmap, labels, area, min_region: int, fill: int, best, changed) -> None:
+    """One sieve pass on ``classmap`` in place (include/instageo_hip.h): ``best`` uint64-sized scratch (int64 tensor) of the map's shape,
+    ``changed`` (1,) int32 on the device, incremented by the number of small regions reassigned."""
+    n, H, W = _class_maps(classmap)
+    assert labels.shape == classmap.shape and area.shape == classmap.shape and labels.dtype == torch.int32 and area.dtype == torch.int32
+    assert best.numel() == classmap.numel() and best.dtype == torch.int64 and changed.dtype == torch.int32
+    _call("ig_sieve_pass", float(classmap.numel()) * 30, _p(classmap), _p(labels), _p(area), int(min_region), n, H, W, int(fill), _p(best),
+          _p(changed), _stream())
+
+
+def region_stats(labels, rid, n_regions: int):
+    """-> (n_regions, 7) int64 {area, row_min, row_max, col_min, col_max, row_sum, col_sum}; ``rid`` int32 of the labels' shape holds the
+    dense region id at root positions."""
+    assert labels.dtype == torch.int32 and rid.dtype == torch.int32 and rid.shape == labels.shape and labels.dim() in (2, 3)
+    n = labels.shape[0] if labels.dim() == 3 else 1
+    H, W = labels.shape[-2:]
+    stats = torch.empty((int(n_regions), 7), dtype=torch.int64, device=labels.device)
+    _call("ig_region_stats", float(labels.numel()) * 4, _p(labels), _p(rid), _p(stats), int(n_regions), n, H, W, _stream())
+    return stats
+
+
 def confusion_update(y_true, y_pred, confusion, k: int, ignore_index: Optional[int]) -> None:
     assert y_true.dtype == torch.int64 and y_pred.dtype == torch.int64 and confusion.dtype == torch.int64
     _lib.call("ig_confusion_update", _p(y_true), _p(y_pred), _p(confusion), y_true.numel(), k,

@@ -4,7 +4,8 @@
 
 Modes ``stats | train | eval | chip_inference`` and every config key are those of the reference; ``tile_inference``
 (whole GeoTIFF tiles -> maps, ``test.blend`` / ``cover_edges`` / ``sigma_scale`` / ``save_probabilities`` / ``tta`` /
-``save_uncertainty``) is this project's.  Hydra, Lightning and Neptune are replaced by :mod:`instageo_amd.config` and the explicit loop below, which logs the
+``save_uncertainty``) is this project's, as are the region keys of both inference modes (``test.min_region`` / ``connectivity`` /
+``sieve_passes`` / ``save_regions``).  Hydra, Lightning and Neptune are replaced by :mod:`instageo_amd.config` and the explicit loop below, which logs the
 same metric names and writes ``instageo_best_checkpoint.ckpt`` (``{"state_dict": ...}``) on the best
 ``val_IoU`` (pipeline_utils.py:347-355).  Data: ``*_filepath`` may be ``synthetic:<n>`` (on-device HLS-shaped
 chips), an ``.npz`` with ``chips (N,T*C,H,W)`` and ``labels (N,H,W)``, or the reference's own CSV of chip / label GeoTIFF paths
@@ -216,7 +217,14 @@ def run_tile_inference(cfg: Dict[str, Any], model, tile: str, output_dir: str, d
                           cfg["train"]["batch_size"], mult, d.get("no_data_value", -9999), device=dev, blend=t.get("blend", "nearest"),
                           cover_edges=bool(t.get("cover_edges", False)), sigma_scale=float(t.get("sigma_scale", 0.125)),
                           save_probabilities=bool(t.get("save_probabilities", False)), tta=str(t.get("tta", "none")),
-                          save_uncertainty=bool(t.get("save_uncertainty", False)))
+                          save_uncertainty=bool(t.get("save_uncertainty", False)), **region_options(cfg))
+
+
+def region_options(cfg: Dict[str, Any]) -> Dict[str, Any]:
+    """The ``test.*`` keys of the region post-processing (sieve + region table) as keyword arguments of chip / tile inference."""
+    t = cfg["test"]
+    return dict(min_region=int(t.get("min_region", 0)), connectivity=int(t.get("connectivity", 4)),
+                sieve_passes=int(t.get("sieve_passes", 8)), save_regions=bool(t.get("save_regions", False)))
 
 
 def main(argv: Optional[List[str]] = None) -> int:
@@ -277,7 +285,7 @@ def main(argv: Optional[List[str]] = None) -> int:
         lo, hi = D.shard_range(len(ds), rank, world)
         bs = cfg["train"]["batch_size"]
         loader = (infer_collate_fn([ds[j] for j in range(i, min(i + bs, hi))]) for i in range(lo, hi, bs))
-        info = chip_inference(loader, output_dir, model, device="gpu")
+        info = chip_inference(loader, output_dir, model, device="gpu", **region_options(cfg))
         if rank == 0:
             print(f"Carbon tracking information: {info}")
     elif cfg["mode"] == "tile_inference":
