@@ -14,10 +14,7 @@ namespace {
 
 constexpr int HD = 64;
 
-inline bool attn_generic_env() {  // IG_ATTN_GENERIC=1: head_dim 64 on the generic kernels (cross-check in the tests); read per call
-    const char* e = getenv("IG_ATTN_GENERIC");
-    return e && atoi(e) != 0;
-}
+inline bool attn_generic_env() { return ig_env_int("IG_ATTN_GENERIC", 0) != 0; }  // 1: head_dim 64 on the generic kernels (cross-check in the tests)
 
 }  // namespace
 

@@ -1,7 +1,7 @@
 // Attention forward, second generation (head_dim 64): F.scaled_dot_product_attention of timm's Attention (pritvhi.py:446-456).
 //
-// The first kernel (attention.hip) gives every wave a 16-query tile and spends ~96 VALU instructions per 8 MFMAs: it is bound
-// by instruction issue (9 % of the MFMA peak).  This one is built around v_mfma_f32_32x32x16_bf16:
+// The first-generation kernel (removed in round 4) gave every wave a 16-query tile and spent ~96 VALU instructions per 8 MFMAs: it was
+// bound by instruction issue (9 % of the MFMA peak).  This one is built around v_mfma_f32_32x32x16_bf16:
 // * a workgroup = 7 waves = 224 queries of one (batch, head); a wave owns 32 queries (Q fragments live in registers);
 // * K and V of the head are brought into LDS by LDS-DMA in full 128-byte rows (one global_load_lds_dwordx4 = 8 keys x 128 B),
 //   224 keys per chunk -- the whole head for T = 1 (197 tokens), three chunks for T = 3 (589 tokens).  The bank swizzles are
@@ -853,38 +853,38 @@ __global__ __launch_bounds__(A2_THREADS) void attn2_bwd_fused_kernel(const bf16_
 }  // namespace
 IG_DET_TU(attention2)  // constant-memory descriptor of the deterministic-reduction mode (common.h)
 
+template <bool SPLIT>
+static int a2_fwd(const bf16_t* qkv_hi, const bf16_t* qkv_lo, bf16_t* out_hi, bf16_t* out_lo, float* lse, int B, int N, int H, hipStream_t st) {
+    ig_note_kernel("attn2_fwd_kernel<%s>", SPLIT ? "true" : "false");
+    return ig_launch<attn2_fwd_kernel<SPLIT>>("ig_attention_fwd(attn2)", dim3((N + A2_QB - 1) / A2_QB, H, B), dim3(A2_THREADS), (SPLIT ? 4 : 2) * A2_TILE,
+                                              st, qkv_hi, qkv_lo, out_hi, out_lo, lse, N, H, 0.125f);  // scale = 64^-0.5
+}
+
 int ig_attention2_fwd(const void* qkv_hi, const void* qkv_lo, void* out_hi, void* out_lo, float* lse, int B, int N, int H, void* stream) {
     IG_REQUIRE(N >= 1 && H <= 65535 && B <= 65535, "ig_attention_fwd: B and H must be <= 65535 (grid dimensions), got B = %d, H = %d", B, H);
     IG_REQUIRE((((uintptr_t)qkv_hi | (uintptr_t)qkv_lo) & 15) == 0, "ig_attention_fwd: qkv must be 16-byte aligned%s", "");
-    const bool split = qkv_lo != nullptr;
-    const dim3 grid((N + A2_QB - 1) / A2_QB, H, B);
-    const int lds = (split ? 4 : 2) * A2_TILE;
-    const float scale = 0.125f;  // 64^-0.5
-    hipStream_t st = (hipStream_t)stream;
-    if (split) {
-        static bool attr = false;
-        if (!attr) {
-            (void)hipFuncSetAttribute((const void*)attn2_fwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            attr = true;
-        }
-        ig_note_kernel("attn2_fwd_kernel<true>");
-        hipLaunchKernelGGL(attn2_fwd_kernel<true>, grid, dim3(A2_THREADS), lds, st, (const bf16_t*)qkv_hi, (const bf16_t*)qkv_lo,
-                           (bf16_t*)out_hi, (bf16_t*)out_lo, lse, N, H, scale);
-    } else {
-        static bool attr = false;
-        if (!attr) {
-            (void)hipFuncSetAttribute((const void*)attn2_fwd_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            attr = true;
-        }
-        ig_note_kernel("attn2_fwd_kernel<false>");
-        hipLaunchKernelGGL(attn2_fwd_kernel<false>, grid, dim3(A2_THREADS), lds, st, (const bf16_t*)qkv_hi, (const bf16_t*)qkv_lo,
-                           (bf16_t*)out_hi, (bf16_t*)out_lo, lse, N, H, scale);
-    }
-    return ig_check_launch("ig_attention_fwd(attn2)");
+    auto fwd = qkv_lo ? a2_fwd<true> : a2_fwd<false>;
+    return fwd((const bf16_t*)qkv_hi, (const bf16_t*)qkv_lo, (bf16_t*)out_hi, (bf16_t*)out_lo, lse, B, N, H, (hipStream_t)stream);
+}
+
+// The two-pass backward.  Plain bf16: two dQ workgroups per CU at 128 registers (56 B of scratch; measured 75 against 85 us for one at 143);
+// the split mode keeps one.  The qkv bias gradient comes out of the dQ kernel (a column-sum pass over dqkv was 41.9 us at T = 3 / B = 36).
+template <bool SPLIT>
+static int a2_bwd(const bf16_t* qkv_hi, const bf16_t* qkv_lo, const bf16_t* out_hi, const bf16_t* out_lo, const bf16_t* dout_hi, const bf16_t* dout_lo,
+                  const float* lse, float* delta, bf16_t* dqkv_hi, bf16_t* dqkv_lo, float* dbias, int B, int N, int H, hipStream_t st) {
+    const char* what = "ig_attention_bwd(attn2)";
+    const dim3 grid((N + A2_QB - 1) / A2_QB, H, B), block(A2_THREADS);
+    const int lds_q = (SPLIT ? 4 : 2) * A2_TILE, lds_kv = lds_q + 2 * A2_CH * (int)sizeof(float);
+    const float scale = 0.125f;
+    ig_note_kernel("attn2_bwd_dq_kernel<%s>+attn2_bwd_dkv_kernel<%s>", SPLIT ? "true" : "false", SPLIT ? "true" : "false");
+    const int rc = ig_launch<attn2_bwd_dq_kernel<SPLIT, SPLIT ? 2 : 4>>(what, grid, block, lds_q, st, qkv_hi, qkv_lo, dout_hi, dout_lo, out_hi, out_lo, lse,
+                                                                        delta, dqkv_hi, dqkv_lo, N, H, scale, dbias);
+    if (rc != IG_OK) return rc;
+    return ig_launch<attn2_bwd_dkv_kernel<SPLIT>>(what, grid, block, lds_kv, st, qkv_hi, qkv_lo, dout_hi, dout_lo, lse, delta, dqkv_hi, dqkv_lo, N, H, scale);
 }
 
 // dbias (optional): the qkv bias gradient, dbias[3][H][64] += column sums of dqkv over the B * N tokens -- fused into the single-pass
-// kernel and into the dQ kernel of the two-pass form (the K third is identically zero; the K third is identically zero)
+// kernel and into the dQ kernel of the two-pass form (the K third is identically zero)
 int ig_attention2_bwd(const void* qkv_hi, const void* qkv_lo, const void* out_hi, const void* out_lo, const void* dout_hi,
                       const void* dout_lo, const float* lse, float* delta, void* dqkv_hi, void* dqkv_lo, float* dbias, int B, int N, int H,
                       void* stream) {
@@ -892,48 +892,13 @@ int ig_attention2_bwd(const void* qkv_hi, const void* qkv_lo, const void* out_hi
     IG_REQUIRE((((uintptr_t)qkv_hi | (uintptr_t)qkv_lo | (uintptr_t)dout_hi | (uintptr_t)dout_lo | (uintptr_t)out_hi | (uintptr_t)out_lo) & 15) == 0,
                "ig_attention_bwd: the tensors must be 16-byte aligned%s", "");
     const bool split = qkv_lo != nullptr;
-    const dim3 grid((N + A2_QB - 1) / A2_QB, H, B);
-    const int lds_q = (split ? 4 : 2) * A2_TILE, lds_kv = lds_q + 2 * A2_CH * (int)sizeof(float);
-    const float scale = 0.125f;
     hipStream_t st = (hipStream_t)stream;
     if (!split && N <= A2_CH) {  // one chunk of keys, plain bf16: the single-pass kernel
-        static bool attr = false;
-        if (!attr) {
-            (void)hipFuncSetAttribute((const void*)attn2_bwd_fused_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, A2F_SMEM);
-            attr = true;
-        }
         ig_note_kernel("attn2_bwd_fused_kernel");
-        hipLaunchKernelGGL(attn2_bwd_fused_kernel, dim3(1, H, B), dim3(A2_THREADS), A2F_SMEM, st, (const bf16_t*)qkv_hi, (const bf16_t*)dout_hi,
-                           (const bf16_t*)out_hi, lse, delta, (bf16_t*)dqkv_hi, N, H, scale, dbias);
-        return ig_check_launch("ig_attention_bwd(attn2 fused)");
+        return ig_launch<attn2_bwd_fused_kernel>("ig_attention_bwd(attn2 fused)", dim3(1, H, B), dim3(A2_THREADS), A2F_SMEM, st, (const bf16_t*)qkv_hi,
+                                                 (const bf16_t*)dout_hi, (const bf16_t*)out_hi, lse, delta, (bf16_t*)dqkv_hi, N, H, 0.125f, dbias);
     }
-    // plain bf16: two dQ workgroups per CU at 128 registers (56 B of scratch; measured 75 against 85 us for one at 143); the qkv bias
-    // gradient comes out of the dQ kernel (a column-sum pass over dqkv was 41.9 us at T = 3 / B = 36)
-    constexpr int dqlb = 4;
-    float* dbias_k = dbias;
-#define IG_A2_BWD(SPLIT_)                                                                                                          \
-    {                                                                                                                              \
-        static bool attr = false;                                                                                                  \
-        if (!attr) {                                                                                                               \
-            (void)hipFuncSetAttribute((const void*)attn2_bwd_dq_kernel<SPLIT_, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_q); \
-            (void)hipFuncSetAttribute((const void*)attn2_bwd_dq_kernel<SPLIT_, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_q); \
-            (void)hipFuncSetAttribute((const void*)attn2_bwd_dkv_kernel<SPLIT_>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_kv); \
-            attr = true;                                                                                                           \
-        }                                                                                                                          \
-        if (dqlb == 4 && !SPLIT_)                                                                                                  \
-            hipLaunchKernelGGL((attn2_bwd_dq_kernel<SPLIT_, 4>), grid, dim3(A2_THREADS), lds_q, st, (const bf16_t*)qkv_hi,          \
-                               (const bf16_t*)qkv_lo, (const bf16_t*)dout_hi, (const bf16_t*)dout_lo, (const bf16_t*)out_hi,       \
-                               (const bf16_t*)out_lo, lse, delta, (bf16_t*)dqkv_hi, (bf16_t*)dqkv_lo, N, H, scale, dbias_k);       \
-        else                                                                                                                       \
-            hipLaunchKernelGGL((attn2_bwd_dq_kernel<SPLIT_, 2>), grid, dim3(A2_THREADS), lds_q, st, (const bf16_t*)qkv_hi,          \
-                               (const bf16_t*)qkv_lo, (const bf16_t*)dout_hi, (const bf16_t*)dout_lo, (const bf16_t*)out_hi,       \
-                               (const bf16_t*)out_lo, lse, delta, (bf16_t*)dqkv_hi, (bf16_t*)dqkv_lo, N, H, scale, dbias_k);       \
-        ig_note_kernel("attn2_bwd_dq_kernel<%s>+attn2_bwd_dkv_kernel<%s>", SPLIT_ ? "true" : "false", SPLIT_ ? "true" : "false");  \
-        hipLaunchKernelGGL(attn2_bwd_dkv_kernel<SPLIT_>, grid, dim3(A2_THREADS), lds_kv, st, (const bf16_t*)qkv_hi,                   \
-                           (const bf16_t*)qkv_lo, (const bf16_t*)dout_hi, (const bf16_t*)dout_lo, lse, delta, (bf16_t*)dqkv_hi,     \
-                           (bf16_t*)dqkv_lo, N, H, scale);                                                                         \
-    }
-    if (split) IG_A2_BWD(true) else IG_A2_BWD(false)
-#undef IG_A2_BWD
-    return ig_check_launch("ig_attention_bwd(attn2)");
+    auto bwd = split ? a2_bwd<true> : a2_bwd<false>;
+    return bwd((const bf16_t*)qkv_hi, (const bf16_t*)qkv_lo, (const bf16_t*)out_hi, (const bf16_t*)out_lo, (const bf16_t*)dout_hi, (const bf16_t*)dout_lo, lse,
+               delta, (bf16_t*)dqkv_hi, (bf16_t*)dqkv_lo, dbias, B, N, H, st);
 }

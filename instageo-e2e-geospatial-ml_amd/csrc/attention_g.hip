@@ -557,75 +557,66 @@ __global__ __launch_bounds__(AGL_WPB * 64) void attng_bwd_dq_lds_kernel(const bf
     }
 }
 
-// plain bf16: the LDS-staged kernels (round 4: backward 587 -> 252 us); split mode: the register / L2 kernels above
-template <class K>
-inline bool agl_attr(K kern, int bytes) {
-    return hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess;
+// the register / L2 kernels: the split mode, and plain bf16 when the LDS of the staged kernels below cannot be reserved
+template <int HD, bool SPLIT>
+int attng_fwd_reg(const bf16_t* qkv_hi, const bf16_t* qkv_lo, bf16_t* out_hi, bf16_t* out_lo, float* lse, int B, int N, int H, float scale, hipStream_t st) {
+    ig_note_kernel("attng_fwd_kernel<%d,%s>", HD, SPLIT ? "true" : "false");
+    return ig_launch<attng_fwd_kernel<HD, SPLIT>>("ig_attention_fwd", dim3(ig_cdiv(ig_cdiv(N, 16), AG_WPB), H, B), dim3(AG_WPB * 64), 0, st, qkv_hi, qkv_lo,
+                                                  out_hi, out_lo, lse, N, H, scale);
 }
-
-template <int HD>
-int attng_fwd(const void* qkv_hi, const void* qkv_lo, void* out_hi, void* out_lo, float* lse, int B, int N, int H, hipStream_t st) {
+template <int HD, bool SPLIT>
+int attng_bwd_reg(const bf16_t* qkv_hi, const bf16_t* qkv_lo, const bf16_t* out_hi, const bf16_t* out_lo, const bf16_t* dout_hi, const bf16_t* dout_lo,
+                  const float* lse, float* delta, bf16_t* dqkv_hi, bf16_t* dqkv_lo, int B, int N, int H, float scale, hipStream_t st) {
+    const char* what = "ig_attention_bwd";
     const dim3 grid(ig_cdiv(ig_cdiv(N, 16), AG_WPB), H, B), block(AG_WPB * 64);
-    const float scale = 1.0f / sqrtf((float)HD);
-    if (!qkv_lo) {
-        constexpr int smem = AGL_CH * (2 * HD + 16) + AGL_CH * 2 * HD;
-        static bool attr = false;
-        if (!attr) attr = agl_attr(attng_fwd_lds_kernel<HD>, smem);
-        if (attr) {
-            ig_note_kernel("attng_fwd_lds_kernel<%d>", HD);
-            hipLaunchKernelGGL((attng_fwd_lds_kernel<HD>), dim3(ig_cdiv(ig_cdiv(N, 16), AGL_WPB), H, B), dim3(AGL_WPB * 64), smem, st,
-                               (const bf16_t*)qkv_hi, (bf16_t*)out_hi, lse, N, H, scale);
-            return ig_check_launch("ig_attention_fwd");
-        }
-    }
-    ig_note_kernel("attng_fwd_kernel<%d,%s>", HD, qkv_lo ? "true" : "false");
-    if (qkv_lo)
-        hipLaunchKernelGGL((attng_fwd_kernel<HD, true>), grid, block, 0, st, (const bf16_t*)qkv_hi, (const bf16_t*)qkv_lo, (bf16_t*)out_hi,
-                           (bf16_t*)out_lo, lse, N, H, scale);
-    else
-        hipLaunchKernelGGL((attng_fwd_kernel<HD, false>), grid, block, 0, st, (const bf16_t*)qkv_hi, (const bf16_t*)nullptr, (bf16_t*)out_hi,
-                           (bf16_t*)nullptr, lse, N, H, scale);
-    return ig_check_launch("ig_attention_fwd");
-}
-
-template <int HD>
-int attng_bwd(const void* qkv_hi, const void* qkv_lo, const void* out_hi, const void* out_lo, const void* dout_hi, const void* dout_lo,
-              const float* lse, float* delta, void* dqkv_hi, void* dqkv_lo, int B, int N, int H, hipStream_t st) {
-    const dim3 grid(ig_cdiv(ig_cdiv(N, 16), AG_WPB), H, B), block(AG_WPB * 64);
-    const float scale = 1.0f / sqrtf((float)HD);
     const long total = (long)B * N * H;
-    if (!qkv_lo) {
-        constexpr int smem_kv = 2 * AGL_CH * (2 * HD + 16) + 2 * AGL_CH * 4, smem_q = 2 * AGL_CH * (2 * HD + 16);
-        static bool attr = false;
-        if (!attr) attr = agl_attr(attng_bwd_dkv_lds_kernel<HD>, smem_kv) && agl_attr(attng_bwd_dq_lds_kernel<HD>, smem_q);
-        if (attr) {
-            const dim3 gl(ig_cdiv(ig_cdiv(N, 16), AGL_WPB), H, B), bl(AGL_WPB * 64);
-            ig_note_kernel("attng_bwd_dkv_lds_kernel<%d>+attng_bwd_dq_lds_kernel", HD);
-            hipLaunchKernelGGL((attng_delta_kernel<HD, false>), dim3(ig_cdiv(total, 256)), dim3(256), 0, st, (const bf16_t*)out_hi,
-                               (const bf16_t*)out_lo, (const bf16_t*)dout_hi, (const bf16_t*)dout_lo, delta, N, H, total);
-            hipLaunchKernelGGL((attng_bwd_dkv_lds_kernel<HD>), gl, bl, smem_kv, st, (const bf16_t*)qkv_hi, (const bf16_t*)dout_hi, lse,
-                               (const float*)delta, (bf16_t*)dqkv_hi, N, H, scale);
-            hipLaunchKernelGGL((attng_bwd_dq_lds_kernel<HD>), gl, bl, smem_q, st, (const bf16_t*)qkv_hi, (const bf16_t*)dout_hi, lse,
-                               (const float*)delta, (bf16_t*)dqkv_hi, N, H, scale);
-            return ig_check_launch("ig_attention_bwd");
-        }
-    }
-    ig_note_kernel("attng_bwd_dkv_kernel<%d,%s>+attng_bwd_dq_kernel", HD, qkv_lo ? "true" : "false");
-#define AG_BWD(SPLIT_)                                                                                                             \
-    {                                                                                                                              \
-        hipLaunchKernelGGL((attng_delta_kernel<HD, SPLIT_>), dim3(ig_cdiv(total, 256)), dim3(256), 0, st, (const bf16_t*)out_hi,   \
-                           (const bf16_t*)out_lo, (const bf16_t*)dout_hi, (const bf16_t*)dout_lo, delta, N, H, total);             \
-        hipLaunchKernelGGL((attng_bwd_dkv_kernel<HD, SPLIT_>), grid, block, 0, st, (const bf16_t*)qkv_hi, (const bf16_t*)qkv_lo,   \
-                           (const bf16_t*)dout_hi, (const bf16_t*)dout_lo, lse, (const float*)delta, (bf16_t*)dqkv_hi,             \
-                           (bf16_t*)dqkv_lo, N, H, scale);                                                                         \
-        hipLaunchKernelGGL((attng_bwd_dq_kernel<HD, SPLIT_>), grid, block, 0, st, (const bf16_t*)qkv_hi, (const bf16_t*)qkv_lo,    \
-                           (const bf16_t*)dout_hi, (const bf16_t*)dout_lo, lse, (const float*)delta, (bf16_t*)dqkv_hi,             \
-                           (bf16_t*)dqkv_lo, N, H, scale);                                                                         \
-    }
-    if (qkv_lo) AG_BWD(true)
-    else AG_BWD(false)
-#undef AG_BWD
-    return ig_check_launch("ig_attention_bwd");
+    ig_note_kernel("attng_bwd_dkv_kernel<%d,%s>+attng_bwd_dq_kernel", HD, SPLIT ? "true" : "false");
+    int rc = ig_launch<attng_delta_kernel<HD, SPLIT>>(what, dim3(ig_cdiv(total, 256)), dim3(256), 0, st, out_hi, out_lo, dout_hi, dout_lo, delta, N, H, total);
+    if (rc == IG_OK)
+        rc = ig_launch<attng_bwd_dkv_kernel<HD, SPLIT>>(what, grid, block, 0, st, qkv_hi, qkv_lo, dout_hi, dout_lo, lse, (const float*)delta, dqkv_hi, dqkv_lo, N,
+                                                        H, scale);
+    if (rc == IG_OK)
+        rc = ig_launch<attng_bwd_dq_kernel<HD, SPLIT>>(what, grid, block, 0, st, qkv_hi, qkv_lo, dout_hi, dout_lo, lse, (const float*)delta, dqkv_hi, dqkv_lo, N,
+                                                       H, scale);
+    return rc;
+}
+
+// plain bf16: the LDS-staged kernels (round 4: backward 587 -> 252 us); split mode: the register / L2 kernels above
+template <int HD>
+int attng_fwd(const void* qkv_hi_, const void* qkv_lo, void* out_hi_, void* out_lo, float* lse, int B, int N, int H, hipStream_t st) {
+    const bf16_t* qkv_hi = (const bf16_t*)qkv_hi_;
+    bf16_t* out_hi = (bf16_t*)out_hi_;
+    const float scale = 1.0f / sqrtf((float)HD);
+    if (qkv_lo) return attng_fwd_reg<HD, true>(qkv_hi, (const bf16_t*)qkv_lo, out_hi, (bf16_t*)out_lo, lse, B, N, H, scale, st);
+    constexpr int smem = AGL_CH * (2 * HD + 16) + AGL_CH * 2 * HD;
+    if (!ig_reserve_lds<attng_fwd_lds_kernel<HD>>(smem)) return attng_fwd_reg<HD, false>(qkv_hi, nullptr, out_hi, nullptr, lse, B, N, H, scale, st);
+    ig_note_kernel("attng_fwd_lds_kernel<%d>", HD);
+    return ig_launch<attng_fwd_lds_kernel<HD>>("ig_attention_fwd", dim3(ig_cdiv(ig_cdiv(N, 16), AGL_WPB), H, B), dim3(AGL_WPB * 64), smem, st, qkv_hi, out_hi,
+                                               lse, N, H, scale);
+}
+
+template <int HD>
+int attng_bwd(const void* qkv_hi_, const void* qkv_lo, const void* out_hi_, const void* out_lo, const void* dout_hi_, const void* dout_lo,
+              const float* lse, float* delta, void* dqkv_hi_, void* dqkv_lo, int B, int N, int H, hipStream_t st) {
+    const char* what = "ig_attention_bwd";
+    const bf16_t *qkv_hi = (const bf16_t*)qkv_hi_, *out_hi = (const bf16_t*)out_hi_, *dout_hi = (const bf16_t*)dout_hi_;
+    bf16_t* dqkv_hi = (bf16_t*)dqkv_hi_;
+    const float scale = 1.0f / sqrtf((float)HD);
+    if (qkv_lo)
+        return attng_bwd_reg<HD, true>(qkv_hi, (const bf16_t*)qkv_lo, out_hi, (const bf16_t*)out_lo, dout_hi, (const bf16_t*)dout_lo, lse, delta, dqkv_hi,
+                                       (bf16_t*)dqkv_lo, B, N, H, scale, st);
+    constexpr int smem_kv = 2 * AGL_CH * (2 * HD + 16) + 2 * AGL_CH * 4, smem_q = 2 * AGL_CH * (2 * HD + 16);
+    if (!ig_reserve_lds<attng_bwd_dkv_lds_kernel<HD>>(smem_kv) || !ig_reserve_lds<attng_bwd_dq_lds_kernel<HD>>(smem_q))
+        return attng_bwd_reg<HD, false>(qkv_hi, nullptr, out_hi, (const bf16_t*)out_lo, dout_hi, (const bf16_t*)dout_lo, lse, delta, dqkv_hi, (bf16_t*)dqkv_lo,
+                                        B, N, H, scale, st);
+    const dim3 gl(ig_cdiv(ig_cdiv(N, 16), AGL_WPB), H, B), bl(AGL_WPB * 64);
+    const long total = (long)B * N * H;
+    ig_note_kernel("attng_bwd_dkv_lds_kernel<%d>+attng_bwd_dq_lds_kernel", HD);
+    int rc = ig_launch<attng_delta_kernel<HD, false>>(what, dim3(ig_cdiv(total, 256)), dim3(256), 0, st, out_hi, (const bf16_t*)out_lo, dout_hi,
+                                                      (const bf16_t*)dout_lo, delta, N, H, total);
+    if (rc == IG_OK) rc = ig_launch<attng_bwd_dkv_lds_kernel<HD>>(what, gl, bl, smem_kv, st, qkv_hi, dout_hi, lse, (const float*)delta, dqkv_hi, N, H, scale);
+    if (rc == IG_OK) rc = ig_launch<attng_bwd_dq_lds_kernel<HD>>(what, gl, bl, smem_q, st, qkv_hi, dout_hi, lse, (const float*)delta, dqkv_hi, N, H, scale);
+    return rc;
 }
 
 }  // namespace

@@ -7,6 +7,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 typedef uint16_t bf16_t;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
@@ -64,8 +65,9 @@ struct G8Params {
     float* colsum;
 };
 int ig_gemm8_nt(const G8Params& p, void* stream);  // IG_ERR_UNSUPPORTED (no error string) when the shape is not covered
-// gemm4.hip: the same contract on the 4-wave (one wave per SIMD, 128 x 128 per wave) kernel with a generated K-loop: plain bf16 operands,
-// N % 256 == 0, K % 128 == 0, >= 128 tiles; ig_gemm8_nt tries it first
+// gemm4.hip: the same contract on the 4-wave (one wave per SIMD, 128 x 128 per wave) kernel with a generated K-loop: plain bf16 operands, or
+// split ones through the paired kernels when every lo plane passes ig_pair_dist (else IG_ERR_UNSUPPORTED); N % 256 == 0, K % 128 == 0,
+// K >= 256, >= 128 tiles (IG_GEMM4=2: any tile count); ig_gemm8_nt tries it first
 int ig_gemm4_nt(const G8Params& p, void* stream);
 // gemm8w.hip: grouped linear weight gradients dW_g += dy_g^T x_g (shared token count M) on the 8-phase schedule with transposed
 // fragment reads; IG_ERR_UNSUPPORTED (no error string) when a shape is not covered (N, K multiples of 256)
@@ -75,8 +77,7 @@ int ig_wgrad8_group(int n, const void* const* dy_hi, const void* const* dy_lo, c
 // (gathering LDS-DMA); dWc[Cout][9][Cin] += ...; IG_ERR_UNSUPPORTED (no error string) when the shape is not covered
 int ig_wgrad8_conv(int kind, const void* dy_hi, const void* dy_lo, const void* x_hi, const void* x_lo, float* dw, int B, int H, int W,
                    int Cin, int Cout, void* stream);
-// runtime.hip: compute units the persistent kernels leave free (for RCCL's kernels when world > 1); ig_set_reserved_cus()
-// attention2.hip: second-generation attention forward (32x32x16 MFMA, whole-head K/V in LDS); IG_ERR_UNSUPPORTED -> first generation
+// attention2.hip: head_dim 64 attention (32x32x16 MFMA, whole-head K/V in LDS); covers every such shape, there is no fallback behind it
 int ig_attention2_fwd(const void* qkv_hi, const void* qkv_lo, void* out_hi, void* out_lo, float* lse, int B, int N, int H, void* stream);
 int ig_attention2_bwd(const void* qkv_hi, const void* qkv_lo, const void* out_hi, const void* out_lo, const void* dout_hi,
                       const void* dout_lo, const float* lse, float* delta, void* dqkv_hi, void* dqkv_lo, float* dbias, int B, int N, int H,
@@ -91,7 +92,7 @@ int ig_attention_generic_bwd(const void* qkv_hi, const void* qkv_lo, const void*
 // spaces), so bench.py can key its per-kernel roofline table by the names the rocprof summaries under profiles/ use
 void ig_note_kernel(const char* fmt, ...);
 void ig_note_grid(int workgroups);  // workgroups of the last persistent GEMM launch (ig_last_grid: the reserved-CU rule is testable)
-int ig_reserved_cus();
+int ig_reserved_cus();  // compute units the persistent kernels leave free (for RCCL's kernels when world > 1): IG_RESERVED_CUS, read once
 int ig_cu_count();
 int ig_tile_grid(int ntiles, int per_cu);
 
@@ -104,6 +105,42 @@ int ig_tile_grid(int ntiles, int per_cu);
     } while (0)
 
 static inline int ig_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+
+// An IG_* engine switch: read on every call (the tests flip switches between calls of one process); atoi, so a non-numeric value is 0.
+static inline int ig_env_int(const char* name, int dflt) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
+
+// Let Kern use `bytes` of dynamic LDS.  The largest size granted so far is kept per kernel (one static per instantiation), so a later
+// launch with more is still covered.  Per process, not per device or thread: the project runs one process per GPU.
+template <auto Kern>
+static inline bool ig_reserve_lds(int bytes) {
+    static int reserved = 0;
+    if (bytes > reserved) {
+        if (hipFuncSetAttribute((const void*)Kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) return false;
+        reserved = bytes;
+    }
+    return true;
+}
+// Reserve, launch, check.  `what` names the entry point in the error texts.
+template <auto Kern, class... Args>
+static inline int ig_launch(const char* what, dim3 grid, dim3 block, int smem, hipStream_t st, Args... args) {
+    if (!ig_reserve_lds<Kern>(smem)) {
+        ig_set_error("%s: cannot reserve %d bytes of dynamic LDS", what, smem);
+        return IG_ERR_HIP;
+    }
+    hipLaunchKernelGGL(Kern, grid, block, smem, st, args...);
+    return ig_check_launch(what);
+}
+
+// Paired split operands: the byte distance from a hi plane to its lo plane when the pair can be fetched as hi + one offset
+// (IG_G8_PAIR=0 turns pairing off; lo above hi; 16-byte multiple, ops.BT._alloc lays split tensors out so), else 0.  How far the
+// offset may reach differs per engine and is checked at the call sites.
+static inline long ig_pair_dist(const void* hi, const void* lo) {
+    const long d = (const char*)lo - (const char*)hi;
+    return ig_env_int("IG_G8_PAIR", 1) != 0 && d > 0 && (d & 15) == 0 ? d : 0;
+}
 
 // Division by a launch-time constant as multiply-high + shift (dividends < 2^31): the pixel -> (b, y, x) and
 // k -> (tap, channel) decodes of the convolution gathers were integer divisions per 16-byte unit.
@@ -284,6 +321,7 @@ __device__ __forceinline__ void dropout_scale4(uint32_t seed, uint32_t idx4, uin
     m[3] = (h1 >> 16) >= thresh16 ? inv_keep : 0.0f;
 }
 static inline uint32_t ig_drop_thresh16(float p) { return p > 0.f ? (uint32_t)((double)p * 65536.0 + 0.5) : 0u; }
+static inline float ig_drop_inv(float p) { return p > 0.f ? 1.f / (1.f - p) : 1.f; }
 
 // erf by Abramowitz-Stegun 7.1.26 (|abs err| <= 1.5e-7): 1 rcp + 1 exp + 5 fma instead of the ~40-instruction
 // branchy libm erff -- the GELU epilogue of the fc1 GEMM (64 values per lane) was costing as much as its K loop.

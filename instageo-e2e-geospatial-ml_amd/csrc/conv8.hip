@@ -792,30 +792,14 @@ __global__ __launch_bounds__(256) void conv8_pack_tr_kernel(const bf16_t* __rest
     }
 }
 
-// IG_CONV8: 0 = off, 1 = default (launches with enough tiles), 2 = every covered shape (tests).  Read per call.
-inline int c8_env() {
-    const char* e = getenv("IG_CONV8");
-    return e ? atoi(e) : 1;
-}
-
 template <int WC, int MT, int NT0, int NT1, int NSEG, bool SPLIT_OUT>
 int c8_launch(const C8Params& p, int grid, hipStream_t st) {
     using Geo = C8Geo<WC, MT, NT0, NT1, SPLIT_OUT>;
-    auto kern = conv8_kernel<WC, MT, NT0, NT1, NSEG, SPLIT_OUT>;
     const int smem = Geo::OFF_TAB + (p.ktab_n + 32) * 4;
     if (smem > 160 * 1024) return IG_ERR_UNSUPPORTED;
-    static int attr_done = 0;
-    if (attr_done < smem) {
-        if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-            ig_set_error("conv8: could not reserve 160 KiB of LDS");
-            return IG_ERR_HIP;
-        }
-        attr_done = 160 * 1024;
-    }
     ig_note_kernel("conv8_kernel<%d,%d,%d,%d,%d,%s>", WC, MT, NT0, NT1, NSEG, SPLIT_OUT ? "true" : "false");
     ig_note_grid(grid);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(Geo::NTHR), smem, st, p);
-    return ig_check_launch("conv8");
+    return ig_launch<conv8_kernel<WC, MT, NT0, NT1, NSEG, SPLIT_OUT>>("conv8", dim3(grid), dim3(Geo::NTHR), smem, st, p);
 }
 
 template <int WC, int MT, int NT0, int NT1>
@@ -823,10 +807,8 @@ int c8_launch_seg(const C8Params& p, int grid, hipStream_t st) {
     if (p.a[1]) {
         // paired K-tiles when one buffer descriptor can span hi and lo of the gathered tensor (ops.BT allocates them as one block; the packed
         // weights always are); IG_G8_PAIR=0: the three-pass form (A/B runs)
-        const char* e = getenv("IG_G8_PAIR");
-        const long dA = (const char*)p.a[1] - (const char*)p.a[0], dB = (const char*)p.b[1] - (const char*)p.b[0];
-        const bool pair = (!e || atoi(e) != 0) && dA > 0 && dB > 0 && !(dA & 15) && !(dB & 15) && dA + (long)p.a_bytes < 0xfffffff0L && dB + (1L << 24) < (1L << 32);
-        if (pair) return c8_launch<WC, MT, NT0, NT1, 2, true>(p, grid, st);
+        const long dA = ig_pair_dist(p.a[0], p.a[1]), dB = ig_pair_dist(p.b[0], p.b[1]);
+        if (dA && dB && dA + (long)p.a_bytes < 0xfffffff0L && dB + (1L << 24) < (1L << 32)) return c8_launch<WC, MT, NT0, NT1, 2, true>(p, grid, st);
         return c8_launch<WC, MT, NT0, NT1, 3, true>(p, grid, st);
     }
     return c8_launch<WC, MT, NT0, NT1, 1, false>(p, grid, st);
@@ -852,7 +834,7 @@ IG_DET_TU(conv8)
 int ig_conv8(int kind, int sign, const void* x_hi, const void* x_lo, const void* w_hi, const void* w_lo, const float* bias,
              const float* scale, const float* shift, void* y_hi, void* y_lo, int B, int H, int W, int C, int N, unsigned drop_seed,
              const unsigned* drop_seed_dev, float drop_p, void* stream) {
-    const int env = c8_env();
+    const int env = ig_env_int("IG_CONV8", 1);  // 0 = off, 1 = default (launches with enough tiles), 2 = every covered shape (tests)
     if (!env) return IG_ERR_UNSUPPORTED;
     if ((x_lo == nullptr) != (w_lo == nullptr) || (x_lo == nullptr) != (y_lo == nullptr)) return IG_ERR_UNSUPPORTED;
     if (C % 8 || N % 8 || B <= 0) return IG_ERR_UNSUPPORTED;
@@ -912,14 +894,11 @@ int ig_conv8(int kind, int sign, const void* x_hi, const void* x_lo, const void*
     const int ni4 = N % 192 == 0 ? 6 : N % 96 == 0 ? 3 : 6;
     const long nt4 = (M + 255) / 256 * ((N + 32 * ni4 - 1) / (32 * ni4)) * pl.nphase;
     {
-        const char* e4 = getenv("IG_GEMM4");
-        const int g4 = e4 ? atoi(e4) : 1;
+        const int g4 = ig_env_int("IG_GEMM4", 1);
         bool ok4 = g4 && (N % 96 == 0 || N == 144) && tent <= C4_TAB_MAX && a_bytes < 2147483648.0 - 16777216.0 && nt4 < (1L << 30);
         if (w_lo) {  // the split mode: paired K-tiles, hi and lo of the gathered tensor under ONE descriptor below 2 GiB
-            const char* ep = getenv("IG_G8_PAIR");
-            const long dA = (const char*)x_lo - (const char*)x_hi, dB = (long)(((size_t)elems * 2 + 255) / 256 * 256);
-            ok4 = ok4 && (!ep || atoi(ep) != 0) && dA > 0 && !(dA & 15) && (double)dA + a_bytes < 2147483648.0 - 16777216.0 &&
-                  dB + (1L << 24) < (1L << 32);
+            const long dA = ig_pair_dist(x_hi, x_lo), dB = (long)(((size_t)elems * 2 + 255) / 256 * 256);
+            ok4 = ok4 && dA && (double)dA + a_bytes < 2147483648.0 - 16777216.0 && dB + (1L << 24) < (1L << 32);
         }
         for (int ph = 0; ph < pl.nphase; ++ph) ok4 = ok4 && pl.kpad[ph] / 64 >= 4;
         use4 = ok4 && (g4 == 2 || nt4 >= slots - slots / 8);
@@ -992,29 +971,14 @@ int ig_conv8(int kind, int sign, const void* x_hi, const void* x_lo, const void*
     p.phase_map = kind == 1;
     p.drop_seed = drop_seed, p.drop_seed_dev = drop_seed_dev;
     p.drop_thresh = ig_drop_thresh16(drop_p);
-    p.drop_inv = drop_p > 0.f ? 1.0f / (1.0f - drop_p) : 1.0f;
-    {
-        if (use4) {  // (also where conv8 would take 256 x 256: 768 -> 384 data gradient 206 -> 194 us)
-            static bool attr4_done = false;
-            if (!attr4_done) {
-                if (hipFuncSetAttribute((const void*)conv4_kernel<6>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-                    hipFuncSetAttribute((const void*)conv4_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-                    hipFuncSetAttribute((const void*)conv4_kernel<6, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-                    hipFuncSetAttribute((const void*)conv4_kernel<3, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-                    ig_set_error("conv4: could not reserve 160 KiB of LDS");
-                    return IG_ERR_HIP;
-                }
-                attr4_done = true;
-            }
-            const int grid4 = ig_tile_grid((int)nt4, 1);
-            ig_note_kernel(w_lo ? "conv4_kernel<%d,true>" : "conv4_kernel<%d>", ni4);
-            ig_note_grid(grid4);
-            if (w_lo && ni4 == 6) hipLaunchKernelGGL((conv4_kernel<6, true>), dim3(grid4), dim3(256), C4_OFF_TAB + (tent + 32) * 4, st, p);
-            else if (w_lo) hipLaunchKernelGGL((conv4_kernel<3, true>), dim3(grid4), dim3(256), C4_OFF_TAB + (tent + 32) * 4, st, p);
-            else if (ni4 == 6) hipLaunchKernelGGL(conv4_kernel<6>, dim3(grid4), dim3(256), C4_OFF_TAB + (tent + 32) * 4, st, p);
-            else hipLaunchKernelGGL(conv4_kernel<3>, dim3(grid4), dim3(256), C4_OFF_TAB + (tent + 32) * 4, st, p);
-            return ig_check_launch("conv4");
-        }
+    p.drop_inv = ig_drop_inv(drop_p);
+    if (use4) {  // (also where conv8 would take 256 x 256: 768 -> 384 data gradient 206 -> 194 us)
+        const dim3 grid4(ig_tile_grid((int)nt4, 1)), block4(256);
+        const int smem4 = C4_OFF_TAB + (tent + 32) * 4;
+        ig_note_kernel(w_lo ? "conv4_kernel<%d,true>" : "conv4_kernel<%d>", ni4);
+        ig_note_grid((int)grid4.x);
+        if (w_lo) return ni4 == 6 ? ig_launch<conv4_kernel<6, true>>("conv4", grid4, block4, smem4, st, p) : ig_launch<conv4_kernel<3, true>>("conv4", grid4, block4, smem4, st, p);
+        return ni4 == 6 ? ig_launch<conv4_kernel<6>>("conv4", grid4, block4, smem4, st, p) : ig_launch<conv4_kernel<3>>("conv4", grid4, block4, smem4, st, p);
     }
     const int grid = ig_tile_grid((int)ntiles, 1);
     switch (best) {

@@ -400,11 +400,6 @@ __global__ __launch_bounds__(CD_TPB, 2) void conv3x3_direct_kernel(CDParams p) {
 template <int C, int NCLS = 0>
 int launch_direct(CDParams p, hipStream_t st, const char* what, double* stat_sums = nullptr) {
     using G = CDCfg<C>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        (void)hipFuncSetAttribute((const void*)conv3x3_direct_kernel<C, NCLS>, hipFuncAttributeMaxDynamicSharedMemorySize, G::SMEM);
-        attr_done = true;
-    }
     long nwg = 512;  // two persistent workgroups per CU
     if (nwg > p.ntiles) nwg = p.ntiles;
     if (stat_sums) {
@@ -415,7 +410,8 @@ int launch_direct(CDParams p, hipStream_t st, const char* what, double* stat_sum
         }
     }
     ig_note_kernel("conv3x3_direct_kernel<%d,%d>", C, NCLS);
-    hipLaunchKernelGGL((conv3x3_direct_kernel<C, NCLS>), dim3((unsigned)nwg), dim3(CD_TPB), G::SMEM, st, p);
+    const int rc = ig_launch<conv3x3_direct_kernel<C, NCLS>>(what, dim3((unsigned)nwg), dim3(CD_TPB), G::SMEM, st, p);
+    if (rc != IG_OK) return rc;
     if (stat_sums) hipLaunchKernelGGL((bn_part_fold_kernel<double>), dim3(ig_cdiv(2 * C, 64)), dim3(1024), 0, st, p.stats_part, stat_sums, (int)nwg, 2 * C);
     return ig_check_launch(what);
 }
@@ -676,11 +672,6 @@ int launch_direct_split(CDParams p, CDSplit q, hipStream_t st, const char* what,
     using G = CDCfg<C>;
     constexpr int smem = 2 * G::W_BYTES + 2 * (G::H_BYTES + 16) + 3 * C * 4;
     static_assert(smem <= 160 * 1024, "hi + lo images must fit the LDS");
-    static bool attr_done = false;
-    if (!attr_done) {
-        (void)hipFuncSetAttribute((const void*)conv3x3_direct_split_kernel<C>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-        attr_done = true;
-    }
     long nwg = ig_cu_count();  // one persistent workgroup per CU
     if (nwg > p.ntiles) nwg = p.ntiles;
     if (stat_sums) {
@@ -691,7 +682,8 @@ int launch_direct_split(CDParams p, CDSplit q, hipStream_t st, const char* what,
         }
     }
     ig_note_kernel("conv3x3_direct_split_kernel<%d>", C);
-    hipLaunchKernelGGL((conv3x3_direct_split_kernel<C>), dim3((unsigned)nwg), dim3(512), smem, st, p, q);
+    const int rc = ig_launch<conv3x3_direct_split_kernel<C>>(what, dim3((unsigned)nwg), dim3(512), smem, st, p, q);
+    if (rc != IG_OK) return rc;
     // this kernel keeps fp32 partials centred on the bias, added back after the fp64 fold.  The per-lane data pivot of the other direct
     // kernels (LaneStats) changed this kernel's stored outputs at full-size batches, for a reason not yet understood; until it is, an
     // output mean carried by the input rather than the bias loses (mean / std)^2 ulps of the variance here (tests: xfail)
@@ -1605,14 +1597,20 @@ __global__ __launch_bounds__(576, 1) void convT_dgrad_direct_kernel(CTDParams p,
 }  // namespace
 IG_DET_TU(conv_direct)  // constant-memory descriptor of the deterministic-reduction mode (common.h)
 
-static const bf16_t* cd_zero_page() {
+// NULL (and the error text, under the entry point's name) when it cannot be allocated
+static const bf16_t* cd_zero_page(const char* entry) {
     static void* z = nullptr;
     if (!z) {
-        if (hipMalloc(&z, 256) != hipSuccess) return nullptr;
+        if (hipMalloc(&z, 256) != hipSuccess) {
+            ig_set_error("%s: could not allocate the zero page", entry);
+            return nullptr;
+        }
         (void)hipMemset(z, 0, 256);
     }
     return (const bf16_t*)z;
 }
+// IG_CONV_DIRECT: 0 = off (the implicit GEMMs and conv8.hip serve these shapes), 1 = default
+static bool cd_enabled() { return ig_env_int("IG_CONV_DIRECT", 1) != 0; }
 
 // Called by ig_conv3x3_fwd / ig_conv3x3_dgrad (gemm.hip) for the shapes this kernel covers; returns IG_ERR_UNSUPPORTED
 // (without setting the error string) when it does not, and the caller falls through to the implicit GEMM.
@@ -1639,9 +1637,7 @@ int ig_conv3x3_direct(const void* x, const void* w, const float* bias, const flo
                       int B, int H, int W, int Cin, int Cout, int dgrad, unsigned drop_seed, const unsigned* drop_seed_dev,
                       float drop_p, void* stream, double* stat_sums, int* stats_fused) {
     if (stats_fused) *stats_fused = 0;
-    const char* e_dir = getenv("IG_CONV_DIRECT");  // read per call, like every engine switch (tests set it for single calls)
-    const int enabled = e_dir ? atoi(e_dir) : 1;
-    if (!enabled || Cin != Cout || (Cin != 48 && Cin != 96)) return IG_ERR_UNSUPPORTED;
+    if (!cd_enabled() || Cin != Cout || (Cin != 48 && Cin != 96)) return IG_ERR_UNSUPPORTED;
     if ((long)B * H * W * Cin >= (1L << 31)) return IG_ERR_UNSUPPORTED;  // 32-bit halo offsets
     CDParams p{};
     p.x = (const bf16_t*)x, p.w = (const bf16_t*)w, p.y = (bf16_t*)y;
@@ -1652,22 +1648,14 @@ int ig_conv3x3_direct(const void* x, const void* w, const float* bias, const flo
     p.dgrad = dgrad;
     p.drop_seed = drop_seed, p.drop_seed_dev = drop_seed_dev;
     p.drop_thresh = ig_drop_thresh16(drop_p);
-    p.drop_inv = drop_p > 0.f ? 1.0f / (1.0f - drop_p) : 1.0f;
+    p.drop_inv = ig_drop_inv(drop_p);
     if (p.ntiles == 0) return IG_OK;
     if (Cin == 96) {
         p.tiles_y = (H + 7) / 8;  // 8 x 16 tiles
         p.ntiles = (long)B * p.tiles_x * p.tiles_y;
         constexpr int smem96 = 48 * (27 * 64 + 32) + 2 * 34 * 1024 + 3 * 48 * 4;
-        const bf16_t* zp = cd_zero_page();
-        if (!zp) {
-            ig_set_error("ig_conv3x3: could not allocate the zero page");
-            return IG_ERR_HIP;
-        }
-        static bool attr96 = false;
-        if (!attr96) {
-            (void)hipFuncSetAttribute((const void*)conv3x3_direct_slice_kernel<96>, hipFuncAttributeMaxDynamicSharedMemorySize, smem96);
-            attr96 = true;
-        }
+        const bf16_t* zp = cd_zero_page("ig_conv3x3");
+        if (!zp) return IG_ERR_HIP;
         const long nwg = p.ntiles < 128 ? p.ntiles : 128;
         const bool st96 = stat_sums && stats_fused && !dgrad;
         if (st96) {
@@ -1678,12 +1666,12 @@ int ig_conv3x3_direct(const void* x, const void* w, const float* bias, const flo
             }
             *stats_fused = 1;
         }
+        const char* what = dgrad ? "ig_conv3x3_dgrad(direct, slices)" : "ig_conv3x3_fwd(direct, slices)";
         ig_note_kernel("conv3x3_direct_slice_kernel<96>");
-        hipLaunchKernelGGL(conv3x3_direct_slice_kernel<96>, dim3((unsigned)nwg, 2), dim3(576), smem96, (hipStream_t)stream, p, zp);
-        if (st96)
-            hipLaunchKernelGGL((bn_part_fold_kernel<double>), dim3(ig_cdiv(2 * 96, 64)), dim3(1024), 0, (hipStream_t)stream, p.stats_part, stat_sums, (int)nwg,
-                               2 * 96);
-        return ig_check_launch(dgrad ? "ig_conv3x3_dgrad(direct, slices)" : "ig_conv3x3_fwd(direct, slices)");
+        const int rc = ig_launch<conv3x3_direct_slice_kernel<96>>(what, dim3((unsigned)nwg, 2), dim3(576), smem96, (hipStream_t)stream, p, zp);
+        if (rc != IG_OK || !st96) return rc;
+        return ig_launch<bn_part_fold_kernel<double>>(what, dim3(ig_cdiv(2 * 96, 64)), dim3(1024), 0, (hipStream_t)stream, p.stats_part, stat_sums, (int)nwg,
+                                                      2 * 96);
     }
     const bool st = stat_sums && stats_fused && !dgrad;
     if (st) *stats_fused = 1;
@@ -1696,9 +1684,7 @@ int ig_conv3x3_direct_split(const void* x_hi, const void* x_lo, const void* w_hi
                             const float* bn_shift, void* y_hi, void* y_lo, int B, int H, int W, int Cin, int Cout, int dgrad, unsigned drop_seed,
                             const unsigned* drop_seed_dev, float drop_p, void* stream, double* stat_sums, int* stats_fused) {
     if (stats_fused) *stats_fused = 0;
-    const char* e_dir = getenv("IG_CONV_DIRECT");  // read per call, like every engine switch (tests set it for single calls)
-    const int enabled = e_dir ? atoi(e_dir) : 1;
-    if (!enabled || Cin != Cout || Cin != 48 || !x_lo || !w_lo || !y_lo) return IG_ERR_UNSUPPORTED;
+    if (!cd_enabled() || Cin != Cout || Cin != 48 || !x_lo || !w_lo || !y_lo) return IG_ERR_UNSUPPORTED;
     if ((long)B * H * W * Cin >= (1L << 31)) return IG_ERR_UNSUPPORTED;  // 32-bit halo offsets
     CDParams p{};
     p.x = (const bf16_t*)x_hi, p.w = (const bf16_t*)w_hi, p.y = (bf16_t*)y_hi;
@@ -1709,7 +1695,7 @@ int ig_conv3x3_direct_split(const void* x_hi, const void* x_lo, const void* w_hi
     p.dgrad = dgrad;
     p.drop_seed = drop_seed, p.drop_seed_dev = drop_seed_dev;
     p.drop_thresh = ig_drop_thresh16(drop_p);
-    p.drop_inv = drop_p > 0.f ? 1.0f / (1.0f - drop_p) : 1.0f;
+    p.drop_inv = ig_drop_inv(drop_p);
     if (p.ntiles == 0) return IG_OK;
     const CDSplit q{(const bf16_t*)x_lo, (const bf16_t*)w_lo, (bf16_t*)y_lo};
     const bool st = stat_sums && stats_fused && !dgrad;
@@ -1720,10 +1706,8 @@ int ig_conv3x3_direct_split(const void* x_hi, const void* x_lo, const void* w_hi
 // Called by ig_conv3x3_wgrad (gemm.hip); IG_ERR_UNSUPPORTED when the shape is not covered.
 int ig_conv3x3_wgrad_direct(const void* dy, const void* x, float* dw, float* dbias, int* bias_fused, int B, int H, int W, int Cin,
                             int Cout, void* stream) {
-    const char* e_dir = getenv("IG_CONV_DIRECT");  // read per call, like every engine switch (tests set it for single calls)
-    const int enabled = e_dir ? atoi(e_dir) : 1;
     *bias_fused = 0;
-    if (!enabled || Cout % 48 != 0 || (Cin != 48 && Cin != 96 && Cin != 192)) return IG_ERR_UNSUPPORTED;
+    if (!cd_enabled() || Cout % 48 != 0 || (Cin != 48 && Cin != 96 && Cin != 192)) return IG_ERR_UNSUPPORTED;
     if ((long)B * H * W * (Cin > Cout ? Cin : Cout) >= (1L << 31)) return IG_ERR_UNSUPPORTED;
     CWParams p{};
     p.x = (const bf16_t*)x, p.dy = (const bf16_t*)dy, p.dw = dw, p.dbias = nullptr;
@@ -1736,36 +1720,24 @@ int ig_conv3x3_wgrad_direct(const void* dy, const void* x, float* dw, float* dbi
     p.ntiles = (long)B * p.tiles_x * p.tiles_y;
     p.dbias = dbias;
     *bias_fused = dbias != nullptr;
-    const bf16_t* zp = cd_zero_page();
-    if (!zp) {
-        ig_set_error("ig_conv3x3_wgrad: could not allocate the zero page");
-        return IG_ERR_HIP;
-    }
+    const bf16_t* zp = cd_zero_page("ig_conv3x3_wgrad");
+    if (!zp) return IG_ERR_HIP;
     constexpr int smem48b = 3 * 42 * 1024, smem96 = 3 * 52 * 1024, smem192 = 3 * 50 * 1024;
-    static bool attr_done = false;
-    if (!attr_done) {
-        (void)hipFuncSetAttribute((const void*)conv3x3_wgrad_dma_kernel<48, 12>, hipFuncAttributeMaxDynamicSharedMemorySize, smem48b);
-        (void)hipFuncSetAttribute((const void*)conv3x3_wgrad_dma_kernel<96, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, smem96);
-        (void)hipFuncSetAttribute((const void*)conv3x3_wgrad_dma_kernel<192, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, smem192);
-        attr_done = true;
-    }
     const int nslices = Cout / 48;
     long nwg = 256 / nslices;
     if (nwg > p.ntiles) nwg = p.ntiles;
-    const dim3 grid((unsigned)nwg, nslices);
+    const dim3 grid((unsigned)nwg, nslices), block(512);
+    const char* what = "ig_conv3x3_wgrad(direct, dma)";
     ig_note_kernel("conv3x3_wgrad_dma_kernel<%d,%d>", Cin, Cin == 48 ? rows : Cin == 96 ? 8 : 4);
-    if (Cin == 48) hipLaunchKernelGGL((conv3x3_wgrad_dma_kernel<48, 12>), grid, dim3(512), smem48b, (hipStream_t)stream, p, zp);
-    else if (Cin == 96) hipLaunchKernelGGL((conv3x3_wgrad_dma_kernel<96, 8>), grid, dim3(512), smem96, (hipStream_t)stream, p, zp);
-    else hipLaunchKernelGGL((conv3x3_wgrad_dma_kernel<192, 4>), grid, dim3(512), smem192, (hipStream_t)stream, p, zp);
-    return ig_check_launch("ig_conv3x3_wgrad(direct, dma)");
+    if (Cin == 48) return ig_launch<conv3x3_wgrad_dma_kernel<48, 12>>(what, grid, block, smem48b, (hipStream_t)stream, p, zp);
+    if (Cin == 96) return ig_launch<conv3x3_wgrad_dma_kernel<96, 8>>(what, grid, block, smem96, (hipStream_t)stream, p, zp);
+    return ig_launch<conv3x3_wgrad_dma_kernel<192, 4>>(what, grid, block, smem192, (hipStream_t)stream, p, zp);
 }
 
 // Called by ig_convT_fwd (gemm.hip); IG_ERR_UNSUPPORTED when the shape is not covered.
 int ig_convT_fwd_direct(const void* x, const void* w, const float* bias, void* y, int B, int H, int W, int Cin, int Cout,
                         unsigned drop_seed, const unsigned* drop_seed_dev, float drop_p, void* stream) {
-    const char* e_dir = getenv("IG_CONV_DIRECT");  // read per call, like every engine switch (tests set it for single calls)
-    const int enabled = e_dir ? atoi(e_dir) : 1;
-    if (!enabled || Cin != 96 || Cout != 48) return IG_ERR_UNSUPPORTED;
+    if (!cd_enabled() || Cin != 96 || Cout != 48) return IG_ERR_UNSUPPORTED;
     if ((long)B * H * W * Cin >= (1L << 31)) return IG_ERR_UNSUPPORTED;
     CTParams p{};
     p.x = (const bf16_t*)x, p.w = (const bf16_t*)w, p.y = (bf16_t*)y, p.bias = bias;
@@ -1774,34 +1746,23 @@ int ig_convT_fwd_direct(const void* x, const void* w, const float* bias, void* y
     p.ntiles = (long)B * p.tiles_x * p.tiles_y;
     p.drop_seed = drop_seed, p.drop_seed_dev = drop_seed_dev;
     p.drop_thresh = ig_drop_thresh16(drop_p);
-    p.drop_inv = drop_p > 0.f ? 1.0f / (1.0f - drop_p) : 1.0f;
+    p.drop_inv = ig_drop_inv(drop_p);
     if (p.ntiles == 0) return IG_OK;
     p.tiles_y = (H + 7) / 8;  // 8 x 16 input tiles
     p.ntiles = (long)B * p.tiles_x * p.tiles_y;
     constexpr int smem_d = 48 * (27 * 64 + 32) + 2 * 34 * 1024 + 48 * 4;
-    const bf16_t* zp = cd_zero_page();
-    if (!zp) {
-        ig_set_error("ig_convT_fwd: could not allocate the zero page");
-        return IG_ERR_HIP;
-    }
-    static bool attr_d = false;
-    if (!attr_d) {
-        (void)hipFuncSetAttribute((const void*)convT_direct_dma_kernel<96, 48>, hipFuncAttributeMaxDynamicSharedMemorySize, smem_d);
-        attr_d = true;
-    }
+    const bf16_t* zp = cd_zero_page("ig_convT_fwd");
+    if (!zp) return IG_ERR_HIP;
     const long nwg_d = p.ntiles < 256 ? p.ntiles : 256;
     ig_note_kernel("convT_direct_dma_kernel<96,48>");
-    hipLaunchKernelGGL((convT_direct_dma_kernel<96, 48>), dim3((unsigned)nwg_d), dim3(576), smem_d, (hipStream_t)stream, p, zp);
-    return ig_check_launch("ig_convT_fwd(direct, dma)");
+    return ig_launch<convT_direct_dma_kernel<96, 48>>("ig_convT_fwd(direct, dma)", dim3((unsigned)nwg_d), dim3(576), smem_d, (hipStream_t)stream, p, zp);
 }
 
 // Called by ig_convT_wgrad (gemm.hip); IG_ERR_UNSUPPORTED when the shape is not covered.
 int ig_convT_wgrad_direct(const void* dy, const void* x, float* dw, float* dbias, int* bias_fused, int B, int H, int W, int Cin,
                           int Cout, void* stream) {
     *bias_fused = 0;
-    const char* e_dir = getenv("IG_CONV_DIRECT");  // read per call, like every engine switch (tests set it for single calls)
-    const int enabled = e_dir ? atoi(e_dir) : 1;
-    if (!enabled || Cin != 96 || Cout != 48) return IG_ERR_UNSUPPORTED;
+    if (!cd_enabled() || Cin != 96 || Cout != 48) return IG_ERR_UNSUPPORTED;
     if ((long)B * H * W * 4 * Cout >= (1L << 31)) return IG_ERR_UNSUPPORTED;
     CTWParams p{};
     p.x = (const bf16_t*)x, p.dy = (const bf16_t*)dy, p.dw = dw;
@@ -1814,26 +1775,15 @@ int ig_convT_wgrad_direct(const void* dy, const void* x, float* dw, float* dbias
     if (p.ntiles == 0) return IG_OK;
     long nwg = p.ntiles < 256 ? p.ntiles : 256;
     constexpr int smem = 3 * 48 * 1024;
-    const bf16_t* zp = cd_zero_page();
-    if (!zp) {
-        ig_set_error("ig_convT_wgrad: could not allocate the zero page");
-        return IG_ERR_HIP;
-    }
-    static bool attr_done = false;
-    if (!attr_done) {
-        (void)hipFuncSetAttribute((const void*)convT_wgrad_dma_kernel<96, 48>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-        attr_done = true;
-    }
+    const bf16_t* zp = cd_zero_page("ig_convT_wgrad");
+    if (!zp) return IG_ERR_HIP;
     ig_note_kernel("convT_wgrad_dma_kernel<96,48>");
-    hipLaunchKernelGGL((convT_wgrad_dma_kernel<96, 48>), dim3((unsigned)nwg), dim3(TW_TPB), smem, (hipStream_t)stream, p, zp);
-    return ig_check_launch("ig_convT_wgrad(direct, dma)");
+    return ig_launch<convT_wgrad_dma_kernel<96, 48>>("ig_convT_wgrad(direct, dma)", dim3((unsigned)nwg), dim3(TW_TPB), smem, (hipStream_t)stream, p, zp);
 }
 
 // Called by ig_convT_dgrad (gemm.hip); IG_ERR_UNSUPPORTED when the shape is not covered.
 int ig_convT_dgrad_direct(const void* dy, const void* w, void* dx, int B, int H, int W, int Cin, int Cout, void* stream) {
-    const char* e_dir = getenv("IG_CONV_DIRECT");  // read per call, like every engine switch (tests set it for single calls)
-    const int enabled = e_dir ? atoi(e_dir) : 1;
-    if (!enabled || Cin != 96 || Cout != 48) return IG_ERR_UNSUPPORTED;
+    if (!cd_enabled() || Cin != 96 || Cout != 48) return IG_ERR_UNSUPPORTED;
     if ((long)B * H * W * 4 * Cout >= (1L << 31)) return IG_ERR_UNSUPPORTED;
     CTDParams p{};
     p.dy = (const bf16_t*)dy, p.w = (const bf16_t*)w, p.dx = (bf16_t*)dx;
@@ -1841,19 +1791,10 @@ int ig_convT_dgrad_direct(const void* dy, const void* w, void* dx, int B, int H,
     p.tiles_x = (W + TW - 1) / TW, p.tiles_y = (H + 3) / 4;
     p.ntiles = (long)B * p.tiles_x * p.tiles_y;
     if (p.ntiles == 0) return IG_OK;
-    const bf16_t* zp = cd_zero_page();
-    if (!zp) {
-        ig_set_error("ig_convT_dgrad: could not allocate the zero page");
-        return IG_ERR_HIP;
-    }
+    const bf16_t* zp = cd_zero_page("ig_convT_dgrad");
+    if (!zp) return IG_ERR_HIP;
     constexpr int smem = 96 * (14 * 64 + 32) + 2 * 32 * 1024 + 16;
-    static bool attr_done = false;
-    if (!attr_done) {
-        (void)hipFuncSetAttribute((const void*)convT_dgrad_direct_kernel<96, 48>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-        attr_done = true;
-    }
     const long nwg = p.ntiles < 256 ? p.ntiles : 256;
     ig_note_kernel("convT_dgrad_direct_kernel<96,48>");
-    hipLaunchKernelGGL((convT_dgrad_direct_kernel<96, 48>), dim3((unsigned)nwg), dim3(576), smem, (hipStream_t)stream, p, zp);
-    return ig_check_launch("ig_convT_dgrad(direct)");
+    return ig_launch<convT_dgrad_direct_kernel<96, 48>>("ig_convT_dgrad(direct)", dim3((unsigned)nwg), dim3(576), smem, (hipStream_t)stream, p, zp);
 }

@@ -1246,15 +1246,10 @@ int launch_gemm(const AL& al, const BL& bl, const EP& ep_in, int M, int N, int K
             }
 #define IG_LAUNCH_V2(NSEG_)                                                                                              \
     {                                                                                                                     \
-        auto kern = gemm2_kernel<AL, BL, EP, A_TR, B_TR, NSEG_>;                                                          \
-        static bool attr_done = false;                                                                                    \
-        if (!attr_done) {                                                                                                 \
-            (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, G2::SMEM);          \
-            attr_done = true;                                                                                             \
-        }                                                                                                                 \
         ig_note_kernel("gemm2_kernel<%s,%s,%s,%s,%s,%d,32,1>", AL::kName, BL::kName, EP::kName, A_TR ? "true" : "false", B_TR ? "true" : "false", NSEG_); \
         ig_note_grid((int)grid.x);                                                                                        \
-        hipLaunchKernelGGL(kern, grid, dim3(NTHR2), G2::SMEM, st, al, bl, ep, M, N, K, tn, ntiles, kchunk, zp);          \
+        const int rc_ = ig_launch<gemm2_kernel<AL, BL, EP, A_TR, B_TR, NSEG_>>(what, grid, dim3(NTHR2), G2::SMEM, st, al, bl, ep, M, N, K, tn, ntiles, kchunk, zp); \
+        if (rc_ != IG_OK) return rc_;                                                                                     \
     }
             if constexpr (EP::kStagedAtomic) {
                 // one tile per workgroup (split-K over blockIdx.y); the fp32 tile is staged through the ring in two halves
@@ -1266,19 +1261,15 @@ int launch_gemm(const AL& al, const BL& bl, const EP& ep_in, int M, int N, int K
                 kchunk = ig_cdiv(nk32, ks);
                 grid.y = ig_cdiv(nk32, kchunk);
                 if (dual) {
-                    auto kern = gemm2_kernel<AL, BL, EP, A_TR, B_TR, 1, 2>;
-                    static bool attr_dual = false;
-                    if (!attr_dual) {
-                        (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * G2::SMEM);
-                        attr_dual = true;
-                    }
                     ig_note_kernel("gemm2_kernel<%s,%s,%s,%s,%s,1,32,2>", AL::kName, BL::kName, EP::kName, A_TR ? "true" : "false", B_TR ? "true" : "false");
                     if (prep_partial((int)grid.y) != IG_OK) return IG_ERR_HIP;
                     {  // 1-D grid, (split, tile) pairs dealt split-major to the XCDs (see gemm2_kernel)
                         ep.pairs = (int)grid.y;
                         grid.x = grid.x * grid.y, grid.y = 1;
                     }
-                    hipLaunchKernelGGL(kern, grid, dim3(2 * NTHR2), 2 * G2::SMEM, st, al, bl, ep, M, N, K, tn, ntiles, kchunk, zp);
+                    const int rc = ig_launch<gemm2_kernel<AL, BL, EP, A_TR, B_TR, 1, 2>>(what, grid, dim3(2 * NTHR2), 2 * G2::SMEM, st, al, bl, ep, M, N, K, tn,
+                                                                                         ntiles, kchunk, zp);
+                    if (rc != IG_OK) return rc;
                     finish_partial();
                     return ig_check_launch(what);
                 }
@@ -1302,19 +1293,14 @@ int launch_gemm(const AL& al, const BL& bl, const EP& ep_in, int M, int N, int K
     dim3 block(NTHR);
 #define IG_LAUNCH_V1K(NSEG_, MT_, NT_, WM_, BKT_)                                                                      \
     {                                                                                                                  \
-        auto kern = gemm_kernel<AL, BL, EP, A_TR, B_TR, NSEG_, MT_, NT_, WM_, BKT_>;                                   \
         constexpr int bme_ = WM_ * MT_ * 16, bne_ = (4 / WM_) * NT_ * 16;                                              \
         constexpr int ta_ = A_TR ? BKT_ * 16 * tr_pitch(bme_ / 8) : BKT_ * 2 * bme_;                                   \
         constexpr int tb_ = B_TR ? BKT_ * 16 * tr_pitch(bne_ / 8) : BKT_ * 2 * bne_;                                   \
         constexpr int ring_ = 2 * (ta_ + tb_), stage_ = EP::kStagedAtomic ? bme_ * 512 : 0;                            \
         constexpr int lds_ = ring_ > stage_ ? ring_ : stage_;                                                          \
-        static bool attr_done = false;                                                                                 \
-        if (!attr_done) {                                                                                              \
-            (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds_);            \
-            attr_done = true;                                                                                          \
-        }                                                                                                              \
         ig_note_kernel("gemm_kernel<%s,%s,%s,%s,%s,%d,%d,%d,%d,%d>", AL::kName, BL::kName, EP::kName, A_TR ? "true" : "false", B_TR ? "true" : "false", NSEG_, MT_, NT_, WM_, BKT_); \
-        hipLaunchKernelGGL(kern, grid, block, lds_, st, al, bl, ep, M, N, K, tn, kchunk);                              \
+        const int rc_ = ig_launch<gemm_kernel<AL, BL, EP, A_TR, B_TR, NSEG_, MT_, NT_, WM_, BKT_>>(what, grid, block, lds_, st, al, bl, ep, M, N, K, tn, kchunk); \
+        if (rc_ != IG_OK) return rc_;                                                                                  \
     }
 #define IG_LAUNCH_V1(NSEG_, MT_, NT_, WM_) IG_LAUNCH_V1K(NSEG_, MT_, NT_, WM_, 64)
     if constexpr (EP::kStagedAtomic) {
@@ -1639,7 +1625,7 @@ int ig_conv3x3_dgrad(const void* dy_hi, const void* dy_lo, const void* w_hi, con
     ep.out_hi = (bf16_t*)dx_hi, ep.out_lo = (bf16_t*)dx_lo, ep.ldo = Cin, ep.mode = 2;
     ep.drop_seed = drop_seed, ep.drop_seed_dev = drop_seed_dev;
     ep.drop_thresh = ig_drop_thresh16(drop_p);
-    ep.drop_inv = drop_p > 0.f ? 1.0f / (1.0f - drop_p) : 1.0f;
+    ep.drop_inv = ig_drop_inv(drop_p);
     return launch_gemm<Conv3Loader, ConvWgtTRLoader, EpGradStore, false, true>(
         al, bl, ep, al.Mtot, Cin, 9 * Cout, 1, dy_lo != nullptr, (hipStream_t)stream, "ig_conv3x3_dgrad");
 }
@@ -1739,7 +1725,7 @@ int ig_convk_dgrad(const void* dy_hi, const void* dy_lo, const void* w_hi, const
     ep.out_hi = (bf16_t*)dx_hi, ep.out_lo = (bf16_t*)dx_lo, ep.ldo = Cin, ep.mode = 2;
     ep.drop_seed = drop_seed, ep.drop_seed_dev = drop_seed_dev;
     ep.drop_thresh = ig_drop_thresh16(drop_p);
-    ep.drop_inv = drop_p > 0.f ? 1.0f / (1.0f - drop_p) : 1.0f;
+    ep.drop_inv = ig_drop_inv(drop_p);
     return launch_gemm<ConvKLoader, ConvWgtTRLoader, EpGradStore, false, true>(
         al, bl, ep, al.Mtot, Cin, KS * KS * Cout, 1, dy_lo != nullptr, (hipStream_t)stream, "ig_convk_dgrad");
 }
@@ -1798,7 +1784,7 @@ int ig_convT_fwd(const void* x_hi, const void* x_lo, const void* w_hi, const voi
     ep.f_hw = make_fdiv(H * W), ep.f_w = make_fdiv(W);
     ep.drop_seed = drop_seed, ep.drop_seed_dev = drop_seed_dev;
     ep.drop_thresh = ig_drop_thresh16(drop_p);
-    ep.drop_inv = drop_p > 0.f ? 1.0f / (1.0f - drop_p) : 1.0f;
+    ep.drop_inv = ig_drop_inv(drop_p);
     return launch_gemm<ConvTFwdALoader, ConvTFwdBLoader, EpStore, false, false>(
         al, bl, ep, al.Mtot, Cout, 4 * Cin, 4, x_lo != nullptr, (hipStream_t)stream, "ig_convT_fwd");
 }

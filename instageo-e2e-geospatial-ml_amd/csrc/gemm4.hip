@@ -289,28 +289,12 @@ __global__ __launch_bounds__(256) void gemm4_kernel(G8Params p) {
     }
 }
 
-// IG_GEMM4: 0 = off (gemm8.hip serves every shape), 1 = default
-inline int g4_env() {
-    const char* e = getenv("IG_GEMM4");
-    return e ? atoi(e) : 1;
-}
-
 template <int KIND, int ACT, bool DACT, int NSEG = 1>
 int g4_launch(const G8Params& p, int grid, hipStream_t st) {
-    auto kern = gemm4_kernel<KIND, ACT, DACT, NSEG>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, G4_SMEM) != hipSuccess) {
-            ig_set_error("gemm4: could not reserve %d bytes of LDS", G4_SMEM);
-            return IG_ERR_HIP;
-        }
-        attr_done = true;
-    }
     if (NSEG == 1) ig_note_kernel("gemm4_kernel<%d,%d,%s>", KIND, ACT, DACT ? "true" : "false");
     else ig_note_kernel("gemm4_kernel<%d,%d,%s,%d>", KIND, ACT, DACT ? "true" : "false", NSEG);
     ig_note_grid(grid);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), G4_SMEM, st, p);
-    return ig_check_launch("gemm4");
+    return ig_launch<gemm4_kernel<KIND, ACT, DACT, NSEG>>("gemm4", dim3(grid), dim3(256), G4_SMEM, st, p);
 }
 
 }  // namespace
@@ -318,28 +302,26 @@ IG_DET_TU(gemm4)  // constant-memory descriptor of the deterministic-reduction m
 
 // IG_ERR_UNSUPPORTED (no error string) when the shape / mode is not covered: ig_gemm8_nt goes on to its own instances.
 int ig_gemm4_nt(const G8Params& p, void* stream) {
-    if (!g4_env()) return IG_ERR_UNSUPPORTED;
+    const int g4_env = ig_env_int("IG_GEMM4", 1);  // 0 = off (gemm8.hip serves every shape), 1 = default, 2 = every kind and tile count it has
+    if (!g4_env) return IG_ERR_UNSUPPORTED;
     if (p.M <= 0 || (p.nseg != 1 && p.nseg != 3)) return IG_ERR_UNSUPPORTED;
     const bool split = p.nseg == 3;  // bf16x3: (a[0], b[0]) = hi hi, (a[1], b[1]) = hi lo, (a[2], b[2]) = lo hi  (gemm8.hip)
     if (split) {
         // the paired form needs both lo tensors above their hi tensors, 16-byte aligned, near enough for the 32-bit lane offsets (ops.BT allocates
         // hi and lo as one block); IG_G8_PAIR=0 (the three-pass A/B arm of gemm8.hip) also keeps the split mode off this engine
-        const char* e = getenv("IG_G8_PAIR");
-        const long dA = (const char*)p.a[2] - (const char*)p.a[0], dB = (const char*)p.b[1] - (const char*)p.b[0];
-        const bool pair = (!e || atoi(e) != 0) && dA > 0 && dB > 0 && !(dA & 15) && !(dB & 15) && dA + 257L * p.lda * 2 < (1L << 32) &&
-                          dB + 257L * p.ldb * 2 < (1L << 32);
-        if (!pair) return IG_ERR_UNSUPPORTED;
+        const long dA = ig_pair_dist(p.a[0], p.a[2]), dB = ig_pair_dist(p.b[0], p.b[1]);
+        if (!dA || !dB || dA + 257L * p.lda * 2 >= (1L << 32) || dB + 257L * p.ldb * 2 >= (1L << 32)) return IG_ERR_UNSUPPORTED;
     }
     if ((p.N & 255) || (p.K & 127) || p.K < 256) return IG_ERR_UNSUPPORTED;  // 256-wide tiles; an even number (>= 4) of K-tiles
     if (p.lda * 2 >= (1L << 24) || p.ldb * 2 >= (1L << 24)) return IG_ERR_UNSUPPORTED;  // 24-bit offset multiply
     if ((p.lda & 7) || (p.ldb & 7) || (p.ldo & 7) || ((uintptr_t)p.a[0] & 15) || ((uintptr_t)p.b[0] & 15)) return IG_ERR_UNSUPPORTED;
     const int ntiles = ((p.M + 255) >> 8) * (p.N >> 8);
-    if (ntiles < 128 && g4_env() != 2) return IG_ERR_UNSUPPORTED;  // below one tile per CU the 128 x 128 instance of gemm8.hip takes over (as there)
+    if (ntiles < 128 && g4_env != 2) return IG_ERR_UNSUPPORTED;  // below one tile per CU the 128 x 128 instance of gemm8.hip takes over (as there)
     // Routing by measurement (same-process A/B at M = 42552, profiles/r06_gemm4_ring_vs_stages.txt): the plain bf16 store (qkv -4 %, the N = 768 /
     // K = 3072 data gradient -9 %), the fp32 residual kind (fc2 -8 %, proj -4 %) and dx * gelu' (-6 %) win; the GELU epilogues are bound by VALU
     // issue -- one wave per SIMD issues a vector instruction every 4 cycles where the two co-resident waves of gemm8.hip issue one every 2 --
     // and come out equal (+0.5 %): they stay on the 8-phase engine.  IG_GEMM4=2 forces every kind this engine has (tests).
-    if (g4_env() != 2 && p.act != 0) return IG_ERR_UNSUPPORTED;
+    if (g4_env != 2 && p.act != 0) return IG_ERR_UNSUPPORTED;
     const int grid = ig_tile_grid(ntiles, 1);
     hipStream_t st = (hipStream_t)stream;
     if (p.kind == 0) {

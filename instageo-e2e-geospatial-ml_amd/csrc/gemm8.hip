@@ -585,29 +585,13 @@ __global__ __launch_bounds__(128 * WC, 2) void gemm8_kernel(G8Params p) {
 #undef G8_INIT_ACC
 }
 
-// IG_GEMM8: 0 = off, 1 = default (shapes with enough tiles), 2 = every covered shape.  Read per call (tests and A/B benches flip it).
-inline int g8_env() {
-    const char* e = getenv("IG_GEMM8");
-    return e ? atoi(e) : 1;
-}
-
 template <int KIND, int NSEG, int ACT, bool DACT, bool SPLIT_OUT, int SCHED = 1, int MT = 4, int WC = 4>
 int g8_launch_v(const G8Params& p, int grid, hipStream_t st) {
     using Geo = G8Geo<MT, WC>;
-    auto kern = gemm8_kernel<KIND, NSEG, ACT, DACT, SPLIT_OUT, SCHED, MT, WC>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, Geo::SMEM) != hipSuccess) {
-            ig_set_error("gemm8: could not reserve %d bytes of LDS", Geo::SMEM);
-            return IG_ERR_HIP;
-        }
-        attr_done = true;
-    }
     if (MT == 4) ig_note_kernel("gemm8_kernel<%d,%d,%d,%s,%s,%d>", KIND, NSEG, ACT, DACT ? "true" : "false", SPLIT_OUT ? "true" : "false", SCHED);
     else ig_note_kernel("gemm8_kernel<%d,%d,%d,%s,%s,%d,%d,%d>", KIND, NSEG, ACT, DACT ? "true" : "false", SPLIT_OUT ? "true" : "false", SCHED, MT, WC);
     ig_note_grid(grid);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(Geo::NTHR), Geo::SMEM, st, p);
-    return ig_check_launch("gemm8");
+    return ig_launch<gemm8_kernel<KIND, NSEG, ACT, DACT, SPLIT_OUT, SCHED, MT, WC>>("gemm8", dim3(grid), dim3(Geo::NTHR), Geo::SMEM, st, p);
 }
 
 // small = the 128 x 128 instance (two workgroups per CU): it keeps the round-2 placement of the LDS-DMA issues (SCHED 2: with schedule 4 its
@@ -624,7 +608,8 @@ IG_DET_TU(gemm8)  // constant-memory descriptor of the deterministic-reduction m
 
 // IG_ERR_UNSUPPORTED (no error string) when the shape is not covered: the caller falls back to the generic engines.
 int ig_gemm8_nt(const G8Params& p, void* stream) {
-    if (!g8_env()) return IG_ERR_UNSUPPORTED;
+    const int g8_env = ig_env_int("IG_GEMM8", 1);  // 0 = off, 1 = default (shapes with enough tiles), 2 = every covered shape
+    if (!g8_env) return IG_ERR_UNSUPPORTED;
     if (p.M <= 0 || p.N <= 0 || p.K <= 0) return IG_ERR_UNSUPPORTED;
     // (Round 6, measured and removed -- profiles/r06_tail_round_split.txt: sending the row tiles of a nearly empty last round to a second launch
     // on the 128 x 128 instance.  At M = 22064 (B = 112: 783 tiles = 3.06 rounds) qkv 86.4 -> 80.6 us, fc2 127.8 -> 123.1, but proj 47.1 -> 50.1 and
@@ -642,7 +627,7 @@ int ig_gemm8_nt(const G8Params& p, void* stream) {
     // YAML's batch 16 (117-156 tiles: 1707 -> 1770 chips/s) and for the 300M model at B = 54 (168 tiles: 1200 -> 1279), neutral at
     // B = 32 / 48 / 108; 96 starts to lose at B = 48.  Below it (and for N = 128 mod 256) the 128 x 128 instance takes over: four
     // times the tiles, two workgroups per CU.
-    const bool small = ntiles256 < min_tiles && g8_env() != 2;
+    const bool small = ntiles256 < min_tiles && g8_env != 2;
     // (Round 4, measured and not kept: taking the 128 x 128 instance whenever its round count beats the big one's by a cost model --
     // 261 tiles of 256 x 256 on 256 CUs are two rounds for 1.02 rounds of work at B = 112, 1044 quarter-tiles are three rounds of 512 --
     // made the cliff WORSE: 4142 -> 4005 chips/s at B = 112, 4599 -> 4343 at B = 221; a small-instance round costs more than half a big one.)
@@ -654,9 +639,8 @@ int ig_gemm8_nt(const G8Params& p, void* stream) {
     // for the 32-bit lane offsets (largest: 255 rows + one row + the distance).  IG_G8_PAIR=0: the three-pass form (A/B runs)
     bool pair = false;
     if (split_in) {
-        const char* e = getenv("IG_G8_PAIR");
-        const long dA = (const char*)p.a[2] - (const char*)p.a[0], dB = (const char*)p.b[1] - (const char*)p.b[0];
-        pair = (!e || atoi(e) != 0) && dA > 0 && dB > 0 && !(dA & 15) && !(dB & 15) && dA + 257L * p.lda * 2 < (1L << 32) && dB + 257L * p.ldb * 2 < (1L << 32);
+        const long dA = ig_pair_dist(p.a[0], p.a[2]), dB = ig_pair_dist(p.b[0], p.b[1]);
+        pair = dA && dB && dA + 257L * p.lda * 2 < (1L << 32) && dB + 257L * p.ldb * 2 < (1L << 32);
     }
     if (p.kind == 0) {
         const bool split_out = p.out_lo != nullptr;

@@ -584,10 +584,6 @@ const bf16_t* w_zero_page() {
     }
     return (const bf16_t*)z[dev];
 }
-inline int wg8_env() {  // IG_WGRAD8: 0 = off (the BK = 32 ring engine of gemm.hip), 1 = default.  Read per call (A/B runs, tests).
-    const char* e = getenv("IG_WGRAD8");
-    return e ? atoi(e) : 1;
-}
 
 struct TileRef {  // one output tile of the launch
     int g;         // GEMM (pointer set)
@@ -598,47 +594,26 @@ struct TileRef {  // one output tile of the launch
     int tap, jcol0;
 };
 
-inline int wg4_env() {  // IG_GEMM4 (shared with gemm4.hip): 0 = the 8-wave kernel for the linears too (tests, A/B runs), otherwise gemm4w_kernel
-    const char* e = getenv("IG_GEMM4");
-    return e ? atoi(e) : 1;
-}
-
 template <int NSEG, int MODE, int MT, int NT1, bool TRANS>
 int w_launch(const WPlan& pl, float* ws, const bf16_t* zp, const WArgs& args, const WConv& cv, const WDw& dws, int overwrite, hipStream_t st) {
     if constexpr (MODE == 0 && MT == 4 && NT1 == 2 && !TRANS) {
-        if (pl.min_nkt >= 2 && wg4_env()) {
-            static bool attr4_done = false;
-            if (!attr4_done) {
-                if (hipFuncSetAttribute((const void*)gemm4w_kernel<NSEG == 2>, hipFuncAttributeMaxDynamicSharedMemorySize, W4_SMEM) != hipSuccess) {
-                    ig_set_error("gemm4w: could not reserve %d bytes of LDS", W4_SMEM);
-                    return IG_ERR_HIP;
-                }
-                attr4_done = true;
-            }
+        // IG_GEMM4 (shared with gemm4.hip): 0 = the 8-wave kernel for the linears too (tests, A/B runs), otherwise gemm4w_kernel
+        if (pl.min_nkt >= 2 && ig_env_int("IG_GEMM4", 1)) {
             ig_note_kernel("gemm4w_kernel<%s>", NSEG == 2 ? "true" : "false");
             ig_note_grid(pl.nwg);
-            hipLaunchKernelGGL(gemm4w_kernel<NSEG == 2>, dim3(pl.nwg), dim3(256), W4_SMEM, st, (const WSeg*)pl.segs, ws, args);
-            hipLaunchKernelGGL((wgrad8_reduce_kernel<4, 2, false, true>), dim3(64, pl.ntiles), dim3(256), 0, st, (const WTile*)pl.tiles,
-                               (const float4*)ws, dws, overwrite, 0, 0);
-            return ig_check_launch("gemm4w");
+            const int rc = ig_launch<gemm4w_kernel<NSEG == 2>>("gemm4w", dim3(pl.nwg), dim3(256), W4_SMEM, st, (const WSeg*)pl.segs, ws, args);
+            if (rc != IG_OK) return rc;
+            return ig_launch<wgrad8_reduce_kernel<4, 2, false, true>>("gemm4w", dim3(64, pl.ntiles), dim3(256), 0, st, (const WTile*)pl.tiles,
+                                                                      (const float4*)ws, dws, overwrite, 0, 0);
         }
-    }
-    auto kern = gemm8w_kernel<NSEG, MODE, MT, NT1>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, W_SMEM) != hipSuccess) {
-            ig_set_error("gemm8w: could not reserve %d bytes of LDS", W_SMEM);
-            return IG_ERR_HIP;
-        }
-        attr_done = true;
     }
     ig_note_kernel("gemm8w_kernel<%d,%d,%d,%d>", NSEG, MODE, MT, NT1);
     ig_note_grid(pl.nwg);
-    hipLaunchKernelGGL(kern, dim3(pl.nwg), dim3(512), W_SMEM, st, (const WSeg*)pl.segs, ws, zp, args, cv);
+    const int rc = ig_launch<gemm8w_kernel<NSEG, MODE, MT, NT1>>("gemm8w", dim3(pl.nwg), dim3(512), W_SMEM, st, (const WSeg*)pl.segs, ws, zp, args, cv);
+    if (rc != IG_OK) return rc;
     constexpr int NA = 2 * (2 + NT1) * MT;
-    hipLaunchKernelGGL((wgrad8_reduce_kernel<MT, NT1, TRANS>), dim3(NA * 2, pl.ntiles), dim3(256), 0, st, (const WTile*)pl.tiles, (const float4*)ws,
-                       dws, overwrite, cv.Cout_t, cv.Cin_t);
-    return ig_check_launch("gemm8w");
+    return ig_launch<wgrad8_reduce_kernel<MT, NT1, TRANS>>("gemm8w", dim3(NA * 2, pl.ntiles), dim3(256), 0, st, (const WTile*)pl.tiles,
+                                                           (const float4*)ws, dws, overwrite, cv.Cout_t, cv.Cin_t);
 }
 
 // Plan (cached by `key`) + launch.  tiles: the output tiles of the launch; every tile reduces over the same M tokens.
@@ -844,7 +819,8 @@ int w_run(const WKey& key, const std::vector<TileRef>& tl, int M, int lda2_of_g[
 // ig_linear_wgrad per GEMM.
 int ig_wgrad8_group(int n, const void* const* dy_hi, const void* const* dy_lo, const void* const* x_hi, const void* const* x_lo,
                     float* const* dw, const int* N, const int* K, int M, int overwrite, void* stream) {
-    if (!wg8_env() || n <= 0 || n > W_MAXG || M <= 0) return IG_ERR_UNSUPPORTED;
+    // IG_WGRAD8: 0 = off (the BK = 32 ring engine of gemm.hip), 1 = default
+    if (!ig_env_int("IG_WGRAD8", 1) || n <= 0 || n > W_MAXG || M <= 0) return IG_ERR_UNSUPPORTED;
     const bool split = dy_lo && dy_lo[0];
     WArgs args{};
     WDw dws{};
@@ -900,10 +876,9 @@ static bool c8w_pays(int kind, bool swap, bool split, int Cin, int Cout, double 
 // string) when the shape is not covered.
 int ig_wgrad8_conv(int kind, const void* dy_hi, const void* dy_lo, const void* x_hi, const void* x_lo, float* dw, int B, int H, int W,
                    int Cin, int Cout, void* stream) {
-    const int env = wg8_env();
+    const int env = ig_env_int("IG_WGRAD8", 1);
     if (!env || B <= 0) return IG_ERR_UNSUPPORTED;
-    const char* ce = getenv("IG_WGRAD8_CONV");  // 0: off, 1: default, 2: every covered shape
-    const int cenv = ce ? atoi(ce) : 1;
+    const int cenv = ig_env_int("IG_WGRAD8_CONV", 1);  // 0: off, 1: default, 2: every covered shape
     if (!cenv) return IG_ERR_UNSUPPORTED;
     if ((Cin % 8) || (Cout % 8)) return IG_ERR_UNSUPPORTED;
     const bool split = dy_lo != nullptr;

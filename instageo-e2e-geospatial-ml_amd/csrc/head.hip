@@ -1092,8 +1092,6 @@ __global__ __launch_bounds__(TPB) void confusion_kernel(const long long* __restr
         if (hist[i]) atomicAdd(confusion + i, (unsigned long long)hist[i]);
 }
 
-inline uint32_t thresh_of(float p) { return ig_drop_thresh16(p); }
-
 }  // namespace
 IG_DET_TU(head)  // constant-memory descriptor of the deterministic-reduction mode (common.h)
 
@@ -1109,15 +1107,9 @@ static int classifier_fwd_impl(const void* f_hi, const void* f_lo, const float* 
     const int cmax = C / 8 < CLS_CHUNK / 8 ? C / 8 : CLS_CHUNK / 8;
     size_t sm = ((size_t)ncls * C + ((ncls + 3) & ~3) + (bn_scale ? 2 * (size_t)C : 0)) * sizeof(float) + (size_t)TPB * (cmax * 16 + 16) * (f_lo ? 2 : 1);
     IG_REQUIRE(sm <= 160 * 1024, "ig_classifier_fwd: ncls x C = %d x %d weights do not fit the LDS", ncls, C);
-    static bool attr_done = false;
-    if (!attr_done) {
-        (void)hipFuncSetAttribute((const void*)classifier_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_done = true;
-    }
-    hipLaunchKernelGGL(classifier_fwd_kernel, dim3((unsigned)((M + TPB - 1) / TPB)), dim3(TPB), sm, (hipStream_t)stream,
-                       (const bf16_t*)f_hi, (const bf16_t*)f_lo, w, bias, logits, M, HW, C, ncls, drop_seed, drop_seed_dev, thresh_of(drop_p),
-                       drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f, bn_scale, bn_shift);
-    return ig_check_launch("ig_classifier_fwd");
+    return ig_launch<classifier_fwd_kernel>("ig_classifier_fwd", dim3((unsigned)((M + TPB - 1) / TPB)), dim3(TPB), (int)sm, (hipStream_t)stream,
+                                            (const bf16_t*)f_hi, (const bf16_t*)f_lo, w, bias, logits, M, HW, C, ncls, drop_seed, drop_seed_dev,
+                                            ig_drop_thresh16(drop_p), ig_drop_inv(drop_p), bn_scale, bn_shift);
 }
 
 int ig_classifier_fwd(const void* f_hi, const void* f_lo, const float* w, const float* bias, float* logits, int B, long HW, int C,
@@ -1164,22 +1156,17 @@ static int classifier_bwd_impl(int mode, ClsBn bn, int* nwg_out, const float* dl
     const long ig_max = wide ? 32 : 8;
     ig = ig < 8 ? 8 : ig > ig_max ? ig_max : ig & ~7L;  // whole trips of the prefetching loop (4 pixels)
     const size_t sm = (32 + (size_t)CLS_SLAB + (size_t)nc * ig * nsl) * sizeof(float);
-    const float inv = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f;
+    const float inv = ig_drop_inv(drop_p);
     constexpr bool sform = true;  // the reduce pass runs in S form at every class count (round 4: 111 -> 83 us at 2 classes)
     // narrow heads (C = 16 with > 8 classes, C = 8 with > 4) stage more than the default 64 KiB limit of dynamic LDS: 32 KiB slab + ig >= 8
-    // groups of nc x nsl floats; every instantiation raises its limit once (as classifier_fwd_kernel does)
+    // groups of nc x nsl floats
 #define IG_CLS_BWD(NC, VEC, MD, GY)                                                                                                      \
     do {                                                                                                                                 \
-        auto kern_ = cls_bwd_kernel<NC, VEC, MD>;                                                                                        \
-        static bool attr_done_ = false;                                                                                                  \
-        if (!attr_done_) {                                                                                                               \
-            IG_REQUIRE(hipFuncSetAttribute((const void*)kern_, hipFuncAttributeMaxDynamicSharedMemorySize, 128 << 10) == hipSuccess,     \
-                       "ig_classifier_bwd: could not raise the dynamic LDS limit%s", "");                                               \
-            attr_done_ = true;                                                                                                           \
-        }                                                                                                                                \
-        hipLaunchKernelGGL(kern_, dim3(gx, GY), dim3(TPB), sm, (hipStream_t)stream, dlogits, (const bf16_t*)f_hi,                        \
-                           (const bf16_t*)f_lo, w, (bf16_t*)df_hi, (bf16_t*)df_lo, dw, db, count, M, HW, C, ncls, drop_seed,             \
-                           drop_seed_dev, thresh_of(drop_p), inv, (int)iters, (int)ig, bn);                                              \
+        const int rc_ = ig_launch<cls_bwd_kernel<NC, VEC, MD>>("ig_classifier_bwd", dim3(gx, GY), dim3(TPB), (int)sm, (hipStream_t)stream, \
+                                                               dlogits, (const bf16_t*)f_hi, (const bf16_t*)f_lo, w, (bf16_t*)df_hi,     \
+                                                               (bf16_t*)df_lo, dw, db, count, M, HW, C, ncls, drop_seed, drop_seed_dev,  \
+                                                               ig_drop_thresh16(drop_p), inv, (int)iters, (int)ig, bn);                  \
+        if (rc_ != IG_OK) return rc_;                                                                                                    \
     } while (0)
 #define IG_CLS_BWD_M(NC)                             \
     do {                                             \
@@ -1209,7 +1196,7 @@ static int classifier_bwd_impl(int mode, ClsBn bn, int* nwg_out, const float* dl
 #undef IG_CLS_BWD_W
 #undef IG_CLS_BWD_M
 #undef IG_CLS_BWD
-    return ig_check_launch("ig_classifier_bwd");
+    return IG_OK;
 }
 
 int ig_classifier_bwd(const float* dlogits, const void* f_hi, const void* f_lo, const float* w, void* df_hi, void* df_lo, float* dw,

@@ -54,8 +54,7 @@ int ig_reserved_cus() {
 // tile counts (84 x 3 / 84 x 9 / 84 x 12 tiles on 256 CUs), so it is honoured only when it is free; IG_RESERVED_STRICT=1 makes it
 // strict.  Kernels whose work divides evenly (split-K weight gradients) always honour it.
 int ig_tile_grid(int ntiles, int per_cu) {
-    const char* e = getenv("IG_RESERVED_STRICT");  // read per call: a test switch
-    const int strict = e ? atoi(e) : 0;
+    const int strict = ig_env_int("IG_RESERVED_STRICT", 0);  // 1: the reservation always holds (a test switch)
     const int slots_x = ig_cu_count() / 8 * per_cu;
     int avail_x = slots_x;
     if (strict) avail_x -= (ig_reserved_cus() * per_cu + 7) / 8;

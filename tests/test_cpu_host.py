@@ -675,3 +675,19 @@ def test_gemm4_generator_configuration_keys(tmp_path):
         assert not [i for i in ins[entry:] if i.startswith(fetch)], name
         ins = _g4_block(free, name)
         assert sum(1 for i in ins if i == "s_barrier") == 1 and [i for i in ins if i.startswith("s_waitcnt vmcnt")] == ["s_waitcnt vmcnt(0)"], name
+
+
+@pytest.mark.parametrize("switch", ["IG_CONV_DIRECT", "IG_CONV8"])
+@pytest.mark.parametrize("value", [None, "0", "1", "2", "abc"])
+def test_engine_switches_are_read_before_any_device_call(built_lib, monkeypatch, switch, value):
+    """An empty batch walks the routing of the convolution entry points -- conv_direct.hip and conv8.hip read their switches and
+    decline or finish -- and returns IG_OK without a HIP call, whatever the switch holds (a non-numeric value counts as 0, as atoi does)."""
+    lib = built_lib.load()
+    if value is None:
+        monkeypatch.delenv(switch, raising=False)
+    else:
+        monkeypatch.setenv(switch, value)
+    p = ctypes.c_void_p(16)
+    assert lib.ig_conv3x3_fwd(p, None, p, None, None, None, None, p, None, 0, 16, 16, 48, 48, None) == 0
+    assert lib.ig_conv3x3_fwd(p, None, p, None, None, None, None, p, None, 0, 16, 16, 96, 96, None) == 0
+    assert lib.ig_convT_dgrad(p, None, p, None, p, None, 0, 16, 16, 96, 48, None) == 0
