@@ -330,6 +330,23 @@ int ig_region_area(const int* labels, int* area, int n, long HW, void* stream);
 int ig_sieve_pass(signed char* cls, const int* labels, const int* area, int min_region, int n, int H, int W, int fill,
                   unsigned long long* best, int* changed, void* stream);
 int ig_region_stats(const int* labels, const int* rid, long long* stats, long n_regions, int n, int H, int W, void* stream);
+/* Post-hoc calibration of the class probabilities (calibrate.hip; not in the reference).  Inputs and validity predicate of ig_ce_loss /
+ * ig_auc_update: logits (B, ncls, HW) f32 planar, labels with label_dtype 0 = int64 / 1 = int32 / 2 = f32, a pixel is valid iff
+ * label != ignore_index and 0 <= label < ncls; 2 <= ncls <= 127.  B == 0 or HW == 0 returns IG_OK without touching a pointer.
+ * ig_calib_nll_grid: inv_temps = HOST array of K values beta_k = 1 / T_k, 1 <= K <= 32, each finite and > 0.  For every valid pixel and k:
+ *   nll[k] += logsumexp_c(beta_k z_c) - beta_k z_y, evaluated max-subtracted (exponents beta_k (z_c - max_c z_c) <= 0).  nll = DEVICE
+ *   double[K], accumulated; count = DEVICE uint64, += #valid.  A thread sums its pixels in double, workgroup partials are folded in
+ *   workgroup order by a second launch, the count is an integer add: bit-identical from run to run, no float atomics.  Uses a per
+ *   (device, stream) scratch buffer: the first call on a stream must not happen during a graph capture.
+ * ig_reliability_update: hist = DEVICE uint64 [ncls][3][nbins], accumulated, indexed by the PREDICTED class.  Per valid pixel:
+ *   p = softmax(inv_temp * z) max-subtracted, pred = the first argmax (ig_argmax_i8's rule), conf = p[pred], bin = min(nbins - 1,
+ *   floor(conf * nbins)); hist[pred][0][bin] += 1, hist[pred][1][bin] += (pred == label), hist[pred][2][bin] += floor(conf * 2^24 + 0.5).
+ *   1 <= nbins <= 64 and ncls * nbins <= 4096 (the workgroup-local LDS histogram); B * HW <= 2^40 per call.  Integer sums only: the
+ *   result does not depend on any order and adds across ranks; the confidence sum cannot overflow below 2^40 pixels in total. */
+int ig_calib_nll_grid(const float* logits, const void* labels, int label_dtype, long ignore_index, const float* inv_temps, int K, double* nll,
+                      unsigned long long* count, int B, long HW, int ncls, void* stream);
+int ig_reliability_update(const float* logits, const void* labels, int label_dtype, long ignore_index, float inv_temp,
+                          unsigned long long* hist, int B, long HW, int ncls, int nbins, void* stream);
 int ig_confusion_update(const long long* y_true, const long long* y_pred, unsigned long long* confusion, long n, int k,
                         long ignore_index, int has_ignore, void* stream);
 /* torch.optim.AdamW step on a flat buffer (+ clip_weights, + bf16 shadow refresh)        base.py:103-126 */

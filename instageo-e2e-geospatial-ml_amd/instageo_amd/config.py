@@ -67,7 +67,15 @@ DEFAULTS: Dict[str, Any] = {'root_dir': None,
           'tta': 'none', 'save_uncertainty': False,
           # chip / tile inference (not in the reference): sieve of regions below min_region pixels (0 = off) under 4- or 8-connectivity
           # with at most sieve_passes passes, and the region table regions_*.csv (postprocess.py)
-          'min_region': 0, 'connectivity': 4, 'sieve_passes': 8, 'save_regions': False}}
+          'min_region': 0, 'connectivity': 4, 'sieve_passes': 8, 'save_regions': False,
+          # calibrated probabilities (not in the reference): logits / temperature in front of every softmax consumer (predict_step, the
+          # blended tile canvas, the test epoch's ROC-AUC).  temperature: a float > 0, None = 1.0 (nothing is scaled); calibration: the
+          # calibration.json of mode=calibrate to take it from (one of the two).  calibration_metrics: mode=eval also logs test_nll /
+          # test_ece / test_mce at the temperature in force
+          'temperature': None, 'calibration': None, 'calibration_metrics': False},
+ # mode=calibrate (not in the reference): temperature fit on valid_filepath -- grid points per pass, passes, the first grid's range,
+ # bins of the reliability histograms (calibration.py)
+ 'calibrate': {'points': 32, 'passes': 2, 't_min': 0.125, 't_max': 8.0, 'nbins': 15}}
 
 PRESETS: Dict[str, Dict[str, Any]] = {'sen1floods11': {'train': {'batch_size': 16, 'class_weights': [1, 3], 'ignore_index': -1},
                   'model': {'model_name': 'prithvi_eo_v1_100'},

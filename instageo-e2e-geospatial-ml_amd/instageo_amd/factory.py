@@ -5,6 +5,7 @@ from typing import Any, Dict
 
 import torch
 
+from .calibration import check_calibrate_options, resolve_temperature
 from .regression import PrithviDistillationRegressionModule, PrithviRegressionModule
 from .segmentation import LOSS_CHOICES, PrithviDistillationSegmentationModule, PrithviSegmentationModule
 
@@ -29,6 +30,15 @@ def create_model(cfg: Dict[str, Any], precision: str = "bf16", device=None) -> P
         precision=precision,
         device=device,
     )
+    test_cfg, cal = cfg.get("test", {}), cfg.get("calibrate", {})
+    temperature = resolve_temperature(test_cfg)
+    check_calibrate_options(cal.get("points", 32), cal.get("passes", 2), cal.get("t_min", 0.125), cal.get("t_max", 8.0), cal.get("nbins", 15),
+                            None if cfg.get("is_reg_task", False) else m["num_classes"])
+    if cfg.get("is_reg_task", False):
+        if cfg["mode"] == "calibrate":
+            raise ValueError("mode=calibrate fits a softmax temperature: a regression task (is_reg_task) has no class probabilities")
+        if temperature != 1.0 or test_cfg.get("calibration_metrics", False):
+            raise ValueError("test.temperature / test.calibration / test.calibration_metrics need class probabilities (not is_reg_task)")
     loss = t.get("loss", "ce")
     if loss not in LOSS_CHOICES:
         raise ValueError(f"train.loss={loss!r}: choose one of {', '.join(LOSS_CHOICES)}")
@@ -53,10 +63,12 @@ def create_model(cfg: Dict[str, Any], precision: str = "bf16", device=None) -> P
                                         include_ee=m.get("include_ee_metric", False), **common)
     else:
         model = PrithviSegmentationModule(num_classes=m["num_classes"], class_weights=t["class_weights"], **seg_loss, **common)
+    if not cfg.get("is_reg_task", False):
+        model.set_calibration(temperature, bool(test_cfg.get("calibration_metrics", False)), int(cal.get("nbins", 15)))
     if not train_mode:
         ckpt = cfg.get("checkpoint_path")
         if not ckpt or str(ckpt) == "None":
-            raise RuntimeError("checkpoint_path is required for eval / chip_inference")
+            raise RuntimeError("checkpoint_path is required for eval / calibrate / chip_inference")
         sd = torch.load(ckpt, map_location="cpu")["state_dict"]
         model.load_checkpoint_state_dict(sd, strict=True)
     return model

@@ -27,6 +27,7 @@ import torch
 
 from . import distributed as D
 from . import ops, postprocess, tiff
+from .calibration import check_temperature
 from .dataloader import d4_codes, d4_inverse, gather_windows, origins_tensor, window_grid, window_origins
 
 
@@ -192,7 +193,7 @@ def blended_window_inference(tile: torch.Tensor, model, mean: Sequence[float], s
                              crop_size: int = 224, stride: int = 224, batch_size: int = 64, constant_multiplier: Optional[float] = None,
                              blend: str = "gaussian", sigma_scale: float = 0.125, cover_edges: bool = True,
                              no_data_value: Optional[float] = None, fill: int = -1, probabilities: bool = False, tta: str = "none",
-                             uncertainty: bool = False) -> Tuple[Optional[torch.Tensor], ...]:
+                             uncertainty: bool = False, temperature: float = 1.0) -> Tuple[Optional[torch.Tensor], ...]:
     """tile (T*C, H, W) int16|f32 on the device, any H, W >= crop -> (class map (H, W) int8, probabilities (ncls, H, W) f32 or None)
     on rank 0, (None, None) elsewhere.  A regression head (one output channel) gives (None, the blended value (1, H, W)).
 
@@ -207,14 +208,21 @@ def blended_window_inference(tile: torch.Tensor, model, mean: Sequence[float], s
     mapped back and all K enter the canvas with the window's weight.  A forward batch holds whole windows (``max(1, batch_size // K)``
     of them, x K images), so all transforms of a window stay on one rank.  ``uncertainty=True`` returns a third tensor (2, H, W) =
     [normalised entropy, top-two margin] of the blended probabilities on rank 0 (NaN where the class map is ``fill``); a regression
-    head has neither and raises ValueError."""
+    head has neither and raises ValueError.
+
+    ``temperature`` != 1 multiplies every window's fp32 logits by 1 / temperature in place before they enter the canvas (calibrated
+    probabilities, calibration.py); at 1 nothing is multiplied and the canvas keeps its bits.  A blended class map can change with the
+    temperature (an average of softmaxes is not monotone in it); a regression head refuses it."""
     codes = d4_codes(tta)
+    inv_t = 1.0 / check_temperature(temperature, "temperature")
     net, eng = _engine_of(model)
     net.eval()
     TC, H, W = tile.shape
     ncls = net.cfg.num_classes
     if uncertainty and ncls == 1:
         raise ValueError("uncertainty rasters need class probabilities (a regression head has one output channel)")
+    if inv_t != 1.0 and ncls == 1:
+        raise ValueError("temperature scaling needs class probabilities (a regression head has one output channel)")
     tops, lefts = window_grid(H, W, crop_size, stride, cover_edges)
     ncol = len(lefts)
     world = D.world_size()
@@ -251,10 +259,14 @@ def blended_window_inference(tile: torch.Tensor, model, mean: Sequence[float], s
         x, _ = gather_windows(tile, mine[i : i + k], mean, std, temporal_size, crop_size, constant_multiplier, out=xbuf[:k])
         if tta == "none":
             logits = eng.forward(x, training=False, save=False)
+            if inv_t != 1.0:
+                logits.mul_(inv_t)
             ops.window_blend_accumulate(logits, tops_d, lefts_d, lo + i, wvec, canvas[:ncls], canvas[ncls], H, y0, rows_of(lo + i, lo + i + k))
             continue
         logits = eng.forward(ops.d4_apply(x, codes, True, out=xk[: k * K]), training=False, save=False)
         ops.d4_apply(logits, inverse, False, out=back[: k * K])
+        if inv_t != 1.0:
+            back[: k * K].mul_(inv_t)
         ops.window_blend_accumulate_tta(back[: k * K].view(k, K, ncls, crop_size, crop_size), tops_d, lefts_d, lo + i, wvec, canvas[:ncls],
                                         canvas[ncls], H, y0, rows_of(lo + i, lo + i + k))
     full = D.reduce_row_bands(canvas, bands, H, dst=0)
@@ -274,7 +286,7 @@ def tile_inference(tile_path: str, output_folder: str, model, mean: Sequence[flo
                    no_data_value: Optional[float] = -9999, fill: int = -1, device: str = "cuda", blend: str = "nearest",
                    cover_edges: bool = False, sigma_scale: float = 0.125, save_probabilities: bool = False, tta: str = "none",
                    save_uncertainty: bool = False, min_region: int = 0, connectivity: int = 4, sieve_passes: int = 8,
-                   save_regions: bool = False) -> Optional[str]:
+                   save_regions: bool = False, temperature: float = 1.0) -> Optional[str]:
     """GeoTIFF tile -> ``prediction_*.tif`` class map of the same georeferencing: read the (T*C, H, W)
     tile, sliding-window inference over all ranks, stitch, blank NODATA pixels (any band == ``no_data_value``) and uncovered
     border pixels with ``fill``, write on rank 0.  Returns the output path on rank 0, None elsewhere.
@@ -289,7 +301,12 @@ def tile_inference(tile_path: str, output_folder: str, model, mean: Sequence[flo
     ``prediction_*.tif`` (regions below the minimum mapping unit take the class of their largest kept 4-neighbour,
     :func:`postprocess.sieve_class_map` with ``connectivity`` and at most ``sieve_passes`` passes); ``save_regions`` writes
     ``regions_*.csv``, the region table of the written map (map coordinates when the tile is georeferenced).  The probability and
-    uncertainty rasters are unchanged by either: they describe the blend BEFORE the sieve.  With the defaults nothing of this runs."""
+    uncertainty rasters are unchanged by either: they describe the blend BEFORE the sieve.  With the defaults nothing of this runs.
+
+    ``temperature`` (blended paths; ``test.temperature`` / ``test.calibration``) calibrates the probabilities that are blended, and
+    through them the class map, probability and uncertainty rasters.  The nearest-centre stitch is an argmax of raw logits, which no
+    positive temperature changes: it ignores the value."""
+    check_temperature(temperature, "temperature")
     postprocess.check_region_options(min_region, connectivity, sieve_passes, save_regions, _is_regression(model))
     if blend not in ("nearest", "mean", "gaussian"):
         raise ValueError(f"blend must be 'nearest', 'mean' or 'gaussian' (got {blend!r})")
@@ -302,7 +319,7 @@ def tile_inference(tile_path: str, output_folder: str, model, mean: Sequence[flo
     if blend != "nearest":
         return _blended_tile_file(arr, profile, tile_path, output_folder, model, mean, std, temporal_size, crop_size, stride, batch_size,
                                   constant_multiplier, no_data_value, fill, device, blend, cover_edges, sigma_scale, save_probabilities,
-                                  tta, save_uncertainty, min_region, connectivity, sieve_passes, save_regions)
+                                  tta, save_uncertainty, min_region, connectivity, sieve_passes, save_regions, temperature)
     if arr.shape[1] != arr.shape[2]:
         raise ValueError("tile_inference expects a square tile (the window rule of process_test uses one img_size)")
     t = torch.from_numpy(arr if arr.dtype in (np.int16, np.float32) else arr.astype(np.float32)).to(device)
@@ -333,10 +350,11 @@ def _region_outputs(classmap: torch.Tensor, tile_path: str, output_folder: str, 
 
 def _blended_tile_file(arr, profile, tile_path, output_folder, model, mean, std, temporal_size, crop_size, stride, batch_size,
                        constant_multiplier, no_data_value, fill, device, blend, cover_edges, sigma_scale, save_probabilities,
-                       tta="none", save_uncertainty=False, min_region=0, connectivity=4, sieve_passes=8, save_regions=False) -> Optional[str]:
+                       tta="none", save_uncertainty=False, min_region=0, connectivity=4, sieve_passes=8, save_regions=False,
+                       temperature=1.0) -> Optional[str]:
     t = torch.from_numpy(arr if arr.dtype in (np.int16, np.float32) else arr.astype(np.float32)).to(device)
     res = blended_window_inference(t, model, mean, std, temporal_size, crop_size, stride, batch_size, constant_multiplier, blend,
-                                   sigma_scale, cover_edges, no_data_value, fill, save_probabilities, tta, save_uncertainty)
+                                   sigma_scale, cover_edges, no_data_value, fill, save_probabilities, tta, save_uncertainty, temperature)
     classmap, prob = res[0], res[1]
     if classmap is None and prob is None:
         return None

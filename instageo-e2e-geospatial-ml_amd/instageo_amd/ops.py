@@ -696,6 +696,32 @@ def auc_update(logits, labels, ignore_index: Optional[int], hist, nbins: int, mi
           _p(hist), B, HW, ncls, nbins, float(min_score), float(max_score), _stream())
 
 
+def calib_nll_grid(logits, labels, ignore_index: Optional[int], inv_temps, nll, count) -> None:
+    """Cross-entropy of softmax(beta_k * logits) at every beta_k = 1 / T_k of ``inv_temps`` (a host sequence of 1..32 finite positive
+    floats) in one pass: ``nll`` (f64 [K]) += the sums over the valid pixels, ``count`` (int64 [1]) += #valid.  Bit-reproducible."""
+    import ctypes
+
+    B, ncls = logits.shape[0], logits.shape[1]
+    HW = logits.numel() // (B * ncls) if B * ncls else 0
+    betas = [float(b) for b in inv_temps]
+    K = len(betas)
+    assert nll.dtype == torch.float64 and nll.numel() >= K and count.dtype == torch.int64 and count.numel() >= 1
+    ign = -(2**62) if ignore_index is None else int(ignore_index)
+    _call("ig_calib_nll_grid", float(B) * HW * (ncls * 4 + labels.element_size()), _p(_f32(logits)), _p(labels), _LABEL_DT[labels.dtype], ign,
+          (ctypes.c_float * max(K, 1))(*betas), K, _p(nll), _p(count), B, HW, ncls, _stream())
+
+
+def reliability_update(logits, labels, ignore_index: Optional[int], inv_temp: float, hist) -> None:
+    """Reliability histograms of the top-class confidence of softmax(inv_temp * logits): ``hist`` int64 [ncls, 3, nbins] += (count,
+    hits, confidence in units of 2^-24) per (predicted class, confidence bin) over the valid pixels.  Integer sums: order-independent."""
+    B, ncls = logits.shape[0], logits.shape[1]
+    HW = logits.numel() // (B * ncls) if B * ncls else 0
+    assert hist.dtype == torch.int64 and hist.dim() == 3 and hist.shape[0] == ncls and hist.shape[1] == 3
+    ign = -(2**62) if ignore_index is None else int(ignore_index)
+    _call("ig_reliability_update", float(B) * HW * (ncls * 4 + labels.element_size()), _p(_f32(logits)), _p(labels), _LABEL_DT[labels.dtype],
+          ign, float(inv_temp), _p(hist), B, HW, ncls, int(hist.shape[2]), _stream())
+
+
 def softmax_prob(logits, cls: int = 1, out=None):
     """softmax(logits, dim=1)[:, cls] -> (B, H, W) f32 (predict_step, segmentation.py:202-213)."""
     B, ncls = logits.shape[0], logits.shape[1]

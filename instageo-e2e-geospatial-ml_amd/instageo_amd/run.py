@@ -2,7 +2,8 @@
 
     python -m instageo_amd.run [--config-name sen1floods11] [--config-path DIR] key=value ...
 
-Modes ``stats | train | eval | chip_inference`` and every config key are those of the reference; ``tile_inference``
+Modes ``stats | train | eval | chip_inference`` and every config key are those of the reference; ``calibrate`` (temperature fit on the
+validation split -> ``calibration.json``; ``calibrate.*``, ``test.temperature`` / ``calibration`` / ``calibration_metrics``) and ``tile_inference``
 (whole GeoTIFF tiles -> maps, ``test.blend`` / ``cover_edges`` / ``sigma_scale`` / ``save_probabilities`` / ``tta`` /
 ``save_uncertainty``) is this project's, as are the region keys of both inference modes (``test.min_region`` / ``connectivity`` /
 ``sieve_passes`` / ``save_regions``).  Hydra, Lightning and Neptune are replaced by :mod:`instageo_amd.config` and the explicit loop below, which logs the
@@ -125,6 +126,10 @@ def _reduce_metrics(metrics, dev, model=None, step_type: Optional[str] = None) -
     D.reduce_loss_stats(acc)
     if step_type == "test" and hasattr(model, "test_auc"):
         D.reduce_confusion(model.test_auc.device_hist(dev))
+        if getattr(model, "test_nll", None) is not None:  # test.calibration_metrics
+            D.reduce_loss_stats(model.test_nll.device_sums(dev))
+            D.reduce_confusion(model.test_nll.device_count(dev))
+            D.reduce_confusion(model.test_reliability.device_hist(dev))
 
 
 def train(cfg: Dict[str, Any], model, out_dir: str, rank: int, world: int) -> Dict[str, float]:
@@ -192,6 +197,63 @@ def evaluate(cfg: Dict[str, Any], model, rank: int, world: int) -> Dict[str, flo
     return {k: float(v) for k, v in model.logged.items() if k.startswith("test_") and not isinstance(v, (list, tuple))}
 
 
+def calibrate(cfg: Dict[str, Any], model, out_dir: str, rank: int, world: int) -> Optional[Dict[str, Any]]:
+    """mode=calibrate: fit one softmax temperature on the validation split and measure calibration before and after.
+
+    The split is walked exactly as :func:`evaluate` walks the test set (``process_test`` windows, eval mode, rank sharding), once per
+    pass of the fit -- logits are never stored, ``ig_calib_nll_grid`` evaluates a batch's loss at the whole temperature grid while
+    the logits are on the device -- and once more for the loss and the reliability histograms at T = 1 and at the fitted T.  Rank 0
+    writes ``<out_dir>/calibration.json`` and returns the record."""
+    from .calibration import RunningNLL, RunningReliability, TemperatureFitter, write_calibration_json
+
+    dev = str(model.net.store.flat.device)
+    ds = create_dataset(cfg["valid_filepath"], {**cfg, "mode": "eval"}, "test", dev)  # the windows of the test path on the valid split
+    d, t, c = cfg["dataloader"], cfg["test"], cfg["calibrate"]
+    ign, ncls = cfg["train"]["ignore_index"], cfg["model"]["num_classes"]
+    eng = model.net.engine
+    model.net.eval()
+    lo, hi = D.shard_range(len(ds), rank, world)
+    mult = getattr(ds, "mult", None)
+
+    def batches():
+        with torch.no_grad():
+            for i in range(lo, hi):
+                raw_x, raw_y = ds.raw(i) if hasattr(ds, "raw") else (ds.chips[i], ds.labels[i])
+                x, y = process_test(raw_x, raw_y, d["mean"], d["std"], d["temporal_dim"], t["img_size"], t["crop_size"], t["stride"], mult, dev)
+                yield eng.forward(x, training=False, save=False), y
+
+    fit = TemperatureFitter(float(c["t_min"]), float(c["t_max"]), int(c["points"]), int(c["passes"]), device=dev)
+    while not fit.done:
+        for logits, y in batches():
+            fit.update(logits, y, ign)
+        D.reduce_loss_stats(fit.device_sums(dev))  # a rank with an empty shard still takes part
+        D.reduce_confusion(fit.device_count(dev))
+        fit.end_pass()
+    res = fit.result()
+    T = res["temperature"]
+    nll = RunningNLL([1.0, T], ign, dev)
+    rel = [RunningReliability(ncls, int(c["nbins"]), temp, ign, dev) for temp in (1.0, T)]
+    for logits, y in batches():
+        nll.update(logits, y)
+        for r in rel:
+            r.update(logits, y)
+    D.reduce_loss_stats(nll.device_sums(dev))
+    D.reduce_confusion(nll.device_count(dev))
+    for r in rel:
+        D.reduce_confusion(r.device_hist(dev))
+    if rank != 0:
+        return None
+    before, after = (r.compute() for r in rel)
+    nll_before, nll_after = nll.compute()
+    record = {"temperature": T, "nll_before": nll_before, "nll_after": nll_after, "ece_before": before["ece"], "ece_after": after["ece"],
+              "mce_before": before["mce"], "mce_after": after["mce"], "classwise_ece_before": before["classwise_ece"],
+              "classwise_ece_after": after["classwise_ece"], "n_valid": res["n_valid"], "at_bound": res["at_bound"],
+              "bins_before": before["bins"], "bins_after": after["bins"], "grids": res["grids"], "nbins": int(c["nbins"]),
+              "fit": {"vertex": res["vertex"], "nll_before": res["nll_before"], "nll_after": res["nll_after"]}}  # fmt: skip
+    print(write_calibration_json(os.path.join(out_dir, "calibration.json"), record))
+    return record
+
+
 def tile_paths(cfg: Dict[str, Any]) -> List[str]:
     """mode=tile_inference input: ``test_filepath`` is one GeoTIFF tile or a CSV whose ``Input`` column lists tiles (paths relative
     to ``root_dir`` unless absolute)."""
@@ -217,7 +279,8 @@ def run_tile_inference(cfg: Dict[str, Any], model, tile: str, output_dir: str, d
                           cfg["train"]["batch_size"], mult, d.get("no_data_value", -9999), device=dev, blend=t.get("blend", "nearest"),
                           cover_edges=bool(t.get("cover_edges", False)), sigma_scale=float(t.get("sigma_scale", 0.125)),
                           save_probabilities=bool(t.get("save_probabilities", False)), tta=str(t.get("tta", "none")),
-                          save_uncertainty=bool(t.get("save_uncertainty", False)), **region_options(cfg))
+                          save_uncertainty=bool(t.get("save_uncertainty", False)), temperature=float(getattr(model, "temperature", 1.0)),
+                          **region_options(cfg))
 
 
 def region_options(cfg: Dict[str, Any]) -> Dict[str, Any]:
@@ -274,6 +337,9 @@ def main(argv: Optional[List[str]] = None) -> int:
         if rank == 0:
             print(json.dumps({"Evaluation results": {k: round(v, 6) for k, v in res.items()}}))
             print(f"Elapsed time: {time.time() - start:.2f} seconds")
+    elif cfg["mode"] == "calibrate":
+        check_required_flags(["valid_filepath", "checkpoint_path"], cfg)
+        calibrate(cfg, model, out_dir, rank, world)
     elif cfg["mode"] == "chip_inference":
         check_required_flags(["root_dir", "test_filepath", "checkpoint_path"], cfg)
         model.net.eval()

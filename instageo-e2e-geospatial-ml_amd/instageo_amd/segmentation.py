@@ -19,6 +19,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
+from .calibration import RunningNLL, RunningReliability, check_temperature
 from .metrics import RunningAUC, RunningConfusionMatrix
 from .model import PrithviSeg
 
@@ -367,6 +368,10 @@ class PrithviSegmentationModule(_Base):
         self.val_metrics = RunningConfusionMatrix(num_classes, ignore_index)
         self.test_metrics = RunningConfusionMatrix(num_classes, ignore_index)
         self.test_auc = RunningAUC(num_classes, ignore_index=ignore_index)  # ROC-AUC only at test time (segmentation.py:153-156)
+        # calibrated probabilities (not in the reference): logits / temperature in front of every softmax consumer; 1.0 scales nothing
+        self.temperature = 1.0
+        self.test_nll: Optional[RunningNLL] = None  # test.calibration_metrics: test_nll / test_ece / test_mce at that temperature
+        self.test_reliability: Optional[RunningReliability] = None
         self.logged: Dict[str, Any] = {}
         self._loss_sums: Dict[str, torch.Tensor] = {}
         self._optimizer: Optional[FusedAdamW] = None
@@ -405,6 +410,27 @@ class PrithviSegmentationModule(_Base):
     def _weights(self) -> Optional[torch.Tensor]:
         return getattr(self.criterion, "weight", None)
 
+    def set_calibration(self, temperature: float = 1.0, metrics: bool = False, nbins: int = 15) -> None:
+        """``test.temperature`` / ``test.calibration`` and ``test.calibration_metrics`` (calibration.py)."""
+        self.temperature = check_temperature(temperature)
+        self.test_nll = RunningNLL([1.0], self.ignore_index) if metrics else None  # fed the scaled logits: its own temperature is 1
+        self.test_reliability = RunningReliability(self._num_classes, nbins, 1.0, self.ignore_index) if metrics else None
+
+    def scale_logits_(self, logits: torch.Tensor) -> torch.Tensor:
+        """logits / temperature IN PLACE; at temperature 1 nothing runs, so every uncalibrated output keeps its bits."""
+        if self.temperature != 1.0:
+            logits.mul_(1.0 / self.temperature)
+        return logits
+
+    def _test_probability_metrics(self, logits: torch.Tensor, labels: torch.Tensor) -> None:
+        """The softmax consumers of the test epoch, after the loss and the confusion matrix have seen the raw logits: ROC-AUC
+        histograms and, with ``test.calibration_metrics``, the cross-entropy sum and the reliability histograms.  Scales ``logits``."""
+        logits = self.scale_logits_(logits)
+        self.test_auc.update_from_logits(logits, labels)
+        if self.test_nll is not None:
+            self.test_nll.update(logits, labels)
+            self.test_reliability.update(logits, labels)
+
     def _shared_step(self, batch: Any, step_type: str) -> torch.Tensor:
         """forward, loss, argmax, confusion-matrix update (segmentation.py:107-168) without host copies."""
         inputs, labels = batch
@@ -413,7 +439,7 @@ class PrithviSegmentationModule(_Base):
         loss = segmentation_loss(outputs, labels, self._weights(), self.ignore_index, confusion=metrics.device_matrix(outputs.device),
                                  spec=self._loss_spec, parts=self._zeroed_loss_parts(outputs.device))
         if step_type == "test":  # ROC-AUC is a test-time metric (segmentation.py:153-156)
-            self.test_auc.update_from_logits(outputs.detach(), labels)
+            self._test_probability_metrics(outputs.detach().clone() if self.temperature != 1.0 else outputs.detach(), labels)
         self._log_region_parts(step_type)
         self._accumulate_loss(step_type, loss.detach())
         return loss
@@ -479,11 +505,19 @@ class PrithviSegmentationModule(_Base):
             self.log(f"{step_type}_IoU_{idx}", value)
         if step_type == "test":
             self.log(f"{step_type}_roc_auc", float(self.test_auc.score()["roc_auc_macro"]))
+            if self.test_nll is not None:
+                rel = self.test_reliability.compute()
+                self.log("test_nll", self.test_nll.compute()[0])
+                self.log("test_ece", rel["ece"])
+                self.log("test_mce", rel["mce"])
         for idx, value in enumerate(m["f1_per_class"]):
             self.log(f"{step_type}_F1_{idx}", value)
         metrics.reset()
         if step_type == "test":
             self.test_auc.reset()
+            if self.test_nll is not None:
+                self.test_nll.reset()
+                self.test_reliability.reset()
 
     def on_train_epoch_end(self) -> None:
         self._shared_epoch_end("train")
@@ -649,8 +683,8 @@ class PrithviSegmentationModule(_Base):
         metrics: RunningConfusionMatrix = getattr(self, f"{step_type}_metrics")
         _loss_call(self._loss_spec, logits, labels.contiguous(), self._weights(), self.ignore_index, stats, dlogits, None,
                    metrics.device_matrix(logits.device), self._zeroed_loss_parts(logits.device))
-        if step_type == "test":
-            self.test_auc.update_from_logits(logits, labels)
+        if step_type == "test":  # a copy when it is scaled: a distillation term still reads the raw logits after this
+            self._test_probability_metrics(logits.clone() if self.temperature != 1.0 else logits, labels)
 
     def predict_step(self, batch: Any) -> torch.Tensor:
         """softmax(forward(batch), dim=1)[:, 1] (segmentation.py:202-213), fused on the device."""
@@ -659,7 +693,7 @@ class PrithviSegmentationModule(_Base):
             self.net.eval()
         with torch.no_grad():
             logits = self.net.engine.forward(inputs, training=False, save=False)
-        return ops.softmax_prob(logits, 1)
+        return ops.softmax_prob(self.scale_logits_(logits), 1)
 
     # ---- checkpoints (pipeline_utils.py:347-355, factory.py:113-115) ----------------------------
     def sync_master_params(self) -> None:
@@ -740,7 +774,7 @@ class PrithviDistillationSegmentationModule(PrithviSegmentationModule):
         loss, ce, kl = _SegKDLoss.apply(outputs, t_logits, labels, self._weights(), self.ignore_index, metrics.device_matrix(outputs.device),
                                         self._loss_spec, self._zeroed_loss_parts(outputs.device))
         if step_type == "test":
-            self.test_auc.update_from_logits(outputs.detach(), labels)
+            self._test_probability_metrics(outputs.detach().clone() if self.temperature != 1.0 else outputs.detach(), labels)
         if self._region_on():  # <step>_ce_loss names the pixel term; the region term is logged beside it
             ce = (self._loss_parts[0] / self._loss_parts[2]).float()
             self.log(f"{step_type}_dice_loss", (self._loss_parts[1] / self._loss_parts[2]).float().item())
