@@ -347,6 +347,27 @@ int ig_calib_nll_grid(const float* logits, const void* labels, int label_dtype, 
                       unsigned long long* count, int B, long HW, int ncls, void* stream);
 int ig_reliability_update(const float* logits, const void* labels, int label_dtype, long ignore_index, float inv_temp,
                           unsigned long long* hist, int B, long HW, int ncls, int nbins, void* stream);
+/* Boundary-quality primitives on class maps (boundary.hip; not in the reference).  Class maps as above: (n, H, W) int8, contiguous, `fill`
+ * (any int8 value) marks invalid pixels, images are independent, H * W <= 2^31 - 1.  All results are integers and unique: bit-identical
+ * from run to run.  n = 0 returns IG_OK without touching a device pointer.
+ * ig_boundary_dist2: dist2 (n, H, W) int32, 1 <= rmax <= 32.  For a pixel p with cls[p] != fill,
+ *   dist2[p] = min{ (py - qy)^2 + (px - qx)^2 : q inside the image, cls[q] != fill, cls[q] != cls[p] }
+ *   when that minimum is <= rmax^2, else IG_BOUNDARY_FAR; dist2[p] = -1 at fill pixels.  Fill is transparent (never a source, distances
+ *   pass through it) and the image border is no boundary.
+ * ig_boundary_update: gt, pred (n, HW) int8 with their dist2 rasters gt_d2, pred_d2 (n, HW) int32; thresholds = HOST array of K squared
+ *   distances t_k, 1 <= K <= 8, strictly ascending, each in [1, 1024].  A pixel counts iff gt != fill, pred != fill and both classes lie
+ *   in [0, ncls), 2 <= ncls <= 127.  Accumulated (the caller zeroes) into DEVICE uint64 tables:
+ *     band[K][ncls][3]:       band[k][c][0] += (gt == c and gt_d2 <= t_k), band[k][c][1] += (pred == c and pred_d2 <= t_k),
+ *                             band[k][c][2] += (gt == pred == c and gt_d2 <= t_k and pred_d2 <= t_k)
+ *     trimap[K][ncls][ncls]:  trimap[k][gt][pred] += (gt_d2 <= t_k)
+ *   Integer sums only: the result does not depend on any order and adds across calls and ranks.  Tables of K * ncls * (ncls + 3) <= 8192
+ *   cells are aggregated per workgroup in LDS (32-bit cells, hence n * HW <= 2^40 per call) and reach memory as one 64-bit add per
+ *   non-empty cell and workgroup; larger tables (e.g. K = 8 beyond 30 classes, K = 1 beyond 89) take one 64-bit global atomic per
+ *   pixel, table and k. */
+#define IG_BOUNDARY_FAR 0x7fffffff
+int ig_boundary_dist2(const signed char* cls, int* dist2, int n, int H, int W, int rmax, int fill, void* stream);
+int ig_boundary_update(const signed char* gt, const signed char* pred, const int* gt_d2, const int* pred_d2, const int* thresholds, int K,
+                       unsigned long long* band, unsigned long long* trimap, int n, long HW, int ncls, int fill, void* stream);
 int ig_confusion_update(const long long* y_true, const long long* y_pred, unsigned long long* confusion, long n, int k,
                         long ignore_index, int has_ignore, void* stream);
 /* torch.optim.AdamW step on a flat buffer (+ clip_weights, + bf16 shadow refresh)        base.py:103-126 */

@@ -72,7 +72,11 @@ DEFAULTS: Dict[str, Any] = {'root_dir': None,
           # blended tile canvas, the test epoch's ROC-AUC).  temperature: a float > 0, None = 1.0 (nothing is scaled); calibration: the
           # calibration.json of mode=calibrate to take it from (one of the two).  calibration_metrics: mode=eval also logs test_nll /
           # test_ece / test_mce at the temperature in force
-          'temperature': None, 'calibration': None, 'calibration_metrics': False},
+          'temperature': None, 'calibration': None, 'calibration_metrics': False,
+          # boundary quality (not in the reference): mode=eval also logs test_bIoU_d<d> (Boundary IoU, with _<class>), test_trimap_Acc_d<d>
+          # and test_trimap_IoU_d<d> over the pixels within d pixels of a class boundary, for each of up to 8 ascending distances in
+          # [1, 32] (boundary.py)
+          'boundary_metrics': False, 'boundary_distances': [1, 2, 4]},
  # mode=calibrate (not in the reference): temperature fit on valid_filepath -- grid points per pass, passes, the first grid's range,
  # bins of the reliability histograms (calibration.py)
  'calibrate': {'points': 32, 'passes': 2, 't_min': 0.125, 't_max': 8.0, 'nbins': 15}}

@@ -5,6 +5,7 @@ from typing import Any, Dict
 
 import torch
 
+from .boundary import check_boundary_options
 from .calibration import check_calibrate_options, resolve_temperature
 from .regression import PrithviDistillationRegressionModule, PrithviRegressionModule
 from .segmentation import LOSS_CHOICES, PrithviDistillationSegmentationModule, PrithviSegmentationModule
@@ -39,6 +40,9 @@ def create_model(cfg: Dict[str, Any], precision: str = "bf16", device=None) -> P
             raise ValueError("mode=calibrate fits a softmax temperature: a regression task (is_reg_task) has no class probabilities")
         if temperature != 1.0 or test_cfg.get("calibration_metrics", False):
             raise ValueError("test.temperature / test.calibration / test.calibration_metrics need class probabilities (not is_reg_task)")
+    boundary = None
+    if test_cfg.get("boundary_metrics", False):
+        boundary = check_boundary_options(test_cfg.get("boundary_distances", [1, 2, 4]), m["num_classes"], bool(cfg.get("is_reg_task", False)))
     loss = t.get("loss", "ce")
     if loss not in LOSS_CHOICES:
         raise ValueError(f"train.loss={loss!r}: choose one of {', '.join(LOSS_CHOICES)}")
@@ -65,6 +69,7 @@ def create_model(cfg: Dict[str, Any], precision: str = "bf16", device=None) -> P
         model = PrithviSegmentationModule(num_classes=m["num_classes"], class_weights=t["class_weights"], **seg_loss, **common)
     if not cfg.get("is_reg_task", False):
         model.set_calibration(temperature, bool(test_cfg.get("calibration_metrics", False)), int(cal.get("nbins", 15)))
+        model.set_boundary_metrics(boundary)
     if not train_mode:
         ckpt = cfg.get("checkpoint_path")
         if not ckpt or str(ckpt) == "None":

@@ -901,6 +901,39 @@ def region_stats(labels, rid, n_regions: int):
     return stats
 
 
+BOUNDARY_FAR = 0x7FFFFFFF  # IG_BOUNDARY_FAR: no pixel of another class within rmax
+
+
+def boundary_dist2(classmap, rmax: int, fill: int = -1, out=None):
+    """Squared Euclidean distance of every pixel of (n, H, W) | (H, W) int8 class maps to the nearest pixel of another class -> int32 of
+    the same shape: the distance when it is <= rmax^2 (1 <= rmax <= 32), else ``BOUNDARY_FAR``; -1 at ``fill``, which is transparent; the
+    image border is no boundary (include/instageo_hip.h)."""
+    n, H, W = _class_maps(classmap)
+    if out is None:
+        out = torch.empty(classmap.shape, dtype=torch.int32, device=classmap.device)
+    assert out.shape == classmap.shape and out.dtype == torch.int32
+    # HBM bytes: the map once (halo re-reads are L2 hits) + dist2 written
+    _call("ig_boundary_dist2", float(n) * H * W * 5, _p(classmap), _p(out), n, H, W, int(rmax), int(fill), _stream())
+    return out
+
+
+def boundary_update(gt, pred, gt_d2, pred_d2, thresholds, band, trimap, ncls: int, fill: int = -1) -> None:
+    """Boundary-band and trimap counts of class maps ``gt`` / ``pred`` (int8) and their :func:`boundary_dist2` rasters at the squared
+    distances ``thresholds`` (a host sequence of 1..8 strictly ascending ints in [1, 1024]): ``band`` int64 [K, ncls, 3] += (gt band,
+    pred band, their intersection) per class, ``trimap`` int64 [K, ncls, ncls] += the confusion matrix inside the gt band.  Integer sums:
+    order-independent."""
+    import ctypes
+
+    ts = [int(t) for t in thresholds]
+    K = len(ts)
+    n, H, W = _class_maps(gt)
+    assert pred.shape == gt.shape and pred.dtype == torch.int8 and gt_d2.shape == gt.shape and pred_d2.shape == gt.shape
+    assert gt_d2.dtype == torch.int32 and pred_d2.dtype == torch.int32
+    assert band.dtype == torch.int64 and tuple(band.shape) == (K, ncls, 3) and trimap.dtype == torch.int64 and tuple(trimap.shape) == (K, ncls, ncls)
+    _call("ig_boundary_update", float(gt.numel()) * 10, _p(gt), _p(pred), _p(gt_d2), _p(pred_d2), (ctypes.c_int * max(K, 1))(*ts), K,
+          _p(band), _p(trimap), n, H * W, int(ncls), int(fill), _stream())
+
+
 def confusion_update(y_true, y_pred, confusion, k: int, ignore_index: Optional[int]) -> None:
     assert y_true.dtype == torch.int64 and y_pred.dtype == torch.int64 and confusion.dtype == torch.int64
     _lib.call("ig_confusion_update", _p(y_true), _p(y_pred), _p(confusion), y_true.numel(), k,

@@ -77,6 +77,10 @@ class PrithviRegressionModule(PrithviSegmentationModule):
     def num_classes(self) -> int:
         return 1
 
+    def set_boundary_metrics(self, distances=None) -> None:
+        if distances is not None:
+            raise ValueError("test.boundary_metrics needs class maps: a regression module has none")
+
     def _fused_loss(self, logits, labels, stats, dlogits, step_type: str) -> None:
         """outputs.squeeze(1)[mask] vs labels[mask] (log1p-scaled when use_log_scale): MSE mean, metrics on the de-scaled
         values (regression.py:153-174) -- one kernel; ``stats`` = (sum of squared errors, #valid)."""

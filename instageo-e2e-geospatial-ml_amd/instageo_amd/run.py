@@ -130,6 +130,9 @@ def _reduce_metrics(metrics, dev, model=None, step_type: Optional[str] = None) -
             D.reduce_loss_stats(model.test_nll.device_sums(dev))
             D.reduce_confusion(model.test_nll.device_count(dev))
             D.reduce_confusion(model.test_reliability.device_hist(dev))
+        if getattr(model, "test_boundary", None) is not None:  # test.boundary_metrics
+            for counts in model.test_boundary.device_counts(dev):
+                D.reduce_confusion(counts)
 
 
 def train(cfg: Dict[str, Any], model, out_dir: str, rank: int, world: int) -> Dict[str, float]:

@@ -19,6 +19,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
+from .boundary import RunningBoundaryMetrics
 from .calibration import RunningNLL, RunningReliability, check_temperature
 from .metrics import RunningAUC, RunningConfusionMatrix
 from .model import PrithviSeg
@@ -372,6 +373,7 @@ class PrithviSegmentationModule(_Base):
         self.temperature = 1.0
         self.test_nll: Optional[RunningNLL] = None  # test.calibration_metrics: test_nll / test_ece / test_mce at that temperature
         self.test_reliability: Optional[RunningReliability] = None
+        self.test_boundary: Optional[RunningBoundaryMetrics] = None  # test.boundary_metrics: test_bIoU_d* / test_trimap_* (boundary.py)
         self.logged: Dict[str, Any] = {}
         self._loss_sums: Dict[str, torch.Tensor] = {}
         self._optimizer: Optional[FusedAdamW] = None
@@ -416,6 +418,11 @@ class PrithviSegmentationModule(_Base):
         self.test_nll = RunningNLL([1.0], self.ignore_index) if metrics else None  # fed the scaled logits: its own temperature is 1
         self.test_reliability = RunningReliability(self._num_classes, nbins, 1.0, self.ignore_index) if metrics else None
 
+    def set_boundary_metrics(self, distances: Optional[Sequence[float]] = None) -> None:
+        """``test.boundary_metrics`` / ``test.boundary_distances`` (boundary.py): Boundary IoU and trimap accuracy of the test epoch at the
+        given distances in pixels; None switches them off."""
+        self.test_boundary = None if distances is None else RunningBoundaryMetrics(self._num_classes, distances, self.ignore_index)
+
     def scale_logits_(self, logits: torch.Tensor) -> torch.Tensor:
         """logits / temperature IN PLACE; at temperature 1 nothing runs, so every uncalibrated output keeps its bits."""
         if self.temperature != 1.0:
@@ -423,8 +430,11 @@ class PrithviSegmentationModule(_Base):
         return logits
 
     def _test_probability_metrics(self, logits: torch.Tensor, labels: torch.Tensor) -> None:
-        """The softmax consumers of the test epoch, after the loss and the confusion matrix have seen the raw logits: ROC-AUC
-        histograms and, with ``test.calibration_metrics``, the cross-entropy sum and the reliability histograms.  Scales ``logits``."""
+        """The test epoch's consumers of the logits beside the loss and the confusion matrix, which have seen the raw logits: with
+        ``test.boundary_metrics`` the boundary counts of the raw logits' argmax, then the softmax consumers -- ROC-AUC histograms and, with
+        ``test.calibration_metrics``, the cross-entropy sum and the reliability histograms.  Scales ``logits``."""
+        if self.test_boundary is not None:
+            self.test_boundary.update(logits, labels)
         logits = self.scale_logits_(logits)
         self.test_auc.update_from_logits(logits, labels)
         if self.test_nll is not None:
@@ -510,6 +520,14 @@ class PrithviSegmentationModule(_Base):
                 self.log("test_nll", self.test_nll.compute()[0])
                 self.log("test_ece", rel["ece"])
                 self.log("test_mce", rel["mce"])
+            if self.test_boundary is not None:
+                for r in self.test_boundary.compute():
+                    d = "%g" % r["distance"]
+                    self.log(f"test_bIoU_d{d}", r["biou"])
+                    for idx, value in enumerate(r["biou_per_class"]):
+                        self.log(f"test_bIoU_d{d}_{idx}", value)
+                    self.log(f"test_trimap_Acc_d{d}", r["trimap_acc"])
+                    self.log(f"test_trimap_IoU_d{d}", r["trimap_iou"])
         for idx, value in enumerate(m["f1_per_class"]):
             self.log(f"{step_type}_F1_{idx}", value)
         metrics.reset()
@@ -518,6 +536,8 @@ class PrithviSegmentationModule(_Base):
             if self.test_nll is not None:
                 self.test_nll.reset()
                 self.test_reliability.reset()
+            if self.test_boundary is not None:
+                self.test_boundary.reset()
 
     def on_train_epoch_end(self) -> None:
         self._shared_epoch_end("train")
