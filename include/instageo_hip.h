@@ -368,6 +368,50 @@ int ig_reliability_update(const float* logits, const void* labels, int label_dty
 int ig_boundary_dist2(const signed char* cls, int* dist2, int n, int H, int W, int rmax, int fill, void* stream);
 int ig_boundary_update(const signed char* gt, const signed char* pred, const int* gt_d2, const int* pred_d2, const int* thresholds, int K,
                        unsigned long long* band, unsigned long long* trimap, int n, long HW, int ncls, int fill, void* stream);
+/* Vectorisation of labelled class maps into polygon rings (vectorize.hip; not in the reference).  labels (n, H, W) int32 are those of
+ * ig_ccl_label (a component's smallest pixel index, -1 at fill; fill and the outside of the image count as label -1); images are
+ * independent; H * W <= 2^31 - 1.  Pixel (r, c) covers [c, c+1] x [r, r+1] in (x, y), y down.  A valid pixel p owns four directed unit
+ * edges with p on their right-hand side: side 0 top (c,r)->(c+1,r) heading E, 1 right (c+1,r)->(c+1,r+1) S, 2 bottom (c+1,r+1)->(c,r+1) W,
+ * 3 left (c,r+1)->(c,r) N; d[0..3] = E, S, W, N as (dr, dc) = (0,1), (1,0), (0,-1), (-1,0).  Side s of p is LIVE iff the pixel across it,
+ * p + d[(s+3)%4], has another label.  The successor of the live edge (p, s), with me = label(p), A = p + d[s], B = A + d[(s+3)%4]:
+ * (B, (s+3)%4) if label(B) == me (left turn), else (A, s) if label(A) == me (straight), else (p, (s+1)%4) (right turn); it is always
+ * live, and the successor map is a permutation of the live edges whose cycles are the rings.  Live edges are numbered 0..E-1 in the
+ * order of (image * HW + pixel) * 4 + side ("compact ids"); E <= 2^31 - 1.  A ring's root is its smallest compact id.  Its vertices are
+ * the tails of the edges whose predecessor has another heading ("turn" edges), in ring order from the root.  Twice its signed area is
+ * sum (x1 y2 - x2 y1) over its edges in lattice coordinates: positive for a region's exterior ring (one per region), negative for a hole.
+ * Under 8-connectivity a ring may touch itself at a vertex.  All results are integers and unique: bit-identical from run to run.  Every
+ * launch does a fixed amount of work; no kernel waits on another workgroup.  n = 0 or E = 0 returns IG_OK without touching a pointer.
+ * ig_edge_mask: mask (n, H, W) uint8: bits 0-3 = the live sides of the pixel, bits 4-6 = their number (0 at fill pixels); *total (device
+ *   uint64) += the live edges of all images.  The exclusive scan of (mask >> 4) over image * HW + pixel is the caller's: off (n, HW)
+ *   int32 = the compact id of the pixel's first live edge, so edge (p, s) has id off[p] + popcount(mask[p] & ((1 << s) - 1)).
+ * ig_edge_link: for every live edge e with successor f: succ[e] = f (E int32), tail[e] = the (x, y) of e's tail vertex ((E, 2) int32),
+ *   flag[f] = heading(f) | (heading(f) != heading(e)) << 2 (E uint8; every f is written once because succ is a permutation).  status:
+ *   device int, zeroed by the caller; nonzero afterwards means a successor was not live (labels and mask do not belong together).
+ * ig_ring_jump: ONE round of pointer jumping over the E edges; the caller loops it, at most ceil(log2 E) rounds per phase, reading one
+ *   buffer pair and writing another (val_in / ptr_in -> val_out / ptr_out, never in place), and may stop when *changed (device int,
+ *   zeroed by the caller before the round) stays 0.
+ *   phase 0, ring root by min-propagation: val_out[e] = min(val_in[e], val_in[ptr_in[e]]), ptr_out[e] = ptr_in[ptr_in[e]]; first round:
+ *     val_in = NULL stands for val_in[e] = e, and ptr_in = succ.  *changed is set when a value fell.  At the end val = the ring's root.
+ *   phase 1, vertex ranking with the cycle cut at the root (a pointer of -1 is the end of the list): val_out[e] = val_in[e] +
+ *     (ptr_in[e] >= 0 ? val_in[ptr_in[e]] : 0), ptr_out[e] = ptr_in[e] >= 0 ? ptr_in[ptr_in[e]] : -1; first round: val_in = NULL stands for
+ *     val_in[e] = flag[e] >> 2 & 1 and ptr_in = succ stands for (succ[e] == root[e] ? -1 : succ[e]); root and flag are read in that
+ *     round only.  *changed is set while a pointer is still >= 0.  At the end val[e] = the turn edges from e to the end of its ring, so
+ *     val[root] = the ring's vertices and val[root[e]] - val[e] = the position of turn edge e among them.
+ * ig_ring_sums: sums (n_rings, 2) int64 += {vertices, twice the signed area} of every ring (the caller zeroes); ring_id (E int32) holds
+ *   at root positions the ring's row in sums (dense; other positions are not read).  Integer atomics, one per run of adjacent edges of
+ *   one ring in a wave.
+ * ig_ring_emit: vertices (n_vertices, 2) int32: for every turn edge e, vertices[first[ring_id[root[e]]] + rank[root[e]] - rank[e]] =
+ *   tail[e]; rank = the result of phase 1, first (n_rings int64) = where the ring's vertices start.  status: device int, zeroed by the
+ *   caller; nonzero afterwards means a destination lay outside [0, n_vertices) (nothing is written there). */
+int ig_edge_mask(const int* labels, unsigned char* mask, unsigned long long* total, int n, int H, int W, void* stream);
+int ig_edge_link(const int* labels, const unsigned char* mask, const int* off, int* succ, int* tail, unsigned char* flag, int n, int H,
+                 int W, long E, int* status, void* stream);
+int ig_ring_jump(int phase, const int* val_in, const int* ptr_in, int* val_out, int* ptr_out, const int* root, const unsigned char* flag,
+                 long E, int* changed, void* stream);
+int ig_ring_sums(const int* root, const int* ring_id, const int* tail, const unsigned char* flag, long long* sums, long E, long n_rings,
+                 void* stream);
+int ig_ring_emit(const int* root, const int* ring_id, const int* rank, const int* tail, const unsigned char* flag, const long long* first,
+                 int* vertices, long E, long n_rings, long n_vertices, int* status, void* stream);
 int ig_confusion_update(const long long* y_true, const long long* y_pred, unsigned long long* confusion, long n, int k,
                         long ignore_index, int has_ignore, void* stream);
 /* torch.optim.AdamW step on a flat buffer (+ clip_weights, + bf16 shadow refresh)        base.py:103-126 */

@@ -20,6 +20,7 @@
 // steps and UNION_CAP retries are far beyond what compression leaves, and a lane that reaches a cap stops, sets *status and every other
 // lane leaves its loop at its next look at *status (once per 256 steps): a bug cannot spin.  The host raises on a nonzero status.
 #include "common.h"
+#include "segreduce.h"
 
 namespace {
 
@@ -208,47 +209,6 @@ __global__ __launch_bounds__(CTPB) void ccl_flatten_kernel(int* __restrict__ lab
     if (l < 0) return;
     const int r = g_find(par, l, status);
     if (r >= 0 && r != l) __hip_atomic_store(&par[p], r, RLX_AGENT);  // an ancestor replaces an ancestor: concurrent finds stay valid
-}
-
-// ---- segmented wave reductions -------------------------------------------------------------------------------------------------------
-// Lanes hold (key, value); runs of equal keys in ADJACENT lanes are reduced to the first lane of the run, which then issues ONE atomic.
-// Equal keys that are not adjacent reach memory as separate atomics (same result).  All 64 lanes must call.
-struct Seg {
-    bool head;
-    int end;  // last lane of this lane's run
-};
-__device__ __forceinline__ Seg seg_of(int key) {
-    const int lane = threadIdx.x & 63;
-    const int prev = __shfl_up(key, 1, 64);
-    Seg s;
-    s.head = lane == 0 || prev != key;
-    const unsigned long long heads = __ballot(s.head);
-    const unsigned long long above = lane == 63 ? 0ull : heads & ~((2ull << lane) - 1ull);
-    s.end = above ? __ffsll((long long)above) - 2 : 63;
-    return s;
-}
-struct OpAdd {
-    template <typename T>
-    __device__ static T f(T a, T b) { return a + b; }
-};
-struct OpMin {
-    template <typename T>
-    __device__ static T f(T a, T b) { return a < b ? a : b; }
-};
-struct OpMax {
-    template <typename T>
-    __device__ static T f(T a, T b) { return a > b ? a : b; }
-};
-// after the call the head lane of a run holds the reduction over the run
-template <typename Op, typename T>
-__device__ __forceinline__ T seg_reduce(T v, const Seg& s) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const T other = __shfl_down(v, o, 64);
-        if (lane + o <= s.end) v = Op::f(v, other);
-    }
-    return v;
 }
 
 // area[root] = pixels of the region, 0 elsewhere (area zeroed by the entry point); grid.y = image

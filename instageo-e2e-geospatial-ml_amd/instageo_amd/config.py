@@ -68,6 +68,8 @@ DEFAULTS: Dict[str, Any] = {'root_dir': None,
           # chip / tile inference (not in the reference): sieve of regions below min_region pixels (0 = off) under 4- or 8-connectivity
           # with at most sieve_passes passes, and the region table regions_*.csv (postprocess.py)
           'min_region': 0, 'connectivity': 4, 'sieve_passes': 8, 'save_regions': False,
+          # the regions of the written class map as polygons_*.geojson, traced on the device under `connectivity` (vectorize.py)
+          'save_polygons': False,
           # calibrated probabilities (not in the reference): logits / temperature in front of every softmax consumer (predict_step, the
           # blended tile canvas, the test epoch's ROC-AUC).  temperature: a float > 0, None = 1.0 (nothing is scaled); calibration: the
           # calibration.json of mode=calibrate to take it from (one of the two).  calibration_metrics: mode=eval also logs test_nll /

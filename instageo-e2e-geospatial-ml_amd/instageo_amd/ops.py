@@ -934,6 +934,79 @@ def boundary_update(gt, pred, gt_d2, pred_d2, thresholds, band, trimap, ncls: in
           _p(band), _p(trimap), n, H * W, int(ncls), int(fill), _stream())
 
 
+MAX_EDGES = 2**31 - 1  # compact edge ids are int32
+
+
+def edge_mask(labels):
+    """labels (n, H, W) | (H, W) int32 of :func:`ccl_label` -> (mask uint8 of the same shape: bits 0-3 the live sides of the pixel, bits
+    4-6 their number; total (1,) int64 on the device = the live edges of all images) (include/instageo_hip.h)."""
+    assert labels.dtype == torch.int32 and labels.dim() in (2, 3)
+    n = labels.shape[0] if labels.dim() == 3 else 1
+    H, W = labels.shape[-2:]
+    mask = torch.empty(labels.shape, dtype=torch.uint8, device=labels.device)
+    total = torch.zeros(1, dtype=torch.int64, device=labels.device)
+    # HBM bytes: the labels once (the rows above and below are L2 hits) + the mask written
+    _call("ig_edge_mask", float(labels.numel()) * 5, _p(labels), _p(mask), _p(total), n, H, W, _stream())
+    return mask, total
+
+
+def edge_link(labels, mask, off, n_edges: int):
+    """-> (succ (E,) int32, tail (E, 2) int32 (x, y), flag (E,) uint8 = heading | turn << 2) of the ``n_edges`` live edges; ``off`` int32 of
+    the labels' shape = the exclusive scan of ``mask >> 4``.  Raises when a successor is not live (mask / off of other labels)."""
+    assert labels.dtype == torch.int32 and labels.dim() in (2, 3) and mask.dtype == torch.uint8 and off.dtype == torch.int32
+    assert mask.shape == labels.shape and off.shape == labels.shape
+    n = labels.shape[0] if labels.dim() == 3 else 1
+    H, W = labels.shape[-2:]
+    E = int(n_edges)
+    dev = labels.device
+    succ = torch.empty(E, dtype=torch.int32, device=dev)
+    tail = torch.empty((E, 2), dtype=torch.int32, device=dev)
+    flag = torch.empty(E, dtype=torch.uint8, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    _call("ig_edge_link", float(labels.numel()) * 9 + float(E) * 17, _p(labels), _p(mask), _p(off), _p(succ), _p(tail), _p(flag), n, H, W, E,
+          _p(status), _stream())
+    if E and n and int(status.item()):
+        raise _lib.HipLibraryError(f"ig_edge_link: an edge's successor is not live (status {int(status.item())}); mask / off do not belong to these labels")
+    return succ, tail, flag
+
+
+def ring_jump(phase: int, val_in, ptr_in, val_out, ptr_out, changed, root=None, flag=None) -> None:
+    """One round of pointer jumping over the E edges (include/instageo_hip.h): phase 0 min-propagation, phase 1 ranking; ``val_in`` None =
+    the first round (``ptr_in`` is succ; phase 1 then needs ``root`` and ``flag``).  Out of place; ``changed`` (1,) int32 on the device."""
+    E = ptr_in.numel()
+    for t in (val_in, ptr_in, val_out, ptr_out, root):
+        assert t is None or (t.dtype == torch.int32 and t.numel() == E)
+    assert changed.dtype == torch.int32 and (flag is None or (flag.dtype == torch.uint8 and flag.numel() == E))
+    _call("ig_ring_jump", float(E) * 24, int(phase), _p(val_in), _p(ptr_in), _p(val_out), _p(ptr_out), _p(root), _p(flag), E, _p(changed),
+          _stream())
+
+
+def ring_sums(root, ring_id, tail, flag, n_rings: int):
+    """-> (n_rings, 2) int64 {vertices, twice the signed area} of every ring; ``ring_id`` int32 holds the ring's row at root positions."""
+    E = root.numel()
+    assert root.dtype == torch.int32 and ring_id.dtype == torch.int32 and ring_id.numel() == E and flag.dtype == torch.uint8
+    assert tail.dtype == torch.int32 and tuple(tail.shape) == (E, 2) and flag.numel() == E
+    sums = torch.zeros((int(n_rings), 2), dtype=torch.int64, device=root.device)
+    _call("ig_ring_sums", float(E) * 17, _p(root), _p(ring_id), _p(tail), _p(flag), _p(sums), E, int(n_rings), _stream())
+    return sums
+
+
+def ring_emit(root, ring_id, rank, tail, flag, first, n_vertices: int):
+    """-> (n_vertices, 2) int32: every turn edge's tail at ``first[ring] + position`` (``rank`` = the result of the ranking rounds,
+    ``first`` (n_rings,) int64).  Raises when a destination lies outside the output."""
+    E = root.numel()
+    assert all(t.dtype == torch.int32 and t.numel() == E for t in (root, ring_id, rank)) and flag.dtype == torch.uint8 and flag.numel() == E
+    assert tail.dtype == torch.int32 and tuple(tail.shape) == (E, 2) and first.dtype == torch.int64
+    V = int(n_vertices)
+    vertices = torch.empty((V, 2), dtype=torch.int32, device=root.device)
+    status = torch.zeros(1, dtype=torch.int32, device=root.device)
+    _call("ig_ring_emit", float(E) * 9 + float(V) * 36, _p(root), _p(ring_id), _p(rank), _p(tail), _p(flag), _p(first), _p(vertices), E,
+          first.numel(), V, _p(status), _stream())
+    if E and int(status.item()):
+        raise _lib.HipLibraryError(f"ig_ring_emit: a vertex lies outside the output (status {int(status.item())}); first / rank are not consistent")
+    return vertices
+
+
 def confusion_update(y_true, y_pred, confusion, k: int, ignore_index: Optional[int]) -> None:
     assert y_true.dtype == torch.int64 and y_pred.dtype == torch.int64 and confusion.dtype == torch.int64
     _lib.call("ig_confusion_update", _p(y_true), _p(y_pred), _p(confusion), y_true.numel(), k,
