@@ -183,6 +183,8 @@ bool ig_deterministic();  // host-side view of the mode (runtime.hip)
 // launches in flight may still use it; NULL on allocation failure.  Not to be grown during a graph capture (first calls are warm-ups).
 void* ig_scratch(int slot, size_t bytes, hipStream_t st);                   // per (device, stream, slot): see runtime.hip
 void* ig_scratch2(int slot, size_t bytes, bool may_grow, hipStream_t st);  // may_grow = false: NULL instead of an allocation (stream captures)
+// per-device page of 256 zeroed bytes for the LDS-DMA kernels' out-of-range units; NULL (+ the error text, under `what`) on failure
+const bf16_t* ig_zero_page(const char* what);
 
 // device side ----------------------------------------------------------------------------------
 __device__ __forceinline__ float bf2f(bf16_t h) { return __uint_as_float(((uint32_t)h) << 16); }

@@ -1597,18 +1597,6 @@ __global__ __launch_bounds__(576, 1) void convT_dgrad_direct_kernel(CTDParams p,
 }  // namespace
 IG_DET_TU(conv_direct)  // constant-memory descriptor of the deterministic-reduction mode (common.h)
 
-// NULL (and the error text, under the entry point's name) when it cannot be allocated
-static const bf16_t* cd_zero_page(const char* entry) {
-    static void* z = nullptr;
-    if (!z) {
-        if (hipMalloc(&z, 256) != hipSuccess) {
-            ig_set_error("%s: could not allocate the zero page", entry);
-            return nullptr;
-        }
-        (void)hipMemset(z, 0, 256);
-    }
-    return (const bf16_t*)z;
-}
 // IG_CONV_DIRECT: 0 = off (the implicit GEMMs and conv8.hip serve these shapes), 1 = default
 static bool cd_enabled() { return ig_env_int("IG_CONV_DIRECT", 1) != 0; }
 
@@ -1654,7 +1642,7 @@ int ig_conv3x3_direct(const void* x, const void* w, const float* bias, const flo
         p.tiles_y = (H + 7) / 8;  // 8 x 16 tiles
         p.ntiles = (long)B * p.tiles_x * p.tiles_y;
         constexpr int smem96 = 48 * (27 * 64 + 32) + 2 * 34 * 1024 + 3 * 48 * 4;
-        const bf16_t* zp = cd_zero_page("ig_conv3x3");
+        const bf16_t* zp = ig_zero_page("ig_conv3x3");
         if (!zp) return IG_ERR_HIP;
         const long nwg = p.ntiles < 128 ? p.ntiles : 128;
         const bool st96 = stat_sums && stats_fused && !dgrad;
@@ -1720,7 +1708,7 @@ int ig_conv3x3_wgrad_direct(const void* dy, const void* x, float* dw, float* dbi
     p.ntiles = (long)B * p.tiles_x * p.tiles_y;
     p.dbias = dbias;
     *bias_fused = dbias != nullptr;
-    const bf16_t* zp = cd_zero_page("ig_conv3x3_wgrad");
+    const bf16_t* zp = ig_zero_page("ig_conv3x3_wgrad");
     if (!zp) return IG_ERR_HIP;
     constexpr int smem48b = 3 * 42 * 1024, smem96 = 3 * 52 * 1024, smem192 = 3 * 50 * 1024;
     const int nslices = Cout / 48;
@@ -1751,7 +1739,7 @@ int ig_convT_fwd_direct(const void* x, const void* w, const float* bias, void* y
     p.tiles_y = (H + 7) / 8;  // 8 x 16 input tiles
     p.ntiles = (long)B * p.tiles_x * p.tiles_y;
     constexpr int smem_d = 48 * (27 * 64 + 32) + 2 * 34 * 1024 + 48 * 4;
-    const bf16_t* zp = cd_zero_page("ig_convT_fwd");
+    const bf16_t* zp = ig_zero_page("ig_convT_fwd");
     if (!zp) return IG_ERR_HIP;
     const long nwg_d = p.ntiles < 256 ? p.ntiles : 256;
     ig_note_kernel("convT_direct_dma_kernel<96,48>");
@@ -1775,7 +1763,7 @@ int ig_convT_wgrad_direct(const void* dy, const void* x, float* dw, float* dbias
     if (p.ntiles == 0) return IG_OK;
     long nwg = p.ntiles < 256 ? p.ntiles : 256;
     constexpr int smem = 3 * 48 * 1024;
-    const bf16_t* zp = cd_zero_page("ig_convT_wgrad");
+    const bf16_t* zp = ig_zero_page("ig_convT_wgrad");
     if (!zp) return IG_ERR_HIP;
     ig_note_kernel("convT_wgrad_dma_kernel<96,48>");
     return ig_launch<convT_wgrad_dma_kernel<96, 48>>("ig_convT_wgrad(direct, dma)", dim3((unsigned)nwg), dim3(TW_TPB), smem, (hipStream_t)stream, p, zp);
@@ -1791,7 +1779,7 @@ int ig_convT_dgrad_direct(const void* dy, const void* w, void* dx, int B, int H,
     p.tiles_x = (W + TW - 1) / TW, p.tiles_y = (H + 3) / 4;
     p.ntiles = (long)B * p.tiles_x * p.tiles_y;
     if (p.ntiles == 0) return IG_OK;
-    const bf16_t* zp = cd_zero_page("ig_convT_dgrad");
+    const bf16_t* zp = ig_zero_page("ig_convT_dgrad");
     if (!zp) return IG_ERR_HIP;
     constexpr int smem = 96 * (14 * 64 + 32) + 2 * 32 * 1024 + 16;
     const long nwg = p.ntiles < 256 ? p.ntiles : 256;

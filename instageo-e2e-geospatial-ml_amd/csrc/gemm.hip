@@ -1132,15 +1132,6 @@ inline float* splitk_workspace(size_t bytes, hipStream_t st) {
 }
 
 // ------------------------------------------------------------------------------------ launch
-inline const bf16_t* zero_page() {
-    static void* z = nullptr;
-    if (!z) {
-        if (hipMalloc(&z, 256) != hipSuccess) return nullptr;
-        (void)hipMemset(z, 0, 256);
-    }
-    return (const bf16_t*)z;
-}
-
 constexpr int tr_pitch(int upr) { return upr <= 8 ? 8 : upr <= 12 ? 12 : 16; }
 
 // `engine`: 2 = v2, 1 = v1, for plain-matrix operands.  Gathered operands always run v1 (measured faster on every convolution
@@ -1239,11 +1230,8 @@ int launch_gemm(const AL& al, const BL& bl, const EP& ep_in, int M, int N, int K
     if constexpr (kPlain) {
         if (ver == 2) {
             const int ntiles = tm * tn;
-            const bf16_t* zp = zero_page();
-            if (!zp) {
-                ig_set_error("%s: could not allocate the zero page", what);
-                return IG_ERR_HIP;
-            }
+            const bf16_t* zp = ig_zero_page(what);
+            if (!zp) return IG_ERR_HIP;
 #define IG_LAUNCH_V2(NSEG_)                                                                                              \
     {                                                                                                                     \
         ig_note_kernel("gemm2_kernel<%s,%s,%s,%s,%s,%d,32,1>", AL::kName, BL::kName, EP::kName, A_TR ? "true" : "false", B_TR ? "true" : "false", NSEG_); \
@@ -1361,13 +1349,166 @@ inline PlainLoader plain_b(const void* hi, const void* lo, int R, int C, long ld
     l.R = R, l.C = C, l.ld = ld;
     return l;
 }
+// Gathering loaders (the caller sets `base` with seg_a / seg_b).  The GEMM's rows walk the (Hr, Wr) grid of B images and gather C
+// channels from a tensor on the (Hs, Ws) grid; sign +1 reads forward taps, -1 the data gradient's mirrored ones.  The two overloads
+// take the same arguments so that the generic tails below are written once; 3 x 3 pad 1 has one grid and no KS.
+inline void conv_gather(Conv3Loader& l, int B, int Hr, int Wr, int, int, int C, int, int sign) {
+    l.Mtot = B * Hr * Wr, l.H = Hr, l.W = Wr, l.C = C, l.sign = sign;
+    l.finish();
+}
+inline void conv_gather(ConvKLoader& l, int B, int Hr, int Wr, int Hs, int Ws, int C, int KS, int sign) {
+    l.Mtot = B * Hr * Wr, l.Hr = Hr, l.Wr = Wr, l.Hs = Hs, l.Ws = Ws, l.C = C, l.KS = KS, l.sign = sign;
+    l.finish();
+}
+inline ConvWgtTRLoader wgt_tr(const void* hi, const void* lo, int Cout, int Cin, int ntaps) {
+    ConvWgtTRLoader l{};
+    seg_b(l.base, hi, lo);
+    l.Cout = Cout, l.Cin = Cin, l.ntaps = ntaps;
+    l.finish();
+    return l;
+}
+inline ConvTGradLoader convT_grad(const void* hi, const void* lo, int B, int H, int W, int Cout, int fixed_tap) {
+    ConvTGradLoader l{};
+    seg_a(l.base, hi, lo);
+    l.Mtot = B * H * W, l.H = H, l.W = W, l.Cout = Cout, l.fixed_tap = fixed_tap;
+    l.finish();
+    return l;
+}
+// epilogues; col_scale / col_shift: eval-mode BatchNorm + ReLU folded into the store
+inline EpStore ep_store(void* hi, void* lo, const float* bias, long ldo, const float* col_scale = nullptr, const float* col_shift = nullptr) {
+    EpStore ep{};
+    ep.out_hi = (bf16_t*)hi, ep.out_lo = (bf16_t*)lo, ep.bias = bias, ep.ldo = ldo;
+    ep.col_scale = col_scale, ep.col_shift = col_shift;
+    return ep;
+}
+inline EpGradStore ep_grad_store(void* hi, void* lo, long ldo, int mode, const void* pre_hi = nullptr, const void* pre_lo = nullptr,
+                                 float* colsum = nullptr) {
+    EpGradStore ep{};
+    ep.out_hi = (bf16_t*)hi, ep.out_lo = (bf16_t*)lo, ep.pre_hi = (const bf16_t*)pre_hi, ep.pre_lo = (const bf16_t*)pre_lo;
+    ep.ldo = ldo, ep.mode = mode, ep.colsum = colsum;
+    return ep;
+}
+template <class EP>
+inline void set_dropout(EP& ep, unsigned seed, const unsigned* seed_dev, float p) {
+    ep.drop_seed = seed, ep.drop_seed_dev = seed_dev;
+    ep.drop_thresh = ig_drop_thresh16(p);
+    ep.drop_inv = ig_drop_inv(p);
+}
+// C[M][N] = a[M][K] @ b[N][K]^T for ig_gemm8_nt (gemm8.hip); the caller adds what its kind needs (bias, outputs, dact, ...)
+inline G8Params g8_params(const void* a_hi, const void* a_lo, const void* b_hi, const void* b_lo, int M, int N, int K, int kind) {
+    G8Params g{};
+    seg_a(g.a, a_hi, a_lo), seg_b(g.b, b_hi, b_lo);
+    g.nseg = a_lo ? 3 : 1, g.M = M, g.N = N, g.K = K, g.lda = K, g.ldb = K, g.ldo = N, g.kind = kind;
+    return g;
+}
 inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
-
-}  // namespace
-IG_DET_TU(gemm)  // constant-memory descriptor of the deterministic-reduction mode (common.h)
 
 #define IG_SPLIT_CONSISTENT(a_lo, b_lo) \
     IG_REQUIRE(((a_lo) == nullptr) == ((b_lo) == nullptr), "split (lo) pointers must be given for all bf16 operands or none")
+
+// The checks every convolution entry point starts with, in this order; KS = 3 always fits.
+inline int conv_checks(const char* entry, bool ptrs, int Cin, int Cout, const void* a_lo, const void* b_lo, int KS = 3, int H = 1, int W = 1) {
+    IG_REQUIRE(ptrs, "%s: null pointer", entry);
+    IG_REQUIRE(Cin % 8 == 0 && Cout % 8 == 0, "%s: channels must be multiples of 8", entry);
+    IG_REQUIRE(KS >= 3 && (KS & 1) && KS <= 9 && H + 3 - KS > 0 && W + 3 - KS > 0, "%s: kernel size %d does not fit a %d x %d input", entry, KS, H, W);
+    IG_SPLIT_CONSISTENT(a_lo, b_lo);
+    return IG_OK;
+}
+
+// dx[M][K] = dy[M][N] @ w[N][K]: the reduce dimension is N.  w[N][K] is a TR B operand (rows n, contiguous k); its transpose wt[K][N]
+// (WT) is contiguous in N like dy, the forward form.
+template <bool WT>
+int linear_dgrad(const char* what, const void* dy_hi, const void* dy_lo, const void* w_hi, const void* w_lo, void* dx_hi, void* dx_lo,
+                 const void* pre_hi, const void* pre_lo, float* dx_colsum, int M, int N, int K, int mode, void* stream) {
+    // dx_colsum (optional): dx_colsum[k] += sum_m dx[m][k] (bias gradient of the layer that produced x)
+    return launch_gemm<PlainLoader, PlainLoader, EpGradStore, false, !WT>(
+        plain_a(dy_hi, dy_lo, M, N, N), WT ? plain_b(w_hi, w_lo, K, N, N) : plain_b(w_hi, w_lo, N, K, K),
+        ep_grad_store(dx_hi, dx_lo, K, mode, pre_hi, pre_lo, dx_colsum), M, K, N, 1, dy_lo != nullptr, (hipStream_t)stream, what);
+}
+
+// The halo-tile direct convolution of the narrow last stages (conv_direct.hip), forward (dgrad = 0) or data gradient: the bf16 kernel
+// when input and output are plain, the split one when both are split, IG_ERR_UNSUPPORTED for a mix (and for every shape they decline).
+inline int conv3x3_direct_any(const void* x_hi, const void* x_lo, const void* w_hi, const void* w_lo, const float* bias, const float* bn_scale,
+                              const float* bn_shift, void* y_hi, void* y_lo, int B, int H, int W, int Cin, int Cout, int dgrad,
+                              unsigned drop_seed, const unsigned* drop_seed_dev, float drop_p, void* stream, double* sums = nullptr,
+                              int* fused = nullptr) {
+    if (!x_lo && !y_lo)
+        return ig_conv3x3_direct(x_hi, w_hi, bias, bn_scale, bn_shift, y_hi, B, H, W, Cin, Cout, dgrad, drop_seed, drop_seed_dev, drop_p, stream,
+                                 sums, fused);
+    if (x_lo && y_lo)
+        return ig_conv3x3_direct_split(x_hi, x_lo, w_hi, w_lo, bias, bn_scale, bn_shift, y_hi, y_lo, B, H, W, Cin, Cout, dgrad, drop_seed,
+                                       drop_seed_dev, drop_p, stream, sums, fused);
+    return IG_ERR_UNSUPPORTED;
+}
+
+// Generic implicit-GEMM tails of nn.Conv2d(kernel_size=KS, padding=1), written once for both gathering loaders: Conv3Loader (KS = 3)
+// and ConvKLoader stay distinct kernels.  x (B,H,W,Cin) -> y (B,Ho,Wo,Cout), Ho = H + 3 - KS.
+template <class GL>
+int conv_fwd_gemm(const char* what, const void* x_hi, const void* x_lo, const void* w_hi, const void* w_lo, const float* bias,
+                  const float* bn_scale, const float* bn_shift, void* y_hi, void* y_lo, int B, int H, int W, int Cin, int Cout, int KS,
+                  void* stream) {
+    const int K = KS * KS * Cin;
+    GL al{};
+    seg_a(al.base, x_hi, x_lo);
+    conv_gather(al, B, H + 3 - KS, W + 3 - KS, H, W, Cin, KS, 1);
+    return launch_gemm<GL, PlainLoader, EpStore, false, false>(al, plain_b(w_hi, w_lo, Cout, K, K),
+                                                               ep_store(y_hi, y_lo, bias, Cout, bn_scale, bn_shift), al.Mtot, Cout, K, 1,
+                                                               x_lo != nullptr, (hipStream_t)stream, what);
+}
+template <class GL>
+int conv_dgrad_gemm(const char* what, const void* dy_hi, const void* dy_lo, const void* w_hi, const void* w_lo, void* dx_hi, void* dx_lo,
+                    int B, int H, int W, int Cin, int Cout, int KS, unsigned drop_seed, const unsigned* drop_seed_dev, float drop_p,
+                    void* stream) {
+    GL al{};
+    seg_a(al.base, dy_hi, dy_lo);
+    conv_gather(al, B, H, W, H + 3 - KS, W + 3 - KS, Cout, KS, -1);
+    EpGradStore ep = ep_grad_store(dx_hi, dx_lo, Cin, 2);
+    set_dropout(ep, drop_seed, drop_seed_dev, drop_p);
+    return launch_gemm<GL, ConvWgtTRLoader, EpGradStore, false, true>(al, wgt_tr(w_hi, w_lo, Cout, Cin, KS * KS), ep, al.Mtot, Cin,
+                                                                      KS * KS * Cout, 1, dy_lo != nullptr, (hipStream_t)stream, what);
+}
+template <class GL>
+int conv_wgrad_gemm(const char* what, const void* dy_hi, const void* dy_lo, const void* x_hi, const void* x_lo, float* dw, int B, int H,
+                    int W, int Cin, int Cout, int KS, void* stream) {
+    const int K = KS * KS * Cin;
+    GL bl{};
+    seg_b(bl.base, x_hi, x_lo);
+    conv_gather(bl, B, H + 3 - KS, W + 3 - KS, H, W, Cin, KS, 1);
+    EpAtomic ep{dw, (long)K, 0, 0, nullptr, 0};
+    return launch_gemm<PlainLoader, GL, EpAtomic, true, true>(plain_a(dy_hi, dy_lo, bl.Mtot, Cout, Cout), bl, ep, Cout, K, bl.Mtot, 1,
+                                                              dy_lo != nullptr, (hipStream_t)stream, what, true);
+}
+
+// The engines in front of the generic weight-gradient GEMM of Conv2d 3 x 3 (kind 0) and ConvTranspose2d (kind 1), and the bias
+// gradient dbias[co] += sum over the bias_rows rows of dy (optional).  Wide stages: the 8-phase engine with a gathering operand
+// (gemm8w.hip).  Narrow stages: `direct`, register-resident partial sums over halo tiles (conv_direct.hip); it accumulates into dw, so
+// split operands are three launches of the bf16 kernel: dy^T x = dy_hi^T x_hi + dy_hi^T x_lo + dy_lo^T x_hi (lo x lo dropped, as in
+// every split GEMM here; 1.7 ms at 48 channels, B = 216, against 4.4 ms on the gather GEMM, whose 128 x 128 tiles fit a 48-row output
+// badly).  The bias gradient is linear in dy: fused, it rides on the launches that carry dy_hi and dy_lo against x_hi.
+// *handled = false (and IG_OK): no engine took the shape, the bias gradient is done and the caller runs its generic GEMM.
+typedef int (*ConvWgradDirect)(const void* dy, const void* x, float* dw, float* dbias, int* bias_fused, int B, int H, int W, int Cin, int Cout,
+                               void* stream);
+inline int conv_wgrad_engines(int kind, ConvWgradDirect direct, long bias_rows, const void* dy_hi, const void* dy_lo, const void* x_hi,
+                              const void* x_lo, float* dw, float* dbias, int B, int H, int W, int Cin, int Cout, void* stream, bool* handled) {
+    int fused = 0, f2 = 0;
+    *handled = true;
+    int rc = ig_wgrad8_conv(kind, dy_hi, dy_lo, x_hi, x_lo, dw, B, H, W, Cin, Cout, stream);
+    if (rc == IG_ERR_UNSUPPORTED) {
+        rc = direct(dy_hi, x_hi, dw, dbias, &fused, B, H, W, Cin, Cout, stream);
+        if (rc == IG_ERR_UNSUPPORTED) {
+            *handled = false, rc = IG_OK;
+        } else if (dy_lo) {
+            if (rc == IG_OK) rc = direct(dy_hi, x_lo, dw, nullptr, &f2, B, H, W, Cin, Cout, stream);
+            if (rc == IG_OK) rc = direct(dy_lo, x_hi, dw, fused ? dbias : nullptr, &f2, B, H, W, Cin, Cout, stream);
+        }
+    }
+    // the one place that decides the bias gradient: an engine fused it, or one column-sum pass over dy follows
+    if (rc == IG_OK && dbias && !fused) rc = ig_colsum(dy_hi, dy_lo, dbias, bias_rows, Cout, stream);
+    return rc;
+}
+
+}  // namespace
+IG_DET_TU(gemm)  // constant-memory descriptor of the deterministic-reduction mode (common.h)
 
 extern "C" {
 
@@ -1380,16 +1521,14 @@ int ig_linear_fwd(const void* x_hi, const void* x_lo, const void* w_hi, const vo
     IG_SPLIT_CONSISTENT(x_lo, w_lo);
     IG_REQUIRE((x_lo == nullptr) == (y_lo == nullptr), "ig_linear_fwd: input and output must both be split or both plain");
     {  // 256 x 256 x 64 8-phase engine (gemm8.hip) for the shapes it covers
-        G8Params g{};
-        seg_a(g.a, x_hi, x_lo), seg_b(g.b, w_hi, w_lo);
-        g.nseg = x_lo ? 3 : 1, g.M = M, g.N = N, g.K = K, g.lda = K, g.ldb = K, g.ldo = N, g.kind = 0, g.act = act, g.bias = bias;
+        G8Params g = g8_params(x_hi, x_lo, w_hi, w_lo, M, N, K, 0);
+        g.act = act, g.bias = bias;
         g.out_hi = (bf16_t*)y_hi, g.out_lo = (bf16_t*)y_lo, g.dact_hi = (bf16_t*)pre_hi, g.dact_lo = (bf16_t*)pre_lo;
         const int rc = ig_gemm8_nt(g, stream);
         if (rc != IG_ERR_UNSUPPORTED) return rc;
     }
-    EpStore ep{};
-    ep.out_hi = (bf16_t*)y_hi, ep.out_lo = (bf16_t*)y_lo, ep.pre_hi = (bf16_t*)pre_hi, ep.pre_lo = (bf16_t*)pre_lo;
-    ep.bias = bias, ep.ldo = N, ep.act = act;
+    EpStore ep = ep_store(y_hi, y_lo, bias, N);
+    ep.pre_hi = (bf16_t*)pre_hi, ep.pre_lo = (bf16_t*)pre_lo, ep.act = act;
     return launch_gemm<PlainLoader, PlainLoader, EpStore, false, false>(
         plain_a(x_hi, x_lo, M, K, K), plain_b(w_hi, w_lo, N, K, K), ep, M, N, K, 1, x_lo != nullptr, (hipStream_t)stream,
         "ig_linear_fwd");
@@ -1402,10 +1541,8 @@ int ig_linear_residual_fwd(const void* x_hi, const void* x_lo, const void* w_hi,
     IG_REQUIRE(N % 8 == 0 && K % 8 == 0, "ig_linear_residual_fwd: N and K must be multiples of 8");
     IG_SPLIT_CONSISTENT(x_lo, w_lo);
     if (aligned16(x_hi) && aligned16(w_hi) && aligned16(resid) && aligned16(out)) {
-        G8Params g{};
-        seg_a(g.a, x_hi, x_lo), seg_b(g.b, w_hi, w_lo);
-        g.nseg = x_lo ? 3 : 1, g.M = M, g.N = N, g.K = K, g.lda = K, g.ldb = K, g.ldo = N, g.kind = 1, g.bias = bias;
-        g.outf = out, g.resid = resid;
+        G8Params g = g8_params(x_hi, x_lo, w_hi, w_lo, M, N, K, 1);
+        g.bias = bias, g.outf = out, g.resid = resid;
         const int rc = ig_gemm8_nt(g, stream);
         if (rc != IG_ERR_UNSUPPORTED) return rc;
     }
@@ -1422,14 +1559,7 @@ int ig_linear_dgrad(const void* dy_hi, const void* dy_lo, const void* w_hi, cons
     IG_REQUIRE(N % 8 == 0 && K % 8 == 0, "ig_linear_dgrad: N and K must be multiples of 8");
     IG_REQUIRE(mode == 0 || (mode == 1 && pre_hi), "ig_linear_dgrad: mode 1 needs the saved activation-derivative tensor (dact)");
     IG_SPLIT_CONSISTENT(dy_lo, w_lo);
-    EpGradStore ep{};
-    ep.out_hi = (bf16_t*)dx_hi, ep.out_lo = (bf16_t*)dx_lo, ep.pre_hi = (const bf16_t*)pre_hi, ep.pre_lo = (const bf16_t*)pre_lo;
-    ep.ldo = K, ep.mode = mode;
-    ep.colsum = dx_colsum;  // optional: dx_colsum[k] += sum_m dx[m][k] (bias gradient of the layer that produced x)
-    // C[m][k] = sum_n dy[m][n] * w[n][k]: reduce dim = N; B operand is TR (rows n, contiguous k)
-    return launch_gemm<PlainLoader, PlainLoader, EpGradStore, false, true>(
-        plain_a(dy_hi, dy_lo, M, N, N), plain_b(w_hi, w_lo, N, K, K), ep, M, K, N, 1, dy_lo != nullptr, (hipStream_t)stream,
-        "ig_linear_dgrad");
+    return linear_dgrad<false>("ig_linear_dgrad", dy_hi, dy_lo, w_hi, w_lo, dx_hi, dx_lo, pre_hi, pre_lo, dx_colsum, M, N, K, mode, stream);
 }
 
 // ig_linear_dgrad with the weight given TRANSPOSED: wt[K][N] = w^T.  Both operands are then contiguous in the reduce dimension N
@@ -1443,22 +1573,13 @@ int ig_linear_dgrad_wt(const void* dy_hi, const void* dy_lo, const void* wt_hi, 
     IG_SPLIT_CONSISTENT(dy_lo, wt_lo);
     IG_REQUIRE((dy_lo == nullptr) == (dx_lo == nullptr), "ig_linear_dgrad_wt: input and output must both be split or both plain");
     if (mode == 1 || dx_colsum == nullptr) {
-        G8Params g{};
-        seg_a(g.a, dy_hi, dy_lo), seg_b(g.b, wt_hi, wt_lo);
-        g.nseg = dy_lo ? 3 : 1, g.M = M, g.N = K, g.K = N, g.lda = N, g.ldb = N, g.ldo = K;
-        g.kind = mode == 1 ? 2 : 0, g.act = 0, g.bias = nullptr;
+        G8Params g = g8_params(dy_hi, dy_lo, wt_hi, wt_lo, M, K, N, mode == 1 ? 2 : 0);
         g.out_hi = (bf16_t*)dx_hi, g.out_lo = (bf16_t*)dx_lo;
         if (mode == 1) g.dact_hi = (bf16_t*)pre_hi, g.dact_lo = (bf16_t*)pre_lo, g.colsum = dx_colsum;
         const int rc = ig_gemm8_nt(g, stream);
         if (rc != IG_ERR_UNSUPPORTED) return rc;
     }
-    EpGradStore ep{};
-    ep.out_hi = (bf16_t*)dx_hi, ep.out_lo = (bf16_t*)dx_lo, ep.pre_hi = (const bf16_t*)pre_hi, ep.pre_lo = (const bf16_t*)pre_lo;
-    ep.ldo = K, ep.mode = mode;
-    ep.colsum = dx_colsum;
-    return launch_gemm<PlainLoader, PlainLoader, EpGradStore, false, false>(
-        plain_a(dy_hi, dy_lo, M, N, N), plain_b(wt_hi, wt_lo, K, N, N), ep, M, K, N, 1, dy_lo != nullptr, (hipStream_t)stream,
-        "ig_linear_dgrad_wt");
+    return linear_dgrad<true>("ig_linear_dgrad_wt", dy_hi, dy_lo, wt_hi, wt_lo, dx_hi, dx_lo, pre_hi, pre_lo, dx_colsum, M, N, K, mode, stream);
 }
 
 // dw[N][K] += dy[M][N]^T @ x[M][K]   (fp32 atomic accumulate)
@@ -1530,31 +1651,17 @@ int ig_patch_embed_fwd(const void* p_hi, const void* p_lo, const void* w_hi, con
 int ig_conv3x3_fwd(const void* x_hi, const void* x_lo, const void* w_hi, const void* w_lo, const float* bias,
                    const float* bn_scale, const float* bn_shift, void* y_hi, void* y_lo, int B, int H, int W, int Cin, int Cout,
                    void* stream) {
-    IG_REQUIRE(x_hi && w_hi && y_hi, "ig_conv3x3_fwd: null pointer");
-    IG_REQUIRE(Cin % 8 == 0 && Cout % 8 == 0, "ig_conv3x3_fwd: channels must be multiples of 8");
-    IG_SPLIT_CONSISTENT(x_lo, w_lo);
+    if (const int rc = conv_checks("ig_conv3x3_fwd", x_hi && w_hi && y_hi, Cin, Cout, x_lo, w_lo)) return rc;
     IG_REQUIRE((bn_scale == nullptr) == (bn_shift == nullptr), "ig_conv3x3_fwd: bn_scale and bn_shift go together");
-    if (!x_lo && !y_lo) {  // narrow last stage: halo-tile direct convolution (conv_direct.hip)
-        const int rc = ig_conv3x3_direct(x_hi, w_hi, bias, bn_scale, bn_shift, y_hi, B, H, W, Cin, Cout, 0, 0, nullptr, 0.f, stream);
-        if (rc != IG_ERR_UNSUPPORTED) return rc;
-    } else if (x_lo && y_lo) {  // the same stage with split operands
-        const int rc = ig_conv3x3_direct_split(x_hi, x_lo, w_hi, w_lo, bias, bn_scale, bn_shift, y_hi, y_lo, B, H, W, Cin, Cout, 0, 0, nullptr, 0.f, stream);
+    {  // narrow last stage: halo-tile direct convolution (conv_direct.hip)
+        const int rc = conv3x3_direct_any(x_hi, x_lo, w_hi, w_lo, bias, bn_scale, bn_shift, y_hi, y_lo, B, H, W, Cin, Cout, 0, 0, nullptr, 0.f, stream);
         if (rc != IG_ERR_UNSUPPORTED) return rc;
     }
     {  // wide stages: implicit GEMM on the 8-phase schedule with gathering LDS-DMA (conv8.hip)
         const int rc = ig_conv8(0, 1, x_hi, x_lo, w_hi, w_lo, bias, bn_scale, bn_shift, y_hi, y_lo, B, H, W, Cin, Cout, 0, nullptr, 0.f, stream);
         if (rc != IG_ERR_UNSUPPORTED) return rc;
     }
-    Conv3Loader al{};
-    seg_a(al.base, x_hi, x_lo);
-    al.Mtot = B * H * W, al.H = H, al.W = W, al.C = Cin, al.sign = 1;
-    al.finish();
-    EpStore ep{};
-    ep.out_hi = (bf16_t*)y_hi, ep.out_lo = (bf16_t*)y_lo, ep.bias = bias, ep.ldo = Cout;
-    ep.col_scale = bn_scale, ep.col_shift = bn_shift;  // eval-mode BatchNorm + ReLU folded into the epilogue
-    return launch_gemm<Conv3Loader, PlainLoader, EpStore, false, false>(
-        al, plain_b(w_hi, w_lo, Cout, 9 * Cin, 9L * Cin), ep, al.Mtot, Cout, 9 * Cin, 1, x_lo != nullptr,
-        (hipStream_t)stream, "ig_conv3x3_fwd");
+    return conv_fwd_gemm<Conv3Loader>("ig_conv3x3_fwd", x_hi, x_lo, w_hi, w_lo, bias, bn_scale, bn_shift, y_hi, y_lo, B, H, W, Cin, Cout, 3, stream);
 }
 
 // The same convolution in front of a training-mode BatchNorm: where the direct kernel runs (the 48-channel last stage) it also
@@ -1564,11 +1671,9 @@ int ig_conv3x3_fwd_stats(const void* x_hi, const void* x_lo, const void* w_hi, c
                          void* y_lo, double* sums, int* fused, int B, int H, int W, int Cin, int Cout, void* stream) {
     IG_REQUIRE(x_hi && w_hi && y_hi && sums && fused, "ig_conv3x3_fwd_stats: null pointer");
     *fused = 0;
-    if (!x_lo && !y_lo && Cin % 8 == 0 && Cout % 8 == 0 && (x_lo == nullptr) == (w_lo == nullptr)) {
-        const int rc = ig_conv3x3_direct(x_hi, w_hi, bias, nullptr, nullptr, y_hi, B, H, W, Cin, Cout, 0, 0, nullptr, 0.f, stream, sums, fused);
-        if (rc != IG_ERR_UNSUPPORTED) return rc;
-    } else if (x_lo && w_lo && y_lo && Cin % 8 == 0 && Cout % 8 == 0) {
-        const int rc = ig_conv3x3_direct_split(x_hi, x_lo, w_hi, w_lo, bias, nullptr, nullptr, y_hi, y_lo, B, H, W, Cin, Cout, 0, 0, nullptr, 0.f, stream, sums, fused);
+    // (arguments ig_conv3x3_fwd would refuse go there for its error text)
+    if (Cin % 8 == 0 && Cout % 8 == 0 && (x_lo == nullptr) == (w_lo == nullptr)) {
+        const int rc = conv3x3_direct_any(x_hi, x_lo, w_hi, w_lo, bias, nullptr, nullptr, y_hi, y_lo, B, H, W, Cin, Cout, 0, 0, nullptr, 0.f, stream, sums, fused);
         if (rc != IG_ERR_UNSUPPORTED) return rc;
     }
     *fused = 0;
@@ -1595,17 +1700,11 @@ int ig_conv3x3_cls_fwd(const void* x_hi, const void* x_lo, const void* w_hi, con
 int ig_conv3x3_dgrad(const void* dy_hi, const void* dy_lo, const void* w_hi, const void* w_lo, void* dx_hi, void* dx_lo,
                      int B, int H, int W, int Cin, int Cout, unsigned drop_seed, const unsigned* drop_seed_dev, float drop_p,
                      void* stream) {
-    IG_REQUIRE(dy_hi && w_hi && dx_hi, "ig_conv3x3_dgrad: null pointer");
-    IG_REQUIRE(Cin % 8 == 0 && Cout % 8 == 0, "ig_conv3x3_dgrad: channels must be multiples of 8");
-    IG_SPLIT_CONSISTENT(dy_lo, w_lo);
+    if (const int rc = conv_checks("ig_conv3x3_dgrad", dy_hi && w_hi && dx_hi, Cin, Cout, dy_lo, w_lo)) return rc;
     IG_REQUIRE(drop_p <= 0.f || (double)B * H * W * Cin < 4294967296.0, "ig_conv3x3_dgrad: dropout needs < 2^32 elements");
-    if (!dy_lo && !dx_lo) {
-        const int rc = ig_conv3x3_direct(dy_hi, w_hi, nullptr, nullptr, nullptr, dx_hi, B, H, W, Cin, Cout, 1, drop_seed, drop_seed_dev,
-                                         drop_p, stream);
-        if (rc != IG_ERR_UNSUPPORTED) return rc;
-    } else if (dy_lo && dx_lo) {
-        const int rc = ig_conv3x3_direct_split(dy_hi, dy_lo, w_hi, w_lo, nullptr, nullptr, nullptr, dx_hi, dx_lo, B, H, W, Cin, Cout, 1, drop_seed,
-                                               drop_seed_dev, drop_p, stream);
+    {
+        const int rc = conv3x3_direct_any(dy_hi, dy_lo, w_hi, w_lo, nullptr, nullptr, nullptr, dx_hi, dx_lo, B, H, W, Cin, Cout, 1, drop_seed,
+                                          drop_seed_dev, drop_p, stream);
         if (rc != IG_ERR_UNSUPPORTED) return rc;
     }
     {
@@ -1613,143 +1712,49 @@ int ig_conv3x3_dgrad(const void* dy_hi, const void* dy_lo, const void* w_hi, con
                                 drop_seed_dev, drop_p, stream);
         if (rc != IG_ERR_UNSUPPORTED) return rc;
     }
-    Conv3Loader al{};
-    seg_a(al.base, dy_hi, dy_lo);
-    al.Mtot = B * H * W, al.H = H, al.W = W, al.C = Cout, al.sign = -1;
-    al.finish();
-    ConvWgtTRLoader bl{};
-    seg_b(bl.base, w_hi, w_lo);
-    bl.Cout = Cout, bl.Cin = Cin;
-    bl.finish();
-    EpGradStore ep{};
-    ep.out_hi = (bf16_t*)dx_hi, ep.out_lo = (bf16_t*)dx_lo, ep.ldo = Cin, ep.mode = 2;
-    ep.drop_seed = drop_seed, ep.drop_seed_dev = drop_seed_dev;
-    ep.drop_thresh = ig_drop_thresh16(drop_p);
-    ep.drop_inv = ig_drop_inv(drop_p);
-    return launch_gemm<Conv3Loader, ConvWgtTRLoader, EpGradStore, false, true>(
-        al, bl, ep, al.Mtot, Cin, 9 * Cout, 1, dy_lo != nullptr, (hipStream_t)stream, "ig_conv3x3_dgrad");
+    return conv_dgrad_gemm<Conv3Loader>("ig_conv3x3_dgrad", dy_hi, dy_lo, w_hi, w_lo, dx_hi, dx_lo, B, H, W, Cin, Cout, 3, drop_seed,
+                                        drop_seed_dev, drop_p, stream);
 }
 
-// dWc[Cout][9][Cin] += sum_pixels dy[p][co] * x[shift_tap(p)][ci]
+// dWc[Cout][9][Cin] += sum_pixels dy[p][co] * x[shift_tap(p)][ci];  dbias[co] += sum_pixels dy[p][co] (optional)
 int ig_conv3x3_wgrad(const void* dy_hi, const void* dy_lo, const void* x_hi, const void* x_lo, float* dw, float* dbias, int B,
                      int H, int W, int Cin, int Cout, void* stream) {
-    IG_REQUIRE(dy_hi && x_hi && dw, "ig_conv3x3_wgrad: null pointer");
-    IG_REQUIRE(Cin % 8 == 0 && Cout % 8 == 0, "ig_conv3x3_wgrad: channels must be multiples of 8");
-    IG_SPLIT_CONSISTENT(dy_lo, x_lo);
-    // dbias (optional): the convolution's bias gradient, dbias[co] += sum_pixels dy[p][co] -- fused into the direct kernels,
-    // otherwise one column-sum pass over dy
-    {  // wide stages: the 8-phase weight-gradient engine with a gathering B operand (gemm8w.hip)
-        const int rc = ig_wgrad8_conv(0, dy_hi, dy_lo, x_hi, x_lo, dw, B, H, W, Cin, Cout, stream);
-        if (rc != IG_ERR_UNSUPPORTED) {
-            if (rc == IG_OK && dbias) return ig_colsum(dy_hi, dy_lo, dbias, (long)B * H * W, Cout, stream);
-            return rc;
-        }
-    }
-    if (!dy_lo) {  // narrow stages: register-resident partial sums over halo tiles (conv_direct.hip)
-        int fused = 0;
-        const int rc = ig_conv3x3_wgrad_direct(dy_hi, x_hi, dw, dbias, &fused, B, H, W, Cin, Cout, stream);
-        if (rc != IG_ERR_UNSUPPORTED) {
-            if (rc == IG_OK && dbias && !fused) return ig_colsum(dy_hi, dy_lo, dbias, (long)B * H * W, Cout, stream);
-            return rc;
-        }
-    } else {
-        // split operands on the narrow stages: the bf16x3 product dy^T x = dy_hi^T x_hi + dy_hi^T x_lo + dy_lo^T x_hi (lo x lo dropped, as in
-        // every split GEMM here) is a SUM of three bf16 products accumulated in fp32 -- and the direct kernel accumulates into dw: three
-        // launches on the operand pairs (1.7 ms at 48 channels, B = 216, against 4.4 ms on the gather GEMM, whose 128 x 128 tiles fit a 48-row
-        // output badly).  The bias gradient is linear in dy: it rides on the launches that carry dy_hi and dy_lo against x_hi.
-        int fused = 0, f2 = 0;
-        int rc = ig_conv3x3_wgrad_direct(dy_hi, x_hi, dw, dbias, &fused, B, H, W, Cin, Cout, stream);
-        if (rc != IG_ERR_UNSUPPORTED) {
-            if (rc == IG_OK) rc = ig_conv3x3_wgrad_direct(dy_hi, x_lo, dw, nullptr, &f2, B, H, W, Cin, Cout, stream);
-            if (rc == IG_OK) rc = ig_conv3x3_wgrad_direct(dy_lo, x_hi, dw, fused ? dbias : nullptr, &f2, B, H, W, Cin, Cout, stream);
-            if (rc == IG_OK && dbias && !fused) return ig_colsum(dy_hi, dy_lo, dbias, (long)B * H * W, Cout, stream);
-            return rc;
-        }
-    }
-    if (dbias) {
-        const int rc = ig_colsum(dy_hi, dy_lo, dbias, (long)B * H * W, Cout, stream);
-        if (rc != IG_OK) return rc;
-    }
-    int Mtot = B * H * W;
-    Conv3Loader bl{};
-    seg_b(bl.base, x_hi, x_lo);
-    bl.Mtot = Mtot, bl.H = H, bl.W = W, bl.C = Cin, bl.sign = 1;
-    bl.finish();
-    EpAtomic ep{dw, 9L * Cin, 0, 0, nullptr, 0};
-    return launch_gemm<PlainLoader, Conv3Loader, EpAtomic, true, true>(
-        plain_a(dy_hi, dy_lo, Mtot, Cout, Cout), bl, ep, Cout, 9 * Cin, Mtot, 1, dy_lo != nullptr, (hipStream_t)stream,
-        "ig_conv3x3_wgrad", true);
+    if (const int rc = conv_checks("ig_conv3x3_wgrad", dy_hi && x_hi && dw, Cin, Cout, dy_lo, x_lo)) return rc;
+    bool handled;
+    const int rc = conv_wgrad_engines(0, ig_conv3x3_wgrad_direct, (long)B * H * W, dy_hi, dy_lo, x_hi, x_lo, dw, dbias, B, H, W, Cin, Cout,
+                                      stream, &handled);
+    if (rc != IG_OK || handled) return rc;
+    return conv_wgrad_gemm<Conv3Loader>("ig_conv3x3_wgrad", dy_hi, dy_lo, x_hi, x_lo, dw, B, H, W, Cin, Cout, 3, stream);
 }
 
 // ---- nn.Conv2d(kernel_size=KS, padding=1), KS odd >= 3, NHWC, weight storage Wc[Cout][KS*KS][Cin]: the 5 x 5 / 7 x 7 convolutions of
 // the 600M variants' decode head (model.py:169-177, 370-375).  x (B,H,W,Cin) -> y (B,Ho,Wo,Cout), Ho = H + 3 - KS. ----
 int ig_convk_fwd(const void* x_hi, const void* x_lo, const void* w_hi, const void* w_lo, const float* bias, const float* bn_scale,
                  const float* bn_shift, void* y_hi, void* y_lo, int B, int H, int W, int Cin, int Cout, int KS, void* stream) {
-    IG_REQUIRE(x_hi && w_hi && y_hi, "ig_convk_fwd: null pointer");
-    IG_REQUIRE(Cin % 8 == 0 && Cout % 8 == 0, "ig_convk_fwd: channels must be multiples of 8");
-    IG_REQUIRE(KS >= 3 && (KS & 1) && KS <= 9 && H + 3 - KS > 0 && W + 3 - KS > 0, "ig_convk_fwd: kernel size %d does not fit a %d x %d input", KS, H, W);
-    IG_SPLIT_CONSISTENT(x_lo, w_lo);
+    if (const int rc = conv_checks("ig_convk_fwd", x_hi && w_hi && y_hi, Cin, Cout, x_lo, w_lo, KS, H, W)) return rc;
     IG_REQUIRE((x_lo == nullptr) == (y_lo == nullptr), "ig_convk_fwd: input and output must both be split or both plain");
     IG_REQUIRE((bn_scale == nullptr) == (bn_shift == nullptr), "ig_convk_fwd: bn_scale and bn_shift go together");
-    const int Ho = H + 3 - KS, Wo = W + 3 - KS;
-    ConvKLoader al{};
-    seg_a(al.base, x_hi, x_lo);
-    al.Mtot = B * Ho * Wo, al.Hr = Ho, al.Wr = Wo, al.Hs = H, al.Ws = W, al.C = Cin, al.KS = KS, al.sign = 1;
-    al.finish();
-    EpStore ep{};
-    ep.out_hi = (bf16_t*)y_hi, ep.out_lo = (bf16_t*)y_lo, ep.bias = bias, ep.ldo = Cout;
-    ep.col_scale = bn_scale, ep.col_shift = bn_shift;
-    return launch_gemm<ConvKLoader, PlainLoader, EpStore, false, false>(
-        al, plain_b(w_hi, w_lo, Cout, KS * KS * Cin, (long)KS * KS * Cin), ep, al.Mtot, Cout, KS * KS * Cin, 1, x_lo != nullptr,
-        (hipStream_t)stream, "ig_convk_fwd");
+    return conv_fwd_gemm<ConvKLoader>("ig_convk_fwd", x_hi, x_lo, w_hi, w_lo, bias, bn_scale, bn_shift, y_hi, y_lo, B, H, W, Cin, Cout, KS, stream);
 }
 
 // dx (B,H,W,Cin) = conv_dgrad(dy (B,Ho,Wo,Cout), w) [* dropout mask of the conv input when drop_p > 0]
 int ig_convk_dgrad(const void* dy_hi, const void* dy_lo, const void* w_hi, const void* w_lo, void* dx_hi, void* dx_lo, int B, int H,
                    int W, int Cin, int Cout, int KS, unsigned drop_seed, const unsigned* drop_seed_dev, float drop_p, void* stream) {
-    IG_REQUIRE(dy_hi && w_hi && dx_hi, "ig_convk_dgrad: null pointer");
-    IG_REQUIRE(Cin % 8 == 0 && Cout % 8 == 0, "ig_convk_dgrad: channels must be multiples of 8");
-    IG_REQUIRE(KS >= 3 && (KS & 1) && KS <= 9 && H + 3 - KS > 0 && W + 3 - KS > 0, "ig_convk_dgrad: kernel size %d does not fit a %d x %d input", KS, H, W);
-    IG_SPLIT_CONSISTENT(dy_lo, w_lo);
+    if (const int rc = conv_checks("ig_convk_dgrad", dy_hi && w_hi && dx_hi, Cin, Cout, dy_lo, w_lo, KS, H, W)) return rc;
     IG_REQUIRE(drop_p <= 0.f || (double)B * H * W * Cin < 4294967296.0, "ig_convk_dgrad: dropout needs < 2^32 elements");
-    const int Ho = H + 3 - KS, Wo = W + 3 - KS;
-    ConvKLoader al{};
-    seg_a(al.base, dy_hi, dy_lo);
-    al.Mtot = B * H * W, al.Hr = H, al.Wr = W, al.Hs = Ho, al.Ws = Wo, al.C = Cout, al.KS = KS, al.sign = -1;
-    al.finish();
-    ConvWgtTRLoader bl{};
-    seg_b(bl.base, w_hi, w_lo);
-    bl.Cout = Cout, bl.Cin = Cin, bl.ntaps = KS * KS;
-    bl.finish();
-    EpGradStore ep{};
-    ep.out_hi = (bf16_t*)dx_hi, ep.out_lo = (bf16_t*)dx_lo, ep.ldo = Cin, ep.mode = 2;
-    ep.drop_seed = drop_seed, ep.drop_seed_dev = drop_seed_dev;
-    ep.drop_thresh = ig_drop_thresh16(drop_p);
-    ep.drop_inv = ig_drop_inv(drop_p);
-    return launch_gemm<ConvKLoader, ConvWgtTRLoader, EpGradStore, false, true>(
-        al, bl, ep, al.Mtot, Cin, KS * KS * Cout, 1, dy_lo != nullptr, (hipStream_t)stream, "ig_convk_dgrad");
+    return conv_dgrad_gemm<ConvKLoader>("ig_convk_dgrad", dy_hi, dy_lo, w_hi, w_lo, dx_hi, dx_lo, B, H, W, Cin, Cout, KS, drop_seed,
+                                        drop_seed_dev, drop_p, stream);
 }
 
 // dWc[Cout][KS*KS][Cin] += sum over output pixels of dy[p][co] * x[shift_tap(p)][ci];  dbias[co] += sum_p dy[p][co] (optional)
 int ig_convk_wgrad(const void* dy_hi, const void* dy_lo, const void* x_hi, const void* x_lo, float* dw, float* dbias, int B, int H,
                    int W, int Cin, int Cout, int KS, void* stream) {
-    IG_REQUIRE(dy_hi && x_hi && dw, "ig_convk_wgrad: null pointer");
-    IG_REQUIRE(Cin % 8 == 0 && Cout % 8 == 0, "ig_convk_wgrad: channels must be multiples of 8");
-    IG_REQUIRE(KS >= 3 && (KS & 1) && KS <= 9 && H + 3 - KS > 0 && W + 3 - KS > 0, "ig_convk_wgrad: kernel size %d does not fit a %d x %d input", KS, H, W);
-    IG_SPLIT_CONSISTENT(dy_lo, x_lo);
-    const int Ho = H + 3 - KS, Wo = W + 3 - KS, Mo = B * Ho * Wo;
-    if (dbias) {
-        const int rc = ig_colsum(dy_hi, dy_lo, dbias, (long)Mo, Cout, stream);
+    if (const int rc = conv_checks("ig_convk_wgrad", dy_hi && x_hi && dw, Cin, Cout, dy_lo, x_lo, KS, H, W)) return rc;
+    if (dbias) {  // no engine in front of this GEMM, so none that could have fused the bias gradient
+        const int rc = ig_colsum(dy_hi, dy_lo, dbias, (long)B * (H + 3 - KS) * (W + 3 - KS), Cout, stream);
         if (rc != IG_OK) return rc;
     }
-    ConvKLoader bl{};
-    seg_b(bl.base, x_hi, x_lo);
-    bl.Mtot = Mo, bl.Hr = Ho, bl.Wr = Wo, bl.Hs = H, bl.Ws = W, bl.C = Cin, bl.KS = KS, bl.sign = 1;
-    bl.finish();
-    EpAtomic ep{dw, (long)KS * KS * Cin, 0, 0, nullptr, 0};
-    return launch_gemm<PlainLoader, ConvKLoader, EpAtomic, true, true>(
-        plain_a(dy_hi, dy_lo, Mo, Cout, Cout), bl, ep, Cout, KS * KS * Cin, Mo, 1, dy_lo != nullptr, (hipStream_t)stream,
-        "ig_convk_wgrad", true);
+    return conv_wgrad_gemm<ConvKLoader>("ig_convk_wgrad", dy_hi, dy_lo, x_hi, x_lo, dw, B, H, W, Cin, Cout, KS, stream);
 }
 
 // ---- ConvTranspose2d(k=3,s=2,p=1,op=1), NHWC, weight storage Wc[Cout][9][Cin]  (model.py:361-368) ----
@@ -1757,9 +1762,7 @@ int ig_convk_wgrad(const void* dy_hi, const void* dy_lo, const void* x_hi, const
 int ig_convT_fwd(const void* x_hi, const void* x_lo, const void* w_hi, const void* w_lo, const float* bias, void* y_hi,
                  void* y_lo, int B, int H, int W, int Cin, int Cout, unsigned drop_seed, const unsigned* drop_seed_dev, float drop_p,
                  void* stream) {
-    IG_REQUIRE(x_hi && w_hi && y_hi, "ig_convT_fwd: null pointer");
-    IG_REQUIRE(Cin % 8 == 0 && Cout % 8 == 0, "ig_convT_fwd: channels must be multiples of 8");
-    IG_SPLIT_CONSISTENT(x_lo, w_lo);
+    if (const int rc = conv_checks("ig_convT_fwd", x_hi && w_hi && y_hi, Cin, Cout, x_lo, w_lo)) return rc;
     IG_REQUIRE(drop_p <= 0.f || (double)B * 4 * H * W * Cout < 4294967296.0, "ig_convT_fwd: dropout needs < 2^32 elements");
     if (!x_lo && !y_lo) {  // last stage (96 -> 48): direct sub-pixel kernel (conv_direct.hip)
         const int rc = ig_convT_fwd_direct(x_hi, w_hi, bias, y_hi, B, H, W, Cin, Cout, drop_seed, drop_seed_dev, drop_p, stream);
@@ -1778,13 +1781,10 @@ int ig_convT_fwd(const void* x_hi, const void* x_lo, const void* w_hi, const voi
     seg_b(bl.base, w_hi, w_lo);
     bl.Cout = Cout, bl.C = Cin;
     bl.finish();
-    EpStore ep{};
-    ep.out_hi = (bf16_t*)y_hi, ep.out_lo = (bf16_t*)y_lo, ep.bias = bias, ep.ldo = Cout;
+    EpStore ep = ep_store(y_hi, y_lo, bias, Cout);
     ep.phase_map = 1, ep.H = H, ep.W = W;
     ep.f_hw = make_fdiv(H * W), ep.f_w = make_fdiv(W);
-    ep.drop_seed = drop_seed, ep.drop_seed_dev = drop_seed_dev;
-    ep.drop_thresh = ig_drop_thresh16(drop_p);
-    ep.drop_inv = ig_drop_inv(drop_p);
+    set_dropout(ep, drop_seed, drop_seed_dev, drop_p);
     return launch_gemm<ConvTFwdALoader, ConvTFwdBLoader, EpStore, false, false>(
         al, bl, ep, al.Mtot, Cout, 4 * Cin, 4, x_lo != nullptr, (hipStream_t)stream, "ig_convT_fwd");
 }
@@ -1792,9 +1792,7 @@ int ig_convT_fwd(const void* x_hi, const void* x_lo, const void* w_hi, const voi
 // dx (H,W,Cin) = stride-2 gather of dy (2H,2W,Cout) against Wc
 int ig_convT_dgrad(const void* dy_hi, const void* dy_lo, const void* w_hi, const void* w_lo, void* dx_hi, void* dx_lo,
                    int B, int H, int W, int Cin, int Cout, void* stream) {
-    IG_REQUIRE(dy_hi && w_hi && dx_hi, "ig_convT_dgrad: null pointer");
-    IG_REQUIRE(Cin % 8 == 0 && Cout % 8 == 0, "ig_convT_dgrad: channels must be multiples of 8");
-    IG_SPLIT_CONSISTENT(dy_lo, w_lo);
+    if (const int rc = conv_checks("ig_convT_dgrad", dy_hi && w_hi && dx_hi, Cin, Cout, dy_lo, w_lo)) return rc;
     if (!dy_lo && !dx_lo) {  // last stage (96 -> 48): direct stride-2 gather over phase planes (conv_direct.hip)
         const int rc = ig_convT_dgrad_direct(dy_hi, w_hi, dx_hi, B, H, W, Cin, Cout, stream);
         if (rc != IG_ERR_UNSUPPORTED) return rc;
@@ -1803,64 +1801,25 @@ int ig_convT_dgrad(const void* dy_hi, const void* dy_lo, const void* w_hi, const
         const int rc = ig_conv8(2, 1, dy_hi, dy_lo, w_hi, w_lo, nullptr, nullptr, nullptr, dx_hi, dx_lo, B, H, W, Cout, Cin, 0, nullptr, 0.f, stream);
         if (rc != IG_ERR_UNSUPPORTED) return rc;
     }
-    ConvTGradLoader al{};
-    seg_a(al.base, dy_hi, dy_lo);
-    al.Mtot = B * H * W, al.H = H, al.W = W, al.Cout = Cout, al.fixed_tap = -1;
-    al.finish();
-    ConvWgtTRLoader bl{};
-    seg_b(bl.base, w_hi, w_lo);
-    bl.Cout = Cout, bl.Cin = Cin;
-    bl.finish();
-    EpGradStore ep{};
-    ep.out_hi = (bf16_t*)dx_hi, ep.out_lo = (bf16_t*)dx_lo, ep.ldo = Cin, ep.mode = 0;
+    const ConvTGradLoader al = convT_grad(dy_hi, dy_lo, B, H, W, Cout, -1);
     return launch_gemm<ConvTGradLoader, ConvWgtTRLoader, EpGradStore, false, true>(
-        al, bl, ep, al.Mtot, Cin, 9 * Cout, 1, dy_lo != nullptr, (hipStream_t)stream, "ig_convT_dgrad");
+        al, wgt_tr(w_hi, w_lo, Cout, Cin, 9), ep_grad_store(dx_hi, dx_lo, Cin, 0), al.Mtot, Cin, 9 * Cout, 1, dy_lo != nullptr,
+        (hipStream_t)stream, "ig_convT_dgrad");
 }
 
-// dWc[Cout][tap][Cin] += sum_{input pixels} dy[shift_tap(p)][co] * x[p][ci]     (blockIdx.z = tap)
+// dWc[Cout][tap][Cin] += sum_{input pixels} dy[shift_tap(p)][co] * x[p][ci]     (blockIdx.z = tap);  dbias[co] += sum over the (2H, 2W)
+// output pixels of dy (optional)
 int ig_convT_wgrad(const void* dy_hi, const void* dy_lo, const void* x_hi, const void* x_lo, float* dw, float* dbias, int B,
                    int H, int W, int Cin, int Cout, void* stream) {
-    IG_REQUIRE(dy_hi && x_hi && dw, "ig_convT_wgrad: null pointer");
-    IG_REQUIRE(Cin % 8 == 0 && Cout % 8 == 0, "ig_convT_wgrad: channels must be multiples of 8");
-    IG_SPLIT_CONSISTENT(dy_lo, x_lo);
-    // dbias (optional): dbias[co] += sum over the (2H, 2W) output pixels of dy -- fused into the direct kernel, otherwise one
-    // column-sum pass over dy
-    {  // wide stages: the 8-phase weight-gradient engine with a gathering A operand (gemm8w.hip)
-        const int rc = ig_wgrad8_conv(1, dy_hi, dy_lo, x_hi, x_lo, dw, B, H, W, Cin, Cout, stream);
-        if (rc != IG_ERR_UNSUPPORTED) {
-            if (rc == IG_OK && dbias) return ig_colsum(dy_hi, dy_lo, dbias, 4L * B * H * W, Cout, stream);
-            return rc;
-        }
-    }
-    if (!dy_lo) {  // last stage (96 -> 48): register-resident partial sums (conv_direct.hip)
-        int fused = 0;
-        const int rc = ig_convT_wgrad_direct(dy_hi, x_hi, dw, dbias, &fused, B, H, W, Cin, Cout, stream);
-        if (rc != IG_ERR_UNSUPPORTED) {
-            if (rc == IG_OK && dbias && !fused) return ig_colsum(dy_hi, dy_lo, dbias, 4L * B * H * W, Cout, stream);
-            return rc;
-        }
-    } else {  // split operands: three launches of the bf16 kernel on (hi, hi), (hi, lo), (lo, hi) -- see ig_conv3x3_wgrad
-        int fused = 0, f2 = 0;
-        int rc = ig_convT_wgrad_direct(dy_hi, x_hi, dw, dbias, &fused, B, H, W, Cin, Cout, stream);
-        if (rc != IG_ERR_UNSUPPORTED) {
-            if (rc == IG_OK) rc = ig_convT_wgrad_direct(dy_hi, x_lo, dw, nullptr, &f2, B, H, W, Cin, Cout, stream);
-            if (rc == IG_OK) rc = ig_convT_wgrad_direct(dy_lo, x_hi, dw, fused ? dbias : nullptr, &f2, B, H, W, Cin, Cout, stream);
-            if (rc == IG_OK && dbias && !fused) return ig_colsum(dy_hi, dy_lo, dbias, 4L * B * H * W, Cout, stream);
-            return rc;
-        }
-    }
-    if (dbias) {
-        const int rc = ig_colsum(dy_hi, dy_lo, dbias, 4L * B * H * W, Cout, stream);
-        if (rc != IG_OK) return rc;
-    }
-    int Mtot = B * H * W;
-    ConvTGradLoader al{};
-    seg_a(al.base, dy_hi, dy_lo);
-    al.Mtot = Mtot, al.H = H, al.W = W, al.Cout = Cout, al.fixed_tap = -2;
-    al.finish();
+    if (const int rc = conv_checks("ig_convT_wgrad", dy_hi && x_hi && dw, Cin, Cout, dy_lo, x_lo)) return rc;
+    bool handled;
+    const int rc = conv_wgrad_engines(1, ig_convT_wgrad_direct, 4L * B * H * W, dy_hi, dy_lo, x_hi, x_lo, dw, dbias, B, H, W, Cin, Cout,
+                                      stream, &handled);
+    if (rc != IG_OK || handled) return rc;
+    const ConvTGradLoader al = convT_grad(dy_hi, dy_lo, B, H, W, Cout, -2);
     EpAtomic ep{dw, 9L * Cin, (long)Cin, 0, nullptr, 0};
     return launch_gemm<ConvTGradLoader, PlainLoader, EpAtomic, true, true>(
-        al, plain_b(x_hi, x_lo, Mtot, Cin, Cin), ep, Cout, Cin, Mtot, 9, dy_lo != nullptr, (hipStream_t)stream,
+        al, plain_b(x_hi, x_lo, al.Mtot, Cin, Cin), ep, Cout, Cin, al.Mtot, 9, dy_lo != nullptr, (hipStream_t)stream,
         "ig_convT_wgrad", true);
 }
 

@@ -573,17 +573,6 @@ PlanCache& plan_cache() {
 float* slab_workspace(long nslab, bool capturing, hipStream_t st) {
     return (float*)ig_scratch2(4, (size_t)nslab * W_SLAB * sizeof(float), !capturing, st);
 }
-const bf16_t* w_zero_page() {
-    constexpr int kMaxDev = 16;
-    static void* z[kMaxDev] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) return nullptr;
-    if (!z[dev]) {
-        if (hipMalloc(&z[dev], 256) != hipSuccess) return nullptr;
-        (void)hipMemset(z[dev], 0, 256);
-    }
-    return (const bf16_t*)z[dev];
-}
 
 struct TileRef {  // one output tile of the launch
     int g;         // GEMM (pointer set)
@@ -803,7 +792,7 @@ int w_run(const WKey& key, const std::vector<TileRef>& tl, int M, int lda2_of_g[
         }
     }
     float* ws = slab_workspace(pl.nslab, capturing, st);
-    const bf16_t* zp = w_zero_page();
+    const bf16_t* zp = ig_zero_page(what);
     if (!ws || !zp) {
         if (capturing) return IG_ERR_UNSUPPORTED;
         ig_set_error("%s: could not allocate the slab workspace (%ld slabs)", what, pl.nslab);

@@ -144,6 +144,23 @@ void* ig_scratch2(int slot, size_t bytes, bool may_grow, hipStream_t st) {
     }
     return e->buf[slot];
 }
+// The 256 zeroed bytes the LDS-DMA kernels read in place of an out-of-range unit: one page per device, allocated on first use and never
+// freed.  NULL (and the error text, under the entry point's name) when it cannot be allocated.
+const bf16_t* ig_zero_page(const char* what) {
+    constexpr int kMaxDev = 16;
+    static void* z[kMaxDev] = {};
+    int dev = 0;
+    if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < kMaxDev) {
+        if (z[dev]) return (const bf16_t*)z[dev];
+        if (hipMalloc(&z[dev], 256) == hipSuccess) {
+            (void)hipMemset(z[dev], 0, 256);
+            return (const bf16_t*)z[dev];
+        }
+        z[dev] = nullptr;
+    }
+    ig_set_error("%s: could not allocate the zero page", what);
+    return nullptr;
+}
 
 namespace {
 // grad[i] += shadow[i] * 2^-44 ; shadow[i] = 0 over a table of flat ranges (blockIdx.y = range; two elements per thread where the

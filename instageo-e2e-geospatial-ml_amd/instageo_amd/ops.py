@@ -504,49 +504,47 @@ def convT_wgrad(dy: BT, x: BT, dw, B, H, W, Cin, Cout, dbias=None) -> None:
     _call("ig_convT_wgrad", 2.0 * B * H * W * Cin * Cout * 9, _p(dy.hi), _p(dy.lo), _p(x.hi), _p(x.lo), _p(dw), _p(dbias), B, H, W, Cin, Cout, _stream())
 
 
-def conv3x3_fwd(x: BT, w: BT, bias, y: BT, B, H, W, Cin, Cout, bn_scale=None, bn_shift=None) -> None:
-    """3x3 conv (+bias); with bn_scale/bn_shift also eval-mode BatchNorm + ReLU in the same epilogue."""
-    _call("ig_conv3x3_fwd", 2.0 * B * H * W * Cin * Cout * 9, _p(x.hi), _p(x.lo), _p(w.hi), _p(w.lo), _p(bias), _p(bn_scale), _p(bn_shift),
-          _p(y.hi), _p(y.lo), B, H, W, Cin, Cout, _stream())
+def _conv_entry(op: str, B, H, W, Cin, Cout, ks: int):
+    """(profiling key, work estimate, entry point, its kernel-size argument) of nn.Conv2d(kernel_size=ks, padding=1): ks = 3 has
+    entry points of its own (``ig_conv3x3_*``, no size argument); 5 / 7 (the 600M head) shrink the map to H + 3 - ks and run
+    ``ig_convk_*``, profiled under the 3 x 3 keys."""
+    work = 2.0 * B * (H + 3 - ks) * (W + 3 - ks) * Cin * Cout * ks * ks
+    return f"ig_conv3x3_{op}", work, (f"ig_conv3x3_{op}", ()) if ks == 3 else (f"ig_convk_{op}", (ks,))
 
 
 def conv_fwd(x: BT, w: BT, bias, y: BT, B, H, W, Cin, Cout, ks: int = 3, bn_scale=None, bn_shift=None) -> None:
-    """nn.Conv2d(kernel_size=ks, padding=1): ks = 3 is :func:`conv3x3_fwd`; 5 / 7 (the 600M head) shrink the map to H + 3 - ks."""
-    if ks == 3:
-        return conv3x3_fwd(x, w, bias, y, B, H, W, Cin, Cout, bn_scale, bn_shift)
-    Ho, Wo = H + 3 - ks, W + 3 - ks
-    _call("ig_conv3x3_fwd", 2.0 * B * Ho * Wo * Cin * Cout * ks * ks, _p(x.hi), _p(x.lo), _p(w.hi), _p(w.lo), _p(bias), _p(bn_scale), _p(bn_shift),
-          _p(y.hi), _p(y.lo), B, H, W, Cin, Cout, ks, _stream(), entry="ig_convk_fwd")
+    """Convolution (+bias); with bn_scale/bn_shift also eval-mode BatchNorm + ReLU in the same epilogue."""
+    key, work, (entry, k) = _conv_entry("fwd", B, H, W, Cin, Cout, ks)
+    _call(key, work, _p(x.hi), _p(x.lo), _p(w.hi), _p(w.lo), _p(bias), _p(bn_scale), _p(bn_shift), _p(y.hi), _p(y.lo), B, H, W, Cin, Cout,
+          *k, _stream(), entry=entry)
 
 
 def conv_dgrad(dy: BT, w: BT, dx: BT, B, H, W, Cin, Cout, ks: int = 3, seed: int = 0, p: float = 0.0, seed_dev=None) -> None:
-    if ks == 3:
-        return conv3x3_dgrad(dy, w, dx, B, H, W, Cin, Cout, seed, p, seed_dev)
-    Ho, Wo = H + 3 - ks, W + 3 - ks
-    _call("ig_conv3x3_dgrad", 2.0 * B * Ho * Wo * Cin * Cout * ks * ks, _p(dy.hi), _p(dy.lo), _p(w.hi), _p(w.lo), _p(dx.hi), _p(dx.lo), B, H, W, Cin,
-          Cout, ks, seed, _p(seed_dev), p, _stream(), entry="ig_convk_dgrad")
+    key, work, (entry, k) = _conv_entry("dgrad", B, H, W, Cin, Cout, ks)
+    _call(key, work, _p(dy.hi), _p(dy.lo), _p(w.hi), _p(w.lo), _p(dx.hi), _p(dx.lo), B, H, W, Cin, Cout, *k, seed, _p(seed_dev), p, _stream(),
+          entry=entry)
 
 
 def conv_wgrad(dy: BT, x: BT, dw, B, H, W, Cin, Cout, ks: int = 3, dbias=None) -> None:
-    if ks == 3:
-        return conv3x3_wgrad(dy, x, dw, B, H, W, Cin, Cout, dbias)
-    Ho, Wo = H + 3 - ks, W + 3 - ks
-    _call("ig_conv3x3_wgrad", 2.0 * B * Ho * Wo * Cin * Cout * ks * ks, _p(dy.hi), _p(dy.lo), _p(x.hi), _p(x.lo), _p(dw), _p(dbias), B, H, W, Cin, Cout,
-          ks, _stream(), entry="ig_convk_wgrad")
+    """dw += dy^T x_gathered; ``dbias`` (fp32 [Cout]) additionally accumulates the column sums of dy (the bias gradient)."""
+    key, work, (entry, k) = _conv_entry("wgrad", B, H, W, Cin, Cout, ks)
+    _call(key, work, _p(dy.hi), _p(dy.lo), _p(x.hi), _p(x.lo), _p(dw), _p(dbias), B, H, W, Cin, Cout, *k, _stream(), entry=entry)
+
+
+def conv3x3_fwd(x: BT, w: BT, bias, y: BT, B, H, W, Cin, Cout, bn_scale=None, bn_shift=None) -> None:
+    conv_fwd(x, w, bias, y, B, H, W, Cin, Cout, 3, bn_scale, bn_shift)
+
+
+def conv3x3_dgrad(dy: BT, w: BT, dx: BT, B, H, W, Cin, Cout, seed: int = 0, p: float = 0.0, seed_dev=None) -> None:
+    conv_dgrad(dy, w, dx, B, H, W, Cin, Cout, 3, seed, p, seed_dev)
+
+
+def conv3x3_wgrad(dy: BT, x: BT, dw, B, H, W, Cin, Cout, dbias=None) -> None:
+    conv_wgrad(dy, x, dw, B, H, W, Cin, Cout, 3, dbias)
 
 
 def bn_eval_affine(gamma, beta, rmean, rvar, scale, shift, C: int, eps: float = 1e-5) -> None:
     _lib.call("ig_bn_eval_affine", _p(gamma), _p(beta), _p(rmean), _p(rvar), _p(scale), _p(shift), C, eps, _stream())
-
-
-def conv3x3_dgrad(dy: BT, w: BT, dx: BT, B, H, W, Cin, Cout, seed: int = 0, p: float = 0.0, seed_dev=None) -> None:
-    _call("ig_conv3x3_dgrad", 2.0 * B * H * W * Cin * Cout * 9, _p(dy.hi), _p(dy.lo), _p(w.hi), _p(w.lo), _p(dx.hi), _p(dx.lo), B, H, W, Cin, Cout, seed, _p(seed_dev), p,
-              _stream())
-
-
-def conv3x3_wgrad(dy: BT, x: BT, dw, B, H, W, Cin, Cout, dbias=None) -> None:
-    """dw += dy^T x_gathered; ``dbias`` (fp32 [Cout]) additionally accumulates the column sums of dy (the bias gradient)."""
-    _call("ig_conv3x3_wgrad", 2.0 * B * H * W * Cin * Cout * 9, _p(dy.hi), _p(dy.lo), _p(x.hi), _p(x.lo), _p(dw), _p(dbias), B, H, W, Cin, Cout, _stream())
 
 
 def bn_relu_fwd(x: BT, gamma, beta, rmean, rvar, y: BT, scale, shift, mean, rstd, sums, M: int, C: int, training: bool,

@@ -680,8 +680,9 @@ def test_gemm4_generator_configuration_keys(tmp_path):
 @pytest.mark.parametrize("switch", ["IG_CONV_DIRECT", "IG_CONV8"])
 @pytest.mark.parametrize("value", [None, "0", "1", "2", "abc"])
 def test_engine_switches_are_read_before_any_device_call(built_lib, monkeypatch, switch, value):
-    """An empty batch walks the routing of the convolution entry points -- conv_direct.hip and conv8.hip read their switches and
-    decline or finish -- and returns IG_OK without a HIP call, whatever the switch holds (a non-numeric value counts as 0, as atoi does)."""
+    """An empty batch walks the routing of the linear and convolution entry points -- gemm8.hip, gemm8w.hip, conv_direct.hip and conv8.hip
+    read their switches and decline or finish -- and returns IG_OK without a HIP call, whatever the switch holds (a non-numeric value
+    counts as 0, as atoi does)."""
     lib = built_lib.load()
     if value is None:
         monkeypatch.delenv(switch, raising=False)
@@ -691,3 +692,183 @@ def test_engine_switches_are_read_before_any_device_call(built_lib, monkeypatch,
     assert lib.ig_conv3x3_fwd(p, None, p, None, None, None, None, p, None, 0, 16, 16, 48, 48, None) == 0
     assert lib.ig_conv3x3_fwd(p, None, p, None, None, None, None, p, None, 0, 16, 16, 96, 96, None) == 0
     assert lib.ig_convT_dgrad(p, None, p, None, p, None, 0, 16, 16, 96, 48, None) == 0
+    # every linear and convolution entry point, on the channel counts that pick each engine (generic, direct 48 / 96 / 96 -> 48 / 192,
+    # conv8 and gemm8w's wide stages), plain and split, weight gradients with and without the bias gradient
+    fused = ctypes.c_int(7)
+    for entry in ("ig_linear_fwd", "ig_linear_residual_fwd", "ig_linear_dgrad", "ig_linear_dgrad_wt", "ig_linear_wgrad"):
+        for N, K in ((16, 16), (768, 768), (256, 512)):
+            assert getattr(lib, entry)(*_entry_args(entry, M=0, N=N, K=K)) == 0, (entry, N, K)
+    for entry in ("ig_linear_dgrad", "ig_linear_dgrad_wt"):
+        assert getattr(lib, entry)(*_entry_args(entry, M=0, N=768, K=768, mode=1, dact_hi=p)) == 0, entry
+        assert getattr(lib, entry)(*_entry_args(entry, M=0, N=768, K=768, dx_colsum=p)) == 0, entry
+    ptrs, dims = (ctypes.c_void_p * 1)(16), (ctypes.c_int * 1)(768)
+    assert lib.ig_linear_wgrad_group(1, ptrs, None, ptrs, None, ptrs, dims, dims, 0, 0, None) == 0
+    assert lib.ig_patch_embed_fwd(*_entry_args("ig_patch_embed_fwd", batch=0, bias=p)) == 0
+    convs = [n for n in built_lib.declared_symbols() if re.match(r"ig_(conv3x3|convk|convT)_", n)]
+    assert len(convs) == 11
+    for entry in convs:
+        header_args = re.search(r"\b%s\s*\(([^)]*)\)" % entry, open(built_lib.HEADER_PATH).read()).group(1)
+        for Cin, Cout in ((16, 16), (48, 48), (96, 96), (96, 48), (192, 96), (384, 192), (256, 256)):
+            for split in (False, True):
+                for dbias in ((None, p) if "wgrad" in entry else (None,)):
+                    over = dict(B=0, H=16, W=16, Cin=Cin, Cout=Cout, dbias=dbias, fused=ctypes.cast(ctypes.byref(fused), ctypes.c_void_p))
+                    if split:
+                        over.update({n: p for n in ("x_lo", "w_lo", "y_lo", "dy_lo", "dx_lo")})
+                    over = {k: v for k, v in over.items() if re.search(r"\b%s\b" % k, header_args)}
+                    assert getattr(lib, entry)(*_entry_args(entry, **over)) == 0, (entry, over)
+                    if entry == "ig_conv3x3_fwd_stats":  # an empty batch fuses nothing
+                        assert fused.value == 0, over
+
+
+# ---- characterisation of the GEMM / convolution entry points' host dispatch (csrc/gemm.hip) ------------------------------------------
+_PTR, _PTR8 = ctypes.c_void_p(16), ctypes.c_void_p(8)  # never dereferenced: every call below ends in a check or on an empty batch before any launch
+_OPTIONAL = {"bias", "bn_scale", "bn_shift", "dbias", "dx_colsum", "dact_hi", "dact_lo", "drop_seed_dev", "stream"}
+_SIZES = {"B": 1, "H": 8, "W": 8, "Cin": 16, "Cout": 16, "KS": 5, "M": 8, "N": 16, "K": 16, "D": 16, "batch": 1, "tokens_per_chip": 4,
+          "ncls": 2}
+_DROP = {"drop_p": 0.5, "B": 65536, "H": 256, "W": 256}  # 2^32 elements at one channel
+_SPLIT = {"split": "split (lo) pointers must be given for all bf16 operands or none"}
+
+
+def _entry_args(entry, **over):
+    """Valid-looking arguments of ``entry`` by the parameter names in the header (optional and lo pointers NULL), then ``over``."""
+    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "instageo_hip.h")).read(), flags=re.S)
+    params = re.search(r"\b%s\s*\(([^)]*)\)" % entry, header).group(1).split(",")
+    names = [re.search(r"(\w+)\s*$", a).group(1) for a in params]
+    assert set(over) <= set(names), (entry, over)
+    vals = {n: (None if n in _OPTIONAL or n.endswith("_lo") else _PTR) if "*" in a else _SIZES.get(n, 0) for n, a in zip(names, params)}
+    vals.update(over)
+    return [vals[n] for n in names]
+
+
+# (entry point, case, argument overrides, return code, ig_last_error(), *fused afterwards where the entry point has one: it is handed a
+# host int holding 7): recorded by running this table against the library as it was before the entry points were folded onto shared
+# helpers
+_BAD_CALLS = [
+    ("ig_linear_fwd", "null", {"x_hi": None}, -1, 'ig_linear_fwd: null pointer', None),
+    ("ig_linear_fwd", "N-not-8", {"N": 12}, -1, 'ig_linear_fwd: N and K must be multiples of 8 (got 12, 16)', None),
+    ("ig_linear_fwd", "K-not-8", {"K": 12}, -1, 'ig_linear_fwd: N and K must be multiples of 8 (got 16, 12)', None),
+    ("ig_linear_fwd", "split", {"x_lo": _PTR}, -1, 'split (lo) pointers must be given for all bf16 operands or none', None),
+    ("ig_linear_residual_fwd", "null", {"x_hi": None}, -1, 'ig_linear_residual_fwd: null pointer', None),
+    ("ig_linear_residual_fwd", "N-not-8", {"N": 12}, -1, 'ig_linear_residual_fwd: N and K must be multiples of 8', None),
+    ("ig_linear_residual_fwd", "K-not-8", {"K": 12}, -1, 'ig_linear_residual_fwd: N and K must be multiples of 8', None),
+    ("ig_linear_residual_fwd", "split", {"x_lo": _PTR}, -1, 'split (lo) pointers must be given for all bf16 operands or none', None),
+    ("ig_linear_dgrad", "null", {"dy_hi": None}, -1, 'ig_linear_dgrad: null pointer', None),
+    ("ig_linear_dgrad", "N-not-8", {"N": 12}, -1, 'ig_linear_dgrad: N and K must be multiples of 8', None),
+    ("ig_linear_dgrad", "K-not-8", {"K": 12}, -1, 'ig_linear_dgrad: N and K must be multiples of 8', None),
+    ("ig_linear_dgrad", "split", {"dy_lo": _PTR}, -1, 'split (lo) pointers must be given for all bf16 operands or none', None),
+    ("ig_linear_dgrad_wt", "null", {"dy_hi": None}, -1, 'ig_linear_dgrad_wt: null pointer', None),
+    ("ig_linear_dgrad_wt", "N-not-8", {"N": 12}, -1, 'ig_linear_dgrad_wt: N and K must be multiples of 8', None),
+    ("ig_linear_dgrad_wt", "K-not-8", {"K": 12}, -1, 'ig_linear_dgrad_wt: N and K must be multiples of 8', None),
+    ("ig_linear_dgrad_wt", "split", {"dy_lo": _PTR}, -1, 'split (lo) pointers must be given for all bf16 operands or none', None),
+    ("ig_linear_wgrad", "null", {"dy_hi": None}, -1, 'ig_linear_wgrad: null pointer', None),
+    ("ig_linear_wgrad", "N-not-8", {"N": 12}, -1, 'ig_linear_wgrad: N and K must be multiples of 8', None),
+    ("ig_linear_wgrad", "K-not-8", {"K": 12}, -1, 'ig_linear_wgrad: N and K must be multiples of 8', None),
+    ("ig_linear_wgrad", "split", {"dy_lo": _PTR}, -1, 'split (lo) pointers must be given for all bf16 operands or none', None),
+    ("ig_linear_fwd", "unaligned", {"x_hi": _PTR8}, -1, 'ig_linear_fwd: pointers must be 16-byte aligned', None),
+    ("ig_linear_fwd", "split-in-plain-out", {"x_lo": _PTR, "w_lo": _PTR}, -1, 'ig_linear_fwd: input and output must both be split or both plain', None),
+    ("ig_linear_dgrad_wt", "unaligned", {"wt_hi": _PTR8}, -1, 'ig_linear_dgrad_wt: pointers must be 16-byte aligned', None),
+    ("ig_linear_dgrad_wt", "split-in-plain-out", {"dy_lo": _PTR, "wt_lo": _PTR}, -1, 'ig_linear_dgrad_wt: input and output must both be split or both plain', None),
+    ("ig_linear_dgrad", "mode1-without-dact", {"mode": 1}, -1, 'ig_linear_dgrad: mode 1 needs the saved activation-derivative tensor (dact)', None),
+    ("ig_linear_dgrad", "mode2", {"mode": 2, "dact_hi": _PTR}, -1, 'ig_linear_dgrad: mode 1 needs the saved activation-derivative tensor (dact)', None),
+    ("ig_linear_dgrad_wt", "mode1-without-dact", {"mode": 1}, -1, 'ig_linear_dgrad_wt: mode 1 needs the saved activation-derivative tensor (dact)', None),
+    ("ig_linear_dgrad_wt", "mode2", {"mode": 2, "dact_hi": _PTR}, -1, 'ig_linear_dgrad_wt: mode 1 needs the saved activation-derivative tensor (dact)', None),
+    ("ig_linear_wgrad_group", "n0", {}, -1, 'ig_linear_wgrad_group: 1..16 GEMMs and non-null arrays', None),
+    ("ig_linear_wgrad_group", "n17", {"n": 17}, -1, 'ig_linear_wgrad_group: 1..16 GEMMs and non-null arrays', None),
+    ("ig_linear_wgrad_group", "null-array", {"n": 1, "dw": None}, -1, 'ig_linear_wgrad_group: 1..16 GEMMs and non-null arrays', None),
+    ("ig_patch_embed_fwd", "null", {"pos": None}, -1, 'ig_patch_embed_fwd: null pointer', None),
+    ("ig_patch_embed_fwd", "null-bias", {}, -1, 'ig_patch_embed_fwd: null pointer', None),
+    ("ig_patch_embed_fwd", "D-not-8", {"bias": _PTR, "D": 12}, -1, 'ig_patch_embed_fwd: D and K must be multiples of 8', None),
+    ("ig_patch_embed_fwd", "K-not-8", {"bias": _PTR, "K": 12}, -1, 'ig_patch_embed_fwd: D and K must be multiples of 8', None),
+    ("ig_patch_embed_fwd", "split", {"bias": _PTR, "w_lo": _PTR}, -1, 'split (lo) pointers must be given for all bf16 operands or none', None),
+    ("ig_conv3x3_fwd", "null", {"x_hi": None}, -1, 'ig_conv3x3_fwd: null pointer', None),
+    ("ig_conv3x3_fwd", "Cin-not-8", {"Cin": 12}, -1, 'ig_conv3x3_fwd: channels must be multiples of 8', None),
+    ("ig_conv3x3_fwd", "Cout-not-8", {"Cout": 20}, -1, 'ig_conv3x3_fwd: channels must be multiples of 8', None),
+    ("ig_conv3x3_fwd", "split", {"x_lo": _PTR}, -1, 'split (lo) pointers must be given for all bf16 operands or none', None),
+    ("ig_conv3x3_dgrad", "null", {"dy_hi": None}, -1, 'ig_conv3x3_dgrad: null pointer', None),
+    ("ig_conv3x3_dgrad", "Cin-not-8", {"Cin": 12}, -1, 'ig_conv3x3_dgrad: channels must be multiples of 8', None),
+    ("ig_conv3x3_dgrad", "Cout-not-8", {"Cout": 20}, -1, 'ig_conv3x3_dgrad: channels must be multiples of 8', None),
+    ("ig_conv3x3_dgrad", "split", {"dy_lo": _PTR}, -1, 'split (lo) pointers must be given for all bf16 operands or none', None),
+    ("ig_conv3x3_wgrad", "null", {"dw": None}, -1, 'ig_conv3x3_wgrad: null pointer', None),
+    ("ig_conv3x3_wgrad", "Cin-not-8", {"Cin": 12}, -1, 'ig_conv3x3_wgrad: channels must be multiples of 8', None),
+    ("ig_conv3x3_wgrad", "Cout-not-8", {"Cout": 20}, -1, 'ig_conv3x3_wgrad: channels must be multiples of 8', None),
+    ("ig_conv3x3_wgrad", "split", {"x_lo": _PTR}, -1, 'split (lo) pointers must be given for all bf16 operands or none', None),
+    ("ig_convk_fwd", "null", {"y_hi": None}, -1, 'ig_convk_fwd: null pointer', None),
+    ("ig_convk_fwd", "Cin-not-8", {"Cin": 12}, -1, 'ig_convk_fwd: channels must be multiples of 8', None),
+    ("ig_convk_fwd", "Cout-not-8", {"Cout": 20}, -1, 'ig_convk_fwd: channels must be multiples of 8', None),
+    ("ig_convk_fwd", "split", {"w_lo": _PTR}, -1, 'split (lo) pointers must be given for all bf16 operands or none', None),
+    ("ig_convk_fwd", "KS-even", {"KS": 4}, -1, 'ig_convk_fwd: kernel size 4 does not fit a 8 x 8 input', None),
+    ("ig_convk_fwd", "KS-1", {"KS": 1}, -1, 'ig_convk_fwd: kernel size 1 does not fit a 8 x 8 input', None),
+    ("ig_convk_fwd", "KS-11", {"KS": 11}, -1, 'ig_convk_fwd: kernel size 11 does not fit a 8 x 8 input', None),
+    ("ig_convk_fwd", "KS-does-not-fit", {"KS": 7, "H": 4}, -1, 'ig_convk_fwd: kernel size 7 does not fit a 4 x 8 input', None),
+    ("ig_convk_fwd", "KS-does-not-fit-W", {"KS": 9, "W": 6}, -1, 'ig_convk_fwd: kernel size 9 does not fit a 8 x 6 input', None),
+    ("ig_convk_fwd", "KS-before-split", {"KS": 4, "w_lo": _PTR}, -1, 'ig_convk_fwd: kernel size 4 does not fit a 8 x 8 input', None),
+    ("ig_convk_dgrad", "null", {"w_hi": None}, -1, 'ig_convk_dgrad: null pointer', None),
+    ("ig_convk_dgrad", "Cin-not-8", {"Cin": 12}, -1, 'ig_convk_dgrad: channels must be multiples of 8', None),
+    ("ig_convk_dgrad", "Cout-not-8", {"Cout": 20}, -1, 'ig_convk_dgrad: channels must be multiples of 8', None),
+    ("ig_convk_dgrad", "split", {"dy_lo": _PTR}, -1, 'split (lo) pointers must be given for all bf16 operands or none', None),
+    ("ig_convk_dgrad", "KS-even", {"KS": 4}, -1, 'ig_convk_dgrad: kernel size 4 does not fit a 8 x 8 input', None),
+    ("ig_convk_dgrad", "KS-1", {"KS": 1}, -1, 'ig_convk_dgrad: kernel size 1 does not fit a 8 x 8 input', None),
+    ("ig_convk_dgrad", "KS-11", {"KS": 11}, -1, 'ig_convk_dgrad: kernel size 11 does not fit a 8 x 8 input', None),
+    ("ig_convk_dgrad", "KS-does-not-fit", {"KS": 7, "H": 4}, -1, 'ig_convk_dgrad: kernel size 7 does not fit a 4 x 8 input', None),
+    ("ig_convk_dgrad", "KS-does-not-fit-W", {"KS": 9, "W": 6}, -1, 'ig_convk_dgrad: kernel size 9 does not fit a 8 x 6 input', None),
+    ("ig_convk_dgrad", "KS-before-split", {"KS": 4, "dy_lo": _PTR}, -1, 'ig_convk_dgrad: kernel size 4 does not fit a 8 x 8 input', None),
+    ("ig_convk_wgrad", "null", {"x_hi": None}, -1, 'ig_convk_wgrad: null pointer', None),
+    ("ig_convk_wgrad", "Cin-not-8", {"Cin": 12}, -1, 'ig_convk_wgrad: channels must be multiples of 8', None),
+    ("ig_convk_wgrad", "Cout-not-8", {"Cout": 20}, -1, 'ig_convk_wgrad: channels must be multiples of 8', None),
+    ("ig_convk_wgrad", "split", {"dy_lo": _PTR}, -1, 'split (lo) pointers must be given for all bf16 operands or none', None),
+    ("ig_convk_wgrad", "KS-even", {"KS": 4}, -1, 'ig_convk_wgrad: kernel size 4 does not fit a 8 x 8 input', None),
+    ("ig_convk_wgrad", "KS-1", {"KS": 1}, -1, 'ig_convk_wgrad: kernel size 1 does not fit a 8 x 8 input', None),
+    ("ig_convk_wgrad", "KS-11", {"KS": 11}, -1, 'ig_convk_wgrad: kernel size 11 does not fit a 8 x 8 input', None),
+    ("ig_convk_wgrad", "KS-does-not-fit", {"KS": 7, "H": 4}, -1, 'ig_convk_wgrad: kernel size 7 does not fit a 4 x 8 input', None),
+    ("ig_convk_wgrad", "KS-does-not-fit-W", {"KS": 9, "W": 6}, -1, 'ig_convk_wgrad: kernel size 9 does not fit a 8 x 6 input', None),
+    ("ig_convk_wgrad", "KS-before-split", {"KS": 4, "dy_lo": _PTR}, -1, 'ig_convk_wgrad: kernel size 4 does not fit a 8 x 8 input', None),
+    ("ig_convT_fwd", "null", {"w_hi": None}, -1, 'ig_convT_fwd: null pointer', None),
+    ("ig_convT_fwd", "Cin-not-8", {"Cin": 12}, -1, 'ig_convT_fwd: channels must be multiples of 8', None),
+    ("ig_convT_fwd", "Cout-not-8", {"Cout": 20}, -1, 'ig_convT_fwd: channels must be multiples of 8', None),
+    ("ig_convT_fwd", "split", {"x_lo": _PTR}, -1, 'split (lo) pointers must be given for all bf16 operands or none', None),
+    ("ig_convT_dgrad", "null", {"dx_hi": None}, -1, 'ig_convT_dgrad: null pointer', None),
+    ("ig_convT_dgrad", "Cin-not-8", {"Cin": 12}, -1, 'ig_convT_dgrad: channels must be multiples of 8', None),
+    ("ig_convT_dgrad", "Cout-not-8", {"Cout": 20}, -1, 'ig_convT_dgrad: channels must be multiples of 8', None),
+    ("ig_convT_dgrad", "split", {"w_lo": _PTR}, -1, 'split (lo) pointers must be given for all bf16 operands or none', None),
+    ("ig_convT_wgrad", "null", {"dy_hi": None}, -1, 'ig_convT_wgrad: null pointer', None),
+    ("ig_convT_wgrad", "Cin-not-8", {"Cin": 12}, -1, 'ig_convT_wgrad: channels must be multiples of 8', None),
+    ("ig_convT_wgrad", "Cout-not-8", {"Cout": 20}, -1, 'ig_convT_wgrad: channels must be multiples of 8', None),
+    ("ig_convT_wgrad", "split", {"x_lo": _PTR}, -1, 'split (lo) pointers must be given for all bf16 operands or none', None),
+    ("ig_conv3x3_fwd", "bn_scale-alone", {"bn_scale": _PTR}, -1, 'ig_conv3x3_fwd: bn_scale and bn_shift go together', None),
+    ("ig_conv3x3_fwd", "bn_shift-alone", {"bn_shift": _PTR}, -1, 'ig_conv3x3_fwd: bn_scale and bn_shift go together', None),
+    ("ig_convk_fwd", "bn_scale-alone", {"bn_scale": _PTR}, -1, 'ig_convk_fwd: bn_scale and bn_shift go together', None),
+    ("ig_convk_fwd", "bn_shift-alone", {"bn_shift": _PTR}, -1, 'ig_convk_fwd: bn_scale and bn_shift go together', None),
+    ("ig_convk_fwd", "split-in-plain-out", {"x_lo": _PTR, "w_lo": _PTR}, -1, 'ig_convk_fwd: input and output must both be split or both plain', None),
+    ("ig_convk_fwd", "split-before-bn", {"x_lo": _PTR, "w_lo": _PTR, "bn_scale": _PTR}, -1, 'ig_convk_fwd: input and output must both be split or both plain', None),
+    ("ig_conv3x3_dgrad", "dropout-2^32", {"Cin": 8, "drop_p": 0.5, "B": 65536, "H": 256, "W": 256}, -1, 'ig_conv3x3_dgrad: dropout needs < 2^32 elements', None),
+    ("ig_convk_dgrad", "dropout-2^32", {"Cin": 8, "drop_p": 0.5, "B": 65536, "H": 256, "W": 256}, -1, 'ig_convk_dgrad: dropout needs < 2^32 elements', None),
+    ("ig_convT_fwd", "dropout-2^32", {"Cout": 8, "drop_p": 0.5, "B": 16384, "H": 256, "W": 256}, -1, 'ig_convT_fwd: dropout needs < 2^32 elements', None),
+    ("ig_conv3x3_dgrad", "split-before-dropout", {"dy_lo": _PTR, "Cin": 8, "drop_p": 0.5, "B": 65536, "H": 256, "W": 256}, -1, 'split (lo) pointers must be given for all bf16 operands or none', None),
+    ("ig_conv3x3_fwd_stats", "null", {"fused": 1, "sums": None}, -1, 'ig_conv3x3_fwd_stats: null pointer', 7),
+    ("ig_conv3x3_fwd_stats", "null-fused", {"fused": None}, -1, 'ig_conv3x3_fwd_stats: null pointer', None),
+    ("ig_conv3x3_fwd_stats", "Cin-not-8", {"fused": 1, "Cin": 12}, -1, 'ig_conv3x3_fwd: channels must be multiples of 8', 0),
+    ("ig_conv3x3_fwd_stats", "Cout-not-8", {"fused": 1, "Cout": 20}, -1, 'ig_conv3x3_fwd: channels must be multiples of 8', 0),
+    ("ig_conv3x3_fwd_stats", "split-x", {"fused": 1, "x_lo": _PTR}, -1, 'split (lo) pointers must be given for all bf16 operands or none', 0),
+    ("ig_conv3x3_fwd_stats", "split-w", {"fused": 1, "w_lo": _PTR, "y_lo": _PTR}, -1, 'split (lo) pointers must be given for all bf16 operands or none', 0),
+    ("ig_conv3x3_cls_fwd", "null", {"fused": 1, "logits": None}, -1, 'ig_conv3x3_cls_fwd: null pointer', 7),
+    ("ig_conv3x3_cls_fwd", "bn_scale-alone", {"fused": 1, "bn_scale": _PTR}, -1, 'ig_conv3x3_cls_fwd: bn_scale and bn_shift go together', 7),
+    ("ig_conv3x3_cls_fwd", "split-declines", {"fused": 1, "x_lo": _PTR}, 0, '', 0),
+    ("ig_conv3x3_cls_fwd", "Cin-not-Cout-declines", {"fused": 1, "Cout": 32}, 0, '', 0),
+]
+
+
+@pytest.mark.parametrize("entry,case,over,rc,text,fused", _BAD_CALLS, ids=[f"{c[0]}-{c[1]}" for c in _BAD_CALLS])
+def test_bad_arguments_keep_their_return_code_and_text(built_lib, entry, case, over, rc, text, fused):
+    lib = built_lib.load()
+    flag = ctypes.c_int(7)
+    if over.get("fused") == 1:
+        over = dict(over, fused=ctypes.cast(ctypes.byref(flag), ctypes.c_void_p))
+    assert getattr(lib, entry)(*_entry_args(entry, **over)) == rc
+    if rc != 0:
+        assert built_lib.last_error() == text
+    assert fused is None or flag.value == fused
+
+
+def test_bad_argument_table_covers_every_gemm_and_conv_entry_point(built_lib):
+    want = {n for n in built_lib.declared_symbols() if re.match(r"ig_(linear_|patch_embed_fwd|conv3x3_|convk_|convT_)", n)}
+    assert want == {c[0] for c in _BAD_CALLS}

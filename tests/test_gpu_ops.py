@@ -737,6 +737,101 @@ def test_convT(split, B, H, Cin, Cout):  # 96 -> 48 unsplit runs the direct sub-
     close(db - 0.25, dyr.sum((0, 1, 2)), 3e-5, what="convT bias gradient")
 
 
+# Shapes that between them reach every engine behind the convolution entry points (B = 2, W = H + 2; the forced wide shapes are the
+# smallest of test_conv8_engine_* / test_wgrad8_conv_engine): name -> (family, H, Cin, Cout, ks, engine switches)
+_ROUTE_SHAPES = {
+    "conv3x3-16-24": ("conv3x3", 8, 16, 24, 3, {}),        # no engine covers it: gemm_kernel with Conv3Loader
+    "conv3x3-48": ("conv3x3", 8, 48, 48, 3, {}),           # direct / direct-split, direct weight gradient (three launches when split)
+    "conv3x3-96": ("conv3x3", 8, 96, 96, 3, {}),           # direct slices
+    "conv3x3-192-48": ("conv3x3", 8, 192, 48, 3, {}),      # direct weight gradient at 192 input channels
+    "conv3x3-192": ("conv3x3", 9, 192, 192, 3, {"IG_CONV8": "2", "IG_WGRAD8_CONV": "2"}),  # conv8, gemm8w
+    "convT-16-8": ("convT", 8, 16, 8, 3, {}),              # gemm_kernel with ConvTFwdALoader / ConvTGradLoader
+    "convT-96-48": ("convT", 8, 96, 48, 3, {}),            # direct sub-pixel kernels
+    "convT-384-192": ("convT", 9, 384, 192, 3, {"IG_CONV8": "2", "IG_WGRAD8_CONV": "2"}),  # conv8, gemm8w
+    "convk-16-8-k7": ("convk", 8, 16, 8, 7, {}),           # gemm_kernel with ConvKLoader
+    "convk-48-k5": ("convk", 8, 48, 48, 5, {}),            # the direct kernels' channel count, which must not reach them
+}
+# (shape, split) -> kernel named by ops.last_kernel() after each op [and the fused flag of conv3x3_fwd_stats], as the library answered
+# before its entry points were folded onto shared helpers (recorded on an MI355X)
+_ROUTES = {
+    ("conv3x3-16-24", False): {'fwd': 'gemm_kernel<Conv3Loader,PlainLoader,EpStore,false,false,1,4,3,4,32>', 'fwd_stats': ('gemm_kernel<Conv3Loader,PlainLoader,EpStore,false,false,1,4,3,4,32>', False), 'dgrad': 'gemm_kernel<Conv3Loader,ConvWgtTRLoader,EpGradStore,false,true,1,4,3,4,32>', 'wgrad': 'gemm_kernel<PlainLoader,Conv3Loader,EpAtomic,true,true,1,3,2,1,64>', 'wgrad_nobias': 'gemm_kernel<PlainLoader,Conv3Loader,EpAtomic,true,true,1,3,2,1,64>'},
+    ("conv3x3-16-24", True): {'fwd': 'gemm_kernel<Conv3Loader,PlainLoader,EpStore,false,false,3,4,3,4,32>', 'fwd_stats': ('gemm_kernel<Conv3Loader,PlainLoader,EpStore,false,false,3,4,3,4,32>', False), 'dgrad': 'gemm_kernel<Conv3Loader,ConvWgtTRLoader,EpGradStore,false,true,3,4,3,4,32>', 'wgrad': 'gemm_kernel<PlainLoader,Conv3Loader,EpAtomic,true,true,3,3,2,1,64>', 'wgrad_nobias': 'gemm_kernel<PlainLoader,Conv3Loader,EpAtomic,true,true,3,3,2,1,64>'},
+    ("conv3x3-48", False): {'fwd': 'conv3x3_direct_kernel<48,0>', 'fwd_stats': ('conv3x3_direct_kernel<48,0>', True), 'dgrad': 'conv3x3_direct_kernel<48,0>', 'wgrad': 'conv3x3_wgrad_dma_kernel<48,12>', 'wgrad_nobias': 'conv3x3_wgrad_dma_kernel<48,12>'},
+    ("conv3x3-48", True): {'fwd': 'conv3x3_direct_split_kernel<48>', 'fwd_stats': ('conv3x3_direct_split_kernel<48>', True), 'dgrad': 'conv3x3_direct_split_kernel<48>', 'wgrad': 'conv3x3_wgrad_dma_kernel<48,12>', 'wgrad_nobias': 'conv3x3_wgrad_dma_kernel<48,12>'},
+    ("conv3x3-96", False): {'fwd': 'conv3x3_direct_slice_kernel<96>', 'fwd_stats': ('conv3x3_direct_slice_kernel<96>', True), 'dgrad': 'conv3x3_direct_slice_kernel<96>', 'wgrad': 'conv3x3_wgrad_dma_kernel<96,8>', 'wgrad_nobias': 'conv3x3_wgrad_dma_kernel<96,8>'},
+    ("conv3x3-96", True): {'fwd': 'gemm_kernel<Conv3Loader,PlainLoader,EpStore,false,false,3,4,3,2,32>', 'fwd_stats': ('gemm_kernel<Conv3Loader,PlainLoader,EpStore,false,false,3,4,3,2,32>', False), 'dgrad': 'gemm_kernel<Conv3Loader,ConvWgtTRLoader,EpGradStore,false,true,3,4,3,2,32>', 'wgrad': 'conv3x3_wgrad_dma_kernel<96,8>', 'wgrad_nobias': 'conv3x3_wgrad_dma_kernel<96,8>'},
+    ("conv3x3-192-48", False): {'fwd': 'gemm_kernel<Conv3Loader,PlainLoader,EpStore,false,false,1,4,3,4,32>', 'fwd_stats': ('gemm_kernel<Conv3Loader,PlainLoader,EpStore,false,false,1,4,3,4,32>', False), 'dgrad': 'gemm_kernel<Conv3Loader,ConvWgtTRLoader,EpGradStore,false,true,1,4,3,2,32>', 'wgrad': 'conv3x3_wgrad_dma_kernel<192,4>', 'wgrad_nobias': 'conv3x3_wgrad_dma_kernel<192,4>'},
+    ("conv3x3-192-48", True): {'fwd': 'gemm_kernel<Conv3Loader,PlainLoader,EpStore,false,false,3,4,3,4,32>', 'fwd_stats': ('gemm_kernel<Conv3Loader,PlainLoader,EpStore,false,false,3,4,3,4,32>', False), 'dgrad': 'gemm_kernel<Conv3Loader,ConvWgtTRLoader,EpGradStore,false,true,3,4,3,2,32>', 'wgrad': 'conv3x3_wgrad_dma_kernel<192,4>', 'wgrad_nobias': 'conv3x3_wgrad_dma_kernel<192,4>'},
+    ("conv3x3-192", False): {'fwd': 'conv8_kernel<4,4,1,1,1,false>', 'fwd_stats': ('conv8_kernel<4,4,1,1,1,false>', False), 'dgrad': 'conv8_kernel<4,4,1,1,1,false>', 'wgrad': 'gemm8w_kernel<1,1,3,2>', 'wgrad_nobias': 'gemm8w_kernel<1,1,3,2>'},
+    ("conv3x3-192", True): {'fwd': 'conv8_kernel<4,4,1,1,2,true>', 'fwd_stats': ('conv8_kernel<4,4,1,1,2,true>', False), 'dgrad': 'conv8_kernel<4,4,1,1,2,true>', 'wgrad': 'gemm8w_kernel<2,1,3,2>', 'wgrad_nobias': 'gemm8w_kernel<2,1,3,2>'},
+    ("convT-16-8", False): {'fwd': 'gemm_kernel<ConvTFwdALoader,ConvTFwdBLoader,EpStore,false,false,1,4,3,4,32>', 'dgrad': 'gemm_kernel<ConvTGradLoader,ConvWgtTRLoader,EpGradStore,false,true,1,4,3,4,32>', 'wgrad': 'gemm_kernel<ConvTGradLoader,PlainLoader,EpAtomic,true,true,1,3,2,1,64>', 'wgrad_nobias': 'gemm_kernel<ConvTGradLoader,PlainLoader,EpAtomic,true,true,1,3,2,1,64>'},
+    ("convT-16-8", True): {'fwd': 'gemm_kernel<ConvTFwdALoader,ConvTFwdBLoader,EpStore,false,false,3,4,3,4,32>', 'dgrad': 'gemm_kernel<ConvTGradLoader,ConvWgtTRLoader,EpGradStore,false,true,3,4,3,4,32>', 'wgrad': 'gemm_kernel<ConvTGradLoader,PlainLoader,EpAtomic,true,true,3,3,2,1,64>', 'wgrad_nobias': 'gemm_kernel<ConvTGradLoader,PlainLoader,EpAtomic,true,true,3,3,2,1,64>'},
+    ("convT-96-48", False): {'fwd': 'convT_direct_dma_kernel<96,48>', 'dgrad': 'convT_dgrad_direct_kernel<96,48>', 'wgrad': 'convT_wgrad_dma_kernel<96,48>', 'wgrad_nobias': 'convT_wgrad_dma_kernel<96,48>'},
+    ("convT-96-48", True): {'fwd': 'gemm_kernel<ConvTFwdALoader,ConvTFwdBLoader,EpStore,false,false,3,4,3,4,32>', 'dgrad': 'gemm_kernel<ConvTGradLoader,ConvWgtTRLoader,EpGradStore,false,true,3,4,3,2,32>', 'wgrad': 'convT_wgrad_dma_kernel<96,48>', 'wgrad_nobias': 'convT_wgrad_dma_kernel<96,48>'},
+    ("convT-384-192", False): {'fwd': 'conv8_kernel<4,4,1,1,1,false>', 'dgrad': 'conv8_kernel<4,4,1,1,1,false>', 'wgrad': 'gemm8w_kernel<1,1,3,2>', 'wgrad_nobias': 'gemm8w_kernel<1,1,3,2>'},
+    ("convT-384-192", True): {'fwd': 'conv8_kernel<4,4,1,1,2,true>', 'dgrad': 'conv8_kernel<4,4,1,1,2,true>', 'wgrad': 'gemm8w_kernel<2,1,3,2>', 'wgrad_nobias': 'gemm8w_kernel<2,1,3,2>'},
+    ("convk-16-8-k7", False): {'fwd': 'gemm_kernel<ConvKLoader,PlainLoader,EpStore,false,false,1,4,3,4,32>', 'dgrad': 'gemm_kernel<ConvKLoader,ConvWgtTRLoader,EpGradStore,false,true,1,4,3,4,32>', 'wgrad': 'gemm_kernel<PlainLoader,ConvKLoader,EpAtomic,true,true,1,3,2,1,64>', 'wgrad_nobias': 'gemm_kernel<PlainLoader,ConvKLoader,EpAtomic,true,true,1,3,2,1,64>'},
+    ("convk-16-8-k7", True): {'fwd': 'gemm_kernel<ConvKLoader,PlainLoader,EpStore,false,false,3,4,3,4,32>', 'dgrad': 'gemm_kernel<ConvKLoader,ConvWgtTRLoader,EpGradStore,false,true,3,4,3,4,32>', 'wgrad': 'gemm_kernel<PlainLoader,ConvKLoader,EpAtomic,true,true,3,3,2,1,64>', 'wgrad_nobias': 'gemm_kernel<PlainLoader,ConvKLoader,EpAtomic,true,true,3,3,2,1,64>'},
+    ("convk-48-k5", False): {'fwd': 'gemm_kernel<ConvKLoader,PlainLoader,EpStore,false,false,1,4,3,4,32>', 'dgrad': 'gemm_kernel<ConvKLoader,ConvWgtTRLoader,EpGradStore,false,true,1,4,3,4,32>', 'wgrad': 'gemm_kernel<PlainLoader,ConvKLoader,EpAtomic,true,true,1,3,2,1,64>', 'wgrad_nobias': 'gemm_kernel<PlainLoader,ConvKLoader,EpAtomic,true,true,1,3,2,1,64>'},
+    ("convk-48-k5", True): {'fwd': 'gemm_kernel<ConvKLoader,PlainLoader,EpStore,false,false,3,4,3,4,32>', 'dgrad': 'gemm_kernel<ConvKLoader,ConvWgtTRLoader,EpGradStore,false,true,3,4,3,4,32>', 'wgrad': 'gemm_kernel<PlainLoader,ConvKLoader,EpAtomic,true,true,3,3,2,1,64>', 'wgrad_nobias': 'gemm_kernel<PlainLoader,ConvKLoader,EpAtomic,true,true,3,3,2,1,64>'},
+}
+
+
+def _conv_routes(name, split, monkeypatch):
+    """Run every op of one _ROUTE_SHAPES row; the weight and bias gradients are checked against float64 torch on the way (dbias starts
+    at 0.25: a dropped and a doubled bias sum both fail), once more without dbias.  Returns {op: kernel}."""
+    family, H, Cin, Cout, ks, env = _ROUTE_SHAPES[name]
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    B, W = 2, H + 2
+    x, xr = bt(nhwc(rnd(B, Cin, H, W, seed=70)), split)
+    xin = xr.permute(0, 3, 1, 2).clone()
+    if family == "convT":
+        wt = rnd(Cin, Cout, 3, 3, seed=71, scale=(2.25 * Cin) ** -0.5)
+        w, wr = bt(wt.permute(1, 2, 3, 0).reshape(Cout, 9, Cin).contiguous(), split)
+        wv = wr.reshape(Cout, 3, 3, Cin).permute(3, 0, 1, 2).clone().requires_grad_(True)
+        ref = F.conv_transpose2d(xin, wv, None, stride=2, padding=1, output_padding=1)
+        Ho, Wo = 2 * H, 2 * W
+    else:
+        wt = rnd(Cout, Cin, ks, ks, seed=71, scale=(ks * ks * Cin) ** -0.5)
+        w, wr = bt(wt.permute(0, 2, 3, 1).reshape(Cout, ks * ks, Cin).contiguous(), split)
+        wv = wr.reshape(Cout, ks, ks, Cin).permute(0, 3, 1, 2).clone().requires_grad_(True)
+        ref = F.conv2d(xin, wv, None, padding=1)
+        Ho, Wo = H + 3 - ks, W + 3 - ks
+    dy, dyr = bt(nhwc(rnd(B, Cout, Ho, Wo, seed=72)), split)
+    (gw,) = torch.autograd.grad((ref * dyr.permute(0, 3, 1, 2)).sum(), [wv])
+    gw = (gw.permute(1, 2, 3, 0) if family == "convT" else gw.permute(0, 2, 3, 1)).reshape(Cout, ks * ks, Cin)
+    bias = rnd(Cout, seed=73).to(DEV)
+    y, dx = BT.empty((B, Ho, Wo, Cout), split, DEV), BT.empty((B, H, W, Cin), split, DEV)
+    fwd, dgrad, wgrad = {"conv3x3": (ops.conv3x3_fwd, ops.conv3x3_dgrad, ops.conv3x3_wgrad), "convT": (ops.convT_fwd, ops.convT_dgrad, ops.convT_wgrad),
+                         "convk": (lambda *a: ops.conv_fwd(*a, ks), lambda *a: ops.conv_dgrad(*a, ks), lambda *a, **k: ops.conv_wgrad(*a, ks, **k))}[family]
+    got = {}
+    fwd(x, w, bias, y, B, H, W, Cin, Cout)
+    got["fwd"] = ops.last_kernel()
+    if family == "conv3x3":
+        sums = torch.zeros(2 * Cout, dtype=torch.float64, device=DEV)
+        fused = ops.conv3x3_fwd_stats(x, w, bias, y, sums, B, H, W, Cin, Cout)
+        got["fwd_stats"] = (ops.last_kernel(), fused)
+    dgrad(dy, w, dx, B, H, W, Cin, Cout)
+    got["dgrad"] = ops.last_kernel()
+    for key, db in (("wgrad", torch.full((Cout,), 0.25, device=DEV)), ("wgrad_nobias", None)):
+        dw = torch.zeros(Cout, ks * ks, Cin, device=DEV)
+        wgrad(dy, x, dw, B, H, W, Cin, Cout, dbias=db)
+        got[key] = ops.last_kernel()
+        close(dw, gw, 3e-5, what=f"{name} {key}")
+        if db is not None:
+            close(db - 0.25, dyr.sum((0, 1, 2)), 3e-5, what=f"{name} bias gradient")
+    return got
+
+
+@pytest.mark.parametrize("split", SPLITS)
+@pytest.mark.parametrize("name", list(_ROUTE_SHAPES))
+def test_conv_entry_points_keep_their_engines_and_bias_gradient(name, split, monkeypatch):
+    got = _conv_routes(name, split, monkeypatch)
+    print(got)
+    assert got == _ROUTES[(name, split)]
+
+
 def test_two_streams_do_not_share_scratch(monkeypatch):
     """The library's scratch buffers are keyed by (device, stream, slot) (runtime.hip): conv8 re-packs its weights into slot 1 on every call
     and the GEMM behind it reads them, and the BatchNorm statistics kernels keep their workgroup partials in slot 0.  Two streams of one
