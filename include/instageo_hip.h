@@ -412,6 +412,40 @@ int ig_ring_sums(const int* root, const int* ring_id, const int* tail, const uns
                  void* stream);
 int ig_ring_emit(const int* root, const int* ring_id, const int* rank, const int* tail, const unsigned char* flag, const long long* first,
                  int* vertices, long E, long n_rings, long n_vertices, int* status, void* stream);
+/* Zonal statistics: polygon zones rasterised onto a class map and tallied per zone and class (zonal.hip; not in the reference).  The
+ * inverse of the vectorisation above, in its coordinates: the raster is one (H, W) int8 class map, `fill` marks invalid pixels,
+ * H * W <= 2^31 - 1, pixel (r, c) covers [c, c+1] x [r, r+1] in lattice (x, y), y down.  Zone vertices arrive in fixed point with Q = 256
+ * units per pixel, X = floor(x * 256 + 0.5) and the same for Y, computed by the host in float64 as int32 with |X|, |Y| <= 2^29 (an edge
+ * with a coordinate beyond that crosses nothing); the centre of pixel (r, c) is (Xc, Yc) = (256 c + 128, 256 r + 128).  A zone is a set
+ * of closed rings (exteriors and holes of a Polygon or MultiPolygon; orientation is irrelevant) given as directed edges
+ * (x0, y0) -> (x1, y1).  An edge CROSSES row r iff (y0 <= Yc) != (y1 <= Yc) (half-open: a horizontal edge crosses nothing, a vertex on
+ * the centre line belongs to the edge that goes down from it); its crossing abscissa is the rational xc = x0 + (x1 - x0)(Yc - y0)/(y1 - y0).
+ * Pixel (r, c) is INSIDE the zone iff an odd number of the zone's edges cross row r with xc <= Xc: the even-odd rule on pixel centres
+ * (GDAL / rasterio without all_touched); ties at vertices and centres are decided by these two inequalities and nothing else.  Every
+ * quantity is an integer: differences stay below 2^31, sums of products below 2^62 (int64), no floating point.  Zones are independent:
+ * a pixel inside several zones counts in each.  Up to 64 zones go through one pass over a (H, W) uint64 canvas, one bit per zone; all
+ * results are unique: bit-identical from run to run.  Every launch does a fixed amount of work; no kernel waits on another workgroup.
+ * E = 0, T = 0 or H * W = 0 returns IG_OK without touching a pointer.
+ * ig_zone_edge_rows: edges (E, 4) int32 {x0, y0, x1, y1}, 16-byte aligned; rows[e] (E int32) = the number of rows in [0, H) that edge e
+ *   crosses under (y0 <= Yc) != (y1 <= Yc), Q = 256.  The exclusive scan of rows is the caller's: first (E int64) = the number of the
+ *   edge's first (edge, crossed row) pair, with total T <= 2^38.
+ * ig_zone_toggle: one work item per (edge, crossed row) pair 0..T-1; the edge is found by binary search in first, so the work is
+ *   balanced whatever the spread of edge lengths (an edge may span every row).  The item computes c* = max(0, ceil((xc - 128)/256)), the
+ *   first column with xc <= Xc (Q = 256: Xc = 256 c + 128), exactly: int64 floor division with the denominator made positive.  If c* < W it
+ *   flips bit bit[e] (E uint8, 0..63: the zone's bit in this pass) of canvas[r][c*] with a 64-bit atomic XOR, which is order-independent;
+ *   the caller zeroes the canvas.  The rows are those of ig_zone_edge_rows ((y0 <= Yc) != (y1 <= Yc)); items that first places outside
+ *   their edge's rows are dropped.
+ * ig_zone_tally: the inclusive prefix XOR along each row of canvas turns the toggles into inside masks (bit z of pixel (r, c) = an odd
+ *   number of zone z's crossings of row r, (y0 <= Yc) != (y1 <= Yc), have c* <= c, i.e. xc <= Xc at Q = 256), and in the same pass
+ *   counts (64, ncls + 1) uint64 += for every set bit z: counts[z][k] with k = cls[r][c] when that is a class in [0, ncls), else
+ *   k = ncls (fill, or a value outside [0, ncls)); 2 <= ncls <= 127.  counts is accumulated (the caller zeroes it): per workgroup in an LDS
+ *   table of 32-bit cells, then one 64-bit atomic add per non-empty cell.  write_mask != 0 leaves the inside masks in canvas, 0 leaves
+ *   the toggles.  cls = NULL (with write_mask != 0) computes the masks only: counts is not touched. */
+int ig_zone_edge_rows(const int* edges, int* rows, long E, int H, void* stream);
+int ig_zone_toggle(const int* edges, const unsigned char* bit, const long long* first, unsigned long long* canvas, long E, long T, int H,
+                   int W, void* stream);
+int ig_zone_tally(unsigned long long* canvas, const signed char* cls, unsigned long long* counts, int H, int W, int ncls, int fill,
+                  int write_mask, void* stream);
 int ig_confusion_update(const long long* y_true, const long long* y_pred, unsigned long long* confusion, long n, int k,
                         long ignore_index, int has_ignore, void* stream);
 /* torch.optim.AdamW step on a flat buffer (+ clip_weights, + bf16 shadow refresh)        base.py:103-126 */

@@ -70,6 +70,10 @@ DEFAULTS: Dict[str, Any] = {'root_dir': None,
           'min_region': 0, 'connectivity': 4, 'sieve_passes': 8, 'save_regions': False,
           # the regions of the written class map as polygons_*.geojson, traced on the device under `connectivity` (vectorize.py)
           'save_polygons': False,
+          # zonal statistics (not in the reference): a GeoJSON FeatureCollection of Polygon / MultiPolygon zones in the raster's coordinate
+          # system (None = off); zones_*.csv then counts the pixels of every class of the written class map inside every zone, rasterised
+          # and tallied on the device (zonal.py).  zone_id_property: the feature property to label the rows with (None = the feature index)
+          'zones': None, 'zone_id_property': None,
           # calibrated probabilities (not in the reference): logits / temperature in front of every softmax consumer (predict_step, the
           # blended tile canvas, the test epoch's ROC-AUC).  temperature: a float > 0, None = 1.0 (nothing is scaled); calibration: the
           # calibration.json of mode=calibrate to take it from (one of the two).  calibration_metrics: mode=eval also logs test_nll /

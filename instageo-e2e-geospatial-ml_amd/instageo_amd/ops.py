@@ -1005,6 +1005,54 @@ def ring_emit(root, ring_id, rank, tail, flag, first, n_vertices: int):
     return vertices
 
 
+ZONE_BITS = 64  # zones per pass: one bit of the uint64 canvas each
+
+
+def zone_edge_rows(edges, H: int):
+    """edges (E, 4) int32 {x0, y0, x1, y1} in Q = 256 fixed point -> (E,) int32: the rows in [0, H) whose centre line each edge crosses
+    (include/instageo_hip.h)."""
+    assert edges.dtype == torch.int32 and edges.dim() == 2 and edges.shape[1] == 4
+    E = edges.shape[0]
+    rows = torch.zeros(E, dtype=torch.int32, device=edges.device)
+    if E:
+        _call("ig_zone_edge_rows", float(E) * 20, _p(edges), _p(rows), E, int(H), _stream())
+    return rows
+
+
+def zone_toggle(edges, bit, first, canvas, n_crossings: int) -> None:
+    """Flip, for each of the ``n_crossings`` (edge, crossed row) pairs, bit ``bit[e]`` of ``canvas`` (H, W) int64 at the first column whose
+    centre lies at or right of the crossing; ``first`` (E,) int64 = the exclusive scan of :func:`zone_edge_rows`, ``bit`` (E,) uint8 in
+    0..63.  The caller zeroes the canvas."""
+    E = edges.shape[0]
+    assert edges.dtype == torch.int32 and edges.dim() == 2 and edges.shape[1] == 4 and bit.dtype == torch.uint8 and bit.numel() == E
+    assert first.dtype == torch.int64 and first.numel() == E and canvas.dtype == torch.int64 and canvas.dim() == 2
+    H, W = canvas.shape
+    T = int(n_crossings)
+    if E == 0 or T == 0 or H * W == 0:
+        return
+    # HBM bytes: per crossing one 8-byte atomic; the edge and the steps of the search are cache hits
+    _call("ig_zone_toggle", float(T) * 8, _p(edges), _p(bit), _p(first), _p(canvas), E, T, H, W, _stream())
+
+
+def zone_tally(canvas, classmap, counts, ncls: int = 2, fill: int = -1, write_mask: bool = False) -> None:
+    """Row-wise prefix XOR of the toggles in ``canvas`` (H, W) int64 = the inside masks of 64 zones, and ``counts`` (64, ncls + 1) int64 +=
+    the pixels of every class inside every zone (last column: ``fill`` and values outside [0, ncls)) of ``classmap`` (H, W) int8.
+    ``write_mask`` leaves the inside masks in ``canvas``; ``classmap`` None (then ``write_mask``) computes the masks only."""
+    assert canvas.dtype == torch.int64 and canvas.dim() == 2
+    if classmap is None:
+        assert write_mask, "without a class map there is nothing to do but the masks"
+        counts = None
+    else:
+        assert classmap.dtype == torch.int8 and classmap.shape == canvas.shape
+        assert counts.dtype == torch.int64 and tuple(counts.shape) == (ZONE_BITS, int(ncls) + 1)
+    H, W = canvas.shape
+    if H * W == 0:
+        return
+    # HBM bytes: the canvas read (and written back as masks) + the class map
+    _call("ig_zone_tally", float(H) * W * (8 + 8 * bool(write_mask) + (classmap is not None)), _p(canvas), _p(classmap), _p(counts), H, W,
+          int(ncls), int(fill), int(bool(write_mask)), _stream())
+
+
 def confusion_update(y_true, y_pred, confusion, k: int, ignore_index: Optional[int]) -> None:
     assert y_true.dtype == torch.int64 and y_pred.dtype == torch.int64 and confusion.dtype == torch.int64
     _lib.call("ig_confusion_update", _p(y_true), _p(y_pred), _p(confusion), y_true.numel(), k,

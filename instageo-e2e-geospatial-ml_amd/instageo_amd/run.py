@@ -6,7 +6,7 @@ Modes ``stats | train | eval | chip_inference`` and every config key are those o
 validation split -> ``calibration.json``; ``calibrate.*``, ``test.temperature`` / ``calibration`` / ``calibration_metrics``) and ``tile_inference``
 (whole GeoTIFF tiles -> maps, ``test.blend`` / ``cover_edges`` / ``sigma_scale`` / ``save_probabilities`` / ``tta`` /
 ``save_uncertainty``) is this project's, as are the region keys of both inference modes (``test.min_region`` / ``connectivity`` /
-``sieve_passes`` / ``save_regions`` / ``save_polygons``).  Hydra, Lightning and Neptune are replaced by :mod:`instageo_amd.config` and the explicit loop below, which logs the
+``sieve_passes`` / ``save_regions`` / ``save_polygons`` / ``zones``).  Hydra, Lightning and Neptune are replaced by :mod:`instageo_amd.config` and the explicit loop below, which logs the
 same metric names and writes ``instageo_best_checkpoint.ckpt`` (``{"state_dict": ...}``) on the best
 ``val_IoU`` (pipeline_utils.py:347-355).  Data: ``*_filepath`` may be ``synthetic:<n>`` (on-device HLS-shaped
 chips), an ``.npz`` with ``chips (N,T*C,H,W)`` and ``labels (N,H,W)``, or the reference's own CSV of chip / label GeoTIFF paths
@@ -283,7 +283,7 @@ def run_tile_inference(cfg: Dict[str, Any], model, tile: str, output_dir: str, d
                           cover_edges=bool(t.get("cover_edges", False)), sigma_scale=float(t.get("sigma_scale", 0.125)),
                           save_probabilities=bool(t.get("save_probabilities", False)), tta=str(t.get("tta", "none")),
                           save_uncertainty=bool(t.get("save_uncertainty", False)), temperature=float(getattr(model, "temperature", 1.0)),
-                          **region_options(cfg), **polygon_options(cfg))
+                          **region_options(cfg), **polygon_options(cfg), **zone_options(cfg))
 
 
 def region_options(cfg: Dict[str, Any]) -> Dict[str, Any]:
@@ -296,6 +296,17 @@ def region_options(cfg: Dict[str, Any]) -> Dict[str, Any]:
 def polygon_options(cfg: Dict[str, Any]) -> Dict[str, Any]:
     """The ``test.save_polygons`` key (``polygons_*.geojson``, vectorize.py) as a keyword argument of chip / tile inference."""
     return dict(save_polygons=bool(cfg["test"].get("save_polygons", False)))
+
+
+def zone_options(cfg: Dict[str, Any]) -> Dict[str, Any]:
+    """The ``test.zones`` / ``test.zone_id_property`` keys (``zones_*.csv``, zonal.py) as keyword arguments of chip / tile inference; a
+    relative ``zones`` path is taken from ``root_dir`` like the tiles."""
+    t, root = cfg["test"], cfg.get("root_dir")
+    none = lambda v: None if v in (None, "None") else str(v)  # noqa: E731  (the string "None" counts as unset, as for the required flags)
+    zones = none(t.get("zones"))
+    if zones is not None and not os.path.isabs(zones) and root not in (None, "None"):
+        zones = os.path.join(root, zones)
+    return dict(zones=zones, zone_id_property=none(t.get("zone_id_property")))
 
 
 def main(argv: Optional[List[str]] = None) -> int:
@@ -359,7 +370,7 @@ def main(argv: Optional[List[str]] = None) -> int:
         lo, hi = D.shard_range(len(ds), rank, world)
         bs = cfg["train"]["batch_size"]
         loader = (infer_collate_fn([ds[j] for j in range(i, min(i + bs, hi))]) for i in range(lo, hi, bs))
-        info = chip_inference(loader, output_dir, model, device="gpu", **region_options(cfg), **polygon_options(cfg))
+        info = chip_inference(loader, output_dir, model, device="gpu", **region_options(cfg), **polygon_options(cfg), **zone_options(cfg))
         if rank == 0:
             print(f"Carbon tracking information: {info}")
     elif cfg["mode"] == "tile_inference":

@@ -1,0 +1,370 @@
+"""Zonal statistics, host side (no GPU): the GeoJSON reader, map -> pixel -> fixed-point coordinates, the 2^29 bound, the option checks,
+the config keys, the CSV writer, the reference (tests/zonal_reference.py) on counts worked out by hand and against rational arithmetic,
+the header's statement of the rule, the argument checks of the three HIP entry points and the generated custom ops."""
+import csv
+import ctypes
+import json
+import os
+import re
+
+import numpy as np
+import pytest
+
+import zonal_reference as ZR
+from instageo_amd import zonal
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "instageo-e2e-geospatial-ml_amd")
+NAMES = ("ig_zone_edge_rows", "ig_zone_toggle", "ig_zone_tally")
+GEO_TAGS = {33550: (12, (30.0, 20.0, 0.0)), 33922: (12, (0.0, 0.0, 0.0, 399960.0, 4500000.0, 0.0))}
+
+
+@pytest.fixture(scope="module")
+def built_lib():
+    import subprocess
+
+    from instageo_amd import _lib
+
+    if not os.path.exists(_lib.LIB_PATH):
+        subprocess.run(["make", "-C", os.path.join(PKG, "csrc"), "-j4"], check=True)
+    return _lib
+
+
+def _feature(geometry, **props):
+    return {"type": "Feature", "properties": props, "geometry": geometry}
+
+
+def _write(path, features):
+    with open(path, "w") as f:
+        json.dump({"type": "FeatureCollection", "features": features}, f)
+    return str(path)
+
+
+# ---- reference ----------------------------------------------------------------------------------------------------------------------------
+def test_reference_gives_the_counts_worked_out_by_hand():
+    # the unit square holds the centre (128, 128) of pixel (0, 0) and no other
+    e, z = ZR.edges_of([[ZR.rect(0, 0, 1, 1)]])
+    assert e.tolist() == [[0, 0, 256, 0], [256, 0, 256, 256], [256, 256, 0, 256], [0, 256, 0, 0]] and z.tolist() == [0, 0, 0, 0]
+    m = ZR.ref_masks(e, z, 1, 3, 3)
+    assert m.sum() == 1 and m[0, 0, 0]
+    # a 4 x 4 square with a 2 x 2 hole: 16 - 4 pixels, whatever the orientation of either ring
+    outer, hole = ZR.rect(0, 0, 4, 4), ZR.rect(1, 1, 3, 3)
+    for rings in ([outer, hole], [outer[::-1], hole], [outer, hole[::-1]]):
+        e, z = ZR.edges_of([rings])
+        m = ZR.ref_masks(e, z, 1, 5, 6)
+        assert m.sum() == 12 and not m[0, 1:3, 1:3].any() and m[0, :4, :4].sum() == 12
+    cm = np.array([[0, 0, 1, 1, 0, 0], [0, 0, 1, 1, 0, 0], [1, 1, -1, 2, 0, 0], [1, 1, -1, 5, 0, 0], [0] * 6], dtype=np.int8)
+    # inside: rows 0 and 3 at columns 0-3, rows 1 and 2 at columns 0 and 3 (the fill of row 2 lies in the hole).  Class 0: 2 + 1;
+    # class 1: 2 + 1 + 1 + 2; the 2 of row 2; the fill and the 5 of row 3.  With two classes the 2 is no class either
+    assert ZR.ref_counts(cm, m, 2).tolist() == [[3, 6, 3]]
+    assert ZR.ref_counts(cm, m, 3).tolist() == [[3, 6, 1, 2]] and ZR.ref_counts(cm, m, 6).tolist() == [[3, 6, 1, 0, 0, 1, 1]]
+    # a square whose corners are the centres of pixels (0, 0) and (2, 2): its top and left edges count, its bottom and right do not
+    c = lambda i: 256 * i + 128  # noqa: E731
+    e, z = ZR.edges_of([[[(c(0), c(0)), (c(2), c(0)), (c(2), c(2)), (c(0), c(2))]]])
+    m = ZR.ref_masks(e, z, 1, 4, 4)
+    assert m.sum() == 4 and m[0, :2, :2].all()
+    assert ZR.to_planes(np.ones((65, 1, 1), dtype=bool)).tolist() == [[[-1]], [[1]]]  # bit 63 is the sign bit of the int64 plane
+
+
+def test_reference_equals_rational_arithmetic_pixel_by_pixel():
+    for name in ("one_pixel", "ties_8x8", "random_19x23"):
+        H, W, _ = ZR.cases()[name]
+        edges, edge_zone, Z, masks = ZR.reference(name)
+        for z in range(Z):
+            ze = edges[edge_zone == z]
+            got = np.array([[ZR.inside(ze, r, c) for c in range(W)] for r in range(H)])
+            assert np.array_equal(got, masks[z]), (name, z)
+    ties = ZR.reference("ties_8x8")[3]
+    assert ties[0].sum() == 12 and ties[0, 1:4, 1:5].all()  # corners on centres (1, 1) and (5, 4): rows 1-3, columns 1-4
+    assert ties[1].sum() == 15 and ties[4].sum() == 0 and ties[9].sum() == 1 and ties[9, 3, 3]
+    assert ties[3].sum() == 21 and ties[3, 2:5, 0:7].all()  # x from 40/256 to 7, y from centre line 2 up to (not including) centre line 5
+
+
+def test_the_cases_cover_what_they_claim():
+    H, W, zones = ZR.cases()["seventy_24x40"]
+    edges, edge_zone, Z, masks = ZR.reference("seventy_24x40")
+    px = masks.sum(axis=(1, 2))
+    assert Z == 70 and px[0] == px[1] == H * W and not px[2:6].any() and px[63] > 0 and px[64] == 12 * W
+    assert (masks.sum(axis=0) >= 4).any()  # overlapping zones
+    ys = edges[edge_zone == 8][:, [1, 3]]
+    assert ((ys.min(axis=1) < 0) & (ys.max(axis=1) > 256 * H)).any()  # an edge that spans every row
+    assert edges[:, [0, 2]].min() < -256 * 20 and edges[:, [0, 2]].max() > 256 * (W + 15)
+    wide = ZR.reference("wide_3x9000")[3]
+    assert wide[0].sum() == 3 * (9000 - 15) and wide[3].sum() == 3 * 9000 - 3 * 3100  # every row, minus the hole's columns 3000..6099
+    assert ZR.reference("one_pixel")[3].sum(axis=(1, 2)).tolist() == [1, 0, 1, 1]
+
+
+# ---- GeoJSON reader -----------------------------------------------------------------------------------------------------------------------
+def test_read_zones_takes_polygons_and_multipolygons_and_names_a_bad_feature(tmp_path):
+    outer = [[0, 0], [4, 0], [4, 4], [0, 4], [0, 0]]  # closed: the duplicate goes
+    hole = [[1, 1], [1, 3], [3, 3], [3, 1]]  # not closed: kept as it is
+    multi = [[[[10, 10], [12, 10], [12, 12], [10, 10]]], [[[20.5, 20.25, 7.0], [22, 20, 7.0], [22, 22, 7.0]], [[21, 21], [21.5, 21], [21.5, 21.5], [21, 21]]]]
+    path = _write(tmp_path / "z.geojson", [_feature({"type": "Polygon", "coordinates": [outer, hole]}, name="north", code=7),
+                                           _feature({"type": "MultiPolygon", "coordinates": multi}, name="south", code=9)])
+    zones = zonal.read_zones(path)
+    assert [z.id for z in zones] == [0, 1] and [len(z.rings) for z in zones] == [2, 3]
+    assert all(r.dtype == np.float64 and r.ndim == 2 and r.shape[1] == 2 for z in zones for r in z.rings)
+    assert zones[0].rings[0].tolist() == outer[:-1] and zones[0].rings[1].tolist() == hole
+    assert zones[1].rings[0].tolist() == [[10, 10], [12, 10], [12, 12]] and zones[1].rings[1].tolist() == [[20.5, 20.25], [22, 20], [22, 22]]
+    assert [z.id for z in zonal.read_zones(path, "name")] == ["north", "south"] and [z.id for z in zonal.read_zones(path, "code")] == [7, 9]
+    with pytest.raises(ValueError, match="feature 0 has no property 'nope'"):
+        zonal.read_zones(path, "nope")
+    bad = _write(tmp_path / "bad.geojson", [_feature({"type": "Polygon", "coordinates": [outer]}, name="ok"),
+                                            _feature({"type": "LineString", "coordinates": outer}, name="river")])
+    with pytest.raises(ValueError, match="feature 1 \\(id 'river'\\) has geometry 'LineString'"):
+        zonal.read_zones(bad, "name")
+    with pytest.raises(ValueError, match="feature 1 \\(id 1\\) has geometry 'LineString'"):
+        zonal.read_zones(bad)
+    with pytest.raises(ValueError, match="feature 0 .* has geometry None"):
+        zonal.read_zones(_write(tmp_path / "null.geojson", [_feature(None)]))
+    with pytest.raises(ValueError, match="malformed"):
+        zonal.read_zones(_write(tmp_path / "m.geojson", [_feature({"type": "Polygon", "coordinates": [[[1], [2], [3]]]})]))
+    with open(tmp_path / "geom.geojson", "w") as f:
+        json.dump({"type": "Polygon", "coordinates": [outer]}, f)
+    with pytest.raises(ValueError, match="FeatureCollection"):
+        zonal.read_zones(str(tmp_path / "geom.geojson"))
+    assert zonal.read_zones(_write(tmp_path / "none.geojson", [])) == []
+
+
+# ---- coordinates --------------------------------------------------------------------------------------------------------------------------
+def test_map_to_pixel_to_fixed_point():
+    from instageo_amd import tiff
+    from instageo_amd.postprocess import georeference
+
+    Zone = zonal.Zone
+    ring = np.array([[0.0, 0.0], [1.0, 0.0], [1.0, 1.0], [0.0, 1.0]])
+    # the golden chip carries neither a pixel scale nor a tiepoint: its coordinates are lattice coordinates already
+    gold = tiff.read_profile(os.path.join(ROOT, "tests", "golden", "tiff", "chip_178_022.tif"))
+    assert georeference(gold) is None
+    for prof in (gold, None):
+        edges, owner = zonal.zones_to_pixels([Zone("a", [ring]), Zone("b", []), Zone("c", [ring * 2.5, ring + 0.001])], prof)
+        assert edges.dtype == np.int32 and owner.dtype == np.int32 and owner.tolist() == [0] * 4 + [2] * 8
+        assert edges[:4].tolist() == [[0, 0, 256, 0], [256, 0, 256, 256], [256, 256, 0, 256], [0, 256, 0, 0]]  # a ring's last edge closes it
+        assert edges[4:8, :2].tolist() == [[0, 0], [640, 0], [640, 640], [0, 640]] and edges[8, :2].tolist() == [0, 0] and edges[9, 0] == 256
+    # floor(v * 256 + 0.5): halves go up, also below zero
+    q = zonal.quantise(np.array([[0.5 / 256, -0.5 / 256], [1.49 / 256, -1.51 / 256], [-3.0, 31.998046875]]))
+    assert q.tolist() == [[1, 0], [1, -2], [-768, 8192]] and q.dtype == np.int32
+    # 30 m x 20 m pixels, raster point (0, 0) at (399960, 4500000): X = (x - 399960) / 30, Y = (4500000 - y) / 20
+    geo = {"tags": GEO_TAGS}
+    m = np.array([[399960.0, 4500000.0], [400020.0, 4499980.0], [399975.0, 4499995.0], [399959.0, 4500001.0]])
+    edges, _ = zonal.zones_to_pixels([Zone(0, [m])], geo)
+    assert edges[:, :2].tolist() == [[0, 0], [512, 256], [128, 64], [-9, -13]]  # -8.53 -> -9 and -12.8 -> -13: floor(v + 0.5)
+    assert edges[:, 2:].tolist() == [[512, 256], [128, 64], [-9, -13], [0, 0]]
+    tags = dict(GEO_TAGS)
+    tags[33922] = (12, (2.0, 1.0, 0.0, 1000.0, 2000.0, 0.0))  # a tiepoint that is not at raster point (0, 0)
+    edges, _ = zonal.zones_to_pixels([Zone(0, [np.array([[1000.0, 2000.0], [1030.0, 1980.0], [1000.0, 1980.0]])])], {"tags": tags})
+    assert edges[:, :2].tolist() == [[512, 256], [768, 512], [512, 512]]
+    e0, o0 = zonal.zones_to_pixels([], geo)
+    assert e0.shape == (0, 4) and e0.dtype == np.int32 and o0.shape == (0,)
+    # what vectorize.write_geojson writes comes back to the lattice corner it came from, bit for bit
+    sx, sy, ti, tj, tx, ty = 0.1, 0.3, 0.5, 0.25, 1234.5678, 8765.4321
+    tags = {33550: (12, (sx, sy, 0.0)), 33922: (12, (ti, tj, 0.0, tx, ty, 0.0))}
+    X, Y = np.meshgrid(np.arange(0.0, 300.0, 7.0), np.arange(0.0, 300.0, 11.0))
+    back = [float(repr(float(v))) for v in tx + (X.ravel() - ti) * sx], [float(repr(float(v))) for v in ty - (Y.ravel() - tj) * sy]
+    edges, _ = zonal.zones_to_pixels([Zone(0, [np.stack(back, axis=1)])], {"tags": tags})
+    assert np.array_equal(edges[:, 0], 256 * X.ravel().astype(np.int32)) and np.array_equal(edges[:, 1], 256 * Y.ravel().astype(np.int32))
+
+
+def test_vertices_beyond_two_to_the_29_are_refused():
+    lim = 2**29 / 256  # 2097152 pixels
+    assert zonal.COORD_LIMIT == 2**29 and zonal.Q == 256
+    assert zonal.quantise(np.array([[lim, -lim]])).tolist() == [[2**29, -(2**29)]]
+    for bad in ([[lim + 1 / 256, 0.0]], [[0.0, -lim - 1 / 256]], [[float("nan"), 0.0]], [[0.0, float("inf")]], [[1e300, 0.0]]):
+        with pytest.raises(ValueError, match="2\\^29"):
+            zonal.quantise(np.array(bad))
+    ring = np.array([[0.0, 0.0], [10.0, 0.0], [10.0, 10.0]])
+    with pytest.raises(ValueError, match="zone 1 \\(id 'far'\\).*2\\^29"):  # degrees fed to a raster in metres, say
+        zonal.zones_to_pixels([zonal.Zone("near", [ring]), zonal.Zone("far", [ring, ring * 1e6])])
+    with pytest.raises(ValueError, match="2\\^29"):  # map coordinates on a profile without georeferencing
+        zonal.zones_to_pixels([zonal.Zone(0, [ring + 4500000.0])], None)
+    zonal.zones_to_pixels([zonal.Zone(0, [ring * 30.0 + [399960.0, 4499000.0]])], {"tags": GEO_TAGS})
+    # the device functions check what they are handed before anything is allocated
+    e = np.array([[0, 0, 2**29 + 1, 5]], dtype=np.int32)
+    with pytest.raises(ValueError, match="2\\^29"):
+        zonal.zone_masks(e, np.zeros(1, dtype=np.int32), 1, 4, 4, "cpu")
+    with pytest.raises(ValueError, match="outside \\[0, Z\\)"):
+        zonal.zone_masks(np.zeros((1, 4), dtype=np.int32), np.ones(1, dtype=np.int32), 1, 4, 4, "cpu")
+    with pytest.raises(ValueError, match="int32"):
+        zonal.zone_masks(np.zeros((1, 4), dtype=np.int64), np.zeros(1, dtype=np.int32), 1, 4, 4, "cpu")
+
+
+# ---- options, config ------------------------------------------------------------------------------------------------------------------------
+def test_zone_options_are_checked_before_any_work(tmp_path):
+    from instageo_amd.infer_utils import chip_inference, tile_inference
+
+    class _Reg:  # a regression head as far as the option check looks: one output channel
+        class cfg:
+            num_classes = 1
+
+    zones = _write(tmp_path / "z.geojson", [])
+    zonal.check_zone_options(None, False)
+    zonal.check_zone_options(None, True)  # off: nothing to object to
+    zonal.check_zone_options(zones, False)
+    with pytest.raises(ValueError, match="zones needs a class map \\(a regression head has one output channel\\)"):
+        zonal.check_zone_options(zones, True)
+    with pytest.raises(ValueError, match="is not a file"):
+        zonal.check_zone_options(str(tmp_path / "missing.geojson"), False)
+    with pytest.raises(ValueError, match="is not a file"):
+        zonal.check_zone_options(str(tmp_path), False)
+    args = ("/nonexistent/tile.tif", "/nonexistent/out")
+    for blend in ("nearest", "gaussian"):
+        with pytest.raises(ValueError, match="zones needs a class map"):
+            tile_inference(*args, _Reg(), [0.0], [1.0], blend=blend, zones=zones)
+        with pytest.raises(ValueError, match="is not a file"):
+            tile_inference(*args, None, [0.0], [1.0], blend=blend, zones=str(tmp_path / "missing.geojson"))
+    with pytest.raises(OSError):  # a valid option gets past the check and fails on the missing tile instead
+        tile_inference(*args, None, [0.0], [1.0], zones=zones)
+
+    def loader():
+        raise AssertionError("the loader must not be touched")
+        yield
+
+    with pytest.raises(ValueError, match="zones needs a class map"):
+        chip_inference(loader(), "/nonexistent/out", _Reg(), zones=zones)
+    with pytest.raises(ValueError, match="is not a file"):
+        chip_inference(loader(), "/nonexistent/out", None, zones="/nonexistent/z.geojson")
+    assert not os.path.exists("/nonexistent")
+
+
+def test_config_carries_the_zone_keys_and_they_default_to_off():
+    import inspect
+
+    from instageo_amd import run
+    from instageo_amd.config import DEFAULTS, load_config
+    from instageo_amd.infer_utils import chip_inference, tile_inference
+
+    assert DEFAULTS["test"]["zones"] is None and DEFAULTS["test"]["zone_id_property"] is None
+    assert run.zone_options(load_config("config", [])) == dict(zones=None, zone_id_property=None)
+    cfg = load_config("sen1floods11", ["mode=tile_inference", "test.zones=/data/admin2.geojson", "test.zone_id_property=ADM2_CODE"])
+    assert run.zone_options(cfg) == dict(zones="/data/admin2.geojson", zone_id_property="ADM2_CODE")
+    cfg = load_config("config", ["root_dir=/data/run", "test.zones=zones/parcels.geojson", "test.zone_id_property=None"])
+    assert run.zone_options(cfg) == dict(zones="/data/run/zones/parcels.geojson", zone_id_property=None)  # relative to root_dir, like the tiles
+    assert run.zone_options(load_config("config", ["test.zones=null"])) == dict(zones=None, zone_id_property=None)
+    assert "zones" not in run.region_options(cfg) and "zones" not in run.polygon_options(cfg)
+    for fn in (chip_inference, tile_inference):
+        p = inspect.signature(fn).parameters
+        assert p["zones"].default is None and p["zone_id_property"].default is None
+
+
+# ---- CSV writer -----------------------------------------------------------------------------------------------------------------------------
+def test_zone_csv_has_one_row_per_zone_and_map_areas_when_georeferenced(tmp_path):
+    counts = np.array([[3, 8, 1], [0, 0, 0], [2**40, 5, 7]], dtype=np.int64)
+    ids = ["north", 17, "a, \"quoted\" name"]
+    with open(zonal.write_zone_csv(str(tmp_path / "a.csv"), ids, counts, None), newline="") as f:
+        rows = list(csv.reader(f))
+    assert rows[0] == ["zone", "id", "pixels", "invalid", "count_0", "count_1"]
+    assert rows[1:] == [["0", "north", "12", "1", "3", "8"], ["1", "17", "0", "0", "0", "0"],
+                        ["2", "a, \"quoted\" name", str(2**40 + 12), "7", str(2**40), "5"]]
+    # 0.1 x 0.3 map units per pixel: products that are not exactly representable still read back to the bit
+    tags = {33550: (12, (0.1, 0.3, 0.0)), 33922: (12, (0.0, 0.0, 0.0, 1234.5678, 8765.4321, 0.0))}
+    with open(zonal.write_zone_csv(str(tmp_path / "b.csv"), ids, counts, {"tags": tags}), newline="") as f:
+        rows = list(csv.reader(f))
+    assert rows[0] == ["zone", "id", "pixels", "invalid", "count_0", "count_1", "area_map_0", "area_map_1"]
+    for row, c in zip(rows[1:], counts.tolist()):
+        assert row[:6] == [row[0], row[1], str(sum(c)), str(c[2]), str(c[0]), str(c[1])]
+        assert [float(v) for v in row[6:]] == [c[0] * 0.1 * 0.3, c[1] * 0.1 * 0.3] and row[6] == repr(float(c[0] * 0.1 * 0.3))
+    with open(zonal.write_zone_csv(str(tmp_path / "c.csv"), [], np.zeros((0, 4), dtype=np.int64), {"tags": GEO_TAGS}), newline="") as f:
+        assert list(csv.reader(f)) == [["zone", "id", "pixels", "invalid"] + [f"count_{k}" for k in range(3)] + [f"area_map_{k}" for k in range(3)]]
+    with pytest.raises(ValueError, match="ncls \\+ 1"):
+        zonal.write_zone_csv(str(tmp_path / "d.csv"), ["a"], counts, None)
+
+
+# ---- header, library, custom ops ------------------------------------------------------------------------------------------------------------
+def test_header_states_the_rule_for_every_entry_point():
+    """The contract: Q = 256 and the two inequalities that decide every tie stand in the description of each entry point."""
+    text = open(os.path.join(ROOT, "include", "instageo_hip.h")).read()
+    block = [c for c in re.findall(r"/\*.*?\*/", text, flags=re.S) if "ig_zone_edge_rows:" in c]
+    assert len(block) == 1
+    block = " ".join(block[0].replace("\n *", " ").split())
+    for phrase in ("X = floor(x * 256 + 0.5)", "|X|, |Y| <= 2^29", "(Xc, Yc) = (256 c + 128, 256 r + 128)", "even-odd", "atomic XOR",
+                   "xc = x0 + (x1 - x0)(Yc - y0)/(y1 - y0)", "max(0, ceil((xc - 128)/256))", "H * W <= 2^31 - 1", "2 <= ncls <= 127"):
+        assert phrase in block, phrase
+    parts = re.split(r"(?=\big_zone_\w+: )", block)
+    assert [p.split(":")[0] for p in parts[1:]] == list(NAMES)
+    for i, part in enumerate(parts):  # the preamble and each entry point's own paragraph; counting rows needs no abscissa
+        assert "Q = 256" in part and "(y0 <= Yc) != (y1 <= Yc)" in part and (i == 1 or "xc <= Xc" in part), part[:40]
+    for n in NAMES:
+        assert re.search(r"\bint %s\(" % n, text)
+    src = open(os.path.join(PKG, "csrc", "zonal.hip")).read()
+    assert "ZCHUNK = ZTPB * ZVPT" in src and "ZTPB = 256" in src and "ZVPT = 4" in src  # the 1024 columns the wide GPU case is built on
+    assert "zonal.hip" in open(os.path.join(PKG, "csrc", "Makefile")).read()
+
+
+def test_entry_points_exported_and_validated_without_gpu(built_lib):
+    """IG_REQUIRE rejects bad arguments before any launch, and empty calls return before a pointer is looked at (safe on a CPU-only box)."""
+    assert set(NAMES) <= set(built_lib.declared_symbols())
+    lib = built_lib.load()
+    err = built_lib.last_error
+    one, odd = ctypes.c_void_p(4096), ctypes.c_void_p(4100)
+
+    rows = lib.ig_zone_edge_rows
+    assert rows(None, one, 4, 8, None) == -1 and "null pointer" in err()
+    assert rows(one, None, 4, 8, None) == -1 and "null pointer" in err()
+    assert rows(odd, one, 4, 8, None) == -1 and "aligned" in err()
+    assert rows(one, one, -1, 8, None) == -1 and "E" in err()
+    assert rows(one, one, 2**31, 8, None) == -1 and "2^31 - 1" in err()
+    assert rows(one, one, 4, -1, None) == -1 and "H" in err()
+    assert rows(None, None, 0, 8, None) == 0  # E = 0
+
+    tog = lib.ig_zone_toggle
+    for k in range(4):
+        a = [one] * 4
+        a[k] = None
+        assert tog(*a, 4, 9, 8, 8, None) == -1 and "null pointer" in err()
+    assert tog(odd, one, one, one, 4, 9, 8, 8, None) == -1 and "aligned" in err()
+    assert tog(one, one, odd, one, 4, 9, 8, 8, None) == -1 and "aligned" in err()
+    assert tog(one, one, one, odd, 4, 9, 8, 8, None) == -1 and "aligned" in err()
+    assert tog(one, one, one, one, 4, -1, 8, 8, None) == -1 and "T" in err()
+    assert tog(one, one, one, one, 4, 2**38 + 1, 8, 8, None) == -1 and "2^38" in err()
+    assert tog(one, one, one, one, 2**31, 9, 8, 8, None) == -1 and "2^31 - 1" in err()
+    assert tog(one, one, one, one, 4, 9, 65536, 32768, None) == -1 and "2^31" in err()
+    assert tog(one, one, one, one, 4, 9, -1, 8, None) == -1 and "H" in err()
+    assert tog(None, None, None, None, 0, 9, 8, 8, None) == 0  # E = 0
+    assert tog(None, None, None, None, 4, 0, 8, 8, None) == 0  # T = 0
+    assert tog(None, None, None, None, 4, 9, 0, 8, None) == 0 and tog(None, None, None, None, 4, 9, 8, 0, None) == 0  # H * W = 0
+
+    tally = lib.ig_zone_tally
+    assert tally(None, one, one, 8, 8, 2, -1, 0, None) == -1 and "null pointer" in err()
+    assert tally(one, one, None, 8, 8, 2, -1, 0, None) == -1 and "null pointer" in err()
+    assert tally(one, None, None, 8, 8, 2, -1, 0, None) == -1 and "write_mask" in err()  # no class map and no masks: nothing to do
+    assert tally(odd, one, one, 8, 8, 2, -1, 0, None) == -1 and "aligned" in err()
+    assert tally(one, one, one, 8, 8, 1, -1, 0, None) == -1 and "ncls" in err()
+    assert tally(one, one, one, 8, 8, 128, -1, 0, None) == -1 and "ncls" in err()
+    assert tally(one, one, one, 8, 8, 2, 128, 0, None) == -1 and "fill" in err()
+    assert tally(one, one, one, 65536, 32768, 2, -1, 0, None) == -1 and "2^31" in err()
+    assert tally(one, one, one, 8, -1, 2, -1, 0, None) == -1 and "W" in err()
+    assert tally(None, None, None, 0, 8, 2, -1, 1, None) == 0 and tally(None, None, None, 8, 0, 2, -1, 1, None) == 0  # H * W = 0
+    with pytest.raises(built_lib.HipLibraryError, match="ncls"):
+        built_lib.call("ig_zone_tally", one, one, one, 8, 8, 0, -1, 0, None)
+
+
+def test_generated_custom_ops_follow_the_header():
+    from instageo_amd import torch_ops
+
+    raw = torch_ops.register()
+    assert {n[3:] for n in NAMES} <= set(raw)
+    assert "Tensor? edges" in raw["zone_edge_rows"] and "Tensor(a!)? rows" in raw["zone_edge_rows"] and "int H" in raw["zone_edge_rows"]
+    assert "Tensor? bit" in raw["zone_toggle"] and "Tensor? first" in raw["zone_toggle"] and "Tensor(a!)? canvas" in raw["zone_toggle"]
+    assert "Tensor(a!)? canvas" in raw["zone_tally"] and "Tensor? cls" in raw["zone_tally"] and "Tensor(b!)? counts" in raw["zone_tally"]
+    assert "int write_mask" in raw["zone_tally"]
+
+
+def test_empty_inputs_need_no_device():
+    """No edge, no zone or no pixel: the answer is known and nothing is launched (the arrays may even live on the CPU)."""
+    import torch
+
+    none = np.zeros((0, 4), dtype=np.int32), np.zeros(0, dtype=np.int32)
+    cm = torch.zeros((5, 7), dtype=torch.int8)
+    assert zonal.zone_counts(cm, *none, 0, 3).shape == (0, 4)
+    got = zonal.zone_counts(cm, *none, 70, 3)  # zones without a ring
+    assert got.shape == (70, 4) and got.dtype == np.int64 and not got.any()
+    planes = zonal.zone_masks(*none, 70, 5, 7, "cpu")
+    assert planes.shape == (2, 5, 7) and planes.dtype == torch.int64 and not planes.any()
+    assert zonal.zone_masks(*none, 0, 5, 7, "cpu").shape == (0, 5, 7)
+    e, z = ZR.edges_of([[ZR.rect(0, 0, 1, 1)]])
+    assert zonal.zone_masks(e, z, 1, 0, 7, "cpu").shape == (1, 0, 7)
+    assert zonal.zone_counts(torch.zeros((0, 7), dtype=torch.int8), e, z, 1, 2).tolist() == [[0, 0, 0]]
+    with pytest.raises(ValueError, match="ncls"):
+        zonal.zone_counts(cm, *none, 1, 1)
+    with pytest.raises(ValueError, match="int8"):
+        zonal.zone_counts(cm.to(torch.int32), *none, 1, 2)
