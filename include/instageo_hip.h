@@ -446,6 +446,39 @@ int ig_zone_toggle(const int* edges, const unsigned char* bit, const long long* 
                    int W, void* stream);
 int ig_zone_tally(unsigned long long* canvas, const signed char* cls, unsigned long long* counts, int H, int W, int ncls, int fill,
                   int write_mask, void* stream);
+/* Overview pyramids and tile layout for Cloud Optimized GeoTIFF output (cog.hip; the reference calls gdal_translate -of COG instead).
+ * Level 0 is the raster itself, H_0 x W_0; level k has H_k = ceil(H_{k-1} / 2) rows and W_k = ceil(W_{k-1} / 2) columns.  Pixel (r, c) of
+ * level k has as CHILDREN the pixels (2r..2r+1, 2c..2c+1) of level k-1 that lie inside that level: 1, 2 or 4 of them, in row-major order.
+ * Levels cascade: level k is computed from level k-1, never from level 0.  H * W <= 2^31 - 1, 1 <= levels <= 12.
+ * MODE rule (int8 class maps with a fill value): children equal to fill are ignored; if none is left the result is fill; otherwise the
+ *   result is the value with the most children, ties go to the smallest value (as signed int8).  The rule does not depend on child order,
+ *   so it commutes with the eight D4 maps of the square whenever H and W are multiples of 2^levels.  It makes no claim of equality with
+ *   GDAL's MODE resampling, which decides ties by position.
+ * MEAN rule (float32 rasters with NaN as NODATA, band by band): the valid children are those that are not NaN; the result is their float32
+ *   sum taken in row-major child order (the first valid child, then one IEEE addition per further one), divided by their count as float32
+ *   with IEEE round-to-nearest division; NaN (the quiet NaN 0x7fc00000) if there are none.  Bit-reproducible and equal to numpy float32
+ *   arithmetic in the same order.
+ * One workgroup owns a 64 x 64 block of the source with its origin at multiples of 64, so every 2 x 2 group of every level nests in one
+ * block: the block is read from memory once (16-byte loads where the row pitch and the pointer allow, single elements elsewhere) and
+ * levels 1..6 come out of LDS; for more than six levels the entry point launches again on level 6.  Every output element is written
+ * exactly once; no kernel waits on another workgroup; results are bit-identical from run to run.  H * W = 0 (or bands = 0) returns IG_OK
+ * without touching a pointer.
+ * ig_overview_mode: src (H, W) int8 -> dst int8: levels 1..levels by the MODE rule back to back in level order (sum of H_k * W_k bytes).
+ *   counts, when not NULL, is (ncls + 1) uint64 and accumulates (the caller zeroes it) the class histogram of src: counts[v] += 1 for a
+ *   pixel whose value v is a class in [0, ncls) and is not fill, counts[ncls] += 1 for fill or any value that is not a class;
+ *   1 <= ncls <= 127.  Integer sums: runs of equal classes are merged per thread and wave, counted per workgroup in LDS and added with one
+ *   64-bit atomic per non-empty cell and workgroup.
+ * ig_overview_mean: src (bands, H, W) float32 -> dst float32: levels 1..levels by the MEAN rule, level-major, each level (bands, H_k, W_k).
+ * ig_cog_tiles: src (bands, H, W) of elem_size = 1, 2 or 4 bytes -> dst (bands, ny, nx, tile, tile) with ny = ceil(H / tile),
+ *   nx = ceil(W / tile), tile a multiple of 16; dst 16-byte aligned.  The part of the edge tiles outside the raster holds the low elem_size
+ *   bytes of pad (the fill value, or the NaN bit pattern).  predictor 1 copies; predictor 2 (integers only: is_float must be 0) applies
+ *   TIFF horizontal differencing along each tile row of the padded tile, out[x] = v[x] - v[x-1] for x > 0, with wrap-around arithmetic in
+ *   the element's width.  A gather: every output element is written exactly once. */
+int ig_overview_mode(const signed char* src, int H, int W, int fill, int ncls, int levels, signed char* dst, unsigned long long* counts,
+                     void* stream);
+int ig_overview_mean(const float* src, int bands, int H, int W, int levels, float* dst, void* stream);
+int ig_cog_tiles(const void* src, int bands, int H, int W, int elem_size, int is_float, int tile, unsigned pad, int predictor, void* dst,
+                 void* stream);
 int ig_confusion_update(const long long* y_true, const long long* y_pred, unsigned long long* confusion, long n, int k,
                         long ignore_index, int has_ignore, void* stream);
 /* torch.optim.AdamW step on a flat buffer (+ clip_weights, + bf16 shadow refresh)        base.py:103-126 */

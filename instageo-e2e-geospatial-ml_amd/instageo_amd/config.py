@@ -74,6 +74,11 @@ DEFAULTS: Dict[str, Any] = {'root_dir': None,
           # system (None = off); zones_*.csv then counts the pixels of every class of the written class map inside every zone, rasterised
           # and tallied on the device (zonal.py).  zone_id_property: the feature property to label the rows with (None = the feature index)
           'zones': None, 'zone_id_property': None,
+          # Cloud Optimized GeoTIFF output of mode=tile_inference (cog.py): the class map, probability and uncertainty rasters become tiled
+          # GeoTIFFs with overviews built on the device (same file names; level 0 holds the same pixels) and cogstats_*.json holds the class
+          # histogram.  cog_blocksize: 128 | 256 | 512 (the reference's BLOCKSIZE=chip_size); overview_levels: 'auto' (until both sides
+          # fit a block) or 0..12 (the reference asks for 6); cog_compress: 'deflate' | 'none'
+          'cog': False, 'cog_blocksize': 256, 'overview_levels': 'auto', 'cog_compress': 'deflate',
           # calibrated probabilities (not in the reference): logits / temperature in front of every softmax consumer (predict_step, the
           # blended tile canvas, the test epoch's ROC-AUC).  temperature: a float > 0, None = 1.0 (nothing is scaled); calibration: the
           # calibration.json of mode=calibrate to take it from (one of the two).  calibration_metrics: mode=eval also logs test_nll /

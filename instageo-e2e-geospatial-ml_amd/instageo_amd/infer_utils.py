@@ -18,6 +18,7 @@ all eight transforms of the square (``ig_d4_apply`` before and after the forward
 """
 from __future__ import annotations
 
+import json
 import os
 from concurrent.futures import ThreadPoolExecutor
 from typing import Any, Dict, List, Optional, Sequence, Tuple
@@ -26,6 +27,7 @@ import numpy as np
 import torch
 
 from . import distributed as D
+from . import cog as cogmod
 from . import ops, postprocess, tiff, vectorize, zonal
 from .calibration import check_temperature
 from .dataloader import d4_codes, d4_inverse, gather_windows, origins_tensor, window_grid, window_origins
@@ -69,6 +71,25 @@ def save_zones_csv(classmap: torch.Tensor, zones, ncls: int, fill: int, file_nam
     ``zones_*.csv`` beside the prediction of ``file_name``."""
     ids, counts = zonal.zone_table(classmap, zones, ncls, fill, profile)
     return zonal.write_zone_csv(_output_path(file_name, output_folder, "zones", ".csv"), ids, counts, profile)
+
+
+def save_cog(raster: torch.Tensor, kind: str, file_name: str, output_folder: str, profile: Optional[Dict[str, Any]], cog_opts: Dict[str, Any],
+             name_kind: str = "prediction", fill: int = -1, ncls: Optional[int] = None) -> str:
+    """Write one raster still on the device as a Cloud Optimized GeoTIFF under :func:`save_prediction`'s name: the overviews by
+    ``kind`` ("mode" for the int8 class map, "mean" for float32 rasters) come from the device (:func:`cog.build_overviews`), level 0 holds
+    the pixels :func:`save_prediction` would write.  ``ncls``: also write ``cogstats_*.json``, the reference's segmentation statistics
+    (:func:`cog.seg_stats`) from the class histogram the pyramid kernel takes along; more classes than its 127 slots: the raster is
+    written without the statistics."""
+    path = _output_path(file_name, output_folder, name_kind)
+    if ncls is not None and ncls > cogmod.MAX_CLASSES:
+        ncls = None
+    counts = torch.zeros(ncls + 1, dtype=torch.int64, device=raster.device) if ncls is not None else None
+    levels = cogmod.build_overviews(raster, kind, cog_opts["overview_levels"], fill, cog_opts["cog_blocksize"], ncls, counts)
+    cogmod.write_cog(path, levels, profile, cog_opts["cog_blocksize"], cog_opts["cog_compress"])
+    if counts is not None:
+        with open(_output_path(file_name, output_folder, "cogstats", ".json"), "w") as f:
+            json.dump(cogmod.seg_stats(counts.cpu().numpy()), f, sort_keys=True)
+    return path
 
 
 def _num_classes(model) -> int:
@@ -319,7 +340,8 @@ def tile_inference(tile_path: str, output_folder: str, model, mean: Sequence[flo
                    cover_edges: bool = False, sigma_scale: float = 0.125, save_probabilities: bool = False, tta: str = "none",
                    save_uncertainty: bool = False, min_region: int = 0, connectivity: int = 4, sieve_passes: int = 8,
                    save_regions: bool = False, temperature: float = 1.0, zones: Optional[str] = None,
-                   zone_id_property: Optional[str] = None, save_polygons: bool = False) -> Optional[str]:
+                   zone_id_property: Optional[str] = None, cog: bool = False, cog_blocksize: int = 256, overview_levels="auto",
+                   cog_compress: Optional[str] = "deflate", save_polygons: bool = False) -> Optional[str]:
     """GeoTIFF tile -> ``prediction_*.tif`` class map of the same georeferencing: read the (T*C, H, W)
     tile, sliding-window inference over all ranks, stitch, blank NODATA pixels (any band == ``no_data_value``) and uncovered
     border pixels with ``fill``, write on rank 0.  Returns the output path on rank 0, None elsewhere.
@@ -341,6 +363,12 @@ def tile_inference(tile_path: str, output_folder: str, model, mean: Sequence[flo
     areas) of every class of the written map inside every zone, rasterised and tallied on the device (:mod:`instageo_amd.zonal`;
     rows labelled by the property ``zone_id_property``, else the feature index).  With the defaults nothing of this runs.
 
+    ``cog`` writes the class map (after the sieve), ``probability_*.tif`` and ``uncertainty_*.tif`` as Cloud Optimized GeoTIFFs under the
+    same names (:mod:`instageo_amd.cog`): tiles of ``cog_blocksize`` (128 | 256 | 512), ``overview_levels`` ("auto" | 0..12) overviews built
+    from the tensors still on the device (mode with ``fill`` for the class map, NaN-aware mean for the float rasters), ``cog_compress``
+    "deflate" | "none".  Level 0 of every file holds exactly the pixels the strip file holds without ``cog``.  ``cogstats_*.json`` holds the
+    class histogram of the written map in the reference's form (valid_pixels / class_counts / unique_values).
+
     ``temperature`` (blended paths; ``test.temperature`` / ``test.calibration``) calibrates the probabilities that are blended, and
     through them the class map, probability and uncertainty rasters.  The nearest-centre stitch is an argmax of raw logits, which no
     positive temperature changes: it ignores the value."""
@@ -348,6 +376,9 @@ def tile_inference(tile_path: str, output_folder: str, model, mean: Sequence[flo
     postprocess.check_region_options(min_region, connectivity, sieve_passes, save_regions, _is_regression(model))
     vectorize.check_polygon_options(save_polygons, _is_regression(model))
     zonal.check_zone_options(zones, _is_regression(model))
+    cogmod.check_cog_options(cog, cog_blocksize, overview_levels, cog_compress,
+                             ncls=getattr(getattr(getattr(model, "net", model), "cfg", None), "num_classes", None))
+    cog_opts = dict(cog_blocksize=cog_blocksize, overview_levels=overview_levels, cog_compress=cog_compress) if cog else None
     if blend not in ("nearest", "mean", "gaussian"):
         raise ValueError(f"blend must be 'nearest', 'mean' or 'gaussian' (got {blend!r})")
     if blend == "nearest" and (cover_edges or save_probabilities):
@@ -360,7 +391,7 @@ def tile_inference(tile_path: str, output_folder: str, model, mean: Sequence[flo
         return _blended_tile_file(arr, profile, tile_path, output_folder, model, mean, std, temporal_size, crop_size, stride, batch_size,
                                   constant_multiplier, no_data_value, fill, device, blend, cover_edges, sigma_scale, save_probabilities,
                                   tta, save_uncertainty, min_region, connectivity, sieve_passes, save_regions, temperature, save_polygons,
-                                  zones, zone_id_property)
+                                  zones, zone_id_property, cog_opts)
     if arr.shape[1] != arr.shape[2]:
         raise ValueError("tile_inference expects a square tile (the window rule of process_test uses one img_size)")
     t = torch.from_numpy(arr if arr.dtype in (np.int16, np.float32) else arr.astype(np.float32)).to(device)
@@ -376,6 +407,8 @@ def tile_inference(tile_path: str, output_folder: str, model, mean: Sequence[flo
     prof["tags"] = {k: v for k, v in profile["tags"].items() if k != 42113}
     canvas = _region_outputs(canvas, tile_path, output_folder, prof, fill, min_region, connectivity, sieve_passes, save_regions,
                              save_polygons, zones, zone_id_property, _num_classes(model) if zones is not None else 0)
+    if cog_opts is not None:
+        return save_cog(canvas, "mode", tile_path, output_folder, prof, cog_opts, fill=fill, ncls=_num_classes(model))
     return save_prediction(canvas.cpu().numpy(), tile_path, output_folder, prof)
 
 
@@ -399,7 +432,7 @@ def _region_outputs(classmap: torch.Tensor, tile_path: str, output_folder: str, 
 def _blended_tile_file(arr, profile, tile_path, output_folder, model, mean, std, temporal_size, crop_size, stride, batch_size,
                        constant_multiplier, no_data_value, fill, device, blend, cover_edges, sigma_scale, save_probabilities,
                        tta="none", save_uncertainty=False, min_region=0, connectivity=4, sieve_passes=8, save_regions=False,
-                       temperature=1.0, save_polygons=False, zones=None, zone_id_property=None) -> Optional[str]:
+                       temperature=1.0, save_polygons=False, zones=None, zone_id_property=None, cog_opts=None) -> Optional[str]:
     t = torch.from_numpy(arr if arr.dtype in (np.int16, np.float32) else arr.astype(np.float32)).to(device)
     res = blended_window_inference(t, model, mean, std, temporal_size, crop_size, stride, batch_size, constant_multiplier, blend,
                                    sigma_scale, cover_edges, no_data_value, fill, save_probabilities, tta, save_uncertainty, temperature)
@@ -410,10 +443,19 @@ def _blended_tile_file(arr, profile, tile_path, output_folder, model, mean, std,
     tags = {k: v for k, v in profile["tags"].items() if k != 42113}
     float_prof = dict(profile, count=1, dtype="float32", nodata=None, tags={**tags, 42113: (2, "nan")})
     if classmap is None:  # regression head: the blended value is the prediction
+        if cog_opts is not None:
+            return save_cog(prob[0], "mean", tile_path, output_folder, float_prof, cog_opts)
         return save_prediction(prob[0].cpu().numpy(), tile_path, output_folder, float_prof)
     int_prof = dict(profile, count=1, dtype="int8", nodata=fill, tags=tags)
     classmap = _region_outputs(classmap, tile_path, output_folder, int_prof, fill, min_region, connectivity, sieve_passes, save_regions,
                                save_polygons, zones, zone_id_property, _num_classes(model) if zones is not None else 0)
+    if cog_opts is not None:
+        out = save_cog(classmap, "mode", tile_path, output_folder, int_prof, cog_opts, fill=fill, ncls=_num_classes(model))
+        if save_probabilities:
+            save_cog(prob, "mean", tile_path, output_folder, dict(float_prof, count=prob.shape[0]), cog_opts, "probability")
+        if save_uncertainty:
+            save_cog(res[2], "mean", tile_path, output_folder, dict(float_prof, count=2), cog_opts, "uncertainty")
+        return out
     out = save_prediction(classmap.cpu().numpy(), tile_path, output_folder, int_prof)
     if save_probabilities:
         save_prediction(prob.cpu().numpy(), tile_path, output_folder, dict(float_prof, count=prob.shape[0]), kind="probability")

@@ -1053,6 +1053,69 @@ def zone_tally(canvas, classmap, counts, ncls: int = 2, fill: int = -1, write_ma
           int(ncls), int(fill), int(bool(write_mask)), _stream())
 
 
+def pyramid_shapes(H: int, W: int, levels: int):
+    """[(H_k, W_k) for k = 1..levels] with H_k = ceil(H_{k-1} / 2), W_k = ceil(W_{k-1} / 2) (include/instageo_hip.h)."""
+    out = []
+    for _ in range(int(levels)):
+        H, W = (H + 1) // 2, (W + 1) // 2
+        out.append((H, W))
+    return out
+
+
+def overview_mode(classmap, levels: int, fill: int = -1, ncls: int = 2, counts=None):
+    """Levels 1..``levels`` of the (H, W) int8 ``classmap`` by the MODE rule (include/instageo_hip.h) -> list of int8 tensors, views of one
+    buffer.  ``counts`` (ncls + 1,) int64, when given, += the class histogram of ``classmap`` (last slot: ``fill`` and values that are
+    no class)."""
+    assert classmap.dtype == torch.int8 and classmap.dim() == 2, "a class map is (H, W) int8"
+    H, W = classmap.shape
+    shapes = pyramid_shapes(H, W, levels)
+    if counts is not None:
+        assert counts.dtype == torch.int64 and tuple(counts.shape) == (int(ncls) + 1,)
+    dst = torch.empty(sum(h * w for h, w in shapes), dtype=torch.int8, device=classmap.device)
+    if H * W:
+        # HBM bytes: the map read once, the levels (a third of it) written
+        _call("ig_overview_mode", float(H) * W + dst.numel(), _p(classmap), H, W, int(fill), int(ncls), int(levels), _p(dst), _p(counts),
+              _stream())
+    out, o = [], 0
+    for h, w in shapes:
+        out.append(dst[o : o + h * w].view(h, w))
+        o += h * w
+    return out
+
+
+def overview_mean(raster, levels: int):
+    """Levels 1..``levels`` of the (bands, H, W) float32 ``raster`` by the MEAN rule (NaN = NODATA; include/instageo_hip.h) -> list of
+    (bands, H_k, W_k) float32 tensors, views of one buffer."""
+    assert raster.dtype == torch.float32 and raster.dim() == 3, "a raster is (bands, H, W) float32"
+    B, H, W = raster.shape
+    shapes = pyramid_shapes(H, W, levels)
+    dst = torch.empty(B * sum(h * w for h, w in shapes), dtype=torch.float32, device=raster.device)
+    if B * H * W:
+        _call("ig_overview_mean", 4.0 * (raster.numel() + dst.numel()), _p(raster), B, H, W, int(levels), _p(dst), _stream())
+    out, o = [], 0
+    for h, w in shapes:
+        out.append(dst[o : o + B * h * w].view(B, h, w))
+        o += B * h * w
+    return out
+
+
+def cog_tiles(raster, tile: int, pad: int = 0, predictor: int = 1):
+    """(bands, H, W) of 1-, 2- or 4-byte elements -> (bands, ny, nx, tile, tile) of the same dtype: the raster cut into tiles, the part of the
+    edge tiles outside it set to the bit pattern ``pad`` (low bytes), with TIFF horizontal differencing along each tile row when
+    ``predictor`` is 2 (integers only)."""
+    assert raster.dim() == 3 and raster.element_size() in (1, 2, 4), "a raster is (bands, H, W) of 1-, 2- or 4-byte elements"
+    B, H, W = raster.shape
+    tile = int(tile)
+    assert tile > 0 and tile % 16 == 0, "tile must be a multiple of 16"
+    ny, nx = -(-H // tile), -(-W // tile)
+    out = torch.empty((B, ny, nx, tile, tile), dtype=raster.dtype, device=raster.device)
+    es = raster.element_size()
+    if out.numel():
+        _call("ig_cog_tiles", float(es) * (raster.numel() + out.numel()), _p(raster), B, H, W, es, int(raster.dtype.is_floating_point), tile,
+              int(pad) & 0xFFFFFFFF, int(predictor), _p(out), _stream())
+    return out
+
+
 def confusion_update(y_true, y_pred, confusion, k: int, ignore_index: Optional[int]) -> None:
     assert y_true.dtype == torch.int64 and y_pred.dtype == torch.int64 and confusion.dtype == torch.int64
     _lib.call("ig_confusion_update", _p(y_true), _p(y_pred), _p(confusion), y_true.numel(), k,

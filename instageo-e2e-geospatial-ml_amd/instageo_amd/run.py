@@ -6,7 +6,8 @@ Modes ``stats | train | eval | chip_inference`` and every config key are those o
 validation split -> ``calibration.json``; ``calibrate.*``, ``test.temperature`` / ``calibration`` / ``calibration_metrics``) and ``tile_inference``
 (whole GeoTIFF tiles -> maps, ``test.blend`` / ``cover_edges`` / ``sigma_scale`` / ``save_probabilities`` / ``tta`` /
 ``save_uncertainty``) is this project's, as are the region keys of both inference modes (``test.min_region`` / ``connectivity`` /
-``sieve_passes`` / ``save_regions`` / ``save_polygons`` / ``zones``).  Hydra, Lightning and Neptune are replaced by :mod:`instageo_amd.config` and the explicit loop below, which logs the
+``sieve_passes`` / ``save_regions`` / ``save_polygons`` / ``zones``) and the COG keys of ``tile_inference`` (``test.cog`` / ``cog_blocksize`` /
+``overview_levels`` / ``cog_compress``).  Hydra, Lightning and Neptune are replaced by :mod:`instageo_amd.config` and the explicit loop below, which logs the
 same metric names and writes ``instageo_best_checkpoint.ckpt`` (``{"state_dict": ...}``) on the best
 ``val_IoU`` (pipeline_utils.py:347-355).  Data: ``*_filepath`` may be ``synthetic:<n>`` (on-device HLS-shaped
 chips), an ``.npz`` with ``chips (N,T*C,H,W)`` and ``labels (N,H,W)``, or the reference's own CSV of chip / label GeoTIFF paths
@@ -283,7 +284,7 @@ def run_tile_inference(cfg: Dict[str, Any], model, tile: str, output_dir: str, d
                           cover_edges=bool(t.get("cover_edges", False)), sigma_scale=float(t.get("sigma_scale", 0.125)),
                           save_probabilities=bool(t.get("save_probabilities", False)), tta=str(t.get("tta", "none")),
                           save_uncertainty=bool(t.get("save_uncertainty", False)), temperature=float(getattr(model, "temperature", 1.0)),
-                          **region_options(cfg), **polygon_options(cfg), **zone_options(cfg))
+                          **region_options(cfg), **polygon_options(cfg), **zone_options(cfg), **cog_options(cfg))
 
 
 def region_options(cfg: Dict[str, Any]) -> Dict[str, Any]:
@@ -309,6 +310,20 @@ def zone_options(cfg: Dict[str, Any]) -> Dict[str, Any]:
     return dict(zones=zones, zone_id_property=none(t.get("zone_id_property")))
 
 
+def cog_options(cfg: Dict[str, Any]) -> Dict[str, Any]:
+    """The ``test.cog`` / ``cog_blocksize`` / ``overview_levels`` / ``cog_compress`` keys (Cloud Optimized GeoTIFF output, cog.py) as
+    keyword arguments of tile inference, checked: a bad value raises ValueError, and so does ``cog`` with ``mode=chip_inference``."""
+    from .cog import check_cog_options
+
+    t = cfg["test"]
+    compress = t.get("cog_compress", "deflate")
+    compress = "none" if compress in (None, "None") else compress
+    opts = dict(cog=bool(t.get("cog", False)), cog_blocksize=t.get("cog_blocksize", 256), overview_levels=t.get("overview_levels", "auto"),
+                cog_compress=compress)
+    check_cog_options(opts["cog"], opts["cog_blocksize"], opts["overview_levels"], compress, chip_mode=cfg.get("mode") == "chip_inference")
+    return opts
+
+
 def main(argv: Optional[List[str]] = None) -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--config-name", default="config")
@@ -318,6 +333,7 @@ def main(argv: Optional[List[str]] = None) -> int:
     ap.add_argument("overrides", nargs="*")
     args = ap.parse_args(argv)
     cfg = load_config(args.config_name, args.overrides, args.config_path)
+    cog_options(cfg)  # a bad COG key, or test.cog with mode=chip_inference, stops here: before the model is built
     start = time.time()
     torch.manual_seed(SEED)
     np.random.seed(SEED)

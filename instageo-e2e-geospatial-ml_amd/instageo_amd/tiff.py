@@ -7,6 +7,9 @@ band-interleaved "separate" or pixel-interleaved "contig" planes, 8/16/32-bit in
 strip-organised files (uncompressed or deflate), carrying the source file's georeferencing tags over verbatim so a prediction
 raster opens in GIS tools at the chip's location -- the role of ``profile`` in the reference's ``save_prediction``.
 
+Files with several IFDs (the overviews of a Cloud Optimized GeoTIFF, :mod:`instageo_amd.cog`) are read level by level: ``level`` counts
+along the next-IFD chain, 0 = the first IFD.
+
 Not a general TIFF library: no BigTIFF, no JPEG codec, no sub-IFDs; LZW (GDAL's COMPRESS=LZW, common for HLS derivatives) is
 READ only, by a pure-Python decoder (a 256 x 256 x 18 int16 chip takes about a second).  Unsupported features raise ``TiffError``.
 """
@@ -113,10 +116,22 @@ def _lzw_decode(data: bytes) -> bytes:
     return bytes(out)
 
 
-class _Header:
-    """Parsed first IFD of a classic TIFF (no pixel data touched)."""
+def _ifd_chain(buf: bytes, bo: str, off: int, stop: Optional[int] = None) -> List[int]:
+    """Offsets of the IFDs along the next-IFD chain from ``off``: the first ``stop`` of them, or all (a chain that loops is corrupt)."""
+    offs: List[int] = []
+    while off and (stop is None or len(offs) < stop):
+        if off in offs or len(offs) >= 4096:
+            raise TiffError("corrupt TIFF: the IFD chain loops")
+        offs.append(off)
+        (n,) = struct.unpack_from(bo + "H", buf, off)
+        (off,) = struct.unpack_from(bo + "I", buf, off + 2 + 12 * n)
+    return offs
 
-    def __init__(self, path: str, buf: bytes):
+
+class _Header:
+    """Parsed IFD ``level`` (0 = the first) of a classic TIFF (no pixel data touched)."""
+
+    def __init__(self, path: str, buf: bytes, level: int = 0):
         self.path, self.buf = path, buf
         if buf[:2] == b"II":
             bo = "<"
@@ -130,6 +145,14 @@ class _Header:
         if magic != 42:
             raise TiffError(f"{path}: bad TIFF magic {magic}")
         (ifd,) = struct.unpack_from(bo + "I", buf, 4)
+        if level:
+            if level < 0:
+                raise TiffError(f"{path}: level must be >= 0 (got {level})")
+            chain = _ifd_chain(buf, bo, ifd, level + 1)
+            if len(chain) <= level:
+                raise TiffError(f"{path}: level {level} is beyond the file ({len(chain)} IFD{'s' if len(chain) != 1 else ''}: levels 0..{len(chain) - 1})")
+            ifd = chain[level]
+        self.first_ifd = ifd if not level else chain[0]
         t = self.t = _read_ifd(buf, bo, ifd)
         self.bo = bo
         self.W, self.H = self.one(_W), self.one(_H)
@@ -165,31 +188,33 @@ class _Header:
                 "nodata": nodata, "tags": {k: t[k] for k in GEO_TAGS if k in t}}  # fmt: skip
 
 
-def _header(path: str, whole: bool) -> _Header:
+def _header(path: str, whole: bool, level: int = 0) -> _Header:
+    level = int(level)
     with open(path, "rb") as f:
         if whole:
             try:
-                return _Header(path, f.read())
+                return _Header(path, f.read(), level)
             except (struct.error, IndexError) as e:
                 raise TiffError(f"{path}: truncated or corrupt TIFF ({e})") from e
         # header only: the IFD and its out-of-line values normally sit in the first or the last kilobytes; fall back to the whole
         # file when an offset points outside what was read
         head = f.read(1 << 16)
         try:
-            return _Header(path, head)
+            return _Header(path, head, level)
         except (struct.error, IndexError):
             f.seek(0)
             try:
-                return _Header(path, f.read())
+                return _Header(path, f.read(), level)
             except (struct.error, IndexError) as e:
                 raise TiffError(f"{path}: truncated or corrupt TIFF ({e})") from e
 
 
-def read(path: str, bands: Optional[List[int]] = None) -> Tuple[np.ndarray, Dict[str, Any]]:
+def read(path: str, bands: Optional[List[int]] = None, level: int = 0) -> Tuple[np.ndarray, Dict[str, Any]]:
     """-> (array (bands, H, W), profile).  ``profile`` holds width/height/count/dtype, ``nodata`` (GDAL_NODATA) and the raw
     georeferencing tags under ``"tags"`` ({tag: (tiff_type, values)}), ready for :func:`write`.  ``bands`` (0-based) decodes
-    only those sample planes of a band-interleaved file (the reference's ``src.read(band)``); the profile still describes the file."""
-    h = _header(path, True)
+    only those sample planes of a band-interleaved file (the reference's ``src.read(band)``); the profile still describes the file.
+    ``level`` > 0 reads that IFD along the next-IFD chain (the overviews of a COG); one beyond the file raises ``TiffError``."""
+    h = _header(path, True, level)
     buf, t, dt, comp, pred, planar = h.buf, h.t, h.dt, h.comp, h.pred, h.planar
     W, H, spp, one = h.W, h.H, h.spp, h.one
     sel = list(range(spp)) if bands is None else [int(b) for b in bands]
@@ -246,10 +271,37 @@ def read(path: str, bands: Optional[List[int]] = None) -> Tuple[np.ndarray, Dict
     return out, h.profile()
 
 
-def read_profile(path: str) -> Dict[str, Any]:
+def read_profile(path: str, level: int = 0) -> Dict[str, Any]:
     """The profile only, from the header: no strip is inflated (the reference opens the source chip just for ``src.profile``,
-    infer_utils.py:103-113, and ``get_valid_filepaths`` only to see that it opens)."""
-    return _header(path, False).profile()
+    infer_utils.py:103-113, and ``get_valid_filepaths`` only to see that it opens).  ``level``: as in :func:`read`."""
+    return _header(path, False, level).profile()
+
+
+def overview_count(path: str) -> int:
+    """The IFDs that follow the first along the next-IFD chain: the overviews of a COG, 0 for a file of :func:`write`."""
+    for whole in (False, True):  # the chain of a COG sits in the first kilobytes; the whole file when it leads beyond them
+        h = _header(path, whole)
+        try:
+            return len(_ifd_chain(h.buf, h.bo, h.first_ifd)) - 1
+        except (struct.error, IndexError) as e:
+            if whole:
+                raise TiffError(f"{path}: truncated or corrupt TIFF ({e})") from e
+    raise AssertionError("unreachable")
+
+
+def _entry(tag: int, typ: int, values) -> Tuple[int, int, int, bytes]:
+    """(tag, type, count, little-endian payload) of one IFD entry; ``values``: a str for ASCII, pairs for rationals, else a sequence."""
+    if typ == 2:
+        payload = values.encode("latin-1") + b"\x00"
+        cnt = len(payload)
+    elif typ in (5, 10):
+        flat = [x for pair in values for x in pair]
+        payload = struct.pack("<" + _TYPES[typ][0][0] * len(flat), *flat)
+        cnt = len(values)
+    else:
+        payload = struct.pack("<" + _TYPES[typ][0] * len(values), *values)
+        cnt = len(values)
+    return tag, typ, cnt, payload
 
 
 def write(path: str, array: np.ndarray, profile: Optional[Dict[str, Any]] = None, compress: Optional[str] = None) -> None:
@@ -277,17 +329,7 @@ def write(path: str, array: np.ndarray, profile: Optional[Dict[str, Any]] = None
     entries: List[Tuple[int, int, int, bytes]] = []  # (tag, type, count, payload)
 
     def ent(tag: int, typ: int, values) -> None:
-        if typ == 2:
-            payload = values.encode("latin-1") + b"\x00"
-            cnt = len(payload)
-        elif typ in (5, 10):
-            flat = [x for pair in values for x in pair]
-            payload = struct.pack("<" + _TYPES[typ][0][0] * len(flat), *flat)
-            cnt = len(values)
-        else:
-            payload = struct.pack("<" + _TYPES[typ][0] * len(values), *values)
-            cnt = len(values)
-        entries.append((tag, typ, cnt, payload))
+        entries.append(_entry(tag, typ, values))
 
     ent(_W, 4, (W,)), ent(_H, 4, (H,)), ent(_BPS, 3, (a.dtype.itemsize * 8,) * bands)
     ent(_COMP, 3, (8 if compress == "deflate" else 1,)), ent(_PHOTO, 3, (1,))
