@@ -20,8 +20,10 @@ from __future__ import annotations
 
 import json
 import os
-from concurrent.futures import ThreadPoolExecutor
-from typing import Any, Dict, List, Optional, Sequence, Tuple
+from concurrent.futures import Executor, ThreadPoolExecutor
+from dataclasses import dataclass
+from functools import partial
+from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -31,6 +33,32 @@ from . import cog as cogmod
 from . import ops, postprocess, tiff, vectorize, zonal
 from .calibration import check_temperature
 from .dataloader import d4_codes, d4_inverse, gather_windows, origins_tensor, window_grid, window_origins
+
+
+@dataclass(frozen=True)
+class OutputOptions:
+    """What inference writes of a finished class map besides the map: the output keywords of :func:`tile_inference`, with its defaults
+    (:func:`chip_inference` has the first seven)."""
+    min_region: int = 0
+    connectivity: int = 4
+    sieve_passes: int = 8
+    save_regions: bool = False
+    save_polygons: bool = False
+    zones: Optional[str] = None
+    zone_id_property: Optional[str] = None
+    cog: bool = False
+    cog_blocksize: int = 256
+    overview_levels: Union[str, int] = "auto"
+    cog_compress: Optional[str] = "deflate"
+
+    def check(self, model, chip_mode: bool = False) -> None:
+        """ValueError for options that cannot work, the first of the four checks that objects: before any file or device is touched.
+        ``model``: only its configured ``num_classes`` is read; None (nothing to ask) leaves the checks that need it out."""
+        ncls = getattr(getattr(getattr(model, "net", model), "cfg", None), "num_classes", None)
+        postprocess.check_region_options(self.min_region, self.connectivity, self.sieve_passes, self.save_regions, ncls == 1)
+        vectorize.check_polygon_options(self.save_polygons, ncls == 1)
+        zonal.check_zone_options(self.zones, ncls == 1)
+        cogmod.check_cog_options(self.cog, self.cog_blocksize, self.overview_levels, self.cog_compress, chip_mode=chip_mode, ncls=ncls)
 
 
 def save_prediction(prediction: np.ndarray, file_name: str, output_folder: str, profile: Optional[Dict[str, Any]] = None,
@@ -44,7 +72,7 @@ def save_prediction(prediction: np.ndarray, file_name: str, output_folder: str, 
 
 
 def _output_path(file_name: str, output_folder: str, kind: str, ext: Optional[str] = None) -> str:
-    """``save_prediction``'s naming; ``ext`` replaces the extension (the region table is ``regions_*.csv``)."""
+    """``save_prediction``'s naming; ``ext`` replaces the extension (``regions_*.csv``, ``polygons_*.geojson``, ``zones_*.csv``)."""
     base = os.path.basename(str(file_name))
     out = base.replace("chip", kind) if "chip" in base else f"{kind}_" + base
     if ext is not None:
@@ -54,26 +82,7 @@ def _output_path(file_name: str, output_folder: str, kind: str, ext: Optional[st
     return os.path.join(output_folder, out)
 
 
-def save_regions_csv(table: Dict[str, np.ndarray], file_name: str, output_folder: str, profile: Optional[Dict[str, Any]] = None) -> str:
-    """Write a region table (:func:`postprocess.region_table`) as ``regions_*.csv`` beside the prediction of ``file_name``."""
-    return postprocess.write_region_csv(_output_path(file_name, output_folder, "regions", ".csv"), table, profile)
-
-
-def save_polygons_geojson(rings: Tuple[np.ndarray, np.ndarray], table: Dict[str, np.ndarray], file_name: str, output_folder: str,
-                          profile: Optional[Dict[str, Any]] = None) -> str:
-    """Write (rings, vertices) of :func:`vectorize.region_rings` as ``polygons_*.geojson`` beside the prediction of ``file_name``."""
-    return vectorize.write_geojson(_output_path(file_name, output_folder, "polygons", ".geojson"), rings[0], rings[1], table, profile)
-
-
-def save_zones_csv(classmap: torch.Tensor, zones, ncls: int, fill: int, file_name: str, output_folder: str,
-                   profile: Optional[Dict[str, Any]] = None) -> str:
-    """Tally one (H, W) class map on the device inside ``zones`` (:func:`zonal.read_zones`, :func:`zonal.zone_table`) and write
-    ``zones_*.csv`` beside the prediction of ``file_name``."""
-    ids, counts = zonal.zone_table(classmap, zones, ncls, fill, profile)
-    return zonal.write_zone_csv(_output_path(file_name, output_folder, "zones", ".csv"), ids, counts, profile)
-
-
-def save_cog(raster: torch.Tensor, kind: str, file_name: str, output_folder: str, profile: Optional[Dict[str, Any]], cog_opts: Dict[str, Any],
+def save_cog(raster: torch.Tensor, kind: str, file_name: str, output_folder: str, profile: Optional[Dict[str, Any]], opts: OutputOptions,
              name_kind: str = "prediction", fill: int = -1, ncls: Optional[int] = None) -> str:
     """Write one raster still on the device as a Cloud Optimized GeoTIFF under :func:`save_prediction`'s name: the overviews by
     ``kind`` ("mode" for the int8 class map, "mean" for float32 rasters) come from the device (:func:`cog.build_overviews`), level 0 holds
@@ -84,23 +93,12 @@ def save_cog(raster: torch.Tensor, kind: str, file_name: str, output_folder: str
     if ncls is not None and ncls > cogmod.MAX_CLASSES:
         ncls = None
     counts = torch.zeros(ncls + 1, dtype=torch.int64, device=raster.device) if ncls is not None else None
-    levels = cogmod.build_overviews(raster, kind, cog_opts["overview_levels"], fill, cog_opts["cog_blocksize"], ncls, counts)
-    cogmod.write_cog(path, levels, profile, cog_opts["cog_blocksize"], cog_opts["cog_compress"])
+    levels = cogmod.build_overviews(raster, kind, opts.overview_levels, fill, opts.cog_blocksize, ncls=ncls, counts=counts)
+    cogmod.write_cog(path, levels, profile, opts.cog_blocksize, opts.cog_compress)
     if counts is not None:
         with open(_output_path(file_name, output_folder, "cogstats", ".json"), "w") as f:
             json.dump(cogmod.seg_stats(counts.cpu().numpy()), f, sort_keys=True)
     return path
-
-
-def _num_classes(model) -> int:
-    """The head's output channels, read from the module's configuration (no device work)."""
-    return int(getattr(getattr(model, "net", model), "cfg").num_classes)
-
-
-def _is_regression(model) -> bool:
-    """A single output channel, read from the module's configuration (no device work); False when there is no model to ask."""
-    cfg = getattr(getattr(model, "net", model), "cfg", None)
-    return getattr(cfg, "num_classes", None) == 1
 
 
 def _engine_of(model):
@@ -127,14 +125,11 @@ def chip_inference(dataloader, output_folder: str, model, device: str = "gpu", n
     """Run inference on chips and save one int8 class map (float32 for single-channel regression heads) per chip as
     ``prediction_*.tif``.  Returns {} (the reference returns CodeCarbon numbers; there is no tracker here).
 
-    ``min_region`` > 0 sieves every class map on the device before it is written (:func:`postprocess.sieve_class_map` with
-    ``connectivity`` and at most ``sieve_passes`` passes); ``save_regions`` writes the region table of the written map as
-    ``regions_*.csv`` beside it; ``save_polygons`` writes its regions as ``polygons_*.geojson`` (:mod:`instageo_amd.vectorize`);
-    ``zones`` (a GeoJSON file of polygons in the chips' coordinate system, labelled by ``zone_id_property``) writes the written map's
-    pixels per zone and class as ``zones_*.csv`` (:mod:`instageo_amd.zonal`).  With the defaults none of them runs."""
-    postprocess.check_region_options(min_region, connectivity, sieve_passes, save_regions, _is_regression(model))
-    vectorize.check_polygon_options(save_polygons, _is_regression(model))
-    zonal.check_zone_options(zones, _is_regression(model))
+    ``min_region``, ``connectivity``, ``sieve_passes``, ``save_regions``, ``save_polygons``, ``zones`` and ``zone_id_property`` are those
+    of :func:`tile_inference`, per chip (``zones`` in the chips' coordinate system).  With the defaults none of them runs."""
+    opts = OutputOptions(min_region=min_region, connectivity=connectivity, sieve_passes=sieve_passes, save_regions=save_regions,
+                         save_polygons=save_polygons, zones=zones, zone_id_property=zone_id_property)
+    opts.check(model, chip_mode=True)
     zone_list = zonal.read_zones(zones, zone_id_property) if zones is not None else None
     os.makedirs(output_folder, exist_ok=True)
     net, eng = _engine_of(model)
@@ -143,29 +138,60 @@ def chip_inference(dataloader, output_folder: str, model, device: str = "gpu", n
         for (data, _), file_names in dataloader:
             data = data.to("cuda" if device == "gpu" else device)
             logits = eng.forward(data, training=False, save=False)
-            if logits.shape[1] == 1:  # regression (single output channel)
-                pred = logits.squeeze(1).cpu().numpy()
+            regression = logits.shape[1] == 1  # a single output channel
+            profiles = [_profile_of(f, np.float32 if regression else np.int8) for f in file_names]
+            if regression:
+                pred = logits.squeeze(1)
             else:
-                maps = ops.argmax_i8(logits)
-                if min_region > 0:
-                    maps, _ = postprocess.sieve_class_map(maps, min_region, connectivity, -1, sieve_passes)
-                table = postprocess.region_table(maps, connectivity, -1) if save_regions or save_polygons else None
-                rings = vectorize.region_rings(maps, connectivity, -1) if save_polygons else None
-                pred = maps.cpu().numpy()
-            profiles = [_profile_of(f, pred.dtype) for f in file_names]
-            if zone_list is not None:  # on the device, chip by chip: each chip has its own georeferencing
-                for i, (f, prof) in enumerate(zip(file_names, profiles)):
-                    save_zones_csv(maps[i], zone_list, logits.shape[1], -1, f, output_folder, prof)
-            futures = [executor.submit(save_prediction, p, f, output_folder, prof) for p, f, prof in zip(pred, file_names, profiles)]
-            if save_regions:
-                futures += [executor.submit(save_regions_csv, postprocess.table_of_image(table, i), f, output_folder, prof)
-                            for i, (f, prof) in enumerate(zip(file_names, profiles))]
-            if save_polygons:
-                futures += [executor.submit(save_polygons_geojson, vectorize.rings_of_image(*rings, i), postprocess.table_of_image(table, i),
-                                            f, output_folder, prof) for i, (f, prof) in enumerate(zip(file_names, profiles))]
-            for fut in futures:
+                pred = _write_products(ops.argmax_i8(logits), list(zip(file_names, profiles)), output_folder, fill=-1, ncls=logits.shape[1],
+                                       opts=opts, zone_list=zone_list, executor=executor)
+            for fut in [executor.submit(save_prediction, p, f, output_folder, prof) for p, f, prof in zip(pred.cpu().numpy(), file_names, profiles)]:
                 fut.result()
     return {}
+
+
+def _write_products(maps: torch.Tensor, targets: Sequence[Tuple[str, Optional[Dict[str, Any]]]], output_folder: str, fill: int, ncls: int,
+                    opts: OutputOptions, zone_list=None, executor: Optional[Executor] = None) -> torch.Tensor:
+    """Everything ``opts`` asks of finished class maps but the rasters: ``maps`` (n, H, W) int8 on the device, ``targets`` the n (file name,
+    profile) pairs the products are named and georeferenced after -> the maps to write.  In this order: the sieve (``min_region`` > 0);
+    ONE labelling of the sieved maps, shared by the region table and the rings, so both describe the same regions; ``regions_*.csv`` and
+    ``polygons_*.geojson`` per image, through ``executor`` when there is one (waited for before returning); ``zones_*.csv`` per image with
+    that image's profile, tallied on the device meanwhile (``zone_list``: :func:`zonal.read_zones`, ``ncls`` classes).  With the defaults
+    nothing is launched and ``maps`` comes back untouched."""
+    if opts.min_region > 0:
+        maps, _ = postprocess.sieve_class_map(maps, opts.min_region, opts.connectivity, fill, opts.sieve_passes)
+    jobs = []
+    if opts.save_regions or opts.save_polygons:
+        labels = postprocess.label_regions(maps, opts.connectivity, fill)
+        table = postprocess.region_table(maps, opts.connectivity, fill, labels=labels)
+        rings = vectorize.region_rings(maps, opts.connectivity, fill, labels=labels) if opts.save_polygons else None
+        for i, (name, prof) in enumerate(targets):
+            rows = postprocess.table_of_image(table, i)
+            if opts.save_regions:
+                jobs.append((postprocess.write_region_csv, (_output_path(name, output_folder, "regions", ".csv"), rows, prof)))
+            if opts.save_polygons:
+                jobs.append((vectorize.write_geojson, (_output_path(name, output_folder, "polygons", ".geojson"),
+                                                       *vectorize.rings_of_image(*rings, i), rows, prof)))
+    pending = [executor.submit(fn, *args) if executor is not None else fn(*args) for fn, args in jobs]
+    if zone_list is not None:
+        for m, (name, prof) in zip(maps, targets):
+            ids, counts = zonal.zone_table(m, zone_list, ncls, fill, prof)
+            zonal.write_zone_csv(_output_path(name, output_folder, "zones", ".csv"), ids, counts, prof)
+    if executor is not None:
+        for fut in pending:
+            fut.result()
+    return maps
+
+
+def _write_raster(raster: torch.Tensor, name_kind: str, overview_kind: str, profile: Dict[str, Any], file_name: str, output_folder: str,
+                  opts: OutputOptions, classes: Optional[Tuple[int, int]] = None) -> str:
+    """One raster still on the device -> ``<name_kind>_*.tif`` (prediction | probability | uncertainty): a strip file, or with ``opts.cog`` a
+    Cloud Optimized GeoTIFF with ``overview_kind`` (mode | mean) overviews.  ``classes`` = (fill, ncls) marks the class map: its mode
+    ignores ``fill``, and only it gets ``cogstats_*.json``."""
+    if not opts.cog:
+        return save_prediction(raster.cpu().numpy(), file_name, output_folder, profile, kind=name_kind)
+    fill, ncls = classes if classes is not None else (-1, None)
+    return save_cog(raster, overview_kind, file_name, output_folder, profile=profile, opts=opts, name_kind=name_kind, fill=fill, ncls=ncls)
 
 
 @torch.no_grad()
@@ -325,7 +351,7 @@ def blended_window_inference(tile: torch.Tensor, model, mean: Sequence[float], s
     full = D.reduce_row_bands(canvas, bands, H, dst=0)
     if full is None:
         return (None, None, None) if uncertainty else (None, None)
-    out = ops.window_blend_finalize(full[:ncls], full[ncls], tile, no_data_value, fill, probabilities)
+    out = ops.window_blend_finalize(full[:ncls], full[ncls], tile, no_data_value, fill, probabilities=probabilities)
     if not uncertainty:
         return out
     unc = torch.empty((2, H, W), dtype=torch.float32, device=dev)
@@ -352,33 +378,27 @@ def tile_inference(tile_path: str, output_folder: str, model, mean: Sequence[flo
     "flips" | "d4" averages every window over its transforms; ``save_uncertainty`` writes ``uncertainty_*.tif`` (float32, band 1 the
     normalised entropy, band 2 the top-two margin of the blended probabilities, NaN = NODATA).
 
-    Region post-processing of the finished class map, on either path and on rank 0: ``min_region`` > 0 writes the sieved map as
-    ``prediction_*.tif`` (regions below the minimum mapping unit take the class of their largest kept 4-neighbour,
-    :func:`postprocess.sieve_class_map` with ``connectivity`` and at most ``sieve_passes`` passes); ``save_regions`` writes
-    ``regions_*.csv``, the region table of the written map (map coordinates when the tile is georeferenced).  The probability and
-    uncertainty rasters are unchanged by either: they describe the blend BEFORE the sieve.  ``save_polygons`` writes
-    ``polygons_*.geojson``: the regions of the written map (so after the sieve) as polygons with holes, traced on the device
-    (:func:`vectorize.region_rings`, :func:`vectorize.write_geojson`; map coordinates when the tile is georeferenced).  ``zones`` names
-    a GeoJSON file of Polygon / MultiPolygon zones in the tile's coordinate system: ``zones_*.csv`` then holds the pixels (and map
-    areas) of every class of the written map inside every zone, rasterised and tallied on the device (:mod:`instageo_amd.zonal`;
-    rows labelled by the property ``zone_id_property``, else the feature index).  With the defaults nothing of this runs.
+    Products of the finished class map, on either path and on rank 0 (:func:`_write_products`), in map coordinates when the tile is
+    georeferenced: ``min_region`` > 0 writes the sieved map as ``prediction_*.tif`` (:func:`postprocess.sieve_class_map` with
+    ``connectivity`` and at most ``sieve_passes`` passes); ``save_regions`` writes ``regions_*.csv``, the region table of the written map;
+    ``save_polygons`` writes ``polygons_*.geojson``, its regions as polygons with holes (:mod:`instageo_amd.vectorize`); ``zones`` names a
+    GeoJSON file of Polygon / MultiPolygon zones in the tile's coordinate system: ``zones_*.csv`` then holds the written map's pixels (and
+    map areas) per zone and class (:mod:`instageo_amd.zonal`; rows labelled by the property ``zone_id_property``, else the feature index).
+    The probability and uncertainty rasters describe the blend BEFORE the sieve.  With the defaults nothing of this runs.
 
     ``cog`` writes the class map (after the sieve), ``probability_*.tif`` and ``uncertainty_*.tif`` as Cloud Optimized GeoTIFFs under the
-    same names (:mod:`instageo_amd.cog`): tiles of ``cog_blocksize`` (128 | 256 | 512), ``overview_levels`` ("auto" | 0..12) overviews built
-    from the tensors still on the device (mode with ``fill`` for the class map, NaN-aware mean for the float rasters), ``cog_compress``
-    "deflate" | "none".  Level 0 of every file holds exactly the pixels the strip file holds without ``cog``.  ``cogstats_*.json`` holds the
-    class histogram of the written map in the reference's form (valid_pixels / class_counts / unique_values).
+    same names (:mod:`instageo_amd.cog`): tiles of ``cog_blocksize`` (128 | 256 | 512), ``overview_levels`` ("auto" | 0..12) overviews (mode
+    with ``fill`` for the class map, NaN-aware mean for the float rasters), ``cog_compress`` "deflate" | "none"; level 0 holds exactly the
+    pixels of the strip file.  ``cogstats_*.json`` holds the class histogram of the written map in the reference's form.
 
     ``temperature`` (blended paths; ``test.temperature`` / ``test.calibration``) calibrates the probabilities that are blended, and
     through them the class map, probability and uncertainty rasters.  The nearest-centre stitch is an argmax of raw logits, which no
     positive temperature changes: it ignores the value."""
+    opts = OutputOptions(min_region=min_region, connectivity=connectivity, sieve_passes=sieve_passes, save_regions=save_regions,
+                         save_polygons=save_polygons, zones=zones, zone_id_property=zone_id_property, cog=cog, cog_blocksize=cog_blocksize,
+                         overview_levels=overview_levels, cog_compress=cog_compress)
     check_temperature(temperature, "temperature")
-    postprocess.check_region_options(min_region, connectivity, sieve_passes, save_regions, _is_regression(model))
-    vectorize.check_polygon_options(save_polygons, _is_regression(model))
-    zonal.check_zone_options(zones, _is_regression(model))
-    cogmod.check_cog_options(cog, cog_blocksize, overview_levels, cog_compress,
-                             ncls=getattr(getattr(getattr(model, "net", model), "cfg", None), "num_classes", None))
-    cog_opts = dict(cog_blocksize=cog_blocksize, overview_levels=overview_levels, cog_compress=cog_compress) if cog else None
+    opts.check(model)
     if blend not in ("nearest", "mean", "gaussian"):
         raise ValueError(f"blend must be 'nearest', 'mean' or 'gaussian' (got {blend!r})")
     if blend == "nearest" and (cover_edges or save_probabilities):
@@ -387,78 +407,38 @@ def tile_inference(tile_path: str, output_folder: str, model, mean: Sequence[flo
     if blend == "nearest" and (tta != "none" or save_uncertainty):
         raise ValueError("tta and save_uncertainty need blend='mean' or 'gaussian' (they work on the probability canvas)")
     arr, profile = tiff.read(tile_path)
-    if blend != "nearest":
-        return _blended_tile_file(arr, profile, tile_path, output_folder, model, mean, std, temporal_size, crop_size, stride, batch_size,
-                                  constant_multiplier, no_data_value, fill, device, blend, cover_edges, sigma_scale, save_probabilities,
-                                  tta, save_uncertainty, min_region, connectivity, sieve_passes, save_regions, temperature, save_polygons,
-                                  zones, zone_id_property, cog_opts)
-    if arr.shape[1] != arr.shape[2]:
+    if blend == "nearest" and arr.shape[1] != arr.shape[2]:
         raise ValueError("tile_inference expects a square tile (the window rule of process_test uses one img_size)")
     t = torch.from_numpy(arr if arr.dtype in (np.int16, np.float32) else arr.astype(np.float32)).to(device)
-    maps, origins = sliding_window_inference(t, model, mean, std, temporal_size, crop_size, stride, batch_size, constant_multiplier)
-    if maps is None:
-        return None
-    canvas = stitch_windows(maps, origins, (arr.shape[1], arr.shape[2]), fill)
-    if no_data_value is not None:
-        canvas[(t == no_data_value).any(0)] = fill
+    window = dict(temporal_size=temporal_size, crop_size=crop_size, stride=stride, batch_size=batch_size, constant_multiplier=constant_multiplier)
+    if blend == "nearest":
+        maps, origins = sliding_window_inference(t, model, mean, std, **window)
+        if maps is None:
+            return None
+        classmap, prob, unc = stitch_windows(maps, origins, tuple(t.shape[1:]), fill), None, None
+        if no_data_value is not None:
+            classmap[(t == no_data_value).any(0)] = fill
+    else:
+        res = blended_window_inference(t, model, mean, std, **window, blend=blend, sigma_scale=sigma_scale, cover_edges=cover_edges,
+                                       no_data_value=no_data_value, fill=fill, probabilities=save_probabilities, tta=tta,
+                                       uncertainty=save_uncertainty, temperature=temperature)
+        classmap, prob, unc = (*res, None)[:3]
+        if classmap is None and prob is None:
+            return None
+    # one tail for both paths, on rank 0
     os.makedirs(output_folder, exist_ok=True)
-    prof = dict(profile)
-    prof.update(count=1, dtype="int8", nodata=fill)
-    prof["tags"] = {k: v for k, v in profile["tags"].items() if k != 42113}
-    canvas = _region_outputs(canvas, tile_path, output_folder, prof, fill, min_region, connectivity, sieve_passes, save_regions,
-                             save_polygons, zones, zone_id_property, _num_classes(model) if zones is not None else 0)
-    if cog_opts is not None:
-        return save_cog(canvas, "mode", tile_path, output_folder, prof, cog_opts, fill=fill, ncls=_num_classes(model))
-    return save_prediction(canvas.cpu().numpy(), tile_path, output_folder, prof)
-
-
-def _region_outputs(classmap: torch.Tensor, tile_path: str, output_folder: str, profile, fill: int, min_region: int, connectivity: int,
-                    sieve_passes: int, save_regions: bool, save_polygons: bool = False, zones: Optional[str] = None,
-                    zone_id_property: Optional[str] = None, ncls: int = 0) -> torch.Tensor:
-    """The class map to write: sieved when ``min_region`` > 0; ``save_regions`` writes its region table, ``save_polygons`` its regions
-    as polygons, ``zones`` its pixels per zone and class (``ncls`` classes).  The defaults return the map untouched without a launch."""
-    if min_region > 0:
-        classmap, _ = postprocess.sieve_class_map(classmap, min_region, connectivity, fill, sieve_passes)
-    table = postprocess.region_table(classmap, connectivity, fill) if save_regions or save_polygons else None
-    if save_regions:
-        save_regions_csv(table, tile_path, output_folder, profile)
-    if save_polygons:
-        save_polygons_geojson(vectorize.region_rings(classmap, connectivity, fill), table, tile_path, output_folder, profile)
-    if zones is not None:
-        save_zones_csv(classmap, zonal.read_zones(zones, zone_id_property), ncls, fill, tile_path, output_folder, profile)
-    return classmap
-
-
-def _blended_tile_file(arr, profile, tile_path, output_folder, model, mean, std, temporal_size, crop_size, stride, batch_size,
-                       constant_multiplier, no_data_value, fill, device, blend, cover_edges, sigma_scale, save_probabilities,
-                       tta="none", save_uncertainty=False, min_region=0, connectivity=4, sieve_passes=8, save_regions=False,
-                       temperature=1.0, save_polygons=False, zones=None, zone_id_property=None, cog_opts=None) -> Optional[str]:
-    t = torch.from_numpy(arr if arr.dtype in (np.int16, np.float32) else arr.astype(np.float32)).to(device)
-    res = blended_window_inference(t, model, mean, std, temporal_size, crop_size, stride, batch_size, constant_multiplier, blend,
-                                   sigma_scale, cover_edges, no_data_value, fill, save_probabilities, tta, save_uncertainty, temperature)
-    classmap, prob = res[0], res[1]
-    if classmap is None and prob is None:
-        return None
-    os.makedirs(output_folder, exist_ok=True)
+    write = partial(_write_raster, file_name=tile_path, output_folder=output_folder, opts=opts)
     tags = {k: v for k, v in profile["tags"].items() if k != 42113}
     float_prof = dict(profile, count=1, dtype="float32", nodata=None, tags={**tags, 42113: (2, "nan")})
     if classmap is None:  # regression head: the blended value is the prediction
-        if cog_opts is not None:
-            return save_cog(prob[0], "mean", tile_path, output_folder, float_prof, cog_opts)
-        return save_prediction(prob[0].cpu().numpy(), tile_path, output_folder, float_prof)
+        return write(prob[0], "prediction", "mean", float_prof)
     int_prof = dict(profile, count=1, dtype="int8", nodata=fill, tags=tags)
-    classmap = _region_outputs(classmap, tile_path, output_folder, int_prof, fill, min_region, connectivity, sieve_passes, save_regions,
-                               save_polygons, zones, zone_id_property, _num_classes(model) if zones is not None else 0)
-    if cog_opts is not None:
-        out = save_cog(classmap, "mode", tile_path, output_folder, int_prof, cog_opts, fill=fill, ncls=_num_classes(model))
-        if save_probabilities:
-            save_cog(prob, "mean", tile_path, output_folder, dict(float_prof, count=prob.shape[0]), cog_opts, "probability")
-        if save_uncertainty:
-            save_cog(res[2], "mean", tile_path, output_folder, dict(float_prof, count=2), cog_opts, "uncertainty")
-        return out
-    out = save_prediction(classmap.cpu().numpy(), tile_path, output_folder, int_prof)
-    if save_probabilities:
-        save_prediction(prob.cpu().numpy(), tile_path, output_folder, dict(float_prof, count=prob.shape[0]), kind="probability")
-    if save_uncertainty:
-        save_prediction(res[2].cpu().numpy(), tile_path, output_folder, dict(float_prof, count=2), kind="uncertainty")
+    ncls = int(getattr(model, "net", model).cfg.num_classes)
+    zone_list = zonal.read_zones(zones, zone_id_property) if zones is not None else None
+    classmap = _write_products(classmap[None], [(tile_path, int_prof)], output_folder, fill, ncls, opts=opts, zone_list=zone_list)[0]
+    out = write(classmap, "prediction", "mode", int_prof, classes=(fill, ncls))
+    if prob is not None:
+        write(prob, "probability", "mean", dict(float_prof, count=prob.shape[0]))
+    if unc is not None:
+        write(unc, "uncertainty", "mean", dict(float_prof, count=2))
     return out

@@ -98,17 +98,24 @@ def sieve_class_map(classmap: torch.Tensor, min_region: int, connectivity: int =
     return out, info
 
 
-def region_table(classmap: torch.Tensor, connectivity: int = 4, fill: int = -1) -> Dict[str, np.ndarray]:
+def _check_labels(labels: Optional[torch.Tensor], classmap: torch.Tensor) -> None:
+    if labels is not None and not (isinstance(labels, torch.Tensor) and labels.dtype == torch.int32 and labels.shape == classmap.shape):
+        raise ValueError("labels must be the int32 tensor of the class map's shape that label_regions returns for it")
+
+
+def region_table(classmap: torch.Tensor, connectivity: int = 4, fill: int = -1, labels: Optional[torch.Tensor] = None) -> Dict[str, np.ndarray]:
     """One row per region, ordered by (image, root): ``image``, ``root`` (the label), ``cls``, ``area``, the bounding box ``row_min,
     row_max, col_min, col_max`` (inclusive pixel indices) as int64 and the centroid ``centroid_row, centroid_col`` as float64 = the
-    integer sums of the pixel indices / area, divided on the host."""
+    integer sums of the pixel indices / area, divided on the host.  ``labels``: what :func:`label_regions` gave for the same map,
+    ``connectivity`` and ``fill``, when the caller has it already (the map is then not labelled again)."""
     _check_map(classmap, connectivity, fill)
+    _check_labels(labels, classmap)
     cm = classmap.contiguous()
     cm3 = cm if cm.dim() == 3 else cm.unsqueeze(0)
     if cm3.numel() == 0:
         return {k: np.zeros(0, dtype=np.float64 if k.startswith("centroid") else np.int64) for k in TABLE_COLUMNS}
     HW = cm3.shape[1] * cm3.shape[2]
-    labels = ops.ccl_label(cm3, connectivity, fill)
+    labels = ops.ccl_label(cm3, connectivity, fill) if labels is None else labels.contiguous().view(cm3.shape)
     area = ops.region_area(labels)
     isroot = (area != 0).view(-1)
     rid = (torch.cumsum(isroot, 0, dtype=torch.int32) - 1).view(labels.shape)

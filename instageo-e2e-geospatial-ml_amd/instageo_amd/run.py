@@ -279,8 +279,9 @@ def run_tile_inference(cfg: Dict[str, Any], model, tile: str, output_dir: str, d
     d, t = cfg["dataloader"], cfg["test"]
     mult = d.get("constant_multiplier", 1.0)
     mult = None if mult in (None, 1, 1.0) else float(mult)
-    return tile_inference(tile, output_dir, model, d["mean"], d["std"], d["temporal_dim"], t["crop_size"], t["stride"],
-                          cfg["train"]["batch_size"], mult, d.get("no_data_value", -9999), device=dev, blend=t.get("blend", "nearest"),
+    return tile_inference(tile, output_dir, model, d["mean"], d["std"], temporal_size=d["temporal_dim"], crop_size=t["crop_size"],
+                          stride=t["stride"], batch_size=cfg["train"]["batch_size"], constant_multiplier=mult,
+                          no_data_value=d.get("no_data_value", -9999), device=dev, blend=t.get("blend", "nearest"),
                           cover_edges=bool(t.get("cover_edges", False)), sigma_scale=float(t.get("sigma_scale", 0.125)),
                           save_probabilities=bool(t.get("save_probabilities", False)), tta=str(t.get("tta", "none")),
                           save_uncertainty=bool(t.get("save_uncertainty", False)), temperature=float(getattr(model, "temperature", 1.0)),

@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
-from .postprocess import _check_map, georeference
+from .postprocess import _check_labels, _check_map, georeference
 
 RING_COLUMNS = ("image", "label", "cls", "n_vertices", "twice_area", "first")
 
@@ -59,20 +59,24 @@ def _empty() -> Tuple[np.ndarray, np.ndarray]:
     return np.zeros((0, len(RING_COLUMNS)), dtype=np.int64), np.zeros((0, 2), dtype=np.int32)
 
 
-def region_rings(classmap: torch.Tensor, connectivity: int = 4, fill: int = -1) -> Tuple[np.ndarray, np.ndarray]:
+def region_rings(classmap: torch.Tensor, connectivity: int = 4, fill: int = -1,
+                 labels: Optional[torch.Tensor] = None) -> Tuple[np.ndarray, np.ndarray]:
     """The rings of every region of an (H, W) | (n, H, W) int8 class map on the device -> (rings, vertices) as numpy arrays.
 
     ``rings`` int64, one row per ring with the columns ``RING_COLUMNS``: ``image``, ``label`` (the region's root of
     :func:`postprocess.region_table`), ``cls``, ``n_vertices``, ``twice_area`` (> 0 exterior, < 0 hole) and ``first`` = its first row
     in ``vertices`` (V, 2) int32 (x, y) lattice corners; a ring is NOT closed there (the first vertex is not repeated).  Rows are ordered
-    by (image, label, hole, root edge): a region's exterior ring, then its holes.  A region's rings sum to twice its pixel count."""
+    by (image, label, hole, root edge): a region's exterior ring, then its holes.  A region's rings sum to twice its pixel count.
+    ``labels``: what :func:`postprocess.label_regions` gave for the same map, ``connectivity`` and ``fill``, when the caller has it
+    already (the map is then not labelled again)."""
     _check_map(classmap, connectivity, fill)
+    _check_labels(labels, classmap)
     cm3 = classmap.contiguous()
     cm3 = cm3 if cm3.dim() == 3 else cm3.unsqueeze(0)
     if cm3.numel() == 0:
         return _empty()
     HW = cm3.shape[1] * cm3.shape[2]
-    labels = ops.ccl_label(cm3, connectivity, fill)
+    labels = ops.ccl_label(cm3, connectivity, fill) if labels is None else labels.contiguous().view(cm3.shape)
     mask, total = ops.edge_mask(labels)
     E = int(total.item())
     if E == 0:
