@@ -479,6 +479,34 @@ int ig_overview_mode(const signed char* src, int H, int W, int fill, int ncls, i
 int ig_overview_mean(const float* src, int bands, int H, int W, int levels, float* dst, void* stream);
 int ig_cog_tiles(const void* src, int bands, int H, int W, int elem_size, int is_float, int tile, unsigned pad, int predictor, void* dst,
                  void* stream);
+/* Mosaic of per-chip rasters on one canvas (mosaic.hip; the reference runs gdal_merge.py over the prediction folder instead).  nchips
+ * rectangles lie on an H x W canvas, H * W <= 2^31 - 1.  Chip i has rects[i] = (row0, col0, h, w) (int32; h, w in [1, 2^30], row0 and col0
+ * in [-2^30, 2^30]) and its h * w pixels row-major at element offset starts[i] (int64, >= 0) of one packed buffer `chips`; pixel (r, c) of
+ * the chip lies on canvas pixel (row0 + r, col0 + c).  A rectangle may hang over the canvas edge, negative row0 / col0 included: only the
+ * part inside the canvas counts.  Chip i CONTRIBUTES to a canvas pixel when it covers the pixel and its value there is not transparent:
+ * for int8 class maps (elem_size 1) transparent means == fill, for float32 rasters (elem_size 4) it means NaN.  The contributors of a
+ * pixel are ordered by chip index.  The value of a canvas pixel by rule:
+ *   0 LAST: the value of the contributor with the largest index (gdal_merge -n fill: later files win);
+ *   1 FIRST: the value of the contributor with the smallest index;
+ *   2 MODE (int8 only): the value that the most contributors have, ties go to the smallest value (as signed int8): the tie rule of
+ *     ig_overview_mode.  It does not depend on the order of the chips;
+ *   3 MEAN (float32 only): the float32 sum of the contributors in index order (the first, then one IEEE addition per further one),
+ *     divided by their count as float32 with IEEE round-to-nearest division: equal to numpy float32 arithmetic in the same order;
+ *   no contributor: fill for int8, the quiet NaN 0x7fc00000 for float32.
+ * LAST and FIRST copy bits: a float keeps its sign of zero.  cover (H, W) uint8, when not NULL, receives the number of contributors of
+ * every pixel, saturating at 255.
+ * ig_mosaic_paste: a gather.  One workgroup owns one 64 x 64 block of the canvas with its origin at multiples of 64 (the blocking of
+ *   ig_overview_mode, which may read the canvas next); blocks are numbered row-major, ceil(W / 64) to a row.  bin_ptr (blocks + 1 int32,
+ *   ascending from 0) and bin_idx are a CSR list made by the caller: bin_idx[bin_ptr[b] .. bin_ptr[b + 1]) holds, in ASCENDING order, the
+ *   indices of all chips whose rectangle intersects block b (more are harmless, fewer lose contributors).  A list may have any length; it is
+ *   staged through LDS 256 entries at a time.  A block with an empty list is written as fill / NaN.  Every pixel of dst (and cover) is
+ *   written exactly once, by the thread that computed it; no atomics, no kernel waits on another workgroup; results are bit-identical
+ *   from run to run.  A chip index outside [0, nchips), a rectangle outside the bounds above or a negative start contributes nothing;
+ *   the caller guarantees that starts[i] + h * w lies inside chips.  dst 16-byte aligned, rects 16-byte aligned.  fill must fit int8 (for
+ *   float32 it is ignored).  H * W = 0 returns IG_OK without touching a pointer; nchips = 0 writes fill / NaN everywhere and reads none
+ *   of chips, starts, rects, bin_ptr, bin_idx.  ceil(H / 64) <= 65535. */
+int ig_mosaic_paste(const void* chips, const long long* starts, const int* rects, int nchips, const int* bin_ptr, const int* bin_idx, int H,
+                    int W, int elem_size, int rule, int fill, void* dst, unsigned char* cover, void* stream);
 int ig_confusion_update(const long long* y_true, const long long* y_pred, unsigned long long* confusion, long n, int k,
                         long ignore_index, int has_ignore, void* stream);
 /* torch.optim.AdamW step on a flat buffer (+ clip_weights, + bf16 shadow refresh)        base.py:103-126 */

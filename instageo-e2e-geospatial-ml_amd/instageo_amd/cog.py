@@ -18,8 +18,8 @@ that level: 1, 2 or 4 of them.  Levels cascade: level k is computed from level k
 Device tensors go through ``ig_overview_mode`` / ``ig_overview_mean`` / ``ig_cog_tiles``; host arrays take a numpy path of the same
 rules, so the writer works (and is tested) without a GPU.  Deflate runs on the host.
 
-Not done: BigTIFF, LZW writing, predictor 3, GDAL's ghost-area metadata block, other resampling rules, argmax-of-mean class overviews,
-and a mosaic of per-chip predictions into one canvas (the reference's ``gdal_merge`` step).
+Not done: BigTIFF, LZW writing, predictor 3, GDAL's ghost-area metadata block, other resampling rules and argmax-of-mean class
+overviews.  The mosaic of per-chip predictions into one canvas (the reference's ``gdal_merge`` step) is :mod:`instageo_amd.mosaic`.
 """
 from __future__ import annotations
 

@@ -79,6 +79,12 @@ DEFAULTS: Dict[str, Any] = {'root_dir': None,
           # histogram.  cog_blocksize: 128 | 256 | 512 (the reference's BLOCKSIZE=chip_size); overview_levels: 'auto' (until both sides
           # fit a block) or 0..12 (the reference asks for 6); cog_compress: 'deflate' | 'none'
           'cog': False, 'cog_blocksize': 256, 'overview_levels': 'auto', 'cog_compress': 'deflate',
+          # mosaic of mode=chip_inference (not in the reference's run.py; its serving layer runs gdal_merge): after the chips are written,
+          # rank 0 pastes the prediction_*.tif files on their common grid on the device and writes predictions_merged.tif with the region /
+          # polygon / zone products of the whole map (mosaic.py).  mosaic_rule: where chips overlap, 'last' | 'first' file in name order,
+          # 'mode' (class maps) or 'mean' (regression); mosaic_cog: a COG with cogstats_merged.json under the cog_blocksize /
+          # overview_levels / cog_compress keys, else a strip file; mosaic_cover: also cover_merged.tif, the chips that cover each pixel
+          'mosaic': False, 'mosaic_rule': 'last', 'mosaic_cog': True, 'mosaic_cover': False,
           # calibrated probabilities (not in the reference): logits / temperature in front of every softmax consumer (predict_step, the
           # blended tile canvas, the test epoch's ROC-AUC).  temperature: a float > 0, None = 1.0 (nothing is scaled); calibration: the
           # calibration.json of mode=calibrate to take it from (one of the two).  calibration_metrics: mode=eval also logs test_nll /

@@ -1116,6 +1116,58 @@ def cog_tiles(raster, tile: int, pad: int = 0, predictor: int = 1):
     return out
 
 
+MOSAIC_RULES = {"last": 0, "first": 1, "mode": 2, "mean": 3}  # include/instageo_hip.h
+MOSAIC_BLOCK = 64  # side of the canvas block one workgroup owns, and of a bin of the chip lists
+MOSAIC_LIMIT = 1 << 30  # |row0|, |col0|, h, w of a chip rectangle
+
+
+def mosaic_paste(chips, starts, rects, bin_ptr, bin_idx, shape: Tuple[int, int], rule: str = "last", fill: int = -1, cover: bool = False,
+                 out=None, cover_out=None):
+    """The mosaic of ``ig_mosaic_paste`` (include/instageo_hip.h): ``chips`` the packed pixels of all chips, a 1-D int8 or float32 tensor
+    on the device; ``starts`` (n,) int64, ``rects`` (n, 4) int32 = (row0, col0, h, w), ``bin_ptr`` / ``bin_idx`` the CSR chip lists of the
+    64 x 64 canvas blocks (:func:`instageo_amd.mosaic.bins`) as host arrays: they are checked here, so that no chip read can leave
+    ``chips``, and uploaded.  -> the (H, W) canvas of ``chips``' dtype, or (canvas, cover (H, W) uint8) with ``cover``.  ``out`` /
+    ``cover_out``: write into these contiguous (H, W) tensors instead of new ones (every pixel is written)."""
+    import numpy as np
+
+    assert chips.dim() == 1 and chips.dtype in (torch.int8, torch.float32), "chips is the packed 1-D int8 or float32 buffer"
+    es = chips.element_size()
+    code = MOSAIC_RULES.get(rule)
+    if code is None or (code == 2 and es != 1) or (code == 3 and es != 4):
+        raise ValueError(f"rule {rule!r} does not go with {chips.dtype} chips (int8: last | first | mode, float32: last | first | mean)")
+    H, W = int(shape[0]), int(shape[1])
+    rects = np.ascontiguousarray(rects, dtype=np.int32).reshape(-1, 4)
+    starts = np.ascontiguousarray(starts, dtype=np.int64).reshape(-1)
+    bin_ptr = np.ascontiguousarray(bin_ptr, dtype=np.int32).reshape(-1)
+    bin_idx = np.ascontiguousarray(bin_idx, dtype=np.int32).reshape(-1)
+    n = rects.shape[0]
+    blocks = -(-H // MOSAIC_BLOCK) * -(-W // MOSAIC_BLOCK)
+    if starts.shape[0] != n:
+        raise ValueError(f"{n} rectangles but {starts.shape[0]} starts")
+    if n:
+        r0, c0, h, w = (rects[:, k].astype(np.int64) for k in range(4))
+        if (h < 1).any() or (w < 1).any() or max(h.max(), w.max(), np.abs(r0).max(), np.abs(c0).max()) > MOSAIC_LIMIT:
+            raise ValueError("a chip rectangle needs h, w >= 1 and |row0|, |col0|, h, w <= 2^30")
+        if (starts < 0).any() or (starts + h * w > chips.numel()).any():
+            raise ValueError(f"a chip's pixels lie outside the packed buffer of {chips.numel()} elements")
+        if bin_ptr.shape[0] != blocks + 1 or bin_ptr[0] != 0 or (np.diff(bin_ptr) < 0).any() or bin_ptr[-1] != bin_idx.shape[0]:
+            raise ValueError(f"bin_ptr must hold {blocks} + 1 ascending offsets into bin_idx, from 0 to its length")
+        if bin_idx.size and (bin_idx.min() < 0 or bin_idx.max() >= n):
+            raise ValueError("bin_idx holds a chip index outside the rectangles")
+    dev = chips.device
+    dst = out if out is not None else torch.empty((H, W), dtype=chips.dtype, device=dev)
+    cover = cover or cover_out is not None
+    cov = cover_out if cover_out is not None else torch.empty((H, W), dtype=torch.uint8, device=dev) if cover else None
+    assert dst.dtype == chips.dtype and tuple(dst.shape) == (H, W) and (cov is None or (cov.dtype == torch.uint8 and tuple(cov.shape) == (H, W)))
+    if H * W:
+        up = lambda a: torch.from_numpy(a).to(dev) if n else None  # noqa: E731
+        meta = [up(starts), up(rects), up(bin_ptr), up(bin_idx)]  # alive until the launch is queued; the copies are stream-ordered
+        # HBM bytes: the chips read once (an upper bound where they overhang or a rule stops early) + the canvas (+ cover) written
+        _call("ig_mosaic_paste", float(es) * (chips.numel() + H * W) + (H * W if cover else 0), _p(chips) if n else None, _p(meta[0]),
+              _p(meta[1]), n, _p(meta[2]), _p(meta[3]), H, W, es, code, int(fill), _p(dst), _p(cov), _stream())
+    return (dst, cov) if cover else dst
+
+
 def confusion_update(y_true, y_pred, confusion, k: int, ignore_index: Optional[int]) -> None:
     assert y_true.dtype == torch.int64 and y_pred.dtype == torch.int64 and confusion.dtype == torch.int64
     _lib.call("ig_confusion_update", _p(y_true), _p(y_pred), _p(confusion), y_true.numel(), k,

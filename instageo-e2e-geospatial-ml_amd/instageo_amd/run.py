@@ -325,6 +325,30 @@ def cog_options(cfg: Dict[str, Any]) -> Dict[str, Any]:
     return opts
 
 
+def mosaic_options(cfg: Dict[str, Any]) -> Dict[str, Any]:
+    """The ``test.mosaic`` / ``mosaic_rule`` / ``mosaic_cog`` / ``mosaic_cover`` keys (the mosaic of the per-chip predictions, mosaic.py),
+    checked: a bad value raises ValueError, and so do ``mosaic`` outside ``mode=chip_inference`` and a rule the task's head cannot have
+    (``mode`` needs class maps, ``mean`` a regression head)."""
+    from .mosaic import RULES
+
+    t = cfg["test"]
+    opts = dict(mosaic=t.get("mosaic", False), rule=t.get("mosaic_rule", "last"), cog=t.get("mosaic_cog", True),
+                save_cover=t.get("mosaic_cover", False))
+    for key, name in (("mosaic", "mosaic"), ("cog", "mosaic_cog"), ("save_cover", "mosaic_cover")):
+        if not isinstance(opts[key], bool):
+            raise ValueError(f"test.{name} must be true or false (got {opts[key]!r})")
+    if opts["rule"] not in RULES:
+        raise ValueError(f"test.mosaic_rule must be one of {RULES} (got {opts['rule']!r})")
+    if opts["mosaic"]:
+        if cfg.get("mode") != "chip_inference":
+            raise ValueError("test.mosaic needs mode=chip_inference: it merges the per-chip prediction files (tile inference writes one raster)")
+        regression = bool(cfg.get("is_reg_task", False)) or cfg["model"].get("num_classes") == 1
+        if opts["rule"] == ("mode" if regression else "mean"):
+            raise ValueError(f"test.mosaic_rule={opts['rule']} does not go with a {'regression' if regression else 'classification'} head "
+                             "(class maps: last | first | mode, regression: last | first | mean)")
+    return opts
+
+
 def main(argv: Optional[List[str]] = None) -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--config-name", default="config")
@@ -335,6 +359,7 @@ def main(argv: Optional[List[str]] = None) -> int:
     args = ap.parse_args(argv)
     cfg = load_config(args.config_name, args.overrides, args.config_path)
     cog_options(cfg)  # a bad COG key, or test.cog with mode=chip_inference, stops here: before the model is built
+    mosaic = mosaic_options(cfg)  # likewise a bad mosaic key, or test.mosaic outside mode=chip_inference
     start = time.time()
     torch.manual_seed(SEED)
     np.random.seed(SEED)
@@ -390,6 +415,17 @@ def main(argv: Optional[List[str]] = None) -> int:
         info = chip_inference(loader, output_dir, model, device="gpu", **region_options(cfg), **polygon_options(cfg), **zone_options(cfg))
         if rank == 0:
             print(f"Carbon tracking information: {info}")
+        if mosaic.pop("mosaic"):
+            if D.dp_active():
+                torch.distributed.barrier()  # every rank's chips are on disk
+            if rank == 0:
+                from .mosaic import merge_predictions
+
+                ncls = int(model.net.cfg.num_classes)
+                cog = {k: v for k, v in cog_options(cfg).items() if k != "cog"}
+                merged = merge_predictions(output_dir, output_dir, fill=-1, num_classes=None if ncls == 1 else ncls, device=dev, **mosaic,
+                                           **cog, **region_options(cfg), **polygon_options(cfg), **zone_options(cfg))
+                print(json.dumps({"mosaic": merged}))
     elif cfg["mode"] == "tile_inference":
         check_required_flags(["root_dir", "test_filepath", "checkpoint_path"], cfg)
         for tile in tile_paths(cfg):
