@@ -507,6 +507,49 @@ int ig_cog_tiles(const void* src, int bands, int H, int W, int elem_size, int is
  *   of chips, starts, rects, bin_ptr, bin_idx.  ceil(H / 64) <= 65535. */
 int ig_mosaic_paste(const void* chips, const long long* starts, const int* rects, int nchips, const int* bin_ptr, const int* bin_idx, int H,
                     int W, int elem_size, int rule, int fill, void* dst, unsigned char* cover, void* stream);
+/* Reprojection and resampling of north-up rasters between grids (warp.hip; the reference's viewer reprojects with rasterio before display,
+ * apps/viz.py).  A COORDINATE SYSTEM is five doubles (kind, lon0, k0, FE, FN): kind 0 geographic WGS84 (x = longitude, y = latitude, degrees;
+ * the other four are ignored but compared), kind 1 transverse Mercator on WGS84 (a = 6378137, 1/f = 298.257223563) with central meridian
+ * lon0 (degrees), scale k0, false easting FE and false northing FN (metres; UTM north: 0.9996, 500000, 0; south: FN = 1e7), kind 2
+ * spherical web Mercator EPSG:3857 (R = 6378137; the other four ignored).  Transverse Mercator is the Krueger series in the third
+ * flattening n to n^6, forward and inverse, in float64: xi + i eta = xi' + i eta' + sum_j alpha_j sin(2j (xi' + i eta')), j = 1..6, summed
+ * by the angle-addition recurrence from one sincos and one sinh / cosh pair; the geographic latitude comes from the conformal one by
+ * three Newton steps on tan(latitude) from tau'/(1 - e^2) (no data-dependent loop).  A GRID is four doubles (X0, Y0, sx, sy), the outer
+ * corner of the top-left pixel and the positive pixel sizes, with its size (h, w): the centre of pixel (r, c) lies at x = X0 + (c + 0.5) sx,
+ * y = Y0 - (r + 0.5) sy, and the point (x, y) has the pixel coordinates u = (x - X0) / sx, v = (Y0 - y) / sy, so that pixel (r, c) covers
+ * [c, c + 1) x [r, r + 1).
+ * The source coordinates (u, v) of a destination pixel: its centre (x, y) -> (longitude, latitude) by the inverse projection of the
+ * destination system -> (x', y') by the forward projection of the source system -> (u, v) on the source grid.  (NaN, NaN) OUTSIDE THE
+ * DOMAIN: a longitude or latitude that is not finite, |latitude| > 89.9 degrees, for a transverse Mercator destination |xi'| > pi / 2, and
+ * for a transverse Mercator source |longitude - lon0| >= 80 degrees (the difference taken into [-180, 180] by IEEE remainder).  Where the
+ * five doubles of the two systems are equal (compared as doubles) no projection is evaluated: (u, v) is the affine arithmetic above.
+ * ig_warp_coords: uv (2, H, W) float64 = the u plane, then the v plane, of the H x W destination grid in the one source grid; dst_crs and
+ *   src_crs point to 5, dst_grid and src_grid to 4 doubles ON THE DEVICE.  H * W = 0 returns IG_OK without touching a pointer.
+ * ig_warp: resamples nsrc <= 8 sources onto the destination in one launch.  Source i has src_crs[5 i ..], src_grid[4 i ..], src_size[2 i ..]
+ *   = (h, w) (int32, in [1, 2^30]) and its h * w pixels row-major at element offset starts[i] (int64, >= 0) of the packed buffer src.
+ *   A value is TRANSPARENT as in the mosaic paste: int8 (elem_size 1) == fill, float32 (elem_size 4) NaN.
+ *   resampling 0 NEAREST (int8, float32): c = floor(u), r = floor(v); the source contributes its pixel (r, c) when 0 <= r < h, 0 <= c < w
+ *     and the value is not transparent; bits are copied.
+ *   resampling 1 BILINEAR (float32 only): c0 = floor(u - 0.5), r0 = floor(v - 0.5), wx = u - 0.5 - c0, wy = v - 0.5 - r0; the neighbours
+ *     (r0, c0), (r0, c0 + 1), (r0 + 1, c0), (r0 + 1, c0 + 1) have the float64 weights (1 - wx)(1 - wy), wx (1 - wy), (1 - wx) wy, wx wy.  A
+ *     neighbour counts when it lies inside the source, is not NaN and has a weight > 0; the value is sum(weight * value) / sum(weight)
+ *     over those that count, both sums in float64 in the order above, rounded once to float32.  None counts: no contribution.
+ *   (u, v) = (NaN, NaN) never contributes.  rule 0 LAST: the contributing source with the largest index gives the value; 1 FIRST: the
+ *   smallest; no contributor: fill (int8) or the quiet NaN 0x7fc00000.  src_id (H, W) uint8, when not NULL, receives that index, 255 for
+ *   none.  One workgroup owns one 64 x 64 block of the destination with its origin at multiples of 64 (the blocking of ig_mosaic_paste and
+ *   ig_overview_mode), blocks numbered row-major; bin_ptr (blocks + 1 int32, ascending from 0) / bin_idx is the caller's CSR list of the
+ *   sources that can reach each block, in ASCENDING order (more are harmless, fewer lose contributors).  The longitude and latitude of
+ *   a pixel are computed once and reused for every source, and sources of one coordinate system share the forward projection.  Every
+ *   pixel of dst (and src_id) is written exactly once by the thread that computed it, a wave stores 64 consecutive pixels of a row; no
+ *   atomics, no kernel waits on another workgroup; results are bit-identical from run to run.  A source index outside [0, nsrc), a size
+ *   outside the bounds, a grid whose pixel sizes are not finite and positive or a negative start contributes nothing; the caller guarantees that
+ *   starts[i] + h * w lies inside src.  H * W <= 2^31 - 1, ceil(H / 64) <= 65535; H * W = 0 returns IG_OK without touching a pointer;
+ *   nsrc = 0 writes fill / NaN everywhere and reads none of the source arguments. */
+int ig_warp_coords(const double* dst_crs, const double* dst_grid, int H, int W, const double* src_crs, const double* src_grid, double* uv,
+                   void* stream);
+int ig_warp(const void* src, const long long* starts, const double* src_crs, const double* src_grid, const int* src_size, int nsrc,
+            const int* bin_ptr, const int* bin_idx, const double* dst_crs, const double* dst_grid, int H, int W, int elem_size, int resampling,
+            int rule, int fill, void* dst, unsigned char* src_id, void* stream);
 int ig_confusion_update(const long long* y_true, const long long* y_pred, unsigned long long* confusion, long n, int k,
                         long ignore_index, int has_ignore, void* stream);
 /* torch.optim.AdamW step on a flat buffer (+ clip_weights, + bf16 shadow refresh)        base.py:103-126 */

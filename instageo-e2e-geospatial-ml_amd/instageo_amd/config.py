@@ -85,6 +85,10 @@ DEFAULTS: Dict[str, Any] = {'root_dir': None,
           # 'mode' (class maps) or 'mean' (regression); mosaic_cog: a COG with cogstats_merged.json under the cog_blocksize /
           # overview_levels / cog_compress keys, else a strip file; mosaic_cover: also cover_merged.tif, the chips that cover each pixel
           'mosaic': False, 'mosaic_rule': 'last', 'mosaic_cog': True, 'mosaic_cover': False,
+          # one mosaic across coordinate systems (warp.py): mosaic_crs None = one mosaic per coordinate system, 'first' = the first
+          # chip's, or 'EPSG:n' (UTM zones, 3857, 4326); mosaic_resolution: the target pixel size, None = the first chip's;
+          # mosaic_resampling: None = nearest for class maps and bilinear for regression, or 'nearest' | 'bilinear'
+          'mosaic_crs': None, 'mosaic_resolution': None, 'mosaic_resampling': None,
           # calibrated probabilities (not in the reference): logits / temperature in front of every softmax consumer (predict_step, the
           # blended tile canvas, the test epoch's ROC-AUC).  temperature: a float > 0, None = 1.0 (nothing is scaled); calibration: the
           # calibration.json of mode=calibrate to take it from (one of the two).  calibration_metrics: mode=eval also logs test_nll /

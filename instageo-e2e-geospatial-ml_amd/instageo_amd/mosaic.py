@@ -16,8 +16,9 @@ counts the contributors, saturating at 255.
 Device tensors go through ``ig_mosaic_paste``; host arrays take a numpy twin of the same rule, so the merge works (and is tested)
 without a GPU.
 
-Not done: reprojection or resampling between grids (chips must share one pixel grid; chips of different coordinate systems become
-separate mosaics, two pixel scales in one are refused), rotated rasters, the reference's RGB ``chips_merged.tif``, multi-band inputs, BigTIFF, a mosaic of
+Not done: reprojection or resampling between grids in this module (chips must share one pixel grid; chips of different coordinate
+systems become separate mosaics, two pixel scales in one are refused; :func:`instageo_amd.warp.merge_reprojected` warps those mosaics
+onto one canvas), rotated rasters, the reference's RGB ``chips_merged.tif``, multi-band inputs, BigTIFF, a mosaic of
 tensors still on the device inside ``chip_inference``, and chip lists built on the device.
 """
 from __future__ import annotations
@@ -268,30 +269,27 @@ def _write_cog_host(canvas: np.ndarray, kind: str, path: str, stats_path: Option
     return path
 
 
-def merge_predictions(paths_or_folder: Union[str, Sequence[str]], output_folder: str, rule: str = "last", fill: int = -1,
-                      num_classes: Optional[int] = None, device: str = "gpu", cog: bool = True, cog_blocksize: int = 256,
-                      overview_levels: Union[str, int] = "auto", cog_compress: Optional[str] = "deflate", min_region: int = 0,
-                      connectivity: int = 4, sieve_passes: int = 8, save_regions: bool = False, save_polygons: bool = False,
-                      zones: Optional[str] = None, zone_id_property: Optional[str] = None, save_cover: bool = False) -> List[str]:
-    """The per-chip ``prediction_*.tif`` files of chip inference -> ``predictions_merged.tif`` (the reference's name), one raster on the
-    chips' common grid.  ``paths_or_folder``: a folder (its ``prediction_*.tif`` files in sorted name order) or a list of files; that
-    order is the chip index of ``rule`` (last | first | mode for int8 class maps, last | first | mean for the float32 files of
-    regression heads), so ``last`` is reproducible.  Chips of several grids (:func:`placement`) give ``predictions_merged_<k>.tif``, k in
-    order of first appearance.  Returns the written paths.
+class _Job(NamedTuple):
+    """What :func:`merge_predictions` knows once its options are checked and its files are read."""
+    opts: Any  # infer_utils.OutputOptions
+    fill: int
+    num_classes: Optional[int]
+    host: bool
+    dev: Optional[str]  # the torch device when not host
+    products: bool
+    paths: List[str]
+    arrays: List[np.ndarray]
+    profiles: List[Dict[str, Any]]
+    regression: bool
+    groups: List[Group]
+    zone_list: Any
+    t: Dict[str, float]  # wall seconds of the phases so far
 
-    The files are read in a pool of at most 8 threads, placed, packed, uploaded and pasted by ``ig_mosaic_paste``; the canvas then takes
-    the way of a tile's class map through the output writer of :mod:`instageo_amd.infer_utils`: the sieve (``min_region``,
-    ``connectivity``, ``sieve_passes``), ``regions_merged.csv`` (``save_regions``), ``polygons_merged.geojson`` (``save_polygons``),
-    ``zones_merged.csv`` (``zones``, ``zone_id_property``), so regions, polygons and zones describe whole objects, not objects cut at
-    chip seams; with ``cog`` the raster is a Cloud Optimized GeoTIFF (``cog_blocksize``, ``overview_levels``, ``cog_compress``; mode
-    overviews that ignore ``fill`` for class maps, NaN-aware mean overviews for floats) and ``cogstats_merged.json`` holds the class
-    histogram in the reference's form, else a strip file.  ``num_classes``: of the model; None = the largest value on the canvas + 1
-    (at least 2).  ``save_cover`` also writes ``cover_merged.tif`` (uint8 strip file: the contributors of every pixel, at most 255).
-    A float32 mosaic has no class products: asking for them raises as in chip inference.  All options are checked before a file is read.
 
-    ``device="cpu"`` pastes and builds the pyramid on the host (the numpy twins of the kernels) and writes the same bytes; the class
-    products run on the device only and are refused there."""
-    from .infer_utils import OutputOptions, _output_path, _write_products, _write_raster, save_prediction
+def _prepare(paths_or_folder, output_folder, rule, fill, num_classes, device, cog, cog_blocksize, overview_levels, cog_compress, min_region,
+             connectivity, sieve_passes, save_regions, save_polygons, zones, zone_id_property) -> _Job:
+    """The first half of :func:`merge_predictions`: every option checked, the files read and placed, the output folder made."""
+    from .infer_utils import OutputOptions
 
     opts = OutputOptions(min_region=min_region, connectivity=connectivity, sieve_passes=sieve_passes, save_regions=save_regions,
                          save_polygons=save_polygons, zones=zones, zone_id_property=zone_id_property, cog=bool(cog),
@@ -333,56 +331,100 @@ def merge_predictions(paths_or_folder: Union[str, Sequence[str]], output_folder:
     zone_list = zonal.read_zones(zones, zone_id_property) if zones is not None else None
     os.makedirs(output_folder, exist_ok=True)
     t = {"read": time.perf_counter() - t0, "paste": 0.0, "products": 0.0, "write": 0.0}
-    if not host:
+    return _Job(opts, fill, None if num_classes is None else int(num_classes), host, None if host else "cuda" if device == "gpu" else device,
+                products, paths, arrays, profiles, regression, groups, zone_list, t)
+
+
+def _paste_group(job: _Job, g: Group, rule: str, save_cover: bool):
+    """The canvas of group ``g`` (and its cover, or None): on the host, or packed, uploaded and pasted by ``ig_mosaic_paste``."""
+    mine = [job.arrays[i] for i in g.members]
+    t0 = time.perf_counter()
+    if job.host:
+        res = paste(mine, g.rects, g.shape, rule, job.fill, save_cover)
+    else:
         import torch
 
         from . import ops
 
-        dev = "cuda" if device == "gpu" else device
-        sync = torch.cuda.synchronize
+        sizes = g.rects[:, 2].astype(np.int64) * g.rects[:, 3]
+        packed = torch.from_numpy(np.concatenate([a.reshape(-1) for a in mine])).to(job.dev)
+        res = ops.mosaic_paste(packed, np.cumsum(sizes) - sizes, g.rects, *bins(g.rects, *g.shape), g.shape, rule, job.fill, save_cover)
+        torch.cuda.synchronize()
+    job.t["paste"] += time.perf_counter() - t0
+    return res if save_cover else (res, None)
+
+
+def _write_canvas(job: _Job, canvas, cover, name: str, profile: Dict[str, Any], output_folder: str) -> List[str]:
+    """One finished canvas (and its cover, or None) -> the class products, the raster, its statistics and the cover file under ``name``
+    -> the written paths."""
+    from .infer_utils import _output_path, _write_products, _write_raster, save_prediction
+
+    opts, fill, host = job.opts, job.fill, job.host
     written: List[str] = []
-    for k, g in enumerate(groups):
-        name = "merged.tif" if len(groups) == 1 else f"merged_{k}.tif"
-        mine = [arrays[i] for i in g.members]
-        t0 = time.perf_counter()
-        if host:
-            res = paste(mine, g.rects, g.shape, rule, fill, save_cover)
-        else:
-            sizes = g.rects[:, 2].astype(np.int64) * g.rects[:, 3]
-            packed = torch.from_numpy(np.concatenate([a.reshape(-1) for a in mine])).to(dev)
-            res = ops.mosaic_paste(packed, np.cumsum(sizes) - sizes, g.rects, *bins(g.rects, *g.shape), g.shape, rule, fill, save_cover)
-            sync()
-        canvas, cover = res if save_cover else (res, None)
-        t["paste"] += time.perf_counter() - t0
-        t0 = time.perf_counter()
-        classes = None
-        if not regression:
-            ncls = int(num_classes) if num_classes is not None else max(2, int(canvas.max()) + 1)
-            classes = (fill, ncls)
-            if products:
-                canvas = _write_products(canvas[None], [(name, g.profile)], output_folder, fill, ncls, opts=opts, zone_list=zone_list)[0]
-                sync()
-                written += [_output_path(name, output_folder, kind, ext) for on, kind, ext in (
-                    (save_regions, "regions", ".csv"), (save_polygons, "polygons", ".geojson"), (zones is not None, "zones", ".csv")) if on]
-        t["products"] += time.perf_counter() - t0
-        t0 = time.perf_counter()
-        kind = "mean" if regression else "mode"
-        stats = _output_path(name, output_folder, "cogstats", ".json")
-        if host and opts.cog:
-            out = _write_cog_host(canvas, kind, _output_path(name, output_folder, "predictions"), stats, g.profile, opts, fill,
-                                  classes[1] if classes else None)
-        elif host:
-            out = save_prediction(canvas, name, output_folder, g.profile, kind="predictions")
-        else:
-            out = _write_raster(canvas, "predictions", kind, g.profile, name, output_folder, opts, classes=classes)
-        written.append(out)
-        if opts.cog and classes is not None and classes[1] <= cogmod.MAX_CLASSES:
-            written.append(stats)
-        if save_cover:
-            tags = {kk: v for kk, v in g.profile["tags"].items() if kk != 42113}
-            cov = cover if host else cover.cpu().numpy()
-            written.append(save_prediction(cov, name, output_folder, dict(g.profile, dtype="uint8", nodata=None, tags=tags), kind="cover"))
-        t["write"] += time.perf_counter() - t0
+    t0 = time.perf_counter()
+    classes = None
+    if not job.regression:
+        ncls = job.num_classes if job.num_classes is not None else max(2, int(canvas.max()) + 1)
+        classes = (fill, ncls)
+        if job.products:
+            import torch
+
+            canvas = _write_products(canvas[None], [(name, profile)], output_folder, fill, ncls, opts=opts, zone_list=job.zone_list)[0]
+            torch.cuda.synchronize()
+            written += [_output_path(name, output_folder, kind, ext) for on, kind, ext in (
+                (opts.save_regions, "regions", ".csv"), (opts.save_polygons, "polygons", ".geojson"), (opts.zones is not None, "zones", ".csv")) if on]
+    job.t["products"] += time.perf_counter() - t0
+    t0 = time.perf_counter()
+    kind = "mean" if job.regression else "mode"
+    stats = _output_path(name, output_folder, "cogstats", ".json")
+    if host and opts.cog:
+        out = _write_cog_host(canvas, kind, _output_path(name, output_folder, "predictions"), stats, profile, opts, fill,
+                              classes[1] if classes else None)
+    elif host:
+        out = save_prediction(canvas, name, output_folder, profile, kind="predictions")
+    else:
+        out = _write_raster(canvas, "predictions", kind, profile, name, output_folder, opts, classes=classes)
+    written.append(out)
+    if opts.cog and classes is not None and classes[1] <= cogmod.MAX_CLASSES:
+        written.append(stats)
+    if cover is not None:
+        tags = {kk: v for kk, v in profile["tags"].items() if kk != 42113}
+        cov = cover if host else cover.cpu().numpy()
+        written.append(save_prediction(cov, name, output_folder, dict(profile, dtype="uint8", nodata=None, tags=tags), kind="cover"))
+    job.t["write"] += time.perf_counter() - t0
+    return written
+
+
+def merge_predictions(paths_or_folder: Union[str, Sequence[str]], output_folder: str, rule: str = "last", fill: int = -1,
+                      num_classes: Optional[int] = None, device: str = "gpu", cog: bool = True, cog_blocksize: int = 256,
+                      overview_levels: Union[str, int] = "auto", cog_compress: Optional[str] = "deflate", min_region: int = 0,
+                      connectivity: int = 4, sieve_passes: int = 8, save_regions: bool = False, save_polygons: bool = False,
+                      zones: Optional[str] = None, zone_id_property: Optional[str] = None, save_cover: bool = False) -> List[str]:
+    """The per-chip ``prediction_*.tif`` files of chip inference -> ``predictions_merged.tif`` (the reference's name), one raster on the
+    chips' common grid.  ``paths_or_folder``: a folder (its ``prediction_*.tif`` files in sorted name order) or a list of files; that
+    order is the chip index of ``rule`` (last | first | mode for int8 class maps, last | first | mean for the float32 files of
+    regression heads), so ``last`` is reproducible.  Chips of several grids (:func:`placement`) give ``predictions_merged_<k>.tif``, k in
+    order of first appearance.  Returns the written paths.
+
+    The files are read in a pool of at most 8 threads, placed, packed, uploaded and pasted by ``ig_mosaic_paste``; the canvas then takes
+    the way of a tile's class map through the output writer of :mod:`instageo_amd.infer_utils`: the sieve (``min_region``,
+    ``connectivity``, ``sieve_passes``), ``regions_merged.csv`` (``save_regions``), ``polygons_merged.geojson`` (``save_polygons``),
+    ``zones_merged.csv`` (``zones``, ``zone_id_property``), so regions, polygons and zones describe whole objects, not objects cut at
+    chip seams; with ``cog`` the raster is a Cloud Optimized GeoTIFF (``cog_blocksize``, ``overview_levels``, ``cog_compress``; mode
+    overviews that ignore ``fill`` for class maps, NaN-aware mean overviews for floats) and ``cogstats_merged.json`` holds the class
+    histogram in the reference's form, else a strip file.  ``num_classes``: of the model; None = the largest value on the canvas + 1
+    (at least 2).  ``save_cover`` also writes ``cover_merged.tif`` (uint8 strip file: the contributors of every pixel, at most 255).
+    A float32 mosaic has no class products: asking for them raises as in chip inference.  All options are checked before a file is read.
+
+    ``device="cpu"`` pastes and builds the pyramid on the host (the numpy twins of the kernels) and writes the same bytes; the class
+    products run on the device only and are refused there."""
+    job = _prepare(paths_or_folder, output_folder, rule, fill, num_classes, device, cog, cog_blocksize, overview_levels, cog_compress, min_region,
+                   connectivity, sieve_passes, save_regions, save_polygons, zones, zone_id_property)
+    written: List[str] = []
+    for k, g in enumerate(job.groups):
+        name = "merged.tif" if len(job.groups) == 1 else f"merged_{k}.tif"
+        canvas, cover = _paste_group(job, g, rule, save_cover)
+        written += _write_canvas(job, canvas, cover, name, g.profile, output_folder)
     TIMINGS.clear()
-    TIMINGS.update(t)
+    TIMINGS.update(job.t)
     return written

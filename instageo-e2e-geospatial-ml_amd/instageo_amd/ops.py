@@ -1168,6 +1168,112 @@ def mosaic_paste(chips, starts, rects, bin_ptr, bin_idx, shape: Tuple[int, int],
     return (dst, cov) if cover else dst
 
 
+WARP_RESAMPLING = {"nearest": 0, "bilinear": 1}  # include/instageo_hip.h
+WARP_RULES = {"last": 0, "first": 1}
+WARP_MAX_SOURCES = 8
+
+
+def _warp_doubles(values, n: int, what: str):
+    import numpy as np
+
+    a = np.ascontiguousarray(values, dtype=np.float64).reshape(-1)
+    if a.shape[0] != n:
+        raise ValueError(f"{what} holds {n} doubles (got {a.shape[0]})")
+    return a
+
+
+def _warp_grid(grid, what: str):
+    import numpy as np
+
+    g = _warp_doubles(grid, 4, what)
+    if not (np.isfinite(g).all() and g[2] > 0 and g[3] > 0):
+        raise ValueError(f"{what} = (X0, Y0, sx, sy) needs finite values and positive pixel sizes (got {tuple(g)})")
+    return g
+
+
+def warp_coords(dst_crs, dst_grid, shape: Tuple[int, int], src_crs, src_grid, device="cuda"):
+    """``ig_warp_coords`` (include/instageo_hip.h): the source pixel coordinates of every pixel centre of the ``shape`` = (H, W)
+    destination grid -> a (2, H, W) float64 tensor (u, v), NaN outside the domain.  ``dst_crs`` / ``src_crs``: five doubles (kind, lon0,
+    k0, FE, FN); ``dst_grid`` / ``src_grid``: (X0, Y0, sx, sy); host values, uploaded here."""
+    import numpy as np
+
+    H, W = int(shape[0]), int(shape[1])
+    if H < 0 or W < 0 or H * W > 2**31 - 1 or -(-H // 4) > 65535:
+        raise ValueError(f"a destination of {H} x {W} pixels is beyond the kernel's limits (H * W <= 2^31 - 1, H <= 262140)")
+    meta = np.concatenate([_warp_doubles(dst_crs, 5, "dst_crs"), _warp_grid(dst_grid, "dst_grid"), _warp_doubles(src_crs, 5, "src_crs"),
+                           _warp_grid(src_grid, "src_grid")])
+    uv = torch.empty((2, H, W), dtype=torch.float64, device=device)
+    if H * W:
+        m = torch.from_numpy(meta).to(uv.device)  # alive until the launch is queued; the copy is stream-ordered
+        _call("ig_warp_coords", 16.0 * H * W, _p(m[0:5]), _p(m[5:9]), H, W, _p(m[9:14]), _p(m[14:18]), _p(uv), _stream())
+    return uv
+
+
+def warp(src, starts, src_crs, src_grid, src_size, bin_ptr, bin_idx, dst_crs, dst_grid, shape: Tuple[int, int], resampling: str = "nearest",
+         rule: str = "last", fill: int = -1, src_id: bool = False, out=None, src_id_out=None):
+    """The warp of ``ig_warp`` (include/instageo_hip.h): ``src`` the packed pixels of all sources, a 1-D int8 or float32 tensor on the
+    device; ``starts`` (n,) int64, ``src_crs`` (n, 5), ``src_grid`` (n, 4) float64, ``src_size`` (n, 2) int32 = (h, w), ``bin_ptr`` /
+    ``bin_idx`` the CSR source lists of the 64 x 64 destination blocks (:func:`instageo_amd.warp.block_lists`), ``dst_crs`` (5,),
+    ``dst_grid`` (4,) as host arrays: they are checked here, so that no source read can leave ``src``, and uploaded.  -> the (H, W)
+    raster of ``src``'s dtype, or (raster, src_id (H, W) uint8) with ``src_id``.  ``out`` / ``src_id_out``: write into these contiguous
+    (H, W) tensors instead of new ones (every pixel is written)."""
+    import numpy as np
+
+    assert src.dim() == 1 and src.dtype in (torch.int8, torch.float32), "src is the packed 1-D int8 or float32 buffer"
+    es = src.element_size()
+    mode, code = WARP_RESAMPLING.get(resampling), WARP_RULES.get(rule)
+    if mode is None or (mode == 1 and es != 4):
+        raise ValueError(f"resampling {resampling!r} does not go with {src.dtype} rasters (int8: nearest, float32: nearest | bilinear)")
+    if code is None:
+        raise ValueError(f"a warp composes its sources by rule last or first (got {rule!r})")
+    if isinstance(fill, bool) or not -128 <= int(fill) <= 127:
+        raise ValueError(f"fill must be an int that fits int8 (got {fill!r})")
+    H, W = int(shape[0]), int(shape[1])
+    if H < 0 or W < 0 or H * W > 2**31 - 1 or -(-H // MOSAIC_BLOCK) > 65535:
+        raise ValueError(f"a destination of {H} x {W} pixels is beyond the kernel's limits (H * W <= 2^31 - 1, H <= 65535 * {MOSAIC_BLOCK})")
+    starts = np.ascontiguousarray(starts, dtype=np.int64).reshape(-1)
+    n = starts.shape[0]
+    if n > WARP_MAX_SOURCES:
+        raise ValueError(f"one launch warps at most {WARP_MAX_SOURCES} sources (got {n})")
+    src_crs = _warp_doubles(src_crs, 5 * n, "src_crs")
+    src_grid = _warp_doubles(src_grid, 4 * n, "src_grid")
+    for i in range(n):
+        _warp_grid(src_grid[4 * i : 4 * i + 4], f"src_grid[{i}]")
+    src_size = np.ascontiguousarray(src_size, dtype=np.int32).reshape(-1, 2)
+    bin_ptr = np.ascontiguousarray(bin_ptr, dtype=np.int32).reshape(-1)
+    bin_idx = np.ascontiguousarray(bin_idx, dtype=np.int32).reshape(-1)
+    dst_crs, dst_grid = _warp_doubles(dst_crs, 5, "dst_crs"), _warp_grid(dst_grid, "dst_grid")
+    blocks = -(-H // MOSAIC_BLOCK) * -(-W // MOSAIC_BLOCK)
+    if src_size.shape[0] != n:
+        raise ValueError(f"{n} starts but {src_size.shape[0]} sizes")
+    if n:
+        h, w = src_size[:, 0].astype(np.int64), src_size[:, 1].astype(np.int64)
+        if (h < 1).any() or (w < 1).any() or max(h.max(), w.max()) > MOSAIC_LIMIT:
+            raise ValueError("a source needs 1 <= h, w <= 2^30")
+        if (starts < 0).any() or (starts + h * w > src.numel()).any():
+            raise ValueError(f"a source's pixels lie outside the packed buffer of {src.numel()} elements")
+        if bin_ptr.shape[0] != blocks + 1 or bin_ptr[0] != 0 or (np.diff(bin_ptr) < 0).any() or bin_ptr[-1] != bin_idx.shape[0]:
+            raise ValueError(f"bin_ptr must hold {blocks} + 1 ascending offsets into bin_idx, from 0 to its length")
+        if bin_idx.size and (bin_idx.min() < 0 or bin_idx.max() >= n):
+            raise ValueError("bin_idx holds a source index outside the sources")
+    dev = src.device
+    dst = out if out is not None else torch.empty((H, W), dtype=src.dtype, device=dev)
+    src_id = src_id or src_id_out is not None
+    sid = src_id_out if src_id_out is not None else torch.empty((H, W), dtype=torch.uint8, device=dev) if src_id else None
+    assert dst.dtype == src.dtype and tuple(dst.shape) == (H, W) and (sid is None or (sid.dtype == torch.uint8 and tuple(sid.shape) == (H, W)))
+    if H * W:
+        # one upload for the float64 descriptions (8-byte aligned slices), one per integer array
+        dbl = torch.from_numpy(np.concatenate([dst_crs, dst_grid, src_crs, src_grid])).to(dev)
+        up = lambda a: torch.from_numpy(a).to(dev) if n else None  # noqa: E731
+        # alive until the launch is queued; an empty list still needs a pointer
+        meta = [up(starts), up(src_size.reshape(-1)), up(bin_ptr), up(bin_idx if bin_idx.size else np.zeros(1, dtype=np.int32))]
+        # HBM bytes: the destination (+ src_id) written, and as many source pixels gathered
+        _call("ig_warp", 2.0 * es * H * W + (H * W if src_id else 0), _p(src) if n else None, _p(meta[0]), _p(dbl[9 : 9 + 5 * n]) if n else None,
+              _p(dbl[9 + 5 * n :]) if n else None, _p(meta[1]), n, _p(meta[2]), _p(meta[3]), _p(dbl[0:5]), _p(dbl[5:9]), H, W, es, mode, code,
+              int(fill), _p(dst), _p(sid), _stream())
+    return (dst, sid) if src_id else dst
+
+
 def confusion_update(y_true, y_pred, confusion, k: int, ignore_index: Optional[int]) -> None:
     assert y_true.dtype == torch.int64 and y_pred.dtype == torch.int64 and confusion.dtype == torch.int64
     _lib.call("ig_confusion_update", _p(y_true), _p(y_pred), _p(confusion), y_true.numel(), k,

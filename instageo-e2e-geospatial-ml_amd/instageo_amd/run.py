@@ -349,6 +349,38 @@ def mosaic_options(cfg: Dict[str, Any]) -> Dict[str, Any]:
     return opts
 
 
+def warp_options(cfg: Dict[str, Any]) -> Dict[str, Any]:
+    """The ``test.mosaic_crs`` / ``mosaic_resolution`` / ``mosaic_resampling`` keys (one mosaic across coordinate systems, warp.py),
+    checked: a bad value raises ValueError, and so do a key without ``test.mosaic=true``, ``bilinear`` with a classification head and
+    ``test.mosaic_cover`` beside ``mosaic_crs``.  ``crs`` None: the mosaic stays one per coordinate system."""
+    from . import crs as crsmod
+    from .warp import RESAMPLING
+
+    t = cfg["test"]
+    none = lambda v: None if v in (None, "None", "none", "null") else v  # noqa: E731
+    opts = dict(crs=none(t.get("mosaic_crs")), resolution=none(t.get("mosaic_resolution")), resampling=none(t.get("mosaic_resampling")))
+    if opts["crs"] is not None and opts["crs"] != "first":
+        if not isinstance(opts["crs"], str):
+            raise ValueError(f"test.mosaic_crs must be None, first or EPSG:<code> (got {opts['crs']!r})")
+        crsmod.parse(opts["crs"])
+    res = opts["resolution"]
+    if res is not None and (isinstance(res, bool) or not isinstance(res, (int, float)) or not 0 < res < float("inf")):
+        raise ValueError(f"test.mosaic_resolution must be None or a positive number (got {res!r})")
+    if opts["resampling"] is not None and opts["resampling"] not in RESAMPLING:
+        raise ValueError(f"test.mosaic_resampling must be None or one of {RESAMPLING} (got {opts['resampling']!r})")
+    for key, name in (("crs", "mosaic_crs"), ("resolution", "mosaic_resolution"), ("resampling", "mosaic_resampling")):
+        if opts[key] is not None and not (t.get("mosaic", False) is True and cfg.get("mode") == "chip_inference"):
+            raise ValueError(f"test.{name} needs test.mosaic=true with mode=chip_inference: it describes the merged raster")
+        if opts[key] is not None and key != "crs" and opts["crs"] is None:
+            raise ValueError(f"test.{name} needs test.mosaic_crs: without it the mosaics stay on their chips' grids")
+    regression = bool(cfg.get("is_reg_task", False)) or cfg["model"].get("num_classes") == 1
+    if opts["resampling"] == "bilinear" and not regression:
+        raise ValueError("test.mosaic_resampling=bilinear does not go with a classification head (classes are not interpolated)")
+    if opts["crs"] is not None and t.get("mosaic_cover", False):
+        raise ValueError("test.mosaic_cover does not go with test.mosaic_crs (contributor counts belong to a group's own grid)")
+    return opts
+
+
 def main(argv: Optional[List[str]] = None) -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--config-name", default="config")
@@ -360,6 +392,7 @@ def main(argv: Optional[List[str]] = None) -> int:
     cfg = load_config(args.config_name, args.overrides, args.config_path)
     cog_options(cfg)  # a bad COG key, or test.cog with mode=chip_inference, stops here: before the model is built
     mosaic = mosaic_options(cfg)  # likewise a bad mosaic key, or test.mosaic outside mode=chip_inference
+    reproject = warp_options(cfg)  # likewise the keys of the reprojected mosaic
     start = time.time()
     torch.manual_seed(SEED)
     np.random.seed(SEED)
@@ -420,11 +453,16 @@ def main(argv: Optional[List[str]] = None) -> int:
                 torch.distributed.barrier()  # every rank's chips are on disk
             if rank == 0:
                 from .mosaic import merge_predictions
+                from .warp import merge_reprojected
 
                 ncls = int(model.net.cfg.num_classes)
                 cog = {k: v for k, v in cog_options(cfg).items() if k != "cog"}
-                merged = merge_predictions(output_dir, output_dir, fill=-1, num_classes=None if ncls == 1 else ncls, device=dev, **mosaic,
-                                           **cog, **region_options(cfg), **polygon_options(cfg), **zone_options(cfg))
+                keys = dict(fill=-1, num_classes=None if ncls == 1 else ncls, device=dev, **mosaic, **cog, **region_options(cfg),
+                            **polygon_options(cfg), **zone_options(cfg))
+                if reproject["crs"] is not None:
+                    merged = merge_reprojected(output_dir, output_dir, **reproject, **keys)
+                else:
+                    merged = merge_predictions(output_dir, output_dir, **keys)
                 print(json.dumps({"mosaic": merged}))
     elif cfg["mode"] == "tile_inference":
         check_required_flags(["root_dir", "test_filepath", "checkpoint_path"], cfg)
