@@ -968,8 +968,10 @@ __global__ void adamw_advance_kernel(float* hyper) {
     if (threadIdx.x == 0 && blockIdx.x == 0) {
         float step = hyper[10] + 1.f;
         hyper[10] = step;
-        hyper[5] = (float)(1.0 - pow((double)hyper[1], (double)step));
-        hyper[6] = (float)sqrt(1.0 - pow((double)hyper[2], (double)step));
+        // beta^step from 1 - beta ([11], [12]: the host rounds the DOUBLE 1 - beta to fp32, relative error 2^-24 of 1 - beta), not from
+        // fp32(beta): that one is off by 2^-24 of beta itself, step times over in the power (beta2 = 0.999 at step 1000: 50 fp32 ulps of [6])
+        hyper[5] = (float)(1.0 - pow(1.0 - (double)hyper[11], (double)step));
+        hyper[6] = (float)sqrt(1.0 - pow(1.0 - (double)hyper[12], (double)step));
     }
 }
 __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,

@@ -990,6 +990,9 @@ __global__ __launch_bounds__(TPB) void softmax_prob_kernel(const float* __restri
 // gradient of the mean squared error (left UN-normalised like the CE kernel: dpred = 2 (pred - label'), divide by stats[1]
 // downstream) and the streaming sums of RunningRegressionMetrics (metrics.py:330-352) on the de-scaled values:
 //   msums = { n, sum x, sum y, sum xy, sum x^2, sum y^2, sum |e|, sum e^2, #(|e| <= ee_bias + ee_coef x) }, x = label, y = prediction
+// Per pixel d, x, y and e are fp32 (the values the reference holds); every PRODUCT is formed in fp64 from the widened operands (exact: two
+// 24-bit significands) and summed in fp64.  The host subtracts n xm^2 from sum x^2 (metrics.py): on offset targets that difference keeps
+// only the low bits of the sums, which an fp32 product would already have rounded away.
 __global__ __launch_bounds__(TPB) void mse_loss_kernel(const float* __restrict__ pred, const float* __restrict__ labels, float ignore_value,
                                                        int use_log, double* __restrict__ stats, float* __restrict__ dpred,
                                                        double* __restrict__ msums, float ee_bias, float ee_coef, int include_ee,
@@ -1004,12 +1007,12 @@ __global__ __launch_bounds__(TPB) void mse_loss_kernel(const float* __restrict__
         const float d = p - t;
         if (dpred) dpred[m] = valid ? 2.f * d : 0.f;
         if (valid) {
-            a[0] += (double)(d * d);
+            a[0] += (double)d * d;
             const float y = use_log ? expm1f(p) : p;   // de-scaled prediction
             const float x = use_log ? expm1f(t) : lab;  // the reference round-trips the label through the scaler too
             const float e = fabsf(y - x);
-            a[1] += 1.0, a[2] += x, a[3] += y, a[4] += (double)(x * y), a[5] += (double)(x * x), a[6] += (double)(y * y);
-            a[7] += e, a[8] += (double)(e * e);
+            a[1] += 1.0, a[2] += x, a[3] += y, a[4] += (double)x * y, a[5] += (double)x * x, a[6] += (double)y * y;
+            a[7] += e, a[8] += (double)e * e;
             if (include_ee && e <= ee_bias + ee_coef * x) a[9] += 1.0;
         }
     }
@@ -1046,7 +1049,7 @@ __global__ __launch_bounds__(TPB) void kd_mse_loss_kernel(const float* __restric
         if (labels[m] == ignore_value) continue;
         const float t = use_log ? log1pf(teacher[m]) : teacher[m];
         const float d = pred[m] - t;
-        a += (double)(d * d);
+        a += (double)d * d;  // fp64 product of the fp32 difference, as in mse_loss_kernel
         if (dpred) dpred[m] += 2.f * d;
     }
 #pragma unroll
