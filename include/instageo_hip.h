@@ -550,6 +550,49 @@ int ig_warp_coords(const double* dst_crs, const double* dst_grid, int H, int W, 
 int ig_warp(const void* src, const long long* starts, const double* src_crs, const double* src_grid, const int* src_size, int nsrc,
             const int* bin_ptr, const int* bin_idx, const double* dst_crs, const double* dst_grid, int H, int W, int elem_size, int resampling,
             int rule, int fill, void* dst, unsigned char* src_id, void* stream);
+/* Chips and label maps cut from a satellite tile (chips.hip; the reference's instageo/data chip creator: apply_mask, decode_fmask_value,
+ * create_segmentation_map, mask_segmentation_map, get_chip_coords and the loop of create_and_save_chips_with_seg_maps).  THE RULE:
+ * tile (T * C, H, W) int16: band b belongs to date b / C.  fmask (T, H, W) uint8, or NULL (no masking).  origins (n, 2) int32 = (row0, col0):
+ *   chip i is the S x S window of the tile with its top-left pixel at (row0, col0); it lies wholly inside the tile, 0 <= row0 <= H - S,
+ *   0 <= col0 <= W - S.  Origins need not be multiples of anything and chips may overlap.
+ * mask_bits: the OR of 1 << position over the requested mask types, positions cloud 1, near_cloud_or_shadow 2, cloud_shadow 3, water 5
+ *   (decode_fmask_value(v, p) = (v >> p) & 1).  Date t is MASKED at a pixel when fmask[t] & mask_bits != 0.
+ *   strategy 0 EACH: the C bands of date t become no_data where date t is masked.  strategy 1 ANY: all T * C bands become no_data where
+ *   any date is masked.  With clip != 0 every value v then becomes min(max(v, clip_lo), clip_hi): clipping comes after masking.
+ * Per chip: chips (n, T * C, S, S) int16, the values by the rule above; valid_values[i] int32 += the number of its values that differ from
+ *   no_data (the caller zeroes it); validity (n, S, S) uint8, or NULL: bit 0 is set when all T * C values of the pixel differ from
+ *   no_data, bit 1 when at least one differs (the reference's `any` and `each` rules of mask_segmentation_map).
+ * Label maps.  A point is (row, col, index) int32: its pixel on the TILE and its original index in the table of P points, whose labels
+ *   (P elements, int16 when elem_size = 2, float32 when 4) are looked up by that index.  The points are grouped by chip in CSR form:
+ *   pts[ptr[i] .. ptr[i + 1]) are those of chip i (ptr: n + 1 int32, ascending from 0); a point that falls in two overlapping chips is
+ *   listed under both.  With (pr, pc) = (row - row0, col - col0), pixel (r, c) of the chip is COVERED by the point when |r - pr| <= w
+ *   and |c - pc| <= w: the window is intersected with the chip and never spills into a neighbouring one.  Among the covering points the one
+ *   with the largest original index WINS (numpy's repeated-index assignment in the reference, made explicit) and the pixel gets its
+ *   label; a pixel with no covering point gets -1; a pixel whose validity bit (valid_bit 1: bit 0, `any`; 2: bit 1, `each`; 0: no
+ *   validity plane) is clear gets -1.  maps (n, S, S) int16 or float32: float labels are copied bit for bit.  valid_labels[i] int32 += the
+ *   pixels != -1; hist (n, K) int32 += for int16 maps the pixels per label in [0, K), K <= 256 (labels outside are not counted); K = 0 or
+ *   hist NULL: no histogram.  The caller zeroes valid_labels and hist.
+ * All results are integers or copies, and unique: the same bits for any launch geometry, run after run.
+ * ig_chip_cut: a gather.  One workgroup of 256 threads owns a block of 16 rows x 128 columns of one chip, a thread 8 consecutive pixels of
+ *   a row.  It reads the T fmask bytes of its pixels once and forms the per-date masks, then streams the T * C values through and stores
+ *   each once; the validity plane comes from the same pass.  The access width is chosen per row segment from the address (16, 8, 4 or 2
+ *   bytes: the row pitch of a 3660-pixel tile is 8 mod 16, so alignment alternates from row to row); a segment that crosses the chip edge
+ *   goes element by element.  valid_values is reduced in the wave and the workgroup and added with one integer atomic per workgroup.
+ *   T <= 32, 1 <= S <= min(H, W), no_data and the clip range fit int16, T * C * S * S <= 2^31 - 1 (valid_values is int32),
+ *   n * T * C * S * S and T * C * H * W below 2^40.  The origins are on
+ *   the device: the caller guarantees them (ops.chip_cut checks them on the host before the upload); a chip whose origin breaks the bounds
+ *   is left unwritten and nothing is read for it, so no read leaves the tile.  n = 0 returns IG_OK without touching a pointer.
+ * ig_chip_labels: one workgroup owns a 64 x 64 block of one chip's label map with an int32 winner plane in LDS (16 KiB) set to -1; its
+ *   threads walk the chip's points, skip those whose window misses the block, and apply an LDS atomic max of the original index over the
+ *   window pixels inside the block; after a barrier each thread resolves winner -> label, applies the validity bit and stores its pixels
+ *   once; valid_labels and the histogram are tallied in LDS and added with integer atomics.  Atomic max and integer adds commute; no
+ *   workgroup waits on another.  0 <= w <= 2^20, 0 <= K <= 256 (K > 0 needs elem_size 2).  A point outside its chip or with an index
+ *   outside [0, P) paints nothing (ops.chip_labels refuses both on the host). */
+int ig_chip_cut(const short* tile, const unsigned char* fmask, const int* origins, int n, int T, int C, int H, int W, int S, int mask_bits,
+                int strategy, int no_data, int clip, int clip_lo, int clip_hi, short* chips, int* valid_values, unsigned char* validity,
+                void* stream);
+int ig_chip_labels(const int* origins, int n, int S, const int* ptr, const int* pts, const void* labels, long P, int elem_size, int w,
+                   const unsigned char* validity, int valid_bit, int K, void* maps, int* valid_labels, int* hist, void* stream);
 int ig_confusion_update(const long long* y_true, const long long* y_pred, unsigned long long* confusion, long n, int k,
                         long ignore_index, int has_ignore, void* stream);
 /* torch.optim.AdamW step on a flat buffer (+ clip_weights, + bf16 shadow refresh)        base.py:103-126 */

@@ -100,7 +100,12 @@ DEFAULTS: Dict[str, Any] = {'root_dir': None,
           'boundary_metrics': False, 'boundary_distances': [1, 2, 4]},
  # mode=calibrate (not in the reference): temperature fit on valid_filepath -- grid points per pass, passes, the first grid's range,
  # bins of the reliability histograms (calibration.py)
- 'calibrate': {'points': 32, 'passes': 2, 't_min': 0.125, 't_max': 8.0, 'nbins': 15}}
+ 'calibrate': {'points': 32, 'passes': 2, 't_min': 0.125, 't_max': 8.0, 'nbins': 15},
+ # mode=create_chips (the reference's instageo/data chip creator under its flag names; chips.py): tiles = the HLS band files ordered per
+ # date and band (B02_0, B03_0, ...), fmasks = one Fmask file per date (None: no masking), records_file = the CSV of x, y, label, date
+ # (None: every complete chip of the grid, for inference), output_directory = where chips/, seg_maps/ and the dataset CSV go
+ 'chips': {'chip_size': 256, 'mask_types': [], 'masking_strategy': 'each', 'window_size': 0, 'task_type': 'seg', 'src_crs': 4326,
+           'tiles': None, 'fmasks': None, 'records_file': None, 'output_directory': None}}
 
 PRESETS: Dict[str, Dict[str, Any]] = {'sen1floods11': {'train': {'batch_size': 16, 'class_weights': [1, 3], 'ignore_index': -1},
                   'model': {'model_name': 'prithvi_eo_v1_100'},

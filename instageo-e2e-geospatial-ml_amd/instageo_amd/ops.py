@@ -1274,6 +1274,59 @@ def warp(src, starts, src_crs, src_grid, src_size, bin_ptr, bin_idx, dst_crs, ds
     return (dst, sid) if src_id else dst
 
 
+def chip_cut(tile, fmask, origins, S: int, T: int, mask_bits: int = 0, strategy: str = "each", no_data_value: int = 0, clip=None):
+    """``ig_chip_cut`` (include/instageo_hip.h): ``tile`` (T * C, H, W) int16 and ``fmask`` (T, H, W) uint8 or None on the device,
+    ``origins`` (n, 2) = (row0, col0) as a host array: it is checked here, so that every chip lies wholly inside the tile, and uploaded.
+    -> (chips (n, T * C, S, S) int16, valid_values (n,) int32, validity (n, S, S) uint8)."""
+    from . import chips as C
+
+    assert tile.dtype == torch.int16 and tile.dim() == 3, "a tile is (T * C, H, W) int16"
+    assert fmask is None or fmask.dtype == torch.uint8, "an Fmask is (T, H, W) uint8"
+    o = C.check_cut(tuple(tile.shape), None if fmask is None else tuple(fmask.shape), origins, S, T, mask_bits, strategy, no_data_value, clip)
+    n, (TC, H, W) = o.shape[0], tile.shape
+    dev = tile.device
+    chips = torch.empty((n, TC, S, S), dtype=torch.int16, device=dev)
+    valid = torch.zeros((n,), dtype=torch.int32, device=dev)
+    plane = torch.empty((n, S, S), dtype=torch.uint8, device=dev)
+    if n:
+        od = torch.from_numpy(o).to(dev)  # alive until the launch is queued; the copy is stream-ordered
+        lo, hi = (int(clip[0]), int(clip[1])) if clip is not None else (0, 0)
+        # HBM bytes: the chips' windows of the tile and the Fmask read, the chips and the validity plane written
+        _call("ig_chip_cut", float(n) * S * S * (4 * TC + (T if fmask is not None else 0) + 1), _p(tile), _p(fmask), _p(od), n, int(T), TC // int(T),
+              H, W, int(S), int(mask_bits), C.STRATEGIES[strategy], int(no_data_value), int(clip is not None), lo, hi, _p(chips), _p(valid),
+              _p(plane), _stream())
+    return chips, valid, plane
+
+
+def chip_labels(origins, S: int, ptr, pts, labels, w: int, validity, valid_bit: int, K: int, device="cuda"):
+    """``ig_chip_labels`` (include/instageo_hip.h): ``origins`` (n, 2), ``ptr`` (n + 1,), ``pts`` (m, 3) = (row, col, original index) and
+    ``labels`` (P,) int16 | float32 as host arrays: they are checked here (ptr monotone, every point inside its chip, every index inside
+    the labels) and uploaded; ``validity`` the (n, S, S) uint8 plane of :func:`chip_cut` on the device, or None with ``valid_bit`` 0.
+    -> (maps (n, S, S) of the labels' dtype, valid_labels (n,) int32, hist (n, K) int32 or None)."""
+    import numpy as np
+
+    from . import chips as C
+
+    labels = np.ascontiguousarray(labels)
+    assert labels.dtype in (np.int16, np.float32) and labels.ndim == 1, "labels is a 1-D int16 or float32 array"
+    task = "seg" if labels.dtype == np.int16 else "reg"
+    strat = {0: None, 1: "any", 2: "each"}[int(valid_bit)]
+    assert (validity is None) == (strat is None), "a validity plane goes with valid_bit 1 or 2"
+    o, p, q = C.check_labels(origins, S, ptr, pts, labels.shape[0], w, K, task, strat)
+    n = o.shape[0]
+    dev = validity.device if validity is not None else torch.device(device)
+    assert validity is None or (validity.dtype == torch.uint8 and tuple(validity.shape) == (n, S, S))
+    maps = torch.empty((n, S, S), dtype=torch.int16 if task == "seg" else torch.float32, device=dev)
+    valid = torch.zeros((n,), dtype=torch.int32, device=dev)
+    hist = torch.zeros((n, K), dtype=torch.int32, device=dev) if K else None
+    if n:
+        up = lambda a: torch.from_numpy(a if a.size else np.zeros(4, dtype=a.dtype)).to(dev)  # noqa: E731  an empty list still needs a pointer
+        meta = [up(o), up(p), up(q.reshape(-1)), up(labels)]  # alive until the launch is queued; the copies are stream-ordered
+        _call("ig_chip_labels", float(n) * S * S * (labels.itemsize + (validity is not None)), _p(meta[0]), n, int(S), _p(meta[1]), _p(meta[2]),
+              _p(meta[3]), labels.shape[0], labels.itemsize, int(w), _p(validity), int(valid_bit), int(K), _p(maps), _p(valid), _p(hist), _stream())
+    return maps, valid, hist
+
+
 def confusion_update(y_true, y_pred, confusion, k: int, ignore_index: Optional[int]) -> None:
     assert y_true.dtype == torch.int64 and y_pred.dtype == torch.int64 and confusion.dtype == torch.int64
     _lib.call("ig_confusion_update", _p(y_true), _p(y_pred), _p(confusion), y_true.numel(), k,

@@ -7,7 +7,8 @@ validation split -> ``calibration.json``; ``calibrate.*``, ``test.temperature`` 
 (whole GeoTIFF tiles -> maps, ``test.blend`` / ``cover_edges`` / ``sigma_scale`` / ``save_probabilities`` / ``tta`` /
 ``save_uncertainty``) is this project's, as are the region keys of both inference modes (``test.min_region`` / ``connectivity`` /
 ``sieve_passes`` / ``save_regions`` / ``save_polygons`` / ``zones``) and the COG keys of ``tile_inference`` (``test.cog`` / ``cog_blocksize`` /
-``overview_levels`` / ``cog_compress``).  Hydra, Lightning and Neptune are replaced by :mod:`instageo_amd.config` and the explicit loop below, which logs the
+``overview_levels`` / ``cog_compress``); ``create_chips`` (``chips.*``: HLS tiles and a table of labelled points -> chips, label maps and
+the dataset CSV the other modes read; the reference's ``instageo/data`` chip creator, :mod:`instageo_amd.chips`) builds no model.  Hydra, Lightning and Neptune are replaced by :mod:`instageo_amd.config` and the explicit loop below, which logs the
 same metric names and writes ``instageo_best_checkpoint.ckpt`` (``{"state_dict": ...}``) on the best
 ``val_IoU`` (pipeline_utils.py:347-355).  Data: ``*_filepath`` may be ``synthetic:<n>`` (on-device HLS-shaped
 chips), an ``.npz`` with ``chips (N,T*C,H,W)`` and ``labels (N,H,W)``, or the reference's own CSV of chip / label GeoTIFF paths
@@ -393,6 +394,10 @@ def main(argv: Optional[List[str]] = None) -> int:
     cog_options(cfg)  # a bad COG key, or test.cog with mode=chip_inference, stops here: before the model is built
     mosaic = mosaic_options(cfg)  # likewise a bad mosaic key, or test.mosaic outside mode=chip_inference
     reproject = warp_options(cfg)  # likewise the keys of the reprojected mosaic
+    if cfg["mode"] == "create_chips":  # no model: HLS tiles + points -> chips, label maps and the dataset CSV (chips.py)
+        from . import chips as chipsmod
+
+        return chipsmod.run_from_config(cfg, "cuda" if torch.cuda.is_available() else None)
     start = time.time()
     torch.manual_seed(SEED)
     np.random.seed(SEED)
