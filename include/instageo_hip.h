@@ -593,6 +593,46 @@ int ig_chip_cut(const short* tile, const unsigned char* fmask, const int* origin
                 void* stream);
 int ig_chip_labels(const int* origins, int n, int S, const int* ptr, const int* pts, const void* labels, long P, int elem_size, int w,
                    const unsigned char* validity, int valid_bit, int K, void* maps, int* valid_labels, int* hist, void* stream);
+/* Dataset cleaning (clean.hip; the reference's instageo/data/data_cleaner.py: should_drop_chip, buffer_observation_pixels,
+ * limit_seg_map_to_observation_pixels).  All results are integers or bit copies, and unique: the same bits for any launch geometry, run
+ * after run.  THE RULE:
+ * No-data planes and counts.  chips (n, B, H, W), 16-bit (int16 or uint16: the comparison is on the 16-bit pattern of no_data, which the
+ *   caller has checked to be representable in the chips' type).  Pixel p of chip i is ANY-no-data when at least one of its B values equals
+ *   no_data, ALL-no-data when all B do.  plane (n, H, W) uint8: bit 0 = any, bit 1 = all.  counts (n, 2) int32 += the chip's any pixels
+ *   (counts[2 i]) and all pixels (counts[2 i + 1]); the caller zeroes it.  A chip is DROPPED when count[strategy] / float(H * W) >
+ *   no_data_threshold, evaluated on the host in float64 (np.mean(mask) > threshold).
+ * Buffer.  labels (n, H, W), int16 (elem_size 2) or float32 (4).  A pixel is a SOURCE when its value != ignore_index, compared in the
+ *   map's type: for float32 a NaN is a source, as in numpy.  Output pixel (r, c) takes the value of the source with the LARGEST ROW-MAJOR
+ *   INDEX r' * W + c' among the sources of the INPUT map with |r - r'| <= w and |c - c'| <= w inside the map; with no such source it keeps
+ *   its input value (which is then ignore_index).  Afterwards a pixel whose plane byte has bit 1 set (all-no-data; plane NULL: no masking)
+ *   becomes ignore_index.  This is the reference's numpy repeated-index assignment made explicit: sources go in np.where order, the later
+ *   assignment wins, and clipping the window to the border only repeats a pixel with the same value.  A source is itself overwritten by a
+ *   later source in its window, and running the buffer twice buffers twice.  Values are copied bit for bit.
+ * Limit.  The points of map i are pts[ptr[i] .. ptr[i + 1]) (ptr: n + 1 int32, ascending from 0 to P; pts (P, 2) int32 = (row, col) on
+ *   the map).  An output pixel keeps its input value where at least one point lies on it and becomes ignore_index elsewhere.  Duplicates
+ *   are harmless; a point outside the map paints nothing.
+ * Both label entry points: out (n, H, W) of the labels' type, distinct from labels; valid_labels[i] int32 += the output pixels !=
+ *   ignore_index; hist (n, K) int32 += for int16 maps the output pixels per value in [0, K), K <= 256 (values outside are not counted);
+ *   K = 0: no histogram, hist may be NULL.  The caller zeroes valid_labels and hist.  ignore_index must be representable in the map's
+ *   type (int16 range; for float32 |ignore_index| <= 2^24).
+ * ig_chip_nodata: a streaming read.  A thread owns 8 consecutive pixels of one chip's plane and walks the B bands: load, compare, OR into
+ *   any, AND into all; it writes its 8 plane bytes once.  The access width of every 8-pixel segment is chosen from its address (16, 8, 4
+ *   or 2 bytes: with H * W odd every second band starts 2-byte aligned); the tail of a plane goes element by element.  The counts are
+ *   summed in the wave and the workgroup and added with one integer atomic pair per workgroup; no workgroup waits on another.  B >= 1,
+ *   H * W <= 2^31 - 1, n * B * H * W < 2^40, -32768 <= no_data <= 65535.  n = 0 returns IG_OK without touching a pointer.
+ * ig_label_buffer: a gather.  One workgroup owns a 64 x 64 block of one map.  It stages the source flags of the block plus a halo of w
+ *   into LDS (outside the map: no source), a row pass gives every staged row and block column the right-most source column within +-w
+ *   (or -1), and the column pass takes the bottom-most staged row within +-w that has a hit: the largest row-major index.  A thread
+ *   resolves 16 pixels: the winner's value from global memory, the plane's bit 1, one store, valid_labels and the histogram tallied in LDS
+ *   and added with integer atomics.  0 <= w <= 32 (w = 0 is only the masking), H, W <= 2^30, n * H * W < 2^40.
+ * ig_label_limit: the same block ownership with a 4096-bit mask in LDS: a thread takes every 256th point of the map's list and sets the
+ *   bit of a point inside the block with an LDS atomic OR; after the barrier the pixels are resolved and tallied as above.  The caller
+ *   guarantees ptr (ops.label_limit checks it on the host); list bounds are clamped to [0, P] all the same, so no read leaves pts. */
+int ig_chip_nodata(const void* chips, int n, int B, int H, int W, int no_data, unsigned char* plane, int* counts, void* stream);
+int ig_label_buffer(const void* labels, int n, int H, int W, int elem_size, int w, int ignore_index, const unsigned char* plane, int K,
+                    void* out, int* valid_labels, int* hist, void* stream);
+int ig_label_limit(const void* labels, int n, int H, int W, int elem_size, const int* ptr, const int* pts, long P, int ignore_index, int K,
+                   void* out, int* valid_labels, int* hist, void* stream);
 int ig_confusion_update(const long long* y_true, const long long* y_pred, unsigned long long* confusion, long n, int k,
                         long ignore_index, int has_ignore, void* stream);
 /* torch.optim.AdamW step on a flat buffer (+ clip_weights, + bf16 shadow refresh)        base.py:103-126 */

@@ -17,6 +17,7 @@
 // host checks origins before they are uploaded, this is the second fence), every pixel access is guarded by row < S and column < S, a
 // point outside its chip or with an index outside [0, P) paints nothing, and a label outside [0, K) is not counted.
 #include "common.h"
+#include "pixel_seg.h"
 
 namespace {
 
@@ -24,95 +25,6 @@ constexpr int CB_H = 16, CB_W = 128, CSEG = 8, CTPB = 256;  // block rows, block
 constexpr int MAX_T = 32;                                   // dates: one bit each in the per-pixel date mask
 constexpr int LB = 64, LTPB = 256, MAX_K = 256;             // label block side, threads, histogram cells
 constexpr int MAX_W = 1 << 20;
-
-// N elements of E bytes each from / to p in the widest units the address allows
-template <int BYTES>
-__device__ __forceinline__ void load_seg(const void* p, void* v) {
-    const unsigned a = (unsigned)reinterpret_cast<uintptr_t>(p);
-    const char* s = static_cast<const char*>(p);
-    char* d = static_cast<char*>(v);
-    if (BYTES >= 16 && (a & 15) == 0) {
-#pragma unroll
-        for (int q = 0; q < BYTES / 16; ++q) {
-            const uint4 u = *reinterpret_cast<const uint4*>(s + 16 * q);
-            __builtin_memcpy(d + 16 * q, &u, 16);
-        }
-    } else if ((a & 7) == 0) {
-#pragma unroll
-        for (int q = 0; q < BYTES / 8; ++q) {
-            const uint2 u = *reinterpret_cast<const uint2*>(s + 8 * q);
-            __builtin_memcpy(d + 8 * q, &u, 8);
-        }
-    } else if ((a & 3) == 0) {
-#pragma unroll
-        for (int q = 0; q < BYTES / 4; ++q) {
-            const unsigned u = *reinterpret_cast<const unsigned*>(s + 4 * q);
-            __builtin_memcpy(d + 4 * q, &u, 4);
-        }
-    } else if ((a & 1) == 0) {
-#pragma unroll
-        for (int q = 0; q < BYTES / 2; ++q) {
-            const unsigned short u = *reinterpret_cast<const unsigned short*>(s + 2 * q);
-            __builtin_memcpy(d + 2 * q, &u, 2);
-        }
-    } else {
-#pragma unroll
-        for (int q = 0; q < BYTES; ++q) d[q] = s[q];
-    }
-}
-
-template <int BYTES>
-__device__ __forceinline__ void store_seg(void* p, const void* v) {
-    const unsigned a = (unsigned)reinterpret_cast<uintptr_t>(p);
-    char* d = static_cast<char*>(p);
-    const char* s = static_cast<const char*>(v);
-    if (BYTES >= 16 && (a & 15) == 0) {
-#pragma unroll
-        for (int q = 0; q < BYTES / 16; ++q) {
-            uint4 u;
-            __builtin_memcpy(&u, s + 16 * q, 16);
-            *reinterpret_cast<uint4*>(d + 16 * q) = u;
-        }
-    } else if ((a & 7) == 0) {
-#pragma unroll
-        for (int q = 0; q < BYTES / 8; ++q) {
-            uint2 u;
-            __builtin_memcpy(&u, s + 8 * q, 8);
-            *reinterpret_cast<uint2*>(d + 8 * q) = u;
-        }
-    } else if ((a & 3) == 0) {
-#pragma unroll
-        for (int q = 0; q < BYTES / 4; ++q) {
-            unsigned u;
-            __builtin_memcpy(&u, s + 4 * q, 4);
-            *reinterpret_cast<unsigned*>(d + 4 * q) = u;
-        }
-    } else if ((a & 1) == 0) {
-#pragma unroll
-        for (int q = 0; q < BYTES / 2; ++q) {
-            unsigned short u;
-            __builtin_memcpy(&u, s + 2 * q, 2);
-            *reinterpret_cast<unsigned short*>(d + 2 * q) = u;
-        }
-    } else {
-#pragma unroll
-        for (int q = 0; q < BYTES; ++q) d[q] = s[q];
-    }
-}
-
-__device__ __forceinline__ int wave_sum_int(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// the workgroup's sum of v (4 waves) -> thread 0
-__device__ __forceinline__ int block_sum_int(int v, int* part) {
-    v = wave_sum_int(v);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return part[0] + part[1] + part[2] + part[3];
-}
 
 struct CutArgs {
     int T, C, H, W, S, mask_bits, any, no_data, clip, lo, hi, bx, by;  // bx, by: blocks across and down one chip

@@ -105,7 +105,15 @@ DEFAULTS: Dict[str, Any] = {'root_dir': None,
  # date and band (B02_0, B03_0, ...), fmasks = one Fmask file per date (None: no masking), records_file = the CSV of x, y, label, date
  # (None: every complete chip of the grid, for inference), output_directory = where chips/, seg_maps/ and the dataset CSV go
  'chips': {'chip_size': 256, 'mask_types': [], 'masking_strategy': 'each', 'window_size': 0, 'task_type': 'seg', 'src_crs': 4326,
-           'tiles': None, 'fmasks': None, 'records_file': None, 'output_directory': None}}
+           'tiles': None, 'fmasks': None, 'records_file': None, 'output_directory': None},
+ # mode=clean_chips (the reference's instageo/data/data_cleaner.py under its flag names; clean.py): drop the chips of chips_dataset_csv
+ # whose share of no-data pixels is above the threshold, buffer the observation pixels of the label maps by window_size (or limit the maps
+ # to the pixels of observation_points_csv), write output_chips_dataset_csv and clean_stats.json.  Not in the reference: num_classes
+ # (cells of the class histogram; None: the largest label + 1) and root_dir (where relative paths of the CSV start; None: the CSV's folder)
+ 'clean': {'chips_dataset_csv': None, 'output_chips_dataset_csv': None, 'drop_chips': False, 'drop_chips_strategy': 'any',
+           'no_data_threshold': 0.5, 'no_data_value': -9999, 'clean_seg_maps': False, 'cleaning_method': 'buffer',
+           'observation_points_csv': None, 'seg_map_output_dir': None, 'ignore_index': -1, 'window_size': 1, 'num_classes': None,
+           'root_dir': None}}
 
 PRESETS: Dict[str, Dict[str, Any]] = {'sen1floods11': {'train': {'batch_size': 16, 'class_weights': [1, 3], 'ignore_index': -1},
                   'model': {'model_name': 'prithvi_eo_v1_100'},

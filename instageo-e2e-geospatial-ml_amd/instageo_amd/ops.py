@@ -1327,6 +1327,68 @@ def chip_labels(origins, S: int, ptr, pts, labels, w: int, validity, valid_bit: 
     return maps, valid, hist
 
 
+def chip_nodata(chips, no_data_value: int):
+    """``ig_chip_nodata`` (include/instageo_hip.h): ``chips`` (n, B, H, W) int16 | uint16 on the device -> (plane (n, H, W) uint8: bit 0
+    any, bit 1 all; counts (n, 2) int32).  A ``no_data_value`` the chips' dtype cannot hold matches nothing: zeros without a launch."""
+    from . import clean as C
+
+    assert chips.dim() == 4 and chips.dtype in (torch.int16, torch.uint16), "chips is (n, B, H, W) int16 or uint16"
+    n, B, H, W = chips.shape
+    pattern = C.check_nodata((n, B, H, W), "int16" if chips.dtype == torch.int16 else "uint16", no_data_value)
+    plane = torch.zeros((n, H, W), dtype=torch.uint8, device=chips.device)
+    counts = torch.zeros((n, 2), dtype=torch.int32, device=chips.device)
+    if n and pattern is not None:
+        # HBM bytes: the chips read once, the plane written
+        _call("ig_chip_nodata", float(n) * H * W * (2 * B + 1), _p(chips), n, B, H, W, pattern, _p(plane), _p(counts), _stream())
+    return plane, counts
+
+
+def _label_outputs(labels, K: int):
+    assert labels.dim() == 3 and labels.dtype in (torch.int16, torch.float32), "labels is (n, H, W) int16 or float32"
+    n = labels.shape[0]
+    out = torch.empty_like(labels)
+    valid = torch.zeros((n,), dtype=torch.int32, device=labels.device)
+    hist = torch.zeros((n, K), dtype=torch.int32, device=labels.device) if K else None
+    return out, valid, hist
+
+
+def label_buffer(labels, w: int, ignore_index: int, plane=None, K: int = 0):
+    """``ig_label_buffer`` (include/instageo_hip.h): ``labels`` (n, H, W) int16 | float32 and ``plane`` (n, H, W) uint8 of
+    :func:`chip_nodata` (or None: no masking) on the device -> (out like labels, valid_labels (n,) int32, hist (n, K) int32 or None)."""
+    from . import clean as C
+
+    out, valid, hist = _label_outputs(labels, K)
+    n, H, W = labels.shape
+    C.check_label_args((n, H, W), "int16" if labels.dtype == torch.int16 else "float32", ignore_index, K, w)
+    assert plane is None or (plane.dtype == torch.uint8 and plane.shape == labels.shape and plane.device == labels.device)
+    if n and H and W:
+        es = labels.element_size()
+        _call("ig_label_buffer", float(n) * H * W * (2 * es + (plane is not None)), _p(labels), n, H, W, es, int(w), int(ignore_index), _p(plane),
+              int(K), _p(out), _p(valid), _p(hist), _stream())
+    return out, valid, hist
+
+
+def label_limit(labels, ptr, pts, ignore_index: int, K: int = 0):
+    """``ig_label_limit`` (include/instageo_hip.h): ``labels`` (n, H, W) int16 | float32 on the device, ``ptr`` (n + 1,) and ``pts``
+    (P, 2) = (row, col) as host arrays: ptr is checked here and the points outside their map are dropped, then both are uploaded.
+    -> (out like labels, valid_labels (n,) int32, hist (n, K) int32 or None)."""
+    import numpy as np
+
+    from . import clean as C
+
+    out, valid, hist = _label_outputs(labels, K)
+    n, H, W = labels.shape
+    C.check_label_args((n, H, W), "int16" if labels.dtype == torch.int16 else "float32", ignore_index, K)
+    p, q = C.check_points(n, H, W, ptr, pts)
+    if n and H and W:
+        up = lambda a: torch.from_numpy(a if a.size else np.zeros(4, dtype=a.dtype)).to(labels.device)  # noqa: E731  an empty list still needs a pointer
+        meta = [up(p), up(q.reshape(-1))]  # alive until the launch is queued; the copies are stream-ordered
+        es = labels.element_size()
+        _call("ig_label_limit", float(n) * H * W * 2 * es, _p(labels), n, H, W, es, _p(meta[0]), _p(meta[1]), q.shape[0], int(ignore_index),
+              int(K), _p(out), _p(valid), _p(hist), _stream())
+    return out, valid, hist
+
+
 def confusion_update(y_true, y_pred, confusion, k: int, ignore_index: Optional[int]) -> None:
     assert y_true.dtype == torch.int64 and y_pred.dtype == torch.int64 and confusion.dtype == torch.int64
     _lib.call("ig_confusion_update", _p(y_true), _p(y_pred), _p(confusion), y_true.numel(), k,

@@ -8,7 +8,9 @@ validation split -> ``calibration.json``; ``calibrate.*``, ``test.temperature`` 
 ``save_uncertainty``) is this project's, as are the region keys of both inference modes (``test.min_region`` / ``connectivity`` /
 ``sieve_passes`` / ``save_regions`` / ``save_polygons`` / ``zones``) and the COG keys of ``tile_inference`` (``test.cog`` / ``cog_blocksize`` /
 ``overview_levels`` / ``cog_compress``); ``create_chips`` (``chips.*``: HLS tiles and a table of labelled points -> chips, label maps and
-the dataset CSV the other modes read; the reference's ``instageo/data`` chip creator, :mod:`instageo_amd.chips`) builds no model.  Hydra, Lightning and Neptune are replaced by :mod:`instageo_amd.config` and the explicit loop below, which logs the
+the dataset CSV the other modes read; the reference's ``instageo/data`` chip creator, :mod:`instageo_amd.chips`) and ``clean_chips``
+(``clean.*``: the reference's ``data_cleaner.py``: the no-data chip filter and label buffering / limiting, :mod:`instageo_amd.clean`) build
+no model.  Hydra, Lightning and Neptune are replaced by :mod:`instageo_amd.config` and the explicit loop below, which logs the
 same metric names and writes ``instageo_best_checkpoint.ckpt`` (``{"state_dict": ...}``) on the best
 ``val_IoU`` (pipeline_utils.py:347-355).  Data: ``*_filepath`` may be ``synthetic:<n>`` (on-device HLS-shaped
 chips), an ``.npz`` with ``chips (N,T*C,H,W)`` and ``labels (N,H,W)``, or the reference's own CSV of chip / label GeoTIFF paths
@@ -398,6 +400,10 @@ def main(argv: Optional[List[str]] = None) -> int:
         from . import chips as chipsmod
 
         return chipsmod.run_from_config(cfg, "cuda" if torch.cuda.is_available() else None)
+    if cfg["mode"] == "clean_chips":  # no model: drop no-data chips, buffer / limit the label maps of a chip dataset (clean.py)
+        from . import clean as cleanmod
+
+        return cleanmod.run_from_config(cfg, "cuda" if torch.cuda.is_available() else None)
     start = time.time()
     torch.manual_seed(SEED)
     np.random.seed(SEED)

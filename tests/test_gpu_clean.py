@@ -1,0 +1,171 @@
+"""Dataset cleaning on the device (-m gpu): ``ig_chip_nodata``, ``ig_label_buffer`` and ``ig_label_limit`` against the sequential twin of
+the rule (tests/clean_reference.py), run-to-run determinism, and clean_data on the device against the host path, file for file.  Every
+comparison is ``torch.equal``: all outputs are integers or bit copies."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import clean_reference as R
+from instageo_amd import _lib, clean
+from test_cpu_clean import write_dataset
+
+pytestmark = pytest.mark.gpu
+
+
+def _same(got, want):
+    for g, w in zip(got, want):
+        if w is None:
+            assert g is None
+            continue
+        w = torch.from_numpy(w)
+        assert g.is_cuda and g.dtype == w.dtype and torch.equal(g.cpu(), w)
+
+
+def _dev(a):
+    return torch.from_numpy(a).cuda()
+
+
+# (1, 1, 1, 1); an odd plane, so chips and bands start 2-byte aligned; 18 bands; several workgroups per chip
+@pytest.mark.parametrize("n,B,H,W", [(1, 1, 1, 1), (3, 5, 33, 31), (2, 18, 64, 64), (2, 6, 130, 70)])
+def test_chip_nodata_equals_the_twin(n, B, H, W):
+    chips = R.make_chips(n, B, H, W, -9999, seed=n + B + H)
+    want = R.nodata(chips, -9999)
+    if H > 1:
+        assert (want[0] == 1).any() and (want[0] == 3).any() and want[0][n - 1, H - 1, W - 1] == 3  # any != all, all, the last pixel
+    got = clean.nodata_planes(_dev(chips), -9999)
+    _same(got, want)
+    again = clean.nodata_planes(_dev(chips), -9999)
+    assert all(torch.equal(a, b) for a, b in zip(got, again))
+
+
+def test_chip_nodata_uint16_pattern_and_unrepresentable_values():
+    chips = R.make_chips(2, 3, 33, 31, 65535, seed=5, dtype=np.uint16)
+    want = R.nodata(chips, 65535)
+    assert want[1][:, 1].min() > 0
+    _same(clean.nodata_planes(_dev(chips), 65535), want)
+    # -1 has the same 16-bit pattern as 65535 but is not a uint16 value; 40000 is not an int16 value: both match nothing
+    for a, nd in ((chips, -1), (chips.view(np.int16), 40000)):
+        plane, counts = clean.nodata_planes(_dev(a), nd)
+        assert plane.is_cuda and not plane.any() and not counts.any()
+    _same(clean.nodata_planes(_dev(chips.view(np.int16)), -1), want)
+
+
+SHAPES = [(64, 64), (65, 130), (129, 66)]
+WINDOWS = [0, 1, 2, 5, 32]
+DENSITIES = ["one", 0.02, 0.5]
+
+
+@pytest.mark.parametrize("shape", SHAPES)
+@pytest.mark.parametrize("w", WINDOWS)
+def test_label_buffer_equals_the_twin(shape, w):
+    H, W = shape
+    density = DENSITIES[(WINDOWS.index(w) + SHAPES.index(shape)) % 3]
+    for dens, ign, K in ((density, -1, 7), (0.02 if density != 0.02 else 0.5, 255, 0)):
+        labels = R.make_labels(1, H, W, dens, seed=H + w, ign=ign)
+        got = clean.buffer_labels(_dev(labels), w, ign, None, K)
+        _same(got, R.buffer(labels, w, ign, None, K))
+        again = clean.buffer_labels(_dev(labels), w, ign, None, K)
+        assert all(a is None and b is None or torch.equal(a, b) for a, b in zip(got, again))
+
+
+def test_label_buffer_map_smaller_than_the_window():
+    labels = np.full((2, 3, 3), -1, dtype=np.int16)
+    labels[0, 0, 0], labels[0, 2, 1], labels[1, 1, 1] = 1, 2, 3
+    got = clean.buffer_labels(_dev(labels), 5, -1, None, 7)
+    _same(got, R.buffer(labels, 5, -1, None, 7))
+    assert (got[0][0] == 2).all() and (got[0][1] == 3).all()
+
+
+def test_label_buffer_adjacent_sources_the_later_one_wins_both_pixels():
+    labels = np.full((1, 65, 130), -1, dtype=np.int16)
+    labels[0, 10, 63:65] = (1, 2)  # across a block seam
+    labels[0, 63:65, 100] = (3, 4)
+    got = clean.buffer_labels(_dev(labels), 1, -1)
+    _same(got, R.buffer(labels, 1, -1))
+    out = got[0][0].cpu()
+    assert out[10, 63] == 2 and out[10, 64] == 2 and out[63, 100] == 4 and out[64, 100] == 4
+
+
+@pytest.mark.parametrize("w", [1, 32])
+def test_label_buffer_batch_with_a_plane_that_masks_sources(w):
+    H, W = 65, 130
+    labels = R.make_labels(3, H, W, 0.02, seed=9)
+    rng = np.random.default_rng(3)
+    plane = rng.integers(0, 4, size=(3, H, W)).astype(np.uint8)
+    plane[0][labels[0] != -1] |= 2  # every source of map 0 lies on an all-no-data pixel: it still spreads, then is masked itself
+    want = R.buffer(labels, w, -1, plane, 7)
+    assert (want[0][0][labels[0] != -1] == -1).all() and want[1][0] > 0
+    _same(clean.buffer_labels(_dev(labels), w, -1, _dev(plane), 7), want)
+
+
+def test_label_buffer_float32_with_a_nan_source_bit_for_bit():
+    labels = R.make_labels(1, 65, 66, 0.02, seed=2, dtype=np.float32) + np.float32(0.25)
+    labels[labels == np.float32(-0.75)] = -1
+    labels[0, 61:65, 9:14] = -1  # the window of (63, 11)
+    labels[0, 64, 10] = np.nan
+    labels[0, 20, 64] = np.float32(-0.0)
+    want = R.buffer(labels, 2, -1)
+    got = clean.buffer_labels(_dev(labels), 2, -1)
+    assert np.isnan(want[0][0, 63, 11])
+    assert torch.equal(got[0].cpu().view(torch.int32), torch.from_numpy(want[0].view(np.int32)))
+    _same(got[1:], want[1:])
+
+
+def _limit_case():
+    H, W = 65, 130
+    labels = R.make_labels(3, H, W, 0.5, seed=4)
+    pts0 = R.seam_sources(H, W) + [(H - 1, W - 1), (3, 3), (3, 3), (3, 3)]  # seams, the last pixel, duplicates
+    rng = np.random.default_rng(8)
+    pts2 = [(int(rng.integers(0, H)), int(rng.integers(0, W))) for _ in range(600)]  # more points than threads
+    ptr = np.array([0, len(pts0), len(pts0), len(pts0) + len(pts2)], dtype=np.int32)  # map 1: an empty list
+    return labels, ptr, np.array(pts0 + pts2, dtype=np.int32)
+
+
+def test_label_limit_equals_the_twin():
+    labels, ptr, pts = _limit_case()
+    for K in (7, 0):
+        got = clean.limit_labels(_dev(labels), ptr, pts, -1, K)
+        want = R.limit(labels, ptr, pts, -1, K)
+        _same(got, want)
+    assert want[1][1] == 0 and want[1][0] > 0
+    f = labels.astype(np.float32)
+    _same(clean.limit_labels(_dev(f), ptr, pts, -1), R.limit(f, ptr, pts, -1))
+
+
+def test_label_limit_kernel_ignores_points_outside_the_map():
+    """Points outside the map handed straight to the entry point (the host wrapper would drop them): they paint nothing."""
+    labels, ptr, pts = _limit_case()
+    H, W = labels.shape[1:]
+    bad = np.array([(-1, 5), (5, -1), (H, 0), (0, W), (2**31 - 1, 2**31 - 1), (-(2**31), 0), (H - 1, W)], dtype=np.int32)
+    pts = np.concatenate([bad, pts]).astype(np.int32)
+    ptr = (ptr + np.array([0, len(bad), len(bad), len(bad)])).astype(np.int32)
+    lab, p, q = _dev(labels), _dev(ptr), _dev(pts.reshape(-1))
+    out = torch.empty_like(lab)
+    valid = torch.zeros(3, dtype=torch.int32, device="cuda")
+    hist = torch.zeros((3, 7), dtype=torch.int32, device="cuda")
+    _lib.call("ig_label_limit", lab.data_ptr(), 3, H, W, 2, p.data_ptr(), q.data_ptr(), pts.shape[0], -1, 7, out.data_ptr(), valid.data_ptr(),
+              hist.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    _same((out, valid, hist), R.limit(labels, ptr, pts, -1, 7))
+
+
+def test_clean_data_on_the_device_writes_the_bytes_of_the_host_path(tmp_path):
+    outs = {}
+    for dev in (None, "cuda"):
+        for method in ("buffer", "limit"):
+            root = str(tmp_path / f"{method}_{dev}")
+            csv, obs = write_dataset(root)
+            clean.clean_data(csv, os.path.join(root, "clean.csv"), drop_chips=True, drop_chips_strategy="all", no_data_threshold=0.5,
+                             clean_seg_maps=True, cleaning_method=method, observation_points_csv=obs, window_size=2,
+                             seg_map_output_dir=os.path.join(root, "cleaned"), device=dev)
+            outs[(method, dev)] = root
+    for method in ("buffer", "limit"):
+        a, b = outs[(method, None)], outs[(method, "cuda")]
+        count = 0
+        for folder, _, names in os.walk(a):
+            for n in names:
+                pa = os.path.join(folder, n)
+                assert open(pa, "rb").read() == open(os.path.join(b, os.path.relpath(pa, a)), "rb").read(), n
+                count += 1
+        assert count >= 6
