@@ -593,6 +593,42 @@ int ig_chip_cut(const short* tile, const unsigned char* fmask, const int* origin
                 void* stream);
 int ig_chip_labels(const int* origins, int n, int S, const int* ptr, const int* pts, const void* labels, long P, int elem_size, int w,
                    const unsigned char* validity, int valid_bit, int K, void* maps, int* valid_labels, int* hist, void* stream);
+/* Chips warped onto label grids (raster_chips.hip; the reference's instageo/data/raster_chip_creator.py: HLSRasterPipeline.process_row on
+ * a stack that stackstac has resampled onto the label's coordinate system and resolution, geo_utils.slice_xr_dataset, apply_mask,
+ * mask_segmentation_map).  THE RULE:
+ * tile (T * C, H, W) int16 and fmask (T, H, W) uint8 or NULL as for ig_chip_cut.  src_crs (5 doubles) and src_grid (4 doubles) describe
+ *   the stack, dst_crs (5 doubles) the one coordinate system of the n chips, dst_grids (n, 4) doubles the grid of every chip, all ON THE
+ *   DEVICE and exactly as ig_warp defines coordinate systems and grids.  Every chip is S x S.
+ * The centre of pixel (r, c) of chip i has the source coordinates (u, v) by the chain of ig_warp / ig_warp_coords: where the five doubles
+ *   of the two systems are equal the affine arithmetic alone, otherwise inverse projection of dst_crs and forward projection of src_crs,
+ *   (NaN, NaN) outside the domain.  NEAREST: cs = floor(u), rs = floor(v), tested on the float64 values.  When 0 <= rs < H and
+ *   0 <= cs < W the pixel takes the T * C values and the T Fmask bytes of source pixel (rs, cs); otherwise (NaN included) it takes no_data
+ *   in every band and Fmask 0 (stackstac's fill_value).  A destination grid, or a source grid, whose values are not finite or whose pixel
+ *   sizes are not positive gives a chip that is no_data everywhere; no read leaves the tile.
+ * Then the rule of ig_chip_cut applies unchanged: date t is masked where fmask[t] & mask_bits != 0, strategy 0 EACH / 1 ANY, the clip
+ *   after the masking, chips (n, T * C, S, S) int16, valid_values[i] += the values that differ from no_data, validity (n, S, S) uint8 or
+ *   NULL with bit 0 = all values of the pixel differ from no_data, bit 1 = at least one does.
+ * Label maps go through the same pass.  labels (n, S, S), int8 (elem_size 1) or float32 (elem_size 4), or NULL (then maps, valid_labels
+ *   and hist are not touched).  The output pixel is the input pixel, bit for bit, except that it becomes -1 when valid_bit != 0 and the
+ *   pixel's validity bit is clear (valid_bit 1: bit 0, `any`; 2: bit 1, `each`; 0: no label masking, the reference's qa_check = false),
+ *   or when it is a float32 NaN (the reference's where(~isnan, -1)).  valid_labels[i] int32 += the output pixels != -1; hist (n, K) int32
+ *   += for int8 maps the output pixels per value in [0, K), K <= 128 (values outside are not counted); K = 0: no histogram, hist may be
+ *   NULL.  The caller zeroes valid_values, valid_labels and hist.
+ * All results are integers or copies, and unique: the same bits for any launch geometry, run after run.
+ * ig_chip_warp: a gather, one launch for all n chips.  One workgroup of 256 threads owns a 64 x 64 block of one chip (the blocking of
+ *   ig_warp and ig_chip_labels); a wave owns 64 consecutive pixels of a row and stores them with one instruction, a thread takes 16 rows.
+ *   A thread evaluates the float64 chain ONCE per pixel and keeps the source offset rs * W + cs (int32, -1 for none) of its 16 pixels in
+ *   registers, gathers their T Fmask bytes into one 32-bit date mask per pixel, then streams the T * C bands: gather, mask, clip, one
+ *   store.  The validity byte and the label pixel come from the same registers.  valid_values and valid_labels are summed in the wave
+ *   and the workgroup, the histogram in LDS, and added with integer atomics, one set per workgroup; no workgroup waits on another.
+ *   1 <= T <= 32, C >= 1, 1 <= S <= 2^15, H * W <= 2^31 - 1, T * C * S * S <= 2^31 - 1 (valid_values is int32), n * T * C * S * S < 2^40,
+ *   no_data and the clip range fit int16, elem_size 1 or 4 (also without labels), 0 <= K <= 128 and K > 0 needs elem_size 1 and labels,
+ *   valid_bit 0, 1 or 2.  tile, chips 2-byte, the int32 arrays and float32 labels / maps 4-byte, the float64 arrays 8-byte aligned.
+ *   n = 0 returns IG_OK without touching a pointer. */
+int ig_chip_warp(const short* tile, const unsigned char* fmask, const double* src_crs, const double* src_grid, const double* dst_crs,
+                 const double* dst_grids, int n, int T, int C, int H, int W, int S, int mask_bits, int strategy, int no_data, int clip,
+                 int clip_lo, int clip_hi, const void* labels, int elem_size, int valid_bit, int K, short* chips, int* valid_values,
+                 unsigned char* validity, void* maps, int* valid_labels, int* hist, void* stream);
 /* Dataset cleaning (clean.hip; the reference's instageo/data/data_cleaner.py: should_drop_chip, buffer_observation_pixels,
  * limit_seg_map_to_observation_pixels).  All results are integers or bit copies, and unique: the same bits for any launch geometry, run
  * after run.  THE RULE:

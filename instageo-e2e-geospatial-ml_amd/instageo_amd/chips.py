@@ -21,8 +21,8 @@ but paints only when it lies inside the chip's pixel-centre bounds ([centre of t
 the first row, centre of the last row]), because the reference filters a chip's points with ``chip["x"].min() <= x <= chip["x"].max()``
 on pixel-centre coordinates.  A point in the outer half-pixel fringe of a chip therefore selects the chip without labelling it.
 
-Not done: STAC search and download, S2 / S1 sources, the label-raster pipeline (``process_row`` with a label file), resampling a tile to
-another resolution, MGRS tile lookup, rotated rasters, and CSR point lists built on the device.
+Not done: STAC search and download, S2 / S1 sources, MGRS tile lookup, rotated rasters, and CSR point lists built on the device.  The
+label-raster pipeline, which resamples a tile to another grid, is :mod:`instageo_amd.raster_chips`.
 """
 from __future__ import annotations
 

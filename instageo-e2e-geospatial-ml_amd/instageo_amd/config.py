@@ -106,6 +106,14 @@ DEFAULTS: Dict[str, Any] = {'root_dir': None,
  # (None: every complete chip of the grid, for inference), output_directory = where chips/, seg_maps/ and the dataset CSV go
  'chips': {'chip_size': 256, 'mask_types': [], 'masking_strategy': 'each', 'window_size': 0, 'task_type': 'seg', 'src_crs': 4326,
            'tiles': None, 'fmasks': None, 'records_file': None, 'output_directory': None},
+ # mode=create_raster_chips (the reference's instageo/data/raster_chip_creator.py under its flag names; raster_chips.py): every label is a
+ # raster of chip_size x chip_size pixels in EPSG:src_crs at spatial_resolution, listed in records_file (a CSV of label_filename, date
+ # [, mgrs_tile_id]) and found under raster_path; the stack of tiles / fmasks is resampled onto each label's grid.  is_bbox_feature: no
+ # labels, chips over the boxes of the JSON list bbox_feature_path, named by date.  Not in the reference: snap (true: the lattice of
+ # multiples of spatial_resolution, as stackstac resamples; false: the label raster's own grid)
+ 'raster_chips': {'tiles': None, 'fmasks': None, 'records_file': None, 'raster_path': None, 'output_directory': None, 'chip_size': 256,
+                  'mask_types': [], 'masking_strategy': 'each', 'src_crs': 4326, 'spatial_resolution': 0.0002694945852358564,
+                  'qa_check': True, 'task_type': 'seg', 'is_bbox_feature': False, 'bbox_feature_path': None, 'date': None, 'snap': True},
  # mode=clean_chips (the reference's instageo/data/data_cleaner.py under its flag names; clean.py): drop the chips of chips_dataset_csv
  # whose share of no-data pixels is above the threshold, buffer the observation pixels of the label maps by window_size (or limit the maps
  # to the pixels of observation_points_csv), write output_chips_dataset_csv and clean_stats.json.  Not in the reference: num_classes

@@ -1327,6 +1327,59 @@ def chip_labels(origins, S: int, ptr, pts, labels, w: int, validity, valid_bit: 
     return maps, valid, hist
 
 
+def chip_warp(tile, fmask, src_crs, src_grid, dst_crs, dst_grids, S: int, T: int, mask_bits: int = 0, strategy: str = "each",
+              no_data_value: int = 0, clip=None, labels=None, valid_bit: int = 0, K: int = 0, out=None):
+    """``ig_chip_warp`` (include/instageo_hip.h): ``tile`` (T * C, H, W) int16 and ``fmask`` (T, H, W) uint8 or None on the device;
+    ``src_crs`` / ``dst_crs`` five doubles, ``src_grid`` (X0, Y0, sx, sy) and ``dst_grids`` (n, 4) as host values: they are checked here,
+    before the upload.  ``labels``: None, or (n, S, S) int8 | float32 as a device tensor or a host array.  -> (chips (n, T * C, S, S)
+    int16, valid_values (n,) int32, validity (n, S, S) uint8, maps, valid_labels, hist): the last three None without labels, hist None
+    with K = 0.  ``out``: a dict with any of ``chips``, ``validity``, ``maps``: contiguous tensors to write into instead of new ones
+    (every element is written)."""
+    import numpy as np
+
+    from . import raster_chips as R
+
+    assert tile.dtype == torch.int16 and tile.dim() == 3, "a tile is (T * C, H, W) int16"
+    assert fmask is None or fmask.dtype == torch.uint8, "an Fmask is (T, H, W) uint8"
+    lab_dtype = None if labels is None else str(labels.dtype).replace("torch.", "")
+    sc, sg, dc, dg = R.check_warp(tuple(tile.shape), None if fmask is None else tuple(fmask.shape), src_crs, src_grid, dst_crs, dst_grids, S, T,
+                                  mask_bits, strategy, no_data_value, clip, None if labels is None else tuple(labels.shape), lab_dtype,
+                                  valid_bit, K)
+    n, (TC, H, W), S = dg.shape[0], tile.shape, int(S)
+    dev = tile.device
+    out = dict(out or {})
+    if labels is not None and not torch.is_tensor(labels):
+        labels = torch.from_numpy(np.ascontiguousarray(labels))
+    if labels is not None:
+        labels = labels.to(dev)
+    chips = out.pop("chips", None)
+    plane = out.pop("validity", None)
+    maps = out.pop("maps", None)
+    assert not out, f"unknown outputs {sorted(out)}"
+    chips = chips if chips is not None else torch.empty((n, TC, S, S), dtype=torch.int16, device=dev)
+    plane = plane if plane is not None else torch.empty((n, S, S), dtype=torch.uint8, device=dev)
+    assert chips.dtype == torch.int16 and tuple(chips.shape) == (n, TC, S, S) and plane.dtype == torch.uint8 and tuple(plane.shape) == (n, S, S)
+    valid = torch.zeros((n,), dtype=torch.int32, device=dev)
+    valid_labels = hist = None
+    if labels is not None:
+        maps = maps if maps is not None else torch.empty_like(labels)
+        assert maps.dtype == labels.dtype and tuple(maps.shape) == (n, S, S)
+        valid_labels = torch.zeros((n,), dtype=torch.int32, device=dev)
+        hist = torch.zeros((n, K), dtype=torch.int32, device=dev) if K else None
+    else:
+        maps = None
+    if n:
+        dbl = torch.from_numpy(np.concatenate([sc, sg, dc, dg.reshape(-1)])).to(dev)  # one upload; every slice 8-byte aligned
+        lo, hi = (int(clip[0]), int(clip[1])) if clip is not None else (0, 0)
+        es = labels.element_size() if labels is not None else 1
+        # HBM bytes: as many tile values and Fmask bytes gathered as chip values written, the validity plane, the labels in and out
+        work = float(n) * S * S * (4 * TC + (T if fmask is not None else 0) + 1 + (2 * es if labels is not None else 0))
+        _call("ig_chip_warp", work, _p(tile), _p(fmask), _p(dbl[0:5]), _p(dbl[5:9]), _p(dbl[9:14]), _p(dbl[14:]), n, int(T), TC // int(T), H, W, S,
+              int(mask_bits), R.STRATEGIES[strategy], int(no_data_value), int(clip is not None), lo, hi, _p(labels), es, int(valid_bit), int(K),
+              _p(chips), _p(valid), _p(plane), _p(maps), _p(valid_labels), _p(hist), _stream())
+    return chips, valid, plane, maps, valid_labels, hist
+
+
 def chip_nodata(chips, no_data_value: int):
     """``ig_chip_nodata`` (include/instageo_hip.h): ``chips`` (n, B, H, W) int16 | uint16 on the device -> (plane (n, H, W) uint8: bit 0
     any, bit 1 all; counts (n, 2) int32).  A ``no_data_value`` the chips' dtype cannot hold matches nothing: zeros without a launch."""

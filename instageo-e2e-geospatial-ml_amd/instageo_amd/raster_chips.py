@@ -1,0 +1,534 @@
+"""Chips cut against label rasters: the granule stack warped onto every label's grid, on the device.
+
+The reference's second way into a dataset is ``instageo/data/raster_chip_creator.py`` with ``HLSRasterPipeline.process_row`` and
+``geo_utils.slice_xr_dataset`` / ``create_grid_polygons``: every label is itself a small raster (``label_*.tif`` / ``mask_*.tif`` of
+``chip_size`` x ``chip_size`` pixels in the user's coordinate system and resolution); stackstac resamples the satellite stack onto that
+system and resolution (nearest neighbour), and the chip is sliced, masked, clipped and quality-checked against the label.  With
+``is_bbox_feature`` the same code cuts label-free inference chips over bounding boxes.  This module is the stand-in on
+:mod:`instageo_amd.tiff`, :mod:`instageo_amd.crs` and the kernel of ``raster_chips.hip``.
+
+The rule (stated in ``include/instageo_hip.h``).  The centre of every pixel of a chip's S x S destination grid is mapped into the
+stack's grid by the chain of the warp (:mod:`instageo_amd.warp`); it takes the T * C values and T Fmask bytes of the source pixel
+(floor(v), floor(u)), or ``no_data_value`` and Fmask 0 outside the tile; then the rule of :func:`instageo_amd.chips.cut` applies
+unchanged (masking, ``each`` / ``any``, clip, ``valid_values``, the validity plane).  A label map keeps its pixels except where its
+validity bit is clear, or where a float label is NaN: those become -1.
+
+Device tensors go through ``ig_chip_warp``; host arrays take a numpy twin of the same rule, so the module works (and is tested) without a
+GPU.
+
+The destination grid of a record.  ``snap=True`` (the reference): stackstac snaps the resampled stack to the lattice of multiples of
+``spatial_resolution`` and ``slice_xr_dataset`` takes S pixels from the lattice cell that holds the top-left corner of the record's
+bounds, so X = res * floor(minx / res), Y = res * ceil(maxy / res), in float64 on the host.  ``snap=False``: the label raster's own
+grid.  Either way the written chip and label carry the label raster's georeferencing (the reference's ``xr.align(join="override")``).
+
+Not done: S2 / S1 sources and SCL masks, STAC search and download, GeoPackage records (a CSV stands in), bilinear / cubic resampling of
+reflectances, rotated rasters.
+"""
+from __future__ import annotations
+
+import json
+import os
+from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
+
+import numpy as np
+
+from . import chips as chipsmod
+from . import crs as crsmod
+from . import tiff, warp
+from .chips import STRATEGIES, VALID_BITS, mask_bits
+
+MAX_DATES = 32
+MAX_SIDE = 1 << 15
+MAX_CLASSES = 128  # cells of the class histogram: every non-negative int8
+HLS_NO_DATA = 0  # the reference's NO_DATA_VALUES.HLS
+SEG_NO_DATA = -1
+_GEO_TAGS = (33550, 33922, 34735, 34736, 34737)
+_BATCH_VALUES = 1 << 28  # chip values of one launch
+
+
+def _params(c) -> np.ndarray:
+    """A coordinate system (EPSG code, :class:`crs.Crs` or five doubles) -> its five doubles."""
+    if isinstance(c, (int, np.integer)) and not isinstance(c, bool):
+        c = crsmod.from_epsg(int(c))
+    a = np.ascontiguousarray(tuple(c)[:5], dtype=np.float64).reshape(-1)
+    if a.shape[0] != 5:
+        raise ValueError(f"a coordinate system is five doubles (got {a.shape[0]})")
+    return a
+
+
+def _grid_ok(g) -> bool:
+    return bool(np.isfinite(g).all() and g[2] > 0 and g[3] > 0)
+
+
+# ---- argument checks shared by the host path and ops.chip_warp ------------------------------------------------------------------------------
+def check_warp(tile_shape, fmask_shape, src_crs, src_grid, dst_crs, dst_grids, S: int, T: int, bits: int, strategy: str, no_data_value: int,
+               clip, labels_shape, labels_dtype, valid_bit: int, K: int):
+    """ValueError unless the arguments of a warped cut obey include/instageo_hip.h -> (src_crs (5,), src_grid (4,), dst_crs (5,),
+    dst_grids (n, 4)) as float64 arrays.  A destination grid may be unusable (it gives a no-data chip); the stack's grid may not."""
+    if len(tile_shape) != 3:
+        raise ValueError(f"a tile is (T * C, H, W) (got shape {tuple(tile_shape)})")
+    TC, H, W = (int(v) for v in tile_shape)
+    if isinstance(S, bool) or not isinstance(S, (int, np.integer)) or not 1 <= int(S) <= MAX_SIDE:
+        raise ValueError(f"chip_size must be an int in [1, 2^15] (got {S!r})")
+    S = int(S)
+    if not 1 <= T <= MAX_DATES or TC % T or TC < 1:
+        raise ValueError(f"{TC} bands do not divide into {T} dates (1 <= dates <= {MAX_DATES})")
+    if fmask_shape is not None and tuple(fmask_shape) != (T, H, W):
+        raise ValueError(f"fmask must be (T, H, W) = {(T, H, W)} (got {tuple(fmask_shape)})")
+    if H < 1 or W < 1 or H * W > 2**31 - 1:
+        raise ValueError(f"a tile of {H} x {W} pixels is beyond 2^31 - 1 (source offsets are int32)")
+    if TC * S * S > 2**31 - 1:
+        raise ValueError(f"a chip of {TC} x {S} x {S} values is beyond 2^31 - 1 (valid_values is int32)")
+    if not 0 <= int(bits) <= 255:
+        raise ValueError(f"mask_bits must be a byte (got {bits!r})")
+    if strategy not in STRATEGIES:
+        raise ValueError(f"masking_strategy must be one of {tuple(STRATEGIES)} (got {strategy!r})")
+    if not -32768 <= int(no_data_value) <= 32767:
+        raise ValueError(f"no_data_value must fit int16 (got {no_data_value!r})")
+    if clip is not None and not (len(clip) == 2 and -32768 <= int(clip[0]) <= int(clip[1]) <= 32767):
+        raise ValueError(f"clip must be None or (lo, hi) inside int16 with lo <= hi (got {clip!r})")
+    sg = np.ascontiguousarray(src_grid, dtype=np.float64).reshape(-1)
+    if sg.shape[0] != 4 or not _grid_ok(sg):
+        raise ValueError(f"src_grid = (X0, Y0, sx, sy) needs finite values and positive pixel sizes (got {tuple(sg)})")
+    dg = np.ascontiguousarray(dst_grids, dtype=np.float64)
+    if dg.size % 4:
+        raise ValueError(f"dst_grids is (n, 4) = (X0, Y0, sx, sy) per chip (got shape {dg.shape})")
+    dg = dg.reshape(-1, 4)
+    n = dg.shape[0]
+    if n * TC * S * S >= 2**40:
+        raise ValueError(f"{n} chips of {TC} x {S} x {S} values are beyond 2^40")
+    if valid_bit not in (0, 1, 2):
+        raise ValueError(f"valid_bit must be 0 none, 1 any or 2 each (got {valid_bit!r})")
+    if isinstance(K, bool) or not 0 <= int(K) <= MAX_CLASSES:
+        raise ValueError(f"a class histogram has 0 <= K <= {MAX_CLASSES} cells (got {K!r})")
+    if labels_shape is None:
+        if K:
+            raise ValueError("a class histogram needs labels")
+    else:
+        if tuple(labels_shape) != (n, S, S):
+            raise ValueError(f"labels must be (n, S, S) = {(n, S, S)} (got {tuple(labels_shape)})")
+        if str(labels_dtype) not in ("int8", "float32"):
+            raise ValueError(f"labels are int8 (seg) or float32 (reg) (got {labels_dtype})")
+        if K and str(labels_dtype) != "int8":
+            raise ValueError(f"a class histogram (K = {K}) needs int8 labels")
+    return _params(src_crs), sg, _params(dst_crs), dg
+
+
+# ---- the rule on host arrays ---------------------------------------------------------------------------------------------------------------
+def _warp_host(tile, fmask, sc, sg, dc, dg, S, T, bits, strategy, nd, clip, labels, bit, K):
+    """numpy twin of ``ig_chip_warp``: chip by chip, vectorised over the pixels."""
+    TC, H, W = tile.shape
+    C = TC // T
+    n = dg.shape[0]
+    chips = np.empty((n, TC, S, S), dtype=np.int16)
+    validity = np.empty((n, S, S), dtype=np.uint8)
+    for i in range(n):
+        a = np.full((TC, S, S), nd, dtype=np.int16)
+        f = np.zeros((T, S, S), dtype=np.uint8)
+        if _grid_ok(dg[i]):
+            u, v = warp.coords(dc, dg[i], (S, S), sc, sg)
+            with np.errstate(invalid="ignore"):
+                fc, fr = np.floor(u), np.floor(v)
+                inside = (fc >= 0) & (fc < W) & (fr >= 0) & (fr < H)
+            rs, cs = fr[inside].astype(np.int64), fc[inside].astype(np.int64)
+            a[:, inside] = tile[:, rs, cs]
+            if fmask is not None:
+                f[:, inside] = fmask[:, rs, cs]
+        if fmask is not None and bits:
+            m = (f & np.uint8(bits)) != 0
+            m = np.broadcast_to(m.any(axis=0), (TC, S, S)) if strategy == "any" else np.repeat(m, C, axis=0)
+            a[m] = nd
+        if clip is not None:
+            np.clip(a, clip[0], clip[1], out=a)
+        ok = a != nd
+        chips[i] = a
+        validity[i] = ok.all(axis=0).astype(np.uint8) | (ok.any(axis=0).astype(np.uint8) << 1)
+    valid_values = (chips != np.int16(nd)).reshape(n, -1).sum(axis=1).astype(np.int32)
+    maps = valid_labels = hist = None
+    if labels is not None:
+        maps = labels.copy()
+        blank = (validity & bit) == 0 if bit else np.zeros(maps.shape, dtype=bool)
+        if maps.dtype == np.float32:
+            blank = blank | np.isnan(maps)
+        maps[blank] = SEG_NO_DATA
+        live = maps != SEG_NO_DATA
+        valid_labels = live.reshape(n, -1).sum(axis=1).astype(np.int32)
+        if K:
+            hist = np.zeros((n, K), dtype=np.int32)
+            for i in range(n):
+                x = maps[i][live[i]].astype(np.int64)
+                hist[i] = np.bincount(x[(x >= 0) & (x < K)], minlength=K)
+    return chips, valid_values, validity, maps, valid_labels, hist
+
+
+def warp_cut(tile, fmask, src_crs, src_grid, dst_crs, dst_grids, chip_size: int, dates: Optional[int] = None,
+             mask: Union[int, Sequence[str]] = 0, strategy: str = "each", no_data_value: int = 0, clip: Optional[Tuple[int, int]] = None,
+             labels=None, label_strategy: Optional[str] = None, num_classes: int = 0):
+    """The stack ``tile`` ((T * C, H, W) int16, with ``fmask`` (T, H, W) uint8 or None) in ``src_crs`` on ``src_grid`` = (X0, Y0, sx, sy),
+    resampled (nearest) onto the n grids ``dst_grids`` ((n, 4)) of side ``chip_size`` in ``dst_crs``, masked and clipped by the rule of the
+    module docstring -> (chips (n, T * C, S, S) int16, valid_values (n,) int32, validity (n, S, S) uint8, maps, valid_labels, hist).
+    A coordinate system is an EPSG code, a :class:`crs.Crs` or five doubles.  ``labels``: None, or (n, S, S) int8 (``seg``) | float32
+    (``reg``): ``maps`` are the labels with -1 where the validity bit of ``label_strategy`` (any | each | None: no masking) is clear and
+    where a float label is NaN, ``valid_labels`` (n,) int32 the pixels != -1, ``hist`` (n, num_classes) int32 (int8 only; None with 0
+    classes).  Without labels the last three are None.  Tensors on the device go through ``ig_chip_warp`` and give device tensors;
+    anything else takes the numpy twin and gives arrays."""
+    bits = mask if isinstance(mask, (int, np.integer)) and not isinstance(mask, bool) else mask_bits(mask)
+    T = int(dates) if dates is not None else (int(fmask.shape[0]) if fmask is not None else 1)
+    if label_strategy not in VALID_BITS:
+        raise ValueError(f"label_strategy must be any, each or None (got {label_strategy!r})")
+    bit = VALID_BITS[label_strategy] if labels is not None else 0
+    dev = chipsmod._is_device(tile)
+    name = lambda a: str(a.dtype).replace("torch.", "")  # noqa: E731
+    if not dev:
+        tile = np.asarray(tile.cpu() if hasattr(tile, "cpu") else tile)
+        fmask = None if fmask is None else np.asarray(fmask.cpu() if hasattr(fmask, "cpu") else fmask)
+        labels = None if labels is None else np.ascontiguousarray(labels.cpu() if hasattr(labels, "cpu") else labels)
+    if name(tile) != "int16" or (fmask is not None and name(fmask) != "uint8"):
+        raise ValueError("a tile is int16 and an Fmask uint8")
+    if dev:
+        from . import ops
+
+        return ops.chip_warp(tile, fmask, src_crs, src_grid, dst_crs, dst_grids, chip_size, T, bits, strategy, no_data_value, clip, labels, bit,
+                             int(num_classes))  # checks the same arguments before the upload
+    sc, sg, dc, dg = check_warp(tuple(tile.shape), None if fmask is None else tuple(fmask.shape), src_crs, src_grid, dst_crs, dst_grids, chip_size,
+                                T, bits, strategy, no_data_value, clip, None if labels is None else tuple(labels.shape),
+                                None if labels is None else name(labels), bit, num_classes)
+    return _warp_host(tile, fmask, sc, sg, dc, dg, int(chip_size), T, int(bits), strategy, int(no_data_value), clip, labels, bit, int(num_classes))
+
+
+# ---- records and grids (float64 on the host) -------------------------------------------------------------------------------------------------
+def complete_chips_coords(coord_min: float, coord_max: float, spatial_resolution: float, chip_size: int, max_bound: float) -> np.ndarray:
+    """The reference's ``get_complete_chips_coords``: the pixel coordinates of as many whole chips as cover [coord_min, coord_max], one
+    chip fewer when they would reach beyond ``max_bound``."""
+    n_chips = int(np.ceil((coord_max - coord_min) / (spatial_resolution * chip_size)))
+    n_pixels = n_chips * chip_size
+    if coord_min + n_pixels * spatial_resolution > max_bound:
+        n_pixels = (n_chips - 1) * chip_size
+    return np.arange(coord_min, coord_min + n_pixels * spatial_resolution, spatial_resolution)
+
+
+def grid_polygons(bbox_list, date: str, chip_size: int, spatial_resolution: float) -> List[Dict[str, Any]]:
+    """The reference's ``create_grid_polygons`` on plain numpy: every [x_min, y_min, x_max, y_max] of ``bbox_list`` is covered with whole
+    chips from its lower left corner (reduced by one chip where they would pass 180 / 90) -> records ``{"label_filename":
+    "label_x{x}_y{y}_{date}.tif", "date", "bounds": (minx, miny, maxx, maxy)}``, x outer and y inner as in the reference.  The bounds
+    are those of the chip's pixel COORDINATES (``get_extent``), S - 1 pixel steps wide; chip y counts upwards from y_min."""
+    S = int(chip_size)
+    out: List[Dict[str, Any]] = []
+    for bbox in bbox_list:
+        x_min, y_min, x_max, y_max = (float(v) for v in bbox)
+        xs = complete_chips_coords(x_min, x_max, spatial_resolution, S, 180)
+        ys = complete_chips_coords(y_min, y_max, spatial_resolution, S, 90)
+        for x in range(len(xs) // S):
+            for y in range(len(ys) // S):
+                cx, cy = xs[x * S : (x + 1) * S], ys[y * S : (y + 1) * S]
+                out.append({"label_filename": f"label_x{x}_y{y}_{date}.tif", "date": date,
+                            "bounds": (float(cx.min()), float(cy.min()), float(cx.max()), float(cy.max()))})
+    return out
+
+
+def snapped_grid(bounds, spatial_resolution: float) -> Tuple[float, float, float, float]:
+    """The destination grid of a record with ``bounds`` = (minx, miny, maxx, maxy) under ``snap=True`` (the module docstring)."""
+    res = float(spatial_resolution)
+    return (float(res * np.floor(bounds[0] / res)), float(res * np.ceil(bounds[3] / res)), res, res)
+
+
+def chip_names(label_filename: str, mgrs_tile_id: str) -> Tuple[str, str]:
+    """The reference's names: ``<label stem>_<mgrs_tile_id>.tif`` for the label map and the same with ``mask -> merged`` and
+    ``label -> chip`` for the chip -> (chip name, label name)."""
+    stem = f"{os.path.splitext(os.path.basename(str(label_filename)))[0]}_{mgrs_tile_id}"
+    return stem.replace("mask", "merged").replace("label", "chip") + ".tif", stem + ".tif"
+
+
+def mgrs_of(first_tile_file: str) -> str:
+    """Field 2 of an HLS file name (``HLS.S30.T38PMB.2022145T072619.v2.0.B02.tif`` -> ``T38PMB``)."""
+    parts = os.path.basename(str(first_tile_file)).split(".")
+    if len(parts) < 4:
+        raise ValueError(f"{first_tile_file}: not an HLS file name (HLS.<sensor>.<tile>.<date>...)")
+    return parts[2]
+
+
+def _read_records(records) -> List[Dict[str, Any]]:
+    import pandas as pd
+
+    df = pd.read_csv(records, dtype={"mgrs_tile_id": str}) if isinstance(records, (str, os.PathLike)) else pd.DataFrame(records)
+    for col in ("label_filename", "date"):
+        if col not in df.columns:
+            raise ValueError(f"the records table needs the columns label_filename and date (no {col!r})")
+    rows = []
+    for _, r in df.iterrows():
+        tid = r["mgrs_tile_id"] if "mgrs_tile_id" in df.columns and isinstance(r["mgrs_tile_id"], str) and r["mgrs_tile_id"] else None
+        rows.append({"label_filename": str(r["label_filename"]), "date": r["date"], "mgrs_tile_id": tid})
+    return rows
+
+
+def _touches(dc, grid, S: int, sc, sg, H: int, W: int) -> bool:
+    """Whether the chip of ``grid`` can reach the tile: a 9 x 9 lattice over its extent, projected on the host; its box in source pixels,
+    grown by one, against the tile.  A lattice wholly outside the domain cannot."""
+    coarse = (grid[0], grid[1], grid[2] * S / 8.0, grid[3] * S / 8.0)
+    u, v = warp.coords(dc, coarse, (8, 8), sc, sg, at="corners")
+    if np.isnan(u).all():
+        return False
+    return bool(np.nanmax(u) + 1 >= 0 and np.nanmin(u) - 1 < W and np.nanmax(v) + 1 >= 0 and np.nanmin(v) - 1 < H)
+
+
+def _seg_labels(a: np.ndarray, name: str) -> np.ndarray:
+    if a.dtype.kind == "f":
+        a = np.where(np.isnan(a), SEG_NO_DATA, a)
+    if a.size and ((a != np.round(a)).any() or a.min() < -128 or a.max() > 127):
+        raise ValueError(f"{name}: seg labels must be integers that fit int8")
+    return a.astype(np.int8)
+
+
+def _to_host(a):
+    return a.cpu().numpy() if hasattr(a, "cpu") else a
+
+
+def create_raster_chips(tile_files: Sequence[str], fmask_files: Optional[Sequence[str]], records, raster_path: Optional[str],
+                        output_directory: str, chip_size: int = 256, mask_types: Sequence[str] = (), masking_strategy: str = "each",
+                        src_crs: int = 4326, spatial_resolution: float = 0.0002694945852358564, qa_check: bool = True, task_type: str = "seg",
+                        is_bbox_feature: bool = False, bbox_feature_path: Optional[str] = None, date: Optional[str] = None, snap: bool = True,
+                        device: Optional[str] = None) -> Tuple[List[str], List[Optional[str]]]:
+    """The reference's raster chip creator (``process_row``) for every record that touches one granule stack.  ``tile_files``: the HLS
+    band files ordered per date and band, one Fmask file per date in ``fmask_files`` (read only when ``mask_types`` asks for masks).
+    ``records``: a CSV path or a table with ``label_filename``, ``date`` and optionally ``mgrs_tile_id`` (default: field 2 of the HLS
+    file name; a record that names another tile is left to that tile's run); the label rasters lie under ``raster_path``, S x S pixels
+    in EPSG:``src_crs`` (a raster whose GeoKeys name another system raises ValueError); the geometry of a record is the bounds of its
+    raster, from the file's own tiepoint and scale.  ``snap`` selects the destination grid (the module docstring).
+
+    Writes ``chips/<chip name>`` (all bands, clipped to [0, 10000], uint16) and ``seg_maps/<label name>`` (int8 for ``seg``, float32 for
+    ``reg``, NaN -> -1) under ``output_directory`` with the names of :func:`chip_names`, both with the label raster's georeferencing.  A
+    record whose files both exist is skipped and still listed; a label raster that is not S x S is skipped (``invalid_shape``); a record
+    whose raster misses the tile entirely is not cut (``outside_tile``); with ``qa_check`` a chip with ``valid_values == 0`` is dropped,
+    then, after the label map was masked by the chip's validity (``masking_strategy``), a pair with ``valid_labels == 0``.
+    ``chips_dataset.csv`` gains the pairs and ``raster_chips_stats.json`` holds the counts by reason, the class histogram and its
+    ``compute_class_weights``.  -> (chip names, label-map names).
+
+    ``is_bbox_feature``: no labels; the records are :func:`grid_polygons` of the JSON list of boxes in ``bbox_feature_path`` (``date``:
+    the date of the names, by default that of the HLS file name); chips only, with the georeferencing of their destination grid
+    (``snap=False``: the box lattice itself, pixel (0, 0) of chip y at the top of its S rows); an existing chip is skipped and listed.
+    ``device``: None = the numpy path, ``"cuda"`` / ``"cuda:n"`` = the kernel; both write the same bytes."""
+    S = int(chip_size)
+    bits = mask_bits(mask_types)
+    if masking_strategy not in STRATEGIES:
+        raise ValueError(f"masking_strategy must be one of {tuple(STRATEGIES)} (got {masking_strategy!r})")
+    if task_type not in ("seg", "reg"):
+        raise ValueError(f"task_type must be seg or reg (got {task_type!r})")
+    if device is not None and not str(device).startswith("cuda"):
+        raise ValueError(f"device must be None (host) or a cuda device (got {device!r})")
+    if not tile_files:
+        raise ValueError("create_raster_chips needs at least one tile file")
+    if bits and not fmask_files:
+        raise ValueError("mask_types needs fmask_files")
+    res = float(spatial_resolution)
+    if not 0 < res < np.inf:
+        raise ValueError(f"spatial_resolution must be a positive number (got {spatial_resolution!r})")
+    dst = crsmod.from_epsg(src_crs)
+    T = len(fmask_files) if fmask_files else 1
+    if len(tile_files) % T:
+        raise ValueError(f"{len(tile_files)} band files do not divide into {T} dates")
+    tile, profile = chipsmod._read_stack(tile_files, "tile", np.int16)
+    fmask = chipsmod._read_stack(fmask_files, "Fmask", np.uint8)[0] if bits else None
+    H, W = tile.shape[1:]
+    src = crsmod.from_profile(profile)
+    sgrid = warp.grid_of(profile, str(tile_files[0]))
+    own_id = mgrs_of(tile_files[0])
+    bbox = bool(is_bbox_feature)
+    if bbox:
+        if not bbox_feature_path:
+            raise ValueError("is_bbox_feature needs bbox_feature_path")
+        with open(bbox_feature_path) as f:
+            rows = grid_polygons(json.load(f), date or chipsmod._date_of_name(tile_files[0]), S, res)
+        for r in rows:
+            r["mgrs_tile_id"] = None
+    else:
+        if raster_path is None:
+            raise ValueError("label records need raster_path")
+        rows = _read_records(records)
+    reasons = ("other_tile", "existing", "invalid_shape", "outside_tile", "no_valid_values", "no_valid_labels")
+    stats: Dict[str, Any] = {"records": len(rows), "kept": 0, "dropped": {k: 0 for k in reasons}}
+    chip_dir, seg_dir = os.path.join(output_directory, "chips"), os.path.join(output_directory, "seg_maps")
+    os.makedirs(chip_dir, exist_ok=True)
+    if not bbox:
+        os.makedirs(seg_dir, exist_ok=True)
+    chips_out: List[str] = []
+    segs_out: List[Optional[str]] = []
+    todo: List[Dict[str, Any]] = []
+    for r in rows:
+        tid = r["mgrs_tile_id"] or own_id
+        if tid.lstrip("T") != own_id.lstrip("T"):
+            stats["dropped"]["other_tile"] += 1
+            continue
+        cname, lname = chip_names(r["label_filename"], tid)
+        have_chip = os.path.exists(os.path.join(chip_dir, cname))
+        if have_chip and (bbox or os.path.exists(os.path.join(seg_dir, lname))):
+            stats["dropped"]["existing"] += 1
+            chips_out.append(cname)
+            segs_out.append(None if bbox else lname)
+            continue
+        item: Dict[str, Any] = {"chip": cname, "label": lname}
+        if bbox:
+            b = r["bounds"]
+            item["grid"] = snapped_grid(b, res) if snap else (b[0], b[1] + S * res, res, res)
+            g = item["grid"]
+            tags = dict(crsmod.geokeys(dst.epsg))
+            tags[33550] = (12, (g[2], g[3], 0.0))
+            tags[33922] = (12, (0.0, 0.0, 0.0, g[0], g[1], 0.0))
+            item["profile"] = {"tags": tags, "nodata": None}
+        else:
+            path = os.path.join(raster_path, r["label_filename"])
+            lab, lprof = tiff.read(path)
+            found = crsmod.from_profile(lprof)
+            if found.epsg != dst.epsg:
+                raise ValueError(f"{path}: the label raster is in EPSG:{found.epsg}, src_crs is EPSG:{dst.epsg}")
+            if lab.shape != (1, S, S):
+                stats["dropped"]["invalid_shape"] += 1
+                continue
+            own = warp.grid_of(lprof, path)
+            bounds = (own[0], own[1] - S * own[3], own[0] + S * own[2], own[1])
+            item["grid"] = snapped_grid(bounds, res) if snap else own
+            item["labels"] = _seg_labels(lab[0], path) if task_type == "seg" else lab[0].astype(np.float32)
+            item["profile"] = {"tags": {k: v for k, v in lprof["tags"].items() if k in _GEO_TAGS}, "nodata": None}
+        if not _touches(dst, item["grid"], S, src, sgrid, H, W):
+            stats["dropped"]["outside_tile"] += 1
+            continue
+        todo.append(item)
+    hist_sum = np.zeros(MAX_CLASSES, dtype=np.int64) if not bbox and task_type == "seg" else None
+    if todo:
+        if device is not None:
+            import torch
+
+            t_dev = torch.from_numpy(tile).to(device)
+            f_dev = None if fmask is None else torch.from_numpy(fmask).to(device)
+        else:
+            t_dev, f_dev = tile, fmask
+        step = max(1, _BATCH_VALUES // (tile.shape[0] * S * S))
+        for first in range(0, len(todo), step):
+            part = todo[first : first + step]
+            labels = None if bbox else np.stack([it["labels"] for it in part])
+            out = warp_cut(t_dev, f_dev, src, sgrid, dst, [it["grid"] for it in part], S, dates=T, mask=bits, strategy=masking_strategy,
+                           no_data_value=HLS_NO_DATA, clip=(0, 10000), labels=labels, label_strategy=masking_strategy if qa_check else None,
+                           num_classes=MAX_CLASSES if hist_sum is not None else 0)
+            chips, valid_values, _, maps, valid_labels, hist = (None if o is None else _to_host(o) for o in out)
+            for k, it in enumerate(part):
+                if qa_check and valid_values[k] == 0:
+                    stats["dropped"]["no_valid_values"] += 1
+                    continue
+                if qa_check and not bbox and valid_labels[k] == 0:
+                    stats["dropped"]["no_valid_labels"] += 1
+                    continue
+                if not bbox:
+                    tiff.write(os.path.join(seg_dir, it["label"]), maps[k], it["profile"])
+                    if hist_sum is not None:
+                        hist_sum += hist[k]
+                tiff.write(os.path.join(chip_dir, it["chip"]), chips[k].astype(np.uint16), it["profile"])
+                chips_out.append(it["chip"])
+                segs_out.append(None if bbox else it["label"])
+                stats["kept"] += 1
+    chipsmod._write_dataset_csv(output_directory, chips_out, segs_out, bbox)
+    if hist_sum is not None:
+        from .pipeline_utils import compute_class_weights
+
+        top = int(np.nonzero(hist_sum)[0].max()) + 1 if hist_sum.any() else 1
+        present = {c: int(v) for c, v in enumerate(hist_sum[:top].tolist()) if v}
+        stats["class_histogram"] = [int(v) for v in hist_sum[:top].tolist()]
+        stats["class_weights"] = compute_class_weights(present) if present else []
+    with open(os.path.join(output_directory, "raster_chips_stats.json"), "w") as f:
+        json.dump(stats, f, sort_keys=True)
+    return chips_out, segs_out
+
+
+# ---- mode=create_raster_chips --------------------------------------------------------------------------------------------------------------
+CONFIG_KEYS = ("tiles", "fmasks", "records_file", "raster_path", "output_directory", "chip_size", "mask_types", "masking_strategy", "src_crs",
+               "spatial_resolution", "qa_check", "task_type", "is_bbox_feature", "bbox_feature_path", "date", "snap")
+
+
+def raster_chips_options(cfg: Dict[str, Any]) -> Dict[str, Any]:
+    """The ``raster_chips.*`` keys of ``mode=create_raster_chips`` checked -> the keyword arguments of :func:`create_raster_chips`.  An
+    unknown key or a bad value raises ValueError; the files are required only in that mode."""
+    c = dict(cfg.get("raster_chips") or {})
+    unknown = set(c) - set(CONFIG_KEYS)
+    if unknown:
+        raise ValueError(f"unknown raster_chips keys {sorted(unknown)}")
+
+    def listing(v, name):
+        if v is None or v == "None":
+            return None
+        if isinstance(v, str):
+            v = [s for s in v.split(",") if s]
+        if not isinstance(v, (list, tuple)) or not all(isinstance(s, str) for s in v):
+            raise ValueError(f"raster_chips.{name} must be a list of names (got {v!r})")
+        return list(v)
+
+    def text(name):
+        v = c.get(name)
+        return None if v in (None, "None") else str(v)
+
+    def flag(name, default):
+        v = c.get(name, default)
+        if not isinstance(v, bool):
+            raise ValueError(f"raster_chips.{name} must be true or false (got {v!r})")
+        return v
+
+    size = c.get("chip_size", 256)
+    if isinstance(size, bool) or not isinstance(size, int) or not 1 <= size <= MAX_SIDE:
+        raise ValueError(f"raster_chips.chip_size must be an int in [1, 2^15] (got {size!r})")
+    types = listing(c.get("mask_types", []), "mask_types") or []
+    mask_bits(types)
+    if c.get("masking_strategy", "each") not in STRATEGIES:
+        raise ValueError(f"raster_chips.masking_strategy must be one of {tuple(STRATEGIES)} (got {c.get('masking_strategy')!r})")
+    if c.get("task_type", "seg") not in ("seg", "reg"):
+        raise ValueError(f"raster_chips.task_type must be seg or reg (got {c.get('task_type')!r})")
+    src = c.get("src_crs", 4326)
+    if isinstance(src, bool) or not isinstance(src, int):
+        raise ValueError(f"raster_chips.src_crs must be an EPSG code (got {src!r})")
+    crsmod.from_epsg(src)
+    res = c.get("spatial_resolution", 0.0002694945852358564)
+    if isinstance(res, bool) or not isinstance(res, (int, float)) or not 0 < float(res) < np.inf:
+        raise ValueError(f"raster_chips.spatial_resolution must be a positive number (got {res!r})")
+    tiles, fmasks = listing(c.get("tiles"), "tiles"), listing(c.get("fmasks"), "fmasks")
+    bbox = flag("is_bbox_feature", False)
+    opts = dict(tile_files=tiles, fmask_files=fmasks, records=text("records_file"), raster_path=text("raster_path"),
+                output_directory=text("output_directory"), chip_size=size, mask_types=types, masking_strategy=c.get("masking_strategy", "each"),
+                src_crs=src, spatial_resolution=float(res), qa_check=flag("qa_check", True), task_type=c.get("task_type", "seg"),
+                is_bbox_feature=bbox, bbox_feature_path=text("bbox_feature_path"), date=text("date"), snap=flag("snap", True))
+    if cfg.get("mode") == "create_raster_chips":
+        if not tiles or opts["output_directory"] is None:
+            raise ValueError("mode=create_raster_chips needs raster_chips.tiles and raster_chips.output_directory")
+        if types and not fmasks:
+            raise ValueError("raster_chips.mask_types needs raster_chips.fmasks (one Fmask file per date)")
+        if bbox and opts["bbox_feature_path"] is None:
+            raise ValueError("raster_chips.is_bbox_feature needs raster_chips.bbox_feature_path")
+        if not bbox and (opts["records"] is None or opts["raster_path"] is None):
+            raise ValueError("mode=create_raster_chips needs raster_chips.records_file and raster_chips.raster_path (or is_bbox_feature)")
+    return opts
+
+
+def run_from_config(cfg: Dict[str, Any], device: Optional[str] = None) -> int:
+    """``mode=create_raster_chips``: :func:`create_raster_chips` under the ``raster_chips.*`` keys; prints one JSON line with the counts."""
+    kw = raster_chips_options(cfg)
+    chips, segs = create_raster_chips(device=device, **kw)
+    print(json.dumps({"create_raster_chips": {"chips": len(chips), "seg_maps": sum(s is not None for s in segs),
+                                              "output_directory": kw["output_directory"]}}))
+    return 0
+
+
+def main(argv: Optional[List[str]] = None) -> int:
+    """``python -m instageo_amd.raster_chips raster_chips.tiles=a.tif,b.tif raster_chips.output_directory=out ...``:
+    mode=create_raster_chips without ``run.py``."""
+    import sys
+
+    from .config import load_config
+
+    cfg = load_config("config", ["mode=create_raster_chips"] + list(sys.argv[1:] if argv is None else argv))
+    dev = None
+    try:
+        import torch
+
+        dev = "cuda" if torch.cuda.is_available() else None
+    except ImportError:
+        pass
+    return run_from_config(cfg, dev)
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

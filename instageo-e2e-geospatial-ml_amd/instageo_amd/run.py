@@ -8,7 +8,8 @@ validation split -> ``calibration.json``; ``calibrate.*``, ``test.temperature`` 
 ``save_uncertainty``) is this project's, as are the region keys of both inference modes (``test.min_region`` / ``connectivity`` /
 ``sieve_passes`` / ``save_regions`` / ``save_polygons`` / ``zones``) and the COG keys of ``tile_inference`` (``test.cog`` / ``cog_blocksize`` /
 ``overview_levels`` / ``cog_compress``); ``create_chips`` (``chips.*``: HLS tiles and a table of labelled points -> chips, label maps and
-the dataset CSV the other modes read; the reference's ``instageo/data`` chip creator, :mod:`instageo_amd.chips`) and ``clean_chips``
+the dataset CSV the other modes read; the reference's ``instageo/data`` chip creator, :mod:`instageo_amd.chips`) ``create_raster_chips`` (``raster_chips.*``: HLS tiles
+resampled onto the grids of label rasters, the reference's ``raster_chip_creator.py``, :mod:`instageo_amd.raster_chips`) and ``clean_chips``
 (``clean.*``: the reference's ``data_cleaner.py``: the no-data chip filter and label buffering / limiting, :mod:`instageo_amd.clean`) build
 no model.  Hydra, Lightning and Neptune are replaced by :mod:`instageo_amd.config` and the explicit loop below, which logs the
 same metric names and writes ``instageo_best_checkpoint.ckpt`` (``{"state_dict": ...}``) on the best
@@ -400,6 +401,10 @@ def main(argv: Optional[List[str]] = None) -> int:
         from . import chips as chipsmod
 
         return chipsmod.run_from_config(cfg, "cuda" if torch.cuda.is_available() else None)
+    if cfg["mode"] == "create_raster_chips":  # no model: HLS tiles + label rasters -> chips on the labels' grids (raster_chips.py)
+        from . import raster_chips as rastermod
+
+        return rastermod.run_from_config(cfg, "cuda" if torch.cuda.is_available() else None)
     if cfg["mode"] == "clean_chips":  # no model: drop no-data chips, buffer / limit the label maps of a chip dataset (clean.py)
         from . import clean as cleanmod
 
