@@ -629,6 +629,47 @@ int ig_chip_warp(const short* tile, const unsigned char* fmask, const double* sr
                  const double* dst_grids, int n, int T, int C, int H, int W, int S, int mask_bits, int strategy, int no_data, int clip,
                  int clip_lo, int clip_hi, const void* labels, int elem_size, int valid_bit, int K, short* chips, int* valid_values,
                  unsigned char* validity, void* maps, int* valid_labels, int* hist, void* stream);
+/* Web Mercator map tiles rendered from an overview pyramid (maptiles.hip; the reference's new_apps/backend/app/tiler_service.py answers
+ * tiles/WebMercatorQuad/{z}/{x}/{y}@1x.png through TiTiler: a warp into EPSG:3857, an overview level, nearest sampling and a colormap or
+ * rescale per request).  THE RULE:
+ * Source.  One raster in one coordinate system src_crs (5 doubles) on one grid src_grid = (X0, Y0, sx, sy) (4 doubles), both ON THE DEVICE
+ *   and exactly as ig_warp defines them, given as a pyramid of nlevels levels in the level geometry of ig_overview_mode / ig_overview_mean:
+ *   level 0 is H x W, level k has H_k = ceil(H_{k-1} / 2) rows and W_k = ceil(W_{k-1} / 2) columns (= ceil(H / 2^k), ceil(W / 2^k)) and
+ *   the grid (X0, Y0, sx 2^k, sy 2^k).  Elements are int8 with 1 band (elem_size 1) or float32 with 1 or 3 bands (elem_size 4); level k is
+ *   laid out (bands, H_k, W_k).  levels is a table ON THE DEVICE of nlevels pointers, one per level: every level stays where it is (level 0
+ *   is never copied; levels 1.. may be the views of the one buffer ig_overview_* filled, or separate allocations).
+ * Tiles.  One launch renders n tiles of tile x tile pixels, tile a multiple of 64 from 64 to 1024.  Tile i has the destination grid
+ *   tile_grids[4 i ..] (4 doubles) in EPSG:3857, the coordinate system (2, 0, 0, 0, 0) of ig_warp, and reads pyramid level tile_level[i]
+ *   (int32); the host chooses both.  A level outside [0, nlevels), a tile grid or a source grid whose values are not finite or whose pixel
+ *   sizes are not positive gives a fully transparent tile and reads nothing.
+ * Sampling.  The source coordinates (u, v) of a pixel centre come from the chain of ig_warp_coords, unchanged (the affine arithmetic alone
+ *   where src_crs equals (2, 0, 0, 0, 0) as doubles, otherwise inverse web Mercator and the forward projection of src_crs, (NaN, NaN)
+ *   outside the domain).  Both are then divided by 2^level, which is exact.  NEAREST: c = floor(u), r = floor(v), tested on the float64
+ *   values; a pixel with r outside [0, H_k), c outside [0, W_k) or NaN coordinates is TRANSPARENT.
+ * Output.  rgba (n, tile, tile, 4) uint8, the bytes R, G, B, A in memory order; a transparent pixel is four zero bytes.  opaque[i] (int32,
+ *   the caller zeroes it) += the pixels of tile i with A != 0.
+ * Styles.  lut is (256, 4) uint8 ON THE DEVICE (R, G, B, A per entry; style 2 does not read it and takes NULL).
+ *   0 PALETTE (int8): a value v with 0 <= v < ncolors (ncolors <= 256) and v != fill gives the four bytes of lut[v]; any other is transparent.
+ *   1 RAMP (float32, 1 band): NaN is transparent; otherwise t = ((double)v - lo) / span, clamped to [0, 1] (below 0 -> 0, above 1 -> 1:
+ *     infinities clamp), idx = (int)rint(t * 255) with ties to even, and the pixel is lut[idx].  span = hi - lo is formed by the caller;
+ *     lo and span are finite, span > 0.
+ *   2 RGB (float32, 3 bands): output channel j comes from plane order[j] (each in 0..2); if any of the three values is NaN the pixel is
+ *     transparent, otherwise each channel is idx as above and A = 255.
+ *   The index is one float64 subtraction, one division, one multiplication and one rint, each rounded on its own (nothing is contracted):
+ *   numpy float64 arithmetic with np.rint gives the same integer.
+ * ig_tile_render: a gather.  One workgroup of 256 threads owns one 64 x 64 block of one tile (the blocking of ig_chip_warp), blocks
+ *   numbered tile-major, then row-major; a wave owns 64 consecutive pixels of a row and stores them as one 32-bit value per lane, 256
+ *   contiguous bytes per instruction; a thread takes 16 rows in turn and evaluates the float64 chain ONCE per pixel.  Every pixel of rgba
+ *   is written exactly once by the thread that computed it.  opaque is summed in the wave and the workgroup (the only LDS) and added with
+ *   one integer atomic per workgroup; no workgroup waits on another; all results are integers or table entries: the same bits for any
+ *   launch geometry, run after run.  1 <= nlevels <= 13, H * W <= 2^31 - 1 (so every level's offsets fit int32), n * tile * tile < 2^31,
+ *   fill fits int8.  The level table and the float64 arrays 8-byte, tile_level, lut, rgba and opaque 4-byte aligned; a level's pointer is
+ *   aligned to its elements (int8 levels may start at any byte).  The caller guarantees that levels[k] holds bands * H_k * W_k elements.
+ *   n = 0 returns IG_OK without touching a pointer. */
+int ig_tile_render(const void* const* levels, int nlevels, int elem_size, int bands, int H, int W, const double* src_crs,
+                   const double* src_grid, const double* tile_grids, const int* tile_level, int n, int tile, int style,
+                   const unsigned char* lut, int ncolors, int fill, double lo, double span, int order0, int order1, int order2,
+                   unsigned char* rgba, int* opaque, void* stream);
 /* Dataset cleaning (clean.hip; the reference's instageo/data/data_cleaner.py: should_drop_chip, buffer_observation_pixels,
  * limit_seg_map_to_observation_pixels).  All results are integers or bit copies, and unique: the same bits for any launch geometry, run
  * after run.  THE RULE:

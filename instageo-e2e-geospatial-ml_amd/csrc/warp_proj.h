@@ -1,6 +1,6 @@
-// The float64 projection code shared by the kernels that map a destination pixel into a source grid (warp.hip, raster_chips.hip): WGS84
-// constants, Krueger's series for transverse Mercator, the coordinate-system and grid descriptions and their chain, as the rule of
-// include/instageo_hip.h states them.  Both files include this text, so both evaluate the same arithmetic.
+// The float64 projection code shared by the kernels that map a destination pixel into a source grid (warp.hip, raster_chips.hip,
+// maptiles.hip): WGS84 constants, Krueger's series for transverse Mercator, the coordinate-system and grid descriptions and their chain,
+// as the rule of include/instageo_hip.h states them.  All three files include this text, so all evaluate the same arithmetic.
 #pragma once
 #include "common.h"
 

@@ -38,6 +38,7 @@ from . import tiff, warp
 
 MASK_POSITIONS = {"HLS": {"cloud": 1, "near_cloud_or_shadow": 2, "cloud_shadow": 3, "water": 5}}
 STRATEGIES = {"each": 0, "any": 1}  # include/instageo_hip.h
+NO_DATA_VALUE = 0  # of the written chips when the caller names none (create_chips; maptiles.merge_chips reads it for files without a tag)
 VALID_BITS = {None: 0, "any": 1, "each": 2}  # the bit of the validity plane a label strategy looks at
 MAX_DATES = 32
 MAX_CLASSES = 256
@@ -339,7 +340,7 @@ def _to_host(a):
 
 def create_chips(tile_files: Sequence[str], fmask_files: Optional[Sequence[str]], points, output_directory: str, chip_size: int = 256,
                  mask_types: Sequence[str] = (), masking_strategy: str = "each", window_size: int = 0, task_type: str = "seg",
-                 src_crs: int = 4326, no_data_value: int = 0, num_classes: Optional[int] = None, device: Optional[str] = None,
+                 src_crs: int = 4326, no_data_value: int = NO_DATA_VALUE, num_classes: Optional[int] = None, device: Optional[str] = None,
                  date: Optional[str] = None) -> Tuple[List[str], List[Optional[str]]]:
     """The reference's chip creator for one HLS tile.  ``tile_files``: the band files ordered per date and band (``B02_0``, ``B03_0``,
     ...), one Fmask file per date in ``fmask_files`` (read only when ``mask_types`` asks for masks); ``points``: a CSV path or a table with

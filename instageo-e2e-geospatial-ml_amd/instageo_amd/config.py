@@ -97,7 +97,16 @@ DEFAULTS: Dict[str, Any] = {'root_dir': None,
           # boundary quality (not in the reference): mode=eval also logs test_bIoU_d<d> (Boundary IoU, with _<class>), test_trimap_Acc_d<d>
           # and test_trimap_IoU_d<d> over the pixels within d pixels of a class boundary, for each of up to 8 ascending distances in
           # [1, 32] (boundary.py)
-          'boundary_metrics': False, 'boundary_distances': [1, 2, 4]},
+          'boundary_metrics': False, 'boundary_distances': [1, 2, 4],
+          # Web Mercator map tiles (not in the reference's run.py; its backend serves them through TiTiler; maptiles.py): map_tiles writes
+          # tiles_<name>/{z}/{x}/{y}.png + tilejson.json of the class map / prediction raster of mode=tile_inference, and tiles_merged/ of
+          # the mosaic of mode=chip_inference (test.mosaic=true), rendered on the device.  map_tiles_minzoom / map_tiles_maxzoom: 'auto' or
+          # 0..24; map_tiles_size: the tile side, a multiple of 64 in 64..1024; map_tiles_palette: a JSON file of [r, g, b(, a)] entries
+          # (the class colours, or the 256 entries of the regression ramp); map_tiles_rescale: [lo, hi] of the ramp, None = the finite
+          # minimum and maximum; map_tiles_imagery: also tiles_chips/ (+ chips_merged.tif) from the input chips; map_tiles_png_level: 0..9.
+          # mode=map_tiles renders the existing GeoTIFF test.input into <its folder>/tiles_<name>/
+          'map_tiles': False, 'map_tiles_minzoom': 'auto', 'map_tiles_maxzoom': 'auto', 'map_tiles_size': 256, 'map_tiles_palette': None,
+          'map_tiles_rescale': None, 'map_tiles_imagery': False, 'map_tiles_png_level': 6, 'input': None},
  # mode=calibrate (not in the reference): temperature fit on valid_filepath -- grid points per pass, passes, the first grid's range,
  # bins of the reliability histograms (calibration.py)
  'calibrate': {'points': 32, 'passes': 2, 't_min': 0.125, 't_max': 8.0, 'nbins': 15},

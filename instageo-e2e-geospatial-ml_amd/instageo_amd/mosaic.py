@@ -18,7 +18,8 @@ without a GPU.
 
 Not done: reprojection or resampling between grids in this module (chips must share one pixel grid; chips of different coordinate
 systems become separate mosaics, two pixel scales in one are refused; :func:`instageo_amd.warp.merge_reprojected` warps those mosaics
-onto one canvas), rotated rasters, the reference's RGB ``chips_merged.tif``, multi-band inputs, BigTIFF, a mosaic of
+onto one canvas), rotated rasters, multi-band inputs (the reference's RGB ``chips_merged.tif`` is
+:func:`instageo_amd.maptiles.merge_chips`), BigTIFF, a mosaic of
 tensors still on the device inside ``chip_inference``, and chip lists built on the device.
 """
 from __future__ import annotations

@@ -1380,6 +1380,84 @@ def chip_warp(tile, fmask, src_crs, src_grid, dst_crs, dst_grids, S: int, T: int
     return chips, valid, plane, maps, valid_labels, hist
 
 
+TILE_STYLES = {"palette": 0, "ramp": 1, "rgb": 2}  # include/instageo_hip.h
+TILE_MAX_LEVELS = 13
+
+
+def tile_render(levels, src_crs, src_grid, tile_grids, tile_level, tile: int, style: str, lut=None, ncolors: int = 0, fill: int = -1,
+                rescale=(0.0, 1.0), order=(0, 1, 2), out=None):
+    """``ig_tile_render`` (include/instageo_hip.h): ``levels`` the pyramid, a list of device tensors (level 0 first; (H_k, W_k) or
+    (bands, H_k, W_k), int8 for ``palette``, float32 for ``ramp`` (1 band) and ``rgb`` (3 bands)) that stay where they are: only a table
+    of their addresses is uploaded.  ``src_crs`` five doubles, ``src_grid`` (X0, Y0, sx, sy), ``tile_grids`` (n, 4) float64 (EPSG:3857)
+    and ``tile_level`` (n,) int32 as host values; ``lut`` (256, 4) uint8 (host array or device tensor); ``rescale`` = (lo, hi).  The level
+    shapes are checked here, so that no read can leave a level.  -> (rgba (n, tile, tile, 4) uint8, opaque (n,) int32).  ``out``: a
+    contiguous (n, tile, tile, 4) uint8 tensor to write into instead of a new one (every pixel is written)."""
+    import numpy as np
+
+    code = TILE_STYLES.get(style)
+    if code is None:
+        raise ValueError(f"style must be one of {tuple(TILE_STYLES)} (got {style!r})")
+    levels = list(levels)
+    if not 1 <= len(levels) <= TILE_MAX_LEVELS:
+        raise ValueError(f"a pyramid has 1..{TILE_MAX_LEVELS} levels (got {len(levels)})")
+    want, bands = (torch.int8, 1) if code == 0 else (torch.float32, 3 if code == 2 else 1)
+    first = levels[0]
+    H, W = int(first.shape[-2]), int(first.shape[-1])
+    if H < 1 or W < 1 or H * W > 2**31 - 1:
+        raise ValueError(f"a source of {H} x {W} pixels is beyond the kernel's limits (1 <= H * W <= 2^31 - 1)")
+    h, w = H, W
+    for k, lv in enumerate(levels):
+        shape = tuple(lv.shape)
+        if lv.dtype != want or shape not in (((h, w), (1, h, w)) if bands == 1 else ((3, h, w),)) or lv.device != first.device:
+            raise ValueError(f"level {k} must be {want} of {'(3, ' if bands == 3 else '('}{h}, {w}) on {first.device} for style {style!r} "
+                             f"(got {lv.dtype} {shape} on {lv.device})")
+        h, w = (h + 1) // 2, (w + 1) // 2
+    tile = int(tile)
+    if tile < 64 or tile > 1024 or tile % 64:
+        raise ValueError(f"tile must be a multiple of 64 in 64..1024 (got {tile})")
+    grids = np.ascontiguousarray(tile_grids, dtype=np.float64).reshape(-1, 4)
+    lvl = np.ascontiguousarray(tile_level, dtype=np.int32).reshape(-1)
+    n = grids.shape[0]
+    if lvl.shape[0] != n:
+        raise ValueError(f"{n} tile grids but {lvl.shape[0]} tile levels")
+    if n * tile * tile >= 2**31:
+        raise ValueError(f"{n} tiles of {tile} x {tile} reach 2^31 pixels: render in batches")
+    lo, hi = float(rescale[0]), float(rescale[1])
+    if code != 0 and not (np.isfinite(lo) and np.isfinite(hi) and hi - lo > 0 and np.isfinite(hi - lo)):
+        raise ValueError(f"rescale = (lo, hi) needs finite values with lo < hi (got {rescale!r})")
+    order = tuple(int(o) for o in order)
+    if code == 2 and (len(order) != 3 or any(not 0 <= o < 3 for o in order)):
+        raise ValueError(f"order names three planes in 0..2 (got {order!r})")
+    if isinstance(fill, bool) or not -128 <= int(fill) <= 127:
+        raise ValueError(f"fill must be an int that fits int8 (got {fill!r})")
+    if not 0 <= int(ncolors) <= 256:
+        raise ValueError(f"ncolors must lie in 0..256 (got {ncolors!r})")
+    dev = first.device
+    if code != 2:
+        if lut is None:
+            raise ValueError(f"style {style!r} needs a lut")
+        if not torch.is_tensor(lut):
+            lut = torch.from_numpy(np.ascontiguousarray(lut, dtype=np.uint8))
+        lut = lut.to(dev)
+        assert lut.dtype == torch.uint8 and tuple(lut.shape) == (256, 4), "lut is (256, 4) uint8"
+    else:
+        lut = None
+    rgba = out if out is not None else torch.empty((n, tile, tile, 4), dtype=torch.uint8, device=dev)
+    assert rgba.dtype == torch.uint8 and tuple(rgba.shape) == (n, tile, tile, 4)
+    opaque = torch.zeros((n,), dtype=torch.int32, device=dev)
+    if n:
+        sc, sg = _warp_doubles(src_crs, 5, "src_crs"), _warp_doubles(src_grid, 4, "src_grid")
+        # alive until the launch is queued; the copies are stream-ordered
+        dbl = torch.from_numpy(np.concatenate([sc, sg, grids.reshape(-1)])).to(dev)
+        table = torch.tensor([_p(lv) for lv in levels], dtype=torch.int64).to(dev)
+        lv_d = torch.from_numpy(lvl).to(dev)
+        # HBM bytes: the tiles written and as many source values gathered
+        _call("ig_tile_render", float(n) * tile * tile * (4 + first.element_size() * bands), _p(table), len(levels), first.element_size(), bands, H, W,
+              _p(dbl[0:5]), _p(dbl[5:9]), _p(dbl[9:]), _p(lv_d), n, tile, code, _p(lut), int(ncolors), int(fill), lo, hi - lo, order[0], order[1],
+              order[2], _p(rgba), _p(opaque), _stream())
+    return rgba, opaque
+
+
 def chip_nodata(chips, no_data_value: int):
     """``ig_chip_nodata`` (include/instageo_hip.h): ``chips`` (n, B, H, W) int16 | uint16 on the device -> (plane (n, H, W) uint8: bit 0
     any, bit 1 all; counts (n, 2) int32).  A ``no_data_value`` the chips' dtype cannot hold matches nothing: zeros without a launch."""

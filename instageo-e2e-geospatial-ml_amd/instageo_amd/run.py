@@ -385,6 +385,75 @@ def warp_options(cfg: Dict[str, Any]) -> Dict[str, Any]:
     return opts
 
 
+def map_tiles_options(cfg: Dict[str, Any]) -> Dict[str, Any]:
+    """The ``test.map_tiles*`` keys (Web Mercator map tiles, maptiles.py), checked: a bad value raises ValueError that names the key, and
+    so do ``map_tiles`` in a mode that writes no raster, ``map_tiles`` with ``mode=chip_inference`` but no ``test.mosaic``, and
+    ``map_tiles_imagery`` without ``map_tiles`` and a mosaic.  -> ``on``, ``imagery`` and the keyword arguments of ``maptiles.export``."""
+    from . import maptiles as M
+
+    t, mode = cfg["test"], cfg.get("mode")
+    none = lambda v: None if v in (None, "None", "none", "null") else v  # noqa: E731
+    on, imagery = t.get("map_tiles", False), t.get("map_tiles_imagery", False)
+    for name, v in (("map_tiles", on), ("map_tiles_imagery", imagery)):
+        if not isinstance(v, bool):
+            raise ValueError(f"test.{name} must be true or false (got {v!r})")
+    tile = M.check_tile_size(t.get("map_tiles_size", 256))
+    zooms = {}
+    for name in ("map_tiles_minzoom", "map_tiles_maxzoom"):
+        v = none(t.get(name, "auto"))
+        if v not in (None, "auto") and (isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= M.MAX_ZOOM):
+            raise ValueError(f"test.{name} must be 'auto' or an int in 0..{M.MAX_ZOOM} (got {v!r})")
+        zooms[name[10:]] = "auto" if v is None else v
+    if "auto" not in zooms.values() and zooms["minzoom"] > zooms["maxzoom"]:
+        raise ValueError(f"test.map_tiles_minzoom {zooms['minzoom']} lies above test.map_tiles_maxzoom {zooms['maxzoom']}")
+    rescale = none(t.get("map_tiles_rescale"))
+    if rescale is not None:
+        ok = isinstance(rescale, (list, tuple)) and len(rescale) == 2 and all(isinstance(v, (int, float)) and not isinstance(v, bool) for v in rescale)
+        if not ok or not float(rescale[0]) < float(rescale[1]) < float("inf") or rescale[0] == float("-inf"):
+            raise ValueError(f"test.map_tiles_rescale must be None or [lo, hi] with finite lo < hi (got {rescale!r})")
+        rescale = (float(rescale[0]), float(rescale[1]))
+    level = t.get("map_tiles_png_level", 6)
+    if isinstance(level, bool) or not isinstance(level, int) or not 0 <= level <= 9:
+        raise ValueError(f"test.map_tiles_png_level must be an int in 0..9 (got {level!r})")
+    palette = none(t.get("map_tiles_palette"))
+    if palette is not None:
+        root = cfg.get("root_dir")
+        if not os.path.isabs(str(palette)) and root not in (None, "None"):
+            palette = os.path.join(root, str(palette))
+        M.load_colors(str(palette))
+    regression = bool(cfg.get("is_reg_task", False)) or cfg["model"].get("num_classes") == 1
+    if rescale is not None and on and not regression and not imagery and mode != "map_tiles":
+        raise ValueError("test.map_tiles_rescale does not go with a classification head (class maps take test.map_tiles_palette)")
+    if on and mode not in ("tile_inference", "chip_inference", "map_tiles"):
+        raise ValueError(f"test.map_tiles needs mode=tile_inference, chip_inference or map_tiles (mode={mode} writes no raster)")
+    if on and mode == "chip_inference" and t.get("mosaic", False) is not True:
+        raise ValueError("test.map_tiles needs test.mosaic=true with mode=chip_inference: the tiles show the merged raster")
+    if imagery and not (on and mode == "chip_inference" and t.get("mosaic", False) is True):
+        raise ValueError("test.map_tiles_imagery needs test.map_tiles=true and test.mosaic=true with mode=chip_inference: the imagery is the "
+                         "mosaic of the input chips")
+    if mode == "map_tiles" and none(t.get("input")) is None:
+        raise ValueError("mode=map_tiles needs test.input=<a GeoTIFF>")
+    return dict(on=on or mode == "map_tiles", imagery=imagery,
+                export=dict(tile=tile, palette=palette, rescale=rescale, png_level=level, **zooms))
+
+
+def write_map_tiles(raster_path: str, opts: Dict[str, Any], device: Optional[str], name: Optional[str] = None) -> List[str]:
+    """``tiles_<name>/`` beside ``raster_path`` (a written prediction raster; the overviews of a COG are reused), through
+    ``maptiles.export``; an int8 raster is a class map (palette), a float32 one goes through the ramp."""
+    from . import maptiles as M
+    from . import tiff as tiffmod
+
+    stem = name or os.path.splitext(os.path.basename(raster_path))[0]
+    out = os.path.join(os.path.dirname(os.path.abspath(raster_path)), f"tiles_{stem}")
+    kw = dict(opts["export"])
+    prof = tiffmod.read_profile(raster_path)
+    if str(prof.get("dtype")) == "int8":
+        kw["rescale"] = None
+        nd = prof.get("nodata")
+        kw["fill"] = int(nd) if nd is not None and -128 <= nd <= 127 and float(nd) == int(nd) else -1
+    return M.export(raster_path, out, device=device, name=stem, **kw)
+
+
 def main(argv: Optional[List[str]] = None) -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--config-name", default="config")
@@ -397,6 +466,13 @@ def main(argv: Optional[List[str]] = None) -> int:
     cog_options(cfg)  # a bad COG key, or test.cog with mode=chip_inference, stops here: before the model is built
     mosaic = mosaic_options(cfg)  # likewise a bad mosaic key, or test.mosaic outside mode=chip_inference
     reproject = warp_options(cfg)  # likewise the keys of the reprojected mosaic
+    tiles = map_tiles_options(cfg)  # likewise the keys of the map tiles
+    if cfg["mode"] == "map_tiles":  # no model: an existing GeoTIFF -> tiles_<name>/{z}/{x}/{y}.png + tilejson.json (maptiles.py)
+        inp = str(cfg["test"]["input"])
+        root = cfg.get("root_dir")
+        inp = inp if os.path.isabs(inp) or root in (None, "None") else os.path.join(root, inp)
+        print(json.dumps({"map_tiles": write_map_tiles(inp, tiles, "cuda" if torch.cuda.is_available() else None)[-1]}))
+        return 0
     if cfg["mode"] == "create_chips":  # no model: HLS tiles + points -> chips, label maps and the dataset CSV (chips.py)
         from . import chips as chipsmod
 
@@ -480,12 +556,28 @@ def main(argv: Optional[List[str]] = None) -> int:
                 else:
                     merged = merge_predictions(output_dir, output_dir, **keys)
                 print(json.dumps({"mosaic": merged}))
+                if tiles["on"]:
+                    for path in merged:
+                        base = os.path.basename(path)
+                        if base.startswith("predictions_merged") and base.endswith(".tif"):
+                            print(json.dumps({"map_tiles": write_map_tiles(path, tiles, dev, base[len("predictions_") : -4])[-1]}))
+                if tiles["imagery"]:
+                    from . import maptiles as M
+
+                    levels, prof = M.merge_chips(tile_paths(cfg), device=dev, out_path=os.path.join(output_dir, "chips_merged.tif"),
+                                                 tile=tiles["export"]["tile"])
+                    kw = dict(tiles["export"], palette=None, rescale=tiles["export"]["rescale"] or (0.0, 3000.0))
+                    print(json.dumps({"map_tiles": M.export(levels, os.path.join(output_dir, "tiles_chips"), prof, order=(2, 1, 0),
+                                                            name="chips", **kw)[-1]}))
     elif cfg["mode"] == "tile_inference":
         check_required_flags(["root_dir", "test_filepath", "checkpoint_path"], cfg)
         for tile in tile_paths(cfg):
             out = run_tile_inference(cfg, model, tile, os.path.join(cfg["root_dir"], "predictions"), dev)
             if rank == 0:
                 print(json.dumps({"tile": tile, "prediction": out}))
+                if tiles["on"] and out is not None:
+                    stem = os.path.splitext(os.path.basename(tile))[0]
+                    print(json.dumps({"map_tiles": write_map_tiles(out, tiles, dev, stem)[-1]}))
     else:
         raise ValueError(f"unknown mode {cfg['mode']!r}")
     if D.dp_active():
