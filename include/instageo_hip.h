@@ -446,6 +446,47 @@ int ig_zone_toggle(const int* edges, const unsigned char* bit, const long long* 
                    int W, void* stream);
 int ig_zone_tally(unsigned long long* canvas, const signed char* cls, unsigned long long* counts, int H, int W, int ncls, int fill,
                   int write_mask, void* stream);
+/* Polygon labels burned into label rasters (burn.hip; the reference assumes its label rasters were made with gdal_rasterize beforehand).
+ * THE RULE:
+ * Grid and inside test.  Those of the zonal block above, unchanged: Q = 256 fixed point, X = floor(x * 256 + 0.5), the centre of pixel
+ *   (r, c) at (256 c + 128, 256 r + 128), an edge crosses row r iff (y0 <= Yc) != (y1 <= Yc), and the pixel is inside a feature iff an odd
+ *   number of the feature's edges cross its row with xc <= Xc.
+ * Features.  An ordered list, in file order; feature i carries one burn value v_i: an int8 in [-1, 127] for segmentation (-1 burns the
+ *   ignore value), a float32 for regression (copied bit for bit).
+ * Which feature wins.  A pixel takes the value of the LAST feature, in order, that contains its centre (gdal_rasterize burning the
+ *   features one after the other).  A pixel in no feature keeps what the raster held before: the host initialises the raster (to the
+ *   background, or to the ignore value -1 / NaN when a labelled area is given, whose polygons are then burned FIRST with the background
+ *   value by the same machinery).
+ * Exactness.  Everything on the device is integer work or a copy of a caller-supplied value: two runs give the same bytes, and so does
+ *   the numpy host path.
+ * Passes.  Features go through a canvas 64 at a time in file order: bit b of a pass is its b-th feature, so inside one pass the last
+ *   containing feature is the HIGHEST set bit of the pixel's inside mask; later passes overwrite earlier ones (the host launches them in
+ *   order on one stream).  The canvas of a pass is not the whole raster but an Hp x Wp rectangle with its top-left pixel at (r0, c0) of
+ *   the raster: ig_zone_edge_rows and ig_zone_toggle are called as they are on that canvas with the edges shifted by (-256 c0, -256 r0),
+ *   whole pixels, which is exact: the toggle clamps crossings left of column 0 to column 0 and drops rows outside [0, Hp) and columns
+ *   >= Wp.
+ * ig_burn_resolve: canvas (Hp, Wp) uint64 holds the TOGGLES of one pass (it is read, not written).  The inclusive prefix XOR along each
+ *   canvas row (thread runs of 4, wave scan, workgroup scan, a carry in a register over the chunks of 1024 columns: the scan of
+ *   ig_zone_tally) is the inside mask m of 64 features; for m != 0 the pixel is written: out[(r0 + r) * pitch + c0 + c] =
+ *   table[63 - clz(m)], table = 64 values of the element type ON THE DEVICE (int8 for elem_size 1, float32 for 4).  Pixels with m == 0
+ *   are NOT written.  out is a raster of H rows of W pixels with a row pitch of `pitch` elements (pitch >= W); the rectangle lies inside
+ *   it: 0 <= r0, r0 + Hp <= H, 0 <= c0, c0 + Wp <= W.  int8 pixels are stored as single bytes, except that a thread whose four
+ *   consecutive pixels are all written and start at a 4-byte aligned address stores them as one 32-bit word (the word is then private to
+ *   that thread): no two lanes ever read-modify-write one word, whatever pitch and c0 are.  written (uint64, or NULL) += the number of
+ *   pixels stored: summed per thread, wave and workgroup, one 64-bit atomic add per workgroup.  A workgroup owns whole rows; no kernel
+ *   waits on another workgroup; every launch does a fixed amount of work.  Hp * Wp <= 2^31 - 1, H * pitch < 2^40; canvas and written
+ *   8-byte aligned, float32 table / out 4-byte aligned.  Hp * Wp = 0 returns IG_OK without touching a pointer.
+ * ig_label_cells: raster (ny * S, nx * S), int8 (elem_size 1) or float32 (4), contiguous, is cut into ny x nx cells of S x S pixels, cell
+ *   (cy, cx) numbered cy * nx + cx.  valid (ny * nx uint64) += the cell's VALID pixels: != ignore for int8, not NaN for float32 (ignore is
+ *   not read).  hist (ny * nx, K) uint64 += for int8 with K > 0 the valid pixels per value in [0, K); a value outside [0, K) counts as
+ *   valid but goes in no histogram cell.  The caller zeroes both.  One workgroup owns up to 64 rows of one cell; lanes of a wave that
+ *   hold the same value add once to an LDS table of 32-bit cells, which reaches memory as one 64-bit atomic add per non-empty cell;
+ *   integer sums, bit-identical from run to run.  1 <= S <= 2^15, ny * nx <= 2^31 - 1, ny * S * nx * S < 2^40, 0 <= K <= 128 (K > 0 needs
+ *   elem_size 1), ignore fits int8.  ny * nx = 0 returns IG_OK without touching a pointer. */
+int ig_burn_resolve(const unsigned long long* canvas, int Hp, int Wp, const void* table, int elem_size, void* out, int H, int W, long pitch,
+                    int r0, int c0, unsigned long long* written, void* stream);
+int ig_label_cells(const void* raster, int ny, int nx, int S, int elem_size, int ignore, int K, unsigned long long* valid,
+                   unsigned long long* hist, void* stream);
 /* Overview pyramids and tile layout for Cloud Optimized GeoTIFF output (cog.hip; the reference calls gdal_translate -of COG instead).
  * Level 0 is the raster itself, H_0 x W_0; level k has H_k = ceil(H_{k-1} / 2) rows and W_k = ceil(W_{k-1} / 2) columns.  Pixel (r, c) of
  * level k has as CHILDREN the pixels (2r..2r+1, 2c..2c+1) of level k-1 that lie inside that level: 1, 2 or 4 of them, in row-major order.

@@ -130,7 +130,17 @@ DEFAULTS: Dict[str, Any] = {'root_dir': None,
  'clean': {'chips_dataset_csv': None, 'output_chips_dataset_csv': None, 'drop_chips': False, 'drop_chips_strategy': 'any',
            'no_data_threshold': 0.5, 'no_data_value': -9999, 'clean_seg_maps': False, 'cleaning_method': 'buffer',
            'observation_points_csv': None, 'seg_map_output_dir': None, 'ignore_index': -1, 'window_size': 1, 'num_classes': None,
-           'root_dir': None}}
+           'root_dir': None},
+ # mode=create_polygon_labels (not in the reference, which expects label rasters made with GDAL; polygon_labels.py): the polygons of the
+ # GeoJSON `features` (EPSG:src_crs) are burned into labels/label_x{x}_y{y}_{date}.tif of chip_size x chip_size pixels + records.csv, the
+ # input of mode=create_raster_chips.  The grid is that of the raster `like` (an HLS tile: the labels sit on its pixels), else EPSG:crs
+ # (None: the UTM zone of the features) at spatial_resolution.  The value of a feature: its value_property (an integer, or a name looked
+ # up in class_map) or the constant burn_value; later features win; background: what no feature covers (None: 0 for seg, NaN for reg);
+ # labelled_area: a GeoJSON outside which pixels get the ignore value; date or date_property name the rasters; a cell with fewer than
+ # min_foreground labelled pixels is dropped; device: None = the device when there is one, host, cuda
+ 'polygon_labels': {'features': None, 'output_directory': None, 'like': None, 'crs': None, 'src_crs': 4326, 'spatial_resolution': 30.0,
+                    'chip_size': 256, 'task_type': 'seg', 'value_property': None, 'burn_value': None, 'class_map': None, 'background': None,
+                    'labelled_area': None, 'date': None, 'date_property': None, 'mgrs_tile_id': None, 'min_foreground': 1, 'device': None}}
 
 PRESETS: Dict[str, Dict[str, Any]] = {'sen1floods11': {'train': {'batch_size': 16, 'class_weights': [1, 3], 'ignore_index': -1},
                   'model': {'model_name': 'prithvi_eo_v1_100'},

@@ -1053,6 +1053,43 @@ def zone_tally(canvas, classmap, counts, ncls: int = 2, fill: int = -1, write_ma
           int(ncls), int(fill), int(bool(write_mask)), _stream())
 
 
+def burn_resolve(canvas, table, out, r0: int, c0: int, written=None) -> None:
+    """One pass of the polygon burn (include/instageo_hip.h): ``canvas`` (Hp, Wp) int64 holds the toggles of up to 64 features
+    (:func:`zone_toggle`); where the prefix XOR along a row is not zero, ``out[r0 + r, c0 + c] = table[highest set bit]``; other pixels
+    are not written.  ``out`` (H, W) int8 | float32 may be a view with any row pitch (its columns contiguous); ``table`` (64,) of its
+    dtype; ``written`` (1,) int64, when given, += the pixels stored."""
+    assert canvas.dtype == torch.int64 and canvas.dim() == 2
+    assert out.dim() == 2 and out.dtype in (torch.int8, torch.float32) and table.dtype == out.dtype and table.numel() == ZONE_BITS
+    assert written is None or (written.dtype == torch.int64 and written.numel() == 1)
+    Hp, Wp = canvas.shape
+    H, W = out.shape
+    if Hp * Wp == 0:
+        return
+    if not out.is_cuda or (W > 1 and out.stride(1) != 1) or (H > 1 and out.stride(0) < W):
+        raise _lib.HipLibraryError("burn_resolve: out must be a HIP tensor with contiguous columns and a row pitch >= W")
+    pitch = int(out.stride(0)) if H > 1 else W
+    # HBM bytes: the canvas read once; the stores depend on the polygons (at most the rectangle)
+    _call("ig_burn_resolve", float(Hp) * Wp * 8, _p(canvas), Hp, Wp, _p(table), out.element_size(), out.data_ptr(), H, W, pitch, int(r0),
+          int(c0), _p(written), _stream())
+
+
+def label_cells(raster, S: int, K: int = 0, ignore: int = -1):
+    """Per S x S cell of ``raster`` (ny * S, nx * S) int8 | float32 -> (valid (ny, nx) int64, hist (ny, nx, K) int64 or None): the pixels
+    that are not ``ignore`` (int8) / not NaN (float32), and for int8 with K > 0 those per value in [0, K)."""
+    assert raster.dim() == 2 and raster.dtype in (torch.int8, torch.float32)
+    S, K = int(S), int(K)
+    H, W = raster.shape
+    if S < 1 or H % S or W % S:
+        raise _lib.HipLibraryError(f"label_cells: a raster of {H} x {W} pixels is not a whole number of {S} x {S} cells")
+    ny, nx = H // S, W // S
+    valid = torch.zeros((ny, nx), dtype=torch.int64, device=raster.device)
+    hist = torch.zeros((ny, nx, K), dtype=torch.int64, device=raster.device) if K else None
+    if ny * nx:
+        _call("ig_label_cells", float(H) * W * raster.element_size(), _p(raster), ny, nx, S, raster.element_size(), int(ignore), K, _p(valid),
+              _p(hist), _stream())
+    return valid, hist
+
+
 def pyramid_shapes(H: int, W: int, levels: int):
     """[(H_k, W_k) for k = 1..levels] with H_k = ceil(H_{k-1} / 2), W_k = ceil(W_{k-1} / 2) (include/instageo_hip.h)."""
     out = []

@@ -9,9 +9,10 @@ validation split -> ``calibration.json``; ``calibrate.*``, ``test.temperature`` 
 ``sieve_passes`` / ``save_regions`` / ``save_polygons`` / ``zones``) and the COG keys of ``tile_inference`` (``test.cog`` / ``cog_blocksize`` /
 ``overview_levels`` / ``cog_compress``); ``create_chips`` (``chips.*``: HLS tiles and a table of labelled points -> chips, label maps and
 the dataset CSV the other modes read; the reference's ``instageo/data`` chip creator, :mod:`instageo_amd.chips`) ``create_raster_chips`` (``raster_chips.*``: HLS tiles
-resampled onto the grids of label rasters, the reference's ``raster_chip_creator.py``, :mod:`instageo_amd.raster_chips`) and ``clean_chips``
-(``clean.*``: the reference's ``data_cleaner.py``: the no-data chip filter and label buffering / limiting, :mod:`instageo_amd.clean`) build
-no model.  Hydra, Lightning and Neptune are replaced by :mod:`instageo_amd.config` and the explicit loop below, which logs the
+resampled onto the grids of label rasters, the reference's ``raster_chip_creator.py``, :mod:`instageo_amd.raster_chips`), ``clean_chips``
+(``clean.*``: the reference's ``data_cleaner.py``: the no-data chip filter and label buffering / limiting, :mod:`instageo_amd.clean`) and
+``create_polygon_labels`` (``polygon_labels.*``: a GeoJSON of polygons burned into the label rasters and the records table that
+``create_raster_chips`` takes, :mod:`instageo_amd.polygon_labels`) build no model.  Hydra, Lightning and Neptune are replaced by :mod:`instageo_amd.config` and the explicit loop below, which logs the
 same metric names and writes ``instageo_best_checkpoint.ckpt`` (``{"state_dict": ...}``) on the best
 ``val_IoU`` (pipeline_utils.py:347-355).  Data: ``*_filepath`` may be ``synthetic:<n>`` (on-device HLS-shaped
 chips), an ``.npz`` with ``chips (N,T*C,H,W)`` and ``labels (N,H,W)``, or the reference's own CSV of chip / label GeoTIFF paths
@@ -485,6 +486,10 @@ def main(argv: Optional[List[str]] = None) -> int:
         from . import clean as cleanmod
 
         return cleanmod.run_from_config(cfg, "cuda" if torch.cuda.is_available() else None)
+    if cfg["mode"] == "create_polygon_labels":  # no model: a GeoJSON of polygons -> label rasters + records.csv (polygon_labels.py)
+        from . import polygon_labels as polymod
+
+        return polymod.run_from_config(cfg, "cuda" if torch.cuda.is_available() else None)
     start = time.time()
     torch.manual_seed(SEED)
     np.random.seed(SEED)
