@@ -26,7 +26,6 @@ label-raster pipeline, which resamples a tile to another grid, is :mod:`instageo
 """
 from __future__ import annotations
 
-import datetime
 import json
 import os
 from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
@@ -34,17 +33,15 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
 import numpy as np
 
 from . import crs as crsmod
-from . import tiff, warp
+from . import prep, tiff, warp
+from .prep import MAX_DATES, STRATEGIES, is_device, to_host  # noqa: F401  (the masking strategies and the date limit of include/instageo_hip.h)
 
 MASK_POSITIONS = {"HLS": {"cloud": 1, "near_cloud_or_shadow": 2, "cloud_shadow": 3, "water": 5}}
-STRATEGIES = {"each": 0, "any": 1}  # include/instageo_hip.h
 NO_DATA_VALUE = 0  # of the written chips when the caller names none (create_chips; maptiles.merge_chips reads it for files without a tag)
 VALID_BITS = {None: 0, "any": 1, "each": 2}  # the bit of the validity plane a label strategy looks at
-MAX_DATES = 32
 MAX_CLASSES = 256
 MAX_WINDOW = 1 << 20
 SEG_NO_DATA = -1  # the reference's NO_DATA_VALUES.SEG_MAP
-_GEO_TAGS = (33550, 34735, 34736, 34737)
 
 
 def decode_fmask_value(value, position: int):
@@ -67,34 +64,14 @@ def mask_bits(mask_types: Sequence[str], data_source: str = "HLS") -> int:
     return bits
 
 
-def _is_device(a) -> bool:
-    return type(a).__module__.startswith("torch") and bool(getattr(a, "is_cuda", False))
-
-
 # ---- argument checks shared by the host path and the device wrappers (ops.chip_cut / ops.chip_labels) -----------------------------------
 def check_cut(tile_shape, fmask_shape, origins, S: int, T: int, bits: int, strategy: str, no_data_value: int, clip) -> np.ndarray:
     """ValueError unless the arguments of a cut obey include/instageo_hip.h -> origins as an (n, 2) int32 array."""
-    if len(tile_shape) != 3:
-        raise ValueError(f"a tile is (T * C, H, W) (got shape {tuple(tile_shape)})")
-    TC, H, W = (int(v) for v in tile_shape)
     if isinstance(S, bool) or int(S) < 1:
         raise ValueError(f"chip_size must be an int >= 1 (got {S!r})")
-    if not 1 <= T <= MAX_DATES or TC % T or TC < 1:
-        raise ValueError(f"{TC} bands do not divide into {T} dates (1 <= dates <= {MAX_DATES})")
-    if fmask_shape is not None and tuple(fmask_shape) != (T, H, W):
-        raise ValueError(f"fmask must be (T, H, W) = {(T, H, W)} (got {tuple(fmask_shape)})")
+    _, H, W = prep.check_stack_args(tile_shape, fmask_shape, int(S), T, bits, strategy, no_data_value, clip)
     if S > H or S > W:
         raise ValueError(f"a chip of side {S} does not fit a tile of {H} x {W} pixels")
-    if TC * S * S > 2**31 - 1:
-        raise ValueError(f"a chip of {TC} x {S} x {S} values is beyond 2^31 - 1 (valid_values is int32)")
-    if not 0 <= int(bits) <= 255:
-        raise ValueError(f"mask_bits must be a byte (got {bits!r})")
-    if strategy not in STRATEGIES:
-        raise ValueError(f"masking_strategy must be one of {tuple(STRATEGIES)} (got {strategy!r})")
-    if not -32768 <= int(no_data_value) <= 32767:
-        raise ValueError(f"no_data_value must fit int16 (got {no_data_value!r})")
-    if clip is not None and not (len(clip) == 2 and -32768 <= int(clip[0]) <= int(clip[1]) <= 32767):
-        raise ValueError(f"clip must be None or (lo, hi) inside int16 with lo <= hi (got {clip!r})")
     o = np.asarray(origins)
     if o.size and o.dtype.kind not in "iu":
         raise ValueError("origins must be integers")
@@ -191,7 +168,7 @@ def cut(tile, fmask, origins, chip_size: int, dates: Optional[int] = None, mask:
     twin and gives arrays."""
     bits = mask if isinstance(mask, (int, np.integer)) and not isinstance(mask, bool) else mask_bits(mask)
     T = int(dates) if dates is not None else (int(fmask.shape[0]) if fmask is not None else 1)
-    dev = _is_device(tile)
+    dev = is_device(tile)
     if not dev:
         tile = np.asarray(tile.cpu() if hasattr(tile, "cpu") else tile)
         fmask = None if fmask is None else np.asarray(fmask.cpu() if hasattr(fmask, "cpu") else fmask)
@@ -215,7 +192,7 @@ def label_maps(origins, chip_size: int, ptr, pts, labels, window_size: int = 0, 
     if task_type not in ("seg", "reg"):
         raise ValueError(f"task_type must be seg or reg (got {task_type!r})")
     dt = np.int16 if task_type == "seg" else np.float32
-    dev = _is_device(validity) if validity is not None else device is not None
+    dev = is_device(validity) if validity is not None else device is not None
     S, w, K = int(chip_size), window_size, int(num_classes)
     strat = label_strategy if validity is not None else None
     lab_host = np.asarray(labels)
@@ -288,32 +265,7 @@ def group_points(rows, cols, tx, ty, index, chip_size: int, shape: Tuple[int, in
 # ---- files -> files -------------------------------------------------------------------------------------------------------------------------
 def tile_id_of(first_tile_file: str) -> str:
     """The reference's tile id of an HLS file name: fields 1..3 of ``HLS.S30.T38PMB.2022145T072619.v2.0.B02.tif``."""
-    parts = os.path.basename(str(first_tile_file)).split(".")
-    if len(parts) < 4:
-        raise ValueError(f"{first_tile_file}: not an HLS file name (HLS.<sensor>.<tile>.<date>...)")
-    return f"{parts[1]}_{parts[2]}_{parts[3]}"
-
-
-def _date_of_name(first_tile_file: str) -> str:
-    stamp = os.path.basename(str(first_tile_file)).split(".")[3]
-    d = datetime.datetime.strptime(stamp[:7], "%Y%j")
-    return d.strftime("%Y%m%d")
-
-
-def _read_stack(files: Sequence[str], what: str, dtype) -> Tuple[np.ndarray, Dict[str, Any]]:
-    planes, first = [], None
-    for f in files:
-        a, prof = tiff.read(str(f))
-        if first is None:
-            first = prof
-        if a.shape[1:] != planes[0].shape[1:] if planes else False:
-            raise ValueError(f"{f}: {a.shape[1]} x {a.shape[2]} pixels, {files[0]} has {planes[0].shape[1]} x {planes[0].shape[2]}")
-        if a.dtype != dtype:
-            if a.dtype.kind not in "iu" or a.size and (a.min() < np.iinfo(dtype).min or a.max() > np.iinfo(dtype).max):
-                raise ValueError(f"{f}: {what} samples must fit {np.dtype(dtype).name} (got {a.dtype.name})")
-            a = a.astype(dtype)
-        planes.append(a)
-    return np.ascontiguousarray(np.concatenate(planes, axis=0)), first
+    return "_".join(prep.hls_name(first_tile_file))
 
 
 def _read_points(points) -> Dict[str, np.ndarray]:
@@ -329,13 +281,9 @@ def _read_points(points) -> Dict[str, np.ndarray]:
 
 def _chip_profile(profile: Dict[str, Any], grid, r0: int, c0: int) -> Dict[str, Any]:
     X0, Y0, sx, sy = grid
-    tags = {k: v for k, v in profile["tags"].items() if k in _GEO_TAGS}
+    tags = prep.geo_tags(profile["tags"], tiepoint=False)
     tags[33922] = (12, (0.0, 0.0, 0.0, X0 + c0 * sx, Y0 - r0 * sy, 0.0))
     return {"tags": tags, "nodata": None}
-
-
-def _to_host(a):
-    return a.cpu().numpy() if hasattr(a, "cpu") else a
 
 
 def create_chips(tile_files: Sequence[str], fmask_files: Optional[Sequence[str]], points, output_directory: str, chip_size: int = 256,
@@ -363,8 +311,7 @@ def create_chips(tile_files: Sequence[str], fmask_files: Optional[Sequence[str]]
         raise ValueError(f"masking_strategy must be one of {tuple(STRATEGIES)} (got {masking_strategy!r})")
     if task_type not in ("seg", "reg"):
         raise ValueError(f"task_type must be seg or reg (got {task_type!r})")
-    if device is not None and not str(device).startswith("cuda"):
-        raise ValueError(f"device must be None (host) or a cuda device (got {device!r})")
+    prep.check_device(device)
     if not tile_files:
         raise ValueError("create_chips needs at least one tile file")
     use_mask = bool(bits) and fmask_files
@@ -374,15 +321,15 @@ def create_chips(tile_files: Sequence[str], fmask_files: Optional[Sequence[str]]
     if len(tile_files) % T:
         raise ValueError(f"{len(tile_files)} band files do not divide into {T} dates")
     tile_id = tile_id_of(tile_files[0])
-    tile, profile = _read_stack(tile_files, "tile", np.int16)
-    fmask = _read_stack(fmask_files, "Fmask", np.uint8)[0] if use_mask else None
+    tile, profile = prep.read_stack(tile_files, "tile", np.int16)
+    fmask = prep.read_stack(fmask_files, "Fmask", np.uint8)[0] if use_mask else None
     H, W = tile.shape[1:]
     grid = warp.grid_of(profile, str(tile_files[0]))
     stats: Dict[str, Any] = {"nominated": 0, "kept": 0, "dropped": {"out_of_bounds": 0, "existing": 0, "no_valid_values": 0, "no_valid_labels": 0}}
     bbox = points is None
     if bbox:
         chip_xy = np.array([(cx, cy) for cx in range(W // S) for cy in range(H // S)], dtype=np.int64).reshape(-1, 2)
-        date_id = date or _date_of_name(tile_files[0])
+        date_id = date or prep.hls_date(tile_files[0])
         ptr = pts = labels = None
     else:
         tab = _read_points(points)
@@ -409,16 +356,10 @@ def create_chips(tile_files: Sequence[str], fmask_files: Optional[Sequence[str]]
     segs_out: List[Optional[str]] = []
     hist_sum = None
     if sel.size:
-        if device is not None:
-            import torch
-
-            t_dev = torch.from_numpy(tile).to(device)
-            f_dev = None if fmask is None else torch.from_numpy(fmask).to(device)
-        else:
-            t_dev, f_dev = tile, fmask
+        t_dev, f_dev = prep.stage(tile, fmask, device)
         chips, valid_values, validity = cut(t_dev, f_dev, origins, S, dates=T, mask=bits, strategy=masking_strategy,
                                             no_data_value=no_data_value, clip=(0, 10000) if bbox else None)
-        valid_values = _to_host(valid_values)
+        valid_values = to_host(valid_values)
         maps = valid_labels = None
         if not bbox:
             # the lists of the chips that are cut: the rows of the fresh ones, re-based
@@ -431,10 +372,10 @@ def create_chips(tile_files: Sequence[str], fmask_files: Optional[Sequence[str]]
                 K = int(min(max(int(np.max(lab)) + 1, 1), MAX_CLASSES)) if lab.size else 1
             maps, valid_labels, hist = label_maps(origins, S, sub_ptr, pts[take.astype(np.int64)], lab, window_size, validity, "any",
                                                   task_type, K if task_type == "seg" else 0)
-            maps, valid_labels = _to_host(maps), _to_host(valid_labels)
+            maps, valid_labels = to_host(maps), to_host(valid_labels)
             if hist is not None:
                 hist_sum = np.zeros(K, dtype=np.int64)
-                hist = _to_host(hist)
+                hist = to_host(hist)
         for k, i in enumerate(sel.tolist()):
             if valid_values[k] == 0:
                 stats["dropped"]["no_valid_values"] += 1
@@ -443,7 +384,7 @@ def create_chips(tile_files: Sequence[str], fmask_files: Optional[Sequence[str]]
                 stats["dropped"]["no_valid_labels"] += 1
                 continue
             prof = _chip_profile(profile, grid, int(origins[k, 0]), int(origins[k, 1]))
-            chip = _to_host(chips[k])
+            chip = to_host(chips[k])
             if bbox:
                 tiff.write(os.path.join(chip_dir, names[i][0]), chip.astype(np.uint16), prof)
                 segs_out.append(None)
@@ -455,39 +396,11 @@ def create_chips(tile_files: Sequence[str], fmask_files: Optional[Sequence[str]]
                     hist_sum += hist[k]
             chips_out.append(names[i][0])
     stats["kept"] = len(chips_out)
-    _write_dataset_csv(output_directory, chips_out, segs_out, bbox)
+    prep.write_dataset_csv(output_directory, chips_out, segs_out, bbox)
     if hist_sum is not None:
-        from .pipeline_utils import compute_class_weights
-
-        present = {c: int(v) for c, v in enumerate(hist_sum.tolist()) if v}
-        stats["class_histogram"] = [int(v) for v in hist_sum.tolist()]
-        stats["class_weights"] = compute_class_weights(present) if present else []
-    with open(os.path.join(output_directory, "chips_stats.json"), "w") as f:
-        json.dump(stats, f, sort_keys=True)
+        stats.update(prep.class_stats(hist_sum))
+    prep.write_stats(os.path.join(output_directory, "chips_stats.json"), stats)
     return chips_out, segs_out
-
-
-def _write_dataset_csv(output_directory: str, chips: List[str], segs: List[Optional[str]], bbox: bool) -> str:
-    """``chips_dataset.csv``: the rows already there plus the new pairs (``Input`` [, ``Label``], paths relative to the folder)."""
-    import csv
-
-    path = os.path.join(output_directory, "chips_dataset.csv")
-    header = ["Input"] if bbox else ["Input", "Label"]
-    rows: List[List[str]] = []
-    if os.path.exists(path):
-        with open(path, newline="") as f:
-            old = list(csv.reader(f))
-        if old and old[0] == header:
-            rows = old[1:]
-    for c, s in zip(chips, segs):
-        row = [f"chips/{c}"] if bbox else [f"chips/{c}", f"seg_maps/{s}"]
-        if row not in rows:
-            rows.append(row)
-    with open(path, "w", newline="") as f:
-        wr = csv.writer(f)
-        wr.writerow(header)
-        wr.writerows(rows)
-    return path
 
 
 # ---- mode=create_chips ---------------------------------------------------------------------------------------------------------------------
@@ -498,46 +411,23 @@ CONFIG_KEYS = ("chip_size", "mask_types", "masking_strategy", "window_size", "ta
 def chips_options(cfg: Dict[str, Any]) -> Dict[str, Any]:
     """The ``chips.*`` keys of ``mode=create_chips`` checked -> the keyword arguments of :func:`create_chips`.  A bad value raises
     ValueError; ``tiles`` and ``output_directory`` are required only in that mode."""
-    c = dict(cfg.get("chips") or {})
-    unknown = set(c) - set(CONFIG_KEYS)
-    if unknown:
-        raise ValueError(f"unknown chips keys {sorted(unknown)}")
-
-    def listing(v, name):
-        if v is None or v == "None":
-            return None
-        if isinstance(v, str):
-            v = [s for s in v.split(",") if s]
-        if not isinstance(v, (list, tuple)) or not all(isinstance(s, str) for s in v):
-            raise ValueError(f"chips.{name} must be a list of names (got {v!r})")
-        return list(v)
-
-    size, w = c.get("chip_size", 256), c.get("window_size", 0)
-    if isinstance(size, bool) or not isinstance(size, int) or size < 1:
-        raise ValueError(f"chips.chip_size must be an int >= 1 (got {size!r})")
-    if isinstance(w, bool) or not isinstance(w, int) or not 0 <= w <= MAX_WINDOW:
-        raise ValueError(f"chips.window_size must be an int >= 0 (got {w!r})")
-    types = listing(c.get("mask_types", []), "mask_types") or []
+    c = prep.Section(cfg, "chips", CONFIG_KEYS)
+    size = c.integer("chip_size", 256, lo=1, what="must be an int >= 1")
+    w = c.integer("window_size", 0, lo=0, hi=MAX_WINDOW, what="must be an int >= 0")
+    types = c.listing("mask_types", []) or []
     mask_bits(types)
-    if c.get("masking_strategy", "each") not in STRATEGIES:
-        raise ValueError(f"chips.masking_strategy must be one of {tuple(STRATEGIES)} (got {c.get('masking_strategy')!r})")
-    if c.get("task_type", "seg") not in ("seg", "reg"):
-        raise ValueError(f"chips.task_type must be seg or reg (got {c.get('task_type')!r})")
-    src = c.get("src_crs", 4326)
-    if isinstance(src, bool) or not isinstance(src, int):
-        raise ValueError(f"chips.src_crs must be an EPSG code (got {src!r})")
-    crsmod.from_epsg(src)
-    tiles, fmasks = listing(c.get("tiles"), "tiles"), listing(c.get("fmasks"), "fmasks")
-    records, out = c.get("records_file"), c.get("output_directory")
-    records = None if records in (None, "None") else str(records)
-    out = None if out in (None, "None") else str(out)
+    strategy = c.choice("masking_strategy", "each", STRATEGIES)
+    task = c.choice("task_type", "seg", ("seg", "reg"), "must be seg or reg")
+    src = c.epsg("src_crs", 4326)
+    tiles, fmasks = c.listing("tiles"), c.listing("fmasks")
+    records, out = c.text("records_file"), c.text("output_directory")
     if cfg.get("mode") == "create_chips":
         if not tiles or out is None:
             raise ValueError("mode=create_chips needs chips.tiles and chips.output_directory")
         if types and not fmasks:
             raise ValueError("chips.mask_types needs chips.fmasks (one Fmask file per date)")
     return dict(tile_files=tiles, fmask_files=fmasks, points=records, output_directory=out, chip_size=size, mask_types=types,
-                masking_strategy=c.get("masking_strategy", "each"), window_size=w, task_type=c.get("task_type", "seg"), src_crs=src)
+                masking_strategy=strategy, window_size=w, task_type=task, src_crs=src)
 
 
 def run_from_config(cfg: Dict[str, Any], device: Optional[str] = None) -> int:
@@ -551,19 +441,7 @@ def run_from_config(cfg: Dict[str, Any], device: Optional[str] = None) -> int:
 
 def main(argv: Optional[List[str]] = None) -> int:
     """``python -m instageo_amd.chips chips.tiles=a.tif,b.tif chips.output_directory=out ...``: mode=create_chips without ``run.py``."""
-    import sys
-
-    from .config import load_config
-
-    cfg = load_config("config", ["mode=create_chips"] + list(sys.argv[1:] if argv is None else argv))
-    dev = None
-    try:
-        import torch
-
-        dev = "cuda" if torch.cuda.is_available() else None
-    except ImportError:
-        pass
-    return run_from_config(cfg, dev)
+    return prep.run_mode_cli("create_chips", run_from_config, argv)
 
 
 if __name__ == "__main__":

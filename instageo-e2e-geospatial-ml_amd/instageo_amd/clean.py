@@ -29,21 +29,14 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import crs as crsmod
-from . import tiff, warp
+from . import prep, tiff, warp
+from .prep import is_device, to_device, to_host
 
 STRATEGIES = {"any": 0, "all": 1}  # the column of counts, the bit of the plane
 METHODS = ("buffer", "limit")
 MAX_WINDOW = 32
 MAX_CLASSES = 256
 BATCH_FILES = 256  # files of one shape and dtype per launch
-
-
-def _is_device(a) -> bool:
-    return type(a).__module__.startswith("torch") and bool(getattr(a, "is_cuda", False))
-
-
-def _host(a) -> np.ndarray:
-    return np.asarray(a.cpu() if hasattr(a, "cpu") else a)
 
 
 # ---- argument checks shared by the host path and the device wrappers (ops.chip_nodata / label_buffer / label_limit) --------------------------
@@ -145,11 +138,11 @@ def nodata_planes(chips, no_data_value: int):
     """``chips`` (n, B, H, W) int16 | uint16 -> (plane (n, H, W) uint8: bit 0 = any of the pixel's B values equals ``no_data_value``, bit
     1 = all do; counts (n, 2) int32: the chip's any and all pixels).  A value the dtype cannot hold matches nothing.  Tensors on the device
     go through ``ig_chip_nodata`` and give device tensors; anything else takes numpy and gives arrays."""
-    if _is_device(chips):
+    if is_device(chips):
         from . import ops
 
         return ops.chip_nodata(chips, no_data_value)
-    a = _host(chips)
+    a = to_host(chips)
     pattern = check_nodata(a.shape, a.dtype.name, no_data_value)
     n, _, H, W = a.shape
     if pattern is None:
@@ -164,7 +157,7 @@ def dropped(counts, pixels: int, strategy: str, no_data_threshold: float) -> np.
     """The chips to drop: ``count[strategy] / float(H * W) > no_data_threshold`` in float64, as ``np.mean(mask) > threshold`` is."""
     if strategy not in STRATEGIES:
         raise ValueError(f"drop_chips_strategy must be one of {tuple(STRATEGIES)} (got {strategy!r})")
-    c = _host(counts).astype(np.int64).reshape(-1, 2)[:, STRATEGIES[strategy]]
+    c = to_host(counts).astype(np.int64).reshape(-1, 2)[:, STRATEGIES[strategy]]
     return c / float(pixels) > float(no_data_threshold)
 
 
@@ -172,13 +165,13 @@ def buffer_labels(labels, window_size: int, ignore_index: int, plane=None, num_c
     """``labels`` (n, H, W) int16 | float32 buffered by the rule of the module docstring; ``plane``: that of :func:`nodata_planes` (None:
     no masking) -> (out like labels, valid_labels (n,) int32, hist (n, num_classes) int32 or None).  Tensors on the device go through
     ``ig_label_buffer``; anything else takes the numpy twin."""
-    if _is_device(labels):
+    if is_device(labels):
         from . import ops
 
         return ops.label_buffer(labels, window_size, ignore_index, plane, int(num_classes))
-    a = _host(labels)
+    a = to_host(labels)
     check_label_args(a.shape, a.dtype.name, ignore_index, num_classes, window_size)
-    p = None if plane is None else _host(plane)
+    p = None if plane is None else to_host(plane)
     if p is not None and (p.dtype != np.uint8 or p.shape != a.shape):
         raise ValueError(f"plane must be uint8 of the labels' shape {a.shape} (got {p.dtype} {p.shape})")
     return _buffer_host(a, int(window_size), int(ignore_index), p, int(num_classes))
@@ -187,11 +180,11 @@ def buffer_labels(labels, window_size: int, ignore_index: int, plane=None, num_c
 def limit_labels(labels, ptr, pts, ignore_index: int, num_classes: int = 0):
     """``labels`` (n, H, W) int16 | float32 limited to the points ``pts`` ((P, 2): row, col) grouped by map through ``ptr`` (CSR, host
     arrays) -> (out, valid_labels, hist) as :func:`buffer_labels`.  Tensors on the device go through ``ig_label_limit``."""
-    if _is_device(labels):
+    if is_device(labels):
         from . import ops
 
         return ops.label_limit(labels, ptr, pts, ignore_index, int(num_classes))
-    a = _host(labels)
+    a = to_host(labels)
     check_label_args(a.shape, a.dtype.name, ignore_index, num_classes)
     p, q = check_points(a.shape[0], a.shape[1], a.shape[2], ptr, pts)
     return _limit_host(a, p, q, int(ignore_index), int(num_classes))
@@ -252,14 +245,6 @@ def _batches(paths: Sequence[str]):
             yield idx, np.stack(arrays), profs
 
 
-def _to_device(a: np.ndarray, device):
-    if device is None:
-        return a
-    import torch
-
-    return torch.from_numpy(a).to(device)
-
-
 def _planes_of(paths: Sequence[str], no_data_value: int, device):
     """-> (planes: one (H, W) uint8 host array per chip file, counts (n, 2) int64, pixels (n,))."""
     n = len(paths)
@@ -268,8 +253,8 @@ def _planes_of(paths: Sequence[str], no_data_value: int, device):
     for idx, stack, _ in _batches(paths):
         if stack.dtype.name not in ("int16", "uint16"):
             raise ValueError(f"{paths[idx[0]]}: chips must be int16 or uint16 (got {stack.dtype.name})")
-        plane, cnt = nodata_planes(_to_device(stack, device), no_data_value)
-        plane, cnt = _host(plane), _host(cnt)
+        plane, cnt = nodata_planes(to_device(stack, device), no_data_value)
+        plane, cnt = to_host(plane), to_host(cnt)
         for k, i in enumerate(idx):
             planes[i], counts[i], pixels[i] = plane[k], cnt[k], plane[k].size
     return planes, counts, pixels
@@ -302,14 +287,13 @@ def clean_data(chips_dataset_csv: str, output_chips_dataset_csv: str, drop_chips
         raise ValueError(f"no_data_threshold must lie in [0, 1] (got {no_data_threshold!r})")
     if isinstance(window_size, bool) or int(window_size) != window_size or not 1 <= int(window_size) <= MAX_WINDOW:
         raise ValueError(f"window_size must be an int in [1, {MAX_WINDOW}] (got {window_size!r})")
-    if device is not None and not str(device).startswith("cuda"):
-        raise ValueError(f"device must be None (host) or a cuda device (got {device!r})")
+    prep.check_device(device)
     if clean_seg_maps and cleaning_method == "limit" and not observation_points_csv:
         raise ValueError("Observation points CSV is required for `limit` cleaning method")
     df = pd.read_csv(chips_dataset_csv)
     if not all(col in df.columns for col in ("Input", "Label")):
         raise ValueError("CSV must contain 'Input' and 'Label' columns")
-    root = root_dir if root_dir not in (None, "None") else os.path.dirname(os.path.abspath(chips_dataset_csv))
+    root = root_dir if prep.none(root_dir) is not None else os.path.dirname(os.path.abspath(chips_dataset_csv))
     full = lambda p: p if os.path.isabs(str(p)) else os.path.join(root, str(p))  # noqa: E731
     inputs, labels = [str(v) for v in df["Input"]], [str(v) for v in df["Label"]]
     keep = np.ones(len(df), dtype=bool)
@@ -353,7 +337,7 @@ def clean_data(chips_dataset_csv: str, output_chips_dataset_csv: str, drop_chips
                 pl = np.stack([planes[r] for r in members])
                 if pl.shape != work.shape:
                     raise ValueError(f"{labels[members[0]]}: a label map of {work.shape[1:]} pixels does not go with a chip of {pl.shape[1:]}")
-                out, _, hist = buffer_labels(_to_device(work, device), int(window_size), int(ignore_index), _to_device(pl, device), K)
+                out, _, hist = buffer_labels(to_device(work, device), int(window_size), int(ignore_index), to_device(pl, device), K)
             else:
                 lists = [locate_observations(obs, labels[r], prof) for r, prof in zip(members, profs)]
                 have = [k for k, q in enumerate(lists) if q is not None]
@@ -365,10 +349,10 @@ def clean_data(chips_dataset_csv: str, output_chips_dataset_csv: str, drop_chips
                     continue
                 members, profs, work = [members[k] for k in have], [profs[k] for k in have], np.ascontiguousarray(work[have])
                 ptr = np.concatenate([[0], np.cumsum([lists[k].shape[0] for k in have])])
-                out, _, hist = limit_labels(_to_device(work, device), ptr, np.concatenate([lists[k] for k in have]), int(ignore_index), K)
-            out = _host(out)
+                out, _, hist = limit_labels(to_device(work, device), ptr, np.concatenate([lists[k] for k in have]), int(ignore_index), K)
+            out = to_host(out)
             if hist is not None:
-                hist_all[:K] += _host(hist).astype(np.int64).sum(axis=0)
+                hist_all[:K] += to_host(hist).astype(np.int64).sum(axis=0)
             for k, r in enumerate(members):
                 cleaned.append((r, out[k].astype(file_dt, copy=False), profs[k]))
         new_labels = list(labels)
@@ -384,16 +368,11 @@ def clean_data(chips_dataset_csv: str, output_chips_dataset_csv: str, drop_chips
     df = df[keep]
     stats["rows_out"] = int(len(df))
     if hist_sum is not None:
-        from .pipeline_utils import compute_class_weights
-
-        present = {c: int(v) for c, v in enumerate(hist_sum.tolist()) if v}
-        stats["class_histogram"] = [int(v) for v in hist_sum.tolist()]
-        stats["class_weights"] = compute_class_weights(present) if present else []
+        stats.update(prep.class_stats(hist_sum))
     out_dir = os.path.dirname(os.path.abspath(output_chips_dataset_csv))
     os.makedirs(out_dir, exist_ok=True)
     df.to_csv(output_chips_dataset_csv, index=False)
-    with open(os.path.join(out_dir, "clean_stats.json"), "w") as f:
-        json.dump(stats, f, sort_keys=True)
+    prep.write_stats(os.path.join(out_dir, "clean_stats.json"), stats)
     return stats
 
 
@@ -406,47 +385,17 @@ CONFIG_KEYS = ("chips_dataset_csv", "output_chips_dataset_csv", "drop_chips", "d
 def clean_options(cfg: Dict[str, Any]) -> Dict[str, Any]:
     """The ``clean.*`` keys of ``mode=clean_chips`` checked -> the keyword arguments of :func:`clean_data`.  A bad value raises ValueError;
     the two CSV paths are required only in that mode."""
-    c = dict(cfg.get("clean") or {})
-    unknown = set(c) - set(CONFIG_KEYS)
-    if unknown:
-        raise ValueError(f"unknown clean keys {sorted(unknown)}")
-
-    def path(name):
-        v = c.get(name)
-        return None if v in (None, "None") else str(v)
-
-    def flag(name):
-        v = c.get(name, False)
-        if not isinstance(v, bool):
-            raise ValueError(f"clean.{name} must be true or false (got {v!r})")
-        return v
-
-    def integer(name, default):
-        v = c.get(name, default)
-        if isinstance(v, bool) or not isinstance(v, int):
-            raise ValueError(f"clean.{name} must be an int (got {v!r})")
-        return v
-
-    strategy, method = c.get("drop_chips_strategy", "any"), c.get("cleaning_method", "buffer")
-    if strategy not in STRATEGIES:
-        raise ValueError(f"clean.drop_chips_strategy must be one of {tuple(STRATEGIES)} (got {strategy!r})")
-    if method not in METHODS:
-        raise ValueError(f"clean.cleaning_method must be one of {METHODS} (got {method!r})")
-    thr = c.get("no_data_threshold", 0.5)
-    if isinstance(thr, bool) or not isinstance(thr, (int, float)) or not 0.0 <= float(thr) <= 1.0:
-        raise ValueError(f"clean.no_data_threshold must lie in [0, 1] (got {thr!r})")
-    w = integer("window_size", 1)
-    if not 1 <= w <= MAX_WINDOW:
-        raise ValueError(f"clean.window_size must lie in [1, {MAX_WINDOW}] (got {w!r})")
-    K = c.get("num_classes")
-    K = None if K in (None, "None") else K
-    if K is not None and (isinstance(K, bool) or not isinstance(K, int) or not 1 <= K <= MAX_CLASSES):
-        raise ValueError(f"clean.num_classes must be None or an int in [1, {MAX_CLASSES}] (got {K!r})")
-    opts = dict(chips_dataset_csv=path("chips_dataset_csv"), output_chips_dataset_csv=path("output_chips_dataset_csv"),
-                drop_chips=flag("drop_chips"), drop_chips_strategy=strategy, no_data_threshold=float(thr),
-                no_data_value=integer("no_data_value", -9999), clean_seg_maps=flag("clean_seg_maps"), cleaning_method=method,
-                observation_points_csv=path("observation_points_csv"), seg_map_output_dir=path("seg_map_output_dir"),
-                ignore_index=integer("ignore_index", -1), window_size=w, num_classes=K, root_dir=path("root_dir"))
+    c = prep.Section(cfg, "clean", CONFIG_KEYS)
+    strategy = c.choice("drop_chips_strategy", "any", STRATEGIES)
+    method = c.choice("cleaning_method", "buffer", METHODS)
+    thr = c.number("no_data_threshold", 0.5, lambda x: 0.0 <= x <= 1.0, "must lie in [0, 1]")
+    w = c.integer("window_size", 1, lo=1, hi=MAX_WINDOW, span=f"must lie in [1, {MAX_WINDOW}]")
+    K = c.integer("num_classes", None, lo=1, hi=MAX_CLASSES, what=f"must be None or an int in [1, {MAX_CLASSES}]", optional=True)
+    opts = dict(chips_dataset_csv=c.text("chips_dataset_csv"), output_chips_dataset_csv=c.text("output_chips_dataset_csv"),
+                drop_chips=c.flag("drop_chips"), drop_chips_strategy=strategy, no_data_threshold=thr,
+                no_data_value=c.integer("no_data_value", -9999), clean_seg_maps=c.flag("clean_seg_maps"), cleaning_method=method,
+                observation_points_csv=c.text("observation_points_csv"), seg_map_output_dir=c.text("seg_map_output_dir"),
+                ignore_index=c.integer("ignore_index", -1), window_size=w, num_classes=K, root_dir=c.text("root_dir"))
     if cfg.get("mode") == "clean_chips":
         if opts["chips_dataset_csv"] is None or opts["output_chips_dataset_csv"] is None:
             raise ValueError("mode=clean_chips needs clean.chips_dataset_csv and clean.output_chips_dataset_csv")
@@ -467,19 +416,7 @@ def run_from_config(cfg: Dict[str, Any], device: Optional[str] = None) -> int:
 def main(argv: Optional[List[str]] = None) -> int:
     """``python -m instageo_amd.clean clean.chips_dataset_csv=in.csv clean.output_chips_dataset_csv=out.csv ...``: mode=clean_chips
     without ``run.py``."""
-    import sys
-
-    from .config import load_config
-
-    cfg = load_config("config", ["mode=clean_chips"] + list(sys.argv[1:] if argv is None else argv))
-    dev = None
-    try:
-        import torch
-
-        dev = "cuda" if torch.cuda.is_available() else None
-    except ImportError:
-        pass
-    return run_from_config(cfg, dev)
+    return prep.run_mode_cli("clean_chips", run_from_config, argv)
 
 
 if __name__ == "__main__":

@@ -31,6 +31,7 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
 import numpy as np
 
 from . import tiff
+from .prep import is_device
 from .tiff import TiffError
 
 BLOCKSIZES = (128, 256, 512)
@@ -127,10 +128,6 @@ def class_histogram(classmap: np.ndarray, ncls: int, fill: int = -1) -> np.ndarr
     return np.bincount(idx, minlength=int(ncls) + 1).astype(np.int64)
 
 
-def _is_device(a) -> bool:
-    return type(a).__module__.startswith("torch") and bool(getattr(a, "is_cuda", False))
-
-
 def build_overviews(raster, kind: str = "mode", levels: Union[str, int] = "auto", fill: int = -1, blocksize: int = 256,
                     ncls: Optional[int] = None, counts=None) -> list:
     """-> [level 0 (``raster`` itself), level 1, ...], ready for :func:`write_cog`.  ``raster``: (H, W) or (bands, H, W); a HIP tensor goes
@@ -142,7 +139,7 @@ def build_overviews(raster, kind: str = "mode", levels: Union[str, int] = "auto"
         raise ValueError(f"kind must be 'mode' or 'mean' (got {kind!r})")
     if counts is not None and (kind != "mode" or ncls is None):
         raise ValueError("counts needs kind='mode' and ncls")
-    dev = _is_device(raster)
+    dev = is_device(raster)
     if not dev:
         raster = np.asarray(raster.cpu() if hasattr(raster, "cpu") else raster)
     want = "int8" if kind == "mode" else "float32"
@@ -211,7 +208,7 @@ def _tiles_host(a: np.ndarray, tile: int, pad_bits: int, predictor: int) -> np.n
 
 def _tile_bytes(level, tile: int, pad_bits: int, predictor: int) -> Tuple[List[bytes], int, int, int, np.dtype]:
     """-> (the raw bytes of the tiles in (band, ty, tx) order, bands, H, W, the little-endian dtype)."""
-    if _is_device(level):
+    if is_device(level):
         from . import ops
 
         t = level if level.dim() == 3 else level.unsqueeze(0)
@@ -259,7 +256,7 @@ def write_cog(path: str, levels: Sequence, profile: Optional[Dict[str, Any]] = N
     if len(levels) == 0:
         raise TiffError("write_cog needs at least level 0")
     first = levels[0]
-    dt0 = np.dtype(str(first.dtype).replace("torch.", "")) if _is_device(first) else np.asarray(first).dtype
+    dt0 = np.dtype(str(first.dtype).replace("torch.", "")) if is_device(first) else np.asarray(first).dtype
     if pred == 2 and dt0.kind == "f":
         raise TiffError("predictor 2 is for integer samples")
     tags = dict((profile or {}).get("tags", {}))

@@ -37,6 +37,7 @@ from . import cog as cogmod
 from . import crs as crsmod
 from . import tiff
 from . import warp as warpmod
+from .prep import is_device
 
 R = 6378137.0
 ORIGIN = math.pi * R  # 20037508.342789244: the web Mercator square spans +-ORIGIN
@@ -236,10 +237,6 @@ def ramp_lut(colors=None) -> np.ndarray:
 
 
 # ---- rendering -------------------------------------------------------------------------------------------------------------------------
-def _is_device(a) -> bool:
-    return type(a).__module__.startswith("torch") and bool(getattr(a, "is_cuda", False))
-
-
 def ramp_index(v: np.ndarray, lo: float, hi: float) -> np.ndarray:
     """rint(clamp((float64(v) - lo) / (hi - lo), 0, 1) * 255) as int64 (NaN -> 0: the caller masks it)."""
     with np.errstate(invalid="ignore", over="ignore"):
@@ -313,7 +310,7 @@ def render(levels, profile: Dict[str, Any], tiles: Sequence[Tuple[int, int, int]
         raise ValueError("a pyramid has at least level 0")
     style = _check_style(levels, style)
     tile = check_tile_size(tile)
-    dev = _is_device(levels[0])
+    dev = is_device(levels[0])
     if not dev:
         levels = [np.asarray(lv.cpu() if hasattr(lv, "cpu") else lv) for lv in levels]
     H, W = (int(v) for v in levels[0].shape[-2:])
@@ -354,7 +351,7 @@ def render(levels, profile: Dict[str, Any], tiles: Sequence[Tuple[int, int, int]
 def finite_range(raster) -> Tuple[float, float]:
     """(lo, hi): the finite minimum and maximum of ``raster`` (array or tensor); hi = lo + 1 where they coincide, (0, 1) where nothing
     is finite."""
-    if _is_device(raster):
+    if is_device(raster):
         import torch
 
         ok = torch.isfinite(raster)
@@ -457,13 +454,13 @@ def load_pyramid(raster, profile=None, kind: Optional[str] = None, fill: int = -
             raise ValueError(f"map tiles render int8 class maps and float32 rasters (got {name})")
         if raster.ndim == 3 and raster.shape[0] == 1:
             raster = raster[0]
-        if device is not None and not _is_device(raster):  # level 0 goes up first, so that the pyramid comes from the kernels of cog.hip
+        if device is not None and not is_device(raster):  # level 0 goes up first, so that the pyramid comes from the kernels of cog.hip
             import torch
 
             raster = torch.from_numpy(np.ascontiguousarray(raster)).to(device)
         levels = cogmod.build_overviews(raster, kind, "auto", fill, blocksize=tile)
     levels = [lv[0] if lv.ndim == 3 and lv.shape[0] == 1 else lv for lv in levels]
-    if device is not None and not _is_device(levels[0]):
+    if device is not None and not is_device(levels[0]):
         import torch
 
         levels = [torch.from_numpy(np.ascontiguousarray(lv)).to(device) for lv in levels]
@@ -508,7 +505,7 @@ def export(raster, out_dir: str, profile=None, style: Optional[str] = None, tile
     t = {"pyramid": time.perf_counter() - t0, "render": 0.0, "readback": 0.0, "png": 0.0}
     written: List[str] = []
     os.makedirs(out_dir, exist_ok=True)
-    dev = _is_device(levels[0])
+    dev = is_device(levels[0])
     for z in range(zmin, zmax + 1):
         tiles = covering_tiles(profile, shape, z)
         per = max(1, BATCH_PIXELS // (tile * tile))

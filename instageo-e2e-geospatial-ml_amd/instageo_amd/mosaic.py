@@ -35,6 +35,7 @@ import numpy as np
 
 from . import cog as cogmod
 from . import postprocess, tiff, vectorize, zonal
+from .prep import is_device
 
 RULES = ("last", "first", "mode", "mean")
 BLOCK = 64  # side of the canvas block one workgroup owns (mosaic.hip), and of a bin
@@ -65,7 +66,7 @@ def check_rule(rule: str, dtype) -> None:
         raise ValueError(f"mosaic rule {rule!r} does not go with {name} rasters (int8: last | first | mode, float32: last | first | mean)")
 
 
-def _check_fill(fill: int) -> int:
+def check_fill(fill: int) -> int:
     if isinstance(fill, bool) or not isinstance(fill, (int, np.integer)) or not -128 <= int(fill) <= 127:
         raise ValueError(f"fill must be an int that fits int8 (got {fill!r})")
     return int(fill)
@@ -208,10 +209,6 @@ def _paste_host(chips: Sequence[np.ndarray], rects: np.ndarray, H: int, W: int, 
     return canvas, count
 
 
-def _is_device(a) -> bool:
-    return type(a).__module__.startswith("torch") and bool(getattr(a, "is_cuda", False))
-
-
 def paste(chips, rects, shape: Tuple[int, int], rule: str = "last", fill: int = -1, cover: bool = False):
     """The mosaic of ``chips`` (a list of 2-D arrays / tensors of one dtype, int8 or float32, or one (N, h, w) array) at ``rects``
     ((N, 4): row0, col0, h, w) on a canvas of ``shape`` by ``rule`` (the module docstring) -> the canvas, or (canvas, cover uint8) with
@@ -220,12 +217,12 @@ def paste(chips, rects, shape: Tuple[int, int], rule: str = "last", fill: int = 
     chips = list(chips)
     rects = np.asarray(rects, dtype=np.int64).reshape(-1, 4)
     H, W = int(shape[0]), int(shape[1])
-    fill = _check_fill(fill)
+    fill = check_fill(fill)
     if len(chips) != len(rects):
         raise ValueError(f"{len(chips)} chips but {len(rects)} rectangles")
     if not chips:
         raise ValueError("a mosaic needs at least one chip")
-    dev = _is_device(chips[0])
+    dev = is_device(chips[0])
     if not dev:
         chips = [np.asarray(c.cpu() if hasattr(c, "cpu") else c) for c in chips]
     if any(c.dtype != chips[0].dtype for c in chips):
@@ -287,8 +284,8 @@ class _Job(NamedTuple):
     t: Dict[str, float]  # wall seconds of the phases so far
 
 
-def _prepare(paths_or_folder, output_folder, rule, fill, num_classes, device, cog, cog_blocksize, overview_levels, cog_compress, min_region,
-             connectivity, sieve_passes, save_regions, save_polygons, zones, zone_id_property) -> _Job:
+def prepare(paths_or_folder, output_folder, rule, fill, num_classes, device, cog, cog_blocksize, overview_levels, cog_compress, min_region,
+            connectivity, sieve_passes, save_regions, save_polygons, zones, zone_id_property) -> _Job:
     """The first half of :func:`merge_predictions`: every option checked, the files read and placed, the output folder made."""
     from .infer_utils import OutputOptions
 
@@ -298,7 +295,7 @@ def _prepare(paths_or_folder, output_folder, rule, fill, num_classes, device, co
     opts.check(None)
     if rule not in RULES:
         raise ValueError(f"mosaic rule must be one of {RULES} (got {rule!r})")
-    fill = _check_fill(fill)
+    fill = check_fill(fill)
     if num_classes is not None and (isinstance(num_classes, bool) or int(num_classes) < 1):
         raise ValueError(f"num_classes must be a positive int or None (got {num_classes!r})")
     if device not in ("gpu", "cpu") and not str(device).startswith("cuda"):
@@ -336,7 +333,7 @@ def _prepare(paths_or_folder, output_folder, rule, fill, num_classes, device, co
                 products, paths, arrays, profiles, regression, groups, zone_list, t)
 
 
-def _paste_group(job: _Job, g: Group, rule: str, save_cover: bool):
+def paste_group(job: _Job, g: Group, rule: str, save_cover: bool):
     """The canvas of group ``g`` (and its cover, or None): on the host, or packed, uploaded and pasted by ``ig_mosaic_paste``."""
     mine = [job.arrays[i] for i in g.members]
     t0 = time.perf_counter()
@@ -355,7 +352,7 @@ def _paste_group(job: _Job, g: Group, rule: str, save_cover: bool):
     return res if save_cover else (res, None)
 
 
-def _write_canvas(job: _Job, canvas, cover, name: str, profile: Dict[str, Any], output_folder: str) -> List[str]:
+def write_canvas(job: _Job, canvas, cover, name: str, profile: Dict[str, Any], output_folder: str) -> List[str]:
     """One finished canvas (and its cover, or None) -> the class products, the raster, its statistics and the cover file under ``name``
     -> the written paths."""
     from .infer_utils import _output_path, _write_products, _write_raster, save_prediction
@@ -419,13 +416,13 @@ def merge_predictions(paths_or_folder: Union[str, Sequence[str]], output_folder:
 
     ``device="cpu"`` pastes and builds the pyramid on the host (the numpy twins of the kernels) and writes the same bytes; the class
     products run on the device only and are refused there."""
-    job = _prepare(paths_or_folder, output_folder, rule, fill, num_classes, device, cog, cog_blocksize, overview_levels, cog_compress, min_region,
-                   connectivity, sieve_passes, save_regions, save_polygons, zones, zone_id_property)
+    job = prepare(paths_or_folder, output_folder, rule, fill, num_classes, device, cog, cog_blocksize, overview_levels, cog_compress, min_region,
+                  connectivity, sieve_passes, save_regions, save_polygons, zones, zone_id_property)
     written: List[str] = []
     for k, g in enumerate(job.groups):
         name = "merged.tif" if len(job.groups) == 1 else f"merged_{k}.tif"
-        canvas, cover = _paste_group(job, g, rule, save_cover)
-        written += _write_canvas(job, canvas, cover, name, g.profile, output_folder)
+        canvas, cover = paste_group(job, g, rule, save_cover)
+        written += write_canvas(job, canvas, cover, name, g.profile, output_folder)
     TIMINGS.clear()
     TIMINGS.update(job.t)
     return written

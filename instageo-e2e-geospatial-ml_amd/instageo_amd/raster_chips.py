@@ -32,17 +32,15 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
-from . import chips as chipsmod
 from . import crs as crsmod
-from . import tiff, warp
-from .chips import STRATEGIES, VALID_BITS, mask_bits
+from . import prep, tiff, warp
+from .chips import VALID_BITS, mask_bits
+from .prep import MAX_DATES, STRATEGIES, is_device, to_host  # noqa: F401
 
-MAX_DATES = 32
 MAX_SIDE = 1 << 15
 MAX_CLASSES = 128  # cells of the class histogram: every non-negative int8
 HLS_NO_DATA = 0  # the reference's NO_DATA_VALUES.HLS
 SEG_NO_DATA = -1
-_GEO_TAGS = (33550, 33922, 34735, 34736, 34737)
 _BATCH_VALUES = 1 << 28  # chip values of one launch
 
 
@@ -65,28 +63,12 @@ def check_warp(tile_shape, fmask_shape, src_crs, src_grid, dst_crs, dst_grids, S
                clip, labels_shape, labels_dtype, valid_bit: int, K: int):
     """ValueError unless the arguments of a warped cut obey include/instageo_hip.h -> (src_crs (5,), src_grid (4,), dst_crs (5,),
     dst_grids (n, 4)) as float64 arrays.  A destination grid may be unusable (it gives a no-data chip); the stack's grid may not."""
-    if len(tile_shape) != 3:
-        raise ValueError(f"a tile is (T * C, H, W) (got shape {tuple(tile_shape)})")
-    TC, H, W = (int(v) for v in tile_shape)
     if isinstance(S, bool) or not isinstance(S, (int, np.integer)) or not 1 <= int(S) <= MAX_SIDE:
         raise ValueError(f"chip_size must be an int in [1, 2^15] (got {S!r})")
     S = int(S)
-    if not 1 <= T <= MAX_DATES or TC % T or TC < 1:
-        raise ValueError(f"{TC} bands do not divide into {T} dates (1 <= dates <= {MAX_DATES})")
-    if fmask_shape is not None and tuple(fmask_shape) != (T, H, W):
-        raise ValueError(f"fmask must be (T, H, W) = {(T, H, W)} (got {tuple(fmask_shape)})")
+    TC, H, W = prep.check_stack_args(tile_shape, fmask_shape, S, T, bits, strategy, no_data_value, clip)
     if H < 1 or W < 1 or H * W > 2**31 - 1:
         raise ValueError(f"a tile of {H} x {W} pixels is beyond 2^31 - 1 (source offsets are int32)")
-    if TC * S * S > 2**31 - 1:
-        raise ValueError(f"a chip of {TC} x {S} x {S} values is beyond 2^31 - 1 (valid_values is int32)")
-    if not 0 <= int(bits) <= 255:
-        raise ValueError(f"mask_bits must be a byte (got {bits!r})")
-    if strategy not in STRATEGIES:
-        raise ValueError(f"masking_strategy must be one of {tuple(STRATEGIES)} (got {strategy!r})")
-    if not -32768 <= int(no_data_value) <= 32767:
-        raise ValueError(f"no_data_value must fit int16 (got {no_data_value!r})")
-    if clip is not None and not (len(clip) == 2 and -32768 <= int(clip[0]) <= int(clip[1]) <= 32767):
-        raise ValueError(f"clip must be None or (lo, hi) inside int16 with lo <= hi (got {clip!r})")
     sg = np.ascontiguousarray(src_grid, dtype=np.float64).reshape(-1)
     if sg.shape[0] != 4 or not _grid_ok(sg):
         raise ValueError(f"src_grid = (X0, Y0, sx, sy) needs finite values and positive pixel sizes (got {tuple(sg)})")
@@ -177,7 +159,7 @@ def warp_cut(tile, fmask, src_crs, src_grid, dst_crs, dst_grids, chip_size: int,
     if label_strategy not in VALID_BITS:
         raise ValueError(f"label_strategy must be any, each or None (got {label_strategy!r})")
     bit = VALID_BITS[label_strategy] if labels is not None else 0
-    dev = chipsmod._is_device(tile)
+    dev = is_device(tile)
     name = lambda a: str(a.dtype).replace("torch.", "")  # noqa: E731
     if not dev:
         tile = np.asarray(tile.cpu() if hasattr(tile, "cpu") else tile)
@@ -241,10 +223,7 @@ def chip_names(label_filename: str, mgrs_tile_id: str) -> Tuple[str, str]:
 
 def mgrs_of(first_tile_file: str) -> str:
     """Field 2 of an HLS file name (``HLS.S30.T38PMB.2022145T072619.v2.0.B02.tif`` -> ``T38PMB``)."""
-    parts = os.path.basename(str(first_tile_file)).split(".")
-    if len(parts) < 4:
-        raise ValueError(f"{first_tile_file}: not an HLS file name (HLS.<sensor>.<tile>.<date>...)")
-    return parts[2]
+    return prep.hls_name(first_tile_file).tile
 
 
 def _read_records(records) -> List[Dict[str, Any]]:
@@ -279,10 +258,6 @@ def _seg_labels(a: np.ndarray, name: str) -> np.ndarray:
     return a.astype(np.int8)
 
 
-def _to_host(a):
-    return a.cpu().numpy() if hasattr(a, "cpu") else a
-
-
 def create_raster_chips(tile_files: Sequence[str], fmask_files: Optional[Sequence[str]], records, raster_path: Optional[str],
                         output_directory: str, chip_size: int = 256, mask_types: Sequence[str] = (), masking_strategy: str = "each",
                         src_crs: int = 4326, spatial_resolution: float = 0.0002694945852358564, qa_check: bool = True, task_type: str = "seg",
@@ -313,8 +288,7 @@ def create_raster_chips(tile_files: Sequence[str], fmask_files: Optional[Sequenc
         raise ValueError(f"masking_strategy must be one of {tuple(STRATEGIES)} (got {masking_strategy!r})")
     if task_type not in ("seg", "reg"):
         raise ValueError(f"task_type must be seg or reg (got {task_type!r})")
-    if device is not None and not str(device).startswith("cuda"):
-        raise ValueError(f"device must be None (host) or a cuda device (got {device!r})")
+    prep.check_device(device)
     if not tile_files:
         raise ValueError("create_raster_chips needs at least one tile file")
     if bits and not fmask_files:
@@ -326,8 +300,8 @@ def create_raster_chips(tile_files: Sequence[str], fmask_files: Optional[Sequenc
     T = len(fmask_files) if fmask_files else 1
     if len(tile_files) % T:
         raise ValueError(f"{len(tile_files)} band files do not divide into {T} dates")
-    tile, profile = chipsmod._read_stack(tile_files, "tile", np.int16)
-    fmask = chipsmod._read_stack(fmask_files, "Fmask", np.uint8)[0] if bits else None
+    tile, profile = prep.read_stack(tile_files, "tile", np.int16)
+    fmask = prep.read_stack(fmask_files, "Fmask", np.uint8)[0] if bits else None
     H, W = tile.shape[1:]
     src = crsmod.from_profile(profile)
     sgrid = warp.grid_of(profile, str(tile_files[0]))
@@ -337,7 +311,7 @@ def create_raster_chips(tile_files: Sequence[str], fmask_files: Optional[Sequenc
         if not bbox_feature_path:
             raise ValueError("is_bbox_feature needs bbox_feature_path")
         with open(bbox_feature_path) as f:
-            rows = grid_polygons(json.load(f), date or chipsmod._date_of_name(tile_files[0]), S, res)
+            rows = grid_polygons(json.load(f), date or prep.hls_date(tile_files[0]), S, res)
         for r in rows:
             r["mgrs_tile_id"] = None
     else:
@@ -387,20 +361,14 @@ def create_raster_chips(tile_files: Sequence[str], fmask_files: Optional[Sequenc
             bounds = (own[0], own[1] - S * own[3], own[0] + S * own[2], own[1])
             item["grid"] = snapped_grid(bounds, res) if snap else own
             item["labels"] = _seg_labels(lab[0], path) if task_type == "seg" else lab[0].astype(np.float32)
-            item["profile"] = {"tags": {k: v for k, v in lprof["tags"].items() if k in _GEO_TAGS}, "nodata": None}
+            item["profile"] = {"tags": prep.geo_tags(lprof["tags"], tiepoint=True), "nodata": None}
         if not _touches(dst, item["grid"], S, src, sgrid, H, W):
             stats["dropped"]["outside_tile"] += 1
             continue
         todo.append(item)
     hist_sum = np.zeros(MAX_CLASSES, dtype=np.int64) if not bbox and task_type == "seg" else None
     if todo:
-        if device is not None:
-            import torch
-
-            t_dev = torch.from_numpy(tile).to(device)
-            f_dev = None if fmask is None else torch.from_numpy(fmask).to(device)
-        else:
-            t_dev, f_dev = tile, fmask
+        t_dev, f_dev = prep.stage(tile, fmask, device)
         step = max(1, _BATCH_VALUES // (tile.shape[0] * S * S))
         for first in range(0, len(todo), step):
             part = todo[first : first + step]
@@ -408,7 +376,7 @@ def create_raster_chips(tile_files: Sequence[str], fmask_files: Optional[Sequenc
             out = warp_cut(t_dev, f_dev, src, sgrid, dst, [it["grid"] for it in part], S, dates=T, mask=bits, strategy=masking_strategy,
                            no_data_value=HLS_NO_DATA, clip=(0, 10000), labels=labels, label_strategy=masking_strategy if qa_check else None,
                            num_classes=MAX_CLASSES if hist_sum is not None else 0)
-            chips, valid_values, _, maps, valid_labels, hist = (None if o is None else _to_host(o) for o in out)
+            chips, valid_values, _, maps, valid_labels, hist = (None if o is None else to_host(o) for o in out)
             for k, it in enumerate(part):
                 if qa_check and valid_values[k] == 0:
                     stats["dropped"]["no_valid_values"] += 1
@@ -424,16 +392,10 @@ def create_raster_chips(tile_files: Sequence[str], fmask_files: Optional[Sequenc
                 chips_out.append(it["chip"])
                 segs_out.append(None if bbox else it["label"])
                 stats["kept"] += 1
-    chipsmod._write_dataset_csv(output_directory, chips_out, segs_out, bbox)
+    prep.write_dataset_csv(output_directory, chips_out, segs_out, bbox)
     if hist_sum is not None:
-        from .pipeline_utils import compute_class_weights
-
-        top = int(np.nonzero(hist_sum)[0].max()) + 1 if hist_sum.any() else 1
-        present = {c: int(v) for c, v in enumerate(hist_sum[:top].tolist()) if v}
-        stats["class_histogram"] = [int(v) for v in hist_sum[:top].tolist()]
-        stats["class_weights"] = compute_class_weights(present) if present else []
-    with open(os.path.join(output_directory, "raster_chips_stats.json"), "w") as f:
-        json.dump(stats, f, sort_keys=True)
+        stats.update(prep.class_stats(hist_sum, trim=True))
+    prep.write_stats(os.path.join(output_directory, "raster_chips_stats.json"), stats)
     return chips_out, segs_out
 
 
@@ -445,52 +407,20 @@ CONFIG_KEYS = ("tiles", "fmasks", "records_file", "raster_path", "output_directo
 def raster_chips_options(cfg: Dict[str, Any]) -> Dict[str, Any]:
     """The ``raster_chips.*`` keys of ``mode=create_raster_chips`` checked -> the keyword arguments of :func:`create_raster_chips`.  An
     unknown key or a bad value raises ValueError; the files are required only in that mode."""
-    c = dict(cfg.get("raster_chips") or {})
-    unknown = set(c) - set(CONFIG_KEYS)
-    if unknown:
-        raise ValueError(f"unknown raster_chips keys {sorted(unknown)}")
-
-    def listing(v, name):
-        if v is None or v == "None":
-            return None
-        if isinstance(v, str):
-            v = [s for s in v.split(",") if s]
-        if not isinstance(v, (list, tuple)) or not all(isinstance(s, str) for s in v):
-            raise ValueError(f"raster_chips.{name} must be a list of names (got {v!r})")
-        return list(v)
-
-    def text(name):
-        v = c.get(name)
-        return None if v in (None, "None") else str(v)
-
-    def flag(name, default):
-        v = c.get(name, default)
-        if not isinstance(v, bool):
-            raise ValueError(f"raster_chips.{name} must be true or false (got {v!r})")
-        return v
-
-    size = c.get("chip_size", 256)
-    if isinstance(size, bool) or not isinstance(size, int) or not 1 <= size <= MAX_SIDE:
-        raise ValueError(f"raster_chips.chip_size must be an int in [1, 2^15] (got {size!r})")
-    types = listing(c.get("mask_types", []), "mask_types") or []
+    c = prep.Section(cfg, "raster_chips", CONFIG_KEYS)
+    size = c.integer("chip_size", 256, lo=1, hi=MAX_SIDE, what="must be an int in [1, 2^15]")
+    types = c.listing("mask_types", []) or []
     mask_bits(types)
-    if c.get("masking_strategy", "each") not in STRATEGIES:
-        raise ValueError(f"raster_chips.masking_strategy must be one of {tuple(STRATEGIES)} (got {c.get('masking_strategy')!r})")
-    if c.get("task_type", "seg") not in ("seg", "reg"):
-        raise ValueError(f"raster_chips.task_type must be seg or reg (got {c.get('task_type')!r})")
-    src = c.get("src_crs", 4326)
-    if isinstance(src, bool) or not isinstance(src, int):
-        raise ValueError(f"raster_chips.src_crs must be an EPSG code (got {src!r})")
-    crsmod.from_epsg(src)
-    res = c.get("spatial_resolution", 0.0002694945852358564)
-    if isinstance(res, bool) or not isinstance(res, (int, float)) or not 0 < float(res) < np.inf:
-        raise ValueError(f"raster_chips.spatial_resolution must be a positive number (got {res!r})")
-    tiles, fmasks = listing(c.get("tiles"), "tiles"), listing(c.get("fmasks"), "fmasks")
-    bbox = flag("is_bbox_feature", False)
-    opts = dict(tile_files=tiles, fmask_files=fmasks, records=text("records_file"), raster_path=text("raster_path"),
-                output_directory=text("output_directory"), chip_size=size, mask_types=types, masking_strategy=c.get("masking_strategy", "each"),
-                src_crs=src, spatial_resolution=float(res), qa_check=flag("qa_check", True), task_type=c.get("task_type", "seg"),
-                is_bbox_feature=bbox, bbox_feature_path=text("bbox_feature_path"), date=text("date"), snap=flag("snap", True))
+    strategy = c.choice("masking_strategy", "each", STRATEGIES)
+    task = c.choice("task_type", "seg", ("seg", "reg"), "must be seg or reg")
+    src = c.epsg("src_crs", 4326)
+    res = c.number("spatial_resolution", 0.0002694945852358564, lambda x: 0 < x < np.inf, "must be a positive number")
+    tiles, fmasks = c.listing("tiles"), c.listing("fmasks")
+    bbox = c.flag("is_bbox_feature", False)
+    opts = dict(tile_files=tiles, fmask_files=fmasks, records=c.text("records_file"), raster_path=c.text("raster_path"),
+                output_directory=c.text("output_directory"), chip_size=size, mask_types=types, masking_strategy=strategy, src_crs=src,
+                spatial_resolution=res, qa_check=c.flag("qa_check", True), task_type=task, is_bbox_feature=bbox,
+                bbox_feature_path=c.text("bbox_feature_path"), date=c.text("date"), snap=c.flag("snap", True))
     if cfg.get("mode") == "create_raster_chips":
         if not tiles or opts["output_directory"] is None:
             raise ValueError("mode=create_raster_chips needs raster_chips.tiles and raster_chips.output_directory")
@@ -515,19 +445,7 @@ def run_from_config(cfg: Dict[str, Any], device: Optional[str] = None) -> int:
 def main(argv: Optional[List[str]] = None) -> int:
     """``python -m instageo_amd.raster_chips raster_chips.tiles=a.tif,b.tif raster_chips.output_directory=out ...``:
     mode=create_raster_chips without ``run.py``."""
-    import sys
-
-    from .config import load_config
-
-    cfg = load_config("config", ["mode=create_raster_chips"] + list(sys.argv[1:] if argv is None else argv))
-    dev = None
-    try:
-        import torch
-
-        dev = "cuda" if torch.cuda.is_available() else None
-    except ImportError:
-        pass
-    return run_from_config(cfg, dev)
+    return prep.run_mode_cli("create_raster_chips", run_from_config, argv)
 
 
 if __name__ == "__main__":

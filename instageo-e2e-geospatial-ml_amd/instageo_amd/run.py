@@ -33,6 +33,7 @@ import numpy as np
 import torch
 
 from . import distributed as D
+from . import prep
 from .config import check_required_flags, load_config
 from .dataloader import (ArrayChipDataset, InstaGeoDataset, SyntheticChipDataset, eval_collate_fn, infer_collate_fn, normalize_batch,
                          process_and_augment, process_and_augment_batch, process_test)
@@ -41,6 +42,11 @@ from .infer_utils import chip_inference
 from .pipeline_utils import compute_stats
 
 SEED = 1042  # pl.seed_everything(1042) in the reference (run.py:50)
+# the dataset-preparation modes -> the module whose ``run_from_config(cfg, device)`` runs them
+PREP_MODES = {"create_chips": "chips",  # HLS tiles + points -> chips, label maps and the dataset CSV
+              "create_raster_chips": "raster_chips",  # HLS tiles + label rasters -> chips on the labels' grids
+              "clean_chips": "clean",  # drop no-data chips, buffer / limit the label maps of a chip dataset
+              "create_polygon_labels": "polygon_labels"}  # a GeoJSON of polygons -> label rasters + records.csv
 
 
 def get_device() -> str:
@@ -309,7 +315,7 @@ def zone_options(cfg: Dict[str, Any]) -> Dict[str, Any]:
     """The ``test.zones`` / ``test.zone_id_property`` keys (``zones_*.csv``, zonal.py) as keyword arguments of chip / tile inference; a
     relative ``zones`` path is taken from ``root_dir`` like the tiles."""
     t, root = cfg["test"], cfg.get("root_dir")
-    none = lambda v: None if v in (None, "None") else str(v)  # noqa: E731  (the string "None" counts as unset, as for the required flags)
+    none = lambda v: None if prep.none(v) is None else str(v)  # noqa: E731  (the string "None" counts as unset, as for the required flags)
     zones = none(t.get("zones"))
     if zones is not None and not os.path.isabs(zones) and root not in (None, "None"):
         zones = os.path.join(root, zones)
@@ -362,7 +368,7 @@ def warp_options(cfg: Dict[str, Any]) -> Dict[str, Any]:
     from .warp import RESAMPLING
 
     t = cfg["test"]
-    none = lambda v: None if v in (None, "None", "none", "null") else v  # noqa: E731
+    none = lambda v: prep.none(v, ("none", "null"))  # noqa: E731
     opts = dict(crs=none(t.get("mosaic_crs")), resolution=none(t.get("mosaic_resolution")), resampling=none(t.get("mosaic_resampling")))
     if opts["crs"] is not None and opts["crs"] != "first":
         if not isinstance(opts["crs"], str):
@@ -393,7 +399,7 @@ def map_tiles_options(cfg: Dict[str, Any]) -> Dict[str, Any]:
     from . import maptiles as M
 
     t, mode = cfg["test"], cfg.get("mode")
-    none = lambda v: None if v in (None, "None", "none", "null") else v  # noqa: E731
+    none = lambda v: prep.none(v, ("none", "null"))  # noqa: E731
     on, imagery = t.get("map_tiles", False), t.get("map_tiles_imagery", False)
     for name, v in (("map_tiles", on), ("map_tiles_imagery", imagery)):
         if not isinstance(v, bool):
@@ -472,24 +478,12 @@ def main(argv: Optional[List[str]] = None) -> int:
         inp = str(cfg["test"]["input"])
         root = cfg.get("root_dir")
         inp = inp if os.path.isabs(inp) or root in (None, "None") else os.path.join(root, inp)
-        print(json.dumps({"map_tiles": write_map_tiles(inp, tiles, "cuda" if torch.cuda.is_available() else None)[-1]}))
+        print(json.dumps({"map_tiles": write_map_tiles(inp, tiles, prep.default_device())[-1]}))
         return 0
-    if cfg["mode"] == "create_chips":  # no model: HLS tiles + points -> chips, label maps and the dataset CSV (chips.py)
-        from . import chips as chipsmod
+    if cfg["mode"] in PREP_MODES:  # no model: files in, files out; the module is imported only when its mode runs
+        import importlib
 
-        return chipsmod.run_from_config(cfg, "cuda" if torch.cuda.is_available() else None)
-    if cfg["mode"] == "create_raster_chips":  # no model: HLS tiles + label rasters -> chips on the labels' grids (raster_chips.py)
-        from . import raster_chips as rastermod
-
-        return rastermod.run_from_config(cfg, "cuda" if torch.cuda.is_available() else None)
-    if cfg["mode"] == "clean_chips":  # no model: drop no-data chips, buffer / limit the label maps of a chip dataset (clean.py)
-        from . import clean as cleanmod
-
-        return cleanmod.run_from_config(cfg, "cuda" if torch.cuda.is_available() else None)
-    if cfg["mode"] == "create_polygon_labels":  # no model: a GeoJSON of polygons -> label rasters + records.csv (polygon_labels.py)
-        from . import polygon_labels as polymod
-
-        return polymod.run_from_config(cfg, "cuda" if torch.cuda.is_available() else None)
+        return importlib.import_module(f".{PREP_MODES[cfg['mode']]}", __package__).run_from_config(cfg, prep.default_device())
     start = time.time()
     torch.manual_seed(SEED)
     np.random.seed(SEED)

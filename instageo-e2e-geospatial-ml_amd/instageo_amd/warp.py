@@ -26,6 +26,7 @@ import numpy as np
 
 from . import crs as crsmod
 from . import mosaic, postprocess
+from .prep import is_device
 
 RESAMPLING = ("nearest", "bilinear")
 RULES = ("last", "first")
@@ -212,7 +213,7 @@ def warp(sources, profiles: Sequence[Dict[str, Any]], dst_profile: Dict[str, Any
         raise ValueError(f"{len(sources)} sources but {len(profiles)} profiles (at least one of each)")
     if len(sources) > MAX_SOURCES:
         raise ValueError(f"one warp takes at most {MAX_SOURCES} sources (got {len(sources)})")
-    dev = mosaic._is_device(sources[0])
+    dev = is_device(sources[0])
     if not dev:
         sources = [np.asarray(s.cpu() if hasattr(s, "cpu") else s) for s in sources]
     if any(s.dtype != sources[0].dtype for s in sources):
@@ -220,7 +221,7 @@ def warp(sources, profiles: Sequence[Dict[str, Any]], dst_profile: Dict[str, Any
     check_resampling(resampling, sources[0].dtype)
     if rule not in RULES:
         raise ValueError(f"a warp composes its sources by rule {RULES} (got {rule!r})")
-    fill = mosaic._check_fill(fill)
+    fill = mosaic.check_fill(fill)
     H, W = int(shape[0]), int(shape[1])
     mosaic.check_canvas(H, W)
     for i, s in enumerate(sources):
@@ -267,15 +268,15 @@ def merge_reprojected(paths_or_folder: Union[str, Sequence[str]], output_folder:
     if resampling is not None and resampling not in RESAMPLING:
         raise ValueError(f"resampling must be None or one of {RESAMPLING} (got {resampling!r})")
     target = crs if isinstance(crs, crsmod.Crs) or crs == "first" else crsmod.parse(crs)
-    job = mosaic._prepare(paths_or_folder, output_folder, rule, fill, num_classes, device, cog, cog_blocksize, overview_levels, cog_compress,
-                          min_region, connectivity, sieve_passes, save_regions, save_polygons, zones, zone_id_property)
+    job = mosaic.prepare(paths_or_folder, output_folder, rule, fill, num_classes, device, cog, cog_blocksize, overview_levels, cog_compress,
+                         min_region, connectivity, sieve_passes, save_regions, save_polygons, zones, zone_id_property)
     resampling = resampling or ("bilinear" if job.regression else "nearest")
     check_resampling(resampling, job.arrays[0].dtype)
     if len(job.groups) > MAX_SOURCES:
         raise ValueError(f"the files span {len(job.groups)} pixel grids; one warp takes at most {MAX_SOURCES}")
     profiles = [g.profile for g in job.groups]
     dst_profile, shape = target_grid(profiles, [g.shape for g in job.groups], target, resolution)
-    canvases = [mosaic._paste_group(job, g, rule, False)[0] for g in job.groups]
+    canvases = [mosaic.paste_group(job, g, rule, False)[0] for g in job.groups]
     t0 = time.perf_counter()
     canvas = warp(canvases, profiles, dst_profile, shape, resampling, "first" if rule == "first" else "last", job.fill)
     if not job.host:
@@ -283,7 +284,7 @@ def merge_reprojected(paths_or_folder: Union[str, Sequence[str]], output_folder:
 
         torch.cuda.synchronize()
     t_warp = time.perf_counter() - t0
-    written = mosaic._write_canvas(job, canvas, None, "merged.tif", dst_profile, output_folder)
+    written = mosaic.write_canvas(job, canvas, None, "merged.tif", dst_profile, output_folder)
     TIMINGS.clear()
     TIMINGS.update(job.t, warp=t_warp)
     return written

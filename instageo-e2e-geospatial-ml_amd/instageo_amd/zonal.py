@@ -45,15 +45,15 @@ def check_zone_options(zones: Optional[str] = None, regression: bool = False) ->
         raise ValueError(f"zones: {str(zones)!r} is not a file (a GeoJSON FeatureCollection of Polygon / MultiPolygon features)")
 
 
-def read_zones(path: str, id_property: Optional[str] = None) -> List[Zone]:
-    """Read a GeoJSON FeatureCollection -> one :class:`Zone` per feature, in file order.  ``Polygon`` and ``MultiPolygon`` geometries
-    are accepted (all their rings, exteriors and holes alike, make up the zone); anything else raises ValueError naming the feature.
-    A ring's closing duplicate vertex is dropped; a third coordinate (height) is ignored."""
+def read_collection(path: str, id_property: Optional[str] = None):
+    """One pass over a GeoJSON FeatureCollection: the file is opened and parsed once -> (index, properties, rings) per feature, in file
+    order.  ``Polygon`` and ``MultiPolygon`` geometries are accepted (all their rings, exteriors and holes alike); anything else raises
+    ValueError naming the feature, by its ``id_property`` when one is given (a feature without it raises too).  A ring's closing
+    duplicate vertex is dropped; a third coordinate (height) is ignored."""
     with open(path) as f:
         doc = json.load(f)
     if not isinstance(doc, dict) or doc.get("type") != "FeatureCollection" or not isinstance(doc.get("features"), list):
         raise ValueError(f"{path}: not a GeoJSON FeatureCollection")
-    zones = []
     for i, feat in enumerate(doc["features"]):
         props = (feat.get("properties") if isinstance(feat, dict) else None) or {}
         zid = i
@@ -80,8 +80,13 @@ def read_zones(path: str, id_property: Optional[str] = None) -> List[Zone]:
                         rings.append(a)
         except (TypeError, IndexError, ValueError) as e:
             raise ValueError(f"{path}: feature {i} (id {zid!r}) has malformed coordinates") from e
-        zones.append(Zone(zid, rings))
-    return zones
+        yield i, props, rings
+
+
+def read_zones(path: str, id_property: Optional[str] = None) -> List[Zone]:
+    """Read a GeoJSON FeatureCollection -> one :class:`Zone` per feature, in file order, its id the feature's ``id_property`` or its
+    index (:func:`read_collection` reads the geometries)."""
+    return [Zone(i if id_property is None else props[id_property], rings) for i, props, rings in read_collection(path, id_property)]
 
 
 def quantise(xy: np.ndarray) -> np.ndarray:
@@ -91,6 +96,11 @@ def quantise(xy: np.ndarray) -> np.ndarray:
         raise ValueError(f"a zone vertex lies beyond 2^29 fixed-point units ({COORD_LIMIT // Q} pixels) of the raster's origin, or is not "
                          "finite: are the zones in the raster's coordinate system?")
     return q.astype(np.int32)
+
+
+def ring_edges(q: np.ndarray) -> np.ndarray:
+    """The closed, directed edges of a ring of vertices ``q`` (n, 2) -> (n, 4) {x0, y0, x1, y1}: one per vertex, the last one closes it."""
+    return np.concatenate([q, np.roll(q, -1, axis=0)], axis=1)
 
 
 def zones_to_pixels(zones: Sequence[Zone], profile: Optional[Dict[str, Any]] = None) -> Tuple[np.ndarray, np.ndarray]:
@@ -113,7 +123,7 @@ def zones_to_pixels(zones: Sequence[Zone], profile: Optional[Dict[str, Any]] = N
                 q = quantise(a)
             except ValueError as e:
                 raise ValueError(f"zone {z} (id {zone.id!r}): {e}") from None
-            parts.append(np.concatenate([q, np.roll(q, -1, axis=0)], axis=1))
+            parts.append(ring_edges(q))
             owner.append(np.full(len(q), z, dtype=np.int32))
     if not parts:
         return np.zeros((0, 4), dtype=np.int32), np.zeros(0, dtype=np.int32)
