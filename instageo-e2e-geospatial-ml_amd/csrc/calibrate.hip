@@ -7,7 +7,7 @@
 // plane); the classes are walked twice with a run-time trip count and NO per-thread class array -- pass A finds the maximum, the first
 // argmax and the label's logit, pass B re-reads each z_c (an L1 / L2 hit) and adds exp2(beta_k log2e (z_c - m)) to K accumulators in
 // registers (compile-time unrolled; the beta_k arrive by value in the kernel argument, i.e. in SGPRs).
-// Valid pixel: label != ignore_index and 0 <= label < ncls (ig_ce_loss's predicate).
+// Valid pixel: valid_label (pixel_logits.h), the rule of ig_ce_loss.
 //
 // Determinism.  calib_nll_kernel: a thread adds its pixels' terms in double in pixel order, the wave and the workgroup are reduced in a
 // fixed pattern, workgroup b stores its K partials (and its sum of max - z_y, the part of the loss that is linear in beta) to
@@ -15,14 +15,14 @@
 // order) and does nll[k] += total_k + beta_k * total_dy.  The grid depends on the shape only: the bits repeat from
 // run to run.  The count and the histograms are integers (LDS adds, then one global add per non-empty cell and workgroup).
 #include "common.h"
+#include "pixel_logits.h"
 
 namespace {
 
-constexpr int TPB = 256, NWAVE = TPB / 64;
-constexpr int MAX_K = 32, NCOL = MAX_K + 1, MAX_WG = 1024, FOLD_SUB = 8;  // a partial row: K sums + the sum of (max - z_y)
+constexpr int TPB = PX_TPB, NWAVE = PX_NWAVE;
+constexpr int MAX_K = 32, NCOL = MAX_K + 1, MAX_WG = PX_MAX_WG, FOLD_SUB = 8;  // a partial row: K sums + the sum of (max - z_y)
 constexpr int MAX_NCLS = 127, MAX_BINS = 64, MAX_CELLS = 4096;
 constexpr double LOG2E = 1.44269504088896340736;
-constexpr int SCRATCH_SLOT = 7;  // runtime.hip: per (device, stream) partial sums of calib_nll_kernel
 
 struct Betas {
     float l2[MAX_K];  // beta_k * log2(e), rounded once from double; entries K.. repeat entry 0 (computed, never stored)
@@ -31,35 +31,21 @@ struct BetasD {
     double b[MAX_K];
 };
 
-// m = b * HW + pix with 32-bit division whenever it fits (every real batch)
+// class 0's logit of pixel m; class c is c * HW floats further on
 __device__ __forceinline__ const float* pixel_base(const float* logits, long m, long HW, int ncls) {
     long b, pix;
-    if ((unsigned long)(m | HW) < (1ul << 31)) {
-        const unsigned bu = (unsigned)m / (unsigned)HW;
-        b = bu, pix = (long)((unsigned)m - bu * (unsigned)HW);
-    } else {
-        b = m / HW, pix = m - b * HW;
-    }
+    split_pixel(m, HW, b, pix);
     return logits + b * ncls * HW + pix;
-}
-
-template <typename LABEL>
-__device__ __forceinline__ bool valid_label(const LABEL* labels, long m, long ignore_index, int ncls, int& y) {
-    const long l = (long)labels[m];
-    y = (int)l;
-    return l != ignore_index && l >= 0 && l < ncls;
 }
 
 template <typename LABEL, int KT>
 __global__ __launch_bounds__(TPB) void calib_nll_kernel(const float* __restrict__ logits, const LABEL* __restrict__ labels, long ignore_index,
                                                         Betas beta, double* __restrict__ part, unsigned long long* __restrict__ count, long M,
                                                         long HW, int ncls) {
-    __shared__ double red[NWAVE][KT];
     __shared__ unsigned cnt[NWAVE];
-    __shared__ double red_dy[NWAVE];
-    double acc[KT], acc_dy = 0.0;  // sum of log(sum_c exp(beta_k (z_c - m))) per k; sum of (m - z_y), which beta_k multiplies in the fold
+    double acc[KT + 1];  // [k < KT] sum of log(sum_c exp(beta_k (z_c - m))); [KT] sum of (m - z_y), which beta_k multiplies in the fold
 #pragma unroll
-    for (int k = 0; k < KT; ++k) acc[k] = 0.0;
+    for (int k = 0; k <= KT; ++k) acc[k] = 0.0;
     unsigned n = 0;
     for (long m = blockIdx.x * (long)TPB + threadIdx.x; m < M; m += (long)gridDim.x * TPB) {
         int y;
@@ -85,36 +71,19 @@ __global__ __launch_bounds__(TPB) void calib_nll_kernel(const float* __restrict_
         }
 #pragma unroll
         for (int k = 0; k < KT; ++k) acc[k] += (double)log1pf(s[k]);
-        acc_dy += (double)(mx - zy);  // >= 0
+        acc[KT] += (double)(mx - zy);  // >= 0
         ++n;
     }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < KT; ++k) {
-        double a = acc[k];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
-        if (lane == 0) red[wave][k] = a;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc_dy += __shfl_xor(acc_dy, o, 64);
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
-    if (lane == 0) cnt[wave] = n, red_dy[wave] = acc_dy;
-    __syncthreads();
-    if (threadIdx.x < KT) {
-        double t = 0.0;
-#pragma unroll
-        for (int w = 0; w < NWAVE; ++w) t += red[w][threadIdx.x];
-        part[(size_t)blockIdx.x * NCOL + threadIdx.x] = t;
-    }
+    if ((threadIdx.x & 63) == 0) cnt[threadIdx.x >> 6] = n;
+    const double t = block_totals<KT + 1>(acc);  // its barrier also publishes cnt
+    if (threadIdx.x <= KT) part[(size_t)blockIdx.x * NCOL + (threadIdx.x < KT ? threadIdx.x : MAX_K)] = t;
     if (threadIdx.x == 0) {
-        unsigned long long t = 0;
-        double d = 0.0;
+        unsigned long long c = 0;
 #pragma unroll
-        for (int w = 0; w < NWAVE; ++w) t += cnt[w], d += red_dy[w];
-        part[(size_t)blockIdx.x * NCOL + MAX_K] = d;
-        if (t) atomicAdd(count, t);
+        for (int w = 0; w < NWAVE; ++w) c += cnt[w];
+        if (c) atomicAdd(count, c);
     }
 }
 
@@ -188,11 +157,6 @@ __global__ __launch_bounds__(TPB) void reliability_kernel(const float* __restric
     }
 }
 
-int grid_of(long M) {
-    const long nblk = (M + TPB - 1) / TPB;
-    return (int)(nblk < MAX_WG ? nblk : MAX_WG);
-}
-
 }  // namespace
 
 #define ST(s) ((hipStream_t)(s))
@@ -220,26 +184,22 @@ int ig_calib_nll_grid(const float* logits, const void* labels, int label_dtype, 
         beta_d.b[k] = (double)inv_temps[k < K ? k : 0];
         beta.l2[k] = (float)(beta_d.b[k] * LOG2E);
     }
-    const int nblk = grid_of(M);
-    double* part = (double*)ig_scratch(SCRATCH_SLOT, (size_t)MAX_WG * NCOL * sizeof(double), ST(stream));
+    const int nblk = pixel_grid(M);
+    double* part = (double*)ig_scratch(IG_SLOT_CALIB_NLL, (size_t)MAX_WG * NCOL * sizeof(double), ST(stream));
     IG_REQUIRE(part, "ig_calib_nll_grid: scratch allocation failed");
-#define IG_NLL(LT, KT)                                                                                                                   \
-    hipLaunchKernelGGL((calib_nll_kernel<LT, KT>), dim3((unsigned)nblk), dim3(TPB), 0, ST(stream), logits, (const LT*)labels, ignore_index, \
-                       beta, part, count, M, HW, ncls)
-#define IG_NLL_K(LT)                  \
-    do {                              \
-        if (K <= 4) IG_NLL(LT, 4);    \
-        else if (K <= 8) IG_NLL(LT, 8); \
-        else if (K <= 16) IG_NLL(LT, 16); \
-        else IG_NLL(LT, 32);          \
-    } while (0)
-    if (label_dtype == 0) IG_NLL_K(long long);
-    else if (label_dtype == 1) IG_NLL_K(int);
-    else IG_NLL_K(float);
-#undef IG_NLL_K
-#undef IG_NLL
-    hipLaunchKernelGGL(calib_fold_kernel, dim3(1), dim3(FOLD_SUB * 64), 0, ST(stream), part, nll, beta_d, nblk, K);
-    return ig_check_launch("ig_calib_nll_grid");
+    const int rc = ig_label_dispatch(label_dtype, [&](auto tag) {
+        using LT = typename decltype(tag)::type;
+        auto nll_k = [&](auto kt) {
+            return ig_launch<calib_nll_kernel<LT, decltype(kt)::value>>("ig_calib_nll_grid", dim3((unsigned)nblk), dim3(TPB), 0, ST(stream), logits,
+                                                                        (const LT*)labels, ignore_index, beta, part, count, M, HW, ncls);
+        };
+        if (K <= 4) return nll_k(IntTag<4>{});
+        if (K <= 8) return nll_k(IntTag<8>{});
+        if (K <= 16) return nll_k(IntTag<16>{});
+        return nll_k(IntTag<32>{});
+    });
+    if (rc != IG_OK) return rc;
+    return ig_launch<calib_fold_kernel>("ig_calib_nll_grid", dim3(1), dim3(FOLD_SUB * 64), 0, ST(stream), part, nll, beta_d, nblk, K);
 }
 
 int ig_reliability_update(const float* logits, const void* labels, int label_dtype, long ignore_index, float inv_temp, unsigned long long* hist,
@@ -253,16 +213,13 @@ int ig_reliability_update(const float* logits, const void* labels, int label_dty
     if (M == 0) return IG_OK;
     IG_REQUIRE(M <= (1L << 40), "ig_reliability_update: B * HW = %ld exceeds 2^40 pixels per call (32-bit LDS counts)", M);
     IG_REQUIRE(logits && labels && hist, "ig_reliability_update: null pointer");
-    const int nblk = grid_of(M), smem = ncls * nbins * 16;
+    const int nblk = pixel_grid(M), smem = ncls * nbins * 16;
     const float bl2 = (float)((double)inv_temp * LOG2E);
-    if (label_dtype == 0)
-        return ig_launch<reliability_kernel<long long>>("ig_reliability_update", dim3((unsigned)nblk), dim3(TPB), smem, ST(stream), logits,
-                                                        (const long long*)labels, ignore_index, bl2, hist, M, HW, ncls, nbins);
-    if (label_dtype == 1)
-        return ig_launch<reliability_kernel<int>>("ig_reliability_update", dim3((unsigned)nblk), dim3(TPB), smem, ST(stream), logits,
-                                                  (const int*)labels, ignore_index, bl2, hist, M, HW, ncls, nbins);
-    return ig_launch<reliability_kernel<float>>("ig_reliability_update", dim3((unsigned)nblk), dim3(TPB), smem, ST(stream), logits,
-                                                (const float*)labels, ignore_index, bl2, hist, M, HW, ncls, nbins);
+    return ig_label_dispatch(label_dtype, [&](auto tag) {
+        using LT = typename decltype(tag)::type;
+        return ig_launch<reliability_kernel<LT>>("ig_reliability_update", dim3((unsigned)nblk), dim3(TPB), smem, ST(stream), logits, (const LT*)labels,
+                                                 ignore_index, bl2, hist, M, HW, ncls, nbins);
+    });
 }
 
 }  // extern "C"

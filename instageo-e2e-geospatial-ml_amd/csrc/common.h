@@ -179,9 +179,20 @@ static __constant__ IgDet g_igdet;
         return hipMemcpyToSymbolAsync(HIP_SYMBOL(g_igdet), d, sizeof(IgDet), 0, hipMemcpyHostToDevice, st) == hipSuccess ? IG_OK : IG_ERR_HIP; \
     }
 bool ig_deterministic();  // host-side view of the mode (runtime.hip)
-// per-device grow-only scratch buffers (slot 0: BatchNorm partial sums); never freed, a superseded buffer stays allocated because
+// per-device grow-only scratch buffers; never freed, a superseded buffer stays allocated because
 // launches in flight may still use it; NULL on allocation failure.  Not to be grown during a graph capture (first calls are warm-ups).
-void* ig_scratch(int slot, size_t bytes, hipStream_t st);                   // per (device, stream, slot): see runtime.hip
+enum IgScratchSlot {
+    IG_SLOT_BN_PARTIALS = 0,    // per-workgroup BatchNorm partial sums of the deterministic mode (elementwise, conv_direct, head)
+    IG_SLOT_CONV8_WEIGHTS = 1,  // packed conv8 weights (hi [, lo]) and their gather table
+    IG_SLOT_LOSS_TOTALS = 2,    // ordered_grid_totals: 1024 workgroups x 16 partials + the ticket (ig_kd_loss, ig_mse_loss, ig_kd_mse_loss)
+    IG_SLOT_CE_ACC = 3,         // ce_loss_kernel: the integer (loss, count) accumulators, the arrival counter and the poison word
+    IG_SLOT_WGRAD_SLABS = 4,    // weight-gradient slabs (gemm8w.hip)
+    IG_SLOT_SPLITK = 5,         // split-K partial tiles (gemm.hip)
+    IG_SLOT_REGION_SUMS = 6,    // ig_seg_loss: per-workgroup class sums of the region term + its 32 gradient coefficients
+    IG_SLOT_CALIB_NLL = 7,      // ig_calib_nll_grid: per-workgroup partial sums of the temperature grid
+    IG_SCRATCH_SLOTS = 8
+};
+void* ig_scratch(int slot, size_t bytes, hipStream_t st);                 // per (device, stream, slot): see runtime.hip
 void* ig_scratch2(int slot, size_t bytes, bool may_grow, hipStream_t st);  // may_grow = false: NULL instead of an allocation (stream captures)
 // per-device page of 256 zeroed bytes for the LDS-DMA kernels' out-of-range units; NULL (+ the error text, under `what`) on failure
 const bf16_t* ig_zero_page(const char* what);

@@ -944,7 +944,7 @@ int ig_conv8(int kind, int sign, const void* x_hi, const void* x_lo, const void*
     const size_t need = wbytes * (w_lo ? 2 : 1) + (size_t)(tent + 32) * 4;
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     const bool capturing = hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
-    char* scratch = (char*)ig_scratch2(1, need, !capturing, st);
+    char* scratch = (char*)ig_scratch2(IG_SLOT_CONV8_WEIGHTS, need, !capturing, st);
     if (!scratch) return IG_ERR_UNSUPPORTED;
     bf16_t* p_hi = (bf16_t*)scratch;
     bf16_t* p_lo = w_lo ? (bf16_t*)(scratch + wbytes) : nullptr;

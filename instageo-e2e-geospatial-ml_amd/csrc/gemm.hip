@@ -1122,13 +1122,13 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float4* __rest
         out[i] = o;
     }
 }
-// workspace of the split-K partial tiles: per (device, stream), grown on demand (runtime.hip: ig_scratch slot 5; a buffer a captured
+// workspace of the split-K partial tiles: per (device, stream), grown on demand (runtime.hip: ig_scratch slot IG_SLOT_SPLITK; a buffer a captured
 // hipGraph may hold is never freed there).  While a stream capture is active nothing may be allocated: the caller then falls back to
 // atomics unless the workspace already fits.
 inline float* splitk_workspace(size_t bytes, hipStream_t st) {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     const bool capturing = hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
-    return (float*)ig_scratch2(5, bytes, !capturing, st);
+    return (float*)ig_scratch2(IG_SLOT_SPLITK, bytes, !capturing, st);
 }
 
 // ------------------------------------------------------------------------------------ launch

@@ -568,10 +568,10 @@ PlanCache& plan_cache() {
     static PlanCache c;
     return c;
 }
-// slab workspace: per (device, stream), grown on demand (runtime.hip: ig_scratch slot 4); nothing is allocated while a stream capture is
+// slab workspace: per (device, stream), grown on demand (runtime.hip: ig_scratch slot IG_SLOT_WGRAD_SLABS); nothing is allocated while a stream capture is
 // active (the first eager step on that stream has sized it by then)
 float* slab_workspace(long nslab, bool capturing, hipStream_t st) {
-    return (float*)ig_scratch2(4, (size_t)nslab * W_SLAB * sizeof(float), !capturing, st);
+    return (float*)ig_scratch2(IG_SLOT_WGRAD_SLABS, (size_t)nslab * W_SLAB * sizeof(float), !capturing, st);
 }
 
 struct TileRef {  // one output tile of the launch

@@ -6,53 +6,11 @@
 //   K17 np.bincount(y_true*k + y_pred) confusion matrix (int64)       metrics.py:86-108
 #include "common.h"
 #include "bn_fold.h"
+#include "pixel_logits.h"
 
 namespace {
 
-// m = b * HW + pix.  A 64-bit integer division is ~150 instructions on this hardware and sat in per-pixel loops; the 32-bit form
-// (pixel counts below 2^31: every real batch) is ~30.
-__device__ __forceinline__ void split_pixel(long m, long HW, long& b, long& pix) {
-    if ((unsigned long)(m | HW) < (1ul << 31)) {
-        const unsigned bu = (unsigned)m / (unsigned)HW;
-        b = bu, pix = (long)((unsigned)m - bu * (unsigned)HW);
-    } else {
-        b = m / HW, pix = m - b * HW;
-    }
-}
-
-// Grid-wide sums in a FIXED order (the reported loss statistics are bit-identical from run to run): thread i < NV of every workgroup
-// hands in its workgroup's partial t; partials go to scratch[workgroup][i]; the workgroup that takes the last ticket adds them up in
-// workgroup order (16 strided subsets per value, folded in subset order) and gets the totals back in t of its threads i < NV.
-// Returns true in that workgroup only.  NV <= 16, blockDim.x == 256.  Launches that share the scratch are ordered on one stream.
-template <int NV>
-__device__ __forceinline__ bool ordered_grid_totals(double& t, double* __restrict__ scratch, unsigned* __restrict__ ticket) {
-    static_assert(NV <= 16, "at most 16 values");
-    __shared__ int s_last;
-    __shared__ double s_sub[16][16];
-    if (threadIdx.x < NV) scratch[(size_t)blockIdx.x * NV + threadIdx.x] = t;
-    __threadfence();
-    __syncthreads();
-    if (threadIdx.x == 0) s_last = atomicAdd(ticket, 1u) == gridDim.x - 1;
-    __syncthreads();
-    if (!s_last) return false;
-    __threadfence();
-    const int i = threadIdx.x & 15, g = threadIdx.x >> 4;
-    double a = 0.0;
-    if (i < NV)
-        for (unsigned b = g; b < gridDim.x; b += 16) a += *reinterpret_cast<volatile double*>(scratch + (size_t)b * NV + i);
-    s_sub[g][i] = a;
-    __syncthreads();
-    if (threadIdx.x < NV) {
-        double s = 0.0;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) s += s_sub[q][threadIdx.x];
-        t = s;
-    }
-    if (threadIdx.x == 0) atomicExch(ticket, 0u);
-    return true;
-}
-
-constexpr int TPB = 256;
+constexpr int TPB = PX_TPB;
 constexpr int MAXC = 16;  // max classes held in registers
 
 // Copy `total` 16-byte units (units per pixel row) from global to LDS rows of `pitch` bytes: consecutive threads take
@@ -542,18 +500,7 @@ __global__ __launch_bounds__(TPB) void ce_loss_kernel(const float* __restrict__ 
         split_pixel(m0, HW, b, pix);
         float z[NCB][VEC];
         LABEL lab[VEC];
-#pragma unroll
-        for (int n = 0; n < NCB; ++n) {
-            if (n < ncls) {
-                const float* src = logits + (b * ncls + n) * HW + pix;
-                if constexpr (VEC == 4) {
-                    const float4 v = *reinterpret_cast<const float4*>(src);
-                    z[n][0] = v.x, z[n][1] = v.y, z[n][2] = v.z, z[n][3] = v.w;
-                } else {
-                    z[n][0] = *src;
-                }
-            }
-        }
+        load_logits<NCB, VEC>(logits, b, pix, HW, ncls, z);
 #pragma unroll
         for (int e = 0; e < VEC; ++e) lab[e] = labels[m0 + e];
         int amv[VEC];
@@ -582,7 +529,7 @@ __global__ __launch_bounds__(TPB) void ce_loss_kernel(const float* __restrict__ 
             // loss of a confident pixel away at ulp(|max|).  expf / logf, not __expf / __logf: those lose ~|x| ulps of the argument and
             // ~2^-22 absolute at se ~ 1, the whole loss of a confident pixel.
             const float lse0 = logf(se), rse = 1.f / se;
-            const bool valid = (y != ignore_index) && y >= 0 && y < ncls;
+            const bool valid = valid_label(y, ignore_index, ncls);
             const float w0 = valid ? (cw ? cw[y] : 1.f) : 0.f;
             float wy = w0, wl = w0;  // weights of the gradient and of the loss term
             if constexpr (SEG) {
@@ -626,18 +573,7 @@ __global__ __launch_bounds__(TPB) void ce_loss_kernel(const float* __restrict__ 
                 if (n < ncls) z[n][e] = wy * (z[n][e] * rse - (n == (int)y ? 1.f : 0.f));  // z now holds dlogits
             amv[e] = am;
         }
-        if (dlogits) {
-#pragma unroll
-            for (int n = 0; n < NCB; ++n) {
-                if (n < ncls) {
-                    float* dst = dlogits + (b * ncls + n) * HW + pix;
-                    if constexpr (VEC == 4)
-                        *reinterpret_cast<float4*>(dst) = make_float4(z[n][0], z[n][1], z[n][2], z[n][3]);
-                    else
-                        *dst = z[n][0];
-                }
-            }
-        }
+        if (dlogits) store_logits<NCB, VEC>(dlogits, b, pix, HW, ncls, z);
         if (preds) {
             if constexpr (VEC == 4) {
                 *reinterpret_cast<longlong2*>(preds + m0) = make_longlong2(amv[0], amv[1]);
@@ -793,24 +729,12 @@ __global__ __launch_bounds__(TPB) void seg_region_grad_kernel(const float* __res
         bool any = false;
 #pragma unroll
         for (int e = 0; e < VEC; ++e) {
-            y[e] = (long)labels[m0 + e];
-            if (y[e] == ignore_index || y[e] < 0 || y[e] >= ncls) y[e] = -1;  // the validity predicate of ce_loss_kernel
+            y[e] = valid_class((long)labels[m0 + e], ignore_index, ncls);
             any = any || y[e] >= 0;
         }
         if (!any) continue;
         float z[NCB][VEC];
-#pragma unroll
-        for (int n = 0; n < NCB; ++n) {
-            if (n < ncls) {
-                const float* src = logits + (b * ncls + n) * HW + pix;
-                if constexpr (VEC == 4) {
-                    const float4 v = *reinterpret_cast<const float4*>(src);
-                    z[n][0] = v.x, z[n][1] = v.y, z[n][2] = v.z, z[n][3] = v.w;
-                } else {
-                    z[n][0] = *src;
-                }
-            }
-        }
+        load_logits<NCB, VEC>(logits, b, pix, HW, ncls, z);
 #pragma unroll
         for (int e = 0; e < VEC; ++e) {
             float mx = -INFINITY;
@@ -843,19 +767,7 @@ __global__ __launch_bounds__(TPB) void seg_region_grad_kernel(const float* __res
             for (int n = 0; n < NCB; ++n)
                 if (n < ncls) z[n][e] *= h[n] - dot;  // z now holds the region gradient
         }
-#pragma unroll
-        for (int n = 0; n < NCB; ++n) {
-            if (n < ncls) {
-                float* dst = dlogits + (b * ncls + n) * HW + pix;
-                if constexpr (VEC == 4) {
-                    float4 v = *reinterpret_cast<const float4*>(dst);
-                    v.x += z[n][0], v.y += z[n][1], v.z += z[n][2], v.w += z[n][3];
-                    *reinterpret_cast<float4*>(dst) = v;
-                } else {
-                    *dst += z[n][0];
-                }
-            }
-        }
+        add_logits<NCB, VEC>(dlogits, b, pix, HW, ncls, z);
     }
 }
 
@@ -867,13 +779,10 @@ template <typename LABEL>
 __global__ __launch_bounds__(TPB) void kd_loss_kernel(const float* __restrict__ student, const float* __restrict__ teacher,
                                                       const LABEL* __restrict__ labels, long ignore_index, double* __restrict__ kl_sum,
                                                       float* __restrict__ dlogits, long M, long HW, int ncls, double* __restrict__ scratch, unsigned* __restrict__ ticket) {
-    __shared__ double red[TPB / 64];
     double my = 0.0;
     for (long m = blockIdx.x * (long)TPB + threadIdx.x; m < M; m += (long)gridDim.x * TPB) {
-        {  // the validity predicate of ce_loss_kernel: ignored AND out-of-range labels carry neither loss nor gradient
-            const long y = (long)labels[m];
-            if (y == ignore_index || y < 0 || y >= ncls) continue;
-        }
+        int y;
+        if (!valid_label(labels, m, ignore_index, ncls, y)) continue;  // ignored AND out-of-range labels carry neither loss nor gradient
         long b, pix;
         split_pixel(m, HW, b, pix);
         float zs[MAXC], zt[MAXC];
@@ -905,13 +814,7 @@ __global__ __launch_bounds__(TPB) void kd_loss_kernel(const float* __restrict__ 
             }
         my += (double)kl;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) my += __shfl_xor(my, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = my;
-    __syncthreads();
-    double t = 0.0;
-    if (threadIdx.x == 0)
-        for (int w = 0; w < TPB / 64; ++w) t += red[w];
+    double t = block_totals<1>(&my);
     if (ordered_grid_totals<1>(t, scratch, ticket) && threadIdx.x == 0) *kl_sum += t;
 }
 
@@ -931,6 +834,8 @@ __global__ __launch_bounds__(TPB) void auc_update_kernel(const float* __restrict
     }
     const float inv = (float)(nbins - 1);
     for (long m = blockIdx.x * (long)TPB + threadIdx.x; m < M; m += (long)gridDim.x * TPB) {
+        // NOT valid_label, on purpose (metrics.py): only ignore_index is skipped; an out-of-range label that is not ignore_index counts as a
+        // negative of every class
         const long y = (long)labels[m];
         if (y == ignore_index) continue;
         long b, pix;
@@ -997,7 +902,6 @@ __global__ __launch_bounds__(TPB) void mse_loss_kernel(const float* __restrict__
                                                        int use_log, double* __restrict__ stats, float* __restrict__ dpred,
                                                        double* __restrict__ msums, float ee_bias, float ee_coef, int include_ee,
                                                        long M, double* __restrict__ scratch, unsigned* __restrict__ ticket) {
-    __shared__ double red[TPB / 64][10];
     double a[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // [0] = sum of squared error in the (possibly log) training domain
     for (long m = blockIdx.x * (long)TPB + threadIdx.x; m < M; m += (long)gridDim.x * TPB) {
         const float lab = labels[m];
@@ -1016,18 +920,7 @@ __global__ __launch_bounds__(TPB) void mse_loss_kernel(const float* __restrict__
             if (include_ee && e <= ee_bias + ee_coef * x) a[9] += 1.0;
         }
     }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int i = 0; i < 10; ++i) {
-        double v = a[i];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-        if (lane == 0) red[wave][i] = v;
-    }
-    __syncthreads();
-    double t = 0.0;
-    if (threadIdx.x < 10)
-        for (int w = 0; w < TPB / 64; ++w) t += red[w][threadIdx.x];
+    double t = block_totals<10>(a);
     if (ordered_grid_totals<10>(t, scratch, ticket) && threadIdx.x < 10) {
         const int i = threadIdx.x;
         if (i == 0) stats[0] += t;
@@ -1043,7 +936,6 @@ __global__ __launch_bounds__(TPB) void mse_loss_kernel(const float* __restrict__
 __global__ __launch_bounds__(TPB) void kd_mse_loss_kernel(const float* __restrict__ pred, const float* __restrict__ teacher,
                                                           const float* __restrict__ labels, float ignore_value, int use_log,
                                                           double* __restrict__ sum, float* __restrict__ dpred, long M, double* __restrict__ scratch, unsigned* __restrict__ ticket) {
-    __shared__ double red[TPB / 64];
     double a = 0.0;
     for (long m = blockIdx.x * (long)TPB + threadIdx.x; m < M; m += (long)gridDim.x * TPB) {
         if (labels[m] == ignore_value) continue;
@@ -1052,13 +944,7 @@ __global__ __launch_bounds__(TPB) void kd_mse_loss_kernel(const float* __restric
         a += (double)d * d;  // fp64 product of the fp32 difference, as in mse_loss_kernel
         if (dpred) dpred[m] += 2.f * d;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = a;
-    __syncthreads();
-    double t = 0.0;
-    if (threadIdx.x == 0)
-        for (int w = 0; w < TPB / 64; ++w) t += red[w];
+    double t = block_totals<1>(&a);
     if (ordered_grid_totals<1>(t, scratch, ticket) && threadIdx.x == 0) *sum += t;
 }
 
@@ -1225,7 +1111,7 @@ int ig_classifier_bn_bwd(const float* dlogits, const void* x_hi, const void* x_l
     if (rc != IG_OK) return rc;
     ClsBn bn{scale, shift, mean, rstd, sums, nullptr, dgamma, dbeta, 1.0 / (double)M};
     if (ig_deterministic()) {
-        bn.part = (float*)ig_scratch(0, (size_t)nwg * 2 * C * sizeof(float), (hipStream_t)stream);
+        bn.part = (float*)ig_scratch(IG_SLOT_BN_PARTIALS, (size_t)nwg * 2 * C * sizeof(float), (hipStream_t)stream);
         IG_REQUIRE(bn.part, "ig_classifier_bn_bwd: scratch allocation failed");
     } else {
         (void)hipMemsetAsync(sums, 0, 2 * (size_t)C * sizeof(double), (hipStream_t)stream);
@@ -1239,73 +1125,68 @@ int ig_classifier_bn_bwd(const float* dlogits, const void* x_hi, const void* x_l
                                drop_seed_dev, drop_p, stream);
 }
 
-// scratch of ordered_grid_totals: 1024 workgroups x 16 partials + the ticket, per (device, stream) (runtime.hip: ig_scratch slot 2, zero-filled
-// when it is made; its kernels re-arm the ticket).  Launches that share it are ordered on their stream; two streams never share it.  Not to be
-// made during a graph capture (the first call on a stream is a warm-up call).
+// scratch of ordered_grid_totals: 1024 workgroups x 16 partials + the ticket, per (device, stream) (zero-filled when it is made; its kernels
+// re-arm the ticket).  Launches that share it are ordered on their stream; two streams never share it.  Not to be made during a graph capture
+// (the first call on a stream is a warm-up call).
 static double* loss_scratch(unsigned** ticket, hipStream_t st) {
-    double* buf = (double*)ig_scratch(2, (1024 * 16 + 2) * sizeof(double), st);
+    double* buf = (double*)ig_scratch(IG_SLOT_LOSS_TOTALS, (PX_MAX_WG * 16 + 2) * sizeof(double), st);
     if (!buf) return nullptr;
-    *ticket = reinterpret_cast<unsigned*>(buf + 1024 * 16);
+    *ticket = reinterpret_cast<unsigned*>(buf + PX_MAX_WG * 16);
     return buf;
 }
 
-// ig_ce_loss and the first pass of ig_seg_loss: one launch of ce_loss_kernel<.., SEG> on nblk workgroups
+static int bad_label_dtype(const char* who, int label_dtype) {
+    ig_set_error("%s: unsupported label dtype %d", who, label_dtype);
+    return IG_ERR_UNSUPPORTED;
+}
+
+// The vector form and the grid of ce_loss_kernel (and of seg_region_grad_kernel, which walks the same pixels), and the launch of
+// Kern<LABEL, VEC, NCB> in the bucket they select: VEC = 4 where HW % 4 == 0 and every vector-accessed pointer is 16-byte aligned,
+// NCB = 2 for the two-class task in the vector form, 16 otherwise.
+struct PixelForm {
+    bool vec4;
+    int nblk;
+};
+static PixelForm pixel_form(const float* logits, const float* dlogits, const long long* preds, const signed char* preds_i8, long M, long HW) {
+    const bool vec4 = HW % 4 == 0 && (reinterpret_cast<uintptr_t>(logits) | reinterpret_cast<uintptr_t>(dlogits) | reinterpret_cast<uintptr_t>(preds) |
+                                      reinterpret_cast<uintptr_t>(preds_i8)) % 16 == 0;
+    return {vec4, pixel_grid(M, vec4 ? 4 : 1)};  // grid-stride: one round of global atomics per workgroup
+}
 extern "C++" {
+template <class F>
+static int pixel_form_dispatch(int label_dtype, PixelForm pf, int ncls, F&& launch) {
+    return ig_label_dispatch(label_dtype, [&](auto lt) {
+        if (pf.vec4 && ncls <= 2) return launch(lt, IntTag<4>{}, IntTag<2>{});
+        if (pf.vec4) return launch(lt, IntTag<4>{}, IntTag<16>{});
+        return launch(lt, IntTag<1>{}, IntTag<16>{});
+    });
+}
+
+// ig_ce_loss and the first pass of ig_seg_loss: one launch of ce_loss_kernel<.., SEG> on pf.nblk workgroups
 template <bool SEG>
 static int ce_loss_launch(const char* who, const float* logits, const void* labels, int label_dtype, const float* class_weights, long ignore_index,
                           double* stats, float* dlogits, long long* preds, signed char* preds_i8, unsigned long long* confusion, long M, long HW,
-                          int ncls, SegArgs seg, bool vec4, int nblk, void* stream) {
-    size_t sm = (size_t)ncls * ncls * sizeof(unsigned);
-    // scratch of the order-independent (loss, count) sums: two 64-bit accumulators + the arrival counter, per (device, stream) (ig_scratch
-    // slot 3, zero-filled when it is made; the kernel re-arms it); never made during a graph capture (the first call on a stream is a warm-up)
-    unsigned long long* acc_stream = nullptr;
+                          int ncls, SegArgs seg, PixelForm pf, void* stream) {
+    // scratch of the order-independent (loss, count) sums: two 64-bit accumulators + the arrival counter, per (device, stream) (zero-filled
+    // when it is made; the kernel re-arms it); never made during a graph capture (the first call on a stream is a warm-up)
+    unsigned long long* acc = nullptr;
     if (stats) {
-        acc_stream = (unsigned long long*)ig_scratch(3, 4 * sizeof(unsigned long long), (hipStream_t)stream);
-        if (!acc_stream) {
+        acc = (unsigned long long*)ig_scratch(IG_SLOT_CE_ACC, 4 * sizeof(unsigned long long), (hipStream_t)stream);
+        if (!acc) {
             ig_set_error("%s: scratch allocation failed", who);
             return IG_ERR_HIP;
         }
     }
-    unsigned long long* acc = acc_stream;
     unsigned* arrived = acc ? reinterpret_cast<unsigned*>(acc + 2) : nullptr;
-    dim3 grid((unsigned)nblk), block(TPB);
-    hipStream_t st = (hipStream_t)stream;
-#define IG_CE(LT)                                                                                                                   \
-    {                                                                                                                               \
-        if (vec4 && ncls <= 2)                                                                                                      \
-            hipLaunchKernelGGL((ce_loss_kernel<LT, 4, 2, SEG>), grid, block, sm, st, logits, (const LT*)labels, class_weights,      \
-                               ignore_index, stats, dlogits, preds, preds_i8, confusion, M, HW, ncls, acc, arrived, seg);          \
-        else if (vec4)                                                                                                              \
-            hipLaunchKernelGGL((ce_loss_kernel<LT, 4, 16, SEG>), grid, block, sm, st, logits, (const LT*)labels, class_weights,     \
-                               ignore_index, stats, dlogits, preds, preds_i8, confusion, M, HW, ncls, acc, arrived, seg);          \
-        else                                                                                                                        \
-            hipLaunchKernelGGL((ce_loss_kernel<LT, 1, 16, SEG>), grid, block, sm, st, logits, (const LT*)labels, class_weights,     \
-                               ignore_index, stats, dlogits, preds, preds_i8, confusion, M, HW, ncls, acc, arrived, seg);          \
-    }
-    if (label_dtype == 0)
-        IG_CE(long long)
-    else if (label_dtype == 1)
-        IG_CE(int)
-    else if (label_dtype == 2)
-        IG_CE(float)
-    else {
-        ig_set_error("%s: unsupported label dtype %d", who, label_dtype);
-        return IG_ERR_UNSUPPORTED;
-    }
-#undef IG_CE
-    return ig_check_launch(who);
+    if (!ig_label_dtype_ok(label_dtype)) return bad_label_dtype(who, label_dtype);
+    return pixel_form_dispatch(label_dtype, pf, ncls, [&](auto lt, auto vec, auto ncb) {
+        using LT = typename decltype(lt)::type;
+        return ig_launch<ce_loss_kernel<LT, decltype(vec)::value, decltype(ncb)::value, SEG>>(
+            who, dim3((unsigned)pf.nblk), dim3(TPB), ncls * ncls * (int)sizeof(unsigned), (hipStream_t)stream, logits, (const LT*)labels, class_weights,
+            ignore_index, stats, dlogits, preds, preds_i8, confusion, M, HW, ncls, acc, arrived, seg);
+    });
 }
 }  // extern "C++"
-
-// the vector form and the grid of ce_loss_kernel (and of seg_region_grad_kernel, which walks the same pixels)
-static int ce_loss_grid(const float* logits, const float* dlogits, const long long* preds, const signed char* preds_i8, long M, long HW, bool* vec4) {
-    *vec4 = HW % 4 == 0 && (reinterpret_cast<uintptr_t>(logits) | reinterpret_cast<uintptr_t>(dlogits) | reinterpret_cast<uintptr_t>(preds) |
-                            reinterpret_cast<uintptr_t>(preds_i8)) % 16 == 0;
-    const int vec = *vec4 ? 4 : 1;
-    long nblk = (M + (long)TPB * vec - 1) / ((long)TPB * vec);
-    if (nblk > 1024) nblk = 1024;  // grid-stride: one round of global atomics per workgroup
-    return (int)nblk;
-}
 
 // label_dtype: 0 = int64, 1 = int32, 2 = float32 (reference labels are float tensors cast with .long())
 int ig_ce_loss(const float* logits, const void* labels, int label_dtype, const float* class_weights, long ignore_index,
@@ -1315,14 +1196,12 @@ int ig_ce_loss(const float* logits, const void* labels, int label_dtype, const f
     IG_REQUIRE(ncls >= 1 && ncls <= MAXC, "ig_ce_loss: 1 <= ncls <= %d (got %d)", MAXC, ncls);
     long M = (long)B * HW;
     if (M == 0) return IG_OK;
-    bool vec4;
-    const int nblk = ce_loss_grid(logits, dlogits, preds, preds_i8, M, HW, &vec4);
     return ce_loss_launch<false>("ig_ce_loss", logits, labels, label_dtype, class_weights, ignore_index, stats, dlogits, preds, preds_i8, confusion,
-                                 M, HW, ncls, SegArgs{0.f, 1, nullptr, nullptr}, vec4, nblk, stream);
+                                 M, HW, ncls, SegArgs{0.f, 1, nullptr, nullptr}, pixel_form(logits, dlogits, preds, preds_i8, M, HW), stream);
 }
 
 // Focal + region (Dice / Tversky) loss; see the header.  Pass 1 is ce_loss_kernel<.., SEG = true>; with region_weight > 0 the class sums
-// go through scratch slot 6 (1024 workgroups x 48 doubles + the 32 gradient coefficients, per (device, stream); not to be made during a
+// go through scratch (1024 workgroups x 48 doubles + the 32 gradient coefficients, per (device, stream); not to be made during a
 // graph capture: the first call on a stream is a warm-up call) to seg_region_finalize_kernel and, with dlogits, seg_region_grad_kernel.
 int ig_seg_loss(const float* logits, const void* labels, int label_dtype, const float* class_weights, long ignore_index, float focal_gamma,
                 int pixel_term, float region_weight, float region_smooth, float tversky_alpha, float tversky_beta, double* stats, double* parts,
@@ -1340,48 +1219,30 @@ int ig_seg_loss(const float* logits, const void* labels, int label_dtype, const 
     IG_REQUIRE(B >= 0 && HW >= 0, "ig_seg_loss: negative size");
     const long M = (long)B * HW;
     if (M == 0) return IG_OK;
-    bool vec4;
-    const int nblk = ce_loss_grid(logits, dlogits, preds, preds_i8, M, HW, &vec4);
+    const PixelForm pf = pixel_form(logits, dlogits, preds, preds_i8, M, HW);
     const bool region = region_weight > 0.f;
     hipStream_t st = (hipStream_t)stream;
     double* part = nullptr;
     float* coef = nullptr;
     if (region) {
-        part = (double*)ig_scratch(6, (size_t)1024 * 3 * MAXC * sizeof(double) + 2 * MAXC * sizeof(float), st);
+        part = (double*)ig_scratch(IG_SLOT_REGION_SUMS, (size_t)PX_MAX_WG * 3 * MAXC * sizeof(double) + 2 * MAXC * sizeof(float), st);
         if (!part) {
             ig_set_error("ig_seg_loss: scratch allocation failed");
             return IG_ERR_HIP;
         }
-        coef = reinterpret_cast<float*>(part + (size_t)1024 * 3 * MAXC);
+        coef = reinterpret_cast<float*>(part + (size_t)PX_MAX_WG * 3 * MAXC);
     }
     int rc = ce_loss_launch<true>("ig_seg_loss", logits, labels, label_dtype, class_weights, ignore_index, stats, dlogits, preds, preds_i8, confusion,
-                                  M, HW, ncls, SegArgs{focal_gamma, pixel_term != 0, parts, part}, vec4, nblk, stream);
+                                  M, HW, ncls, SegArgs{focal_gamma, pixel_term != 0, parts, part}, pf, stream);
     if (rc != IG_OK || !region) return rc;
-    hipLaunchKernelGGL(seg_region_finalize_kernel, dim3(1), dim3(SEG_FOLD * 3 * MAXC), 0, st, part, nblk, ncls, region_weight, region_smooth,
-                       tversky_alpha, tversky_beta, coef, stats, parts);
-    if (dlogits) {
-        dim3 grid((unsigned)nblk), block(TPB);
-#define IG_RG(LT)                                                                                                                              \
-    {                                                                                                                                          \
-        if (vec4 && ncls <= 2)                                                                                                                 \
-            hipLaunchKernelGGL((seg_region_grad_kernel<LT, 4, 2>), grid, block, 0, st, logits, (const LT*)labels, ignore_index, coef, dlogits, \
-                               M, HW, ncls);                                                                                                   \
-        else if (vec4)                                                                                                                         \
-            hipLaunchKernelGGL((seg_region_grad_kernel<LT, 4, 16>), grid, block, 0, st, logits, (const LT*)labels, ignore_index, coef,         \
-                               dlogits, M, HW, ncls);                                                                                          \
-        else                                                                                                                                   \
-            hipLaunchKernelGGL((seg_region_grad_kernel<LT, 1, 16>), grid, block, 0, st, logits, (const LT*)labels, ignore_index, coef,         \
-                               dlogits, M, HW, ncls);                                                                                          \
-    }
-        if (label_dtype == 0)
-            IG_RG(long long)
-        else if (label_dtype == 1)
-            IG_RG(int)
-        else
-            IG_RG(float)
-#undef IG_RG
-    }
-    return ig_check_launch("ig_seg_loss");
+    rc = ig_launch<seg_region_finalize_kernel>("ig_seg_loss", dim3(1), dim3(SEG_FOLD * 3 * MAXC), 0, st, part, pf.nblk, ncls, region_weight,
+                                               region_smooth, tversky_alpha, tversky_beta, coef, stats, parts);
+    if (rc != IG_OK || !dlogits) return rc;
+    return pixel_form_dispatch(label_dtype, pf, ncls, [&](auto lt, auto vec, auto ncb) {
+        using LT = typename decltype(lt)::type;
+        return ig_launch<seg_region_grad_kernel<LT, decltype(vec)::value, decltype(ncb)::value>>(
+            "ig_seg_loss", dim3((unsigned)pf.nblk), dim3(TPB), 0, st, logits, (const LT*)labels, ignore_index, coef, dlogits, M, HW, ncls);
+    });
 }
 
 // kl_sum: device double += KL sum over valid pixels; dlogits (optional) += softmax(student) - softmax(teacher) on valid pixels
@@ -1391,26 +1252,15 @@ int ig_kd_loss(const float* student_logits, const float* teacher_logits, const v
     IG_REQUIRE(ncls >= 1 && ncls <= MAXC, "ig_kd_loss: 1 <= ncls <= %d (got %d)", MAXC, ncls);
     const long M = (long)B * HW;
     if (M == 0) return IG_OK;
-    long nblk = (M + TPB - 1) / TPB;
-    if (nblk > 1024) nblk = 1024;
-    hipStream_t st = (hipStream_t)stream;
     unsigned* ticket = nullptr;
     double* scratch = loss_scratch(&ticket, (hipStream_t)stream);
     IG_REQUIRE(scratch, "ig_kd_loss: scratch allocation failed");
-    if (label_dtype == 0)
-        hipLaunchKernelGGL(kd_loss_kernel<long long>, dim3((unsigned)nblk), dim3(TPB), 0, st, student_logits, teacher_logits,
-                           (const long long*)labels, ignore_index, kl_sum, dlogits, M, HW, ncls, scratch, ticket);
-    else if (label_dtype == 1)
-        hipLaunchKernelGGL(kd_loss_kernel<int>, dim3((unsigned)nblk), dim3(TPB), 0, st, student_logits, teacher_logits, (const int*)labels,
-                           ignore_index, kl_sum, dlogits, M, HW, ncls, scratch, ticket);
-    else if (label_dtype == 2)
-        hipLaunchKernelGGL(kd_loss_kernel<float>, dim3((unsigned)nblk), dim3(TPB), 0, st, student_logits, teacher_logits,
-                           (const float*)labels, ignore_index, kl_sum, dlogits, M, HW, ncls, scratch, ticket);
-    else {
-        ig_set_error("ig_kd_loss: unsupported label dtype %d", label_dtype);
-        return IG_ERR_UNSUPPORTED;
-    }
-    return ig_check_launch("ig_kd_loss");
+    if (!ig_label_dtype_ok(label_dtype)) return bad_label_dtype("ig_kd_loss", label_dtype);
+    return ig_label_dispatch(label_dtype, [&](auto lt) {
+        using LT = typename decltype(lt)::type;
+        return ig_launch<kd_loss_kernel<LT>>("ig_kd_loss", dim3((unsigned)pixel_grid(M)), dim3(TPB), 0, (hipStream_t)stream, student_logits,
+                                             teacher_logits, (const LT*)labels, ignore_index, kl_sum, dlogits, M, HW, ncls, scratch, ticket);
+    });
 }
 
 // hist: device uint64 [2][ncls][nbins] (0 = positives of class c, 1 = negatives); label_dtype as ig_ce_loss
@@ -1421,29 +1271,17 @@ int ig_auc_update(const float* logits, const void* labels, int label_dtype, long
     IG_REQUIRE(nbins >= 2 && max_score > min_score, "ig_auc_update: need nbins >= 2 and max_score > min_score");
     const long M = (long)B * HW;
     if (M == 0) return IG_OK;
-    long nblk = (M + TPB - 1) / TPB;
-    if (nblk > 1024) nblk = 1024;
     const size_t lds = 2 * (size_t)ncls * nbins * sizeof(unsigned int);
-    const bool use_lds = lds <= 65536;
-    hipStream_t st = (hipStream_t)stream;
-#define IG_AUC(LT)                                                                                                              \
-    {                                                                                                                            \
-        if (use_lds)                                                                                                             \
-            hipLaunchKernelGGL((auc_update_kernel<LT, true>), dim3((unsigned)nblk), dim3(TPB), lds, st, logits, (const LT*)labels, \
-                               ignore_index, hist, M, HW, ncls, nbins, min_score, max_score);                                     \
-        else                                                                                                                     \
-            hipLaunchKernelGGL((auc_update_kernel<LT, false>), dim3((unsigned)nblk), dim3(TPB), 0, st, logits, (const LT*)labels, \
-                               ignore_index, hist, M, HW, ncls, nbins, min_score, max_score);                                     \
-    }
-    if (label_dtype == 0) IG_AUC(long long)
-    else if (label_dtype == 1) IG_AUC(int)
-    else if (label_dtype == 2) IG_AUC(float)
-    else {
-        ig_set_error("ig_auc_update: unsupported label dtype %d", label_dtype);
-        return IG_ERR_UNSUPPORTED;
-    }
-#undef IG_AUC
-    return ig_check_launch("ig_auc_update");
+    if (!ig_label_dtype_ok(label_dtype)) return bad_label_dtype("ig_auc_update", label_dtype);
+    return ig_label_dispatch(label_dtype, [&](auto lt) {
+        using LT = typename decltype(lt)::type;
+        const dim3 grid((unsigned)pixel_grid(M)), block(TPB);
+        if (lds <= 65536)
+            return ig_launch<auc_update_kernel<LT, true>>("ig_auc_update", grid, block, (int)lds, (hipStream_t)stream, logits, (const LT*)labels,
+                                                          ignore_index, hist, M, HW, ncls, nbins, min_score, max_score);
+        return ig_launch<auc_update_kernel<LT, false>>("ig_auc_update", grid, block, 0, (hipStream_t)stream, logits, (const LT*)labels, ignore_index,
+                                                       hist, M, HW, ncls, nbins, min_score, max_score);
+    });
 }
 
 int ig_softmax_prob(const float* logits, float* out, int B, long HW, int ncls, int cls, void* stream) {
@@ -1451,9 +1289,8 @@ int ig_softmax_prob(const float* logits, float* out, int B, long HW, int ncls, i
     IG_REQUIRE(ncls >= 1 && cls >= 0 && cls < ncls, "ig_softmax_prob: need 0 <= cls < ncls");
     const long M = (long)B * HW;
     if (M == 0) return IG_OK;
-    hipLaunchKernelGGL(softmax_prob_kernel, dim3((unsigned)((M + TPB - 1) / TPB)), dim3(TPB), 0, (hipStream_t)stream, logits, out, M, HW,
-                       ncls, cls);
-    return ig_check_launch("ig_softmax_prob");
+    return ig_launch<softmax_prob_kernel>("ig_softmax_prob", dim3((unsigned)((M + TPB - 1) / TPB)), dim3(TPB), 0, (hipStream_t)stream, logits, out, M,
+                                          HW, ncls, cls);
 }
 
 // stats: double[2] += (sum of squared error, #valid); msums: optional double[9] (see the kernel)
@@ -1461,28 +1298,22 @@ int ig_mse_loss(const float* pred, const float* labels, float ignore_value, int 
                 double* msums, float ee_bias, float ee_coef, int include_ee, long n, void* stream) {
     IG_REQUIRE(pred && labels && stats, "ig_mse_loss: null pointer");
     if (n == 0) return IG_OK;
-    long nblk = (n + TPB - 1) / TPB;
-    if (nblk > 1024) nblk = 1024;
     unsigned* ticket = nullptr;
     double* scratch = loss_scratch(&ticket, (hipStream_t)stream);
     IG_REQUIRE(scratch, "ig_mse_loss: scratch allocation failed");
-    hipLaunchKernelGGL(mse_loss_kernel, dim3((unsigned)nblk), dim3(TPB), 0, (hipStream_t)stream, pred, labels, ignore_value, use_log_scale,
-                       stats, dpred, msums, ee_bias, ee_coef, include_ee, n, scratch, ticket);
-    return ig_check_launch("ig_mse_loss");
+    return ig_launch<mse_loss_kernel>("ig_mse_loss", dim3((unsigned)pixel_grid(n)), dim3(TPB), 0, (hipStream_t)stream, pred, labels, ignore_value,
+                                      use_log_scale, stats, dpred, msums, ee_bias, ee_coef, include_ee, n, scratch, ticket);
 }
 
 int ig_kd_mse_loss(const float* pred, const float* teacher, const float* labels, float ignore_value, int use_log_scale, double* sum,
                    float* dpred, long n, void* stream) {
     IG_REQUIRE(pred && teacher && labels && sum, "ig_kd_mse_loss: null pointer");
     if (n == 0) return IG_OK;
-    long nblk = (n + TPB - 1) / TPB;
-    if (nblk > 1024) nblk = 1024;
     unsigned* ticket = nullptr;
     double* scratch = loss_scratch(&ticket, (hipStream_t)stream);
     IG_REQUIRE(scratch, "ig_kd_mse_loss: scratch allocation failed");
-    hipLaunchKernelGGL(kd_mse_loss_kernel, dim3((unsigned)nblk), dim3(TPB), 0, (hipStream_t)stream, pred, teacher, labels, ignore_value,
-                       use_log_scale, sum, dpred, n, scratch, ticket);
-    return ig_check_launch("ig_kd_mse_loss");
+    return ig_launch<kd_mse_loss_kernel>("ig_kd_mse_loss", dim3((unsigned)pixel_grid(n)), dim3(TPB), 0, (hipStream_t)stream, pred, teacher, labels,
+                                         ignore_value, use_log_scale, sum, dpred, n, scratch, ticket);
 }
 
 int ig_argmax_i8(const float* logits, signed char* out, int B, long HW, int ncls, void* stream) {
@@ -1490,9 +1321,7 @@ int ig_argmax_i8(const float* logits, signed char* out, int B, long HW, int ncls
     IG_REQUIRE(ncls >= 1 && ncls <= 127, "ig_argmax_i8: 1 <= ncls <= 127");
     long M = (long)B * HW;
     if (M == 0) return IG_OK;
-    hipLaunchKernelGGL(argmax_kernel, dim3((unsigned)((M + TPB - 1) / TPB)), dim3(TPB), 0, (hipStream_t)stream, logits, out, M, HW,
-                       ncls);
-    return ig_check_launch("ig_argmax_i8");
+    return ig_launch<argmax_kernel>("ig_argmax_i8", dim3((unsigned)((M + TPB - 1) / TPB)), dim3(TPB), 0, (hipStream_t)stream, logits, out, M, HW, ncls);
 }
 
 int ig_confusion_update(const long long* y_true, const long long* y_pred, unsigned long long* confusion, long n, int k,
@@ -1502,9 +1331,8 @@ int ig_confusion_update(const long long* y_true, const long long* y_pred, unsign
     if (n == 0) return IG_OK;
     long g = (n + TPB - 1) / TPB;
     if (g > 4096) g = 4096;
-    hipLaunchKernelGGL(confusion_kernel, dim3((unsigned)g), dim3(TPB), (size_t)k * k * sizeof(unsigned), (hipStream_t)stream, y_true,
-                       y_pred, confusion, n, k, ignore_index, has_ignore);
-    return ig_check_launch("ig_confusion_update");
+    return ig_launch<confusion_kernel>("ig_confusion_update", dim3((unsigned)g), dim3(TPB), k * k * (int)sizeof(unsigned), (hipStream_t)stream, y_true,
+                                       y_pred, confusion, n, k, ignore_index, has_ignore);
 }
 
 }  // extern "C"

@@ -628,12 +628,23 @@ def classifier_bn_bwd(dlogits, x: BT, scale, shift, mean, rstd, w, dx: BT, dw, d
 _LABEL_DT = {torch.int64: 0, torch.int32: 1, torch.float32: 2}
 
 
-def ce_loss(logits, labels, class_weights, ignore_index: int, stats, dlogits=None, preds=None, preds_i8=None, confusion=None) -> None:
+def _pixel_shape(logits):
+    """(B, HW, ncls) of (B, ncls, ...) logits; HW = 0 for an empty batch (the entry points return at once on B * HW == 0)."""
     B, ncls = logits.shape[0], logits.shape[1]
-    HW = logits.numel() // (B * ncls)
+    return B, (logits.numel() // (B * ncls) if B * ncls else 0), ncls
+
+
+def _pixel_args(logits, labels, ignore_index):
+    """What every per-pixel loss / metric entry point takes: B, HW, ncls, the label pointer, the label dtype code of the C ABI and the
+    ignore value (``None`` = no label is ignored: a value no label takes)."""
+    return _pixel_shape(logits) + (_p(labels), _LABEL_DT[labels.dtype], -(2**62) if ignore_index is None else int(ignore_index))
+
+
+def ce_loss(logits, labels, class_weights, ignore_index: int, stats, dlogits=None, preds=None, preds_i8=None, confusion=None) -> None:
+    B, HW, ncls, lab, dt, ign = _pixel_args(logits, labels, ignore_index)
     work = float(B) * HW * (ncls * 4 + labels.element_size() + (ncls * 4 if dlogits is not None else 0) + (8 if preds is not None else 0)
                             + (1 if preds_i8 is not None else 0))
-    _call("ig_ce_loss", work, _p(_f32(logits)), _p(labels), _LABEL_DT[labels.dtype], _p(class_weights), int(ignore_index), _p(stats),
+    _call("ig_ce_loss", work, _p(_f32(logits)), lab, dt, _p(class_weights), ign, _p(stats),
           _p(dlogits), _p(preds), _p(preds_i8), _p(confusion), B, HW, ncls, _stream())
 
 
@@ -643,25 +654,22 @@ def seg_loss(logits, labels, class_weights, ignore_index: int, stats, dlogits=No
     """Focal + region (Dice / Tversky) loss, the arguments of :func:`ce_loss` first: ``stats`` (f64 [2]) += (pixel-term sum + #valid * region
     term, #valid), ``dlogits`` = the un-normalised gradient of ``stats[0]``, ``parts`` (f64 [2], optional) += the two summands.  The class
     sums of the region term run over the tensors given -- the local batch of a data-parallel rank, like the loss count."""
-    B, ncls = logits.shape[0], logits.shape[1]
-    HW = logits.numel() // (B * ncls)
+    B, HW, ncls, lab, dt, ign = _pixel_args(logits, labels, ignore_index)
     assert stats is None or stats.dtype == torch.float64
     assert parts is None or (parts.dtype == torch.float64 and parts.numel() >= 2)
     passes = 2 if region_weight > 0 and dlogits is not None else 1  # the region gradient re-reads logits, labels and dlogits
     work = float(B) * HW * (passes * (ncls * 4 + labels.element_size()) + (ncls * 4 * (2 * passes - 1) if dlogits is not None else 0)
                             + (8 if preds is not None else 0) + (1 if preds_i8 is not None else 0))
-    _call("ig_seg_loss", work, _p(_f32(logits)), _p(labels), _LABEL_DT[labels.dtype], _p(class_weights), int(ignore_index), float(focal_gamma),
+    _call("ig_seg_loss", work, _p(_f32(logits)), lab, dt, _p(class_weights), ign, float(focal_gamma),
           int(bool(pixel_term)), float(region_weight), float(region_smooth), float(tversky[0]), float(tversky[1]), _p(stats), _p(parts), _p(dlogits),
           _p(preds), _p(preds_i8), _p(confusion), B, HW, ncls, _stream())
 
 
 def kd_loss(student_logits, teacher_logits, labels, ignore_index: Optional[int], kl_sum, dlogits=None) -> None:
     """KLDivLoss(batchmean) numerator over the valid pixels into ``kl_sum`` (f64 [1]); ``dlogits`` += softmax(s) - softmax(t)."""
-    B, ncls = student_logits.shape[0], student_logits.shape[1]
-    HW = student_logits.numel() // (B * ncls)
+    B, HW, ncls, lab, dt, ign = _pixel_args(student_logits, labels, ignore_index)
     assert teacher_logits.shape == student_logits.shape and kl_sum.dtype == torch.float64
-    ign = -(2**62) if ignore_index is None else int(ignore_index)
-    _call("ig_kd_loss", float(B) * HW * ncls * 12, _p(_f32(student_logits)), _p(_f32(teacher_logits)), _p(labels), _LABEL_DT[labels.dtype], ign,
+    _call("ig_kd_loss", float(B) * HW * ncls * 12, _p(_f32(student_logits)), _p(_f32(teacher_logits)), lab, dt, ign,
           _p(kl_sum), _p(dlogits), B, HW, ncls, _stream())
 
 
@@ -686,11 +694,9 @@ def kd_mse_loss(pred, teacher, labels, ignore_index: float, use_log_scale: bool,
 
 def auc_update(logits, labels, ignore_index: Optional[int], hist, nbins: int, min_score: float = 0.0, max_score: float = 1.0) -> None:
     """RunningAUC histograms of softmax(logits): hist int64 [2, ncls, nbins] (0 positives, 1 negatives of each class)."""
-    B, ncls = logits.shape[0], logits.shape[1]
-    HW = logits.numel() // (B * ncls)
+    B, HW, ncls, lab, dt, ign = _pixel_args(logits, labels, ignore_index)
     assert hist.dtype == torch.int64 and hist.numel() == 2 * ncls * nbins
-    ign = -(2**62) if ignore_index is None else int(ignore_index)
-    _call("ig_auc_update", float(B) * HW * (ncls * 4 + labels.element_size()), _p(_f32(logits)), _p(labels), _LABEL_DT[labels.dtype], ign,
+    _call("ig_auc_update", float(B) * HW * (ncls * 4 + labels.element_size()), _p(_f32(logits)), lab, dt, ign,
           _p(hist), B, HW, ncls, nbins, float(min_score), float(max_score), _stream())
 
 
@@ -699,31 +705,26 @@ def calib_nll_grid(logits, labels, ignore_index: Optional[int], inv_temps, nll, 
     floats) in one pass: ``nll`` (f64 [K]) += the sums over the valid pixels, ``count`` (int64 [1]) += #valid.  Bit-reproducible."""
     import ctypes
 
-    B, ncls = logits.shape[0], logits.shape[1]
-    HW = logits.numel() // (B * ncls) if B * ncls else 0
+    B, HW, ncls, lab, dt, ign = _pixel_args(logits, labels, ignore_index)
     betas = [float(b) for b in inv_temps]
     K = len(betas)
     assert nll.dtype == torch.float64 and nll.numel() >= K and count.dtype == torch.int64 and count.numel() >= 1
-    ign = -(2**62) if ignore_index is None else int(ignore_index)
-    _call("ig_calib_nll_grid", float(B) * HW * (ncls * 4 + labels.element_size()), _p(_f32(logits)), _p(labels), _LABEL_DT[labels.dtype], ign,
+    _call("ig_calib_nll_grid", float(B) * HW * (ncls * 4 + labels.element_size()), _p(_f32(logits)), lab, dt, ign,
           (ctypes.c_float * max(K, 1))(*betas), K, _p(nll), _p(count), B, HW, ncls, _stream())
 
 
 def reliability_update(logits, labels, ignore_index: Optional[int], inv_temp: float, hist) -> None:
     """Reliability histograms of the top-class confidence of softmax(inv_temp * logits): ``hist`` int64 [ncls, 3, nbins] += (count,
     hits, confidence in units of 2^-24) per (predicted class, confidence bin) over the valid pixels.  Integer sums: order-independent."""
-    B, ncls = logits.shape[0], logits.shape[1]
-    HW = logits.numel() // (B * ncls) if B * ncls else 0
+    B, HW, ncls, lab, dt, ign = _pixel_args(logits, labels, ignore_index)
     assert hist.dtype == torch.int64 and hist.dim() == 3 and hist.shape[0] == ncls and hist.shape[1] == 3
-    ign = -(2**62) if ignore_index is None else int(ignore_index)
-    _call("ig_reliability_update", float(B) * HW * (ncls * 4 + labels.element_size()), _p(_f32(logits)), _p(labels), _LABEL_DT[labels.dtype],
-          ign, float(inv_temp), _p(hist), B, HW, ncls, int(hist.shape[2]), _stream())
+    _call("ig_reliability_update", float(B) * HW * (ncls * 4 + labels.element_size()), _p(_f32(logits)), lab, dt, ign, float(inv_temp), _p(hist),
+          B, HW, ncls, int(hist.shape[2]), _stream())
 
 
 def softmax_prob(logits, cls: int = 1, out=None):
     """softmax(logits, dim=1)[:, cls] -> (B, H, W) f32 (predict_step, segmentation.py:202-213)."""
-    B, ncls = logits.shape[0], logits.shape[1]
-    HW = logits.numel() // (B * ncls)
+    B, HW, ncls = _pixel_shape(logits)
     if out is None:
         out = torch.empty((B,) + tuple(logits.shape[2:]), dtype=torch.float32, device=logits.device)
     _call("ig_softmax_prob", float(B) * HW * (ncls * 4 + 4), _p(_f32(logits)), _p(out), B, HW, ncls, int(cls), _stream())
@@ -731,8 +732,7 @@ def softmax_prob(logits, cls: int = 1, out=None):
 
 
 def argmax_i8(logits, out=None):
-    B, ncls = logits.shape[0], logits.shape[1]
-    HW = logits.numel() // (B * ncls)
+    B, HW, ncls = _pixel_shape(logits)
     if out is None:
         out = torch.empty((B,) + tuple(logits.shape[2:]), dtype=torch.int8, device=logits.device)
     _call("ig_argmax_i8", float(B) * HW * (ncls * 4 + 1), _p(_f32(logits)), _p(out), B, HW, ncls, _stream())

@@ -2,7 +2,9 @@
 dlogits, at the two flagship head shapes (B = 432, K = 2 and B = 72, K = 13 at 224 x 224), next to the box's copy rate (the "copy"
 line of tools/hbm_ceiling.py -- a 1 GiB torch copy_ -- measured again here, in this process, with this file's event timing) and, with --step, the chips/s of a fused train step with loss = ce against focal_dice.
 
-    python tools/seg_loss_bench.py [--step] [--batch 432]
+    python tools/seg_loss_bench.py [--metrics] [--step] [--batch 432]
+
+IG_HIP_LIB=<another build> runs the same timings on that build (same-box A/B of two builds: alternate the two in separate processes).
 
 Each kernel variant is timed ROUNDS times, interleaved with the others (so drift hits all alike), each sample = REPS back-to-back launches
 between two HIP events after a warm-up; the table gives the median and the min-max spread of the samples, the ratio to ce_loss's median,
@@ -81,6 +83,37 @@ def kernels(B, K, rate):
         print(line)
 
 
+def metrics(B, K):
+    """The other label-walking kernels of the family: distillation loss, AUC histograms, temperature grid, reliability histograms."""
+    g = torch.Generator().manual_seed(7)
+    z = (torch.randn(B, K, 224, 224, generator=g) * 3).to(DEV)
+    zt = (torch.randn(B, K, 224, 224, generator=g) * 3).to(DEV)
+    y = torch.randint(-1, K, (B, 224, 224), generator=g).to(DEV)
+    kl = torch.zeros(1, dtype=torch.float64, device=DEV)
+    dl = torch.zeros_like(z)
+    auc = torch.zeros(2 * K * 100, dtype=torch.int64, device=DEV)
+    nll = torch.zeros(9, dtype=torch.float64, device=DEV)
+    cnt = torch.zeros(1, dtype=torch.int64, device=DEV)
+    rel = torch.zeros(K, 3, 15, dtype=torch.int64, device=DEV)
+    variants = {"kd_loss +dlogits": lambda: ops.kd_loss(z, zt, y, -1, kl, dl),
+                "auc_update 100 bins": lambda: ops.auc_update(z, y, -1, auc, 100),
+                "calib_nll_grid K=9": lambda: ops.calib_nll_grid(z, y, -1, [0.5 + 0.125 * k for k in range(9)], nll, cnt),
+                "reliability_update 15 bins": lambda: ops.reliability_update(z, y, -1, 1.0, rel)}
+    for fn in variants.values():
+        for _ in range(5):
+            fn()
+    torch.cuda.synchronize()
+    t = {k: [] for k in variants}
+    for _ in range(ROUNDS):
+        for k, fn in variants.items():
+            t[k].append(sample(fn))
+    print(f"\nB = {B}, K = {K}, 224 x 224, int64 labels; {ROUNDS} samples of {REPS} launches")
+    print(f"{'variant':40s} {'median us':>10s} {'min':>8s} {'max':>8s} {'spread':>7s}")
+    for k, v in t.items():
+        m = statistics.median(v)
+        print(f"{k:40s} {m:10.1f} {min(v):8.1f} {max(v):8.1f} {(max(v) - min(v)) / m * 100:6.1f}%")
+
+
 def step(B):
     from instageo_amd.segmentation import PrithviSegmentationModule
 
@@ -115,12 +148,16 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--step", action="store_true", help="also time the whole fused train step with loss = ce and focal_dice")
     ap.add_argument("--batch", type=int, default=432, help="batch of the --step leg")
+    ap.add_argument("--metrics", action="store_true", help="also time ig_kd_loss, ig_auc_update, ig_calib_nll_grid and ig_reliability_update")
     args = ap.parse_args()
     print(torch.cuda.get_device_name(0))
     rate = copy_rate()
     print(f"copy rate (1 GiB read + 1 GiB write): {rate / 1e12:.2f} TB/s")
     kernels(432, 2, rate)
     kernels(72, 13, rate)
+    if args.metrics:
+        metrics(432, 2)
+        metrics(72, 13)
     if args.step:
         step(args.batch)
 
