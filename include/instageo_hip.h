@@ -634,6 +634,51 @@ int ig_chip_cut(const short* tile, const unsigned char* fmask, const int* origin
                 void* stream);
 int ig_chip_labels(const int* origins, int n, int S, const int* ptr, const int* pts, const void* labels, long P, int elem_size, int w,
                    const unsigned char* validity, int valid_bit, int K, void* maps, int* valid_labels, int* hist, void* stream);
+/* Chips cut from Sentinel-2 L2A planes of several resolutions under the scene classification (s2_chips.hip; the reference's
+ * instageo/data/s2_utils.py: S2PointsPipeline on a stack that stackstac has resampled onto one resolution, create_mask_from_scl,
+ * MASK_DECODING_POS["S2"], apply_mask).  THE RULE:
+ * Planes.  T * C band planes, uint16, band b of date b / C, and T SCL planes, uint8, or none (scl NULL: no masking).  Plane k has its own
+ *   size H_k x W_k and its own square pixel size p_k, a positive integer (metres).  All planes and the output grid SHARE THE TOP-LEFT
+ *   CORNER (Sentinel-2 resolutions do; the host checks the tiepoints, the coordinate system and that every pixel scale is an integer).
+ * Packing.  The band planes lie row-major in one uint16 buffer `bands`, plane k at element offset starts[k] (int64, >= 0), as ig_warp packs
+ *   its sources; the SCL planes in one uint8 buffer `scl`, plane t at scl_starts[t].  geom holds (H_k, W_k, p_k) as int32, 3 per plane, the
+ *   T * C bands first and then, when scl is not NULL, the T SCL planes.  starts, scl_starts and geom are ON THE DEVICE.
+ * Output grid.  Pixel size p_o (integer metres), H_o x W_o pixels.  origins (n, 2) int32 = (row0, col0) on the OUTPUT grid: chip i is its
+ *   S x S window, wholly inside, 0 <= row0 <= H_o - S, 0 <= col0 <= W_o - S.
+ * Source pixel.  Output pixel (r, c) reads plane k at rs = ((2 r + 1) p_o) div (2 p_k), cs = ((2 c + 1) p_o) div (2 p_k), floor division in
+ *   exact integers: the NEAREST rule of ig_warp (the floor of the centre's source coordinate) without float64.  With p_k = 2 p_o a source
+ *   pixel fans out into 2 x 2 output pixels (rs = r div 2); with p_o = 2 p_k the output picks source pixel (2 r + 1, 2 c + 1).  An (rs, cs)
+ *   outside the plane gives the band value 0 and the SCL class 0 (stackstac's fill_value).
+ * Value chain of a band value v (an integer in [0, 65535]):
+ *   1. boa_offset > 0 and v != 0: v = max(v - boa_offset, 0) (the +1000 BOA_ADD_OFFSET of processing baseline >= 04.00; 0, the default,
+ *      is the reference, which does not subtract);
+ *   2. date t is MASKED at the pixel when scl_t < 32 and (class_bits >> scl_t) & 1 (class_bits: the OR of 1 << class over the requested
+ *      SCL classes, cloud 8 and 9, water 6, ...).  strategy 0 EACH / 1 ANY exactly as in ig_chip_cut; a masked value becomes no_data;
+ *   3. range != 0: a value outside [range_lo, range_hi] becomes no_data (the reference's chip.where((chip >= 0) & (chip <= 10000), 0): it
+ *      REPLACES the value, it does not clip, unlike the HLS rule).
+ * Per chip: chips (n, T * C, S, S) uint16; valid_values[i] int32 += the values that differ from no_data (the caller zeroes it); validity
+ *   (n, S, S) uint8, or NULL, with the bits of ig_chip_cut (bit 0: all values of the pixel differ from no_data, bit 1: at least one
+ *   does): it feeds ig_chip_labels unchanged.
+ * All results are integers or copies, and unique: the same bits for any launch geometry, run after run.
+ * ig_s2_chip_cut: a gather in the blocking of ig_chip_cut.  One workgroup of 256 threads owns 16 rows x 128 columns of one chip, a thread 8
+ *   consecutive output pixels of a row.  The SCL bytes are read once into a per-pixel date mask, then the T * C bands stream through (gather,
+ *   offset, mask, range, count, one 16-byte store); the validity byte comes from the same pass.  The read side is chosen per plane,
+ *   uniformly for the workgroup: p_k = p_o reads the 8 pixels in the widest units the address allows; p_k = 2 p_o reads the 4 or 5 source
+ *   pixels (odd first column: 5) the 8 outputs come from, 8 / 4 / 2 bytes at a time, and expands them in registers; any other ratio, and
+ *   any segment that crosses the chip's or the plane's edge, goes element by element: one 64-bit division for the thread's first pixel,
+ *   then quotient-and-remainder steps.  valid_values is reduced in the wave and the workgroup and added with one integer atomic per
+ *   workgroup; no workgroup waits on another.
+ *   1 <= T <= 32, C >= 1, S >= 1, S <= min(H_o, W_o), 1 <= p_o <= 2^15, H_o * W_o <= 2^31 - 1, T * C * S * S <= 2^31 - 1 (valid_values is
+ *   int32), n * T * C * S * S < 2^40, no_data, boa_offset and the range inside [0, 65535] with range_lo <= range_hi; these are refused
+ *   before any launch.  Per plane 1 <= p_k <= 2^15, H_k, W_k >= 1, H_k * W_k <= 2^31 - 1, 0 <= starts[k] and the packed totals below
+ *   2^40: the tables are on the device, so ops.s2_chip_cut checks them (and the origins) on the host before the upload, and the kernel is
+ *   the second fence: a plane whose entry breaks these bounds reads nothing and gives the fill, a chip whose origin breaks its bounds is
+ *   left unwritten and nothing is read for it.  The caller guarantees that starts[k] + H_k * W_k lies inside its buffer; no read leaves a
+ *   plane.  bands, chips 2-byte, the int32 arrays 4-byte, the int64 arrays 8-byte aligned.  n = 0 returns IG_OK without touching a pointer. */
+int ig_s2_chip_cut(const unsigned short* bands, const long long* starts, const unsigned char* scl, const long long* scl_starts,
+                   const int* geom, const int* origins, int n, int T, int C, int Ho, int Wo, int po, int S, unsigned class_bits, int strategy,
+                   int no_data, int boa_offset, int range, int range_lo, int range_hi, unsigned short* chips, int* valid_values,
+                   unsigned char* validity, void* stream);
 /* Chips warped onto label grids (raster_chips.hip; the reference's instageo/data/raster_chip_creator.py: HLSRasterPipeline.process_row on
  * a stack that stackstac has resampled onto the label's coordinate system and resolution, geo_utils.slice_xr_dataset, apply_mask,
  * mask_segmentation_map).  THE RULE:

@@ -21,8 +21,9 @@ but paints only when it lies inside the chip's pixel-centre bounds ([centre of t
 the first row, centre of the last row]), because the reference filters a chip's points with ``chip["x"].min() <= x <= chip["x"].max()``
 on pixel-centre coordinates.  A point in the outer half-pixel fringe of a chip therefore selects the chip without labelling it.
 
-Not done: STAC search and download, S2 / S1 sources, MGRS tile lookup, rotated rasters, and CSR point lists built on the device.  The
-label-raster pipeline, which resamples a tile to another grid, is :mod:`instageo_amd.raster_chips`.
+Not done: STAC search and download, the S1 source, MGRS tile lookup, rotated rasters, and CSR point lists built on the device.  The
+label-raster pipeline, which resamples a tile to another grid, is :mod:`instageo_amd.raster_chips`; Sentinel-2 L2A tiles, whose bands
+differ in resolution and whose mask is a class raster, go through :mod:`instageo_amd.s2_chips`.
 """
 from __future__ import annotations
 

@@ -115,6 +115,16 @@ DEFAULTS: Dict[str, Any] = {'root_dir': None,
  # (None: every complete chip of the grid, for inference), output_directory = where chips/, seg_maps/ and the dataset CSV go
  'chips': {'chip_size': 256, 'mask_types': [], 'masking_strategy': 'each', 'window_size': 0, 'task_type': 'seg', 'src_crs': 4326,
            'tiles': None, 'fmasks': None, 'records_file': None, 'output_directory': None},
+ # mode=create_s2_chips (the reference's S2PointsPipeline of instageo/data/s2_utils.py; s2_chips.py): tiles = the Sentinel-2 L2A band files
+ # (GeoTIFF / COG) ordered per date and band, each on its own grid (10 m, 20 m, 60 m) with one shared top-left corner; scl = one scene
+ # classification file per date (None: no masking); mask_types = names of SCL classes (cloud, water, cloud_shadow, cirrus, snow),
+ # mask_classes = further class numbers 0..31; spatial_resolution = the chips' pixel size in metres (None: that of the first band file);
+ # boa_offset = subtracted from every non-zero value (1000 for processing baseline >= 04.00; 0: the reference); valid_range = [lo, hi]
+ # outside which a value becomes 0 (None: no check); granule_id = the product name the tile id is taken from (None: from the first file
+ # name); records_file = the CSV of x, y, label, date (None: every complete chip of the grid, for inference)
+ 's2_chips': {'chip_size': 256, 'mask_types': [], 'mask_classes': [], 'masking_strategy': 'each', 'window_size': 0, 'task_type': 'seg',
+              'src_crs': 4326, 'spatial_resolution': None, 'boa_offset': 0, 'valid_range': None, 'tiles': None, 'scl': None,
+              'granule_id': None, 'records_file': None, 'output_directory': None},
  # mode=create_raster_chips (the reference's instageo/data/raster_chip_creator.py under its flag names; raster_chips.py): every label is a
  # raster of chip_size x chip_size pixels in EPSG:src_crs at spatial_resolution, listed in records_file (a CSV of label_filename, date
  # [, mgrs_tile_id]) and found under raster_path; the stack of tiles / fmasks is resampled onto each label's grid.  is_bbox_feature: no

@@ -1335,6 +1335,41 @@ def chip_cut(tile, fmask, origins, S: int, T: int, mask_bits: int = 0, strategy:
     return chips, valid, plane
 
 
+def s2_chip_cut(bands, starts, geom, scl, scl_starts, scl_geom, origins, S: int, out_grid, T: int, class_bits: int = 0,
+                strategy: str = "each", no_data_value: int = 0, boa_offset: int = 0, valid_range=None):
+    """``ig_s2_chip_cut`` (include/instageo_hip.h): ``bands`` the packed uint16 planes and ``scl`` the packed uint8 SCL planes (or None) as
+    1-D tensors on the device; ``starts`` / ``geom`` ((T * C,) element offsets, (T * C, 3) = H, W, pixel size), ``scl_starts`` /
+    ``scl_geom`` (T of each) and ``origins`` (n, 2) as host arrays: they are checked here (every plane inside its buffer, every chip
+    wholly inside the output grid ``out_grid`` = (H_o, W_o, p_o)) and uploaded.
+    -> (chips (n, T * C, S, S) uint16, valid_values (n,) int32, validity (n, S, S) uint8)."""
+    import numpy as np
+
+    from . import s2_chips as S2
+
+    assert bands.dtype == torch.uint16 and bands.dim() == 1, "the band planes are one packed 1-D uint16 buffer"
+    assert scl is None or (scl.dtype == torch.uint8 and scl.dim() == 1), "the SCL planes are one packed 1-D uint8 buffer"
+    st, g, sst, sg, o = S2.check_cut(int(bands.shape[0]), starts, geom, None if scl is None else int(scl.shape[0]), scl_starts, scl_geom,
+                                     origins, S, out_grid, T, class_bits, strategy, no_data_value, boa_offset, valid_range)
+    n, TC, S = o.shape[0], g.shape[0], int(S)
+    Ho, Wo, po = (int(v) for v in out_grid)
+    dev = bands.device
+    chips = torch.empty((n, TC, S, S), dtype=torch.uint16, device=dev)
+    valid = torch.zeros((n,), dtype=torch.int32, device=dev)
+    plane = torch.empty((n, S, S), dtype=torch.uint8, device=dev)
+    if n:
+        # alive until the launch is queued; the copies are stream-ordered
+        od = torch.from_numpy(o).to(dev)
+        gd = torch.from_numpy(np.ascontiguousarray(np.concatenate([g, sg]) if scl is not None else g)).to(dev)
+        sd = torch.from_numpy(st).to(dev)
+        ssd = torch.from_numpy(sst).to(dev) if scl is not None else None
+        lo, hi = (int(valid_range[0]), int(valid_range[1])) if valid_range is not None else (0, 0)
+        # HBM bytes: the chips and the validity plane written, the bands read at their own resolution (at most the bytes written)
+        _call("ig_s2_chip_cut", float(n) * S * S * (4 * TC + (T if scl is not None else 0) + 1), _p(bands), _p(sd), _p(scl), _p(ssd), _p(gd),
+              _p(od), n, int(T), TC // int(T), Ho, Wo, po, S, int(class_bits), S2.STRATEGIES[strategy], int(no_data_value), int(boa_offset),
+              int(valid_range is not None), lo, hi, _p(chips), _p(valid), _p(plane), _stream())
+    return chips, valid, plane
+
+
 def chip_labels(origins, S: int, ptr, pts, labels, w: int, validity, valid_bit: int, K: int, device="cuda"):
     """``ig_chip_labels`` (include/instageo_hip.h): ``origins`` (n, 2), ``ptr`` (n + 1,), ``pts`` (m, 3) = (row, col, original index) and
     ``labels`` (P,) int16 | float32 as host arrays: they are checked here (ptr monotone, every point inside its chip, every index inside

@@ -108,6 +108,27 @@ def read_stack(files: Sequence[str], what: str, dtype) -> Tuple[np.ndarray, Dict
     return np.ascontiguousarray(np.concatenate(planes, axis=0)), first
 
 
+def read_planes(files: Sequence[str], what: str, dtype) -> Tuple[np.ndarray, np.ndarray, List[Tuple[int, int]], List[Dict[str, Any]]]:
+    """The single-band rasters ``files``, whose sizes may differ, packed row-major into one 1-D buffer of ``dtype`` -> (buffer, starts: the
+    int64 element offset of every plane, [(H, W)], the files' profiles).  ValueError for a file with more than one band, or samples
+    ``dtype`` cannot hold (``what`` names them)."""
+    planes, shapes, profiles = [], [], []
+    for f in files:
+        a, prof = tiff.read(str(f))
+        if a.shape[0] != 1:
+            raise ValueError(f"{f}: {what} files hold one band each (got {a.shape[0]})")
+        if a.dtype != dtype:
+            if a.dtype.kind not in "iu" or a.size and (a.min() < np.iinfo(dtype).min or a.max() > np.iinfo(dtype).max):
+                raise ValueError(f"{f}: {what} samples must fit {np.dtype(dtype).name} (got {a.dtype.name})")
+            a = a.astype(dtype)
+        planes.append(a.reshape(-1))
+        shapes.append((int(a.shape[1]), int(a.shape[2])))
+        profiles.append(prof)
+    starts = np.concatenate([[0], np.cumsum([p.size for p in planes])[:-1]]).astype(np.int64) if planes else np.zeros(0, dtype=np.int64)
+    buf = np.ascontiguousarray(np.concatenate(planes)) if planes else np.zeros(0, dtype=dtype)
+    return buf, starts, shapes, profiles
+
+
 def write_dataset_csv(output_directory: str, chips: List[str], segs: List[Optional[str]], bbox: bool) -> str:
     """``chips_dataset.csv``: the rows already there plus the new pairs (``Input`` [, ``Label``], paths relative to the folder)."""
     import csv

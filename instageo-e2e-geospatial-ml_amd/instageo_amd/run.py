@@ -8,7 +8,9 @@ validation split -> ``calibration.json``; ``calibrate.*``, ``test.temperature`` 
 ``save_uncertainty``) is this project's, as are the region keys of both inference modes (``test.min_region`` / ``connectivity`` /
 ``sieve_passes`` / ``save_regions`` / ``save_polygons`` / ``zones``) and the COG keys of ``tile_inference`` (``test.cog`` / ``cog_blocksize`` /
 ``overview_levels`` / ``cog_compress``); ``create_chips`` (``chips.*``: HLS tiles and a table of labelled points -> chips, label maps and
-the dataset CSV the other modes read; the reference's ``instageo/data`` chip creator, :mod:`instageo_amd.chips`) ``create_raster_chips`` (``raster_chips.*``: HLS tiles
+the dataset CSV the other modes read; the reference's ``instageo/data`` chip creator, :mod:`instageo_amd.chips`), ``create_s2_chips``
+(``s2_chips.*``: the same from Sentinel-2 L2A band planes of several resolutions under the scene classification, the reference's
+``S2PointsPipeline``, :mod:`instageo_amd.s2_chips`), ``create_raster_chips`` (``raster_chips.*``: HLS tiles
 resampled onto the grids of label rasters, the reference's ``raster_chip_creator.py``, :mod:`instageo_amd.raster_chips`), ``clean_chips``
 (``clean.*``: the reference's ``data_cleaner.py``: the no-data chip filter and label buffering / limiting, :mod:`instageo_amd.clean`) and
 ``create_polygon_labels`` (``polygon_labels.*``: a GeoJSON of polygons burned into the label rasters and the records table that
@@ -44,6 +46,7 @@ from .pipeline_utils import compute_stats
 SEED = 1042  # pl.seed_everything(1042) in the reference (run.py:50)
 # the dataset-preparation modes -> the module whose ``run_from_config(cfg, device)`` runs them
 PREP_MODES = {"create_chips": "chips",  # HLS tiles + points -> chips, label maps and the dataset CSV
+              "create_s2_chips": "s2_chips",  # Sentinel-2 band planes of several resolutions + points -> chips, label maps, the dataset CSV
               "create_raster_chips": "raster_chips",  # HLS tiles + label rasters -> chips on the labels' grids
               "clean_chips": "clean",  # drop no-data chips, buffer / limit the label maps of a chip dataset
               "create_polygon_labels": "polygon_labels"}  # a GeoJSON of polygons -> label rasters + records.csv
