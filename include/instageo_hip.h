@@ -715,6 +715,60 @@ int ig_chip_warp(const short* tile, const unsigned char* fmask, const double* sr
                  const double* dst_grids, int n, int T, int C, int H, int W, int S, int mask_bits, int strategy, int no_data, int clip,
                  int clip_lo, int clip_hi, const void* labels, int elem_size, int valid_bit, int K, short* chips, int* valid_values,
                  unsigned char* validity, void* maps, int* valid_labels, int* hist, void* stream);
+/* Sentinel-2 chips warped onto label grids (s2_raster_chips.hip; the reference's instageo/data/raster_chip_creator.py:
+ * S2RasterPipeline.process_row on a stack that stackstac has resampled onto the label's coordinate system and resolution, then
+ * create_mask_from_scl, apply_mask, the range replacement and mask_segmentation_map).  THE RULE:
+ * Sources.  T * C band planes, uint16, band b of date b / C, and T SCL planes, uint8, or none (scl NULL: no masking), packed exactly as
+ *   ig_s2_chip_cut packs them: `bands` with starts[k] (int64 element offsets, >= 0), `scl` with scl_starts[t].  All planes are in ONE
+ *   coordinate system src_crs (5 doubles, as ig_warp defines them) but need not share a lattice, nor a corner: every plane belongs to
+ *   one of G geometry classes, 1 <= G <= 8.  plane_class int32, one entry per band plane and then, when scl is not NULL, one per SCL
+ *   plane, in [0, G); class_grid (G, 4) doubles = (X0, Y0, sx, sy) as ig_warp defines a grid; class_size (G, 2) int32 = (H, W).  A real
+ *   product has 2 or 3 classes (10 m, 20 m, 60 m).  All tables are ON THE DEVICE.
+ * Destination.  dst_crs (5 doubles) the one coordinate system of the n chips, dst_grids (n, 4) doubles the grid of every chip, ON THE
+ *   DEVICE; every chip is S x S: exactly as ig_chip_warp.
+ * Coordinates.  The centre of pixel (r, c) of chip i is taken to source map coordinates (x, y) ONCE, by the chain of ig_warp /
+ *   ig_chip_warp: where the five doubles of the two systems are equal the affine arithmetic alone, otherwise inverse projection of
+ *   dst_crs and forward projection of src_crs, (NaN, NaN) outside the domain.  For class g: u_g = (x - X0_g) / sx_g,
+ *   v_g = (Y0_g - y) / sy_g, the arithmetic of ig_chip_warp for its single grid, so with one class the source offsets are
+ *   ig_chip_warp's bit for bit.  NEAREST: cs = floor(u_g), rs = floor(v_g), tested on the float64 values.  When 0 <= rs < H_g and
+ *   0 <= cs < W_g the pixel reads source pixel (rs, cs) of every plane of class g; otherwise (NaN included) it takes no_data in every
+ *   band of class g and SCL class 0 in every SCL plane of class g; the other classes are unaffected.  A destination grid, or ANY of the
+ *   G class grids, whose values are not finite or whose pixel sizes are not positive gives a chip that is no_data everywhere (and
+ *   SCL class 0).  No read leaves a plane.
+ * Value chain of a band value v that was READ (a fill stays no_data), that of ig_s2_chip_cut unchanged:
+ *   1. boa_offset > 0 and v != 0: v = max(v - boa_offset, 0);
+ *   2. date t is MASKED at the pixel when scl_t < 32 and (class_bits >> scl_t) & 1; strategy 0 EACH / 1 ANY as in ig_chip_cut; a masked
+ *      value becomes no_data;
+ *   3. range != 0: a value outside [range_lo, range_hi] becomes no_data (replaced, not clipped).
+ * chips (n, T * C, S, S) uint16; valid_values[i] int32 += the values that differ from no_data; validity (n, S, S) uint8 or NULL with
+ *   the bits of ig_chip_cut (bit 0: all values of the pixel differ from no_data, bit 1: at least one does).
+ * Label maps: labels, elem_size, valid_bit, K, maps, valid_labels and hist exactly as in ig_chip_warp (int8 or float32, NaN -> -1,
+ *   -1 where the validity bit of valid_bit is clear, the histogram of int8 values in [0, K)).  The caller zeroes valid_values,
+ *   valid_labels and hist.
+ * All results are integers or copies, and unique: the same bits for any launch geometry, run after run.
+ * ig_s2_chip_warp: a gather in the blocking of ig_chip_warp, one launch for all n chips.  One workgroup of 256 threads owns a 64 x 64
+ *   block of one chip; a wave owns 64 consecutive pixels of a row and stores them with one instruction, a thread takes 16 rows.  A
+ *   thread evaluates the float64 chain ONCE per pixel and keeps (x, y) of its 16 pixels in registers.  The int32 source offsets
+ *   rs * W_g + cs (-1 for none) are held for ONE class at a time: class by class the thread derives its 16 offsets (two divisions per
+ *   pixel), gathers the SCL bytes of that class's SCL planes into the 32-bit date mask per pixel, and in a second sweep over the classes
+ *   derives the offsets again and streams that class's bands: gather, offset, mask, range, count, one store.  (16 x G offsets do not fit
+ *   the register file for G = 8; the affine step is cheap next to the projection.)  The validity byte and the label pixel come from
+ *   the same registers; valid_values and valid_labels are summed in the wave and the workgroup, the histogram in LDS, and added with
+ *   integer atomics, one set per workgroup; no workgroup waits on another.
+ *   1 <= T <= 32, C >= 1, 1 <= S <= 2^15, 1 <= G <= 8, T * C * S * S <= 2^31 - 1 (valid_values is int32), n * T * C * S * S < 2^40,
+ *   no_data, boa_offset and the range inside [0, 65535] with range_lo <= range_hi, elem_size 1 or 4 (also without labels),
+ *   0 <= K <= 128 and K > 0 needs elem_size 1 and labels, valid_bit 0, 1 or 2; these are refused before any launch.  Per table entry
+ *   0 <= plane_class < G, H_g, W_g >= 1, H_g * W_g <= 2^31 - 1, 0 <= starts[k]: the tables are on the device, so ops.s2_chip_warp checks
+ *   them on the host before the upload, and the kernel is the second fence: a plane whose class index or start breaks these bounds,
+ *   and every plane of a class whose size does, reads nothing and gives the fill (no_data, SCL class 0).  The caller guarantees that
+ *   starts[k] + H_g * W_g lies inside its buffer.  bands, chips 2-byte, the int32 arrays and float32 labels / maps 4-byte, the int64
+ *   and float64 arrays 8-byte aligned.  n = 0 returns IG_OK without touching a pointer. */
+int ig_s2_chip_warp(const unsigned short* bands, const long long* starts, const unsigned char* scl, const long long* scl_starts,
+                    const int* plane_class, const double* class_grid, const int* class_size, int G, const double* src_crs,
+                    const double* dst_crs, const double* dst_grids, int n, int T, int C, int S, unsigned class_bits, int strategy, int no_data,
+                    int boa_offset, int range, int range_lo, int range_hi, const void* labels, int elem_size, int valid_bit, int K,
+                    unsigned short* chips, int* valid_values, unsigned char* validity, void* maps, int* valid_labels, int* hist,
+                    void* stream);
 /* Web Mercator map tiles rendered from an overview pyramid (maptiles.hip; the reference's new_apps/backend/app/tiler_service.py answers
  * tiles/WebMercatorQuad/{z}/{x}/{y}@1x.png through TiTiler: a warp into EPSG:3857, an overview level, nearest sampling and a colormap or
  * rescale per request).  THE RULE:

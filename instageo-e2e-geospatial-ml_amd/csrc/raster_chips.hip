@@ -9,11 +9,13 @@
 //                         rs * W + cs (int32, -1: outside the tile or the domain) in registers.  Phase 2: the T Fmask bytes of each pixel
 //                         -> one 32-bit date mask per pixel.  Phase 3: the T * C bands stream through: gather, mask, clip, one store; the
 //                         all / some bits of the validity plane and the count of valid values accumulate.  Phase 4: the validity byte and
-//                         the label pixel (L = signed char | float; void: no labels) from the same registers.
+//                         the label pixel (L = signed char | float; void: no labels) from the same registers (chip_epilogue.h, shared
+//                         with s2_raster_chips.hip).
 //
 // Out-of-range accesses are impossible: a source offset is formed only after 0 <= floor(v) < H and 0 <= floor(u) < W held on the float64
 // values (NaN fails), H * W <= 2^31 - 1 is checked by the entry point, a grid that is not finite and positive yields no offset at all, and
 // every store and every label load is guarded by row < S and column < S of a chip index below n.
+#include "chip_epilogue.h"
 #include "common.h"
 #include "pixel_seg.h"
 #include "warp_proj.h"
@@ -21,17 +23,12 @@
 namespace {
 
 constexpr int RB = 64, RTPB = 256, RROWS = RB / 4;  // block side, threads, rows per thread
-constexpr int RMAX_T = 32, RMAX_K = 128, RMAX_S = 1 << 15;
+constexpr int RMAX_T = 32, RMAX_K = EPI_MAX_K, RMAX_S = 1 << 15;
 constexpr long RLIM40 = 1L << 40;
 
 struct WarpCutArgs {
     int T, C, H, W, S, mask_bits, any, no_data, clip, lo, hi, nb, valid_bit, K;
 };
-
-template <typename L>
-__device__ __forceinline__ bool label_nan(L) { return false; }
-template <>
-__device__ __forceinline__ bool label_nan<float>(float v) { return v != v; }
 
 template <typename L>  // signed char, float, or void (no labels)
 __global__ __launch_bounds__(RTPB) void chip_warp_kernel(const short* __restrict__ tile, const unsigned char* __restrict__ fmask,
@@ -129,37 +126,8 @@ __global__ __launch_bounds__(RTPB) void chip_warp_kernel(const short* __restrict
     }
 
     // phase 4: validity and labels
-    int lcount = 0;
-#pragma unroll
-    for (int k = 0; k < RROWS; ++k) {
-        if (!(live >> k & 1u)) continue;
-        const long at = (long)chip * cplane + at0 + (long)(4 * k) * a.S;
-        const unsigned m = (all >> k & 1u) | (some >> k & 1u) << 1;
-        if (validity) validity[at] = (unsigned char)m;
-        if constexpr (LABELS) {
-            L v = static_cast<const L*>(labels_v)[at];
-            if ((a.valid_bit && !(m & (unsigned)a.valid_bit)) || label_nan<L>(v)) v = (L)-1;
-            static_cast<L*>(maps_v)[at] = v;
-            if (v != (L)-1) {
-                ++lcount;
-                if constexpr (sizeof(L) == 1) {
-                    if (hist && (unsigned)(int)v < (unsigned)a.K) atomicAdd(&cells[(int)v], 1);
-                }
-            }
-        }
-    }
-    const int total = block_sum_int(count, part);
-    if (threadIdx.x == 0 && total) atomicAdd(valid_values + chip, total);
-    if constexpr (LABELS) {
-        __syncthreads();  // part is read by every thread before it is written again; also orders the histogram cells
-        const int ltotal = block_sum_int(lcount, part);
-        if (threadIdx.x == 0 && ltotal) atomicAdd(valid_labels + chip, ltotal);
-        if constexpr (sizeof(L) == 1) {
-            if (hist)
-                for (int k = threadIdx.x; k < a.K; k += RTPB)
-                    if (cells[k]) atomicAdd(hist + (long)chip * a.K + k, cells[k]);
-        }
-    }
+    chip_epilogue<L, RROWS, RTPB>(live, all, some, count, chip, cplane, at0, a.S, a.valid_bit, a.K, labels_v, valid_values, validity, maps_v,
+                                  valid_labels, hist, part, cells);
 }
 
 }  // namespace

@@ -133,6 +133,15 @@ DEFAULTS: Dict[str, Any] = {'root_dir': None,
  'raster_chips': {'tiles': None, 'fmasks': None, 'records_file': None, 'raster_path': None, 'output_directory': None, 'chip_size': 256,
                   'mask_types': [], 'masking_strategy': 'each', 'src_crs': 4326, 'spatial_resolution': 0.0002694945852358564,
                   'qa_check': True, 'task_type': 'seg', 'is_bbox_feature': False, 'bbox_feature_path': None, 'date': None, 'snap': True},
+ # mode=create_s2_raster_chips (the reference's S2RasterPipeline of instageo/data/s2_utils.py, the default source of raster_chip_creator.py;
+ # s2_raster_chips.py): tiles / scl / mask_types / mask_classes / boa_offset / granule_id as in s2_chips (the band files may lie on grids of
+ # any corner), records_file / raster_path / chip_size / src_crs / spatial_resolution / snap / qa_check as in raster_chips.  valid_range =
+ # [lo, hi] outside which a value becomes 0 ([0, 10000]: the reference always applies it here; None: no check).  is_bbox_feature: no labels,
+ # records_file is then the JSON list of boxes and the chips are named by the granule's date
+ 's2_raster_chips': {'tiles': None, 'scl': None, 'records_file': None, 'raster_path': None, 'output_directory': None, 'chip_size': 256,
+                     'mask_types': [], 'mask_classes': [], 'masking_strategy': 'each', 'src_crs': 4326,
+                     'spatial_resolution': 0.0002694945852358564, 'snap': True, 'qa_check': True, 'is_bbox_feature': False, 'boa_offset': 0,
+                     'valid_range': [0, 10000], 'granule_id': None},
  # mode=clean_chips (the reference's instageo/data/data_cleaner.py under its flag names; clean.py): drop the chips of chips_dataset_csv
  # whose share of no-data pixels is above the threshold, buffer the observation pixels of the label maps by window_size (or limit the maps
  # to the pixels of observation_points_csv), write output_chips_dataset_csv and clean_stats.json.  Not in the reference: num_classes

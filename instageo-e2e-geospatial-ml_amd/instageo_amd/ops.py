@@ -1452,6 +1452,68 @@ def chip_warp(tile, fmask, src_crs, src_grid, dst_crs, dst_grids, S: int, T: int
     return chips, valid, plane, maps, valid_labels, hist
 
 
+def s2_chip_warp(bands, starts, plane_class, class_grid, class_size, scl, scl_starts, src_crs, dst_crs, dst_grids, S: int, T: int,
+                 class_bits: int = 0, strategy: str = "each", no_data_value: int = 0, boa_offset: int = 0, valid_range=None, labels=None,
+                 valid_bit: int = 0, K: int = 0, out=None):
+    """``ig_s2_chip_warp`` (include/instageo_hip.h): ``bands`` the packed uint16 planes and ``scl`` the packed uint8 SCL planes (or None)
+    as 1-D tensors on the device; ``starts`` (T * C,), ``scl_starts`` (T,), ``plane_class`` (one entry per band plane, then one per SCL
+    plane), ``class_grid`` (G, 4) = (X0, Y0, sx, sy), ``class_size`` (G, 2) = (H, W), ``src_crs`` / ``dst_crs`` five doubles and
+    ``dst_grids`` (n, 4) as host values: they are checked here (every class index in [0, G), every plane inside its buffer) and
+    uploaded.  ``labels``: None, or (n, S, S) int8 | float32 as a device tensor or a host array.  -> (chips (n, T * C, S, S) uint16,
+    valid_values (n,) int32, validity (n, S, S) uint8, maps, valid_labels, hist): the last three None without labels, hist None with
+    K = 0.  ``out``: a dict with any of ``chips``, ``validity``, ``maps``: contiguous tensors to write into instead of new ones (every
+    element is written)."""
+    import numpy as np
+
+    from . import s2_raster_chips as R
+
+    assert bands.dtype == torch.uint16 and bands.dim() == 1, "the band planes are one packed 1-D uint16 buffer"
+    assert scl is None or (scl.dtype == torch.uint8 and scl.dim() == 1), "the SCL planes are one packed 1-D uint8 buffer"
+    lab_dtype = None if labels is None else str(labels.dtype).replace("torch.", "")
+    st, sst, pc, cg, cs, sc, dc, dg = R.check_warp(int(bands.shape[0]), starts, plane_class, class_grid, class_size,
+                                                   None if scl is None else int(scl.shape[0]), scl_starts, src_crs, dst_crs, dst_grids, S, T,
+                                                   class_bits, strategy, no_data_value, boa_offset, valid_range,
+                                                   None if labels is None else tuple(labels.shape), lab_dtype, valid_bit, K)
+    n, TC, G, S, T = dg.shape[0], st.shape[0], cg.shape[0], int(S), int(T)
+    dev = bands.device
+    out = dict(out or {})
+    if labels is not None and not torch.is_tensor(labels):
+        labels = torch.from_numpy(np.ascontiguousarray(labels))
+    if labels is not None:
+        labels = labels.to(dev)
+    chips = out.pop("chips", None)
+    plane = out.pop("validity", None)
+    maps = out.pop("maps", None)
+    assert not out, f"unknown outputs {sorted(out)}"
+    chips = chips if chips is not None else torch.empty((n, TC, S, S), dtype=torch.uint16, device=dev)
+    plane = plane if plane is not None else torch.empty((n, S, S), dtype=torch.uint8, device=dev)
+    assert chips.dtype == torch.uint16 and tuple(chips.shape) == (n, TC, S, S) and plane.dtype == torch.uint8 and tuple(plane.shape) == (n, S, S)
+    valid = torch.zeros((n,), dtype=torch.int32, device=dev)
+    valid_labels = hist = None
+    if labels is not None:
+        maps = maps if maps is not None else torch.empty_like(labels)
+        assert maps.dtype == labels.dtype and tuple(maps.shape) == (n, S, S)
+        valid_labels = torch.zeros((n,), dtype=torch.int32, device=dev)
+        hist = torch.zeros((n, K), dtype=torch.int32, device=dev) if K else None
+    else:
+        maps = None
+    if n:
+        # alive until the launch is queued; the copies are stream-ordered.  One upload of the doubles; every slice 8-byte aligned
+        dbl = torch.from_numpy(np.concatenate([sc, dc, cg.reshape(-1), dg.reshape(-1)])).to(dev)
+        ints = torch.from_numpy(np.concatenate([pc, cs.reshape(-1)])).to(dev)
+        sd = torch.from_numpy(st).to(dev)
+        ssd = torch.from_numpy(sst).to(dev) if scl is not None else None
+        lo, hi = (int(valid_range[0]), int(valid_range[1])) if valid_range is not None else (0, 0)
+        es = labels.element_size() if labels is not None else 1
+        # HBM bytes: the chips and the validity plane written, at most as many band values and SCL bytes gathered, the labels in and out
+        work = float(n) * S * S * (4 * TC + (T if scl is not None else 0) + 1 + (2 * es if labels is not None else 0))
+        _call("ig_s2_chip_warp", work, _p(bands), _p(sd), _p(scl), _p(ssd), _p(ints[: pc.shape[0]]), _p(dbl[10 : 10 + 4 * G]),
+              _p(ints[pc.shape[0] :]), G, _p(dbl[0:5]), _p(dbl[5:10]), _p(dbl[10 + 4 * G :]), n, T, TC // T, S, int(class_bits),
+              R.STRATEGIES[strategy], int(no_data_value), int(boa_offset), int(valid_range is not None), lo, hi, _p(labels), es, int(valid_bit),
+              int(K), _p(chips), _p(valid), _p(plane), _p(maps), _p(valid_labels), _p(hist), _stream())
+    return chips, valid, plane, maps, valid_labels, hist
+
+
 TILE_STYLES = {"palette": 0, "ramp": 1, "rgb": 2}  # include/instageo_hip.h
 TILE_MAX_LEVELS = 13
 

@@ -21,8 +21,9 @@ The destination grid of a record.  ``snap=True`` (the reference): stackstac snap
 bounds, so X = res * floor(minx / res), Y = res * ceil(maxy / res), in float64 on the host.  ``snap=False``: the label raster's own
 grid.  Either way the written chip and label carry the label raster's georeferencing (the reference's ``xr.align(join="override")``).
 
-Not done: S2 / S1 sources and SCL masks, STAC search and download, GeoPackage records (a CSV stands in), bilinear / cubic resampling of
-reflectances, rotated rasters.
+Not done: the S1 source, STAC search and download, GeoPackage records (a CSV stands in), bilinear / cubic resampling of reflectances,
+rotated rasters.  Sentinel-2 band planes of several resolutions under SCL masks (``S2RasterPipeline``) go through
+:mod:`instageo_amd.s2_raster_chips`.
 """
 from __future__ import annotations
 

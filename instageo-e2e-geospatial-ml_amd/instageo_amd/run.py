@@ -11,7 +11,9 @@ validation split -> ``calibration.json``; ``calibrate.*``, ``test.temperature`` 
 the dataset CSV the other modes read; the reference's ``instageo/data`` chip creator, :mod:`instageo_amd.chips`), ``create_s2_chips``
 (``s2_chips.*``: the same from Sentinel-2 L2A band planes of several resolutions under the scene classification, the reference's
 ``S2PointsPipeline``, :mod:`instageo_amd.s2_chips`), ``create_raster_chips`` (``raster_chips.*``: HLS tiles
-resampled onto the grids of label rasters, the reference's ``raster_chip_creator.py``, :mod:`instageo_amd.raster_chips`), ``clean_chips``
+resampled onto the grids of label rasters, the reference's ``raster_chip_creator.py``, :mod:`instageo_amd.raster_chips`),
+``create_s2_raster_chips`` (``s2_raster_chips.*``: Sentinel-2 band planes of several resolutions warped onto the grids of label rasters, the
+reference's ``S2RasterPipeline``, :mod:`instageo_amd.s2_raster_chips`), ``clean_chips``
 (``clean.*``: the reference's ``data_cleaner.py``: the no-data chip filter and label buffering / limiting, :mod:`instageo_amd.clean`) and
 ``create_polygon_labels`` (``polygon_labels.*``: a GeoJSON of polygons burned into the label rasters and the records table that
 ``create_raster_chips`` takes, :mod:`instageo_amd.polygon_labels`) build no model.  Hydra, Lightning and Neptune are replaced by :mod:`instageo_amd.config` and the explicit loop below, which logs the
@@ -48,6 +50,7 @@ SEED = 1042  # pl.seed_everything(1042) in the reference (run.py:50)
 PREP_MODES = {"create_chips": "chips",  # HLS tiles + points -> chips, label maps and the dataset CSV
               "create_s2_chips": "s2_chips",  # Sentinel-2 band planes of several resolutions + points -> chips, label maps, the dataset CSV
               "create_raster_chips": "raster_chips",  # HLS tiles + label rasters -> chips on the labels' grids
+              "create_s2_raster_chips": "s2_raster_chips",  # Sentinel-2 band planes + label rasters -> chips on the labels' grids
               "clean_chips": "clean",  # drop no-data chips, buffer / limit the label maps of a chip dataset
               "create_polygon_labels": "polygon_labels"}  # a GeoJSON of polygons -> label rasters + records.csv
 

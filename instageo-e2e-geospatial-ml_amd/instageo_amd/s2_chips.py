@@ -18,9 +18,9 @@ validity plane of :func:`chips.cut`, which :func:`chips.label_maps` reads unchan
 Device tensors go through ``ig_s2_chip_cut``; host arrays take a numpy twin of the same rule, so the module works (and is tested) without
 a GPU and both write the same bytes.
 
-Not done: JPEG 2000 / SAFE archives (there is no decoder here: the inputs are GeoTIFF / COG), STAC search and download, the S2
-label-raster pipeline (``S2RasterPipeline``), Sentinel-1, any resampling but nearest, and per-band offsets read from product metadata
-(``boa_offset`` is one number for all bands).
+Not done: JPEG 2000 / SAFE archives (there is no decoder here: the inputs are GeoTIFF / COG), STAC search and download, Sentinel-1, any
+resampling but nearest, and per-band offsets read from product metadata (``boa_offset`` is one number for all bands).  The S2 label-raster
+pipeline (``S2RasterPipeline``) is :mod:`instageo_amd.s2_raster_chips`.
 """
 from __future__ import annotations
 
