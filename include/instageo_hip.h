@@ -769,6 +769,57 @@ int ig_s2_chip_warp(const unsigned short* bands, const long long* starts, const 
                     int boa_offset, int range, int range_lo, int range_hi, const void* labels, int elem_size, int valid_bit, int K,
                     unsigned short* chips, int* valid_values, unsigned char* validity, void* maps, int* valid_labels, int* hist,
                     void* stream);
+/* Sentinel-1 chips cut from float32 RTC scenes stacked per date (s1_chips.hip; the reference's instageo/data/s1_utils.py:
+ * S1PointsPipeline on what stackstac.stack(..., epsg, resolution, fill_value = -1) has resampled, nearest, onto one lattice over the union
+ * of the scenes' bounds; NO_DATA_VALUES.S1 = -1, no mask band).  THE RULE:
+ * Sources.  T dates, 1 <= T <= 32, C >= 1 bands per date (a real product: vv, vh).  Date t has n_t >= 1 SCENES, the slices of its orbit,
+ *   listed date after date; N = the sum of the n_t <= 32.  first_bits marks where the dates begin: bit s is set when scene s is the first
+ *   scene of a date (so bit 0 is set, T bits are set in all and none at or above N).  Scene s has its own coordinate system
+ *   scene_crs[5 s ..] (5 doubles), its own grid scene_grid[4 s ..] = (X0, Y0, sx, sy) and its own size scene_size[2 s ..] = (H_s, W_s)
+ *   int32, all as ig_warp defines them, and C float32 planes, row-major in the one buffer `planes`, band b at the int64 element offset
+ *   starts[s C + b] >= 0.  All tables are ON THE DEVICE.
+ * Destination.  One coordinate system dst_crs (5 doubles) and one grid dst_grid (4 doubles), the STACK lattice, ON THE DEVICE; n chips of
+ *   S x S pixels; origins (n, 2) int32 = (row0, col0) of chip i's top-left pixel on the stack lattice, ON THE DEVICE.  An origin may be
+ *   negative or beyond every scene.
+ * Coordinates.  Pixel (r, c) of chip i has the centre x = X0 + (col0 + c + 0.5) sx, y = Y0 - (row0 + r + 0.5) sy on the stack's map.  For
+ *   scene s it has (u, v) by the chain of ig_warp / ig_chip_warp: where the five doubles of dst_crs and the scene's system are equal the
+ *   affine arithmetic alone, u = (x - X0_s) / sx_s, v = (Y0_s - y) / sy_s (the common case: every scene in the stack's UTM zone);
+ *   otherwise the inverse projection of dst_crs, evaluated ONCE per pixel and not once per scene, then the forward projection of the
+ *   scene's system, (NaN, NaN) outside the domain.  NEAREST: cs = floor(u), rs = floor(v), tested on the float64 values; the pixel lies
+ *   INSIDE scene s when 0 <= rs < H_s and 0 <= cs < W_s (NaN fails).  A stack grid whose values are not finite or whose pixel sizes are
+ *   not positive gives chips that are no_data everywhere; a scene whose grid is such, or whose size breaks 1 <= H_s, W_s,
+ *   H_s * W_s <= 2^31 - 1, reads nothing, and so does a plane with a negative start.  No read leaves a plane.
+ * Value of band b of date t at a pixel.  A value v is PRESENT when it is not NaN and, with has_src_nodata != 0, v != src_nodata (float32
+ *   comparison: the source's own no-data, e.g. -32768).  Walk the scenes of date t in list order: the first scene the pixel lies inside
+ *   and whose value of band b is present gives the value, its 32 bits copied (-0.0, denormals and infinities included).  If no scene
+ *   does, the value is no_data (float32; -1: stackstac's fill_value).  Presence is decided per value and not per scene: vv and vh of one
+ *   pixel may come from different slices.  With clip != 0 a present value v then becomes clip_lo where v < clip_lo and clip_hi where
+ *   v > clip_hi (the bits of the bound); a fill is not clipped.  A value that equals no_data counts as no-data wherever it came from (the
+ *   reference's chip != NO_DATA_VALUES.S1).
+ * Per chip: chips (n, T * C, S, S) float32, band b of date t in plane t C + b; valid_values[i] int32 += the values that differ from
+ *   no_data (float32 comparison; the caller zeroes it); validity (n, S, S) uint8, or NULL, with the bits of ig_chip_cut (bit 0: all
+ *   T * C values of the pixel differ from no_data, bit 1: at least one does): it feeds ig_chip_labels unchanged, which then reproduces
+ *   create_segmentation_map + mask_segmentation_map(chip, seg_map, -1, strategy): `any` reads bit 0, `each` bit 1.
+ * All results are copies or integers, and unique: the same bits for any launch geometry, run after run.
+ * ig_s1_chip_cut: a gather in the blocking of ig_chip_warp, one launch for all n chips.  One workgroup of 256 threads owns a 64 x 64
+ *   block of one chip; a wave owns 64 consecutive float32 of a row (256 bytes per store instruction), a thread takes 16 rows, 4 at a
+ *   time.  Only when some scene lives in another system a thread first keeps (lon, lat) of those pixels.  Then date by date, and within a
+ *   date slice by slice: the thread derives the slice's int32 source offsets rs * W_s + cs (-1 for none) and streams the C bands: a
+ *   4-byte gather, the presence test, clip, count, one store.  One 32-bit mask per pixel (a bit per band; C > 32 goes in groups of 32
+ *   bands) holds the values still pending: a present value is stored at once, the date's last slice stores whatever is still pending,
+ *   and a later slice is neither projected nor read for a pixel with nothing pending.  The offsets are held for ONE slice at a time
+ *   (16 x 32 do not fit the register file).  The validity byte comes from two per-pixel flags kept across the dates; valid_values is
+ *   summed in the wave and the workgroup and added with one integer atomic per workgroup; no workgroup waits on another.
+ *   1 <= T <= 32, C >= 1, 1 <= N <= 32 with first_bits as above (every n_t >= 1), 1 <= S <= 2^15, T * C * S * S <= 2^31 - 1
+ *   (valid_values is int32), n * T * C * S * S < 2^40, no_data and (when given) src_nodata not NaN, clip_lo <= clip_hi; these are refused
+ *   before any launch.  Per table entry H_s, W_s >= 1, H_s * W_s <= 2^31 - 1, 0 <= starts[k]: the tables are on the device, so
+ *   ops.s1_chip_cut checks them on the host before the upload, and the kernel is the second fence (above).  The caller guarantees that
+ *   starts[s C + b] + H_s * W_s lies inside the buffer.  planes, chips and the int32 arrays 4-byte, starts and the float64 arrays 8-byte
+ *   aligned.  n = 0 returns IG_OK without touching a pointer. */
+int ig_s1_chip_cut(const float* planes, const long long* starts, const double* scene_crs, const double* scene_grid, const int* scene_size,
+                   int N, unsigned first_bits, const double* dst_crs, const double* dst_grid, const int* origins, int n, int T, int C, int S,
+                   float no_data, int has_src_nodata, float src_nodata, int clip, float clip_lo, float clip_hi, float* chips,
+                   int* valid_values, unsigned char* validity, void* stream);
 /* Web Mercator map tiles rendered from an overview pyramid (maptiles.hip; the reference's new_apps/backend/app/tiler_service.py answers
  * tiles/WebMercatorQuad/{z}/{x}/{y}@1x.png through TiTiler: a warp into EPSG:3857, an overview level, nearest sampling and a colormap or
  * rescale per request).  THE RULE:

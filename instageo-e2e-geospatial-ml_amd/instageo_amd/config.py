@@ -142,6 +142,15 @@ DEFAULTS: Dict[str, Any] = {'root_dir': None,
                      'mask_types': [], 'mask_classes': [], 'masking_strategy': 'each', 'src_crs': 4326,
                      'spatial_resolution': 0.0002694945852358564, 'snap': True, 'qa_check': True, 'is_bbox_feature': False, 'boa_offset': 0,
                      'valid_range': [0, 10000], 'granule_id': None},
+ # mode=create_s1_chips (the reference's S1PointsPipeline of instageo/data/s1_utils.py; s1_chips.py): scenes = the Sentinel-1 RTC band files
+ # (float32 GeoTIFF / COG) as a list of dates, each a list of scenes (the slices of the orbit, tried in order), each a list of one file per
+ # band ([[[a_vv.tif, a_vh.tif]], [[b1_vv.tif, b1_vh.tif], [b2_vv.tif, b2_vh.tif]]]; a date written as one flat list is one scene);
+ # epsg = the coordinate system of the stack (None: the first scene's), spatial_resolution = its pixel size; no_data_value = the fill and
+ # the no-data value of the chips (-1: NO_DATA_VALUES.S1), src_nodata = the files' own no-data value (None: only NaN), clip = [lo, hi] for
+ # present values (None: the reference, which does not clip); records_file = the CSV of x, y, label, date (None: every complete chip)
+ 's1_chips': {'scenes': None, 'records_file': None, 'output_directory': None, 'chip_size': 256, 'bands': ['vv', 'vh'],
+              'masking_strategy': 'each', 'window_size': 0, 'task_type': 'seg', 'src_crs': 4326, 'epsg': None, 'spatial_resolution': 10,
+              'no_data_value': -1, 'src_nodata': None, 'clip': None},
  # mode=clean_chips (the reference's instageo/data/data_cleaner.py under its flag names; clean.py): drop the chips of chips_dataset_csv
  # whose share of no-data pixels is above the threshold, buffer the observation pixels of the label maps by window_size (or limit the maps
  # to the pixels of observation_points_csv), write output_chips_dataset_csv and clean_stats.json.  Not in the reference: num_classes

@@ -1514,7 +1514,46 @@ def s2_chip_warp(bands, starts, plane_class, class_grid, class_size, scl, scl_st
     return chips, valid, plane, maps, valid_labels, hist
 
 
-TILE_STYLES = {"palette": 0, "ramp": 1, "rgb": 2}  # include/instageo_hip.h
+def s1_chip_cut(planes, starts, scene_crs, scene_grid, scene_size, date_scenes, dst_crs, dst_grid, origins, S: int, no_data_value: float = -1.0,
+                src_nodata=None, clip=None, out=None):
+    """``ig_s1_chip_cut`` (include/instageo_hip.h): ``planes`` the packed float32 planes as a 1-D tensor on the device; ``date_scenes`` the
+    number of scenes of every date, ``starts`` (N * C,), ``scene_crs`` (N systems), ``scene_grid`` (N, 4) = (X0, Y0, sx, sy), ``scene_size``
+    (N, 2) = (H, W), ``dst_crs``, ``dst_grid`` (4,) and ``origins`` (n, 2) as host values: they are checked here (every plane inside the
+    buffer) and uploaded.  -> (chips (n, T * C, S, S) float32, valid_values (n,) int32, validity (n, S, S) uint8).  ``out``: a dict with
+    any of ``chips``, ``validity``: contiguous tensors to write into instead of new ones (every element is written)."""
+    import numpy as np
+
+    from . import s1_chips as V
+
+    assert planes.dtype == torch.float32 and planes.dim() == 1, "the planes are one packed 1-D float32 buffer"
+    st, sc, sg, ss, first_bits, T, C, dc, dg, o, nd, snd, clip = V.check_cut(int(planes.shape[0]), starts, scene_crs, scene_grid, scene_size,
+                                                                            date_scenes, dst_crs, dst_grid, origins, S, no_data_value,
+                                                                            src_nodata, clip)
+    n, N, S = o.shape[0], sg.shape[0], int(S)
+    dev = planes.device
+    out = dict(out or {})
+    chips = out.pop("chips", None)
+    plane = out.pop("validity", None)
+    assert not out, f"unknown outputs {sorted(out)}"
+    chips = chips if chips is not None else torch.empty((n, T * C, S, S), dtype=torch.float32, device=dev)
+    plane = plane if plane is not None else torch.empty((n, S, S), dtype=torch.uint8, device=dev)
+    assert chips.dtype == torch.float32 and tuple(chips.shape) == (n, T * C, S, S) and plane.dtype == torch.uint8 and tuple(plane.shape) == (n, S, S)
+    valid = torch.zeros((n,), dtype=torch.int32, device=dev)
+    if n:
+        # alive until the launch is queued; the copies are stream-ordered.  One upload of the doubles; every slice 8-byte aligned
+        dbl = torch.from_numpy(np.concatenate([dc, dg, sc.reshape(-1), sg.reshape(-1)])).to(dev)
+        ints = torch.from_numpy(np.concatenate([ss.reshape(-1), o.reshape(-1)])).to(dev)
+        sd = torch.from_numpy(st).to(dev)
+        lo, hi = (float(clip[0]), float(clip[1])) if clip is not None else (0.0, 0.0)
+        # HBM bytes: the chips and the validity plane written, at least as many values gathered
+        work = float(n) * S * S * (8 * T * C + 1)
+        _call("ig_s1_chip_cut", work, _p(planes), _p(sd), _p(dbl[9 : 9 + 5 * N]), _p(dbl[9 + 5 * N :]), _p(ints[: 2 * N]), N, int(first_bits),
+              _p(dbl[0:5]), _p(dbl[5:9]), _p(ints[2 * N :]), n, T, C, S, float(nd), int(snd is not None), float(snd) if snd is not None else 0.0,
+              int(clip is not None), lo, hi, _p(chips), _p(valid), _p(plane), _stream())
+    return chips, valid, plane
+
+
+TILE_STYLES ={"palette": 0, "ramp": 1, "rgb": 2}  # include/instageo_hip.h
 TILE_MAX_LEVELS = 13
 
 

@@ -51,6 +51,7 @@ PREP_MODES = {"create_chips": "chips",  # HLS tiles + points -> chips, label map
               "create_s2_chips": "s2_chips",  # Sentinel-2 band planes of several resolutions + points -> chips, label maps, the dataset CSV
               "create_raster_chips": "raster_chips",  # HLS tiles + label rasters -> chips on the labels' grids
               "create_s2_raster_chips": "s2_raster_chips",  # Sentinel-2 band planes + label rasters -> chips on the labels' grids
+              "create_s1_chips": "s1_chips",  # Sentinel-1 RTC scenes stacked per date + points -> float32 chips, label maps, the dataset CSV
               "clean_chips": "clean",  # drop no-data chips, buffer / limit the label maps of a chip dataset
               "create_polygon_labels": "polygon_labels"}  # a GeoJSON of polygons -> label rasters + records.csv
 
