@@ -27,9 +27,8 @@ differ in resolution and whose mask is a class raster, go through :mod:`instageo
 """
 from __future__ import annotations
 
-import json
 import os
-from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
+from typing import Any, Callable, Dict, List, NamedTuple, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
@@ -73,13 +72,7 @@ def check_cut(tile_shape, fmask_shape, origins, S: int, T: int, bits: int, strat
     _, H, W = prep.check_stack_args(tile_shape, fmask_shape, int(S), T, bits, strategy, no_data_value, clip)
     if S > H or S > W:
         raise ValueError(f"a chip of side {S} does not fit a tile of {H} x {W} pixels")
-    o = np.asarray(origins)
-    if o.size and o.dtype.kind not in "iu":
-        raise ValueError("origins must be integers")
-    o = o.astype(np.int64).reshape(-1, 2)
-    if o.size and (o.min() < 0 or (o[:, 0] > H - S).any() or (o[:, 1] > W - S).any()):
-        raise ValueError(f"a chip of side {S} at one of the origins does not lie wholly inside the tile of {H} x {W} pixels")
-    return np.ascontiguousarray(o, dtype=np.int32)
+    return prep.check_origins(origins, S, H, W, "tile of")
 
 
 def check_labels(origins, S: int, ptr, pts, P: int, w: int, K: int, task_type: str, label_strategy) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
@@ -287,6 +280,105 @@ def _chip_profile(profile: Dict[str, Any], grid, r0: int, c0: int) -> Dict[str, 
     return {"tags": tags, "nodata": None}
 
 
+class PointSource(NamedTuple):
+    """What a point mode has read and staged, as :func:`create_from_points` takes it."""
+
+    profile: Dict[str, Any]  # the lattice the chips are cut on, as a raster profile
+    grid: Tuple[float, float, float, float]  # (X0, Y0, sx, sy) of the lattice
+    shape: Tuple[int, int]  # its (H, W)
+    tile_id: str
+    date: Optional[str]  # the YYYYMMDD of the names in the bounding-box case when the caller gives none
+    noun: str  # of "no point lies inside the ..."
+    cut: Callable[[np.ndarray, bool], Tuple[Any, Any, Any]]  # (origins, bbox) -> (chips, valid_values, validity)
+    bbox_dtype: Optional[Any]  # what a bounding-box chip is written as (None: as cut)
+
+
+def create_from_points(source: PointSource, points, output_directory: str, chip_size: int, window_size: int, task_type: str, src_crs,
+                       label_strategy: Optional[str], num_classes: Optional[int], date: Optional[str]) -> Tuple[List[str], List[Optional[str]]]:
+    """The pipeline the point modes share (:func:`create_chips`, :func:`s2_chips.create_s2_chips`, :func:`s1_chips.create_s1_chips`) from
+    the lattice of ``source`` on: the chips the ``points`` nominate (None: every complete chip of the lattice), without those whose files
+    exist, cut by one call of ``source.cut``; their label maps, masked at the validity bit of ``label_strategy``; a chip is dropped when
+    ``valid_values == 0``, then a pair when ``valid_labels == 0``; the label map is written before its chip; ``chips_dataset.csv`` and
+    ``chips_stats.json``.  ``num_classes`` None: the largest label + 1, ``MAX_CLASSES`` at most.  -> (chip names, label-map names)."""
+    S = int(chip_size)
+    profile, grid, (H, W), tile_id = source.profile, source.grid, source.shape, source.tile_id
+    stats: Dict[str, Any] = {"nominated": 0, "kept": 0, "dropped": {"out_of_bounds": 0, "existing": 0, "no_valid_values": 0, "no_valid_labels": 0}}
+    bbox = points is None
+    if bbox:
+        chip_xy = np.array([(cx, cy) for cx in range(W // S) for cy in range(H // S)], dtype=np.int64).reshape(-1, 2)
+        date_id = date or source.date
+        ptr = pts = labels = None
+    else:
+        tab = _read_points(points)
+        keep, rows, cols, tx, ty = locate_points(tab["x"], tab["y"], src_crs, profile, (H, W))
+        if keep.size == 0:
+            raise ValueError(f"no point lies inside the {source.noun}")
+        date_id = date or tab["date"].iloc[int(keep[0])].strftime("%Y%m%d")
+        labels = np.asarray(tab["label"])
+        chip_xy, beyond, ptr, pts = group_points(rows, cols, tx, ty, keep, S, (H, W), grid)
+        stats["dropped"]["out_of_bounds"] = beyond
+        stats["nominated"] = beyond
+    stats["nominated"] += int(chip_xy.shape[0])
+    chip_dir, seg_dir = os.path.join(output_directory, "chips"), os.path.join(output_directory, "seg_maps")
+    os.makedirs(chip_dir, exist_ok=True)
+    if not bbox:
+        os.makedirs(seg_dir, exist_ok=True)
+    names = [(f"chip_{date_id}_{tile_id}_{x}_{y}.tif", f"seg_map_{date_id}_{tile_id}_{x}_{y}.tif") for x, y in chip_xy.tolist()]
+    fresh = np.array([not (os.path.exists(os.path.join(chip_dir, c)) or (not bbox and os.path.exists(os.path.join(seg_dir, s))))
+                      for c, s in names], dtype=bool)
+    stats["dropped"]["existing"] = int((~fresh).sum())
+    sel = np.nonzero(fresh)[0]
+    origins = np.stack((chip_xy[sel, 1] * S, chip_xy[sel, 0] * S), axis=-1).astype(np.int32).reshape(-1, 2)
+    chips_out: List[str] = []
+    segs_out: List[Optional[str]] = []
+    hist_sum = None
+    if sel.size:
+        chips, valid_values, validity = source.cut(origins, bbox)
+        valid_values = to_host(valid_values)
+        maps = valid_labels = hist = None
+        if not bbox:
+            # the lists of the chips that are cut: the rows of the fresh ones, re-based
+            cnt = np.diff(ptr)[sel]
+            take = np.concatenate([np.arange(ptr[i], ptr[i + 1]) for i in sel])
+            sub_ptr = np.concatenate([[0], np.cumsum(cnt)])
+            lab = labels.astype(np.float32) if task_type == "reg" else labels
+            K = int(num_classes) if num_classes is not None else 0
+            if task_type == "seg" and num_classes is None:
+                K = int(min(max(int(np.max(lab)) + 1, 1), MAX_CLASSES)) if lab.size else 1
+            maps, valid_labels, hist = label_maps(origins, S, sub_ptr, pts[take.astype(np.int64)], lab, window_size, validity, label_strategy,
+                                                  task_type, K if task_type == "seg" else 0)
+            maps, valid_labels = to_host(maps), to_host(valid_labels)
+            if hist is not None:
+                hist_sum = np.zeros(K, dtype=np.int64)
+                hist = to_host(hist)
+        for k, i in enumerate(sel.tolist()):
+            if valid_values[k] == 0:  # the reference's "no valid data pixels"
+                stats["dropped"]["no_valid_values"] += 1
+                continue
+            if not bbox and valid_labels[k] == 0:  # "empty label"
+                stats["dropped"]["no_valid_labels"] += 1
+                continue
+            prof = _chip_profile(profile, grid, int(origins[k, 0]), int(origins[k, 1]))
+            chip = to_host(chips[k])
+            if bbox:
+                if source.bbox_dtype is not None:
+                    chip = chip.astype(source.bbox_dtype)
+                segs_out.append(None)
+            else:
+                tiff.write(os.path.join(seg_dir, names[i][1]), maps[k], prof)
+                segs_out.append(names[i][1])
+                if hist_sum is not None:
+                    hist_sum += hist[k]
+            tiff.write(os.path.join(chip_dir, names[i][0]), chip, prof)
+            chips_out.append(names[i][0])
+    stats["kept"] = len(chips_out)
+    prep.write_dataset_csv(output_directory, chips_out, segs_out, bbox)
+    if hist_sum is not None:
+        stats.update(prep.class_stats(hist_sum))
+    prep.write_stats(os.path.join(output_directory, "chips_stats.json"), stats)
+    return chips_out, segs_out
+
+
 def create_chips(tile_files: Sequence[str], fmask_files: Optional[Sequence[str]], points, output_directory: str, chip_size: int = 256,
                  mask_types: Sequence[str] = (), masking_strategy: str = "each", window_size: int = 0, task_type: str = "seg",
                  src_crs: int = 4326, no_data_value: int = NO_DATA_VALUE, num_classes: Optional[int] = None, device: Optional[str] = None,
@@ -326,82 +418,13 @@ def create_chips(tile_files: Sequence[str], fmask_files: Optional[Sequence[str]]
     fmask = prep.read_stack(fmask_files, "Fmask", np.uint8)[0] if use_mask else None
     H, W = tile.shape[1:]
     grid = warp.grid_of(profile, str(tile_files[0]))
-    stats: Dict[str, Any] = {"nominated": 0, "kept": 0, "dropped": {"out_of_bounds": 0, "existing": 0, "no_valid_values": 0, "no_valid_labels": 0}}
-    bbox = points is None
-    if bbox:
-        chip_xy = np.array([(cx, cy) for cx in range(W // S) for cy in range(H // S)], dtype=np.int64).reshape(-1, 2)
-        date_id = date or prep.hls_date(tile_files[0])
-        ptr = pts = labels = None
-    else:
-        tab = _read_points(points)
-        keep, rows, cols, tx, ty = locate_points(tab["x"], tab["y"], src_crs, profile, (H, W))
-        if keep.size == 0:
-            raise ValueError("no point lies inside the tile")
-        date_id = date or tab["date"].iloc[int(keep[0])].strftime("%Y%m%d")
-        labels = np.asarray(tab["label"])
-        chip_xy, beyond, ptr, pts = group_points(rows, cols, tx, ty, keep, S, (H, W), grid)
-        stats["dropped"]["out_of_bounds"] = beyond
-        stats["nominated"] = beyond
-    stats["nominated"] += int(chip_xy.shape[0])
-    chip_dir, seg_dir = os.path.join(output_directory, "chips"), os.path.join(output_directory, "seg_maps")
-    os.makedirs(chip_dir, exist_ok=True)
-    if not bbox:
-        os.makedirs(seg_dir, exist_ok=True)
-    names = [(f"chip_{date_id}_{tile_id}_{x}_{y}.tif", f"seg_map_{date_id}_{tile_id}_{x}_{y}.tif") for x, y in chip_xy.tolist()]
-    fresh = np.array([not (os.path.exists(os.path.join(chip_dir, c)) or (not bbox and os.path.exists(os.path.join(seg_dir, s))))
-                      for c, s in names], dtype=bool)
-    stats["dropped"]["existing"] = int((~fresh).sum())
-    sel = np.nonzero(fresh)[0]
-    origins = np.stack((chip_xy[sel, 1] * S, chip_xy[sel, 0] * S), axis=-1).astype(np.int32).reshape(-1, 2)
-    chips_out: List[str] = []
-    segs_out: List[Optional[str]] = []
-    hist_sum = None
-    if sel.size:
+    def cut_at(origins, bbox):
         t_dev, f_dev = prep.stage(tile, fmask, device)
-        chips, valid_values, validity = cut(t_dev, f_dev, origins, S, dates=T, mask=bits, strategy=masking_strategy,
-                                            no_data_value=no_data_value, clip=(0, 10000) if bbox else None)
-        valid_values = to_host(valid_values)
-        maps = valid_labels = None
-        if not bbox:
-            # the lists of the chips that are cut: the rows of the fresh ones, re-based
-            cnt = np.diff(ptr)[sel]
-            take = np.concatenate([np.arange(ptr[i], ptr[i + 1]) for i in sel]) if sel.size else np.zeros(0, dtype=np.int64)
-            sub_ptr = np.concatenate([[0], np.cumsum(cnt)])
-            lab = labels.astype(np.float32) if task_type == "reg" else labels
-            K = int(num_classes) if num_classes is not None else 0
-            if task_type == "seg" and num_classes is None:
-                K = int(min(max(int(np.max(lab)) + 1, 1), MAX_CLASSES)) if lab.size else 1
-            maps, valid_labels, hist = label_maps(origins, S, sub_ptr, pts[take.astype(np.int64)], lab, window_size, validity, "any",
-                                                  task_type, K if task_type == "seg" else 0)
-            maps, valid_labels = to_host(maps), to_host(valid_labels)
-            if hist is not None:
-                hist_sum = np.zeros(K, dtype=np.int64)
-                hist = to_host(hist)
-        for k, i in enumerate(sel.tolist()):
-            if valid_values[k] == 0:
-                stats["dropped"]["no_valid_values"] += 1
-                continue
-            if not bbox and valid_labels[k] == 0:
-                stats["dropped"]["no_valid_labels"] += 1
-                continue
-            prof = _chip_profile(profile, grid, int(origins[k, 0]), int(origins[k, 1]))
-            chip = to_host(chips[k])
-            if bbox:
-                tiff.write(os.path.join(chip_dir, names[i][0]), chip.astype(np.uint16), prof)
-                segs_out.append(None)
-            else:
-                tiff.write(os.path.join(seg_dir, names[i][1]), maps[k], prof)
-                tiff.write(os.path.join(chip_dir, names[i][0]), chip, prof)
-                segs_out.append(names[i][1])
-                if hist_sum is not None:
-                    hist_sum += hist[k]
-            chips_out.append(names[i][0])
-    stats["kept"] = len(chips_out)
-    prep.write_dataset_csv(output_directory, chips_out, segs_out, bbox)
-    if hist_sum is not None:
-        stats.update(prep.class_stats(hist_sum))
-    prep.write_stats(os.path.join(output_directory, "chips_stats.json"), stats)
-    return chips_out, segs_out
+        return cut(t_dev, f_dev, origins, S, dates=T, mask=bits, strategy=masking_strategy, no_data_value=no_data_value,
+                   clip=(0, 10000) if bbox else None)
+
+    source = PointSource(profile, grid, (H, W), tile_id, prep.hls_date(tile_files[0]) if points is None else None, "tile", cut_at, np.uint16)
+    return create_from_points(source, points, output_directory, S, window_size, task_type, src_crs, "any", num_classes, date)
 
 
 # ---- mode=create_chips ---------------------------------------------------------------------------------------------------------------------
@@ -433,11 +456,7 @@ def chips_options(cfg: Dict[str, Any]) -> Dict[str, Any]:
 
 def run_from_config(cfg: Dict[str, Any], device: Optional[str] = None) -> int:
     """``mode=create_chips``: :func:`create_chips` under the ``chips.*`` keys; prints one JSON line with the counts."""
-    kw = chips_options(cfg)
-    chips, segs = create_chips(device=device, **kw)
-    print(json.dumps({"create_chips": {"chips": len(chips), "seg_maps": sum(s is not None for s in segs),
-                                       "output_directory": kw["output_directory"]}}))
-    return 0
+    return prep.run_creator("create_chips", create_chips, chips_options(cfg), device)
 
 
 def main(argv: Optional[List[str]] = None) -> int:

@@ -1311,6 +1311,30 @@ def warp(src, starts, src_crs, src_grid, src_size, bin_ptr, bin_idx, dst_crs, ds
     return (dst, sid) if src_id else dst
 
 
+def _chip_outputs(out, dev, shape, dtype, labels=None, K: int = 0):
+    """The output tensors of a chip launch, checked.  ``out``: None, or a dict with any of ``chips``, ``validity`` and (with ``labels``, on
+    the device) ``maps``: contiguous tensors to write into instead of new ones.  -> (chips ``shape`` = (n, T * C, S, S) of ``dtype``,
+    validity (n, S, S) uint8, valid_values (n,) int32 zeros, maps like ``labels``, valid_labels (n,) int32 zeros, hist (n, K) int32 zeros):
+    the last three None without labels, hist None with K = 0."""
+    n, S = shape[0], shape[-1]
+    out = dict(out or {})
+    chips = out.pop("chips", None)
+    plane = out.pop("validity", None)
+    maps = out.pop("maps", None) if labels is not None else None
+    assert not out, f"unknown outputs {sorted(out)}"
+    chips = chips if chips is not None else torch.empty(shape, dtype=dtype, device=dev)
+    plane = plane if plane is not None else torch.empty((n, S, S), dtype=torch.uint8, device=dev)
+    assert chips.dtype == dtype and tuple(chips.shape) == tuple(shape) and plane.dtype == torch.uint8 and tuple(plane.shape) == (n, S, S)
+    valid = torch.zeros((n,), dtype=torch.int32, device=dev)
+    valid_labels = hist = None
+    if labels is not None:
+        maps = maps if maps is not None else torch.empty_like(labels)
+        assert maps.dtype == labels.dtype and tuple(maps.shape) == (n, S, S)
+        valid_labels = torch.zeros((n,), dtype=torch.int32, device=dev)
+        hist = torch.zeros((n, K), dtype=torch.int32, device=dev) if K else None
+    return chips, plane, valid, maps, valid_labels, hist
+
+
 def chip_cut(tile, fmask, origins, S: int, T: int, mask_bits: int = 0, strategy: str = "each", no_data_value: int = 0, clip=None):
     """``ig_chip_cut`` (include/instageo_hip.h): ``tile`` (T * C, H, W) int16 and ``fmask`` (T, H, W) uint8 or None on the device,
     ``origins`` (n, 2) = (row0, col0) as a host array: it is checked here, so that every chip lies wholly inside the tile, and uploaded.
@@ -1322,9 +1346,7 @@ def chip_cut(tile, fmask, origins, S: int, T: int, mask_bits: int = 0, strategy:
     o = C.check_cut(tuple(tile.shape), None if fmask is None else tuple(fmask.shape), origins, S, T, mask_bits, strategy, no_data_value, clip)
     n, (TC, H, W) = o.shape[0], tile.shape
     dev = tile.device
-    chips = torch.empty((n, TC, S, S), dtype=torch.int16, device=dev)
-    valid = torch.zeros((n,), dtype=torch.int32, device=dev)
-    plane = torch.empty((n, S, S), dtype=torch.uint8, device=dev)
+    chips, plane, valid = _chip_outputs(None, dev, (n, TC, S, S), torch.int16)[:3]
     if n:
         od = torch.from_numpy(o).to(dev)  # alive until the launch is queued; the copy is stream-ordered
         lo, hi = (int(clip[0]), int(clip[1])) if clip is not None else (0, 0)
@@ -1353,9 +1375,7 @@ def s2_chip_cut(bands, starts, geom, scl, scl_starts, scl_geom, origins, S: int,
     n, TC, S = o.shape[0], g.shape[0], int(S)
     Ho, Wo, po = (int(v) for v in out_grid)
     dev = bands.device
-    chips = torch.empty((n, TC, S, S), dtype=torch.uint16, device=dev)
-    valid = torch.zeros((n,), dtype=torch.int32, device=dev)
-    plane = torch.empty((n, S, S), dtype=torch.uint8, device=dev)
+    chips, plane, valid = _chip_outputs(None, dev, (n, TC, S, S), torch.uint16)[:3]
     if n:
         # alive until the launch is queued; the copies are stream-ordered
         od = torch.from_numpy(o).to(dev)
@@ -1419,27 +1439,11 @@ def chip_warp(tile, fmask, src_crs, src_grid, dst_crs, dst_grids, S: int, T: int
                                   valid_bit, K)
     n, (TC, H, W), S = dg.shape[0], tile.shape, int(S)
     dev = tile.device
-    out = dict(out or {})
     if labels is not None and not torch.is_tensor(labels):
         labels = torch.from_numpy(np.ascontiguousarray(labels))
     if labels is not None:
         labels = labels.to(dev)
-    chips = out.pop("chips", None)
-    plane = out.pop("validity", None)
-    maps = out.pop("maps", None)
-    assert not out, f"unknown outputs {sorted(out)}"
-    chips = chips if chips is not None else torch.empty((n, TC, S, S), dtype=torch.int16, device=dev)
-    plane = plane if plane is not None else torch.empty((n, S, S), dtype=torch.uint8, device=dev)
-    assert chips.dtype == torch.int16 and tuple(chips.shape) == (n, TC, S, S) and plane.dtype == torch.uint8 and tuple(plane.shape) == (n, S, S)
-    valid = torch.zeros((n,), dtype=torch.int32, device=dev)
-    valid_labels = hist = None
-    if labels is not None:
-        maps = maps if maps is not None else torch.empty_like(labels)
-        assert maps.dtype == labels.dtype and tuple(maps.shape) == (n, S, S)
-        valid_labels = torch.zeros((n,), dtype=torch.int32, device=dev)
-        hist = torch.zeros((n, K), dtype=torch.int32, device=dev) if K else None
-    else:
-        maps = None
+    chips, plane, valid, maps, valid_labels, hist = _chip_outputs(out, dev, (n, TC, S, S), torch.int16, labels, K)
     if n:
         dbl = torch.from_numpy(np.concatenate([sc, sg, dc, dg.reshape(-1)])).to(dev)  # one upload; every slice 8-byte aligned
         lo, hi = (int(clip[0]), int(clip[1])) if clip is not None else (0, 0)
@@ -1476,27 +1480,11 @@ def s2_chip_warp(bands, starts, plane_class, class_grid, class_size, scl, scl_st
                                                    None if labels is None else tuple(labels.shape), lab_dtype, valid_bit, K)
     n, TC, G, S, T = dg.shape[0], st.shape[0], cg.shape[0], int(S), int(T)
     dev = bands.device
-    out = dict(out or {})
     if labels is not None and not torch.is_tensor(labels):
         labels = torch.from_numpy(np.ascontiguousarray(labels))
     if labels is not None:
         labels = labels.to(dev)
-    chips = out.pop("chips", None)
-    plane = out.pop("validity", None)
-    maps = out.pop("maps", None)
-    assert not out, f"unknown outputs {sorted(out)}"
-    chips = chips if chips is not None else torch.empty((n, TC, S, S), dtype=torch.uint16, device=dev)
-    plane = plane if plane is not None else torch.empty((n, S, S), dtype=torch.uint8, device=dev)
-    assert chips.dtype == torch.uint16 and tuple(chips.shape) == (n, TC, S, S) and plane.dtype == torch.uint8 and tuple(plane.shape) == (n, S, S)
-    valid = torch.zeros((n,), dtype=torch.int32, device=dev)
-    valid_labels = hist = None
-    if labels is not None:
-        maps = maps if maps is not None else torch.empty_like(labels)
-        assert maps.dtype == labels.dtype and tuple(maps.shape) == (n, S, S)
-        valid_labels = torch.zeros((n,), dtype=torch.int32, device=dev)
-        hist = torch.zeros((n, K), dtype=torch.int32, device=dev) if K else None
-    else:
-        maps = None
+    chips, plane, valid, maps, valid_labels, hist = _chip_outputs(out, dev, (n, TC, S, S), torch.uint16, labels, K)
     if n:
         # alive until the launch is queued; the copies are stream-ordered.  One upload of the doubles; every slice 8-byte aligned
         dbl = torch.from_numpy(np.concatenate([sc, dc, cg.reshape(-1), dg.reshape(-1)])).to(dev)
@@ -1531,14 +1519,7 @@ def s1_chip_cut(planes, starts, scene_crs, scene_grid, scene_size, date_scenes, 
                                                                             src_nodata, clip)
     n, N, S = o.shape[0], sg.shape[0], int(S)
     dev = planes.device
-    out = dict(out or {})
-    chips = out.pop("chips", None)
-    plane = out.pop("validity", None)
-    assert not out, f"unknown outputs {sorted(out)}"
-    chips = chips if chips is not None else torch.empty((n, T * C, S, S), dtype=torch.float32, device=dev)
-    plane = plane if plane is not None else torch.empty((n, S, S), dtype=torch.uint8, device=dev)
-    assert chips.dtype == torch.float32 and tuple(chips.shape) == (n, T * C, S, S) and plane.dtype == torch.uint8 and tuple(plane.shape) == (n, S, S)
-    valid = torch.zeros((n,), dtype=torch.int32, device=dev)
+    chips, plane, valid = _chip_outputs(out, dev, (n, T * C, S, S), torch.float32)[:3]
     if n:
         # alive until the launch is queued; the copies are stream-ordered.  One upload of the doubles; every slice 8-byte aligned
         dbl = torch.from_numpy(np.concatenate([dc, dg, sc.reshape(-1), sg.reshape(-1)])).to(dev)

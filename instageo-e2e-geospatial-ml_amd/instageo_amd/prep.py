@@ -1,12 +1,16 @@
 """The host layer shared by the dataset-preparation modes: what :mod:`instageo_amd.chips`, :mod:`instageo_amd.raster_chips`,
-:mod:`instageo_amd.clean` and :mod:`instageo_amd.polygon_labels` have in common around their kernels, each defined once.  A leaf module: it
-imports only :mod:`instageo_amd.tiff` and :mod:`instageo_amd.crs` at module level (``torch``, ``pandas`` and the config loader inside the
-functions that need them), so every mode, and :mod:`mosaic` / :mod:`cog` / :mod:`maptiles` / :mod:`warp`, can import it without a cycle.
+:mod:`instageo_amd.s2_chips`, :mod:`instageo_amd.s2_raster_chips`, :mod:`instageo_amd.s1_chips`, :mod:`instageo_amd.clean` and
+:mod:`instageo_amd.polygon_labels` have in common around their kernels, each defined once.  A leaf module: it imports only
+:mod:`instageo_amd.tiff` and :mod:`instageo_amd.crs` at module level (``torch``, ``pandas`` and the config loader inside the functions that
+need them), so every mode, and :mod:`mosaic` / :mod:`cog` / :mod:`maptiles` / :mod:`warp`, can import it without a cycle.
 
 Here belongs what is the same for every files-in / files-out mode: telling device tensors from host arrays and moving between them, HLS
-file names, reading a band stack, the dataset CSV, the georeferencing tags a written chip keeps, the class statistics and ``*_stats.json``,
-the checks common to the two cut entry points, the reader of one config section, and the command-line entry.  A mode's rule, its numpy
-twin, its record handling and its own "needs ..." checks stay in its module.
+file names, reading a band stack or packed planes, the dataset CSV, the georeferencing tags a written chip keeps, the class statistics and
+``*_stats.json``, the checks common to the cut entry points (the stack arguments, the origins), the reader of one config section, the
+tail of a chip creator's ``run_from_config`` and the command-line entry.  A mode's rule, its numpy twin and its own checks stay in its
+module.  The two pipelines the chip creators share sit on top of this layer, each in the module of its first mode:
+:func:`chips.create_from_points` (the point modes: HLS, Sentinel-2, Sentinel-1) and :func:`raster_chips.create_from_records` (the
+label-raster modes: HLS, Sentinel-2); a mode keeps its argument checks and its reading and makes one call of its driver.
 """
 from __future__ import annotations
 
@@ -201,6 +205,18 @@ def check_stack_args(tile_shape, fmask_shape, S: int, T: int, bits: int, strateg
     return TC, H, W
 
 
+def check_origins(origins, S: int, H: int, W: int, what: str) -> np.ndarray:
+    """ValueError unless ``origins`` are integers and every chip of side ``S`` at one of them lies wholly inside the ``H`` x ``W`` pixels of
+    ``what`` (``tile of`` | ``output grid of``) -> origins as an (n, 2) int32 array."""
+    o = np.asarray(origins)
+    if o.size and o.dtype.kind not in "iu":
+        raise ValueError("origins must be integers")
+    o = o.astype(np.int64).reshape(-1, 2)
+    if o.size and (o.min() < 0 or (o[:, 0] > H - S).any() or (o[:, 1] > W - S).any()):
+        raise ValueError(f"a chip of side {S} at one of the origins does not lie wholly inside the {what} {H} x {W} pixels")
+    return np.ascontiguousarray(o, dtype=np.int32)
+
+
 # ---- one config section ----------------------------------------------------------------------------------------------------------------------
 def none(v, also: Tuple[str, ...] = ()):
     """``v``, or None where it is unset: None, the string ``"None"`` (what an override ``key=None`` gives) or one of ``also``."""
@@ -286,7 +302,15 @@ class Section:
         return v
 
 
-# ---- the command line of a mode --------------------------------------------------------------------------------------------------------------
+# ---- the entry points of a mode --------------------------------------------------------------------------------------------------------------
+def run_creator(mode: str, create: Callable[..., Tuple[List[str], List[Optional[str]]]], kw: Dict[str, Any], device: Optional[str]) -> int:
+    """The tail of a chip-creation mode's ``run_from_config``: ``create(device=device, **kw)`` -> (chip names, label-map names), then one
+    JSON line with the counts under ``mode``."""
+    chips, segs = create(device=device, **kw)
+    print(json.dumps({mode: {"chips": len(chips), "seg_maps": sum(s is not None for s in segs), "output_directory": kw["output_directory"]}}))
+    return 0
+
+
 def run_mode_cli(mode: str, run_from_config: Callable[[Dict[str, Any], Optional[str]], int], argv: Optional[List[str]] = None) -> int:
     """``python -m instageo_amd.<module> key=value ...``: ``mode`` without ``run.py``, on the device when there is one."""
     import sys

@@ -29,7 +29,7 @@ from __future__ import annotations
 
 import json
 import os
-from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
+from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
@@ -45,7 +45,7 @@ SEG_NO_DATA = -1
 _BATCH_VALUES = 1 << 28  # chip values of one launch
 
 
-def _params(c) -> np.ndarray:
+def params(c) -> np.ndarray:
     """A coordinate system (EPSG code, :class:`crs.Crs` or five doubles) -> its five doubles."""
     if isinstance(c, (int, np.integer)) and not isinstance(c, bool):
         c = crsmod.from_epsg(int(c))
@@ -55,7 +55,7 @@ def _params(c) -> np.ndarray:
     return a
 
 
-def _grid_ok(g) -> bool:
+def grid_ok(g) -> bool:
     return bool(np.isfinite(g).all() and g[2] > 0 and g[3] > 0)
 
 
@@ -71,7 +71,7 @@ def check_warp(tile_shape, fmask_shape, src_crs, src_grid, dst_crs, dst_grids, S
     if H < 1 or W < 1 or H * W > 2**31 - 1:
         raise ValueError(f"a tile of {H} x {W} pixels is beyond 2^31 - 1 (source offsets are int32)")
     sg = np.ascontiguousarray(src_grid, dtype=np.float64).reshape(-1)
-    if sg.shape[0] != 4 or not _grid_ok(sg):
+    if sg.shape[0] != 4 or not grid_ok(sg):
         raise ValueError(f"src_grid = (X0, Y0, sx, sy) needs finite values and positive pixel sizes (got {tuple(sg)})")
     dg = np.ascontiguousarray(dst_grids, dtype=np.float64)
     if dg.size % 4:
@@ -94,7 +94,7 @@ def check_warp(tile_shape, fmask_shape, src_crs, src_grid, dst_crs, dst_grids, S
             raise ValueError(f"labels are int8 (seg) or float32 (reg) (got {labels_dtype})")
         if K and str(labels_dtype) != "int8":
             raise ValueError(f"a class histogram (K = {K}) needs int8 labels")
-    return _params(src_crs), sg, _params(dst_crs), dg
+    return params(src_crs), sg, params(dst_crs), dg
 
 
 # ---- the rule on host arrays ---------------------------------------------------------------------------------------------------------------
@@ -108,7 +108,7 @@ def _warp_host(tile, fmask, sc, sg, dc, dg, S, T, bits, strategy, nd, clip, labe
     for i in range(n):
         a = np.full((TC, S, S), nd, dtype=np.int16)
         f = np.zeros((T, S, S), dtype=np.uint8)
-        if _grid_ok(dg[i]):
+        if grid_ok(dg[i]):
             u, v = warp.coords(dc, dg[i], (S, S), sc, sg)
             with np.errstate(invalid="ignore"):
                 fc, fr = np.floor(u), np.floor(v)
@@ -227,7 +227,7 @@ def mgrs_of(first_tile_file: str) -> str:
     return prep.hls_name(first_tile_file).tile
 
 
-def _read_records(records) -> List[Dict[str, Any]]:
+def read_records(records) -> List[Dict[str, Any]]:
     import pandas as pd
 
     df = pd.read_csv(records, dtype={"mgrs_tile_id": str}) if isinstance(records, (str, os.PathLike)) else pd.DataFrame(records)
@@ -241,7 +241,7 @@ def _read_records(records) -> List[Dict[str, Any]]:
     return rows
 
 
-def _touches(dc, grid, S: int, sc, sg, H: int, W: int) -> bool:
+def touches(dc, grid, S: int, sc, sg, H: int, W: int) -> bool:
     """Whether the chip of ``grid`` can reach the tile: a 9 x 9 lattice over its extent, projected on the host; its box in source pixels,
     grown by one, against the tile.  A lattice wholly outside the domain cannot."""
     coarse = (grid[0], grid[1], grid[2] * S / 8.0, grid[3] * S / 8.0)
@@ -251,12 +251,110 @@ def _touches(dc, grid, S: int, sc, sg, H: int, W: int) -> bool:
     return bool(np.nanmax(u) + 1 >= 0 and np.nanmin(u) - 1 < W and np.nanmax(v) + 1 >= 0 and np.nanmin(v) - 1 < H)
 
 
-def _seg_labels(a: np.ndarray, name: str) -> np.ndarray:
+def seg_labels(a: np.ndarray, name: str) -> np.ndarray:
     if a.dtype.kind == "f":
         a = np.where(np.isnan(a), SEG_NO_DATA, a)
     if a.size and ((a != np.round(a)).any() or a.min() < -128 or a.max() > 127):
         raise ValueError(f"{name}: seg labels must be integers that fit int8")
     return a.astype(np.int8)
+
+
+def box_records(path: str, date: str, S: int, res: float) -> List[Dict[str, Any]]:
+    """The records of the bounding-box case: :func:`grid_polygons` of the JSON list of boxes in ``path``, none of them naming a tile."""
+    with open(path) as f:
+        rows = grid_polygons(json.load(f), date, S, res)
+    for r in rows:
+        r["mgrs_tile_id"] = None
+    return rows
+
+
+def create_from_records(rows: List[Dict[str, Any]], own_id: str, dst: crsmod.Crs, touches: Callable[[Tuple[float, float, float, float]], bool],
+                        labels_of: Optional[Callable[[np.ndarray, str], np.ndarray]], warp_cut_at: Callable[[List[Any], Any], Tuple],
+                        chip_values: int, chip_dtype, histogram: bool, stats_name: str, output_directory: str, chip_size: int,
+                        raster_path: Optional[str], spatial_resolution: float, snap: bool, qa_check: bool) -> Tuple[List[str], List[Optional[str]]]:
+    """The pipeline the label-raster modes share (:func:`create_raster_chips`, :func:`s2_raster_chips.create_s2_raster_chips`) from the
+    records on.  ``rows``: records of ``label_filename``, ``mgrs_tile_id`` (None: ``own_id``) and, in the bounding-box case, ``bounds``;
+    ``labels_of(array, path)``: a label raster as the kernel takes it, None in the bounding-box case (chips only, with the georeferencing
+    of their destination grid in ``dst``); ``touches(grid)``: whether a chip on that grid can reach the source; ``warp_cut_at(grids,
+    labels)``: the six results of a warped cut, called for at most ``_BATCH_VALUES // chip_values`` records at a time.  A record of another
+    tile is left alone, one whose files exist is skipped and still listed, a label raster that is not S x S or misses the source is not
+    cut; with ``qa_check`` a chip with ``valid_values == 0`` is dropped, then a pair with ``valid_labels == 0``; the label map is written
+    before its chip (as ``chip_dtype``).  Writes ``chips_dataset.csv`` and ``stats_name`` (with the class histogram when ``histogram``).
+    -> (chip names, label-map names)."""
+    S, res, bbox = int(chip_size), float(spatial_resolution), labels_of is None
+    reasons = ("other_tile", "existing", "invalid_shape", "outside_tile", "no_valid_values", "no_valid_labels")
+    stats: Dict[str, Any] = {"records": len(rows), "kept": 0, "dropped": {k: 0 for k in reasons}}
+    chip_dir, seg_dir = os.path.join(output_directory, "chips"), os.path.join(output_directory, "seg_maps")
+    os.makedirs(chip_dir, exist_ok=True)
+    if not bbox:
+        os.makedirs(seg_dir, exist_ok=True)
+    chips_out: List[str] = []
+    segs_out: List[Optional[str]] = []
+    todo: List[Dict[str, Any]] = []
+    for r in rows:
+        tid = r["mgrs_tile_id"] or own_id
+        if tid.lstrip("T") != own_id.lstrip("T"):
+            stats["dropped"]["other_tile"] += 1
+            continue
+        cname, lname = chip_names(r["label_filename"], tid)
+        have_chip = os.path.exists(os.path.join(chip_dir, cname))
+        if have_chip and (bbox or os.path.exists(os.path.join(seg_dir, lname))):
+            stats["dropped"]["existing"] += 1
+            chips_out.append(cname)
+            segs_out.append(None if bbox else lname)
+            continue
+        item: Dict[str, Any] = {"chip": cname, "label": lname}
+        if bbox:
+            b = r["bounds"]
+            g = item["grid"] = snapped_grid(b, res) if snap else (b[0], b[1] + S * res, res, res)
+            tags = dict(crsmod.geokeys(dst.epsg))
+            tags[33550] = (12, (g[2], g[3], 0.0))
+            tags[33922] = (12, (0.0, 0.0, 0.0, g[0], g[1], 0.0))
+            item["profile"] = {"tags": tags, "nodata": None}
+        else:
+            path = os.path.join(raster_path, r["label_filename"])
+            lab, lprof = tiff.read(path)
+            found = crsmod.from_profile(lprof)
+            if found.epsg != dst.epsg:
+                raise ValueError(f"{path}: the label raster is in EPSG:{found.epsg}, src_crs is EPSG:{dst.epsg}")
+            if lab.shape != (1, S, S):
+                stats["dropped"]["invalid_shape"] += 1
+                continue
+            own = warp.grid_of(lprof, path)
+            bounds = (own[0], own[1] - S * own[3], own[0] + S * own[2], own[1])
+            item["grid"] = snapped_grid(bounds, res) if snap else own
+            item["labels"] = labels_of(lab[0], path)
+            item["profile"] = {"tags": prep.geo_tags(lprof["tags"], tiepoint=True), "nodata": None}
+        if not touches(item["grid"]):
+            stats["dropped"]["outside_tile"] += 1
+            continue
+        todo.append(item)
+    hist_sum = np.zeros(MAX_CLASSES, dtype=np.int64) if histogram else None
+    step = max(1, _BATCH_VALUES // chip_values)
+    for first in range(0, len(todo), step):
+        part = todo[first : first + step]
+        out = warp_cut_at([it["grid"] for it in part], None if bbox else np.stack([it["labels"] for it in part]))
+        chips, valid_values, _, maps, valid_labels, hist = (None if o is None else to_host(o) for o in out)
+        for k, it in enumerate(part):
+            if qa_check and valid_values[k] == 0:
+                stats["dropped"]["no_valid_values"] += 1
+                continue
+            if qa_check and not bbox and valid_labels[k] == 0:
+                stats["dropped"]["no_valid_labels"] += 1
+                continue
+            if not bbox:
+                tiff.write(os.path.join(seg_dir, it["label"]), maps[k], it["profile"])
+                if hist_sum is not None:
+                    hist_sum += hist[k]
+            tiff.write(os.path.join(chip_dir, it["chip"]), chips[k].astype(chip_dtype), it["profile"])
+            chips_out.append(it["chip"])
+            segs_out.append(None if bbox else it["label"])
+            stats["kept"] += 1
+    prep.write_dataset_csv(output_directory, chips_out, segs_out, bbox)
+    if hist_sum is not None:
+        stats.update(prep.class_stats(hist_sum, trim=True))
+    prep.write_stats(os.path.join(output_directory, stats_name), stats)
+    return chips_out, segs_out
 
 
 def create_raster_chips(tile_files: Sequence[str], fmask_files: Optional[Sequence[str]], records, raster_path: Optional[str],
@@ -311,93 +409,24 @@ def create_raster_chips(tile_files: Sequence[str], fmask_files: Optional[Sequenc
     if bbox:
         if not bbox_feature_path:
             raise ValueError("is_bbox_feature needs bbox_feature_path")
-        with open(bbox_feature_path) as f:
-            rows = grid_polygons(json.load(f), date or prep.hls_date(tile_files[0]), S, res)
-        for r in rows:
-            r["mgrs_tile_id"] = None
+        rows = box_records(bbox_feature_path, date or prep.hls_date(tile_files[0]), S, res)
     else:
         if raster_path is None:
             raise ValueError("label records need raster_path")
-        rows = _read_records(records)
-    reasons = ("other_tile", "existing", "invalid_shape", "outside_tile", "no_valid_values", "no_valid_labels")
-    stats: Dict[str, Any] = {"records": len(rows), "kept": 0, "dropped": {k: 0 for k in reasons}}
-    chip_dir, seg_dir = os.path.join(output_directory, "chips"), os.path.join(output_directory, "seg_maps")
-    os.makedirs(chip_dir, exist_ok=True)
-    if not bbox:
-        os.makedirs(seg_dir, exist_ok=True)
-    chips_out: List[str] = []
-    segs_out: List[Optional[str]] = []
-    todo: List[Dict[str, Any]] = []
-    for r in rows:
-        tid = r["mgrs_tile_id"] or own_id
-        if tid.lstrip("T") != own_id.lstrip("T"):
-            stats["dropped"]["other_tile"] += 1
-            continue
-        cname, lname = chip_names(r["label_filename"], tid)
-        have_chip = os.path.exists(os.path.join(chip_dir, cname))
-        if have_chip and (bbox or os.path.exists(os.path.join(seg_dir, lname))):
-            stats["dropped"]["existing"] += 1
-            chips_out.append(cname)
-            segs_out.append(None if bbox else lname)
-            continue
-        item: Dict[str, Any] = {"chip": cname, "label": lname}
-        if bbox:
-            b = r["bounds"]
-            item["grid"] = snapped_grid(b, res) if snap else (b[0], b[1] + S * res, res, res)
-            g = item["grid"]
-            tags = dict(crsmod.geokeys(dst.epsg))
-            tags[33550] = (12, (g[2], g[3], 0.0))
-            tags[33922] = (12, (0.0, 0.0, 0.0, g[0], g[1], 0.0))
-            item["profile"] = {"tags": tags, "nodata": None}
-        else:
-            path = os.path.join(raster_path, r["label_filename"])
-            lab, lprof = tiff.read(path)
-            found = crsmod.from_profile(lprof)
-            if found.epsg != dst.epsg:
-                raise ValueError(f"{path}: the label raster is in EPSG:{found.epsg}, src_crs is EPSG:{dst.epsg}")
-            if lab.shape != (1, S, S):
-                stats["dropped"]["invalid_shape"] += 1
-                continue
-            own = warp.grid_of(lprof, path)
-            bounds = (own[0], own[1] - S * own[3], own[0] + S * own[2], own[1])
-            item["grid"] = snapped_grid(bounds, res) if snap else own
-            item["labels"] = _seg_labels(lab[0], path) if task_type == "seg" else lab[0].astype(np.float32)
-            item["profile"] = {"tags": prep.geo_tags(lprof["tags"], tiepoint=True), "nodata": None}
-        if not _touches(dst, item["grid"], S, src, sgrid, H, W):
-            stats["dropped"]["outside_tile"] += 1
-            continue
-        todo.append(item)
-    hist_sum = np.zeros(MAX_CLASSES, dtype=np.int64) if not bbox and task_type == "seg" else None
-    if todo:
-        t_dev, f_dev = prep.stage(tile, fmask, device)
-        step = max(1, _BATCH_VALUES // (tile.shape[0] * S * S))
-        for first in range(0, len(todo), step):
-            part = todo[first : first + step]
-            labels = None if bbox else np.stack([it["labels"] for it in part])
-            out = warp_cut(t_dev, f_dev, src, sgrid, dst, [it["grid"] for it in part], S, dates=T, mask=bits, strategy=masking_strategy,
-                           no_data_value=HLS_NO_DATA, clip=(0, 10000), labels=labels, label_strategy=masking_strategy if qa_check else None,
-                           num_classes=MAX_CLASSES if hist_sum is not None else 0)
-            chips, valid_values, _, maps, valid_labels, hist = (None if o is None else to_host(o) for o in out)
-            for k, it in enumerate(part):
-                if qa_check and valid_values[k] == 0:
-                    stats["dropped"]["no_valid_values"] += 1
-                    continue
-                if qa_check and not bbox and valid_labels[k] == 0:
-                    stats["dropped"]["no_valid_labels"] += 1
-                    continue
-                if not bbox:
-                    tiff.write(os.path.join(seg_dir, it["label"]), maps[k], it["profile"])
-                    if hist_sum is not None:
-                        hist_sum += hist[k]
-                tiff.write(os.path.join(chip_dir, it["chip"]), chips[k].astype(np.uint16), it["profile"])
-                chips_out.append(it["chip"])
-                segs_out.append(None if bbox else it["label"])
-                stats["kept"] += 1
-    prep.write_dataset_csv(output_directory, chips_out, segs_out, bbox)
-    if hist_sum is not None:
-        stats.update(prep.class_stats(hist_sum, trim=True))
-    prep.write_stats(os.path.join(output_directory, "raster_chips_stats.json"), stats)
-    return chips_out, segs_out
+        rows = read_records(records)
+    histogram = not bbox and task_type == "seg"
+    staged: List[Any] = []  # the stack and its Fmask where the cut runs, uploaded with the first batch
+
+    def warp_cut_at(grids, labels):
+        if not staged:
+            staged.extend(prep.stage(tile, fmask, device))
+        return warp_cut(staged[0], staged[1], src, sgrid, dst, grids, S, dates=T, mask=bits, strategy=masking_strategy, no_data_value=HLS_NO_DATA,
+                        clip=(0, 10000), labels=labels, label_strategy=masking_strategy if qa_check else None,
+                        num_classes=MAX_CLASSES if histogram else 0)
+
+    labels_of = None if bbox else seg_labels if task_type == "seg" else lambda a, path: a.astype(np.float32)
+    return create_from_records(rows, own_id, dst, lambda grid: touches(dst, grid, S, src, sgrid, H, W), labels_of, warp_cut_at, tile.shape[0] * S * S,
+                               np.uint16, histogram, "raster_chips_stats.json", output_directory, S, raster_path, res, snap, qa_check)
 
 
 # ---- mode=create_raster_chips --------------------------------------------------------------------------------------------------------------
@@ -436,11 +465,7 @@ def raster_chips_options(cfg: Dict[str, Any]) -> Dict[str, Any]:
 
 def run_from_config(cfg: Dict[str, Any], device: Optional[str] = None) -> int:
     """``mode=create_raster_chips``: :func:`create_raster_chips` under the ``raster_chips.*`` keys; prints one JSON line with the counts."""
-    kw = raster_chips_options(cfg)
-    chips, segs = create_raster_chips(device=device, **kw)
-    print(json.dumps({"create_raster_chips": {"chips": len(chips), "seg_maps": sum(s is not None for s in segs),
-                                              "output_directory": kw["output_directory"]}}))
-    return 0
+    return prep.run_creator("create_raster_chips", create_raster_chips, raster_chips_options(cfg), device)
 
 
 def main(argv: Optional[List[str]] = None) -> int:

@@ -23,7 +23,6 @@ rotated rasters, and a label-raster pipeline for Sentinel-1 (the reference has n
 """
 from __future__ import annotations
 
-import json
 import os
 import re
 from typing import Any, Dict, List, Optional, Sequence, Tuple
@@ -32,7 +31,7 @@ import numpy as np
 
 from . import chips as chipmod
 from . import crs as crsmod
-from . import prep, raster_chips, tiff, warp
+from . import prep, raster_chips, warp
 from .prep import MAX_DATES, STRATEGIES, is_device, to_host  # noqa: F401  (the masking strategies and the date limit of include/instageo_hip.h)
 
 NO_DATA_VALUE = -1.0  # the reference's NO_DATA_VALUES.S1, stackstac's fill_value
@@ -67,13 +66,13 @@ def check_cut(size: int, starts, scene_crs, scene_grid, scene_size, date_scenes,
     T, N = len(counts), sum(counts)
     if N > MAX_SCENES:
         raise ValueError(f"{N} scenes in all: at most {MAX_SCENES} go into one stack")
-    sc = np.stack([raster_chips._params(c) for c in scene_crs]).reshape(-1, 5) if len(scene_crs) else np.zeros((0, 5))
+    sc = np.stack([raster_chips.params(c) for c in scene_crs]).reshape(-1, 5) if len(scene_crs) else np.zeros((0, 5))
     sg = np.ascontiguousarray(scene_grid, dtype=np.float64)
     ss = np.asarray(scene_size)
     if sg.size != 4 * N or ss.size != 2 * N or sc.shape[0] != N or ss.size and ss.dtype.kind not in "iu":
         raise ValueError(f"{N} scenes need {N} coordinate systems, {N} grids (X0, Y0, sx, sy) and {N} integer sizes (H, W)")
     sg, ss = sg.reshape(N, 4), ss.astype(np.int64).reshape(N, 2)
-    if not all(raster_chips._grid_ok(g) for g in sg):
+    if not all(raster_chips.grid_ok(g) for g in sg):
         raise ValueError("a scene grid = (X0, Y0, sx, sy) needs finite values and positive pixel sizes")
     if (ss < 1).any() or (ss[:, 0] * ss[:, 1] > 2**31 - 1).any():
         raise ValueError("a scene has 1 <= H * W <= 2^31 - 1 pixels (source offsets are int32)")
@@ -115,7 +114,7 @@ def check_cut(size: int, starts, scene_crs, scene_grid, scene_size, date_scenes,
         first_bits |= 1 << at
         at += k
     return (st, np.ascontiguousarray(sc, dtype=np.float64), sg, np.ascontiguousarray(ss, dtype=np.int32), first_bits, T, C,
-            raster_chips._params(dst_crs), dg, np.ascontiguousarray(o, dtype=np.int32), nd, snd, clip)
+            raster_chips.params(dst_crs), dg, np.ascontiguousarray(o, dtype=np.int32), nd, snd, clip)
 
 
 # ---- the rule on host arrays ---------------------------------------------------------------------------------------------------------------
@@ -126,7 +125,7 @@ def _cut_host(planes, st, sc, sg, ss, first_bits, T, C, dc, dg, origins, S, nd, 
     n = origins.shape[0]
     chips = np.full((n, T * C, S, S), nd, dtype=np.float32)
     validity = np.empty((n, S, S), dtype=np.uint8)
-    usable = raster_chips._grid_ok(dg)
+    usable = raster_chips.grid_ok(dg)
     same = [tuple(sc[s]) == tuple(dc) for s in range(N)]
     step = np.arange(S, dtype=np.float64)
     for i, (r0, c0) in enumerate(origins.tolist()):
@@ -305,80 +304,12 @@ def create_s1_chips(scenes, points, output_directory: str, chip_size: int = 256,
     scene_crs = [crsmod.from_profile(p) for p, _ in scene_profiles]
     scene_grid = [warp.grid_of(p) for p, _ in scene_profiles]
     scene_size = [s for _, s in scene_profiles]
-    stats: Dict[str, Any] = {"nominated": 0, "kept": 0, "dropped": {"out_of_bounds": 0, "existing": 0, "no_valid_values": 0, "no_valid_labels": 0}}
-    bbox = points is None
-    if bbox:
-        chip_xy = np.array([(cx, cy) for cx in range(W // S) for cy in range(H // S)], dtype=np.int64).reshape(-1, 2)
-        date_id = date or stamp_date
-        ptr = pts = labels = None
-    else:
-        tab = chipmod._read_points(points)
-        keep, rows, cols, tx, ty = chipmod.locate_points(tab["x"], tab["y"], src_crs, profile, (H, W))
-        if keep.size == 0:
-            raise ValueError("no point lies inside the stack")
-        date_id = date or tab["date"].iloc[int(keep[0])].strftime("%Y%m%d")
-        labels = np.asarray(tab["label"])
-        chip_xy, beyond, ptr, pts = chipmod.group_points(rows, cols, tx, ty, keep, S, (H, W), grid)
-        stats["dropped"]["out_of_bounds"] = beyond
-        stats["nominated"] = beyond
-    stats["nominated"] += int(chip_xy.shape[0])
-    chip_dir, seg_dir = os.path.join(output_directory, "chips"), os.path.join(output_directory, "seg_maps")
-    os.makedirs(chip_dir, exist_ok=True)
-    if not bbox:
-        os.makedirs(seg_dir, exist_ok=True)
-    names = [(f"chip_{date_id}_{tile_id}_{x}_{y}.tif", f"seg_map_{date_id}_{tile_id}_{x}_{y}.tif") for x, y in chip_xy.tolist()]
-    fresh = np.array([not (os.path.exists(os.path.join(chip_dir, c)) or (not bbox and os.path.exists(os.path.join(seg_dir, s))))
-                      for c, s in names], dtype=bool)
-    stats["dropped"]["existing"] = int((~fresh).sum())
-    sel = np.nonzero(fresh)[0]
-    origins = np.stack((chip_xy[sel, 1] * S, chip_xy[sel, 0] * S), axis=-1).astype(np.int32).reshape(-1, 2)
-    chips_out: List[str] = []
-    segs_out: List[Optional[str]] = []
-    hist_sum = None
-    if sel.size:
-        p_dev = prep.to_device(planes, device)
-        chips, valid_values, validity = cut(p_dev, starts, scene_crs, scene_grid, scene_size, counts, system, grid, origins, S,
-                                            no_data_value=no_data_value, src_nodata=src_nodata, clip=clip)
-        valid_values = to_host(valid_values)
-        maps = valid_labels = hist = None
-        if not bbox:
-            # the lists of the chips that are cut: the rows of the fresh ones, re-based
-            cnt = np.diff(ptr)[sel]
-            take = np.concatenate([np.arange(ptr[i], ptr[i + 1]) for i in sel])
-            sub_ptr = np.concatenate([[0], np.cumsum(cnt)])
-            lab = labels.astype(np.float32) if task_type == "reg" else labels
-            K = int(num_classes) if num_classes is not None else 0
-            if task_type == "seg" and num_classes is None:
-                K = int(min(max(int(np.max(lab)) + 1, 1), chipmod.MAX_CLASSES)) if lab.size else 1
-            maps, valid_labels, hist = chipmod.label_maps(origins, S, sub_ptr, pts[take.astype(np.int64)], lab, window_size, validity,
-                                                          masking_strategy, task_type, K if task_type == "seg" else 0)
-            maps, valid_labels = to_host(maps), to_host(valid_labels)
-            if hist is not None:
-                hist_sum = np.zeros(K, dtype=np.int64)
-                hist = to_host(hist)
-        for k, i in enumerate(sel.tolist()):
-            if valid_values[k] == 0:  # the reference's "no valid data pixels"
-                stats["dropped"]["no_valid_values"] += 1
-                continue
-            if not bbox and valid_labels[k] == 0:  # "empty label"
-                stats["dropped"]["no_valid_labels"] += 1
-                continue
-            prof = chipmod._chip_profile(profile, grid, int(origins[k, 0]), int(origins[k, 1]))
-            if bbox:
-                segs_out.append(None)
-            else:
-                tiff.write(os.path.join(seg_dir, names[i][1]), maps[k], prof)
-                segs_out.append(names[i][1])
-                if hist_sum is not None:
-                    hist_sum += hist[k]
-            tiff.write(os.path.join(chip_dir, names[i][0]), to_host(chips[k]), prof)
-            chips_out.append(names[i][0])
-    stats["kept"] = len(chips_out)
-    prep.write_dataset_csv(output_directory, chips_out, segs_out, bbox)
-    if hist_sum is not None:
-        stats.update(prep.class_stats(hist_sum))
-    prep.write_stats(os.path.join(output_directory, "chips_stats.json"), stats)
-    return chips_out, segs_out
+    def cut_at(origins, bbox):
+        return cut(prep.to_device(planes, device), starts, scene_crs, scene_grid, scene_size, counts, system, grid, origins, S,
+                   no_data_value=no_data_value, src_nodata=src_nodata, clip=clip)
+
+    source = chipmod.PointSource(profile, grid, (H, W), tile_id, stamp_date, "stack", cut_at, None)
+    return chipmod.create_from_points(source, points, output_directory, S, window_size, task_type, src_crs, masking_strategy, num_classes, date)
 
 
 # ---- mode=create_s1_chips ------------------------------------------------------------------------------------------------------------------
@@ -427,11 +358,7 @@ def s1_chips_options(cfg: Dict[str, Any]) -> Dict[str, Any]:
 
 def run_from_config(cfg: Dict[str, Any], device: Optional[str] = None) -> int:
     """``mode=create_s1_chips``: :func:`create_s1_chips` under the ``s1_chips.*`` keys; prints one JSON line with the counts."""
-    kw = s1_chips_options(cfg)
-    chips, segs = create_s1_chips(device=device, **kw)
-    print(json.dumps({"create_s1_chips": {"chips": len(chips), "seg_maps": sum(s is not None for s in segs),
-                                          "output_directory": kw["output_directory"]}}))
-    return 0
+    return prep.run_creator("create_s1_chips", create_s1_chips, s1_chips_options(cfg), device)
 
 
 def main(argv: Optional[List[str]] = None) -> int:

@@ -26,21 +26,19 @@ float (``reg``) label maps in the files-to-files mode (the reference's S2 pipeli
 """
 from __future__ import annotations
 
-import json
 import os
 from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
 from . import crs as crsmod
-from . import prep, raster_chips, s2_chips, tiff, warp
+from . import prep, raster_chips, s2_chips, warp
 from .chips import VALID_BITS
 from .prep import MAX_DATES, STRATEGIES, is_device, to_host  # noqa: F401
 from .raster_chips import MAX_CLASSES, MAX_SIDE, SEG_NO_DATA
 from .s2_chips import NO_DATA_VALUE
 
 MAX_GEOMETRIES = 8  # geometry classes of one launch (include/instageo_hip.h)
-_BATCH_VALUES = 1 << 28  # chip values of one launch
 
 
 # ---- argument checks shared by the host path and ops.s2_chip_warp ----------------------------------------------------------------------------
@@ -77,7 +75,7 @@ def check_warp(band_size: int, starts, plane_class, class_grid, class_size, scl_
     G = cg.shape[0]
     if not 1 <= G <= MAX_GEOMETRIES or cs.shape[0] != G:
         raise ValueError(f"1 <= G <= {MAX_GEOMETRIES} geometry classes, one grid and one size each (got {G} grids, {cs.shape[0]} sizes)")
-    if not all(raster_chips._grid_ok(g) for g in cg):
+    if not all(raster_chips.grid_ok(g) for g in cg):
         raise ValueError("a class grid = (X0, Y0, sx, sy) needs finite values and positive pixel sizes")
     if (cs < 1).any() or (cs[:, 0] * cs[:, 1] > 2**31 - 1).any():
         raise ValueError("a geometry class has 1 <= H * W <= 2^31 - 1 pixels (source offsets are int32)")
@@ -131,8 +129,8 @@ def check_warp(band_size: int, starts, plane_class, class_grid, class_size, scl_
             raise ValueError(f"labels are int8 (seg) or float32 (reg) (got {labels_dtype})")
         if K and str(labels_dtype) != "int8":
             raise ValueError(f"a class histogram (K = {K}) needs int8 labels")
-    return (st, sst, np.ascontiguousarray(pc, dtype=np.int32), cg, np.ascontiguousarray(cs, dtype=np.int32), raster_chips._params(src_crs),
-            raster_chips._params(dst_crs), dg)
+    return (st, sst, np.ascontiguousarray(pc, dtype=np.int32), cg, np.ascontiguousarray(cs, dtype=np.int32), raster_chips.params(src_crs),
+            raster_chips.params(dst_crs), dg)
 
 
 # ---- the rule on host arrays ---------------------------------------------------------------------------------------------------------------
@@ -148,7 +146,7 @@ def _warp_host(bands, st, scl, sst, pc, cg, cs, sc, dc, dg, S, T, bits, strategy
         a = np.full((TC, S, S), nd, dtype=np.int32)
         read = np.zeros((TC, S, S), dtype=bool)
         f = np.zeros((T, S, S), dtype=np.uint8)
-        if raster_chips._grid_ok(dg[i]):
+        if raster_chips.grid_ok(dg[i]):
             X0, Y0, sx, sy = (float(v) for v in dg[i])
             x = X0 + (np.arange(S, dtype=np.float64) + 0.5) * sx
             y = Y0 - (np.arange(S, dtype=np.float64) + 0.5) * sy
@@ -309,97 +307,29 @@ def create_s2_raster_chips(band_files: Sequence[str], scl_files: Optional[Sequen
         plane_class = plane_class + scl_class
     class_grid = np.array([g for g, _ in classes], dtype=np.float64).reshape(-1, 4)
     class_size = np.array([s for _, s in classes], dtype=np.int32).reshape(-1, 2)
-    TC = len(band_files)
     bbox = bool(is_bbox_feature)
     if bbox:
         if not records or not isinstance(records, (str, os.PathLike)):
             raise ValueError("is_bbox_feature needs records: the path of a JSON list of boxes")
-        with open(records) as f:
-            rows = raster_chips.grid_polygons(json.load(f), stamp_date, S, res)
-        for r in rows:
-            r["mgrs_tile_id"] = None
+        rows = raster_chips.box_records(records, stamp_date, S, res)
     else:
         if raster_path is None or records is None:
             raise ValueError("label records need records and raster_path")
-        rows = raster_chips._read_records(records)
-    reasons = ("other_tile", "existing", "invalid_shape", "outside_tile", "no_valid_values", "no_valid_labels")
-    stats: Dict[str, Any] = {"records": len(rows), "kept": 0, "dropped": {k: 0 for k in reasons}}
-    chip_dir, seg_dir = os.path.join(output_directory, "chips"), os.path.join(output_directory, "seg_maps")
-    os.makedirs(chip_dir, exist_ok=True)
-    if not bbox:
-        os.makedirs(seg_dir, exist_ok=True)
-    chips_out: List[str] = []
-    segs_out: List[Optional[str]] = []
-    todo: List[Dict[str, Any]] = []
-    for r in rows:
-        tid = r["mgrs_tile_id"] or own_id
-        if tid.lstrip("T") != own_id.lstrip("T"):
-            stats["dropped"]["other_tile"] += 1
-            continue
-        cname, lname = raster_chips.chip_names(r["label_filename"], tid)
-        have_chip = os.path.exists(os.path.join(chip_dir, cname))
-        if have_chip and (bbox or os.path.exists(os.path.join(seg_dir, lname))):
-            stats["dropped"]["existing"] += 1
-            chips_out.append(cname)
-            segs_out.append(None if bbox else lname)
-            continue
-        item: Dict[str, Any] = {"chip": cname, "label": lname}
-        if bbox:
-            b = r["bounds"]
-            g = item["grid"] = raster_chips.snapped_grid(b, res) if snap else (b[0], b[1] + S * res, res, res)
-            tags = dict(crsmod.geokeys(dst.epsg))
-            tags[33550] = (12, (g[2], g[3], 0.0))
-            tags[33922] = (12, (0.0, 0.0, 0.0, g[0], g[1], 0.0))
-            item["profile"] = {"tags": tags, "nodata": None}
-        else:
-            path = os.path.join(raster_path, r["label_filename"])
-            lab, lprof = tiff.read(path)
-            found = crsmod.from_profile(lprof)
-            if found.epsg != dst.epsg:
-                raise ValueError(f"{path}: the label raster is in EPSG:{found.epsg}, src_crs is EPSG:{dst.epsg}")
-            if lab.shape != (1, S, S):
-                stats["dropped"]["invalid_shape"] += 1
-                continue
-            own = warp.grid_of(lprof, path)
-            bounds = (own[0], own[1] - S * own[3], own[0] + S * own[2], own[1])
-            item["grid"] = raster_chips.snapped_grid(bounds, res) if snap else own
-            item["labels"] = raster_chips._seg_labels(lab[0], path)
-            item["profile"] = {"tags": prep.geo_tags(lprof["tags"], tiepoint=True), "nodata": None}
-        if not any(raster_chips._touches(dst, item["grid"], S, src, g, H, W) for g, (H, W) in classes):
-            stats["dropped"]["outside_tile"] += 1
-            continue
-        todo.append(item)
-    hist_sum = None if bbox else np.zeros(MAX_CLASSES, dtype=np.int64)
-    if todo:
-        b_dev, s_dev = prep.stage(bands, scl, device)
-        bit = VALID_BITS[masking_strategy] if qa_check and not bbox else 0
-        step = max(1, _BATCH_VALUES // (TC * S * S))
-        for first in range(0, len(todo), step):
-            part = todo[first : first + step]
-            labels = None if bbox else np.stack([it["labels"] for it in part])
-            out = warp_cut(b_dev, starts, plane_class, class_grid, class_size, s_dev, scl_starts, src, dst, [it["grid"] for it in part], S,
-                           dates=T, class_bits=bits, strategy=masking_strategy, no_data_value=NO_DATA_VALUE, boa_offset=boa_offset,
-                           valid_range=valid_range, labels=labels, valid_bit=bit, classes=0 if bbox else MAX_CLASSES)
-            chips, valid_values, _, maps, valid_labels, hist = (None if o is None else to_host(o) for o in out)
-            for k, it in enumerate(part):
-                if qa_check and valid_values[k] == 0:
-                    stats["dropped"]["no_valid_values"] += 1
-                    continue
-                if qa_check and not bbox and valid_labels[k] == 0:
-                    stats["dropped"]["no_valid_labels"] += 1
-                    continue
-                if not bbox:
-                    tiff.write(os.path.join(seg_dir, it["label"]), maps[k], it["profile"])
-                    hist_sum += hist[k]
-                tiff.write(os.path.join(chip_dir, it["chip"]), chips[k], it["profile"])
-                chips_out.append(it["chip"])
-                segs_out.append(None if bbox else it["label"])
-                stats["kept"] += 1
-    prep.write_dataset_csv(output_directory, chips_out, segs_out, bbox)
-    if hist_sum is not None:
-        stats.update(prep.class_stats(hist_sum, trim=True))
-    prep.write_stats(os.path.join(output_directory, "s2_raster_chips_stats.json"), stats)
-    return chips_out, segs_out
+        rows = raster_chips.read_records(records)
+    staged: List[Any] = []  # the packed planes where the cut runs, uploaded with the first batch
+
+    def warp_cut_at(grids, labels):
+        if not staged:
+            staged.extend(prep.stage(bands, scl, device))
+        return warp_cut(staged[0], starts, plane_class, class_grid, class_size, staged[1], scl_starts, src, dst, grids, S, dates=T, class_bits=bits,
+                        strategy=masking_strategy, no_data_value=NO_DATA_VALUE, boa_offset=boa_offset, valid_range=valid_range, labels=labels,
+                        valid_bit=VALID_BITS[masking_strategy] if qa_check and not bbox else 0, classes=0 if bbox else MAX_CLASSES)
+
+    def touches(grid):
+        return any(raster_chips.touches(dst, grid, S, src, g, H, W) for g, (H, W) in classes)
+
+    return raster_chips.create_from_records(rows, own_id, dst, touches, None if bbox else raster_chips.seg_labels, warp_cut_at, len(band_files) * S * S,
+                                            np.uint16, not bbox, "s2_raster_chips_stats.json", output_directory, S, raster_path, res, snap, qa_check)
 
 
 # ---- mode=create_s2_raster_chips -------------------------------------------------------------------------------------------------------------
@@ -451,11 +381,7 @@ def s2_raster_chips_options(cfg: Dict[str, Any]) -> Dict[str, Any]:
 def run_from_config(cfg: Dict[str, Any], device: Optional[str] = None) -> int:
     """``mode=create_s2_raster_chips``: :func:`create_s2_raster_chips` under the ``s2_raster_chips.*`` keys; prints one JSON line with the
     counts."""
-    kw = s2_raster_chips_options(cfg)
-    chips, segs = create_s2_raster_chips(device=device, **kw)
-    print(json.dumps({"create_s2_raster_chips": {"chips": len(chips), "seg_maps": sum(s is not None for s in segs),
-                                                 "output_directory": kw["output_directory"]}}))
-    return 0
+    return prep.run_creator("create_s2_raster_chips", create_s2_raster_chips, s2_raster_chips_options(cfg), device)
 
 
 def main(argv: Optional[List[str]] = None) -> int:
