@@ -820,6 +820,52 @@ int ig_s1_chip_cut(const float* planes, const long long* starts, const double* s
                    int N, unsigned first_bits, const double* dst_crs, const double* dst_grid, const int* origins, int n, int T, int C, int S,
                    float no_data, int has_src_nodata, float src_nodata, int clip, float clip_lo, float clip_hi, float* chips,
                    int* valid_values, unsigned char* validity, void* stream);
+/* Cloud-free temporal composites of HLS scenes (composite.hip; not in the reference, whose add_hls_stac_items takes the single least
+ * cloudy granule near a step's date and loses what Fmask flags in it).  THE RULE:
+ * Inputs.  N scenes of one MGRS tile on ONE grid of H x W pixels (the host checks size, tiepoint, pixel scale and GeoKeys).  Scene n has C
+ *   int16 band planes and one uint8 Fmask plane, each row-major and whole, packed in the one int16 buffer `bands` and the one uint8 buffer
+ *   `fmasks`: band c of scene n at the int64 element offset starts[n C + c], its Fmask at fmask_starts[n]; both tables ON THE DEVICE, as
+ *   ig_warp and ig_s2_chip_cut pack theirs.  fmasks NULL (then fmask_starts NULL): no scene has an Fmask.  The scenes are grouped into T
+ *   temporal steps: step_ptr, T + 1 ascending int32 values from 0 to N ON THE DEVICE, lists the CANDIDATES of step t as the scenes
+ *   step_ptr[t] .. step_ptr[t + 1] - 1, in the order the host gives them; a step has 0 <= m <= 16 candidates, T <= 32.  max_m is the
+ *   largest m, which the caller states (the table is on the device): it sizes the kernel's registers and sorting network.
+ * Clear observations.  Candidate n is CLEAR at a pixel when fmask_n & mask_bits == 0 and every one of its C values differs from no_data.
+ *   mask_bits has the bit positions of ig_chip_cut (cloud 1, near_cloud_or_shadow 2, cloud_shadow 3, water 5); an Fmask of 255 (fill) is
+ *   masked by any non-zero mask_bits.
+ * Count.  count is the number of clear candidates at the pixel.  A pixel with count < min_clear (min_clear >= 1) gets no_data in all C
+ *   bands and source = 255.  Otherwise, by method:
+ *   0 NEAREST: the first clear candidate in list order gives all C values; its position in the step's list goes to source.  The host
+ *     orders candidates by |acquisition date - the step's target date|, the earlier date on a tie, so this is the nearest clear date: the
+ *     rule ig_s1_chip_cut has for orbit slices.
+ *   1 MEDIAN: per band the LOWER MEDIAN of the clear values, the floor((count - 1) / 2)-th smallest, 0-based: an observed value, nothing
+ *     is rounded.  source = 255.
+ *   2 MEDOID: with med_c the MEDIAN of band c, the clear candidate with the smallest sum over c of |v_{n,c} - med_c| gives all C values,
+ *     so the output is a spectrum that was observed; the EARLIEST IN LIST ORDER wins a tie.  The differences are formed in 32 bits and the
+ *     sum is exact in int32 (C <= 32767).  The candidate's position goes to source.
+ * Outputs.  composite (T, C, H, W) int16, count (T, H, W) uint8, source (T, H, W) uint8; hist (T, 17) int32 += the number of pixels of
+ *   step t per count value 0 .. 16 (the caller zeroes it).  Every output pixel is WRITTEN EXACTLY ONCE.  A step with m = 0 writes no_data,
+ *   count 0 and source 255 everywhere.  All results are integers or copies, and unique: the same bits for any launch geometry, run after
+ *   run.
+ * ig_composite: a streaming read bound by HBM, m (2 C + 1) bytes in and 2 C + 2 bytes out per pixel, all T steps in one launch.  Every
+ *   plane is a whole grid, so pixels are taken in plane order (the row pitch never enters); one workgroup of 256 threads owns 512
+ *   consecutive pixels of one step, a thread two of them, kept as the two 16-bit halves of one register.  The access width is chosen per
+ *   plane from its address (4 bytes, or 2 + 2 for a plane that starts at an odd element); the workgroup at the end of a plane goes element
+ *   by element.  For C in {1, 2, 3, 4, 6} every value is read ONCE and stays in registers: first the clear masks, then band by band the
+ *   keys (a candidate that is not clear becomes 32767, which sorts behind every clear value and equals what it may tie with) go through
+ *   Batcher's odd-even merge network on packed 16-bit minima and maxima (63 comparators at 16 keys, both pixels per instruction); MEDOID
+ *   accumulates the distances while the band is in registers and copies the winner out of them.  For any other C the register file cannot
+ *   hold the stack: the no_data test takes a pass of its own, the bands are read again and the winner's values a third time.  hist is
+ *   tallied in LDS and added with at most 17 integer atomics per workgroup; no workgroup waits on another.
+ *   Refused before any launch: T > 32, max_m > 16 (a step with more candidates), N > T * max_m, C outside [1, 32767], no_data outside
+ *   int16, mask_bits outside a byte, min_clear outside [1, 16], a method outside 0..2, H * W > 2^31 - 1, T * C * H * W >= 2^40, null
+ *   pointers, bands / composite not 2-byte, step_ptr / hist not 4-byte, starts / fmask_starts not 8-byte aligned.  H * W = 0 or T = 0
+ *   returns IG_OK without touching a pointer.  The tables are on the device, so ops.composite checks them on the host before the upload
+ *   (every plane inside its buffer, step_ptr ascending, m <= max_m); the kernel is the second fence: a step whose bounds break
+ *   0 <= step_ptr[t] <= step_ptr[t + 1] <= N has no candidates and one longer than max_m is cut.  The caller guarantees that
+ *   starts[k] + H * W and fmask_starts[n] + H * W lie inside the buffers. */
+int ig_composite(const short* bands, const long long* starts, const unsigned char* fmasks, const long long* fmask_starts,
+                 const int* step_ptr, int T, int N, int max_m, int C, int H, int W, int mask_bits, int no_data, int min_clear, int method,
+                 short* composite, unsigned char* count, unsigned char* source, int* hist, void* stream);
 /* Web Mercator map tiles rendered from an overview pyramid (maptiles.hip; the reference's new_apps/backend/app/tiler_service.py answers
  * tiles/WebMercatorQuad/{z}/{x}/{y}@1x.png through TiTiler: a warp into EPSG:3857, an overview level, nearest sampling and a colormap or
  * rescale per request).  THE RULE:

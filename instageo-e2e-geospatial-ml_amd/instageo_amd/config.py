@@ -151,6 +151,16 @@ DEFAULTS: Dict[str, Any] = {'root_dir': None,
  's1_chips': {'scenes': None, 'records_file': None, 'output_directory': None, 'chip_size': 256, 'bands': ['vv', 'vh'],
               'masking_strategy': 'each', 'window_size': 0, 'task_type': 'seg', 'src_crs': 4326, 'epsg': None, 'spatial_resolution': 10,
               'no_data_value': -1, 'src_nodata': None, 'clip': None},
+ # mode=create_composite (not in the reference, which takes one scene per temporal step; composite.py): scenes = the HLS band files of one
+ # MGRS tile as a list of steps, each a list of scenes, each a list of one file per band ([[[a_B02.tif, a_B03.tif], [b_B02.tif, b_B03.tif]]]);
+ # fmasks = the same nesting without the band level, one Fmask file per scene (None: only no_data decides what is clear); dates = one target
+ # date per step, the candidates are tried by distance from it (None: the date of the step's first scene, list order kept); method = nearest
+ # (the nearest clear date), median (per band the lower median of the clear values) or medoid (the clear scene closest to the median
+ # spectrum); mask_types = the Fmask types that make an observation not clear; a pixel with fewer than min_clear clear observations gets
+ # no_data; device: None = the device when there is one, host, cuda
+ 'composite': {'scenes': None, 'fmasks': None, 'dates': None, 'method': 'medoid',
+               'mask_types': ['cloud', 'near_cloud_or_shadow', 'cloud_shadow'], 'min_clear': 1, 'no_data': -9999, 'output_directory': None,
+               'device': None},
  # mode=clean_chips (the reference's instageo/data/data_cleaner.py under its flag names; clean.py): drop the chips of chips_dataset_csv
  # whose share of no-data pixels is above the threshold, buffer the observation pixels of the label maps by window_size (or limit the maps
  # to the pixels of observation_points_csv), write output_chips_dataset_csv and clean_stats.json.  Not in the reference: num_classes

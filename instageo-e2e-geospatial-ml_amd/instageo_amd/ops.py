@@ -1534,6 +1534,37 @@ def s1_chip_cut(planes, starts, scene_crs, scene_grid, scene_size, date_scenes, 
     return chips, valid, plane
 
 
+def composite(bands, starts, fmasks, fmask_starts, step_ptr, C: int, shape: Tuple[int, int], mask_bits: int = 0, no_data_value: int = -9999,
+              min_clear: int = 1, method: str = "medoid"):
+    """``ig_composite`` (include/instageo_hip.h): ``bands`` the packed int16 planes and ``fmasks`` the packed uint8 Fmask planes (or None)
+    as 1-D tensors on the device; ``starts`` (N * C,), ``fmask_starts`` (N,) and ``step_ptr`` (T + 1,) as host arrays: they are checked
+    here (every plane of ``shape`` = (H, W) inside its buffer, step_ptr ascending from 0, at most 16 candidates per step) and uploaded.
+    -> (composite (T, C, H, W) int16, count (T, H, W) uint8, source (T, H, W) uint8, hist (T, 17) int32)."""
+    import numpy as np
+
+    from . import composite as K
+
+    assert bands.dtype == torch.int16 and bands.dim() == 1, "the band planes are one packed 1-D int16 buffer"
+    assert fmasks is None or (fmasks.dtype == torch.uint8 and fmasks.dim() == 1), "the Fmask planes are one packed 1-D uint8 buffer"
+    st, fst, ptr, T, N, max_m, H, W = K.check_composite(int(bands.shape[0]), starts, None if fmasks is None else int(fmasks.shape[0]), fmask_starts,
+                                                        step_ptr, C, shape, mask_bits, no_data_value, min_clear, method)
+    C, dev = int(C), bands.device
+    comp = torch.empty((T, C, H, W), dtype=torch.int16, device=dev)
+    count = torch.empty((T, H, W), dtype=torch.uint8, device=dev)
+    source = torch.empty((T, H, W), dtype=torch.uint8, device=dev)
+    hist = torch.zeros((T, K.CELLS), dtype=torch.int32, device=dev)
+    if T and H * W:
+        # alive until the launch is queued; the copies are stream-ordered.  One upload of the offsets; both slices 8-byte aligned
+        tab = torch.from_numpy(np.concatenate([st, fst] if fst is not None else [st])).to(dev)
+        pd = torch.from_numpy(ptr).to(dev)
+        # HBM bytes: every value and Fmask byte of every candidate read once, the composites, counts and sources written
+        work = float(H * W) * (N * (2 * C + 1 if fst is not None else 2 * C) + T * (2 * C + 2))
+        _call("ig_composite", work, _p(bands) if N else None, _p(tab[: N * C]) if N else None, _p(fmasks) if fst is not None and N else None,
+              _p(tab[N * C :]) if fst is not None and N else None, _p(pd), T, N, max_m, C, H, W, int(mask_bits), int(no_data_value), int(min_clear),
+              K.METHODS[method], _p(comp), _p(count), _p(source), _p(hist), _stream())
+    return comp, count, source, hist
+
+
 TILE_STYLES ={"palette": 0, "ramp": 1, "rgb": 2}  # include/instageo_hip.h
 TILE_MAX_LEVELS = 13
 

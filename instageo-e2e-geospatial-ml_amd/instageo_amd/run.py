@@ -16,7 +16,9 @@ resampled onto the grids of label rasters, the reference's ``raster_chip_creator
 reference's ``S2RasterPipeline``, :mod:`instageo_amd.s2_raster_chips`), ``clean_chips``
 (``clean.*``: the reference's ``data_cleaner.py``: the no-data chip filter and label buffering / limiting, :mod:`instageo_amd.clean`) and
 ``create_polygon_labels`` (``polygon_labels.*``: a GeoJSON of polygons burned into the label rasters and the records table that
-``create_raster_chips`` takes, :mod:`instageo_amd.polygon_labels`) build no model.  Hydra, Lightning and Neptune are replaced by :mod:`instageo_amd.config` and the explicit loop below, which logs the
+``create_raster_chips`` takes, :mod:`instageo_amd.polygon_labels`) build no model; neither does ``create_composite`` (``composite.*``: the
+HLS scenes near each temporal step's date become one cloud-free composite scene per step, nearest clear date, median or medoid, written
+under HLS-style names that ``chips.tiles`` takes with ``fmasks=None``, :mod:`instageo_amd.composite`).  Hydra, Lightning and Neptune are replaced by :mod:`instageo_amd.config` and the explicit loop below, which logs the
 same metric names and writes ``instageo_best_checkpoint.ckpt`` (``{"state_dict": ...}``) on the best
 ``val_IoU`` (pipeline_utils.py:347-355).  Data: ``*_filepath`` may be ``synthetic:<n>`` (on-device HLS-shaped
 chips), an ``.npz`` with ``chips (N,T*C,H,W)`` and ``labels (N,H,W)``, or the reference's own CSV of chip / label GeoTIFF paths
@@ -52,6 +54,7 @@ PREP_MODES = {"create_chips": "chips",  # HLS tiles + points -> chips, label map
               "create_raster_chips": "raster_chips",  # HLS tiles + label rasters -> chips on the labels' grids
               "create_s2_raster_chips": "s2_raster_chips",  # Sentinel-2 band planes + label rasters -> chips on the labels' grids
               "create_s1_chips": "s1_chips",  # Sentinel-1 RTC scenes stacked per date + points -> float32 chips, label maps, the dataset CSV
+              "create_composite": "composite",  # the HLS scenes near each step's date -> one cloud-free composite scene per step
               "clean_chips": "clean",  # drop no-data chips, buffer / limit the label maps of a chip dataset
               "create_polygon_labels": "polygon_labels"}  # a GeoJSON of polygons -> label rasters + records.csv
 
