@@ -1,6 +1,6 @@
-// The last phase shared by the kernels that warp chips onto label grids (raster_chips.hip, s2_raster_chips.hip): the validity byte and the
-// label pixel of a thread's ROWS pixels, then the tallies, as the rule of include/instageo_hip.h states them.  Both files include this
-// text, so both evaluate the same epilogue.
+// The last phase shared by the column kernels (raster_chips.hip, s2_raster_chips.hip, and s1_chips.hip without labels; they include it
+// through chip_kernels.h): the validity byte and the label pixel of a thread's ROWS pixels, then the tallies, as the rule of
+// include/instageo_hip.h states them.  All three files include this text, so all evaluate the same epilogue.
 #pragma once
 #include "common.h"
 #include "pixel_seg.h"

@@ -16,13 +16,12 @@
 // Out-of-range accesses are impossible: a chip whose origin does not leave it wholly inside the tile is skipped by its workgroups (the
 // host checks origins before they are uploaded, this is the second fence), every pixel access is guarded by row < S and column < S, a
 // point outside its chip or with an index outside [0, P) paints nothing, and a label outside [0, K) is not counted.
+#include "chip_kernels.h"
 #include "common.h"
-#include "pixel_seg.h"
 
 namespace {
 
 constexpr int CB_H = 16, CB_W = 128, CSEG = 8, CTPB = 256;  // block rows, block columns, pixels per thread, threads
-constexpr int MAX_T = 32;                                   // dates: one bit each in the per-pixel date mask
 constexpr int LB = 64, LTPB = 256, MAX_K = 256;             // label block side, threads, histogram cells
 constexpr int MAX_W = 1 << 20;
 
@@ -62,10 +61,7 @@ __global__ __launch_bounds__(CTPB) void chip_cut_kernel(const short* __restrict_
 #pragma unroll
                 for (int j = 0; j < CSEG; ++j) dm[j] |= (f[j] & a.mask_bits) ? 1u << t : 0u;
             }
-            if (a.any) {
-#pragma unroll
-                for (int j = 0; j < CSEG; ++j) dm[j] = dm[j] ? 0xffffffffu : 0u;
-            }
+            if (a.any) any_date(dm);
         }
         unsigned all = 0xffu, some = 0u;  // bit j: all / at least one of the pixel's values differ from no_data
         const short nd = (short)a.no_data, lo = (short)a.lo, hi = (short)a.hi;
@@ -175,32 +171,22 @@ __global__ __launch_bounds__(LTPB) void chip_labels_kernel(const int* __restrict
     }
 }
 
-constexpr long LIM40 = 1L << 40;
-
 }  // namespace
 
 extern "C" int ig_chip_cut(const short* tile, const unsigned char* fmask, const int* origins, int n, int T, int C, int H, int W, int S,
                            int mask_bits, int strategy, int no_data, int clip, int clip_lo, int clip_hi, short* chips, int* valid_values,
                            unsigned char* validity, void* stream) {
-    IG_REQUIRE(n >= 0, "ig_chip_cut: need n >= 0 (got %d)", n);
-    IG_REQUIRE(T >= 1 && T <= MAX_T, "ig_chip_cut: 1 <= T <= %d dates (got %d)", MAX_T, T);
-    IG_REQUIRE(C >= 1, "ig_chip_cut: need C >= 1 bands per date (got %d)", C);
+    CHIP_CHECK(chip_check_stack("ig_chip_cut", n, T, C));
     IG_REQUIRE(H >= 1 && W >= 1, "ig_chip_cut: need H >= 1 and W >= 1 (H %d, W %d)", H, W);
     IG_REQUIRE(S >= 1, "ig_chip_cut: need a chip side S >= 1 (got %d)", S);
     IG_REQUIRE(S <= H && S <= W, "ig_chip_cut: a chip of side S = %d does not fit a tile of %d x %d pixels", S, H, W);
-    IG_REQUIRE(mask_bits >= 0 && mask_bits <= 255, "ig_chip_cut: mask_bits must be a byte (got %d)", mask_bits);
-    IG_REQUIRE(strategy == 0 || strategy == 1, "ig_chip_cut: strategy must be 0 each or 1 any (got %d)", strategy);
-    IG_REQUIRE(no_data >= -32768 && no_data <= 32767, "ig_chip_cut: no_data must fit int16 (got %d)", no_data);
-    IG_REQUIRE(clip == 0 || clip == 1, "ig_chip_cut: clip must be 0 or 1 (got %d)", clip);
-    IG_REQUIRE(!clip || (clip_lo >= -32768 && clip_hi <= 32767 && clip_lo <= clip_hi),
-               "ig_chip_cut: the clip range must fit int16 with clip_lo <= clip_hi (got %d, %d)", clip_lo, clip_hi);
+    CHIP_CHECK(chip_check_hls_rule("ig_chip_cut", mask_bits, strategy, no_data, clip, clip_lo, clip_hi));
     const long TC = (long)T * C;
-    IG_REQUIRE(TC * H * W < LIM40, "ig_chip_cut: T * C * H * W = %ld values exceeds 2^40", TC * H * W);
-    IG_REQUIRE(TC * S * S <= 0x7fffffffL, "ig_chip_cut: T * C * S * S = %ld values per chip exceeds 2^31 - 1 (valid_values is int32)", TC * S * S);
+    IG_REQUIRE(TC * H * W < CHIP_LIM40, "ig_chip_cut: T * C * H * W = %ld values exceeds 2^40", TC * H * W);
+    CHIP_CHECK(chip_check_values("ig_chip_cut", TC, S));
     if (n == 0) return IG_OK;
-    IG_REQUIRE(TC * S * S < LIM40 / n, "ig_chip_cut: n * T * C * S * S exceeds 2^40 values (n %d, S %d)", n, S);
     const int bx = ig_cdiv(S, CB_W), by = ig_cdiv(S, CB_H);
-    IG_REQUIRE((long)bx * by * n <= 0x7fffffffL, "ig_chip_cut: %ld workgroups exceed 2^31 - 1 (n %d, S %d)", (long)bx * by * n, n, S);
+    CHIP_CHECK(chip_check_launch("ig_chip_cut", n, TC, S, (long)bx * by));
     IG_REQUIRE(tile && origins && chips && valid_values, "ig_chip_cut: null pointer");
     IG_REQUIRE((((uintptr_t)tile | (uintptr_t)chips) & 1) == 0 && (((uintptr_t)origins | (uintptr_t)valid_values) & 3) == 0,
                "ig_chip_cut: tile and chips must be 2-byte, origins and valid_values 4-byte aligned");
@@ -225,7 +211,7 @@ extern "C" int ig_chip_labels(const int* origins, int n, int S, const int* ptr, 
     if (n == 0) return IG_OK;
     const int nb = ig_cdiv(S, LB);
     IG_REQUIRE((long)nb * nb * n <= 0x7fffffffL, "ig_chip_labels: %ld workgroups exceed 2^31 - 1 (n %d, S %d)", (long)nb * nb * n, n, S);
-    IG_REQUIRE((long)S * S < LIM40 / n, "ig_chip_labels: n * S * S exceeds 2^40 pixels (n %d, S %d)", n, S);
+    IG_REQUIRE((long)S * S < CHIP_LIM40 / n, "ig_chip_labels: n * S * S exceeds 2^40 pixels (n %d, S %d)", n, S);
     IG_REQUIRE(origins && ptr && maps && valid_labels, "ig_chip_labels: null pointer");
     IG_REQUIRE(P == 0 || (pts && labels), "ig_chip_labels: null pointer (pts, labels)");
     IG_REQUIRE(K == 0 || hist, "ig_chip_labels: null pointer (hist)");

@@ -56,14 +56,7 @@ __global__ __launch_bounds__(NTPB) void chip_nodata_kernel(const unsigned short*
         unsigned char m[NSEG];
 #pragma unroll
         for (int j = 0; j < NSEG; ++j) m[j] = (unsigned char)((any >> j & 1u) | (all >> j & 1u) << 1);
-        unsigned char* q = plane + (long)chip * HW + p0;
-        if (whole) {
-            store_seg<NSEG>(q, m);
-        } else {
-#pragma unroll
-            for (int j = 0; j < NSEG; ++j)
-                if (j < npx) q[j] = m[j];
-        }
+        store_run<NSEG>(plane + (long)chip * HW + p0, whole, npx, m);
     }
     const int n_any = block_sum_int(__popc(any), part_any), n_all = block_sum_int(__popc(all), part_all);
     if (threadIdx.x == 0) {

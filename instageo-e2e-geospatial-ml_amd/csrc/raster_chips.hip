@@ -15,16 +15,14 @@
 // Out-of-range accesses are impossible: a source offset is formed only after 0 <= floor(v) < H and 0 <= floor(u) < W held on the float64
 // values (NaN fails), H * W <= 2^31 - 1 is checked by the entry point, a grid that is not finite and positive yields no offset at all, and
 // every store and every label load is guarded by row < S and column < S of a chip index below n.
-#include "chip_epilogue.h"
+#include "chip_kernels.h"
 #include "common.h"
-#include "pixel_seg.h"
 #include "warp_proj.h"
 
 namespace {
 
 constexpr int RB = 64, RTPB = 256, RROWS = RB / 4;  // block side, threads, rows per thread
-constexpr int RMAX_T = 32, RMAX_K = EPI_MAX_K, RMAX_S = 1 << 15;
-constexpr long RLIM40 = 1L << 40;
+constexpr int RMAX_K = EPI_MAX_K;
 
 struct WarpCutArgs {
     int T, C, H, W, S, mask_bits, any, no_data, clip, lo, hi, nb, valid_bit, K;
@@ -137,28 +135,17 @@ extern "C" int ig_chip_warp(const short* tile, const unsigned char* fmask, const
                             int strategy, int no_data, int clip, int clip_lo, int clip_hi, const void* labels, int elem_size, int valid_bit,
                             int K, short* chips, int* valid_values, unsigned char* validity, void* maps, int* valid_labels, int* hist,
                             void* stream) {
-    IG_REQUIRE(n >= 0, "ig_chip_warp: need n >= 0 (got %d)", n);
-    IG_REQUIRE(T >= 1 && T <= RMAX_T, "ig_chip_warp: 1 <= T <= %d dates (got %d)", RMAX_T, T);
-    IG_REQUIRE(C >= 1, "ig_chip_warp: need C >= 1 bands per date (got %d)", C);
+    CHIP_CHECK(chip_check_stack("ig_chip_warp", n, T, C));
     IG_REQUIRE(H >= 1 && W >= 1, "ig_chip_warp: need H >= 1 and W >= 1 (H %d, W %d)", H, W);
     IG_REQUIRE((long)H * W <= 0x7fffffffL, "ig_chip_warp: H * W = %ld exceeds 2^31 - 1 (source offsets are int32)", (long)H * W);
-    IG_REQUIRE(S >= 1 && S <= RMAX_S, "ig_chip_warp: need a chip side 1 <= S <= 2^15 (got %d)", S);
-    IG_REQUIRE(mask_bits >= 0 && mask_bits <= 255, "ig_chip_warp: mask_bits must be a byte (got %d)", mask_bits);
-    IG_REQUIRE(strategy == 0 || strategy == 1, "ig_chip_warp: strategy must be 0 each or 1 any (got %d)", strategy);
-    IG_REQUIRE(no_data >= -32768 && no_data <= 32767, "ig_chip_warp: no_data must fit int16 (got %d)", no_data);
-    IG_REQUIRE(clip == 0 || clip == 1, "ig_chip_warp: clip must be 0 or 1 (got %d)", clip);
-    IG_REQUIRE(!clip || (clip_lo >= -32768 && clip_hi <= 32767 && clip_lo <= clip_hi),
-               "ig_chip_warp: the clip range must fit int16 with clip_lo <= clip_hi (got %d, %d)", clip_lo, clip_hi);
-    IG_REQUIRE(elem_size == 1 || elem_size == 4, "ig_chip_warp: elem_size must be 1 (int8) or 4 (float32) (got %d)", elem_size);
-    IG_REQUIRE(valid_bit >= 0 && valid_bit <= 2, "ig_chip_warp: valid_bit must be 0 none, 1 any or 2 each (got %d)", valid_bit);
-    IG_REQUIRE(K >= 0 && K <= RMAX_K, "ig_chip_warp: need 0 <= K <= %d histogram cells (got %d)", RMAX_K, K);
-    IG_REQUIRE(K == 0 || elem_size == 1, "ig_chip_warp: a class histogram (K = %d) needs int8 labels", K);
+    CHIP_CHECK(chip_check_side("ig_chip_warp", S));
+    CHIP_CHECK(chip_check_hls_rule("ig_chip_warp", mask_bits, strategy, no_data, clip, clip_lo, clip_hi));
+    CHIP_CHECK(chip_check_labels("ig_chip_warp", elem_size, valid_bit, K));
     const long TC = (long)T * C;
-    IG_REQUIRE(TC * S * S <= 0x7fffffffL, "ig_chip_warp: T * C * S * S = %ld values per chip exceeds 2^31 - 1 (valid_values is int32)", TC * S * S);
+    CHIP_CHECK(chip_check_values("ig_chip_warp", TC, S));
     if (n == 0) return IG_OK;
-    IG_REQUIRE(TC * S * S < RLIM40 / n, "ig_chip_warp: n * T * C * S * S exceeds 2^40 values (n %d, S %d)", n, S);
     const int nb = ig_cdiv(S, RB);
-    IG_REQUIRE((long)nb * nb * n <= 0x7fffffffL, "ig_chip_warp: %ld workgroups exceed 2^31 - 1 (n %d, S %d)", (long)nb * nb * n, n, S);
+    CHIP_CHECK(chip_check_launch("ig_chip_warp", n, TC, S, (long)nb * nb));
     IG_REQUIRE(tile && src_crs && src_grid && dst_crs && dst_grids && chips && valid_values, "ig_chip_warp: null pointer");
     IG_REQUIRE(!labels || (maps && valid_labels), "ig_chip_warp: null pointer (maps, valid_labels)");
     IG_REQUIRE(K == 0 || (labels && hist), "ig_chip_warp: null pointer (labels, hist): a class histogram needs both");

@@ -25,16 +25,14 @@
 // float64 values (NaN fails) for a scene with 1 <= H_s, W_s and H_s * W_s <= 2^31 - 1; a plane whose start is negative is never addressed;
 // a grid (the stack's or the scene's) that is not finite and positive yields no offsets at all; every store is guarded by row < S and
 // column < S of a chip index below n.  The caller guarantees that starts[k] + H_s * W_s lies inside the buffer.
-#include "chip_epilogue.h"
+#include "chip_kernels.h"
 #include "common.h"
-#include "pixel_seg.h"
 #include "warp_proj.h"
 
 namespace {
 
 constexpr int VB = 64, VTPB = 256, VROWS = VB / 4, VG = 4;  // block side, threads, rows per thread, rows in flight at a time
-constexpr int VMAX_T = 32, VMAX_N = 32, VMAX_S = 1 << 15;
-constexpr long VLIM40 = 1L << 40;
+constexpr int VMAX_N = 32;
 
 struct S1CutArgs {
     int T, C, N, S, nb, has_nodata, clip;
@@ -175,15 +173,13 @@ extern "C" int ig_s1_chip_cut(const float* planes, const long long* starts, cons
                               const int* scene_size, int N, unsigned first_bits, const double* dst_crs, const double* dst_grid,
                               const int* origins, int n, int T, int C, int S, float no_data, int has_src_nodata, float src_nodata, int clip,
                               float clip_lo, float clip_hi, float* chips, int* valid_values, unsigned char* validity, void* stream) {
-    IG_REQUIRE(n >= 0, "ig_s1_chip_cut: need n >= 0 (got %d)", n);
-    IG_REQUIRE(T >= 1 && T <= VMAX_T, "ig_s1_chip_cut: 1 <= T <= %d dates (got %d)", VMAX_T, T);
-    IG_REQUIRE(C >= 1, "ig_s1_chip_cut: need C >= 1 bands per date (got %d)", C);
+    CHIP_CHECK(chip_check_stack("ig_s1_chip_cut", n, T, C));
     IG_REQUIRE(N >= 1 && N <= VMAX_N, "ig_s1_chip_cut: 1 <= N <= %d scenes in all (got %d)", VMAX_N, N);
     IG_REQUIRE((first_bits & 1u) && __builtin_popcount(first_bits) == T && (N == 32 || (first_bits >> N) == 0u),
                "ig_s1_chip_cut: every date needs at least one scene: first_bits 0x%x must mark the first scene of each of the %d dates among "
                "%d scenes (bit 0, T bits in all, none at or above N)",
                first_bits, T, N);
-    IG_REQUIRE(S >= 1 && S <= VMAX_S, "ig_s1_chip_cut: need a chip side 1 <= S <= 2^15 (got %d)", S);
+    CHIP_CHECK(chip_check_side("ig_s1_chip_cut", S));
     IG_REQUIRE(no_data == no_data, "ig_s1_chip_cut: no_data must not be NaN (a NaN equals nothing, itself included)");
     IG_REQUIRE(has_src_nodata == 0 || has_src_nodata == 1, "ig_s1_chip_cut: has_src_nodata must be 0 or 1 (got %d)", has_src_nodata);
     IG_REQUIRE(!has_src_nodata || src_nodata == src_nodata, "ig_s1_chip_cut: src_nodata must not be NaN (a NaN is absent anyway)");
@@ -191,12 +187,10 @@ extern "C" int ig_s1_chip_cut(const float* planes, const long long* starts, cons
     IG_REQUIRE(!clip || clip_lo <= clip_hi, "ig_s1_chip_cut: the clip range needs clip_lo <= clip_hi, neither NaN (got %g, %g)", (double)clip_lo,
                (double)clip_hi);
     const long TC = (long)T * C;
-    IG_REQUIRE(TC * S * S <= 0x7fffffffL, "ig_s1_chip_cut: T * C * S * S = %ld values per chip exceeds 2^31 - 1 (valid_values is int32)",
-               TC * S * S);
+    CHIP_CHECK(chip_check_values("ig_s1_chip_cut", TC, S));
     if (n == 0) return IG_OK;
-    IG_REQUIRE(TC * S * S < VLIM40 / n, "ig_s1_chip_cut: n * T * C * S * S exceeds 2^40 values (n %d, S %d)", n, S);
     const int nb = ig_cdiv(S, VB);
-    IG_REQUIRE((long)nb * nb * n <= 0x7fffffffL, "ig_s1_chip_cut: %ld workgroups exceed 2^31 - 1 (n %d, S %d)", (long)nb * nb * n, n, S);
+    CHIP_CHECK(chip_check_launch("ig_s1_chip_cut", n, TC, S, (long)nb * nb));
     IG_REQUIRE(planes && starts && scene_crs && scene_grid && scene_size && dst_crs && dst_grid && origins && chips && valid_values,
                "ig_s1_chip_cut: null pointer");
     IG_REQUIRE((((uintptr_t)starts | (uintptr_t)scene_crs | (uintptr_t)scene_grid | (uintptr_t)dst_crs | (uintptr_t)dst_grid) & 7) == 0,

@@ -23,46 +23,18 @@
 // (the host checks origins before they are uploaded, this is the second fence); a plane whose table entry breaks the bounds of the header
 // reads nothing; every source index is compared with the plane's size before it is used and a vector read is taken only when its last
 // element lies inside the row; every store is guarded by row < S and column < S.
+#include "chip_kernels.h"
 #include "common.h"
-#include "pixel_seg.h"
 
 namespace {
 
 constexpr int CB_H = 16, CB_W = 128, CSEG = 8, CTPB = 256;  // block rows, block columns, pixels per thread, threads
-constexpr int MAX_T = 32;                                   // dates: one bit each in the per-pixel date mask
 constexpr int MAX_P = 1 << 15;                              // pixel sizes
 
 struct S2Args {
     int T, C, Ho, Wo, po, S, any, no_data, boa, range, lo, hi, bx, by;
     unsigned class_bits;
 };
-
-// n <= 8 bytes from p in the widest units the address allows (n = 4 or 8)
-template <int BYTES>
-__device__ __forceinline__ void load_few(const void* p, void* v) {
-    const unsigned a = (unsigned)reinterpret_cast<uintptr_t>(p);
-    const char* s = static_cast<const char*>(p);
-    char* d = static_cast<char*>(v);
-    if (BYTES == 8 && (a & 7) == 0) {
-        const uint2 u = *reinterpret_cast<const uint2*>(s);
-        __builtin_memcpy(d, &u, 8);
-    } else if ((a & 3) == 0) {
-#pragma unroll
-        for (int q = 0; q < BYTES / 4; ++q) {
-            const unsigned u = *reinterpret_cast<const unsigned*>(s + 4 * q);
-            __builtin_memcpy(d + 4 * q, &u, 4);
-        }
-    } else if ((a & 1) == 0) {
-#pragma unroll
-        for (int q = 0; q < BYTES / 2; ++q) {
-            const unsigned short u = *reinterpret_cast<const unsigned short*>(s + 2 * q);
-            __builtin_memcpy(d + 2 * q, &u, 2);
-        }
-    } else {
-#pragma unroll
-        for (int q = 0; q < BYTES; ++q) d[q] = s[q];
-    }
-}
 
 // The CSEG values of plane `base` (H x W pixels of size p; H = 0: a plane that reads nothing) under the output pixels (R, Cc .. Cc + 7) of
 // size po, the first npx of them; 0 where the source pixel lies outside the plane and for j >= npx.
@@ -89,7 +61,7 @@ __device__ __forceinline__ void gather_seg(const E* __restrict__ base, int H, in
         const E* src = base + (long)rs * W + cs;
         if (npx == CSEG && cs + 4 + odd <= W) {
             E e[5];
-            load_few<4 * (int)sizeof(E)>(src, e);
+            load_seg<4 * (int)sizeof(E)>(src, e);
             e[4] = odd ? src[4] : (E)0;
 #pragma unroll
             for (int j = 0; j < CSEG; ++j) v[j] = odd ? e[(j + 1) >> 1] : e[j >> 1];
@@ -154,10 +126,7 @@ __global__ __launch_bounds__(CTPB) void s2_chip_cut_kernel(const unsigned short*
 #pragma unroll
                 for (int j = 0; j < CSEG; ++j) dm[j] |= (f[j] < 32 && (a.class_bits >> f[j] & 1u)) ? 1u << t : 0u;
             }
-            if (a.any) {
-#pragma unroll
-                for (int j = 0; j < CSEG; ++j) dm[j] = dm[j] ? 0xffffffffu : 0u;
-            }
+            if (a.any) any_date(dm);
         }
         unsigned all = 0xffu, some = 0u;  // bit j: all / at least one of the pixel's values differ from no_data
         int t = 0, cc = 0;
@@ -182,13 +151,7 @@ __global__ __launch_bounds__(CTPB) void s2_chip_cut_kernel(const unsigned short*
             }
             all &= ok, some |= ok;
             count += __popc(ok);
-            if (whole) {
-                store_seg<2 * CSEG>(q, v);
-            } else {
-#pragma unroll
-                for (int j = 0; j < CSEG; ++j)
-                    if (j < npx) q[j] = v[j];
-            }
+            store_run<CSEG>(q, whole, npx, v);
             if (++cc == a.C) cc = 0, ++t;
         }
         if (validity) {
@@ -196,20 +159,12 @@ __global__ __launch_bounds__(CTPB) void s2_chip_cut_kernel(const unsigned short*
 #pragma unroll
             for (int j = 0; j < CSEG; ++j) m[j] = (unsigned char)((all >> j & 1u) | (some >> j & 1u) << 1);
             unsigned char* q = validity + (long)chip * cplane + (long)r * a.S + c;
-            if (whole) {
-                store_seg<CSEG>(q, m);
-            } else {
-#pragma unroll
-                for (int j = 0; j < CSEG; ++j)
-                    if (j < npx) q[j] = m[j];
-            }
+            store_run<CSEG>(q, whole, npx, m);
         }
     }
     const int total = block_sum_int(count, part);
     if (threadIdx.x == 0 && total) atomicAdd(valid_values + chip, total);
 }
-
-constexpr long LIM40 = 1L << 40;
 
 }  // namespace
 
@@ -217,28 +172,19 @@ extern "C" int ig_s2_chip_cut(const unsigned short* bands, const long long* star
                               const int* geom, const int* origins, int n, int T, int C, int Ho, int Wo, int po, int S, unsigned class_bits,
                               int strategy, int no_data, int boa_offset, int range, int range_lo, int range_hi, unsigned short* chips,
                               int* valid_values, unsigned char* validity, void* stream) {
-    IG_REQUIRE(n >= 0, "ig_s2_chip_cut: need n >= 0 (got %d)", n);
-    IG_REQUIRE(T >= 1 && T <= MAX_T, "ig_s2_chip_cut: 1 <= T <= %d dates (got %d)", MAX_T, T);
-    IG_REQUIRE(C >= 1, "ig_s2_chip_cut: need C >= 1 bands per date (got %d)", C);
+    CHIP_CHECK(chip_check_stack("ig_s2_chip_cut", n, T, C));
     IG_REQUIRE(Ho >= 1 && Wo >= 1, "ig_s2_chip_cut: need an output grid of Ho >= 1 and Wo >= 1 pixels (Ho %d, Wo %d)", Ho, Wo);
     IG_REQUIRE((long)Ho * Wo <= 0x7fffffffL, "ig_s2_chip_cut: an output grid of Ho * Wo = %ld pixels exceeds 2^31 - 1", (long)Ho * Wo);
     IG_REQUIRE(po >= 1 && po <= MAX_P, "ig_s2_chip_cut: the output pixel size must lie in [1, 2^15] (got %d)", po);
     IG_REQUIRE(S >= 1, "ig_s2_chip_cut: need a chip side S >= 1 (got %d)", S);
     IG_REQUIRE(S <= Ho && S <= Wo, "ig_s2_chip_cut: a chip of side S = %d does not fit an output grid of %d x %d pixels", S, Ho, Wo);
-    IG_REQUIRE(strategy == 0 || strategy == 1, "ig_s2_chip_cut: strategy must be 0 each or 1 any (got %d)", strategy);
-    IG_REQUIRE(no_data >= 0 && no_data <= 65535, "ig_s2_chip_cut: no_data must fit uint16 (got %d)", no_data);
-    IG_REQUIRE(boa_offset >= 0 && boa_offset <= 65535, "ig_s2_chip_cut: boa_offset must lie in [0, 65535] (got %d)", boa_offset);
-    IG_REQUIRE(range == 0 || range == 1, "ig_s2_chip_cut: range must be 0 or 1 (got %d)", range);
-    IG_REQUIRE(!range || (range_lo >= 0 && range_hi <= 65535 && range_lo <= range_hi),
-               "ig_s2_chip_cut: the valid range must fit uint16 with range_lo <= range_hi (got %d, %d)", range_lo, range_hi);
+    CHIP_CHECK(chip_check_s2_rule("ig_s2_chip_cut", strategy, no_data, boa_offset, range, range_lo, range_hi));
     const long TC = (long)T * C;
-    IG_REQUIRE(TC <= 0x7fffffffL / 3 - MAX_T, "ig_s2_chip_cut: T * C = %ld planes are too many for the int32 plane table", TC);
-    IG_REQUIRE(TC * S * S <= 0x7fffffffL, "ig_s2_chip_cut: T * C * S * S = %ld values per chip exceeds 2^31 - 1 (valid_values is int32)",
-               TC * S * S);
+    IG_REQUIRE(TC <= 0x7fffffffL / 3 - CHIP_MAX_T, "ig_s2_chip_cut: T * C = %ld planes are too many for the int32 plane table", TC);
+    CHIP_CHECK(chip_check_values("ig_s2_chip_cut", TC, S));
     if (n == 0) return IG_OK;
-    IG_REQUIRE(TC * S * S < LIM40 / n, "ig_s2_chip_cut: n * T * C * S * S exceeds 2^40 values (n %d, S %d)", n, S);
     const int bx = ig_cdiv(S, CB_W), by = ig_cdiv(S, CB_H);
-    IG_REQUIRE((long)bx * by * n <= 0x7fffffffL, "ig_s2_chip_cut: %ld workgroups exceed 2^31 - 1 (n %d, S %d)", (long)bx * by * n, n, S);
+    CHIP_CHECK(chip_check_launch("ig_s2_chip_cut", n, TC, S, (long)bx * by));
     IG_REQUIRE(bands && starts && geom && origins && chips && valid_values, "ig_s2_chip_cut: null pointer");
     IG_REQUIRE(!scl || scl_starts, "ig_s2_chip_cut: null pointer (scl_starts goes with scl)");
     IG_REQUIRE((((uintptr_t)bands | (uintptr_t)chips) & 1) == 0 && (((uintptr_t)geom | (uintptr_t)origins | (uintptr_t)valid_values) & 3) == 0 &&

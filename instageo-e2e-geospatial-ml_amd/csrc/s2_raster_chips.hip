@@ -19,16 +19,14 @@
 // float64 values (NaN fails) for a class with 1 <= H_g, W_g and H_g * W_g <= 2^31 - 1; a plane whose class index lies outside [0, G) or
 // whose start is negative is never addressed; a grid (the chip's or any class's) that is not finite and positive yields no coordinates at
 // all; every store and every label load is guarded by row < S and column < S of a chip index below n.
-#include "chip_epilogue.h"
+#include "chip_kernels.h"
 #include "common.h"
-#include "pixel_seg.h"
 #include "warp_proj.h"
 
 namespace {
 
 constexpr int QB = 64, QTPB = 256, QROWS = QB / 4;  // block side, threads, rows per thread
-constexpr int QMAX_T = 32, QMAX_G = 8, QMAX_S = 1 << 15;
-constexpr long QLIM40 = 1L << 40;
+constexpr int QMAX_G = 8;
 
 struct S2WarpArgs {
     int T, C, S, G, any, no_data, boa, range, lo, hi, nb, valid_bit, K;
@@ -199,29 +197,17 @@ extern "C" int ig_s2_chip_warp(const unsigned short* bands, const long long* sta
                                int no_data, int boa_offset, int range, int range_lo, int range_hi, const void* labels, int elem_size,
                                int valid_bit, int K, unsigned short* chips, int* valid_values, unsigned char* validity, void* maps,
                                int* valid_labels, int* hist, void* stream) {
-    IG_REQUIRE(n >= 0, "ig_s2_chip_warp: need n >= 0 (got %d)", n);
-    IG_REQUIRE(T >= 1 && T <= QMAX_T, "ig_s2_chip_warp: 1 <= T <= %d dates (got %d)", QMAX_T, T);
-    IG_REQUIRE(C >= 1, "ig_s2_chip_warp: need C >= 1 bands per date (got %d)", C);
-    IG_REQUIRE(S >= 1 && S <= QMAX_S, "ig_s2_chip_warp: need a chip side 1 <= S <= 2^15 (got %d)", S);
+    CHIP_CHECK(chip_check_stack("ig_s2_chip_warp", n, T, C));
+    CHIP_CHECK(chip_check_side("ig_s2_chip_warp", S));
     IG_REQUIRE(G >= 1 && G <= QMAX_G, "ig_s2_chip_warp: 1 <= G <= %d geometry classes (got %d)", QMAX_G, G);
-    IG_REQUIRE(strategy == 0 || strategy == 1, "ig_s2_chip_warp: strategy must be 0 each or 1 any (got %d)", strategy);
-    IG_REQUIRE(no_data >= 0 && no_data <= 65535, "ig_s2_chip_warp: no_data must fit uint16 (got %d)", no_data);
-    IG_REQUIRE(boa_offset >= 0 && boa_offset <= 65535, "ig_s2_chip_warp: boa_offset must lie in [0, 65535] (got %d)", boa_offset);
-    IG_REQUIRE(range == 0 || range == 1, "ig_s2_chip_warp: range must be 0 or 1 (got %d)", range);
-    IG_REQUIRE(!range || (range_lo >= 0 && range_hi <= 65535 && range_lo <= range_hi),
-               "ig_s2_chip_warp: the valid range must fit uint16 with range_lo <= range_hi (got %d, %d)", range_lo, range_hi);
-    IG_REQUIRE(elem_size == 1 || elem_size == 4, "ig_s2_chip_warp: elem_size must be 1 (int8) or 4 (float32) (got %d)", elem_size);
-    IG_REQUIRE(valid_bit >= 0 && valid_bit <= 2, "ig_s2_chip_warp: valid_bit must be 0 none, 1 any or 2 each (got %d)", valid_bit);
-    IG_REQUIRE(K >= 0 && K <= EPI_MAX_K, "ig_s2_chip_warp: need 0 <= K <= %d histogram cells (got %d)", EPI_MAX_K, K);
-    IG_REQUIRE(K == 0 || elem_size == 1, "ig_s2_chip_warp: a class histogram (K = %d) needs int8 labels", K);
+    CHIP_CHECK(chip_check_s2_rule("ig_s2_chip_warp", strategy, no_data, boa_offset, range, range_lo, range_hi));
+    CHIP_CHECK(chip_check_labels("ig_s2_chip_warp", elem_size, valid_bit, K));
     const long TC = (long)T * C;
-    IG_REQUIRE(TC <= 0x7fffffffL - QMAX_T, "ig_s2_chip_warp: T * C = %ld planes are too many for the int32 class table", TC);
-    IG_REQUIRE(TC * S * S <= 0x7fffffffL, "ig_s2_chip_warp: T * C * S * S = %ld values per chip exceeds 2^31 - 1 (valid_values is int32)",
-               TC * S * S);
+    IG_REQUIRE(TC <= 0x7fffffffL - CHIP_MAX_T, "ig_s2_chip_warp: T * C = %ld planes are too many for the int32 class table", TC);
+    CHIP_CHECK(chip_check_values("ig_s2_chip_warp", TC, S));
     if (n == 0) return IG_OK;
-    IG_REQUIRE(TC * S * S < QLIM40 / n, "ig_s2_chip_warp: n * T * C * S * S exceeds 2^40 values (n %d, S %d)", n, S);
     const int nb = ig_cdiv(S, QB);
-    IG_REQUIRE((long)nb * nb * n <= 0x7fffffffL, "ig_s2_chip_warp: %ld workgroups exceed 2^31 - 1 (n %d, S %d)", (long)nb * nb * n, n, S);
+    CHIP_CHECK(chip_check_launch("ig_s2_chip_warp", n, TC, S, (long)nb * nb));
     IG_REQUIRE(bands && starts && plane_class && class_grid && class_size && src_crs && dst_crs && dst_grids && chips && valid_values,
                "ig_s2_chip_warp: null pointer");
     IG_REQUIRE(!scl || scl_starts, "ig_s2_chip_warp: null pointer (scl_starts goes with scl)");

@@ -1,6 +1,7 @@
-// The float64 projection code shared by the kernels that map a destination pixel into a source grid (warp.hip, raster_chips.hip,
-// maptiles.hip): WGS84 constants, Krueger's series for transverse Mercator, the coordinate-system and grid descriptions and their chain,
-// as the rule of include/instageo_hip.h states them.  All three files include this text, so all evaluate the same arithmetic.
+// The float64 projection code shared by the kernels that map a destination pixel into a source grid (warp.hip, maptiles.hip,
+// raster_chips.hip, s2_raster_chips.hip, s1_chips.hip): WGS84 constants, Krueger's series for transverse Mercator, the coordinate-system
+// and grid descriptions and their chain, as the rule of include/instageo_hip.h states them.  All of them include this text, so all
+// evaluate the same arithmetic.
 #pragma once
 #include "common.h"
 

@@ -48,6 +48,32 @@ def test_s2_chip_cut_on_a_band_buffer_one_element_off_a_16_byte_boundary(name):
         _same(got, SR.twin(name, 32, option))
 
 
+def test_s2_chip_cut_at_every_alignment_of_the_4_and_5_source_pixel_reads():
+    """A 20 m band and a 20 m SCL under a 10 m grid: the 8 outputs of a segment come from 4 (even first column) or 5 (odd) source pixels,
+    read as one 8-byte (band) or 4-byte (SCL) segment in the widest units the address allows.  The band buffer starts 0..3 elements and the
+    SCL buffer 0..7 bytes into its allocation, so every alignment arm of both reads is taken; an arm that read nothing would leave the
+    SCL mask empty or the band zero, which the comparison with the twin and the two assertions on the mask exclude."""
+    grid, S, origins = (80, 80, 10), 32, [(3, 10), (6, 21)]  # both wholly inside: every segment takes the vector form
+    planes = [(SR.band_plane(80, 80, seed=5), 10), (SR.band_plane(40, 40, seed=6), 20)]
+    scls = [(SR.scl_plane(40, 40, seed=7), 20)]
+    want = SR.cut(planes, scls, origins, S, grid, 1, SR.CLASS_BITS, "each")
+    unmasked = SR.cut(planes, None, origins, S, grid, 1, SR.CLASS_BITS, "each")
+    assert (want[0] != unmasked[0]).any() and (want[0] != 0).any()  # the mask removed some values and left others
+    for lead in range(4):
+        bands, starts, geom = SR.pack(planes, np.uint16, lead=lead)
+        b = _dev(bands)[lead:]
+        assert b.data_ptr() % 16 == 2 * lead
+        for scl_lead in range(8):
+            scl, scl_starts, scl_geom = SR.pack(scls, np.uint8, lead=scl_lead)
+            s = _dev(scl)[scl_lead:]
+            assert s.data_ptr() % 16 == scl_lead
+            got = s2_chips.cut(b, starts - lead, geom, s, scl_starts - scl_lead, scl_geom, origins, S, grid, class_bits=SR.CLASS_BITS,
+                               strategy="each")
+            _same(got, want)
+    chips = got[0].cpu().numpy()
+    assert (chips != unmasked[0]).any() and (chips != 0).any()  # on the device output too
+
+
 def test_two_runs_give_equal_outputs_and_a_window_masked_on_all_dates_has_no_valid_value():
     k, planes, scls = SR.make_case("t3c2", fully_masked=(64, 32), S=32)
     bands, starts, geom = SR.pack(planes, np.uint16)
