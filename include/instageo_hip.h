@@ -866,6 +866,48 @@ int ig_s1_chip_cut(const float* planes, const long long* starts, const double* s
 int ig_composite(const short* bands, const long long* starts, const unsigned char* fmasks, const long long* fmask_starts,
                  const int* step_ptr, int T, int N, int max_m, int C, int H, int W, int mask_bits, int no_data, int min_clear, int method,
                  short* composite, unsigned char* count, unsigned char* source, int* hist, void* stream);
+/* Speckle filtering and dB scaling of Sentinel-1 RTC planes (s1_filter.hip; not in the reference, whose S1PointsPipeline copies linear
+ * gamma0 into the chips as it comes).  THE RULE:
+ * Inputs.  N float32 planes, each row-major and whole, packed in the one float32 buffer `planes` of `total` elements: plane p has the size
+ *   sizes[2 p ..] = (H, W) int32 and starts at the int64 element offset starts[p]; both tables ON THE DEVICE, the packing of
+ *   ig_s1_chip_cut and ig_composite.  h in 1..7 gives the window w = 2 h + 1 of 3..15; method is 0 BOXCAR, 1 LEE or 2 GAMMA_MAP; looks is
+ *   a float32 > 0, the equivalent number of looks (a user setting, 4.4 for IW GRD); has_src_nodata / src_nodata as in ig_s1_chip_cut;
+ *   to_db is 0 or 1.
+ * Presence.  A value is PRESENT when it is finite (NaN and +-inf are absent) and, with has_src_nodata != 0, differs from src_nodata.
+ * Window moments.  For pixel (r, c) the window is rows r - h .. r + h and columns c - h .. c + h, clipped to the plane.  All arithmetic is
+ *   in FLOAT64 WITH CONTRACTION OFF, in this order: per window row, left to right over the present values, starting from +0.0:
+ *   A_i += x, Q_i += x x, K_i += 1 (x the float32 widened, so x x is exact); then top to bottom, starting from +0.0: A += A_i, Q += Q_i,
+ *   n += K_i.  The order is part of the rule.
+ * Centre absent: the output is the quiet NaN 0x7FC00000; absent stays absent, nothing is filled in.
+ * Centre present (then n >= 1): m = A / n, v = Q / n - m m with each operation rounded once, v = 0 where v < 0; s = 1 / (double)looks.
+ *   0 BOXCAR: y = m.
+ *   1 LEE (Lee 1980, MMSE form): t = (m m) s, vx = (v - t) / (1 + s), b = vx / v when v > 0 and vx > 0, else 0, y = m + b (x - m).
+ *   2 GAMMA_MAP (Lopes 1990): if m <= 0, y = m.  Otherwise ci2 = v / (m m); if ci2 <= s, y = m; if ci2 >= 2 s, y = x; otherwise
+ *     a = (1 + s) / (ci2 - s), B = a - (double)looks - 1, D = (m m)(B B) + ((4 a)(double)looks)(m x), y = (B m + sqrt(D)) / (2 a) when
+ *     D >= 0, else m.
+ * Scale.  to_db = 0: out = (float)y, rounded to nearest.  to_db = 1: out = (float)(10 log10(y)) when y > 0, else the quiet NaN and the
+ *   pixel is counted as DROPPED.
+ * Outputs.  out float32 with the layout and starts of planes (`total` elements; it must not overlap planes); every element of every
+ *   plane is WRITTEN EXACTLY ONCE, elements between planes are left alone.  counts (N, 2) int32 (the caller zeroes it): counts[p][0] +=
+ *   the outputs of plane p that are present (centre present and not dropped), counts[p][1] += the pixels dropped by the dB step.
+ *   Add, multiply, divide, compare and convert are correctly rounded, so BOXCAR and LEE in linear scale are the same bits on any
+ *   IEEE-754 machine; sqrt and log10 are the library's.  Each result depends on its window alone: the same bits for any launch geometry.
+ * ig_s1_speckle: one launch for all planes.  One workgroup of 256 threads owns a tile of 64 columns x 32 rows of one plane; tile_ptr
+ *   (N + 1 ascending int64 from 0, ON THE DEVICE, built by the host: plane p has ceil(H / 32) ceil(W / 64) tiles) lets workgroup b find
+ *   its plane by binary search, `tiles` = tile_ptr[N] is the grid.  The tile and its halo of h pixels are staged in LDS once as float32,
+ *   absent values (and what lies outside the plane) as NaN; then the row moments of the 32 + 2 h staged rows go to LDS as float64,
+ *   float64, int32 and are summed down the columns.  Each value comes from HBM once plus the halo; a wave stores 64 consecutive float32
+ *   of a row, 4 bytes per lane, which any W and any 4-byte-aligned start allow; borders and ragged last tiles are bounds tests, no
+ *   padding is read; LDS 73 232 bytes at h = 7: two workgroups per CU.  The counts are summed in the wave and the workgroup and added
+ *   with one integer atomic each per workgroup; no workgroup waits on another.
+ *   Refused before any launch: h outside 1..7, method outside 0..2, looks not > 0 or not finite, has_src_nodata or to_db outside 0..1,
+ *   src_nodata NaN, N < 0, total < 0 or >= 2^40, tiles < 0 or > 2^31 - 1, null pointers, planes / out / sizes / counts not 4-byte,
+ *   starts / tile_ptr not 8-byte aligned, out overlapping planes.  N = 0 returns IG_OK without touching a pointer.  Per table entry
+ *   1 <= H W <= 2^31 - 1, starts >= 0 and starts + H W <= total: the tables are on the device, so ops.s1_speckle checks them on the host
+ *   before the upload, and the kernel is the second fence: a plane whose stated size is not positive (or that breaks the other bounds) is
+ *   skipped, as is a workgroup beyond its plane's own number of tiles. */
+int ig_s1_speckle(const float* planes, const long long* starts, const int* sizes, const long long* tile_ptr, int N, long total, long tiles,
+                  int h, int method, float looks, int has_src_nodata, float src_nodata, int to_db, float* out, int* counts, void* stream);
 /* Web Mercator map tiles rendered from an overview pyramid (maptiles.hip; the reference's new_apps/backend/app/tiler_service.py answers
  * tiles/WebMercatorQuad/{z}/{x}/{y}@1x.png through TiTiler: a warp into EPSG:3857, an overview level, nearest sampling and a colormap or
  * rescale per request).  THE RULE:

@@ -161,6 +161,12 @@ DEFAULTS: Dict[str, Any] = {'root_dir': None,
  'composite': {'scenes': None, 'fmasks': None, 'dates': None, 'method': 'medoid',
                'mask_types': ['cloud', 'near_cloud_or_shadow', 'cloud_shadow'], 'min_clear': 1, 'no_data': -9999, 'output_directory': None,
                'device': None},
+ # mode=filter_s1 (not in the reference, which neither filters speckle nor converts to dB; s1_filter.py): scenes = Sentinel-1 RTC band
+ # files (float32) in the nesting of s1_chips.scenes, or one flat list; each is written under the same base name into output_directory,
+ # ready to be named in s1_chips.scenes.  method = boxcar, lee or gamma_map over a window x window neighbourhood (odd, 3..15), looks = the
+ # equivalent number of looks (4.4: IW GRD), scale = linear or db (cut dB chips with s1_chips.no_data_value=-9999: -1.0 is a valid dB
+ # value), src_nodata = the files' own no-data value (None: each file's no-data tag)
+ 's1_filter': {'scenes': None, 'output_directory': None, 'method': 'lee', 'window': 7, 'looks': 4.4, 'scale': 'linear', 'src_nodata': None},
  # mode=clean_chips (the reference's instageo/data/data_cleaner.py under its flag names; clean.py): drop the chips of chips_dataset_csv
  # whose share of no-data pixels is above the threshold, buffer the observation pixels of the label maps by window_size (or limit the maps
  # to the pixels of observation_points_csv), write output_chips_dataset_csv and clean_stats.json.  Not in the reference: num_classes

@@ -1565,6 +1565,37 @@ def composite(bands, starts, fmasks, fmask_starts, step_ptr, C: int, shape: Tupl
     return comp, count, source, hist
 
 
+def s1_speckle(planes, starts, sizes, window: int = 7, method: str = "lee", looks: float = 4.4, src_nodata=None, scale: str = "linear",
+               out=None):
+    """``ig_s1_speckle`` (include/instageo_hip.h): ``planes`` the packed float32 planes as a 1-D tensor on the device; ``starts`` (N,) and
+    ``sizes`` (N, 2) = (H, W) as host arrays: they are checked here (every plane inside the buffer, no two overlapping) and uploaded with
+    the prefix table of tiles.  -> (out: float32 with the layout of ``planes``, elements outside every plane 0; counts (N, 2) int32: the
+    present outputs and the pixels the dB step dropped).  ``out``: a contiguous float32 tensor of the size of ``planes`` to write into
+    instead of a new one (only the elements of the planes are written)."""
+    import numpy as np
+
+    from . import s1_filter as F
+
+    assert planes.dtype == torch.float32 and planes.dim() == 1, "the planes are one packed 1-D float32 buffer"
+    st, ss, h, code, lk, snd, to_db = F.check_speckle(int(planes.shape[0]), starts, sizes, window, method, looks, src_nodata, scale)
+    N, dev, total = st.shape[0], planes.device, int(planes.shape[0])
+    pixels = int((ss[:, 0].astype(np.int64) * ss[:, 1]).sum())
+    if out is None:
+        out = (torch.empty if pixels == total else torch.zeros)(total, dtype=torch.float32, device=dev)
+    assert out.dtype == torch.float32 and out.shape == planes.shape and out.device == dev, "out is a float32 tensor of the size of planes"
+    counts = torch.zeros((N, 2), dtype=torch.int32, device=dev)
+    if N:
+        tp = F.tile_table(ss)
+        # alive until the launch is queued; the copies are stream-ordered.  One upload of the int64 tables; both slices 8-byte aligned
+        tab = torch.from_numpy(np.concatenate([st, tp])).to(dev)
+        sd = torch.from_numpy(ss.reshape(-1)).to(dev)
+        # HBM bytes: every value read once (the halo comes from the caches) and written once
+        work = 8.0 * pixels
+        _call("ig_s1_speckle", work, _p(planes), _p(tab[:N]), _p(sd), _p(tab[N:]), N, total, int(tp[-1]), h, code, float(lk), int(snd is not None),
+              float(snd) if snd is not None else 0.0, to_db, _p(out), _p(counts), _stream())
+    return out, counts
+
+
 TILE_STYLES ={"palette": 0, "ramp": 1, "rgb": 2}  # include/instageo_hip.h
 TILE_MAX_LEVELS = 13
 

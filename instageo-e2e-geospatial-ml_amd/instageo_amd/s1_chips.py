@@ -18,8 +18,9 @@ takes the value of the first scene of the date, in list order, that the pixel li
 Device tensors go through ``ig_s1_chip_cut``; host arrays take a numpy twin of the same rule, so the module works (and is tested) without
 a GPU and both write the same bytes.
 
-Not done: STAC search and signing, SAFE / GRD input and calibration, dB conversion, speckle filtering, any resampling but nearest,
-rotated rasters, and a label-raster pipeline for Sentinel-1 (the reference has none).
+Not done: STAC search and signing, SAFE / GRD input and calibration, any resampling but nearest, rotated rasters, and a label-raster
+pipeline for Sentinel-1 (the reference has none).  Speckle filtering and dB conversion are :mod:`instageo_amd.s1_filter`, whose output
+files this module takes as they are.
 """
 from __future__ import annotations
 

@@ -1,0 +1,104 @@
+"""Speckle filtering: HIP-event time of ``ig_s1_speckle`` on one date of three synthetic Sentinel-1 RTC scenes of 11000 x 11000 pixels x 2
+bands (six float32 planes, 0.73 G values), windows 7 and 15, each method, linear and dB, next to a device copy of the same number of bytes
+(read plus written) and to the numpy host path on rows of one plane.  About 3 % of the values are NaN and a border of 200 pixels of every
+plane is the source's no-data value.
+
+    python tools/s1_filter_bench.py [--reps 5] [--side 11000] [--host-rows 256] [--out profiles/s1_filter.txt]
+"""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "instageo-e2e-geospatial-ml_amd"))
+
+
+def timed(fn, reps):
+    fn()
+    torch.cuda.synchronize()
+    best = float("inf")
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        best = min(best, a.elapsed_time(b) * 1e3)
+    return best
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--side", type=int, default=11000)
+    ap.add_argument("--host-rows", type=int, default=256, help="rows of one plane the numpy host path is timed on (scaled to all planes)")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    from instageo_amd import s1_filter as F
+    from instageo_amd import torch_ops
+
+    torch_ops.register()
+    ns = torch.ops.instageo_mi355x
+    lines = []
+
+    def emit(s):
+        print(s, flush=True)
+        lines.append(s)
+
+    side, N, snd = args.side, 6, -32768.0
+    HW = side * side
+    gen = torch.Generator(device="cuda").manual_seed(1)
+    planes = torch.empty(N * HW, dtype=torch.float32, device="cuda")
+    for p in range(N):  # exponential speckle on a texture of 64 x 64 blocks; built plane by plane to bound the temporaries
+        tex = 10.0 ** (torch.rand(((side + 63) // 64, (side + 63) // 64), device="cuda", generator=gen) * 3.0 - 3.0)
+        v = planes[p * HW : (p + 1) * HW].view(side, side)
+        v.copy_(tex.repeat_interleave(64, 0).repeat_interleave(64, 1)[:side, :side])
+        v.mul_(torch.empty((side, side), device="cuda").exponential_(1.0, generator=gen))
+        v[torch.rand((side, side), device="cuda", generator=gen) < 0.03] = float("nan")
+        edge = min(200, side // 4)
+        v[:edge], v[-edge:], v[:, :edge], v[:, -edge:] = snd, snd, snd, snd
+        del tex
+    sizes_h = np.array([(side, side)] * N, dtype=np.int32)
+    starts = torch.arange(N, dtype=torch.int64, device="cuda") * HW
+    sizes = torch.from_numpy(sizes_h.reshape(-1)).cuda()
+    tp = F.tile_table(sizes_h)
+    tile_ptr = torch.from_numpy(tp).cuda()
+    out = torch.empty_like(planes)
+    counts = torch.zeros((N, 2), dtype=torch.int32, device="cuda")
+    moved = 8 * N * HW  # read plus written
+    copy_us = timed(lambda: out.copy_(planes), args.reps)
+    emit(f"{torch.cuda.get_device_name(0)}; {N} planes of {side} x {side} float32 in one launch ({int(tp[-1])} workgroups); best of {args.reps}")
+    emit(f"{moved / 1e6:7.1f} MB read + written; a device copy moving as many bytes: {copy_us:9.1f} us = {moved / copy_us / 1e6:5.2f} TB/s")
+    rows = min(args.host_rows, side)
+    host_plane = planes[:HW].view(side, side)[:rows].contiguous().view(-1).cpu().numpy()
+    for window in (7, 15):
+        h = window // 2
+        for method, code in F.METHODS.items():
+            for scale, to_db in F.SCALES.items():
+                run = lambda: ns.s1_speckle(planes, starts, sizes, tile_ptr, N, N * HW, int(tp[-1]), h, code, F.LOOKS, 1, snd, to_db, out, counts)  # noqa: E731
+                us = timed(run, args.reps)
+                counts.zero_()
+                run()
+                c = counts.sum(dim=0).cpu().tolist()
+                t0 = time.perf_counter()
+                host, _ = F.speckle(host_plane, [0], [(rows, side)], window, method, F.LOOKS, snd, scale)
+                host_ms = (time.perf_counter() - t0) * 1e3 * (side / rows) * N
+                inner = slice(h, rows - h)  # rows whose windows the strip holds whole
+                dev = out[:HW].view(side, side)[:rows].cpu().numpy()[inner].view(np.int32).astype(np.int64)
+                ref = host.reshape(rows, side)[inner].view(np.int32).astype(np.int64)
+                nan = dev == 0x7FC00000
+                same_nan = bool(np.array_equal(nan, ref == 0x7FC00000))
+                ulp = int(np.abs(dev - ref)[~nan].max()) if same_nan and (~nan).any() else -1
+                emit(f"  w = {window:2d} {method:9s} {scale:6s}: {us:9.1f} us = {moved / us / 1e6:5.2f} TB/s = {us / copy_us:5.2f} x the copy's time; "
+                     f"present {c[0] / (N * HW):.3f}, dropped {c[1]}; numpy host path {host_ms / 1e3:7.1f} s (from {rows} rows of one plane) = "
+                     f"{host_ms * 1e3 / us:6.0f} x; against it: NaN pattern equal {same_nan}, at most {ulp} ulp")
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
