@@ -820,6 +820,45 @@ int ig_s1_chip_cut(const float* planes, const long long* starts, const double* s
                    int N, unsigned first_bits, const double* dst_crs, const double* dst_grid, const int* origins, int n, int T, int C, int S,
                    float no_data, int has_src_nodata, float src_nodata, int clip, float clip_lo, float clip_hi, float* chips,
                    int* valid_values, unsigned char* validity, void* stream);
+/* Sentinel-1 chips warped onto label grids (s1_raster_chips.hip; not in the reference, which has no label-raster pipeline for Sentinel-1:
+ * the sources and the value rule of ig_s1_chip_cut on the destination and with the label maps of ig_chip_warp).  THE RULE:
+ * Sources.  Exactly those of ig_s1_chip_cut: T <= 32 dates of C >= 1 float32 bands, date t with n_t >= 1 scenes, N <= 32 in all, marked
+ *   by first_bits; scene s with its own scene_crs (5 doubles), scene_grid, scene_size and its planes at starts[s C + b] in the one
+ *   buffer `planes`.  All tables are ON THE DEVICE.
+ * Destination.  Exactly that of ig_chip_warp: dst_crs (5 doubles) the one coordinate system of the n chips, dst_grids (n, 4) doubles the
+ *   grid of every chip, ON THE DEVICE; every chip is S x S.
+ * Coordinates.  The centre of pixel (r, c) of chip i comes from the arithmetic of ig_chip_warp on dst_grids[i],
+ *   x = X0_i + (c + 0.5) sx_i, y = Y0_i - (r + 0.5) sy_i, and goes to every scene by the chain of ig_s1_chip_cut: where the five doubles
+ *   of dst_crs equal the scene's, the affine arithmetic alone; otherwise the inverse projection of dst_crs ONCE per pixel and not once
+ *   per scene, then the forward projection of the scene's system, (NaN, NaN) outside the domain.  NEAREST: floor, tested on the float64
+ *   values; INSIDE as in ig_s1_chip_cut.  A destination grid whose values are not finite or whose pixel sizes are not positive gives a
+ *   chip that is no_data everywhere; a scene with such a grid, or whose size breaks 1 <= H_s, W_s, H_s * W_s <= 2^31 - 1, reads nothing,
+ *   and so does a plane with a negative start.  No read leaves a plane.
+ * Value of band b of date t at a pixel: the rule of ig_s1_chip_cut unchanged (presence per value: not NaN and, with has_src_nodata,
+ *   != src_nodata; the first scene of the date in list order that the pixel lies inside and whose value is present gives its 32 bits;
+ *   otherwise no_data, float32; clip on present values only).  chips (n, T * C, S, S) float32; valid_values and validity (or NULL) with
+ *   the bits of ig_chip_cut, as in ig_s1_chip_cut.
+ * Label maps: labels, elem_size, valid_bit, K, maps, valid_labels and hist exactly as in ig_chip_warp (int8 or float32, NaN -> -1,
+ *   -1 where the validity bit of valid_bit is clear, valid_bit 0: no masking, the histogram of int8 values in [0, K), K <= 128).  The
+ *   caller zeroes valid_values, valid_labels and hist.
+ * All results are copies or integers, and unique: the same bits for any launch geometry, run after run.
+ * ig_s1_chip_warp: a gather in the blocking of ig_chip_warp, one launch for all n chips, with the inner loop of ig_s1_chip_cut: a thread
+ *   takes its 16 rows 4 at a time, keeps (lon, lat) of those pixels when some scene lives in another system than the chips (label grids
+ *   in EPSG:4326 or 3857: the common case here), holds the int32 source offsets of ONE slice at a time and the 32-bit pending mask per
+ *   pixel; the validity byte, the label pixel and the tallies come from the epilogue of ig_chip_warp (the histogram in LDS; integer
+ *   atomics, one set per workgroup; no workgroup waits on another).
+ *   The limits are the union of the two parents': 1 <= T <= 32, C >= 1, 1 <= N <= 32 with first_bits as in ig_s1_chip_cut,
+ *   1 <= S <= 2^15, T * C * S * S <= 2^31 - 1, n * T * C * S * S < 2^40, no_data and (when given) src_nodata not NaN,
+ *   clip_lo <= clip_hi, elem_size 1 or 4 (also without labels), 0 <= K <= 128 and K > 0 needs elem_size 1 and labels, valid_bit 0, 1 or
+ *   2; these are refused before any launch.  Per table entry H_s, W_s >= 1, H_s * W_s <= 2^31 - 1, 0 <= starts[k]: the tables are on the
+ *   device, so ops.s1_chip_warp checks them on the host before the upload, and the kernel is the second fence (above).  The caller
+ *   guarantees that starts[s C + b] + H_s * W_s lies inside the buffer.  planes, chips, the int32 arrays and float32 labels / maps
+ *   4-byte, starts and the float64 arrays 8-byte aligned.  n = 0 returns IG_OK without touching a pointer. */
+int ig_s1_chip_warp(const float* planes, const long long* starts, const double* scene_crs, const double* scene_grid, const int* scene_size,
+                    int N, unsigned first_bits, const double* dst_crs, const double* dst_grids, int n, int T, int C, int S, float no_data,
+                    int has_src_nodata, float src_nodata, int clip, float clip_lo, float clip_hi, const void* labels, int elem_size,
+                    int valid_bit, int K, float* chips, int* valid_values, unsigned char* validity, void* maps, int* valid_labels, int* hist,
+                    void* stream);
 /* Cloud-free temporal composites of HLS scenes (composite.hip; not in the reference, whose add_hls_stac_items takes the single least
  * cloudy granule near a step's date and loses what Fmask flags in it).  THE RULE:
  * Inputs.  N scenes of one MGRS tile on ONE grid of H x W pixels (the host checks size, tiepoint, pixel scale and GeoKeys).  Scene n has C

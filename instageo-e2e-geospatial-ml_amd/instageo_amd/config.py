@@ -151,6 +151,14 @@ DEFAULTS: Dict[str, Any] = {'root_dir': None,
  's1_chips': {'scenes': None, 'records_file': None, 'output_directory': None, 'chip_size': 256, 'bands': ['vv', 'vh'],
               'masking_strategy': 'each', 'window_size': 0, 'task_type': 'seg', 'src_crs': 4326, 'epsg': None, 'spatial_resolution': 10,
               'no_data_value': -1, 'src_nodata': None, 'clip': None},
+ # mode=create_s1_raster_chips (not in the reference, which has no label-raster pipeline for Sentinel-1; s1_raster_chips.py): scenes / bands /
+ # no_data_value / src_nodata / clip as in s1_chips (cut dB scenes with no_data_value=-9999: -1.0 is a valid dB value), records_file /
+ # raster_path / chip_size / src_crs / spatial_resolution / snap / qa_check / task_type / is_bbox_feature / bbox_feature_path / date as in
+ # raster_chips; tile_id = the id of the names and of the records this run takes (None: from the first file's name)
+ 's1_raster_chips': {'scenes': None, 'records_file': None, 'raster_path': None, 'output_directory': None, 'chip_size': 256,
+                     'bands': ['vv', 'vh'], 'masking_strategy': 'each', 'src_crs': 4326, 'spatial_resolution': 0.0002694945852358564,
+                     'qa_check': True, 'task_type': 'seg', 'is_bbox_feature': False, 'bbox_feature_path': None, 'date': None, 'snap': True,
+                     'no_data_value': -1, 'src_nodata': None, 'clip': None, 'tile_id': None},
  # mode=create_composite (not in the reference, which takes one scene per temporal step; composite.py): scenes = the HLS band files of one
  # MGRS tile as a list of steps, each a list of scenes, each a list of one file per band ([[[a_B02.tif, a_B03.tif], [b_B02.tif, b_B03.tif]]]);
  # fmasks = the same nesting without the band level, one Fmask file per scene (None: only no_data decides what is clear); dates = one target

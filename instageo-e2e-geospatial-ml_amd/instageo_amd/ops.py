@@ -1534,6 +1534,47 @@ def s1_chip_cut(planes, starts, scene_crs, scene_grid, scene_size, date_scenes, 
     return chips, valid, plane
 
 
+def s1_chip_warp(planes, starts, scene_crs, scene_grid, scene_size, date_scenes, dst_crs, dst_grids, S: int, no_data_value: float = -1.0,
+                 src_nodata=None, clip=None, labels=None, valid_bit: int = 0, K: int = 0, out=None):
+    """``ig_s1_chip_warp`` (include/instageo_hip.h): ``planes`` the packed float32 planes as a 1-D tensor on the device; ``date_scenes``,
+    ``starts``, ``scene_crs``, ``scene_grid`` and ``scene_size`` as :func:`s1_chip_cut` takes them, ``dst_crs`` and ``dst_grids`` (n, 4) as
+    :func:`chip_warp` does, all as host values: they are checked here (every plane inside the buffer) and uploaded.  ``labels``: None, or
+    (n, S, S) int8 | float32 as a device tensor or a host array.  -> (chips (n, T * C, S, S) float32, valid_values (n,) int32, validity
+    (n, S, S) uint8, maps, valid_labels, hist): the last three None without labels, hist None with K = 0.  ``out``: a dict with any of
+    ``chips``, ``validity``, ``maps``: contiguous tensors to write into instead of new ones (every element is written)."""
+    import numpy as np
+
+    from . import s1_raster_chips as R
+
+    assert planes.dtype == torch.float32 and planes.dim() == 1, "the planes are one packed 1-D float32 buffer"
+    lab_dtype = None if labels is None else str(labels.dtype).replace("torch.", "")
+    st, sc, sg, ss, first_bits, T, C, dc, dg, nd, snd, clip = R.check_warp(int(planes.shape[0]), starts, scene_crs, scene_grid, scene_size,
+                                                                          date_scenes, dst_crs, dst_grids, S, no_data_value, src_nodata, clip,
+                                                                          None if labels is None else tuple(labels.shape), lab_dtype,
+                                                                          valid_bit, K)
+    n, N, S = dg.shape[0], sg.shape[0], int(S)
+    dev = planes.device
+    if labels is not None and not torch.is_tensor(labels):
+        labels = torch.from_numpy(np.ascontiguousarray(labels))
+    if labels is not None:
+        labels = labels.to(dev)
+    chips, plane, valid, maps, valid_labels, hist = _chip_outputs(out, dev, (n, T * C, S, S), torch.float32, labels, K)
+    if n:
+        # alive until the launch is queued; the copies are stream-ordered.  One upload of the doubles; every slice 8-byte aligned
+        dbl = torch.from_numpy(np.concatenate([dc, sc.reshape(-1), sg.reshape(-1), dg.reshape(-1)])).to(dev)
+        ints = torch.from_numpy(np.ascontiguousarray(ss.reshape(-1))).to(dev)
+        sd = torch.from_numpy(st).to(dev)
+        lo, hi = (float(clip[0]), float(clip[1])) if clip is not None else (0.0, 0.0)
+        es = labels.element_size() if labels is not None else 1
+        # HBM bytes: the chips and the validity plane written, at least as many values gathered, the labels in and out
+        work = float(n) * S * S * (8 * T * C + 1 + (2 * es if labels is not None else 0))
+        _call("ig_s1_chip_warp", work, _p(planes), _p(sd), _p(dbl[5 : 5 + 5 * N]), _p(dbl[5 + 5 * N : 5 + 9 * N]), _p(ints), N, int(first_bits),
+              _p(dbl[0:5]), _p(dbl[5 + 9 * N :]), n, T, C, S, float(nd), int(snd is not None), float(snd) if snd is not None else 0.0,
+              int(clip is not None), lo, hi, _p(labels), es, int(valid_bit), int(K), _p(chips), _p(valid), _p(plane), _p(maps),
+              _p(valid_labels), _p(hist), _stream())
+    return chips, valid, plane, maps, valid_labels, hist
+
+
 def composite(bands, starts, fmasks, fmask_starts, step_ptr, C: int, shape: Tuple[int, int], mask_bits: int = 0, no_data_value: int = -9999,
               min_clear: int = 1, method: str = "medoid"):
     """``ig_composite`` (include/instageo_hip.h): ``bands`` the packed int16 planes and ``fmasks`` the packed uint8 Fmask planes (or None)

@@ -21,9 +21,9 @@ The destination grid of a record.  ``snap=True`` (the reference): stackstac snap
 bounds, so X = res * floor(minx / res), Y = res * ceil(maxy / res), in float64 on the host.  ``snap=False``: the label raster's own
 grid.  Either way the written chip and label carry the label raster's georeferencing (the reference's ``xr.align(join="override")``).
 
-Not done: the S1 source, STAC search and download, GeoPackage records (a CSV stands in), bilinear / cubic resampling of reflectances,
+Not done: STAC search and download, GeoPackage records (a CSV stands in), bilinear / cubic resampling of reflectances,
 rotated rasters.  Sentinel-2 band planes of several resolutions under SCL masks (``S2RasterPipeline``) go through
-:mod:`instageo_amd.s2_raster_chips`.
+:mod:`instageo_amd.s2_raster_chips`, Sentinel-1 RTC scenes stacked per date through :mod:`instageo_amd.s1_raster_chips`.
 """
 from __future__ import annotations
 
@@ -73,6 +73,13 @@ def check_warp(tile_shape, fmask_shape, src_crs, src_grid, dst_crs, dst_grids, S
     sg = np.ascontiguousarray(src_grid, dtype=np.float64).reshape(-1)
     if sg.shape[0] != 4 or not grid_ok(sg):
         raise ValueError(f"src_grid = (X0, Y0, sx, sy) needs finite values and positive pixel sizes (got {tuple(sg)})")
+    dg = check_dst(dst_grids, S, TC, labels_shape, labels_dtype, valid_bit, K)
+    return params(src_crs), sg, params(dst_crs), dg
+
+
+def check_dst(dst_grids, S: int, TC: int, labels_shape, labels_dtype, valid_bit: int, K: int) -> np.ndarray:
+    """The checks of the destination grids and the labels of a warped cut of ``TC`` planes per chip, shared by :func:`check_warp` and
+    :func:`s1_raster_chips.check_warp` -> dst_grids (n, 4) float64.  A destination grid may be unusable (it gives a no-data chip)."""
     dg = np.ascontiguousarray(dst_grids, dtype=np.float64)
     if dg.size % 4:
         raise ValueError(f"dst_grids is (n, 4) = (X0, Y0, sx, sy) per chip (got shape {dg.shape})")
@@ -94,7 +101,7 @@ def check_warp(tile_shape, fmask_shape, src_crs, src_grid, dst_crs, dst_grids, S
             raise ValueError(f"labels are int8 (seg) or float32 (reg) (got {labels_dtype})")
         if K and str(labels_dtype) != "int8":
             raise ValueError(f"a class histogram (K = {K}) needs int8 labels")
-    return params(src_crs), sg, params(dst_crs), dg
+    return dg
 
 
 # ---- the rule on host arrays ---------------------------------------------------------------------------------------------------------------
@@ -127,21 +134,28 @@ def _warp_host(tile, fmask, sc, sg, dc, dg, S, T, bits, strategy, nd, clip, labe
         chips[i] = a
         validity[i] = ok.all(axis=0).astype(np.uint8) | (ok.any(axis=0).astype(np.uint8) << 1)
     valid_values = (chips != np.int16(nd)).reshape(n, -1).sum(axis=1).astype(np.int32)
+    return (chips, valid_values, validity) + label_maps_host(labels, validity, bit, K)
+
+
+def label_maps_host(labels, validity, bit: int, K: int):
+    """The label step of the host twins (``ig_chip_warp``'s label maps): ``labels`` (n, S, S) int8 | float32 or None under the validity
+    planes -> (maps, valid_labels (n,) int32, hist (n, K) int32 or None with K = 0); three None without labels."""
     maps = valid_labels = hist = None
     if labels is not None:
+        n = labels.shape[0]
         maps = labels.copy()
         blank = (validity & bit) == 0 if bit else np.zeros(maps.shape, dtype=bool)
         if maps.dtype == np.float32:
             blank = blank | np.isnan(maps)
         maps[blank] = SEG_NO_DATA
         live = maps != SEG_NO_DATA
-        valid_labels = live.reshape(n, -1).sum(axis=1).astype(np.int32)
+        valid_labels = live.sum(axis=(1, 2)).astype(np.int32)
         if K:
             hist = np.zeros((n, K), dtype=np.int32)
             for i in range(n):
                 x = maps[i][live[i]].astype(np.int64)
                 hist[i] = np.bincount(x[(x >= 0) & (x < K)], minlength=K)
-    return chips, valid_values, validity, maps, valid_labels, hist
+    return maps, valid_labels, hist
 
 
 def warp_cut(tile, fmask, src_crs, src_grid, dst_crs, dst_grids, chip_size: int, dates: Optional[int] = None,

@@ -19,7 +19,9 @@ reference's ``S2RasterPipeline``, :mod:`instageo_amd.s2_raster_chips`), ``clean_
 ``create_raster_chips`` takes, :mod:`instageo_amd.polygon_labels`) build no model; neither does ``create_composite`` (``composite.*``: the
 HLS scenes near each temporal step's date become one cloud-free composite scene per step, nearest clear date, median or medoid, written
 under HLS-style names that ``chips.tiles`` takes with ``fmasks=None``, :mod:`instageo_amd.composite`) and ``filter_s1`` (``s1_filter.*``:
-Sentinel-1 RTC band files speckle-filtered, optionally to dB, under the same names for ``s1_chips.scenes``, :mod:`instageo_amd.s1_filter`).  Hydra, Lightning and Neptune are replaced by :mod:`instageo_amd.config` and the explicit loop below, which logs the
+Sentinel-1 RTC band files speckle-filtered, optionally to dB, under the same names for ``s1_chips.scenes``, :mod:`instageo_amd.s1_filter`);
+``create_s1_raster_chips`` (``s1_raster_chips.*``: Sentinel-1 RTC scenes stacked per date warped onto the grids of label rasters,
+:mod:`instageo_amd.s1_raster_chips`) is the radar sibling of ``create_raster_chips``.  Hydra, Lightning and Neptune are replaced by :mod:`instageo_amd.config` and the explicit loop below, which logs the
 same metric names and writes ``instageo_best_checkpoint.ckpt`` (``{"state_dict": ...}``) on the best
 ``val_IoU`` (pipeline_utils.py:347-355).  Data: ``*_filepath`` may be ``synthetic:<n>`` (on-device HLS-shaped
 chips), an ``.npz`` with ``chips (N,T*C,H,W)`` and ``labels (N,H,W)``, or the reference's own CSV of chip / label GeoTIFF paths
@@ -55,6 +57,7 @@ PREP_MODES = {"create_chips": "chips",  # HLS tiles + points -> chips, label map
               "create_raster_chips": "raster_chips",  # HLS tiles + label rasters -> chips on the labels' grids
               "create_s2_raster_chips": "s2_raster_chips",  # Sentinel-2 band planes + label rasters -> chips on the labels' grids
               "create_s1_chips": "s1_chips",  # Sentinel-1 RTC scenes stacked per date + points -> float32 chips, label maps, the dataset CSV
+              "create_s1_raster_chips": "s1_raster_chips",  # Sentinel-1 RTC scenes stacked per date + label rasters -> float32 chips on the labels' grids
               "create_composite": "composite",  # the HLS scenes near each step's date -> one cloud-free composite scene per step
               "filter_s1": "s1_filter",  # Sentinel-1 RTC band files -> speckle-filtered (and dB) band files under the same names
               "clean_chips": "clean",  # drop no-data chips, buffer / limit the label maps of a chip dataset

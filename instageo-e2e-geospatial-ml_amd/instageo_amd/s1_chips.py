@@ -18,9 +18,9 @@ takes the value of the first scene of the date, in list order, that the pixel li
 Device tensors go through ``ig_s1_chip_cut``; host arrays take a numpy twin of the same rule, so the module works (and is tested) without
 a GPU and both write the same bytes.
 
-Not done: STAC search and signing, SAFE / GRD input and calibration, any resampling but nearest, rotated rasters, and a label-raster
-pipeline for Sentinel-1 (the reference has none).  Speckle filtering and dB conversion are :mod:`instageo_amd.s1_filter`, whose output
-files this module takes as they are.
+Not done: STAC search and signing, SAFE / GRD input and calibration, any resampling but nearest, rotated rasters.  Chips on the grids of
+label rasters are :mod:`instageo_amd.s1_raster_chips`.  Speckle filtering and dB conversion are :mod:`instageo_amd.s1_filter`, whose
+output files this module takes as they are.
 """
 from __future__ import annotations
 
@@ -50,12 +50,11 @@ def _f32(v, what: str, optional: bool = False) -> Optional[np.float32]:
     return np.float32(v)
 
 
-def check_cut(size: int, starts, scene_crs, scene_grid, scene_size, date_scenes, dst_crs, dst_grid, origins, S: int, no_data_value,
-              src_nodata, clip):
-    """ValueError unless the arguments of a cut obey include/instageo_hip.h -> (starts int64 (N * C,), scene_crs (N, 5) float64,
-    scene_grid (N, 4) float64, scene_size (N, 2) int32, first_bits, T, C, dst_crs (5,), dst_grid (4,), origins (n, 2) int32, no_data,
-    src_nodata or None, clip (lo, hi) or None) with the three values as float32.  The stack grid may be unusable (it gives no-data
-    chips); a scene's grid may not."""
+def check_scenes(size: int, starts, scene_crs, scene_grid, scene_size, date_scenes, S: int, no_data_value, src_nodata, clip):
+    """The checks of the sources and of the value rule, shared by :func:`check_cut` and :func:`s1_raster_chips.check_warp`: ValueError
+    unless they obey include/instageo_hip.h -> (starts int64 (N * C,), scene_crs (N, 5) float64, scene_grid (N, 4) float64, scene_size
+    (N, 2) int32, first_bits, T, C, no_data, src_nodata or None, clip (lo, hi) or None) with the three values as float32.  A scene's
+    grid may not be unusable."""
     if isinstance(S, bool) or not isinstance(S, (int, np.integer)) or not 1 <= int(S) <= MAX_SIDE:
         raise ValueError(f"chip_size must be an int in [1, 2^15] (got {S!r})")
     S = int(S)
@@ -98,6 +97,23 @@ def check_cut(size: int, starts, scene_crs, scene_grid, scene_size, date_scenes,
         clip = (_f32(clip[0], "clip"), _f32(clip[1], "clip"))
         if not clip[0] <= clip[1]:
             raise ValueError(f"clip must be None or (lo, hi) with lo <= hi (got {clip!r})")
+    first_bits = 0
+    at = 0
+    for k in counts:
+        first_bits |= 1 << at
+        at += k
+    return (st, np.ascontiguousarray(sc, dtype=np.float64), sg, np.ascontiguousarray(ss, dtype=np.int32), first_bits, T, C, nd, snd, clip)
+
+
+def check_cut(size: int, starts, scene_crs, scene_grid, scene_size, date_scenes, dst_crs, dst_grid, origins, S: int, no_data_value,
+              src_nodata, clip):
+    """ValueError unless the arguments of a cut obey include/instageo_hip.h -> (starts int64 (N * C,), scene_crs (N, 5) float64,
+    scene_grid (N, 4) float64, scene_size (N, 2) int32, first_bits, T, C, dst_crs (5,), dst_grid (4,), origins (n, 2) int32, no_data,
+    src_nodata or None, clip (lo, hi) or None) with the three values as float32.  The stack grid may be unusable (it gives no-data
+    chips); a scene's grid may not."""
+    st, sc, sg, ss, first_bits, T, C, nd, snd, clip = check_scenes(size, starts, scene_crs, scene_grid, scene_size, date_scenes, S,
+                                                                   no_data_value, src_nodata, clip)
+    S = int(S)
     dg = np.ascontiguousarray(dst_grid, dtype=np.float64).reshape(-1)
     if dg.shape[0] != 4:
         raise ValueError(f"the stack grid is (X0, Y0, sx, sy) (got {dst_grid!r})")
@@ -109,13 +125,7 @@ def check_cut(size: int, starts, scene_crs, scene_grid, scene_size, date_scenes,
         raise ValueError("origins must fit int32")
     if o.shape[0] * T * C * S * S >= 2**40:
         raise ValueError(f"{o.shape[0]} chips of {T * C} x {S} x {S} values are beyond 2^40")
-    first_bits = 0
-    at = 0
-    for k in counts:
-        first_bits |= 1 << at
-        at += k
-    return (st, np.ascontiguousarray(sc, dtype=np.float64), sg, np.ascontiguousarray(ss, dtype=np.int32), first_bits, T, C,
-            raster_chips.params(dst_crs), dg, np.ascontiguousarray(o, dtype=np.int32), nd, snd, clip)
+    return st, sc, sg, ss, first_bits, T, C, raster_chips.params(dst_crs), dg, np.ascontiguousarray(o, dtype=np.int32), nd, snd, clip
 
 
 # ---- the rule on host arrays ---------------------------------------------------------------------------------------------------------------
@@ -260,6 +270,30 @@ def _dates_of(scenes, C: int) -> List[List[List[str]]]:
     return dates
 
 
+def scene_files(scenes, C: int) -> Tuple[List[str], List[int]]:
+    """``scenes`` ([date][scene][band] files of ``C`` bands; a flat date is one scene) -> (the files in order, the number of scenes of every
+    date).  ValueError for too many dates or scenes."""
+    dates = _dates_of(scenes, C)
+    counts = [len(d) for d in dates]
+    if len(dates) > MAX_DATES or sum(counts) > MAX_SCENES:
+        raise ValueError(f"{len(dates)} dates of {sum(counts)} scenes in all: at most {MAX_DATES} dates and {MAX_SCENES} scenes go into one stack")
+    return [f for d in dates for s in d for f in s], counts
+
+
+def read_scenes(files: Sequence[str], C: int):
+    """The band files of :func:`scene_files` read -> (the packed float32 planes, their starts, [(profile, (H, W))] per scene).  ValueError
+    for band files of one scene that differ in grid, size or coordinate system."""
+    planes, starts, shapes, profiles = prep.read_planes(files, "band", np.float32)
+    scene_profiles = []
+    for k in range(0, len(files), C):
+        key = (tuple(crsmod.from_profile(profiles[k]))[:5], warp.grid_of(profiles[k], files[k]), shapes[k])
+        for j in range(k + 1, k + C):
+            if (tuple(crsmod.from_profile(profiles[j]))[:5], warp.grid_of(profiles[j], files[j]), shapes[j]) != key:
+                raise ValueError(f"{files[j]}: its grid, size or coordinate system differs from that of {files[k]}, a band of the same scene")
+        scene_profiles.append((profiles[k], shapes[k]))
+    return planes, starts, scene_profiles
+
+
 def create_s1_chips(scenes, points, output_directory: str, chip_size: int = 256, bands: Sequence[str] = BANDS, masking_strategy: str = "each",
                     window_size: int = 0, task_type: str = "seg", src_crs: int = 4326, epsg: Optional[int] = None,
                     spatial_resolution: float = 10.0, no_data_value: float = NO_DATA_VALUE, src_nodata: Optional[float] = None,
@@ -285,20 +319,9 @@ def create_s1_chips(scenes, points, output_directory: str, chip_size: int = 256,
     if isinstance(bands, str) or not bands:
         raise ValueError(f"bands is a list of at least one name (got {bands!r})")
     C = len(bands)
-    dates = _dates_of(scenes, C)
-    counts = [len(d) for d in dates]
-    if len(dates) > MAX_DATES or sum(counts) > MAX_SCENES:
-        raise ValueError(f"{len(dates)} dates of {sum(counts)} scenes in all: at most {MAX_DATES} dates and {MAX_SCENES} scenes go into one stack")
-    files = [f for d in dates for s in d for f in s]
+    files, counts = scene_files(scenes, C)
     tile_id, stamp_date = tile_id_of(files[0])
-    planes, starts, shapes, profiles = prep.read_planes(files, "band", np.float32)
-    scene_profiles = []
-    for k in range(0, len(files), C):
-        key = (tuple(crsmod.from_profile(profiles[k]))[:5], warp.grid_of(profiles[k], files[k]), shapes[k])
-        for j in range(k + 1, k + C):
-            if (tuple(crsmod.from_profile(profiles[j]))[:5], warp.grid_of(profiles[j], files[j]), shapes[j]) != key:
-                raise ValueError(f"{files[j]}: its grid, size or coordinate system differs from that of {files[k]}, a band of the same scene")
-        scene_profiles.append((profiles[k], shapes[k]))
+    planes, starts, scene_profiles = read_scenes(files, C)
     grid, (H, W), system = stack_grid(scene_profiles, epsg, spatial_resolution)
     tags = {33550: (12, (grid[2], grid[3], 0.0)), 33922: (12, (0.0, 0.0, 0.0, grid[0], grid[1], 0.0)), **crsmod.geokeys(system.epsg)}
     profile = {"tags": tags, "nodata": None}  # the stack lattice as a raster profile
@@ -318,6 +341,34 @@ CONFIG_KEYS = ("scenes", "records_file", "output_directory", "chip_size", "bands
                "epsg", "spatial_resolution", "no_data_value", "src_nodata", "clip")
 
 
+def value_options(c: prep.Section) -> Tuple[float, Optional[float], Optional[Tuple[float, float]]]:
+    """The keys ``no_data_value``, ``src_nodata`` and ``clip`` of a Sentinel-1 section, checked."""
+    nd = c.number("no_data_value", -1, lambda v: v == v, "must be a number that is not NaN")
+    snd = c.get("src_nodata")
+    if snd is not None:
+        snd = c.number("src_nodata", None, lambda v: v == v, "must be None or a number that is not NaN")
+    clip = c.get("clip")
+    if clip is not None:
+        ok = isinstance(clip, (list, tuple)) and len(clip) == 2 and all(isinstance(v, (int, float)) and not isinstance(v, bool) for v in clip)
+        if not ok or not float(clip[0]) <= float(clip[1]):
+            raise c.bad("clip", "must be None or [lo, hi] with lo <= hi", clip)
+        clip = (float(clip[0]), float(clip[1]))
+    return nd, snd, clip
+
+
+def scenes_option(c: prep.Section, C: int) -> Optional[List[List[List[str]]]]:
+    """The key ``scenes`` of a Sentinel-1 section as [date][scene][band] of ``C`` band files, checked; unset gives None."""
+    scenes = c.get("scenes")
+    if scenes is not None:
+        try:
+            scenes = _dates_of(scenes, C)
+        except ValueError as e:
+            raise c.bad("scenes", f"must be a list of dates of scenes of {C} band files ({e})", scenes) from None
+        if len(scenes) > MAX_DATES or sum(len(d) for d in scenes) > MAX_SCENES:
+            raise c.bad("scenes", f"holds at most {MAX_DATES} dates and {MAX_SCENES} scenes in all", scenes)
+    return scenes
+
+
 def s1_chips_options(cfg: Dict[str, Any]) -> Dict[str, Any]:
     """The ``s1_chips.*`` keys of ``mode=create_s1_chips`` checked -> the keyword arguments of :func:`create_s1_chips`.  A bad value raises
     ValueError; ``scenes`` and ``output_directory`` are required only in that mode."""
@@ -332,24 +383,8 @@ def s1_chips_options(cfg: Dict[str, Any]) -> Dict[str, Any]:
     src = c.epsg("src_crs", 4326)
     epsg = c.epsg("epsg", None)
     res = c.number("spatial_resolution", 10, lambda v: 0 < v < np.inf, "must be a positive number")
-    nd = c.number("no_data_value", -1, lambda v: v == v, "must be a number that is not NaN")
-    snd = c.get("src_nodata")
-    if snd is not None:
-        snd = c.number("src_nodata", None, lambda v: v == v, "must be None or a number that is not NaN")
-    clip = c.get("clip")
-    if clip is not None:
-        ok = isinstance(clip, (list, tuple)) and len(clip) == 2 and all(isinstance(v, (int, float)) and not isinstance(v, bool) for v in clip)
-        if not ok or not float(clip[0]) <= float(clip[1]):
-            raise c.bad("clip", "must be None or [lo, hi] with lo <= hi", clip)
-        clip = (float(clip[0]), float(clip[1]))
-    scenes = c.get("scenes")
-    if scenes is not None:
-        try:
-            scenes = _dates_of(scenes, len(bands))
-        except ValueError as e:
-            raise c.bad("scenes", f"must be a list of dates of scenes of {len(bands)} band files ({e})", scenes) from None
-        if len(scenes) > MAX_DATES or sum(len(d) for d in scenes) > MAX_SCENES:
-            raise c.bad("scenes", f"holds at most {MAX_DATES} dates and {MAX_SCENES} scenes in all", scenes)
+    nd, snd, clip = value_options(c)
+    scenes = scenes_option(c, len(bands))
     records, out = c.text("records_file"), c.text("output_directory")
     if cfg.get("mode") == "create_s1_chips" and (not scenes or out is None):
         raise ValueError("mode=create_s1_chips needs s1_chips.scenes and s1_chips.output_directory")

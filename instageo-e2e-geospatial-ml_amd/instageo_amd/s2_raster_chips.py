@@ -175,21 +175,7 @@ def _warp_host(bands, st, scl, sst, pc, cg, cs, sc, dc, dg, S, T, bits, strategy
         chips[i] = a.astype(np.uint16)
         validity[i] = ok.all(axis=0).astype(np.uint8) | (ok.any(axis=0).astype(np.uint8) << 1)
     valid_values = (chips != np.uint16(nd)).reshape(n, TC * S * S).sum(axis=1).astype(np.int32)
-    maps = valid_labels = hist = None
-    if labels is not None:
-        maps = labels.copy()
-        blank = (validity & bit) == 0 if bit else np.zeros(maps.shape, dtype=bool)
-        if maps.dtype == np.float32:
-            blank = blank | np.isnan(maps)
-        maps[blank] = SEG_NO_DATA
-        live = maps != SEG_NO_DATA
-        valid_labels = live.reshape(n, S * S).sum(axis=1).astype(np.int32)
-        if K:
-            hist = np.zeros((n, K), dtype=np.int32)
-            for i in range(n):
-                v = maps[i][live[i]].astype(np.int64)
-                hist[i] = np.bincount(v[(v >= 0) & (v < K)], minlength=K)
-    return chips, valid_values, validity, maps, valid_labels, hist
+    return (chips, valid_values, validity) + raster_chips.label_maps_host(labels, validity, bit, K)
 
 
 def _dtype_name(a) -> str:
