@@ -446,6 +446,37 @@ int ig_zone_toggle(const int* edges, const unsigned char* bit, const long long* 
                    int W, void* stream);
 int ig_zone_tally(unsigned long long* canvas, const signed char* cls, unsigned long long* counts, int H, int W, int ncls, int fill,
                   int write_mask, void* stream);
+/* Zonal statistics of float rasters (zonal.hip; not in the reference): per zone and band the count, mean, sum of squared deviations,
+ * minimum and maximum of a band-major float32 raster (B, H, W) under the inside masks of the block above.  canvas (H, W) uint64 holds the
+ * TOGGLES of one pass as ig_zone_toggle leaves them; it is read, never written, so one canvas serves any number of calls (band groups).
+ * The masks are the inclusive prefix XOR along each row, by the same device function as ig_zone_tally (one rule, one scan).
+ * VALIDITY.  A pixel's value v is VALID iff it is finite (not NaN, not +-Inf) and, when has_nodata != 0, v != nodata (compared as
+ *   float32).  An invalid value counts in `pixels` and in nothing else.
+ * ARITHMETIC.  Every partial result is a triple (n, T, M2): the number of valid values, their sum and the sum of their squared deviations
+ *   from their own mean T / n, all float64 (n is an integer below 2^31, exact).  A thread forms the triple of its run of 4 pixels by the
+ *   two-pass formula; from there on triples are only ever MERGED, by the pairwise update of Chan, Golub and LeVeque in its (T, M2) form:
+ *     n = na + nb,  T = Ta + Tb,  M2 = M2a + M2b + (Tb / nb - Ta / na)^2 * (na * nb / n),   an empty side contributes nothing,
+ *   through the wave (a fixed 6-step butterfly, the lower lane always the left operand), the wave's own accumulator over the chunks and
+ *   rows it owns (in the order it meets them), the workgroup (waves 0..3 in order) and the grid (ig_zone_value_reduce, workgroups in
+ *   order).  No sum of squares, no pivot, no floating-point atomic.  T is a plain float64 sum: exact for integer-valued data below 2^53
+ *   in total, within n * 2^-53 * sum|v| otherwise.  min and max are those of the valid float32 values.
+ * DETERMINISM.  The grid is G = ig_zone_value_grid(H) = min(H, 512) workgroups whatever the device; workgroup g owns rows g, g + G, ...;
+ *   the order of every merge is fixed by (H, W) alone and each band goes through the same instructions whatever B is: two runs give the
+ *   same bits, and a band gives the same bits in any band group.
+ * ig_zone_value_tally: raster (B, H, W) float32, contiguous, 1 <= B <= 8 (IG_ZONE_VALUE_BANDS; the caller loops over groups of bands).
+ *   Writes, for its workgroup g, EVERY cell of partials (G, B, 64, 4) float64 {n, T, M2, the float32 pair (min, max) in one 8-byte
+ *   word} and of pix_partials (G, 64) uint64 = the inside pixels per zone bit (band-independent): the caller need not zero them.  Empty
+ *   cells hold n = 0, T = M2 = 0, min = +Inf, max = -Inf.  There are 64 bits per pixel and nothing is written for any other bit.
+ * ig_zone_value_reduce: partials and pix_partials of G workgroups, merged in workgroup order, -> valid (64, B) int64, stats (64, B, 4)
+ *   float64 {mean = T / n, M2, min, max} and pixels (64) int64 (NULL: not wanted).  A zone bit without a valid value reports valid = 0,
+ *   mean = M2 = 0, min = +Inf, max = -Inf; population variance is M2 / valid.
+ * H * W = 0 or B = 0 returns IG_OK before a pointer is looked at (ig_zone_value_reduce: G = 0 or B = 0).  Pointers are 8-byte aligned,
+ * partials 16-byte, raster 4-byte. */
+int ig_zone_value_grid(int H);
+int ig_zone_value_tally(const unsigned long long* canvas, const float* raster, double* partials, unsigned long long* pix_partials, int H,
+                        int W, int B, int has_nodata, float nodata, void* stream);
+int ig_zone_value_reduce(const double* partials, const unsigned long long* pix_partials, long long* valid, double* stats,
+                         long long* pixels, int G, int B, void* stream);
 /* Polygon labels burned into label rasters (burn.hip; the reference assumes its label rasters were made with gdal_rasterize beforehand).
  * THE RULE:
  * Grid and inside test.  Those of the zonal block above, unchanged: Q = 256 fixed point, X = floor(x * 256 + 0.5), the centre of pixel

@@ -8,6 +8,11 @@
 //   3  zone_tally_kernel       per row: inclusive prefix XOR of the toggles (thread run of ZVPT, wave scan, workgroup scan, carry over the
 //                              chunks of ZCHUNK columns), which is the inside mask of 64 zones; every set bit is counted into an LDS table
 //                              [64][ncls + 1] and the table reaches memory as one 64-bit add per non-empty cell and workgroup
+//   4  zone_value_tally_kernel the same rows and the same scan over a float32 raster of up to 8 bands: per zone bit and band the valid
+//                              values' (n, sum, M2, min, max), merged as triples (Chan, Golub, LeVeque) through the wave, the wave's LDS
+//                              accumulators and the workgroup into one partial per workgroup; the canvas is only read
+//   5  zone_value_reduce_kernel  the partials merged in workgroup order -> valid, mean, M2, min, max and the inside pixels
+//   (4) and (5) are float64 in a fixed order, without atomics: unique results too.
 //
 // Up to 64 zones share a pass: one bit of a uint64 canvas each.  A pass costs one sweep of the 8-byte canvas (read, optionally written)
 // and of the 1-byte class map, whatever the number of edges; the toggles are one atomic per crossing.
@@ -78,6 +83,35 @@ __global__ __launch_bounds__(ZTPB) void zone_toggle_kernel(const int4* __restric
     if (c < W) atomicXor(canvas + (long)r * W + c, 1ull << b);
 }
 
+// The scan, once for every kernel that turns toggles into inside masks: the inclusive prefix XOR of one chunk of ZCHUNK columns of a
+// canvas row, continued from the row's earlier chunks.  v[j] = the toggles of this thread's columns c .. c + ZVPT - 1 (0 past the row's
+// end) become the inside masks of those columns (dead columns hold the mask of the last live one: the caller drops them).  Thread run,
+// wave scan, workgroup scan through wtot (the wave totals of this chunk: the caller alternates two of them, so one barrier per chunk is
+// enough), and carry = the prefix XOR of the row's earlier chunks, the same in every thread, updated for the next chunk.  Every thread of
+// the workgroup calls it (it holds a barrier).
+__device__ __forceinline__ void zone_scan_chunk(unsigned long long (&v)[ZVPT], unsigned long long& carry, unsigned long long* wtot) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int j = 1; j < ZVPT; ++j) v[j] ^= v[j - 1];
+    unsigned long long t = v[ZVPT - 1];  // inclusive scan of the thread totals over the wave
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const unsigned long long u = __shfl_up(t, o, 64);
+        if (lane >= o) t ^= u;
+    }
+    if (lane == 63) wtot[wave] = t;
+    __syncthreads();
+    unsigned long long pre = carry ^ t ^ v[ZVPT - 1];  // XOR undoes itself: inclusive ^ own = exclusive
+#pragma unroll
+    for (int w = 0; w < ZWAVES; ++w) {
+        const unsigned long long u = wtot[w];
+        if (w < wave) pre ^= u;
+        carry ^= u;
+    }
+#pragma unroll
+    for (int j = 0; j < ZVPT; ++j) v[j] ^= pre;
+}
+
 // cls = NULL: the masks only, nothing is counted.  grid.x workgroups take rows blockIdx.x, blockIdx.x + gridDim.x, ...  LDS: tab[64][ncls + 1]
 // u32 (dynamic; a cell counts at most the H * W <= 2^31 - 1 pixels of the raster, so it cannot wrap) and the wave totals of two
 // consecutive chunks (one barrier per chunk).
@@ -88,7 +122,7 @@ __global__ __launch_bounds__(ZTPB) void zone_tally_kernel(unsigned long long* __
     unsigned* tab = reinterpret_cast<unsigned*>(smem);
     __shared__ unsigned long long wtot[2][ZWAVES];
     const int cols = ncls + 1, cells = ZBITS * cols;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
     for (int i = threadIdx.x; i < cells; i += ZTPB) tab[i] = 0u;
     __syncthreads();
     int par = 0;
@@ -109,27 +143,12 @@ __global__ __launch_bounds__(ZTPB) void zone_tally_kernel(unsigned long long* __
                     const int s = cls ? crow[c + j] : fill;
                     if (s != fill && s >= 0 && s < ncls) k[j] = s;
                 }
-                if (j) v[j] ^= v[j - 1];
             }
-            unsigned long long t = v[ZVPT - 1];  // inclusive scan of the thread totals over the wave
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const unsigned long long u = __shfl_up(t, o, 64);
-                if (lane >= o) t ^= u;
-            }
-            if (lane == 63) wtot[par][wave] = t;
-            __syncthreads();
-            unsigned long long pre = carry ^ t ^ v[ZVPT - 1];  // XOR undoes itself: inclusive ^ own = exclusive
-#pragma unroll
-            for (int w = 0; w < ZWAVES; ++w) {
-                const unsigned long long u = wtot[par][w];
-                if (w < wave) pre ^= u;
-                carry ^= u;
-            }
+            zone_scan_chunk(v, carry, wtot[par]);
 #pragma unroll
             for (int j = 0; j < ZVPT; ++j) {
                 const bool live = c + j < W;
-                const unsigned long long m = live ? v[j] ^ pre : 0ull;
+                const unsigned long long m = live ? v[j] : 0ull;
                 if (live && write_mask) row[c + j] = m;
                 if (!cls) continue;  // masks only (uniform over the grid)
                 // runs of adjacent lanes with the same (mask, class) add once, at their first lane
@@ -153,6 +172,169 @@ __global__ __launch_bounds__(ZTPB) void zone_tally_kernel(unsigned long long* __
     if (!cls) return;
     for (int i = threadIdx.x; i < cells; i += ZTPB)
         if (tab[i]) atomicAdd(counts + i, (unsigned long long)tab[i]);
+}
+
+// ---- values: per zone and band (n, T, M2, min, max) of a float32 raster -----------------------------------------------------------------
+// A partial result of the valid values of one zone and band: their number, their sum, the sum of their squared deviations from their own
+// mean t / n, and their extremes.  32 bytes; the partials in memory are arrays of it.
+struct __attribute__((aligned(16))) ZAcc {
+    double n, t, m2;
+    float lo, hi;
+};
+constexpr int ZV_MAX_BANDS = 8, ZV_MAX_WG = 512;
+static_assert(sizeof(ZAcc) == 32, "the partials are (.., 4) float64 records");
+
+__device__ __forceinline__ ZAcc zacc_empty() { return ZAcc{0.0, 0.0, 0.0, __builtin_huge_valf(), -__builtin_huge_valf()}; }
+
+// Chan, Golub and LeVeque's pairwise update, a before b.  An empty side leaves the other's bits as they are.
+__device__ __forceinline__ ZAcc zacc_merge(const ZAcc& a, const ZAcc& b) {
+    ZAcc r;
+    r.n = a.n + b.n;
+    r.t = a.t + b.t;
+    double w = 0.0;
+    if (a.n > 0.0 && b.n > 0.0) {
+        const double d = b.t / b.n - a.t / a.n;
+        w = d * d * (a.n * b.n / r.n);
+    }
+    r.m2 = a.m2 + b.m2 + w;
+    r.lo = fminf(a.lo, b.lo);
+    r.hi = fmaxf(a.hi, b.hi);
+    return r;
+}
+
+__device__ __forceinline__ ZAcc zacc_shfl_xor(const ZAcc& a, int o) {
+    return ZAcc{__shfl_xor(a.n, o, 64), __shfl_xor(a.t, o, 64), __shfl_xor(a.m2, o, 64), __shfl_xor(a.lo, o, 64), __shfl_xor(a.hi, o, 64)};
+}
+
+// The rows, chunks and scan of zone_tally_kernel; the canvas is only read.  Per chunk a wave loops over the zone bits that any of its
+// lanes is inside of (the OR of the lanes' masks: wave-uniform), band by band: every lane forms the triple of its own run (two passes
+// over at most ZVPT values), a 6-step butterfly merges the 64 of them (the lower lane is the left operand, so both lanes of a pair
+// compute the same bits), lane z keeps the result of bit z, and the lanes of the bits present then merge into the wave's own LDS
+// accumulators acc[wave][band][64], which nobody else writes.  Lane z also counts the inside pixels of bit z in a register.  At the end
+// waves 0..3 are merged in order into the workgroup's partials.  LDS (dynamic): acc, then pixw[ZWAVES][64] u32.
+__global__ __launch_bounds__(ZTPB) void zone_value_tally_kernel(const unsigned long long* __restrict__ canvas, const float* __restrict__ raster,
+                                                                ZAcc* __restrict__ partials, unsigned long long* __restrict__ pix_partials,
+                                                                int H, int W, int B, int has_nodata, float nodata) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    ZAcc* acc = reinterpret_cast<ZAcc*>(smem);
+    unsigned* pixw = reinterpret_cast<unsigned*>(acc + ZWAVES * B * ZBITS);
+    __shared__ unsigned long long wtot[2][ZWAVES];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int i = threadIdx.x; i < ZWAVES * B * ZBITS; i += ZTPB) acc[i] = zacc_empty();
+    __syncthreads();
+    ZAcc* mine_acc = acc + (long)wave * B * ZBITS;
+    const long plane = (long)H * W;
+    unsigned inside = 0;  // the inside pixels of bit `lane` this wave has met: at most H * W <= 2^31 - 1
+    int par = 0;
+    for (int r = blockIdx.x; r < H; r += gridDim.x) {
+        const unsigned long long* row = canvas + (long)r * W;
+        const float* vrow = raster + (long)r * W;
+        unsigned long long carry = 0;
+        for (long c0 = 0; c0 < W; c0 += ZCHUNK, par ^= 1) {
+            const long c = c0 + (long)threadIdx.x * ZVPT;
+            unsigned long long m[ZVPT];
+#pragma unroll
+            for (int j = 0; j < ZVPT; ++j) m[j] = c + j < W ? row[c + j] : 0ull;
+            zone_scan_chunk(m, carry, wtot[par]);  // the workgroup's only barrier in this loop: what follows is per wave
+            unsigned long long present = 0;
+#pragma unroll
+            for (int j = 0; j < ZVPT; ++j) {
+                if (c + j >= W) m[j] = 0ull;
+                present |= m[j];
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) present |= __shfl_xor(present, o, 64);
+            if (!present) continue;  // the same in every lane of the wave
+            for (unsigned long long rest = present; rest; rest &= rest - 1) {
+                const int z = __ffsll((long long)rest) - 1;
+                unsigned cnt = 0;
+#pragma unroll
+                for (int j = 0; j < ZVPT; ++j) cnt += (unsigned)__popcll(__ballot((m[j] >> z) & 1ull));
+                if (lane == z) inside += cnt;
+            }
+            for (int b = 0; b < B; ++b) {
+                float x[ZVPT];
+                bool ok[ZVPT];
+#pragma unroll
+                for (int j = 0; j < ZVPT; ++j) {
+                    x[j] = c + j < W ? vrow[b * plane + c + j] : 0.f;
+                    // finite (the exponent is not all ones) and not the no-data value
+                    ok[j] = c + j < W && (__float_as_uint(x[j]) & 0x7f800000u) != 0x7f800000u && !(has_nodata && x[j] == nodata);
+                }
+                ZAcc keep = zacc_empty();  // lane z: the wave's result of bit z
+                for (unsigned long long rest = present; rest; rest &= rest - 1) {
+                    const int z = __ffsll((long long)rest) - 1;
+                    ZAcc a = zacc_empty();
+                    bool in[ZVPT];
+#pragma unroll
+                    for (int j = 0; j < ZVPT; ++j) {
+                        in[j] = ok[j] && ((m[j] >> z) & 1ull);
+                        if (in[j]) {
+                            a.n += 1.0;
+                            a.t += (double)x[j];
+                            a.lo = fminf(a.lo, x[j]);
+                            a.hi = fmaxf(a.hi, x[j]);
+                        }
+                    }
+                    if (__ballot(a.n > 0.0) == 0ull) continue;  // no valid value of this bit in the wave: keep stays empty
+                    if (a.n > 0.0) {
+                        const double mean = a.t / a.n;
+#pragma unroll
+                        for (int j = 0; j < ZVPT; ++j) {
+                            const double d = (double)x[j] - mean;
+                            if (in[j]) a.m2 += d * d;
+                        }
+                    }
+#pragma unroll
+                    for (int o = 1; o < 64; o <<= 1) {
+                        const ZAcc other = zacc_shfl_xor(a, o);
+                        const bool upper = (lane & o) != 0;
+                        a = zacc_merge(upper ? other : a, upper ? a : other);
+                    }
+                    if (lane == z) keep = a;
+                }
+                if ((present >> lane) & 1ull) {
+                    ZAcc* slot = mine_acc + b * ZBITS + lane;
+                    *slot = zacc_merge(*slot, keep);
+                }
+            }
+        }
+    }
+    pixw[wave * ZBITS + lane] = inside;
+    __syncthreads();
+    for (int i = threadIdx.x; i < B * ZBITS; i += ZTPB) {  // i = band * 64 + bit
+        ZAcc a = acc[i];
+#pragma unroll
+        for (int w = 1; w < ZWAVES; ++w) a = zacc_merge(a, acc[w * B * ZBITS + i]);
+        partials[(long)blockIdx.x * B * ZBITS + i] = a;
+    }
+    if (threadIdx.x < ZBITS) {
+        unsigned long long total = 0;
+#pragma unroll
+        for (int w = 0; w < ZWAVES; ++w) total += pixw[w * ZBITS + threadIdx.x];
+        pix_partials[(long)blockIdx.x * ZBITS + threadIdx.x] = total;
+    }
+}
+
+// One workgroup per band, one thread per zone bit: the G partials merged in workgroup order.
+__global__ __launch_bounds__(ZBITS) void zone_value_reduce_kernel(const ZAcc* __restrict__ partials,
+                                                                  const unsigned long long* __restrict__ pix_partials,
+                                                                  long long* __restrict__ valid, double* __restrict__ stats,
+                                                                  long long* __restrict__ pixels, int G, int B) {
+    const int z = threadIdx.x, b = blockIdx.x;
+    ZAcc a = zacc_empty();
+    for (int g = 0; g < G; ++g) a = zacc_merge(a, partials[((long)g * B + b) * ZBITS + z]);
+    valid[z * B + b] = (long long)a.n;
+    double* out = stats + ((long)z * B + b) * 4;
+    out[0] = a.n > 0.0 ? a.t / a.n : 0.0;
+    out[1] = a.m2;
+    out[2] = (double)a.lo;
+    out[3] = (double)a.hi;
+    if (b == 0 && pixels) {
+        unsigned long long total = 0;
+        for (int g = 0; g < G; ++g) total += pix_partials[(long)g * ZBITS + z];
+        pixels[z] = (long long)total;
+    }
 }
 
 }  // namespace
@@ -198,6 +380,34 @@ int ig_zone_tally(unsigned long long* canvas, const signed char* cls, unsigned l
     IG_REQUIRE(((uintptr_t)canvas & 7) == 0 && ((uintptr_t)counts & 7) == 0, "ig_zone_tally: canvas and counts must be 8-byte aligned");
     return ig_launch<zone_tally_kernel>("ig_zone_tally", dim3((unsigned)(H < MAX_WG ? H : MAX_WG)), dim3(ZTPB), ZBITS * (ncls + 1) * 4,
                                         ST(stream), canvas, cls, counts, H, W, ncls, fill, write_mask);
+}
+
+int ig_zone_value_grid(int H) { return H < 0 ? 0 : H < ZV_MAX_WG ? H : ZV_MAX_WG; }
+
+int ig_zone_value_tally(const unsigned long long* canvas, const float* raster, double* partials, unsigned long long* pix_partials, int H,
+                        int W, int B, int has_nodata, float nodata, void* stream) {
+    IG_REQUIRE(B >= 0 && B <= ZV_MAX_BANDS, "ig_zone_value_tally: 0 <= B <= %d bands per call (got %d)", ZV_MAX_BANDS, B);
+    IG_REQUIRE_RASTER("ig_zone_value_tally");
+    if ((long)H * W == 0 || B == 0) return IG_OK;
+    IG_REQUIRE(canvas && raster && partials && pix_partials, "ig_zone_value_tally: null pointer");
+    IG_REQUIRE(((uintptr_t)canvas & 7) == 0 && ((uintptr_t)partials & 15) == 0 && ((uintptr_t)pix_partials & 7) == 0,
+               "ig_zone_value_tally: canvas and pix_partials must be 8-byte aligned, partials 16-byte");
+    IG_REQUIRE(((uintptr_t)raster & 3) == 0, "ig_zone_value_tally: raster must be 4-byte aligned");
+    return ig_launch<zone_value_tally_kernel>("ig_zone_value_tally", dim3((unsigned)ig_zone_value_grid(H)), dim3(ZTPB),
+                                              ZWAVES * ZBITS * (B * (int)sizeof(ZAcc) + 4), ST(stream), canvas, raster,
+                                              reinterpret_cast<ZAcc*>(partials), pix_partials, H, W, B, has_nodata, nodata);
+}
+
+int ig_zone_value_reduce(const double* partials, const unsigned long long* pix_partials, long long* valid, double* stats,
+                         long long* pixels, int G, int B, void* stream) {
+    IG_REQUIRE(B >= 0 && B <= ZV_MAX_BANDS, "ig_zone_value_reduce: 0 <= B <= %d bands per call (got %d)", ZV_MAX_BANDS, B);
+    IG_REQUIRE(G >= 0 && G <= ZV_MAX_WG, "ig_zone_value_reduce: 0 <= G <= %d workgroups (got %d)", ZV_MAX_WG, G);
+    if (G == 0 || B == 0) return IG_OK;
+    IG_REQUIRE(partials && pix_partials && valid && stats, "ig_zone_value_reduce: null pointer");
+    IG_REQUIRE((((uintptr_t)pix_partials | (uintptr_t)valid | (uintptr_t)stats | (uintptr_t)pixels) & 7) == 0 && ((uintptr_t)partials & 15) == 0,
+               "ig_zone_value_reduce: every pointer must be 8-byte aligned, partials 16-byte");
+    return ig_launch<zone_value_reduce_kernel>("ig_zone_value_reduce", dim3((unsigned)B), dim3(ZBITS), 0, ST(stream),
+                                               reinterpret_cast<const ZAcc*>(partials), pix_partials, valid, stats, pixels, G, B);
 }
 
 }  // extern "C"

@@ -192,7 +192,15 @@ DEFAULTS: Dict[str, Any] = {'root_dir': None,
  # min_foreground labelled pixels is dropped; device: None = the device when there is one, host, cuda
  'polygon_labels': {'features': None, 'output_directory': None, 'like': None, 'crs': None, 'src_crs': 4326, 'spatial_resolution': 30.0,
                     'chip_size': 256, 'task_type': 'seg', 'value_property': None, 'burn_value': None, 'class_map': None, 'background': None,
-                    'labelled_area': None, 'date': None, 'date_property': None, 'mgrs_tile_id': None, 'min_foreground': 1, 'device': None}}
+                    'labelled_area': None, 'date': None, 'date_property': None, 'mgrs_tile_id': None, 'min_foreground': 1, 'device': None},
+ # mode=zonal_stats (not in the reference; zonal.py): per zone and band the count, mean, std, min, max and sum of the GeoTIFF `raster`
+ # (any sample type, float32 on the device: a prediction, probability or uncertainty raster, a Sentinel-1 dB scene, a composite) over the
+ # Polygon / MultiPolygon features of the GeoJSON `zones`, written as the CSV `output` (None: zonevalues_<raster base name>.csv next to
+ # the raster).  zone_id_property: the property that names a zone (None: its index); bands: a list of band indices (None: all); nodata:
+ # the value that marks missing samples (None: the file's own no-data tag; NaN and Inf are always missing); zones_crs: the EPSG code of
+ # the zones' coordinates (None: those of the raster)
+ 'zonal_stats': {'raster': None, 'zones': None, 'zone_id_property': None, 'output': None, 'bands': None, 'nodata': None,
+                 'zones_crs': None}}
 
 PRESETS: Dict[str, Dict[str, Any]] = {'sen1floods11': {'train': {'batch_size': 16, 'class_weights': [1, 3], 'ignore_index': -1},
                   'model': {'model_name': 'prithvi_eo_v1_100'},

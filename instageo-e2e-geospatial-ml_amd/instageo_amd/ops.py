@@ -1053,6 +1053,43 @@ def zone_tally(canvas, classmap, counts, ncls: int = 2, fill: int = -1, write_ma
           int(ncls), int(fill), int(bool(write_mask)), _stream())
 
 
+ZONE_VALUE_BANDS = 8  # bands per launch of ig_zone_value_tally (its LDS accumulators: 32 bytes per wave, zone bit and band)
+
+
+def zone_value_tally(canvas, raster, nodata: Optional[float] = None):
+    """The values of ``raster`` (B, H, W) float32, 1 <= B <= ``ZONE_VALUE_BANDS``, under the inside masks of the toggles in ``canvas``
+    (H, W) int64, which is read and left as it is -> (pixels (64,) int64: the inside pixels per zone bit; valid (64, B) int64: those whose
+    value is finite and not ``nodata``; stats (64, B, 4) float64 {mean, M2 = sum of squared deviations from the mean, min, max} of the
+    valid values; where valid is 0: 0, 0, +inf, -inf).  Merged (n, sum, M2) triples in a fixed order (include/instageo_hip.h): the same
+    bits from run to run, and for a band in any group of bands."""
+    if canvas.dtype != torch.int64 or canvas.dim() != 2:
+        raise ValueError(f"zone_value_tally: canvas must be (H, W) int64 (got {tuple(canvas.shape)} {canvas.dtype})")
+    if raster.dtype != torch.float32 or raster.dim() != 3 or tuple(raster.shape[1:]) != tuple(canvas.shape):
+        raise ValueError(f"zone_value_tally: raster must be (B, H, W) float32 on the canvas's {tuple(canvas.shape)} pixels "
+                         f"(got {tuple(raster.shape)} {raster.dtype})")
+    B, H, W = raster.shape
+    if not 1 <= B <= ZONE_VALUE_BANDS:
+        raise ValueError(f"zone_value_tally: 1 <= bands <= {ZONE_VALUE_BANDS} per call (got {B}); zonal.zone_values loops over groups")
+    if not (canvas.is_contiguous() and raster.is_contiguous()):
+        raise ValueError("zone_value_tally: canvas and raster must be contiguous")
+    dev = raster.device
+    pixels = torch.zeros(ZONE_BITS, dtype=torch.int64, device=dev)
+    valid = torch.zeros((ZONE_BITS, B), dtype=torch.int64, device=dev)
+    stats = torch.zeros((ZONE_BITS, B, 4), dtype=torch.float64, device=dev)
+    if H * W == 0:
+        stats[..., 2], stats[..., 3] = float("inf"), float("-inf")
+        return pixels, valid, stats
+    G = int(_lib.load().ig_zone_value_grid(H))
+    partials = torch.empty((G, B, ZONE_BITS, 4), dtype=torch.float64, device=dev)  # every cell is written
+    pix_partials = torch.empty((G, ZONE_BITS), dtype=torch.int64, device=dev)
+    # HBM bytes: the canvas and the bands read once
+    _call("ig_zone_value_tally", float(H) * W * (8 + 4 * B), _p(canvas), _p(raster), _p(partials), _p(pix_partials), H, W, B,
+          int(nodata is not None), float(0.0 if nodata is None else nodata), _stream())
+    _call("ig_zone_value_reduce", float(G) * ZONE_BITS * (32 * B + 8), _p(partials), _p(pix_partials), _p(valid), _p(stats), _p(pixels), G, B,
+          _stream())
+    return pixels, valid, stats
+
+
 def burn_resolve(canvas, table, out, r0: int, c0: int, written=None) -> None:
     """One pass of the polygon burn (include/instageo_hip.h): ``canvas`` (Hp, Wp) int64 holds the toggles of up to 64 features
     (:func:`zone_toggle`); where the prefix XOR along a row is not zero, ``out[r0 + r, c0 + c] = table[highest set bit]``; other pixels

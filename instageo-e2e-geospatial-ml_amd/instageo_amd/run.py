@@ -61,7 +61,8 @@ PREP_MODES = {"create_chips": "chips",  # HLS tiles + points -> chips, label map
               "create_composite": "composite",  # the HLS scenes near each step's date -> one cloud-free composite scene per step
               "filter_s1": "s1_filter",  # Sentinel-1 RTC band files -> speckle-filtered (and dB) band files under the same names
               "clean_chips": "clean",  # drop no-data chips, buffer / limit the label maps of a chip dataset
-              "create_polygon_labels": "polygon_labels"}  # a GeoJSON of polygons -> label rasters + records.csv
+              "create_polygon_labels": "polygon_labels",  # a GeoJSON of polygons -> label rasters + records.csv
+              "zonal_stats": "zonal"}  # a float raster + a GeoJSON of zones -> per-zone count, mean, std, min, max, sum as CSV
 
 
 def get_device() -> str:

@@ -9,8 +9,14 @@ cross its row's centre line at or left of its centre (even-odd on pixel centres:
 inequalities that decide every tie: ``include/instageo_hip.h``).  Zones are independent: a pixel inside several zones counts in each
 of them, as rasterstats does.  Everything on the device is integer and unique: two runs give the same bits.
 
-Out of scope: per-zone means of the probabilities, ``all_touched``, rotated or sheared geotransforms, one table merged across chips
-or tiles, zone rasters written as TIFF.
+Values.  The same masks also summarise float32 rasters (regression predictions, probabilities, uncertainty, Sentinel-1 dB scenes,
+composites): :func:`zone_values` gives per zone and band the count, sum, mean, population std, min and max of the values that are finite
+and not the no-data value, and ``mode=zonal_stats`` (:func:`run_from_config`) does it from a GeoTIFF and a GeoJSON to a CSV.  The
+variance comes from merged (n, sum, M2) triples in a fixed order, float64 (``include/instageo_hip.h``): no sum of squares, no atomics,
+the same bits from run to run.
+
+Out of scope: percentiles and the median, ``all_touched``, rotated or sheared geotransforms, one table merged across chips or tiles,
+zone rasters written as TIFF.
 """
 from __future__ import annotations
 
@@ -22,7 +28,8 @@ from typing import Any, Dict, List, NamedTuple, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import ops
+from . import crs as crsmod
+from . import ops, prep, tiff
 from .postprocess import georeference
 
 Q = 256  # fixed-point units per pixel
@@ -220,3 +227,198 @@ def zone_table(classmap: torch.Tensor, zones: Sequence[Zone], ncls: int, fill: i
     (ids, counts) for :func:`write_zone_csv`."""
     edges, edge_zone = zones_to_pixels(zones, profile)
     return [z.id for z in zones], zone_counts(classmap, edges, edge_zone, len(zones), ncls, fill)
+
+
+# ---- values: per-zone statistics of float rasters ---------------------------------------------------------------------------------------------
+class ZoneValues(NamedTuple):
+    pixels: np.ndarray  # (Z,) int64: all inside pixels of the zone
+    valid: np.ndarray  # (Z, B) int64: those whose value is finite and not the no-data value
+    sum: np.ndarray  # (Z, B) float64 each; NaN where valid is 0
+    mean: np.ndarray
+    std: np.ndarray  # population standard deviation, sqrt(M2 / valid)
+    min: np.ndarray
+    max: np.ndarray
+
+
+def _check_nodata(nodata) -> Optional[float]:
+    if nodata is None:
+        return None
+    if isinstance(nodata, bool) or not isinstance(nodata, (int, float, np.integer, np.floating)):
+        raise ValueError(f"nodata must be None or a number (got {nodata!r})")
+    nd = float(np.float32(nodata))
+    return None if nd != nd else nd  # NaN is invalid anyway
+
+
+def zone_values(raster: torch.Tensor, edges: np.ndarray, edge_zone: np.ndarray, Z: int, nodata: Optional[float] = None) -> ZoneValues:
+    """Per zone and band the count, sum, mean, population std, min and max of one (H, W) or (B, H, W) float32 raster on the device ->
+    :class:`ZoneValues`.  A value is valid when it is finite and differs from ``nodata`` (compared as float32); where a zone has no valid
+    value its statistics are NaN.  ``edges`` / ``edge_zone`` are those of :func:`zones_to_pixels`.  One canvas per pass of 64 zones serves
+    every group of ``ops.ZONE_VALUE_BANDS`` bands; the variance comes from merged (n, sum, M2) triples in a fixed order
+    (include/instageo_hip.h): two runs give the same bits, and a band gives the same bits whatever other bands go with it."""
+    if raster.dtype != torch.float32 or raster.dim() not in (2, 3):
+        raise ValueError(f"zone_values takes one (H, W) or (B, H, W) float32 raster (got {tuple(raster.shape)} {raster.dtype})")
+    r = (raster[None] if raster.dim() == 2 else raster).contiguous()
+    B, H, W = r.shape
+    if B < 1:
+        raise ValueError("zone_values: the raster has no band")
+    nd, Z = _check_nodata(nodata), int(Z)
+    pixels = np.zeros(Z, dtype=np.int64)
+    valid = np.zeros((Z, B), dtype=np.int64)
+    stats = np.zeros((Z, B, 4), dtype=np.float64)  # mean, M2, min, max
+    for p, canvas in _passes(edges, edge_zone, Z, H, W, r.device):
+        lo = p * ops.ZONE_BITS
+        n = min(ops.ZONE_BITS, Z - lo)
+        for b0 in range(0, B, ops.ZONE_VALUE_BANDS):
+            pix, val, st = ops.zone_value_tally(canvas, r[b0:b0 + ops.ZONE_VALUE_BANDS], nd)
+            if b0 == 0:
+                pixels[lo:lo + n] = pix[:n].cpu().numpy()
+            valid[lo:lo + n, b0:b0 + val.shape[1]] = val[:n].cpu().numpy()
+            stats[lo:lo + n, b0:b0 + val.shape[1]] = st[:n].cpu().numpy()
+    has = valid > 0
+    nan = np.full((Z, B), np.nan)
+    mean = np.where(has, stats[..., 0], nan)
+    std = np.sqrt(np.divide(stats[..., 1], valid, out=nan.copy(), where=has))
+    return ZoneValues(pixels, valid, mean * valid, mean, std, np.where(has, stats[..., 2], nan), np.where(has, stats[..., 3], nan))
+
+
+def zone_value_table(raster: torch.Tensor, zones: Sequence[Zone], nodata: Optional[float] = None,
+                     profile: Optional[Dict[str, Any]] = None) -> Tuple[List[Any], ZoneValues]:
+    """``zones`` (:func:`read_zones`; map coordinates when ``profile`` is georeferenced) on ``raster`` -> (ids, values) for
+    :func:`write_zone_values_csv`: what :func:`zone_table` is to a class map."""
+    edges, edge_zone = zones_to_pixels(zones, profile)
+    return [z.id for z in zones], zone_values(raster, edges, edge_zone, len(zones), nodata)
+
+
+VALUE_COLUMNS = ("valid", "mean", "std", "min", "max", "sum")  # per band, in this order
+
+
+def write_zone_values_csv(path: str, ids: Sequence[Any], values: ZoneValues, band_names: Optional[Sequence[Any]] = None,
+                          profile: Optional[Dict[str, Any]] = None) -> str:
+    """Write one row per zone: ``zone`` (its index), ``id``, ``pixels`` (all its inside pixels), then per band ``valid_<b>``, ``mean_<b>``,
+    ``std_<b>``, ``min_<b>``, ``max_<b>``, ``sum_<b>`` (``<b>`` from ``band_names``, else the band's index) and, with a georeferenced
+    ``profile``, ``area_map`` = pixels * scale_x * scale_y in squared map units.  Floats are written with ``repr`` (they read back
+    exactly); the statistics of a zone without a valid value are empty cells."""
+    valid = np.asarray(values.valid)
+    if valid.ndim != 2 or valid.shape[0] != len(ids) or np.asarray(values.pixels).shape != (len(ids),):
+        raise ValueError("values must hold (len(ids),) pixels and (len(ids), bands) statistics")
+    B = valid.shape[1]
+    names = [str(b) for b in (range(B) if band_names is None else band_names)]
+    if len(names) != B or len(set(names)) != B:
+        raise ValueError(f"band_names must give {B} distinct names (got {list(band_names)!r})")
+    geo = georeference(profile)
+    cols = ["zone", "id", "pixels"] + [f"{k}_{b}" for b in names for k in VALUE_COLUMNS] + (["area_map"] if geo else [])
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(cols)
+        for z, zid in enumerate(ids):
+            out = [z, zid, int(values.pixels[z])]
+            for b in range(B):
+                n = int(valid[z, b])
+                out.append(n)
+                out += [repr(float(getattr(values, k)[z, b])) if n else "" for k in VALUE_COLUMNS[1:]]
+            if geo:
+                out.append(repr(float(int(values.pixels[z]) * geo[0] * geo[1])))
+            w.writerow(out)
+    return path
+
+
+# ---- mode=zonal_stats -------------------------------------------------------------------------------------------------------------------------
+CONFIG_KEYS = ("raster", "zones", "zone_id_property", "output", "bands", "nodata", "zones_crs")
+
+
+def zonal_stats_options(cfg: Dict[str, Any]) -> Dict[str, Any]:
+    """The ``zonal_stats.*`` keys checked -> {raster, zones (a list of :class:`Zone` in the raster's coordinate system), bands, nodata,
+    output, profile}.  An unknown key, a bad value, a missing file, a band the file does not have, a feature that is no (Multi)Polygon,
+    or ``zones_crs`` with a raster that carries no coordinate system raises ValueError naming the key.  Reads the raster's header and the
+    GeoJSON; touches no device."""
+    c = prep.Section(cfg, "zonal_stats", CONFIG_KEYS)
+    raster, zfile = c.text("raster"), c.text("zones")
+    for key, path in (("raster", raster), ("zones", zfile)):
+        if path is None:
+            raise ValueError(f"mode=zonal_stats needs zonal_stats.{key}")
+        if not os.path.isfile(path):
+            raise c.bad(key, "is not a file", path)
+    try:
+        profile = tiff.read_profile(raster)
+    except tiff.TiffError as e:
+        raise ValueError(f"zonal_stats.raster: {e}") from None
+    count = int(profile["count"])
+    bands = c.get("bands")
+    if bands is None:
+        bands = list(range(count))
+    elif not isinstance(bands, (list, tuple)) or not bands or not all(prep.is_int(b) for b in bands) or len(set(bands)) != len(bands):
+        raise c.bad("bands", "must be None or a list of distinct band indices", bands)
+    elif not all(0 <= b < count for b in bands):
+        raise c.bad("bands", f"names a band outside [0, {count}): {raster} has {count} band{'s' if count != 1 else ''}", bands)
+    nodata = c.get("nodata")
+    try:
+        nodata = _check_nodata(profile.get("nodata") if nodata is None else nodata)
+    except ValueError:
+        raise c.bad("nodata", "must be None (the file's own no-data tag) or a number", nodata) from None
+    try:
+        zones = read_zones(zfile, c.text("zone_id_property"))
+    except ValueError as e:
+        raise ValueError(f"zonal_stats.zones: {e}") from None
+    epsg = c.get("zones_crs")
+    if epsg is not None:
+        if not prep.is_int(epsg):
+            raise c.bad("zones_crs", "must be an EPSG code", epsg)
+        try:
+            crsmod.from_epsg(epsg)
+        except ValueError as e:
+            raise ValueError(f"zonal_stats.zones_crs: {e}") from None
+        try:
+            if georeference(profile) is None:
+                raise ValueError("no pixel scale and tiepoint")
+            dst = crsmod.from_profile(profile)
+        except ValueError as e:
+            raise ValueError(f"zonal_stats.zones_crs = {epsg} needs a raster with a coordinate system ({raster}: {e})") from None
+        src, moved = crsmod.from_epsg(epsg), []
+        for z in zones:
+            rings = []
+            for ring in z.rings:
+                x, y = crsmod.transform(src, dst, ring[:, 0], ring[:, 1])
+                rings.append(np.stack([x, y], axis=1))
+            moved.append(Zone(z.id, rings))
+        zones = moved
+    try:
+        zones_to_pixels(zones, profile)  # a vertex beyond the fixed-point range (or outside the projection's domain) stops here
+    except ValueError as e:
+        raise ValueError(f"zonal_stats.zones: {e}") from None
+    output = c.text("output")
+    if output is None:
+        output = os.path.join(os.path.dirname(raster), f"zonevalues_{os.path.splitext(os.path.basename(raster))[0]}.csv")
+    return dict(raster=raster, zones=zones, bands=[int(b) for b in bands], nodata=nodata, output=output, profile=profile)
+
+
+def _to_float32(a: np.ndarray, device) -> torch.Tensor:
+    """Samples of any dtype :mod:`tiff` reads -> float32 on the device.  The conversion runs there; unsigned 16 / 32 / 64-bit samples,
+    which torch does not convert, are widened on the host first (without loss up to 32 bits)."""
+    if a.dtype.kind == "u" and a.dtype.itemsize > 1:
+        a = a.astype(np.int32 if a.dtype.itemsize == 2 else np.int64 if a.dtype.itemsize == 4 else np.float64)
+    return torch.from_numpy(np.ascontiguousarray(a)).to(device).to(torch.float32)
+
+
+def run_from_config(cfg: Dict[str, Any], device: Optional[str] = None) -> int:
+    """``mode=zonal_stats``: the per-zone statistics of the GeoTIFF ``zonal_stats.raster`` over the polygons of ``zonal_stats.zones``,
+    written as the CSV of :func:`write_zone_values_csv`; prints one JSON line (zones, bands, zones without a valid pixel, the output
+    path).  Every option is checked before the device is touched; there is no host path."""
+    kw = zonal_stats_options(cfg)
+    if device is None:
+        raise RuntimeError("mode=zonal_stats runs on a HIP device and there is none (the tally has no host path)")
+    a, profile = tiff.read(kw["raster"], kw["bands"])
+    ids, values = zone_value_table(_to_float32(a, device), kw["zones"], kw["nodata"], profile)
+    write_zone_values_csv(kw["output"], ids, values, kw["bands"], profile)
+    print(json.dumps({"zonal_stats": {"zones": len(ids), "bands": len(kw["bands"]), "empty_zones": int((values.valid.sum(axis=1) == 0).sum()),
+                                      "output": kw["output"]}}))
+    return 0
+
+
+def main(argv: Optional[List[str]] = None) -> int:
+    """``python -m instageo_amd.zonal zonal_stats.raster=prediction.tif zonal_stats.zones=districts.geojson ...``: mode=zonal_stats
+    without ``run.py``."""
+    return prep.run_mode_cli("zonal_stats", run_from_config, argv)
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

@@ -1,0 +1,282 @@
+"""Zonal statistics of float rasters, host side (no GPU): the reference (tests/zonal_values_reference.py) on numbers worked by hand, the
+CSV writer, the option checks of mode=zonal_stats, the config keys, the header's statement of the validity rule, and the argument checks
+of the two HIP entry points and of ops.zone_value_tally."""
+import csv
+import ctypes
+import json
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import zonal_reference as ZR
+import zonal_values_reference as VR
+from instageo_amd import tiff, zonal
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "instageo-e2e-geospatial-ml_amd")
+NAMES = ("ig_zone_value_tally", "ig_zone_value_reduce")
+GEO_TAGS = {33550: (12, (30.0, 20.0, 0.0)), 33922: (12, (0.0, 0.0, 0.0, 399960.0, 4500000.0, 0.0))}
+UTM_KEYS = {34735: (3, (1, 1, 0, 3, 1024, 0, 1, 1, 1025, 0, 1, 1, 3072, 0, 1, 32613))}
+
+
+@pytest.fixture(scope="module")
+def built_lib():
+    import subprocess
+
+    from instageo_amd import _lib
+
+    if not os.path.exists(_lib.LIB_PATH):
+        subprocess.run(["make", "-C", os.path.join(PKG, "csrc"), "-j4"], check=True)
+    return _lib
+
+
+def _square(x0, y0, x1, y1):
+    return {"type": "Polygon", "coordinates": [[[x0, y0], [x1, y0], [x1, y1], [x0, y1], [x0, y0]]]}
+
+
+def _geojson(path, geometries, **props):
+    feats = [{"type": "Feature", "properties": dict(props, name=f"z{i}"), "geometry": g} for i, g in enumerate(geometries)]
+    with open(path, "w") as f:
+        json.dump({"type": "FeatureCollection", "features": feats}, f)
+    return str(path)
+
+
+# ---- reference ----------------------------------------------------------------------------------------------------------------------------
+def test_reference_gives_the_numbers_worked_by_hand():
+    raster, masks, nodata, want, _ = VR.hand_case()
+    assert masks.sum() == 12 and not masks[0, 2:4, 2:4].any()
+    got = VR.ref_values(raster, masks, nodata)
+    assert got.pixels.tolist() == want["pixels"] and got.valid.tolist() == want["valid"]
+    for k in ("sum", "min", "max"):
+        assert getattr(got, k).tolist() == want[k], k
+    assert got.mean[0, 0] == 17.5 and got.std[0, 0] == np.sqrt(703.0 / 12.0)
+    assert got.mean[0, 1] == pytest.approx(want["mean"][0][1], rel=1e-15) and got.std[0, 1] == pytest.approx(want["std"][0][1], rel=1e-15)
+    # without the no-data value the 16 of band 1 is back (-9999 is then a value like any other); NaN and Inf never are
+    again = VR.ref_values(raster, masks, None)
+    assert again.valid.tolist() == [[12, 10]] and again.min[0, 1] == VR.NODATA
+    # a zone without a valid pixel: NaN statistics, its pixels still counted
+    raster[1][masks[0]] = np.nan
+    empty = VR.ref_values(raster, masks, nodata)
+    assert empty.pixels.tolist() == [12] and empty.valid.tolist() == [[12, 0]]
+    assert all(np.isnan(getattr(empty, k)[0, 1]) for k in ("sum", "mean", "std", "min", "max"))
+
+
+def test_test_rasters_hold_all_three_kinds_of_invalid_pixels():
+    for name, (H, W, _) in ZR.cases().items():
+        r = VR.integer_raster(len(name), 3, H, W)
+        assert r.dtype == np.float32 and r.shape == (3, H, W)
+        ok = np.isfinite(r) & (r != VR.NODATA)
+        assert (r[ok] == np.rint(r[ok])).all() and (np.abs(r[ok]) <= 1000).all()
+        if H * W >= 6:
+            assert all(np.isnan(b).any() and np.isposinf(b).any() and (b == VR.NODATA).any() for b in r), name
+        if H * W > 600:
+            assert 0.1 < 1 - ok.mean() < 0.25
+    off = VR.offset_raster(1, 1, 37, 67)
+    assert (off.astype(np.float64) - 2.0**23).min() == -3 and (off.astype(np.float64) - 2.0**23).max() == 3
+
+
+# ---- the CSV ------------------------------------------------------------------------------------------------------------------------------
+def _values():
+    nan = np.nan
+    return zonal.ZoneValues(pixels=np.array([12, 5, 0]), valid=np.array([[12, 9], [5, 0], [0, 0]]),
+                            sum=np.array([[210.0, 159.0], [0.1 + 0.2, nan], [nan, nan]]),
+                            mean=np.array([[17.5, 159.0 / 9.0], [(0.1 + 0.2) / 5, nan], [nan, nan]]),
+                            std=np.array([[np.sqrt(703.0 / 12.0), 1 / 3], [1e-300, nan], [nan, nan]]),
+                            min=np.array([[7.0, 8.0], [-1e30, nan], [nan, nan]]), max=np.array([[28.0, 27.0], [1e30, nan], [nan, nan]]))
+
+
+def test_csv_columns_repr_round_trip_empty_cells_and_area(tmp_path):
+    v = _values()
+    path = zonal.write_zone_values_csv(str(tmp_path / "v.csv"), ["a", "b", 7], v)
+    rows = list(csv.reader(open(path)))
+    per_band = ["valid", "mean", "std", "min", "max", "sum"]
+    assert rows[0] == ["zone", "id", "pixels"] + [f"{k}_{b}" for b in (0, 1) for k in per_band]
+    assert len(rows) == 4 and [r[:3] for r in rows[1:]] == [["0", "a", "12"], ["1", "b", "5"], ["2", "7", "0"]]
+    recs = list(csv.DictReader(open(path)))
+    for z, rec in enumerate(recs):
+        for b in (0, 1):
+            assert int(rec[f"valid_{b}"]) == v.valid[z, b]
+            for k in per_band[1:]:
+                cell = rec[f"{k}_{b}"]
+                if v.valid[z, b]:
+                    assert float(cell) == getattr(v, k)[z, b] and cell == repr(float(getattr(v, k)[z, b]))  # reads back exactly
+                else:
+                    assert cell == ""  # a zone without a valid pixel: empty cells, not "nan"
+    assert recs[1]["sum_0"] == "0.30000000000000004"
+    # band names, and the area column of a georeferenced profile: pixels * 30 * 20
+    path = zonal.write_zone_values_csv(str(tmp_path / "g.csv"), ["a", "b", 7], v, band_names=["vv", "vh"], profile={"tags": GEO_TAGS})
+    rows = list(csv.reader(open(path)))
+    assert rows[0] == ["zone", "id", "pixels"] + [f"{k}_{b}" for b in ("vv", "vh") for k in per_band] + ["area_map"]
+    assert [r[-1] for r in rows[1:]] == ["7200.0", "3000.0", "0.0"]
+    with pytest.raises(ValueError, match="band_names"):
+        zonal.write_zone_values_csv(str(tmp_path / "x.csv"), ["a", "b", 7], v, band_names=["only"])
+    with pytest.raises(ValueError, match="values must hold"):
+        zonal.write_zone_values_csv(str(tmp_path / "x.csv"), ["a"], v)
+
+
+# ---- mode=zonal_stats: the options ------------------------------------------------------------------------------------------------------------
+@pytest.fixture()
+def files(tmp_path):
+    tiff.write(str(tmp_path / "r.tif"), np.zeros((2, 8, 10), dtype=np.float32), {"tags": {**GEO_TAGS, **UTM_KEYS}, "nodata": -9999.0})
+    tiff.write(str(tmp_path / "bare.tif"), np.zeros((1, 8, 10), dtype=np.int16))
+    zones = _geojson(tmp_path / "z.geojson", [_square(399990, 4499900, 400200, 4499990), _square(0, 0, 1, 1)])
+    return str(tmp_path / "r.tif"), str(tmp_path / "bare.tif"), zones
+
+
+def _cfg(**keys):
+    return {"mode": "zonal_stats", "zonal_stats": keys}
+
+
+def test_options_are_checked_before_a_device_is_touched(files, tmp_path, monkeypatch):
+    raster, bare, zones = files
+    from instageo_amd import ops
+
+    def boom(*a, **k):
+        raise AssertionError("an option check reached the device")
+
+    for fn in ("zone_edge_rows", "zone_toggle", "zone_value_tally"):
+        monkeypatch.setattr(ops, fn, boom)
+    o = zonal.zonal_stats_options(_cfg(raster=raster, zones=zones))
+    assert o["bands"] == [0, 1] and o["nodata"] == -9999.0 and o["output"] == str(tmp_path / "zonevalues_r.csv") and len(o["zones"]) == 2
+    assert [z.id for z in o["zones"]] == [0, 1]
+    o = zonal.zonal_stats_options(_cfg(raster=raster, zones=zones, bands=[1], nodata=0, output="out.csv", zone_id_property="name"))
+    assert o["bands"] == [1] and o["nodata"] == 0.0 and o["output"] == "out.csv" and [z.id for z in o["zones"]] == ["z0", "z1"]
+    pixel_zones = _geojson(tmp_path / "px.geojson", [_square(1, 1, 5, 5)])  # a raster without georeferencing: lattice coordinates
+    assert zonal.zonal_stats_options(_cfg(raster=bare, zones=pixel_zones))["nodata"] is None  # no tag, no key: only NaN and Inf are missing
+    # zones in another coordinate system go through the projection: a square in degrees lands near the UTM 13 raster's origin
+    o = zonal.zonal_stats_options(_cfg(raster=raster, zones=_geojson(tmp_path / "ll.geojson", [_square(-106.2, 40.6, -106.1, 40.7)]), zones_crs=4326))
+    xy = o["zones"][0].rings[0]
+    assert xy.shape == (4, 2) and 390000 < xy[:, 0].min() < 410000 and 4490000 < xy[:, 1].min() < 4510000
+
+    def bad(match, **keys):
+        with pytest.raises(ValueError, match=match):
+            zonal.run_from_config(_cfg(**dict(dict(raster=raster, zones=zones), **keys)), "cuda")
+
+    bad(r"unknown zonal_stats keys \['band'\]", band=[0])
+    bad(r"needs zonal_stats\.raster", raster=None)
+    bad(r"needs zonal_stats\.zones", zones=None)
+    bad(r"zonal_stats\.raster is not a file", raster=str(tmp_path / "missing.tif"))
+    bad(r"zonal_stats\.zones is not a file", zones=str(tmp_path / "missing.geojson"))
+    bad(r"zonal_stats\.raster: .*not a TIFF", raster=zones)
+    bad(r"zonal_stats\.bands names a band outside \[0, 2\)", bands=[0, 2])
+    bad(r"zonal_stats\.bands names a band outside", bands=[-1])
+    bad(r"zonal_stats\.bands must be None or a list of distinct band indices", bands=[0, 0])
+    bad(r"zonal_stats\.bands must be None or a list", bands="0")
+    bad(r"zonal_stats\.bands must be None or a list", bands=[])
+    bad(r"zonal_stats\.nodata must be None", nodata="x")
+    bad(r"zonal_stats\.nodata must be None", nodata=True)
+    bad(r"zonal_stats\.zones: .*feature 1 .*'LineString'", zones=_geojson(tmp_path / "l.geojson", [_square(0, 0, 1, 1), {"type": "LineString", "coordinates": [[0, 0], [1, 1]]}]))
+    bad(r"zonal_stats\.zones: .*no property 'district'", zone_id_property="district")
+    bad(r"zonal_stats\.zones_crs must be an EPSG code", zones_crs="utm")
+    bad(r"zonal_stats\.zones_crs: EPSG:2154", zones_crs=2154)
+    bad(r"zonal_stats\.zones_crs = 4326 needs a raster with a coordinate system", raster=bare, zones=pixel_zones, zones_crs=4326)
+    bad(r"zonal_stats\.zones: zone 0 .*2\^29", zones=_geojson(tmp_path / "far.geojson", [_square(0, 0, 1e12, 1e12)]))
+    # the options in order, and no device: an error of its own, after every check
+    with pytest.raises(RuntimeError, match="HIP device"):
+        zonal.run_from_config(_cfg(raster=raster, zones=zones), None)
+    assert not os.path.exists(tmp_path / "zonevalues_r.csv")
+
+
+def test_mode_and_defaults_are_wired():
+    from instageo_amd import config, run
+
+    assert run.PREP_MODES["zonal_stats"] == "zonal"
+    assert set(config.DEFAULTS["zonal_stats"]) == {"raster", "zones", "zone_id_property", "output", "bands", "nodata", "zones_crs"}
+    assert set(config.DEFAULTS["zonal_stats"]) == set(zonal.CONFIG_KEYS) and all(v is None for v in config.DEFAULTS["zonal_stats"].values())
+    cfg = config.load_config("config", ["mode=zonal_stats", "zonal_stats.raster=a.tif", "zonal_stats.bands=[1, 0]", "zonal_stats.nodata=-1.5"])
+    assert cfg["mode"] == "zonal_stats" and cfg["zonal_stats"]["bands"] == [1, 0] and cfg["zonal_stats"]["nodata"] == -1.5
+    assert callable(zonal.run_from_config) and callable(zonal.main)
+    # what the counting path refuses stays refused: a regression head has no class map for test.zones
+    with pytest.raises(ValueError, match="class map"):
+        zonal.check_zone_options("zones.geojson", regression=True)
+
+
+# ---- header, library, ops -------------------------------------------------------------------------------------------------------------------
+def test_header_declares_both_entry_points_and_states_the_rule():
+    text = open(os.path.join(ROOT, "include", "instageo_hip.h")).read()
+    block = [c for c in re.findall(r"/\*.*?\*/", text, flags=re.S) if "ig_zone_value_tally:" in c]
+    assert len(block) == 1
+    block = " ".join(block[0].replace("\n *", " ").split())
+    for phrase in ("VALID iff it is finite (not NaN, not +-Inf)", "v != nodata", "Chan, Golub and LeVeque", "(n, T, M2)",
+                   "M2 = M2a + M2b + (Tb / nb - Ta / na)^2 * (na * nb / n)", "No sum of squares", "no floating-point atomic",
+                   "two runs give the same bits", "min(H, 512)", "1 <= B <= 8", "partials (G, B, 64, 4) float64", "stats (64, B, 4)",
+                   "valid = 0", "it is read, never written", "ig_zone_value_reduce:"):
+        assert phrase in block, phrase
+    for n in NAMES + ("ig_zone_value_grid",):
+        assert re.search(r"\bint %s\(" % n, text)
+    src = open(os.path.join(PKG, "csrc", "zonal.hip")).read()
+    assert src.count("__shfl_up(t, o, 64)") == 1  # one scan, shared by the counting and the value tally
+    assert "atomicAdd" not in src[src.index("zone_value_tally_kernel"):src.index("zone_value_reduce_kernel")]
+
+
+def test_entry_points_exported_and_validated_without_gpu(built_lib):
+    """IG_REQUIRE rejects bad arguments before any launch, and empty calls return before a pointer is looked at."""
+    assert set(NAMES) <= set(built_lib.declared_symbols())
+    lib, err = built_lib.load(), built_lib.last_error
+    one, odd8, odd4 = ctypes.c_void_p(4096), ctypes.c_void_p(4104), ctypes.c_void_p(4098)
+    nd = ctypes.c_float(0.0)
+    assert [lib.ig_zone_value_grid(h) for h in (-3, 0, 1, 37, 512, 513, 2**31 - 1)] == [0, 0, 1, 37, 512, 512, 512]
+
+    tally = lib.ig_zone_value_tally
+    for k in range(4):
+        a = [one] * 4
+        a[k] = None
+        assert tally(*a, 8, 8, 1, 0, nd, None) == -1 and "null pointer" in err()
+    assert tally(odd4, one, one, one, 8, 8, 1, 0, nd, None) == -1 and "aligned" in err()
+    assert tally(one, odd4, one, one, 8, 8, 1, 0, nd, None) == -1 and "aligned" in err()
+    assert tally(one, one, odd8, one, 8, 8, 1, 0, nd, None) == -1 and "16-byte" in err()
+    assert tally(one, one, one, odd4, 8, 8, 1, 0, nd, None) == -1 and "aligned" in err()
+    assert tally(one, one, one, one, 8, 8, 9, 0, nd, None) == -1 and "0 <= B <= 8" in err()
+    assert tally(one, one, one, one, 8, 8, -1, 0, nd, None) == -1 and "B" in err()
+    assert tally(one, one, one, one, -1, 8, 1, 0, nd, None) == -1 and "H" in err()
+    assert tally(one, one, one, one, 65536, 32768, 1, 0, nd, None) == -1 and "2^31" in err()
+    assert tally(None, None, None, None, 0, 8, 1, 0, nd, None) == 0 and tally(None, None, None, None, 8, 0, 1, 0, nd, None) == 0  # H * W = 0
+    assert tally(None, None, None, None, 8, 8, 0, 0, nd, None) == 0  # B = 0
+
+    red = lib.ig_zone_value_reduce
+    for k in range(4):
+        a = [one] * 5
+        a[k] = None
+        assert red(*a, 4, 1, None) == -1 and "null pointer" in err()
+    assert red(odd8, one, one, one, one, 4, 1, None) == -1 and "aligned" in err()
+    assert red(one, one, one, odd4, None, 4, 1, None) == -1 and "aligned" in err()
+    assert red(one, one, one, one, one, 4, 9, None) == -1 and "0 <= B <= 8" in err()
+    assert red(one, one, one, one, one, 513, 1, None) == -1 and "0 <= G <= 512" in err()
+    assert red(one, one, one, one, one, -1, 1, None) == -1 and "G" in err()
+    assert red(None, None, None, None, None, 0, 1, None) == 0 and red(None, None, None, None, None, 4, 0, None) == 0
+
+
+def test_ops_wrapper_rejects_bad_arguments_and_the_ops_are_registered(built_lib):
+    from instageo_amd import ops, torch_ops
+
+    assert ops.ZONE_VALUE_BANDS == 8
+    canvas, raster = torch.zeros((4, 6), dtype=torch.int64), torch.zeros((2, 4, 6), dtype=torch.float32)
+    with pytest.raises(ValueError, match="canvas must be"):
+        ops.zone_value_tally(canvas.int(), raster)
+    with pytest.raises(ValueError, match="canvas must be"):
+        ops.zone_value_tally(canvas[None], raster)
+    with pytest.raises(ValueError, match="raster must be"):
+        ops.zone_value_tally(canvas, raster.double())
+    with pytest.raises(ValueError, match="raster must be"):
+        ops.zone_value_tally(canvas, raster[0])
+    with pytest.raises(ValueError, match="raster must be"):
+        ops.zone_value_tally(canvas, torch.zeros((2, 4, 7)))
+    with pytest.raises(ValueError, match="1 <= bands <= 8"):
+        ops.zone_value_tally(canvas, torch.zeros((9, 4, 6)))
+    with pytest.raises(ValueError, match="1 <= bands <= 8"):
+        ops.zone_value_tally(canvas, torch.zeros((0, 4, 6)))
+    with pytest.raises(ValueError, match="contiguous"):
+        ops.zone_value_tally(canvas, torch.zeros((2, 6, 4)).transpose(1, 2))
+    with pytest.raises(built_lib.HipLibraryError, match="HIP device tensors"):  # well-formed, but on the host: there is no CPU path
+        ops.zone_value_tally(canvas, raster)
+    with pytest.raises(ValueError, match="float32 raster"):
+        zonal.zone_values(raster.double(), np.zeros((0, 4), np.int32), np.zeros(0, np.int32), 1)
+    with pytest.raises(ValueError, match="nodata must be"):
+        zonal.zone_values(raster, np.zeros((0, 4), np.int32), np.zeros(0, np.int32), 1, nodata="x")
+    reg = torch_ops.register()
+    assert "Tensor? canvas" in reg["zone_value_tally"] and "Tensor(a!)? partials" in reg["zone_value_tally"] and "float nodata" in reg["zone_value_tally"]
+    assert "Tensor? partials" in reg["zone_value_reduce"] and "Tensor(c!)? pixels" in reg["zone_value_reduce"]
+    assert "zone_value_grid" not in reg  # no tensors: a host-side query
