@@ -477,6 +477,39 @@ int ig_zone_value_tally(const unsigned long long* canvas, const float* raster, d
                         int W, int B, int has_nodata, float nodata, void* stream);
 int ig_zone_value_reduce(const double* partials, const unsigned long long* pix_partials, long long* valid, double* stats,
                          long long* pixels, int G, int B, void* stream);
+/* Order statistics of float rasters per zone and band: the median and percentiles (zonal.hip; not in the reference).  canvas, raster,
+ * has_nodata and nodata are those of ig_zone_value_tally; the canvas is read, never written.
+ * THE RULE.  The VALID values of zone z and band b are exactly those ig_zone_value_tally counts: inside the mask, finite, and != nodata
+ *   as float32 when has_nodata != 0.  Zeros are canonical: a value enters as v + 0.0f, so -0.0 counts and comes out as +0.0.  Sorted
+ *   ascending they are v(0) <= ... <= v(n-1), n = valid[z][b].  For a fraction f in [0, 1] (float64; the host forms f = q / 100.0 once)
+ *     h = (double)(n - 1) * f,   lo = floor(h),   hi = min(lo + 1, n - 1)      (one float64 multiply and a floor, no contraction)
+ *   and the device delivers the pair (v(lo), v(hi)) as float32, exactly: order statistics are members of the data, so the result is
+ *   unique.  n = 0 delivers (NaN, NaN).  The host interpolates in float64 by numpy's `linear` method: g = h - lo,
+ *   p = a + (b - a) * g for g > 0, else p = a, with (a, b) the pair widened to float64.  f = 0 is the minimum, 1 the maximum, 0.5 the median.
+ * METHOD.  Most-significant-digit radix selection on order-preserving keys: u = bits(v + 0.0f), key = u ^ (u >> 31 ? 0xFFFFFFFF :
+ *   0x80000000); IG_ZONE_QUANTILE_ROUNDS = 4 rounds of 8 bits, round r deciding key bits 31 - 8r .. 24 - 8r.  A selection of Q fractions
+ *   has S = 2 Q rank slots (slot 2 i = lo, slot 2 i + 1 = hi of fraction i); 1 <= B <= 8 bands and 1 <= Q <= 8 fractions per selection
+ *   (the caller loops over groups).  One selection is rounds 0, 1, 2, 3 of (ig_zone_quantile_hist, ig_zone_quantile_pick) on one stream
+ *   with the same B, Q, state and hist: 8 launches, no host round trip, no wait between workgroups.  All additions are unsigned 32-bit
+ *   integer atomics (a counter holds at most H * W <= 2^31 - 1), so the result does not depend on arrival order: the same bits from run
+ *   to run.  Before an add reaches memory a wave merges its lanes' equal (band, zone bit, slot, digit) targets into one add of their count.
+ * BUFFERS.  hist (B, 64, S, 256) uint32, zeroed by the caller before round 0 (ig_zone_quantile_pick clears what it has read); state
+ *   (B, 64, S, 4) uint32 {key prefix, remaining 0-based rank (0xFFFFFFFF: n = 0), leader, unused}, 16-byte aligned, written by round 0
+ *   (the caller need not initialise it).  Slots of one (band, zone bit) whose prefixes are equal share the bins of the first of them, their
+ *   leader: in round 0 (empty prefix) that is slot 0 for all.
+ * ig_zone_quantile_hist: round r.  The rows, the scan and the validity test of ig_zone_value_tally; for every valid pixel, zone bit z of
+ *   its mask, band b and leader slot s whose prefix equals the key's bits above the round's digit d: hist[b][z][s][d] += 1.
+ * ig_zone_quantile_pick: round r.  Per (band, zone bit, slot) the first digit d, ascending, whose cumulative count exceeds the slot's
+ *   remaining rank; the count below d is subtracted from the rank, d is appended to the prefix, the bins read are cleared and the leaders
+ *   of the next round are found.  Round 0 first forms n (the sum of the bins) -> valid (64, B) int64, and lo, hi from fractions (Q
+ *   float64 in HOST memory, read during the call in every round; each in [0, 1]).  Round 3 inverts the key transform -> order (64, B, Q, 2) float32.
+ * H * W = 0, B = 0 or Q = 0 returns IG_OK before a pointer is looked at (ig_zone_quantile_pick: B = 0 or Q = 0).  canvas, valid: 8-byte
+ * aligned; state, hist: 16-byte; raster, order: 4-byte.  A fraction outside [0, 1] (or NaN), B > 8, Q > 8 or a round outside 0..3 is an
+ * argument error. */
+int ig_zone_quantile_hist(const unsigned long long* canvas, const float* raster, const unsigned* state, unsigned* hist, int H, int W,
+                          int B, int Q, int round, int has_nodata, float nodata, void* stream);
+int ig_zone_quantile_pick(unsigned* hist, unsigned* state, const double* fractions, long long* valid, float* order, int B, int Q,
+                          int round, void* stream);
 /* Polygon labels burned into label rasters (burn.hip; the reference assumes its label rasters were made with gdal_rasterize beforehand).
  * THE RULE:
  * Grid and inside test.  Those of the zonal block above, unchanged: Q = 256 fixed point, X = floor(x * 256 + 0.5), the centre of pixel

@@ -13,6 +13,11 @@
 //                              accumulators and the workgroup into one partial per workgroup; the canvas is only read
 //   5  zone_value_reduce_kernel  the partials merged in workgroup order -> valid, mean, M2, min, max and the inside pixels
 //   (4) and (5) are float64 in a fixed order, without atomics: unique results too.
+//   6  zone_quantile_hist_kernel  one round of a radix selection of order statistics (median, percentiles): the rows and scan of (4);
+//                              per valid value, zone bit, band and rank slot whose key prefix it continues, one count in the histogram of
+//                              the round's 8-bit digit: unsigned integer atomics, equal targets merged across the wave first
+//   7  zone_quantile_pick_kernel  per (band, zone bit, slot): the digit that holds the wanted rank; after the last round the values
+//   (6) and (7) count with integer atomics only and select members of the data: unique results as well.
 //
 // Up to 64 zones share a pass: one bit of a uint64 canvas each.  A pass costs one sweep of the 8-byte canvas (read, optionally written)
 // and of the 1-byte class map, whatever the number of edges; the toggles are one atomic per crossing.
@@ -337,6 +342,184 @@ __global__ __launch_bounds__(ZBITS) void zone_value_reduce_kernel(const ZAcc* __
     }
 }
 
+// ---- order statistics: per zone and band the values of given ranks (the median, percentiles) ------------------------------------------------
+// Radix selection, most significant digit first, on order-preserving keys (the rule: include/instageo_hip.h).  ZQ_ROUNDS rounds of
+// ZQ_DIGIT bits; a round is one histogram launch and one pick launch.
+constexpr int ZQ_ROUNDS = 4, ZQ_DIGIT = 8, ZQ_BINS = 1 << ZQ_DIGIT;
+constexpr int ZQ_MAX_Q = 8, ZQ_MAX_SLOTS = 2 * ZQ_MAX_Q;
+constexpr int ZQ_MERGE = 8;               // digits a wave merges before the lanes left over add on their own
+constexpr unsigned ZQ_DEAD = 0xFFFFFFFFu;  // the rank of a slot whose zone has no valid value
+static_assert(ZQ_ROUNDS * ZQ_DIGIT == 32, "the rounds cover the key");
+
+struct ZFractions {
+    double f[ZQ_MAX_Q];
+};
+
+// ascending floats <-> ascending unsigned keys; zeros are canonical (-0.0 + 0.0 = +0.0)
+__device__ __forceinline__ unsigned zq_key(float v) {
+    const unsigned u = __float_as_uint(v + 0.0f);
+    return u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u);
+}
+__device__ __forceinline__ float zq_unkey(unsigned k) { return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xFFFFFFFFu)); }
+
+// bins[d[j]] += 1 for every j with act[j], over the wave: up to ZQ_MERGE times the digit of the first lane that still has one is taken,
+// every (lane, j) that holds it is counted by ballots and that lane adds the count once; what is left adds one by one.  Integer adds: the
+// sums do not depend on any of this.  `bins` is the same in every lane; every lane of the wave calls it.
+__device__ __forceinline__ void zq_wave_add(unsigned* bins, bool (&act)[ZVPT], const unsigned (&d)[ZVPT], int lane) {
+    for (int it = 0; it < ZQ_MERGE; ++it) {
+        bool any = false;
+        unsigned mine = 0;
+#pragma unroll
+        for (int j = ZVPT - 1; j >= 0; --j)
+            if (act[j]) any = true, mine = d[j];
+        const unsigned long long todo = __ballot(any);
+        if (!todo) return;
+        const int src = __ffsll((long long)todo) - 1;
+        const unsigned digit = __shfl(mine, src, 64);
+        unsigned cnt = 0;
+#pragma unroll
+        for (int j = 0; j < ZVPT; ++j) {
+            const bool hit = act[j] && d[j] == digit;
+            cnt += (unsigned)__popcll(__ballot(hit));
+            act[j] = act[j] && !hit;
+        }
+        if (lane == src) atomicAdd(bins + digit, cnt);
+    }
+#pragma unroll
+    for (int j = 0; j < ZVPT; ++j)
+        if (act[j]) atomicAdd(bins + d[j], 1u);
+}
+
+// Round `round` of a selection: the rows, chunks, scan and validity test of zone_value_tally_kernel.  Per chunk and band a wave walks
+// the zone bits any of its lanes is inside of and, per bit, the leader slots of (band, bit): the lanes whose key continues the slot's
+// prefix add their digit to hist[band][bit][slot][.].  Round 0 has no prefix: slot 0 counts every valid value and state is not read.
+// state: (B, 64, S) x {prefix, rank, leader, -}.  Every index into hist is below B * 64 * S * 256 (band < B, bit < 64, slot < S, digit < 256).
+__global__ __launch_bounds__(ZTPB) void zone_quantile_hist_kernel(const unsigned long long* __restrict__ canvas, const float* __restrict__ raster,
+                                                                  const uint4* __restrict__ state, unsigned* __restrict__ hist, int H, int W,
+                                                                  int B, int S, int round, int has_nodata, float nodata) {
+    __shared__ unsigned long long wtot[2][ZWAVES];
+    const int lane = threadIdx.x & 63;
+    const long plane = (long)H * W;
+    const int shift = 32 - ZQ_DIGIT * round;  // the key bits from here up are the prefix (round >= 1: 24, 16, 8)
+    int par = 0;
+    for (int r = blockIdx.x; r < H; r += gridDim.x) {
+        const unsigned long long* row = canvas + (long)r * W;
+        const float* vrow = raster + (long)r * W;
+        unsigned long long carry = 0;
+        for (long c0 = 0; c0 < W; c0 += ZCHUNK, par ^= 1) {
+            const long c = c0 + (long)threadIdx.x * ZVPT;
+            unsigned long long m[ZVPT];
+#pragma unroll
+            for (int j = 0; j < ZVPT; ++j) m[j] = c + j < W ? row[c + j] : 0ull;
+            zone_scan_chunk(m, carry, wtot[par]);  // the workgroup's only barrier in this loop: what follows is per wave
+            unsigned long long present = 0;
+#pragma unroll
+            for (int j = 0; j < ZVPT; ++j) {
+                if (c + j >= W) m[j] = 0ull;
+                present |= m[j];
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) present |= __shfl_xor(present, o, 64);
+            if (!present) continue;  // the same in every lane of the wave
+            for (int b = 0; b < B; ++b) {
+                unsigned key[ZVPT], dig[ZVPT];
+                bool ok[ZVPT];
+#pragma unroll
+                for (int j = 0; j < ZVPT; ++j) {
+                    const float x = c + j < W ? vrow[b * plane + c + j] : 0.f;
+                    ok[j] = c + j < W && (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u && !(has_nodata && x == nodata);
+                    key[j] = zq_key(x);
+                    dig[j] = (key[j] >> (shift - ZQ_DIGIT)) & (unsigned)(ZQ_BINS - 1);
+                }
+                for (unsigned long long rest = present; rest; rest &= rest - 1) {
+                    const int z = __ffsll((long long)rest) - 1;
+                    const long cell = ((long)b * ZBITS + z) * S;
+                    bool in[ZVPT];
+                    bool some = false;
+#pragma unroll
+                    for (int j = 0; j < ZVPT; ++j) {
+                        in[j] = ok[j] && ((m[j] >> z) & 1ull);
+                        some = some || in[j];
+                    }
+                    if (__ballot(some) == 0ull) continue;
+                    if (round == 0) {
+                        zq_wave_add(hist + cell * ZQ_BINS, in, dig, lane);
+                        continue;
+                    }
+                    for (int s = 0; s < S; ++s) {
+                        const uint4 st = state[cell + s];  // the same address in every lane
+                        if (st.z != (unsigned)s) continue;  // another slot with this prefix counts for it
+                        bool act[ZVPT];
+#pragma unroll
+                        for (int j = 0; j < ZVPT; ++j) act[j] = in[j] && (key[j] >> shift) == (st.x >> shift);
+                        zq_wave_add(hist + (cell + s) * ZQ_BINS, act, dig, lane);
+                    }
+                }
+            }
+        }
+    }
+}
+
+// One workgroup per (band, zone bit), one thread per slot.  See include/instageo_hip.h.
+__global__ __launch_bounds__(ZQ_MAX_SLOTS) void zone_quantile_pick_kernel(unsigned* __restrict__ hist, uint4* __restrict__ state,
+                                                                          const ZFractions fr, long long* __restrict__ valid,
+                                                                          float* __restrict__ order, int B, int S, int round) {
+#pragma clang fp contract(off)
+    __shared__ unsigned pre[ZQ_MAX_SLOTS], dead[ZQ_MAX_SLOTS];
+    const int s = threadIdx.x, b = blockIdx.x / ZBITS, z = blockIdx.x % ZBITS;
+    const long cell = (long)blockIdx.x * S;
+    const bool live = s < S;
+    uint4 st = make_uint4(0u, 0u, 0u, 0u);  // round 0: empty prefix, slot 0 leads
+    if (live && round > 0) st = state[cell + s];
+    const uint4* bins = reinterpret_cast<const uint4*>(hist + (cell + (live ? st.z : 0u)) * ZQ_BINS);
+    if (live && round == 0) {
+        unsigned n = 0;
+        for (int i = 0; i < ZQ_BINS / 4; ++i) {
+            const uint4 q = bins[i];
+            n += q.x + q.y + q.z + q.w;
+        }
+        if (s == 0) valid[(long)z * B + b] = (long long)n;
+        if (n == 0) {
+            st.y = ZQ_DEAD;
+        } else {
+            const double h = (double)(n - 1u) * fr.f[s >> 1];
+            const unsigned lo = (unsigned)floor(h);
+            const unsigned hi = lo + 1u < n - 1u ? lo + 1u : n - 1u;
+            st.y = (s & 1) ? hi : lo;
+        }
+    }
+    const bool sel = live && st.y != ZQ_DEAD;
+    if (sel) {
+        unsigned cum = 0, digit = 0, below = 0;
+        bool found = false;
+        for (int i = 0; i < ZQ_BINS / 4; ++i) {  // no early exit: the loads do not wait for one another
+            const uint4 q = bins[i];
+            const unsigned cnt[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                if (!found && cum + cnt[k] > st.y) found = true, digit = (unsigned)(4 * i + k), below = cum;
+                cum += cnt[k];
+            }
+        }
+        st.y -= below;
+        st.x |= digit << (32 - ZQ_DIGIT * (round + 1));
+    }
+    pre[s] = st.x;
+    dead[s] = sel ? 0u : 1u;
+    __syncthreads();  // every slot has read its leader's bins
+    if (live && st.z == (unsigned)s && round + 1 < ZQ_ROUNDS) {
+        uint4* mine = reinterpret_cast<uint4*>(hist + (cell + s) * ZQ_BINS);
+        for (int i = 0; i < ZQ_BINS / 4; ++i) mine[i] = make_uint4(0u, 0u, 0u, 0u);
+    }
+    if (!live) return;
+    unsigned lead = (unsigned)s;
+    for (int t = s - 1; t >= 0; --t)
+        if (sel && !dead[t] && pre[t] == st.x) lead = (unsigned)t;
+    st.z = lead;
+    state[cell + s] = st;
+    if (round + 1 == ZQ_ROUNDS) order[((long)z * B + b) * S + s] = sel ? zq_unkey(st.x) : __builtin_nanf("");
+}
+
 }  // namespace
 
 #define ST(s) ((hipStream_t)(s))
@@ -408,6 +591,40 @@ int ig_zone_value_reduce(const double* partials, const unsigned long long* pix_p
                "ig_zone_value_reduce: every pointer must be 8-byte aligned, partials 16-byte");
     return ig_launch<zone_value_reduce_kernel>("ig_zone_value_reduce", dim3((unsigned)B), dim3(ZBITS), 0, ST(stream),
                                                reinterpret_cast<const ZAcc*>(partials), pix_partials, valid, stats, pixels, G, B);
+}
+
+#define IG_REQUIRE_SELECTION(name)                                                                                            \
+    IG_REQUIRE(B >= 0 && B <= ZV_MAX_BANDS, name ": 0 <= B <= %d bands per selection (got %d)", ZV_MAX_BANDS, B);             \
+    IG_REQUIRE(Q >= 0 && Q <= ZQ_MAX_Q, name ": 0 <= Q <= %d fractions per selection (got %d)", ZQ_MAX_Q, Q);                 \
+    IG_REQUIRE(round >= 0 && round < ZQ_ROUNDS, name ": round must be 0..%d (got %d)", ZQ_ROUNDS - 1, round)
+
+int ig_zone_quantile_hist(const unsigned long long* canvas, const float* raster, const unsigned* state, unsigned* hist, int H, int W,
+                          int B, int Q, int round, int has_nodata, float nodata, void* stream) {
+    IG_REQUIRE_SELECTION("ig_zone_quantile_hist");
+    IG_REQUIRE_RASTER("ig_zone_quantile_hist");
+    if ((long)H * W == 0 || B == 0 || Q == 0) return IG_OK;
+    IG_REQUIRE(canvas && raster && state && hist, "ig_zone_quantile_hist: null pointer");
+    IG_REQUIRE(((uintptr_t)canvas & 7) == 0 && (((uintptr_t)state | (uintptr_t)hist) & 15) == 0 && ((uintptr_t)raster & 3) == 0,
+               "ig_zone_quantile_hist: canvas must be 8-byte aligned, state and hist 16-byte, raster 4-byte");
+    return ig_launch<zone_quantile_hist_kernel>("ig_zone_quantile_hist", dim3((unsigned)ig_zone_value_grid(H)), dim3(ZTPB), 0, ST(stream),
+                                                canvas, raster, reinterpret_cast<const uint4*>(state), hist, H, W, B, 2 * Q, round, has_nodata,
+                                                nodata);
+}
+
+int ig_zone_quantile_pick(unsigned* hist, unsigned* state, const double* fractions, long long* valid, float* order, int B, int Q,
+                          int round, void* stream) {
+    IG_REQUIRE_SELECTION("ig_zone_quantile_pick");
+    if (B == 0 || Q == 0) return IG_OK;
+    IG_REQUIRE(hist && state && fractions && valid && order, "ig_zone_quantile_pick: null pointer");
+    IG_REQUIRE((((uintptr_t)state | (uintptr_t)hist) & 15) == 0 && ((uintptr_t)valid & 7) == 0 && ((uintptr_t)order & 3) == 0,
+               "ig_zone_quantile_pick: state and hist must be 16-byte aligned, valid 8-byte, order 4-byte");
+    ZFractions fr = {};
+    for (int q = 0; q < Q; ++q) {
+        IG_REQUIRE(fractions[q] >= 0.0 && fractions[q] <= 1.0, "ig_zone_quantile_pick: fraction %d = %g is outside [0, 1]", q, fractions[q]);
+        fr.f[q] = fractions[q];
+    }
+    return ig_launch<zone_quantile_pick_kernel>("ig_zone_quantile_pick", dim3((unsigned)(B * ZBITS)), dim3(ZQ_MAX_SLOTS), 0, ST(stream), hist,
+                                                reinterpret_cast<uint4*>(state), fr, valid, order, B, 2 * Q, round);
 }
 
 }  // extern "C"

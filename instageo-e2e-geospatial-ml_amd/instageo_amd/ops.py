@@ -1090,6 +1090,52 @@ def zone_value_tally(canvas, raster, nodata: Optional[float] = None):
     return pixels, valid, stats
 
 
+ZONE_QUANTILES = 8  # fractions per selection of ig_zone_quantile_hist / ig_zone_quantile_pick (two rank slots each)
+ZONE_QUANTILE_ROUNDS = 4  # radix rounds of 8 bits over the 32-bit keys
+
+
+def zone_value_quantiles(canvas, raster, fractions, nodata: Optional[float] = None):
+    """Order statistics of ``raster`` (B, H, W) float32, 1 <= B <= ``ZONE_VALUE_BANDS``, under the inside masks of the toggles in
+    ``canvas`` (H, W) int64, which is read and left as it is; ``fractions``: a host sequence of 1..``ZONE_QUANTILES`` float64 in [0, 1]
+    -> (valid (64, B) int64: the values that are finite and not ``nodata``, as :func:`zone_value_tally` counts them; order (64, B, Q, 2)
+    float32: the sorted valid values at ranks lo = floor((valid - 1) f) and hi = min(lo + 1, valid - 1), exactly; NaN where valid is 0).
+    A radix selection in ``ZONE_QUANTILE_ROUNDS`` rounds of two launches, integer atomics only (include/instageo_hip.h): the same bits
+    from run to run."""
+    import ctypes
+
+    if canvas.dtype != torch.int64 or canvas.dim() != 2:
+        raise ValueError(f"zone_value_quantiles: canvas must be (H, W) int64 (got {tuple(canvas.shape)} {canvas.dtype})")
+    if raster.dtype != torch.float32 or raster.dim() != 3 or tuple(raster.shape[1:]) != tuple(canvas.shape):
+        raise ValueError(f"zone_value_quantiles: raster must be (B, H, W) float32 on the canvas's {tuple(canvas.shape)} pixels "
+                         f"(got {tuple(raster.shape)} {raster.dtype})")
+    B, H, W = raster.shape
+    if not 1 <= B <= ZONE_VALUE_BANDS:
+        raise ValueError(f"zone_value_quantiles: 1 <= bands <= {ZONE_VALUE_BANDS} per call (got {B}); zonal.zone_quantiles loops over groups")
+    fr = [float(f) for f in fractions]
+    Q = len(fr)
+    if not 1 <= Q <= ZONE_QUANTILES:
+        raise ValueError(f"zone_value_quantiles: 1 <= fractions <= {ZONE_QUANTILES} per call (got {Q}); zonal.zone_quantiles loops over groups")
+    if not all(0.0 <= f <= 1.0 for f in fr):
+        raise ValueError(f"zone_value_quantiles: every fraction must lie in [0, 1] (got {fr!r})")
+    if not (canvas.is_contiguous() and raster.is_contiguous()):
+        raise ValueError("zone_value_quantiles: canvas and raster must be contiguous")
+    dev = raster.device
+    valid = torch.zeros((ZONE_BITS, B), dtype=torch.int64, device=dev)
+    order = torch.full((ZONE_BITS, B, Q, 2), float("nan"), dtype=torch.float32, device=dev)
+    if H * W == 0:
+        return valid, order
+    hist = torch.zeros((B, ZONE_BITS, 2 * Q, 256), dtype=torch.int32, device=dev)
+    state = torch.empty((B, ZONE_BITS, 2 * Q, 4), dtype=torch.int32, device=dev)  # round 0 writes it
+    host = (ctypes.c_double * Q)(*fr)
+    nd = (int(nodata is not None), float(0.0 if nodata is None else nodata))
+    for rnd in range(ZONE_QUANTILE_ROUNDS):
+        # HBM bytes: the canvas and the bands read once per round; the histograms live in L2
+        _call("ig_zone_quantile_hist", float(H) * W * (8 + 4 * B), _p(canvas), _p(raster), _p(state), _p(hist), H, W, B, Q, rnd, *nd, _stream())
+        _call("ig_zone_quantile_pick", float(B) * ZONE_BITS * 2 * Q * (2 * 1024 + 32), _p(hist), _p(state), host, _p(valid), _p(order), B, Q, rnd,
+              _stream())
+    return valid, order
+
+
 def burn_resolve(canvas, table, out, r0: int, c0: int, written=None) -> None:
     """One pass of the polygon burn (include/instageo_hip.h): ``canvas`` (Hp, Wp) int64 holds the toggles of up to 64 features
     (:func:`zone_toggle`); where the prefix XOR along a row is not zero, ``out[r0 + r, c0 + c] = table[highest set bit]``; other pixels

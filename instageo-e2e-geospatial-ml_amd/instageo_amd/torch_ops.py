@@ -32,11 +32,12 @@ NAMESPACE = "instageo_mi355x"
 _SCALAR_SCHEMA = {"int": "int", "long": "int", "unsigned": "int", "float": "float", "double": "float"}
 _SKIP = {"ig_last_error", "ig_last_kernel", "ig_note_reset", "ig_last_grid", "ig_version", "ig_header_stamp", "ig_device_info",
          "ig_set_reserved_cus", "ig_get_reserved_cus", "ig_set_deterministic", "ig_get_deterministic", "ig_det_fold", "ig_det_fold_ranges",
-         "ig_linear_wgrad_group", "ig_conv3x3_fwd_stats", "ig_conv3x3_cls_fwd", "ig_d4_apply", "ig_calib_nll_grid", "ig_boundary_update"}  # host-side queries: no tensors; the grouped launch takes
+         "ig_linear_wgrad_group", "ig_conv3x3_fwd_stats", "ig_conv3x3_cls_fwd", "ig_d4_apply", "ig_calib_nll_grid", "ig_boundary_update", "ig_zone_quantile_pick"}  # host-side queries: no tensors; the grouped launch takes
 # HOST arrays of device pointers; ig_conv3x3_fwd_stats / ig_conv3x3_cls_fwd report through a HOST int (ig_conv3x3_fwd + ig_bn_relu_fwd /
 # ig_classifier_fwd are the op-level equivalents); ig_d4_apply takes its transform codes as a HOST int array (ops.d4_apply);
 # ig_calib_nll_grid takes its inverse temperatures as a HOST float array (ops.calib_nll_grid); ig_boundary_update takes its squared
-# distances as a HOST int array (ops.boundary_update)
+# distances as a HOST int array (ops.boundary_update); ig_zone_quantile_pick takes its fractions as a HOST double array
+# (ops.zone_value_quantiles)
 
 
 def parse_prototypes(path: str = _lib.HEADER_PATH) -> Dict[str, List[Tuple[str, str]]]:

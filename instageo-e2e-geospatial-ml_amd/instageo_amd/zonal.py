@@ -15,8 +15,13 @@ and not the no-data value, and ``mode=zonal_stats`` (:func:`run_from_config`) do
 variance comes from merged (n, sum, M2) triples in a fixed order, float64 (``include/instageo_hip.h``): no sum of squares, no atomics,
 the same bits from run to run.
 
-Out of scope: percentiles and the median, ``all_touched``, rotated or sheared geotransforms, one table merged across chips or tiles,
-zone rasters written as TIFF.
+Order statistics.  :func:`zone_quantiles` gives the median and any percentiles of the same valid values: the device selects, per zone,
+band and percentile, the two neighbouring order statistics by a radix selection on order-preserving keys (integer atomics only, exact,
+the same bits from run to run) and the host interpolates between them in float64 as numpy's default ``linear`` method does
+(``include/instageo_hip.h``).  :func:`zone_quantiles_host` is the numpy twin of the rule.  ``zonal_stats.percentiles`` adds them to the CSV.
+
+Out of scope: ``all_touched``, ``majority`` / ``minority`` / ``unique``, percentiles in ``test.zones`` of the inference modes, rotated or
+sheared geotransforms, one table merged across chips or tiles, zone rasters written as TIFF.
 """
 from __future__ import annotations
 
@@ -281,23 +286,123 @@ def zone_values(raster: torch.Tensor, edges: np.ndarray, edge_zone: np.ndarray, 
     return ZoneValues(pixels, valid, mean * valid, mean, std, np.where(has, stats[..., 2], nan), np.where(has, stats[..., 3], nan))
 
 
+# ---- order statistics: the median and percentiles -------------------------------------------------------------------------------------------
+def check_percentiles(percentiles) -> List[float]:
+    """A sequence of numbers in [0, 100] -> a list of float; ValueError for anything else (no sequence, empty, a bool, a string, NaN,
+    a value outside the range)."""
+    if isinstance(percentiles, (str, bytes)) or not isinstance(percentiles, (list, tuple, np.ndarray)) or len(percentiles) == 0:
+        raise ValueError(f"percentiles must be a non-empty list of numbers in [0, 100] (got {percentiles!r})")
+    out = []
+    for q in percentiles:
+        if isinstance(q, (bool, np.bool_)) or not isinstance(q, (int, float, np.integer, np.floating)) or not 0.0 <= float(q) <= 100.0:
+            raise ValueError(f"percentiles must be a non-empty list of numbers in [0, 100] (got {q!r})")
+        out.append(float(q))
+    return out
+
+
+def quantile_ranks(n, f) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """The rule's ranks for ``n`` valid values (int, any shape) and fractions ``f`` = q / 100.0 (float64, broadcast against ``n``) ->
+    (lo, hi int64, g float64): h = (n - 1) * f in float64, lo = floor(h), hi = min(lo + 1, n - 1), g = h - lo.  Where n is 0: (0, 0, 0)."""
+    n = np.asarray(n, dtype=np.int64)
+    h = np.maximum(n - 1, 0).astype(np.float64) * np.asarray(f, dtype=np.float64)
+    lo = np.floor(h)
+    hi = np.minimum(lo + 1, np.maximum(n - 1, 0))
+    return lo.astype(np.int64), hi.astype(np.int64), h - lo
+
+
+def quantile_lerp(a, b, g) -> np.ndarray:
+    """numpy's ``linear`` method between the order statistics ``a`` = v(lo) and ``b`` = v(hi), widened to float64: a + (b - a) * g for
+    g > 0, else a."""
+    a, b, g = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64), np.asarray(g, dtype=np.float64)
+    with np.errstate(invalid="ignore"):
+        return np.where(g > 0, a + (b - a) * g, a)
+
+
+def zone_quantiles(raster: torch.Tensor, edges: np.ndarray, edge_zone: np.ndarray, Z: int, percentiles, nodata: Optional[float] = None,
+                   pairs: bool = False):
+    """Per zone and band the ``percentiles`` (numbers in [0, 100]; 50 is the median, 0 the minimum, 100 the maximum) of the valid values
+    of one (H, W) or (B, H, W) float32 raster on the device -> (valid (Z, B) int64, values (Z, B, Q) float64), NaN where a zone has no
+    valid value; with ``pairs`` also the order statistics themselves, (Z, B, Q, 2) float32 {v(lo), v(hi)}.  Validity, ``edges`` and
+    ``edge_zone`` are those of :func:`zone_values`.  The device selects the pairs exactly (``ops.zone_value_quantiles``: groups of
+    ``ops.ZONE_VALUE_BANDS`` bands and ``ops.ZONE_QUANTILES`` percentiles on one canvas per pass of 64 zones; a percentile given twice is
+    selected once); the interpolation is :func:`quantile_lerp` on the host."""
+    if raster.dtype != torch.float32 or raster.dim() not in (2, 3):
+        raise ValueError(f"zone_quantiles takes one (H, W) or (B, H, W) float32 raster (got {tuple(raster.shape)} {raster.dtype})")
+    qs = check_percentiles(percentiles)
+    r = (raster[None] if raster.dim() == 2 else raster).contiguous()
+    B, H, W = r.shape
+    if B < 1:
+        raise ValueError("zone_quantiles: the raster has no band")
+    nd, Z = _check_nodata(nodata), int(Z)
+    uniq = list(dict.fromkeys(qs))
+    fr = [q / 100.0 for q in uniq]
+    valid = np.zeros((Z, B), dtype=np.int64)
+    order = np.full((Z, B, len(uniq), 2), np.nan, dtype=np.float32)
+    for p, canvas in _passes(edges, edge_zone, Z, H, W, r.device):
+        lo = p * ops.ZONE_BITS
+        n = min(ops.ZONE_BITS, Z - lo)
+        for b0 in range(0, B, ops.ZONE_VALUE_BANDS):
+            for q0 in range(0, len(fr), ops.ZONE_QUANTILES):
+                val, od = ops.zone_value_quantiles(canvas, r[b0:b0 + ops.ZONE_VALUE_BANDS], fr[q0:q0 + ops.ZONE_QUANTILES], nd)
+                valid[lo:lo + n, b0:b0 + val.shape[1]] = val[:n].cpu().numpy()
+                order[lo:lo + n, b0:b0 + val.shape[1], q0:q0 + od.shape[2]] = od[:n].cpu().numpy()
+    g = quantile_ranks(valid[..., None], np.array(fr, dtype=np.float64))[2]
+    values = np.where(valid[..., None] > 0, quantile_lerp(order[..., 0], order[..., 1], g), np.nan)
+    pick = [uniq.index(q) for q in qs]
+    values, order = np.ascontiguousarray(values[:, :, pick]), np.ascontiguousarray(order[:, :, pick])
+    return (valid, values, order) if pairs else (valid, values)
+
+
+def zone_quantiles_host(mask: np.ndarray, raster: np.ndarray, percentiles, nodata: Optional[float] = None, pairs: bool = False):
+    """The numpy twin of the rule, for one zone: ``mask`` (H, W) bool and ``raster`` (H, W) or (B, H, W) float32 -> (valid (B,) int64,
+    values (B, Q) float64); with ``pairs`` also (B, Q, 2) float32 {v(lo), v(hi)}.  ``np.sort`` of the canonicalised (v + 0.0) valid
+    values, then the rank and interpolation formulas of :func:`quantile_ranks` and :func:`quantile_lerp`."""
+    qs = check_percentiles(percentiles)
+    raster, mask = np.asarray(raster), np.asarray(mask, dtype=bool)
+    if raster.dtype != np.float32 or raster.ndim not in (2, 3) or raster.shape[-2:] != mask.shape:
+        raise ValueError("zone_quantiles_host takes a (H, W) mask and a (H, W) or (B, H, W) float32 raster")
+    r = raster[None] if raster.ndim == 2 else raster
+    nd = _check_nodata(nodata)
+    fr = np.array([q / 100.0 for q in qs], dtype=np.float64)
+    valid = np.zeros(len(r), dtype=np.int64)
+    values = np.full((len(r), len(qs)), np.nan)
+    order = np.full((len(r), len(qs), 2), np.nan, dtype=np.float32)
+    for b, band in enumerate(r):
+        v = band[mask]
+        ok = np.isfinite(v)
+        if nd is not None:
+            ok &= v != np.float32(nd)
+        v = np.sort(v[ok] + np.float32(0.0))
+        valid[b] = v.size
+        if v.size:
+            lo, hi, g = quantile_ranks(v.size, fr)
+            order[b, :, 0], order[b, :, 1] = v[lo], v[hi]
+            values[b] = quantile_lerp(v[lo], v[hi], g)
+    return (valid, values, order) if pairs else (valid, values)
+
+
 def zone_value_table(raster: torch.Tensor, zones: Sequence[Zone], nodata: Optional[float] = None,
-                     profile: Optional[Dict[str, Any]] = None) -> Tuple[List[Any], ZoneValues]:
+                     profile: Optional[Dict[str, Any]] = None, percentiles=None):
     """``zones`` (:func:`read_zones`; map coordinates when ``profile`` is georeferenced) on ``raster`` -> (ids, values) for
-    :func:`write_zone_values_csv`: what :func:`zone_table` is to a class map."""
+    :func:`write_zone_values_csv`: what :func:`zone_table` is to a class map.  With ``percentiles`` -> (ids, values, (Z, B, Q) float64 of
+    :func:`zone_quantiles`)."""
     edges, edge_zone = zones_to_pixels(zones, profile)
-    return [z.id for z in zones], zone_values(raster, edges, edge_zone, len(zones), nodata)
+    ids, values = [z.id for z in zones], zone_values(raster, edges, edge_zone, len(zones), nodata)
+    if percentiles is None:
+        return ids, values
+    return ids, values, zone_quantiles(raster, edges, edge_zone, len(zones), percentiles, nodata)[1]
 
 
 VALUE_COLUMNS = ("valid", "mean", "std", "min", "max", "sum")  # per band, in this order
 
 
 def write_zone_values_csv(path: str, ids: Sequence[Any], values: ZoneValues, band_names: Optional[Sequence[Any]] = None,
-                          profile: Optional[Dict[str, Any]] = None) -> str:
+                          profile: Optional[Dict[str, Any]] = None, percentiles=None) -> str:
     """Write one row per zone: ``zone`` (its index), ``id``, ``pixels`` (all its inside pixels), then per band ``valid_<b>``, ``mean_<b>``,
     ``std_<b>``, ``min_<b>``, ``max_<b>``, ``sum_<b>`` (``<b>`` from ``band_names``, else the band's index) and, with a georeferenced
     ``profile``, ``area_map`` = pixels * scale_x * scale_y in squared map units.  Floats are written with ``repr`` (they read back
-    exactly); the statistics of a zone without a valid value are empty cells."""
+    exactly); the statistics of a zone without a valid value are empty cells.  ``percentiles`` = (the percentiles, their (Z, B, Q)
+    values of :func:`zone_quantiles`) adds, per band after ``sum_<b>``, the columns ``percentile_<q>_<b>`` (``<q>`` written with ``%g``)."""
     valid = np.asarray(values.valid)
     if valid.ndim != 2 or valid.shape[0] != len(ids) or np.asarray(values.pixels).shape != (len(ids),):
         raise ValueError("values must hold (len(ids),) pixels and (len(ids), bands) statistics")
@@ -305,8 +410,14 @@ def write_zone_values_csv(path: str, ids: Sequence[Any], values: ZoneValues, ban
     names = [str(b) for b in (range(B) if band_names is None else band_names)]
     if len(names) != B or len(set(names)) != B:
         raise ValueError(f"band_names must give {B} distinct names (got {list(band_names)!r})")
+    qnames, qvalues = [], None
+    if percentiles is not None:
+        qs, qvalues = percentiles
+        qnames, qvalues = ["percentile_%g" % q for q in check_percentiles(qs)], np.asarray(qvalues)
+        if len(set(qnames)) != len(qnames) or qvalues.shape != (len(ids), B, len(qnames)):
+            raise ValueError(f"percentiles must be (distinct percentiles, their ({len(ids)}, {B}, Q) values)")
     geo = georeference(profile)
-    cols = ["zone", "id", "pixels"] + [f"{k}_{b}" for b in names for k in VALUE_COLUMNS] + (["area_map"] if geo else [])
+    cols = ["zone", "id", "pixels"] + [f"{k}_{b}" for b in names for k in VALUE_COLUMNS + tuple(qnames)] + (["area_map"] if geo else [])
     with open(path, "w", newline="") as f:
         w = csv.writer(f)
         w.writerow(cols)
@@ -316,6 +427,7 @@ def write_zone_values_csv(path: str, ids: Sequence[Any], values: ZoneValues, ban
                 n = int(valid[z, b])
                 out.append(n)
                 out += [repr(float(getattr(values, k)[z, b])) if n else "" for k in VALUE_COLUMNS[1:]]
+                out += [repr(float(qvalues[z, b, i])) if n else "" for i in range(len(qnames))]
             if geo:
                 out.append(repr(float(int(values.pixels[z]) * geo[0] * geo[1])))
             w.writerow(out)
@@ -324,14 +436,26 @@ def write_zone_values_csv(path: str, ids: Sequence[Any], values: ZoneValues, ban
 
 # ---- mode=zonal_stats -------------------------------------------------------------------------------------------------------------------------
 CONFIG_KEYS = ("raster", "zones", "zone_id_property", "output", "bands", "nodata", "zones_crs")
+# keys without a default: given as ``+zonal_stats.<key>=...`` on the command line, or in a YAML config.  percentiles: None, or a list of
+# 1..MAX_PERCENTILES distinct numbers in [0, 100] (50 = the median): the columns percentile_<q>_<b> of the CSV
+OPTIONAL_KEYS = ("percentiles",)
+MAX_PERCENTILES = 32
 
 
 def zonal_stats_options(cfg: Dict[str, Any]) -> Dict[str, Any]:
     """The ``zonal_stats.*`` keys checked -> {raster, zones (a list of :class:`Zone` in the raster's coordinate system), bands, nodata,
-    output, profile}.  An unknown key, a bad value, a missing file, a band the file does not have, a feature that is no (Multi)Polygon,
+    output, profile, percentiles}.  An unknown key, a bad value, a missing file, a band the file does not have, a feature that is no (Multi)Polygon,
     or ``zones_crs`` with a raster that carries no coordinate system raises ValueError naming the key.  Reads the raster's header and the
     GeoJSON; touches no device."""
-    c = prep.Section(cfg, "zonal_stats", CONFIG_KEYS)
+    c = prep.Section(cfg, "zonal_stats", CONFIG_KEYS + OPTIONAL_KEYS)
+    percentiles = c.get("percentiles")
+    if percentiles is not None:
+        try:
+            percentiles = check_percentiles(list(percentiles) if isinstance(percentiles, (list, tuple)) else percentiles)
+            if len(percentiles) > MAX_PERCENTILES or len(set(percentiles)) != len(percentiles):
+                raise ValueError
+        except ValueError:
+            raise c.bad("percentiles", f"must be None or a list of 1..{MAX_PERCENTILES} distinct numbers in [0, 100]", c.get("percentiles")) from None
     raster, zfile = c.text("raster"), c.text("zones")
     for key, path in (("raster", raster), ("zones", zfile)):
         if path is None:
@@ -388,7 +512,8 @@ def zonal_stats_options(cfg: Dict[str, Any]) -> Dict[str, Any]:
     output = c.text("output")
     if output is None:
         output = os.path.join(os.path.dirname(raster), f"zonevalues_{os.path.splitext(os.path.basename(raster))[0]}.csv")
-    return dict(raster=raster, zones=zones, bands=[int(b) for b in bands], nodata=nodata, output=output, profile=profile)
+    return dict(raster=raster, zones=zones, bands=[int(b) for b in bands], nodata=nodata, output=output, profile=profile,
+                percentiles=percentiles)
 
 
 def _to_float32(a: np.ndarray, device) -> torch.Tensor:
@@ -401,14 +526,16 @@ def _to_float32(a: np.ndarray, device) -> torch.Tensor:
 
 def run_from_config(cfg: Dict[str, Any], device: Optional[str] = None) -> int:
     """``mode=zonal_stats``: the per-zone statistics of the GeoTIFF ``zonal_stats.raster`` over the polygons of ``zonal_stats.zones``,
-    written as the CSV of :func:`write_zone_values_csv`; prints one JSON line (zones, bands, zones without a valid pixel, the output
+    written as the CSV of :func:`write_zone_values_csv` (with ``zonal_stats.percentiles`` also the percentiles of :func:`zone_quantiles`);
+    prints one JSON line (zones, bands, zones without a valid pixel, the output
     path).  Every option is checked before the device is touched; there is no host path."""
     kw = zonal_stats_options(cfg)
     if device is None:
         raise RuntimeError("mode=zonal_stats runs on a HIP device and there is none (the tally has no host path)")
     a, profile = tiff.read(kw["raster"], kw["bands"])
-    ids, values = zone_value_table(_to_float32(a, device), kw["zones"], kw["nodata"], profile)
-    write_zone_values_csv(kw["output"], ids, values, kw["bands"], profile)
+    qs = kw["percentiles"]
+    ids, values, *rest = zone_value_table(_to_float32(a, device), kw["zones"], kw["nodata"], profile, qs)
+    write_zone_values_csv(kw["output"], ids, values, kw["bands"], profile, None if qs is None else (qs, rest[0]))
     print(json.dumps({"zonal_stats": {"zones": len(ids), "bands": len(kw["bands"]), "empty_zones": int((values.valid.sum(axis=1) == 0).sum()),
                                       "output": kw["output"]}}))
     return 0
