@@ -175,7 +175,7 @@ int ig_aug_blur(const float* src, float* dst, const int* apply, const float* ker
                 void* stream) {
     if (B == 0) return IG_OK;  // an empty batch carries null data pointers
     IG_REQUIRE(src && dst && apply && kernel2d && src != dst, "ig_aug_blur: null pointer or in-place call (src and dst must differ)");
-    IG_REQUIRE(ksize > 0 && (ksize & 1) && ksize / 2 < S, "ig_aug_blur: kernel size must be odd and smaller than 2*S (got %d)", ksize);
+    IG_REQUIRE(ksize > 0 && (ksize & 1) && ksize / 2 < S, "ig_aug_blur: kernel size must be odd with ksize / 2 < S, one reflection per side (got %d)", ksize);
     IG_REQUIRE(B >= 0 && CT > 0 && S > 0 && max_pixel > 0.f, "ig_aug_blur: bad sizes");
     const long total = (long)B * CT * S * S;
     if (total == 0) return IG_OK;

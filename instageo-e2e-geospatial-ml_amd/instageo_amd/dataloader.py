@@ -247,7 +247,12 @@ def draw_photometric_params(batch: int, im_size: int, augmentations: Optional[Di
 
 def apply_photometric(buf: torch.Tensor, labels: Optional[torch.Tensor], plan: List[Dict], chip_no_data_value: float = 0.0,
                       label_no_data_value: float = -1.0, max_pixel_value: float = 10000.0, noise: Optional[torch.Tensor] = None):
-    """Run a plan of :func:`draw_photometric_params` over a raw-domain batch (B, T*C, S, S) f32 [+ labels (B, S, S)]."""
+    """Run a plan of :func:`draw_photometric_params` over a raw-domain batch (B, T*C, S, S) f32 [+ labels (B, S, S)].  A noise step may
+    carry its own standard-normal field under ``"noise"`` (buf's shape); it takes precedence over the ``noise`` argument."""
+    S = buf.shape[-1]
+    if S % 2 and any(step["name"] == "brightness" for step in plan):  # checked before any kernel has run on the batch
+        raise ValueError(f"the brightness augmentation reads four pixels at a time and needs an even chip size (got {S}): "
+                         "use an even dataloader.img_size or switch the augmentation off")
     for step in plan:
         name, t, cfg = step["name"], step["table"].to(buf.device), step["cfg"]
         if name == "rotate":
@@ -258,7 +263,7 @@ def apply_photometric(buf: torch.Tensor, labels: Optional[torch.Tensor], plan: L
             k2 = gaussian_kernel2d(int(cfg.get("kernel_size", 3)), cfg.get("sigma_range", (0.1, 2.0))).to(buf.device)
             buf = ops.aug_blur(buf, t, k2, max_pixel_value)
         else:
-            buf = ops.aug_noise(buf, t, float(cfg.get("noise_std", 0.05)), max_pixel_value, noise)
+            buf = ops.aug_noise(buf, t, float(cfg.get("noise_std", 0.05)), max_pixel_value, step.get("noise", noise))
     return buf, labels
 
 
