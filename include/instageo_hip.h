@@ -1092,6 +1092,48 @@ int ig_label_buffer(const void* labels, int n, int H, int W, int elem_size, int 
                     void* out, int* valid_labels, int* hist, void* stream);
 int ig_label_limit(const void* labels, int n, int H, int W, int elem_size, const int* ptr, const int* pts, long P, int ignore_index, int K,
                    void* out, int* valid_labels, int* hist, void* stream);
+/* Spatially blocked train / val / test splitting of a chip dataset (split.hip; the step of the reference's instageo/data/data_splitter.py,
+ * under a rule of this project's own: DESIGN.md 3.34).  Everything the kernels compute is integer, so every result is unique: the same
+ * bits for any launch geometry and any order of arrival, run after run.  THE RULE:
+ * Location.  The location of a dataset row is the centre of the grid of its Input GeoTIFF, taken from the file's profile (the pixels are
+ *   never read) and brought to longitude / latitude in float64 (crs.inverse).  A row whose file has no georeferencing is dropped
+ *   (reason no_location).
+ * Position.  p = (cos(lat) cos(lon), cos(lat) sin(lon), sin(lat)) in float64; every component is multiplied by 2^29 and rounded half to
+ *   even to int32: |p_i| <= 2^29, one unit is about 1.2 cm on the ground.  This is done on the host; the kernels only see int32 (N, 3).
+ * Distance.  d2(p, q) = sum_i (p_i - q_i)^2 as an unsigned 64-bit integer: |p_i - q_i| <= 2^30, so d2 <= 3 * 2^60.  Kilometres, for the
+ *   buffer test and the report only, are 2 * 6371.0088 * asin(sqrt(d2) / 2^30), clipped at the antipode, in float64 on the host.  The
+ *   antimeridian and the poles are no special case.
+ * Spherical k-means.  Initial centres (host): the first is the point at index numpy.random.default_rng(random_state).integers(N); each
+ *   further one is the point with the largest d2 to its nearest chosen centre, ties to the smallest index; with fewer than n_clusters
+ *   distinct positions K becomes their number.  One Lloyd round is one launch of ig_split_assign: every point takes the centre with the
+ *   smallest d2, ties to the smallest centre index; per centre the int64 sums of x, y, z and the count; the number of points whose
+ *   assignment changed (assignments start at -1).  The host then divides the sums by the count in float64, normalises to unit length and
+ *   quantises as above; an empty centre, or one whose mean vector is zero, keeps its position.  Rounds stop when nothing changed or after
+ *   max_iter.
+ * Clusters to sets (host, K items).  Targets are floor(N * test_ratio) and floor(N * val_ratio) rows.  Test: the seed is the cluster
+ *   with the highest mean year when every row has a year (the first of 19xx | 20xx in the file name), ties to the smallest index, else
+ *   cluster 0; then the untaken cluster whose centre is nearest (d2) to any taken test centre is added, ties to the smallest index,
+ *   until the target is reached.  Val: the same among the remaining clusters, seeded by the remaining cluster at position
+ *   rng.integers(number remaining) of the same generator.  Train is the rest.  A set that would take every cluster raises.
+ * Audit and guard band.  The nearest-row search (ig_split_nearest) runs train -> (val u test) and val -> test: per row the smallest d2 to
+ *   a row of the other side and the SMALLEST INDEX that attains it.  With buffer_km > 0 the train rows nearer than that to any val or
+ *   test row are removed, then the val rows nearer than that to any test row (reason buffer).
+ * ig_split_assign: pts (N, 3) int32, centres (K, 3) int32, |coordinate| <= 2^29 (the caller guarantees it; differences are taken modulo
+ *   2^32, so any input is memory-safe).  assign (N) int32 is read (the previous assignment) and written; sums (K, 4) int64 += (sum x,
+ *   sum y, sum z, count) and changed (1) int32 += the points whose assignment differs from the one read; the caller zeroes both.  The
+ *   centres live in LDS; a thread owns 8 points, keeps the sums of a run of points with one centre in registers, adds them to per-centre
+ *   64-bit cells in LDS with integer atomics, and the workgroup adds its non-zero cells to sums with 64-bit integer atomics.
+ *   0 <= N < 2^30, 1 <= K <= 256; N = 0 returns IG_OK without touching a pointer.
+ * ig_split_nearest: a (Na, 3), b (Nb, 3) int32 as above -> d2 (Na) uint64 and idx (Na) int32, every element written exactly once.  A
+ *   thread owns 4 rows of a (1 when Na < 1024) in registers; b is staged through LDS in tiles of 1024 points and read as a broadcast; a
+ *   pair costs three subtractions and three 32 x 32 + 64 multiply-adds.  b is walked in ascending index with a strict comparison, so
+ *   the first minimum is the smallest index.  When the blocks of a alone do not fill the device b is cut into contiguous ranges, one
+ *   workgroup each, whose results go to a scratch buffer and are merged by a second kernel in ascending range order (smaller d2, then
+ *   smaller index: associative, so the result does not depend on the cut).  No floating point, no workgroup waits on another.
+ *   0 <= Na < 2^30, 1 <= Nb < 2^30; Na = 0 returns IG_OK without touching a pointer.  pts, centres, assign, changed, a, b and idx 4-byte,
+ *   sums and d2 8-byte aligned. */
+int ig_split_assign(const int* pts, int N, const int* centres, int K, int* assign, long long* sums, int* changed, void* stream);
+int ig_split_nearest(const int* a, int Na, const int* b, int Nb, unsigned long long* d2, int* idx, void* stream);
 int ig_confusion_update(const long long* y_true, const long long* y_pred, unsigned long long* confusion, long n, int k,
                         long ignore_index, int has_ignore, void* stream);
 /* torch.optim.AdamW step on a flat buffer (+ clip_weights, + bf16 shadow refresh)        base.py:103-126 */

@@ -190,7 +190,8 @@ enum IgScratchSlot {
     IG_SLOT_SPLITK = 5,         // split-K partial tiles (gemm.hip)
     IG_SLOT_REGION_SUMS = 6,    // ig_seg_loss: per-workgroup class sums of the region term + its 32 gradient coefficients
     IG_SLOT_CALIB_NLL = 7,      // ig_calib_nll_grid: per-workgroup partial sums of the temperature grid
-    IG_SCRATCH_SLOTS = 8
+    IG_SLOT_SPLIT_NEAREST = 8,  // ig_split_nearest: the per-range (d2, idx) candidates of the rows of a, merged by its second kernel
+    IG_SCRATCH_SLOTS = 9
 };
 void* ig_scratch(int slot, size_t bytes, hipStream_t st);                 // per (device, stream, slot): see runtime.hip
 void* ig_scratch2(int slot, size_t bytes, bool may_grow, hipStream_t st);  // may_grow = false: NULL instead of an allocation (stream captures)

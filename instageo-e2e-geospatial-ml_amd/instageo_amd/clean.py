@@ -17,8 +17,8 @@ buffering twice buffers twice.
 Device tensors go through ``ig_chip_nodata`` / ``ig_label_buffer`` / ``ig_label_limit``; host arrays take a vectorised numpy path that
 gives the same arrays, so the module works (and is tested) without a GPU.
 
-Deliberate difference: errors raise (the reference logs them and writes nothing).  Not done: ``data_splitter.py``, deriving MGRS tile
-ids for an observation table without ``mgrs_tile_id``, window sizes above 32.
+Deliberate difference: errors raise (the reference logs them and writes nothing).  Not done: deriving MGRS tile ids for an observation
+table without ``mgrs_tile_id``, window sizes above 32.
 """
 from __future__ import annotations
 

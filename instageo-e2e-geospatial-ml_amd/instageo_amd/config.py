@@ -200,7 +200,17 @@ DEFAULTS: Dict[str, Any] = {'root_dir': None,
  # the value that marks missing samples (None: the file's own no-data tag; NaN and Inf are always missing); zones_crs: the EPSG code of
  # the zones' coordinates (None: those of the raster)
  'zonal_stats': {'raster': None, 'zones': None, 'zone_id_property': None, 'output': None, 'bands': None, 'nodata': None,
-                 'zones_crs': None}}
+                 'zones_crs': None},
+ # mode=split_dataset (the step of the reference's instageo/data/data_splitter.py under its flag names where they exist, on a rule of this
+ # project's own; split.py): the rows of the dataset CSV input_file go to output_dir/splits/train.csv, val.csv and test.csv by whole
+ # spatial clusters (strategy kmeans: n_clusters, max_iter), whole years (year) or at random (random), seeded by random_state;
+ # include_val / include_test = false skip a set.  Not in the reference: buffer_km (the guard band: train rows nearer than that to a val
+ # or test row, then val rows nearer than that to a test row, are left out; 0 removes nothing), max_iter, root_dir (where relative paths
+ # of the CSV start; None: the CSV's folder), save_geojson (splits.geojson, one Point per row) and device: None = the device when there
+ # is one, host, cuda
+ 'split': {'input_file': None, 'output_dir': None, 'test_ratio': 0.2, 'val_ratio': 0.2, 'include_val': True, 'include_test': True,
+           'random_state': 42, 'n_clusters': 20, 'strategy': 'kmeans', 'buffer_km': 0.0, 'max_iter': 100, 'root_dir': None,
+           'save_geojson': True, 'device': None}}
 
 PRESETS: Dict[str, Dict[str, Any]] = {'sen1floods11': {'train': {'batch_size': 16, 'class_weights': [1, 3], 'ignore_index': -1},
                   'model': {'model_name': 'prithvi_eo_v1_100'},

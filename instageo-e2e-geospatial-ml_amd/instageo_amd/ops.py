@@ -1860,6 +1860,50 @@ def label_limit(labels, ptr, pts, ignore_index: int, K: int = 0):
     return out, valid, hist
 
 
+def _split_dtype(t) -> str:
+    return str(t.dtype).replace("torch.", "")
+
+
+def split_assign(pts, centres, assign, check_range: bool = True):
+    """``ig_split_assign`` (include/instageo_hip.h): one Lloyd round.  ``pts`` (N, 3) int32 and ``assign`` (N,) int32 on the device
+    (``assign`` is read and overwritten), ``centres`` (K, 3) int32 as a host array or a tensor -> (sums (K, 4) int64: sum x, sum y, sum z,
+    count per centre; changed (1,) int32), both on the device.  ``check_range=False`` skips the device reduction that checks
+    |coordinate| <= 2^29 of ``pts`` (a caller that quantised them itself)."""
+    import numpy as np
+
+    from . import split as S
+
+    cen = np.ascontiguousarray(centres.cpu().numpy() if torch.is_tensor(centres) else centres)
+    N, K = S.check_assign(tuple(pts.shape), _split_dtype(pts), cen, tuple(assign.shape), _split_dtype(assign))
+    assert assign.device == pts.device, "assign must live on the device of pts"
+    if check_range and N and int(pts.abs().max()) > S.SCALE:
+        raise ValueError(f"pts must be quantised unit vectors: |coordinate| <= 2^29 (got {int(pts.abs().max())})")
+    sums = torch.zeros((K, 4), dtype=torch.int64, device=pts.device)
+    changed = torch.zeros((1,), dtype=torch.int32, device=pts.device)
+    if N:
+        cen_d = torch.from_numpy(cen).to(pts.device)  # alive until the launch is queued; the copy is stream-ordered
+        # integer work: three multiply-adds per (point, centre)
+        _call("ig_split_assign", 3.0 * N * K, _p(pts), N, _p(cen_d), K, _p(assign), _p(sums), _p(changed), _stream())
+    return sums, changed
+
+
+def split_nearest(a, b, check_range: bool = True):
+    """``ig_split_nearest`` (include/instageo_hip.h): ``a`` (Na, 3) and ``b`` (Nb, 3) int32 on the device, Nb >= 1 -> (d2 (Na,) int64: the
+    smallest squared distance of every row of ``a`` to a row of ``b`` (the library's uint64, at most 3 * 2^60, so the int64 holds it
+    exactly); idx (Na,) int32: the smallest index of ``b`` that attains it)."""
+    from . import split as S
+
+    Na, Nb = S.check_nearest(tuple(a.shape), _split_dtype(a), tuple(b.shape), _split_dtype(b))
+    assert a.device == b.device, "a and b must live on one device"
+    if check_range and max(int(a.abs().max()) if Na else 0, int(b.abs().max())) > S.SCALE:
+        raise ValueError("a and b must be quantised unit vectors: |coordinate| <= 2^29")
+    d2 = torch.empty((Na,), dtype=torch.int64, device=a.device)
+    idx = torch.empty((Na,), dtype=torch.int32, device=a.device)
+    if Na:
+        _call("ig_split_nearest", 3.0 * Na * Nb, _p(a), Na, _p(b), Nb, _p(d2), _p(idx), _stream())
+    return d2, idx
+
+
 def confusion_update(y_true, y_pred, confusion, k: int, ignore_index: Optional[int]) -> None:
     assert y_true.dtype == torch.int64 and y_pred.dtype == torch.int64 and confusion.dtype == torch.int64
     _lib.call("ig_confusion_update", _p(y_true), _p(y_pred), _p(confusion), y_true.numel(), k,

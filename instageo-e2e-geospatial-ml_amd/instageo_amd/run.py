@@ -14,7 +14,9 @@ the dataset CSV the other modes read; the reference's ``instageo/data`` chip cre
 resampled onto the grids of label rasters, the reference's ``raster_chip_creator.py``, :mod:`instageo_amd.raster_chips`),
 ``create_s2_raster_chips`` (``s2_raster_chips.*``: Sentinel-2 band planes of several resolutions warped onto the grids of label rasters, the
 reference's ``S2RasterPipeline``, :mod:`instageo_amd.s2_raster_chips`), ``clean_chips``
-(``clean.*``: the reference's ``data_cleaner.py``: the no-data chip filter and label buffering / limiting, :mod:`instageo_amd.clean`) and
+(``clean.*``: the reference's ``data_cleaner.py``: the no-data chip filter and label buffering / limiting, :mod:`instageo_amd.clean`),
+``split_dataset`` (``split.*``: the dataset CSV cut into spatially blocked ``splits/train.csv`` / ``val.csv`` / ``test.csv`` with a leakage
+audit and a guard band, the step of the reference's ``data_splitter.py``, :mod:`instageo_amd.split`) and
 ``create_polygon_labels`` (``polygon_labels.*``: a GeoJSON of polygons burned into the label rasters and the records table that
 ``create_raster_chips`` takes, :mod:`instageo_amd.polygon_labels`) build no model; neither does ``create_composite`` (``composite.*``: the
 HLS scenes near each temporal step's date become one cloud-free composite scene per step, nearest clear date, median or medoid, written
@@ -61,6 +63,7 @@ PREP_MODES = {"create_chips": "chips",  # HLS tiles + points -> chips, label map
               "create_composite": "composite",  # the HLS scenes near each step's date -> one cloud-free composite scene per step
               "filter_s1": "s1_filter",  # Sentinel-1 RTC band files -> speckle-filtered (and dB) band files under the same names
               "clean_chips": "clean",  # drop no-data chips, buffer / limit the label maps of a chip dataset
+              "split_dataset": "split",  # a dataset CSV -> spatially blocked train / val / test CSVs with a leakage audit and a guard band
               "create_polygon_labels": "polygon_labels",  # a GeoJSON of polygons -> label rasters + records.csv
               "zonal_stats": "zonal"}  # a float raster + a GeoJSON of zones -> per-zone count, mean, std, min, max, sum as CSV
 
