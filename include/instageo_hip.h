@@ -1011,6 +1011,54 @@ int ig_composite(const short* bands, const long long* starts, const unsigned cha
  *   skipped, as is a workgroup beyond its plane's own number of tiles. */
 int ig_s1_speckle(const float* planes, const long long* starts, const int* sizes, const long long* tile_ptr, int N, long total, long tiles,
                   int h, int method, float looks, int has_src_nodata, float src_nodata, int to_db, float* out, int* counts, void* stream);
+/* Multi-temporal speckle filtering of Sentinel-1 RTC planes (s1_temporal.hip; Quegan and Yu 2001 with the boxcar local mean; not in the
+ * reference).  Every date of a stack is filtered by borrowing the other dates at the same pixel, at the input's resolution.  THE RULE:
+ * Inputs.  N float32 planes packed in `planes` with starts / sizes exactly as for ig_s1_speckle.  Every plane belongs to one GROUP (the
+ *   planes of one band on one pixel lattice of H_g x W_g pixels, lattice[2 g ..] = (H_g, W_g) int32) and one DATE (an index >= 0) and sits
+ *   at an integer offset on its group's lattice: place[3 p ..] = (row0, col0, date) int32 with row0, col0 >= 0, row0 + H <= H_g and
+ *   col0 + W <= W_g.  The members of group g are members[member_ptr[g] .. member_ptr[g + 1]) (plane indices; member_ptr: G + 1 ascending
+ *   int32 from 0 to M), ORDERED BY DATE, THEN BY THE ORDER GIVEN: the order in which orbit slices are tried, the slice order of
+ *   ig_s1_chip_cut.  All tables ON THE DEVICE.  h, has_src_nodata / src_nodata and to_db as in ig_s1_speckle.
+ * Presence and local mean.  A value is PRESENT by ig_s1_speckle's definition (finite and, with has_src_nodata != 0, not src_nodata).  The
+ *   local mean of plane p at one of its pixels whose value is present is m_p = A / (double)n, with A and n exactly ig_s1_speckle's first
+ *   moment and count: the window of w = 2 h + 1 around the pixel CLIPPED TO THE PLANE p (not to the lattice), present values only, FLOAT64
+ *   WITH CONTRACTION OFF, per window row left to right from +0.0, then the rows top to bottom from +0.0.  No second moment.
+ * Ratio sum at lattice pixel x.  Walk the group's members in order.  The value of a date is that of the FIRST member of the date that
+ *   covers x and is present there; later members of that date are not looked at for x.  The date CONTRIBUTES when that member's m > 0: it
+ *   adds r = x_p / m_p to R (float64, from +0.0, in date order) and 1 to c (int).  A date with no present member at x, or whose first
+ *   present member has m <= 0, contributes nothing.
+ * Output of plane k at x, for every element of every plane, WRITTEN EXACTLY ONCE (elements between planes are left alone).
+ *   Centre absent: the quiet NaN 0x7FC00000.  Centre present with m_k > 0 and c >= 1: y = m_k * (R / (double)c), each operation rounded
+ *   once.  Any other present centre: y = x_k, counted as PASSED THROUGH.  to_db = 0 stores (float)y; to_db = 1 stores
+ *   (float)(10 log10(y)) when y > 0, else the quiet NaN and the pixel is counted as DROPPED (a passed-through pixel can be dropped too, and
+ *   is then counted as both).  Overflow of the float conversion to +-inf is IEEE's and not special-cased.
+ * Counts.  counts (N, 4) int32 (the caller zeroes it), per plane: [0] += the present outputs (centre present and not dropped), [1] +=
+ *   the pixels dropped by the dB step, [2] += the pixels passed through, [3] += the present outputs at pixels with c == 1 (no temporal
+ *   gain there: with m_k > 0 the output is m_k (x_p / m_p), which for the date's own value is x_k up to rounding).
+ * Bits.  Each output depends on its pixel's windows and the member order alone: the same bits for any launch geometry, run after run.
+ *   Add, multiply, divide, compare and convert are correctly rounded, so the linear scale is the same bits on any IEEE-754 machine; dB goes
+ *   through each side's log10.
+ * ig_s1_temporal: one launch for all groups.  One workgroup of 256 threads owns a tile of 64 columns x 32 rows of one group's LATTICE;
+ *   tile_ptr (G + 1 ascending int64 from 0, built by the host: group g has ceil(H_g / 32) ceil(W_g / 64) tiles) lets workgroup b find its
+ *   group by binary search, `tiles` = tile_ptr[G] is the grid.  Two sweeps over the group's members inside the workgroup; a member whose
+ *   extent misses the tile is passed over.  Sweep 1 stages the member's part of the tile and a halo of h pixels in LDS as float32 (absent
+ *   values and what lies outside the plane as NaN, bounds tests at the load, no padding read), forms the row moments (A float64, K int32) and
+ *   the column sums as ig_s1_speckle does, and keeps R, c and the last date taken of a thread's 8 pixels in registers.  Sweep 2 stages
+ *   every member again (a cache hit), forms m_k and stores y: a wave writes 64 consecutive float32 of a row, 4 bytes per lane, which any
+ *   W and any 4-byte-aligned start allow.  LDS 49 680 bytes at h = 7: three workgroups per CU.  The counts are summed in the wave and the
+ *   workgroup and added with integer atomics per workgroup and touched plane; no workgroup waits on another.
+ *   Refused before any launch: h outside 1..7, has_src_nodata or to_db outside 0..1, src_nodata NaN, N < 0, G outside [1, N], M outside
+ *   [0, N], total < 0 or >= 2^40, tiles < 0 or > 2^31 - 1, null pointers, planes / out / sizes / place / lattice / member_ptr / members /
+ *   counts not 4-byte, starts / tile_ptr not 8-byte aligned, out overlapping planes.  N = 0 returns IG_OK without touching a pointer.  The
+ *   tables are on the device, so ops.s1_temporal checks them on the host before the upload (planes inside the buffer and not overlapping,
+ *   every plane inside its group's lattice, H_g W_g <= 2^31 - 1, the member lists consistent with the planes' groups and dates, at most 64
+ *   planes per group and 32 dates: the kernel's loop is a runtime loop, these bounds only size tables), and the kernel is the second fence:
+ *   a group whose lattice is not positive or whose member range breaks 0 <= begin <= end <= M is skipped, as is a workgroup beyond its
+ *   group's own number of tiles, a member entry outside [0, N) and a plane that breaks the bounds of ig_s1_speckle, has a negative offset
+ *   or date, or leaves its lattice. */
+int ig_s1_temporal(const float* planes, const long long* starts, const int* sizes, const int* place, const int* lattice,
+                   const int* member_ptr, const int* members, const long long* tile_ptr, int N, int G, int M, long total, long tiles, int h,
+                   int has_src_nodata, float src_nodata, int to_db, float* out, int* counts, void* stream);
 /* Web Mercator map tiles rendered from an overview pyramid (maptiles.hip; the reference's new_apps/backend/app/tiler_service.py answers
  * tiles/WebMercatorQuad/{z}/{x}/{y}@1x.png through TiTiler: a warp into EPSG:3857, an overview level, nearest sampling and a colormap or
  * rescale per request).  THE RULE:

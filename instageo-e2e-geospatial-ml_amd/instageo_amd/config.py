@@ -175,6 +175,12 @@ DEFAULTS: Dict[str, Any] = {'root_dir': None,
  # equivalent number of looks (4.4: IW GRD), scale = linear or db (cut dB chips with s1_chips.no_data_value=-9999: -1.0 is a valid dB
  # value), src_nodata = the files' own no-data value (None: each file's no-data tag)
  's1_filter': {'scenes': None, 'output_directory': None, 'method': 'lee', 'window': 7, 'looks': 4.4, 'scale': 'linear', 'src_nodata': None},
+ # mode=filter_s1_temporal (not in the reference; s1_temporal.py): scenes = the Sentinel-1 RTC band files (float32) of a stack in the nesting
+ # of s1_chips.scenes, dates of scenes of one file per band; every date is filtered by borrowing the other dates at the same pixel (Quegan
+ # and Yu's multi-temporal filter on a window x window local mean, odd, 3..15) and written under the same base name into output_directory,
+ # ready to be named in s1_chips.scenes or s1_filter.scenes.  Files are grouped per band by coordinate system and pixel lattice; a file
+ # alone on its lattice comes back unfiltered.  scale = linear or db, src_nodata = the files' own no-data value (None: each file's tag)
+ 's1_temporal': {'scenes': None, 'output_directory': None, 'bands': ['vv', 'vh'], 'window': 7, 'scale': 'linear', 'src_nodata': None},
  # mode=clean_chips (the reference's instageo/data/data_cleaner.py under its flag names; clean.py): drop the chips of chips_dataset_csv
  # whose share of no-data pixels is above the threshold, buffer the observation pixels of the label maps by window_size (or limit the maps
  # to the pixels of observation_points_csv), write output_chips_dataset_csv and clean_stats.json.  Not in the reference: num_classes

@@ -1720,6 +1720,39 @@ def s1_speckle(planes, starts, sizes, window: int = 7, method: str = "lee", look
     return out, counts
 
 
+def s1_temporal(planes, starts, sizes, group, date, offsets, window: int = 7, src_nodata=None, scale: str = "linear", out=None):
+    """``ig_s1_temporal`` (include/instageo_hip.h): ``planes`` the packed float32 planes as a 1-D tensor on the device; ``starts`` (N,),
+    ``sizes`` (N, 2) = (H, W), ``group`` (N,), ``date`` (N,) and ``offsets`` (N, 2) = (row0, col0) as host arrays: they are checked here
+    (every plane inside the buffer, no two overlapping, the lattices and member lists built from them, at most 64 planes and 32 dates per
+    group) and uploaded with the prefix table of tiles.  -> (out: float32 with the layout of ``planes``, elements outside every plane 0;
+    counts (N, 4) int32: the present outputs, the pixels the dB step dropped, the pixels passed through and the present outputs where one
+    date contributed).  ``out``: a contiguous float32 tensor of the size of ``planes`` to write into instead of a new one (only the
+    elements of the planes are written)."""
+    import numpy as np
+
+    from . import s1_temporal as Q
+
+    assert planes.dtype == torch.float32 and planes.dim() == 1, "the planes are one packed 1-D float32 buffer"
+    st, ss, h, snd, to_db, T = Q.check_temporal(int(planes.shape[0]), starts, sizes, group, date, offsets, window, src_nodata, scale)
+    N, dev, total = st.shape[0], planes.device, int(planes.shape[0])
+    pixels = int((ss[:, 0].astype(np.int64) * ss[:, 1]).sum())
+    if out is None:
+        out = (torch.empty if pixels == total else torch.zeros)(total, dtype=torch.float32, device=dev)
+    assert out.dtype == torch.float32 and out.shape == planes.shape and out.device == dev, "out is a float32 tensor of the size of planes"
+    counts = torch.zeros((N, 4), dtype=torch.int32, device=dev)
+    if N:
+        G = T.lattice.shape[0]
+        # alive until the launch is queued; the copies are stream-ordered.  One upload per element width; every int64 slice 8-byte aligned
+        tab = torch.from_numpy(np.concatenate([st, T.tile_ptr])).to(dev)
+        ints = torch.from_numpy(np.concatenate([ss.reshape(-1), T.place.reshape(-1), T.lattice.reshape(-1), T.member_ptr, T.members])).to(dev)
+        sd, pl, la, mp, mm = ints[: 2 * N], ints[2 * N : 5 * N], ints[5 * N : 5 * N + 2 * G], ints[5 * N + 2 * G : 5 * N + 3 * G + 1], ints[5 * N + 3 * G + 1 :]
+        # HBM bytes: every value read once (the second sweep and the halo come from the caches) and written once
+        work = 8.0 * pixels
+        _call("ig_s1_temporal", work, _p(planes), _p(tab[:N]), _p(sd), _p(pl), _p(la), _p(mp), _p(mm), _p(tab[N:]), N, G, N, total,
+              int(T.tile_ptr[-1]), h, int(snd is not None), float(snd) if snd is not None else 0.0, to_db, _p(out), _p(counts), _stream())
+    return out, counts
+
+
 TILE_STYLES ={"palette": 0, "ramp": 1, "rgb": 2}  # include/instageo_hip.h
 TILE_MAX_LEVELS = 13
 

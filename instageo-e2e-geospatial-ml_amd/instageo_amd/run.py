@@ -21,7 +21,9 @@ audit and a guard band, the step of the reference's ``data_splitter.py``, :mod:`
 ``create_raster_chips`` takes, :mod:`instageo_amd.polygon_labels`) build no model; neither does ``create_composite`` (``composite.*``: the
 HLS scenes near each temporal step's date become one cloud-free composite scene per step, nearest clear date, median or medoid, written
 under HLS-style names that ``chips.tiles`` takes with ``fmasks=None``, :mod:`instageo_amd.composite`) and ``filter_s1`` (``s1_filter.*``:
-Sentinel-1 RTC band files speckle-filtered, optionally to dB, under the same names for ``s1_chips.scenes``, :mod:`instageo_amd.s1_filter`);
+Sentinel-1 RTC band files speckle-filtered, optionally to dB, under the same names for ``s1_chips.scenes``, :mod:`instageo_amd.s1_filter`) and ``filter_s1_temporal`` (``s1_temporal.*``: the band files of a
+stack of dates filtered by Quegan and Yu's multi-temporal rule, every date borrowing the others at the same pixel, under the same names,
+:mod:`instageo_amd.s1_temporal`);
 ``create_s1_raster_chips`` (``s1_raster_chips.*``: Sentinel-1 RTC scenes stacked per date warped onto the grids of label rasters,
 :mod:`instageo_amd.s1_raster_chips`) is the radar sibling of ``create_raster_chips``.  Hydra, Lightning and Neptune are replaced by :mod:`instageo_amd.config` and the explicit loop below, which logs the
 same metric names and writes ``instageo_best_checkpoint.ckpt`` (``{"state_dict": ...}``) on the best
@@ -62,6 +64,7 @@ PREP_MODES = {"create_chips": "chips",  # HLS tiles + points -> chips, label map
               "create_s1_raster_chips": "s1_raster_chips",  # Sentinel-1 RTC scenes stacked per date + label rasters -> float32 chips on the labels' grids
               "create_composite": "composite",  # the HLS scenes near each step's date -> one cloud-free composite scene per step
               "filter_s1": "s1_filter",  # Sentinel-1 RTC band files -> speckle-filtered (and dB) band files under the same names
+              "filter_s1_temporal": "s1_temporal",  # the Sentinel-1 RTC band files of a stack of dates -> multi-temporally filtered band files
               "clean_chips": "clean",  # drop no-data chips, buffer / limit the label maps of a chip dataset
               "split_dataset": "split",  # a dataset CSV -> spatially blocked train / val / test CSVs with a leakage audit and a guard band
               "create_polygon_labels": "polygon_labels",  # a GeoJSON of polygons -> label rasters + records.csv

@@ -26,7 +26,8 @@ a GPU.  ``boxcar`` and ``lee`` in linear scale use correctly rounded operations 
 A dB value of exactly -1.0 collides with the default ``no_data_value`` of ``create_s1_chips``: cut dB chips with
 ``s1_chips.no_data_value=-9999``.
 
-Not done: multi-temporal (Quegan) filtering, refined-Lee edge windows, a vv / vh ratio band, calibration of GRD, SAFE input.
+Multi-temporal (Quegan) filtering of a stack of dates is :mod:`instageo_amd.s1_temporal`.  Not done: refined-Lee edge windows, a vv / vh
+ratio band, calibration of GRD, SAFE input.
 """
 from __future__ import annotations
 
