@@ -1011,6 +1011,51 @@ int ig_composite(const short* bands, const long long* starts, const unsigned cha
  *   skipped, as is a workgroup beyond its plane's own number of tiles. */
 int ig_s1_speckle(const float* planes, const long long* starts, const int* sizes, const long long* tile_ptr, int N, long total, long tiles,
                   int h, int method, float looks, int has_src_nodata, float src_nodata, int to_db, float* out, int* counts, void* stream);
+/* Refined Lee speckle filtering of Sentinel-1 RTC planes (s1_filter.hip; Lee 1981, the edge-aligned window that is the default speckle
+ * filter of ESA's SNAP toolbox; not in the reference).  The square window of ig_s1_speckle straddles both sides of an edge; this filter
+ * estimates from the half of a 7 x 7 window that lies on the pixel's own side of the local edge.  THE RULE:
+ * Exactly ig_s1_speckle's: presence, the packed planes and starts / sizes / tile_ptr, an absent centre stays absent (the quiet NaN
+ *   0x7FC00000), the dB step and the two counts per plane.  The window is 7 x 7 (h = 3), clipped to the plane.  All arithmetic is FLOAT64
+ *   WITH CONTRACTION OFF, every operation rounded on its own; an absent or outside value adds +0.0 and counts 0; s = 1 / (double)looks.
+ *   For a present centre x at (r, c):
+ * 1 Full window.  A, Q and n as in ig_s1_speckle at h = 3 (row moments left to right, rows top to bottom).  m = A / n,
+ *   v = max(Q / n - m m, 0), t = (m m) s, vx = (v - t) / (1 + s).  If not (v > 0 and vx > 0) the window is HOMOGENEOUS: y = m, which is
+ *   what LEE at h = 3 returns there, and steps 2 to 4 are skipped.
+ * 2 Sub-window means.  For i, j in {0, 1, 2} the 3 x 3 window centred at (r + 2 (i - 1), c + 2 (j - 1)), clipped to the plane: A3 is
+ *   summed per row left to right from +0.0, then the rows top to bottom from +0.0, n3 is its number of present values, M[i][j] = A3 / n3
+ *   (Mij below).  If any of the nine has n3 = 0, y is the LEE value of the full window from step 1's sums, y = m + (vx / v)(x - m), and
+ *   steps 3 and 4 are skipped (the FALLBACK: the outermost ring of a plane and pixels next to large holes).
+ * 3 Direction.  With c0 = M11, the four gradients, each evaluated as written, left to right:
+ *     g_d1 = |(M12 + M21 + M22) - (M00 + M01 + M10)|   halves SE / NW
+ *     g_d2 = |(M01 + M02 + M12) - (M10 + M20 + M21)|   halves NE / SW
+ *     g_h  = |(M02 + M12 + M22) - (M00 + M10 + M20)|   halves E / W
+ *     g_v  = |(M20 + M21 + M22) - (M00 + M01 + M02)|   halves S / N
+ *   The largest gradient wins; on a tie the first in the order d1, d2, h, v.  Inside the winning pair the first-named half wins if its
+ *   sub-window is at least as close to the centre mean as the other's: SE if |M22 - c0| <= |M00 - c0|, else NW; NE if
+ *   |M02 - c0| <= |M20 - c0|, else SW; E if |M12 - c0| <= |M10 - c0|, else W; S if |M21 - c0| <= |M01 - c0|, else N.
+ * 4 Half window.  With offsets (dy, dx) in [-3, 3]^2, dy down and dx right, the masks are E: dx >= 0, W: dx <= 0, S: dy >= 0,
+ *   N: dy <= 0, SE: dx + dy >= 0, NW: dx + dy <= 0, NE: dx - dy >= 0, SW: dx - dy <= 0; each holds 28 pixels and always the centre.  The
+ *   sums A', Q', n' run over the mask's present pixels inside the plane: per mask row left to right from +0.0, then the row sums top to
+ *   bottom from +0.0 over all seven rows (a pixel outside the mask adds +0.0, so a predicated 7 x 7 loop and a 28-term loop give the
+ *   same bits).  Then LEE on (A', Q', n', x): m' = A' / n', v' = max(Q' / n' - m' m', 0), t' = (m' m') s, vx' = (v' - t') / (1 + s),
+ *   b' = vx' / v' when v' > 0 and vx' > 0, else 0, y = m' + b' (x - m').
+ * 5 Scale and outputs as in ig_s1_speckle: to_db = 0 stores (float)y, to_db = 1 stores (float)(10 log10(y)) when y > 0, else the quiet
+ *   NaN and a DROPPED count; every element of every plane is written exactly once, counts (N, 2) int32 is zeroed by the caller.
+ *   Only correctly rounded operations occur before the dB step, so the linear scale is the same bits on any IEEE-754 machine and for any
+ *   launch geometry; dB goes through each side's log10.
+ * ig_s1_refined_lee: one launch for all planes with the tile of ig_s1_speckle (64 columns x 32 rows, 256 threads, the plane found by
+ *   binary search in tile_ptr, so one tile table serves both).  The tile and its halo of 3 pixels are staged in LDS as float32, absent
+ *   values and what lies outside the plane as NaN; the row moments of the full window go to LDS and are summed down the columns as in
+ *   ig_s1_speckle; the sub-window means of the (32 + 4) x (64 + 4) centres a tile can ask for go to LDS once as float64 (NaN where
+ *   n3 = 0), so a pixel reads nine of them; the half window is one uniform 7 x 7 loop over the staged tile under the chosen direction's
+ *   49-bit mask, taken only by the lanes that reach step 4.  Less than 80 KB of LDS: two workgroups per CU.  Stores and counts as in
+ *   ig_s1_speckle.
+ *   Refused before any launch: looks not > 0 or not finite, has_src_nodata or to_db outside 0..1, src_nodata NaN, N < 0, total < 0 or
+ *   >= 2^40, tiles < 0 or > 2^31 - 1, null pointers, planes / out / sizes / counts not 4-byte, starts / tile_ptr not 8-byte aligned, out
+ *   overlapping planes.  N = 0 returns IG_OK without touching a pointer.  The tables are on the device, so ops.s1_refined_lee checks them
+ *   on the host before the upload, and the kernel is the second fence, exactly as in ig_s1_speckle. */
+int ig_s1_refined_lee(const float* planes, const long long* starts, const int* sizes, const long long* tile_ptr, int N, long total,
+                      long tiles, float looks, int has_src_nodata, float src_nodata, int to_db, float* out, int* counts, void* stream);
 /* Multi-temporal speckle filtering of Sentinel-1 RTC planes (s1_temporal.hip; Quegan and Yu 2001 with the boxcar local mean; not in the
  * reference).  Every date of a stack is filtered by borrowing the other dates at the same pixel, at the input's resolution.  THE RULE:
  * Inputs.  N float32 planes packed in `planes` with starts / sizes exactly as for ig_s1_speckle.  Every plane belongs to one GROUP (the

@@ -171,7 +171,8 @@ DEFAULTS: Dict[str, Any] = {'root_dir': None,
                'device': None},
  # mode=filter_s1 (not in the reference, which neither filters speckle nor converts to dB; s1_filter.py): scenes = Sentinel-1 RTC band
  # files (float32) in the nesting of s1_chips.scenes, or one flat list; each is written under the same base name into output_directory,
- # ready to be named in s1_chips.scenes.  method = boxcar, lee or gamma_map over a window x window neighbourhood (odd, 3..15), looks = the
+ # ready to be named in s1_chips.scenes.  method = boxcar, lee or gamma_map over a window x window neighbourhood (odd, 3..15), or refined_lee
+ # (edge-aligned half windows; window must be 7), looks = the
  # equivalent number of looks (4.4: IW GRD), scale = linear or db (cut dB chips with s1_chips.no_data_value=-9999: -1.0 is a valid dB
  # value), src_nodata = the files' own no-data value (None: each file's no-data tag)
  's1_filter': {'scenes': None, 'output_directory': None, 'method': 'lee', 'window': 7, 'looks': 4.4, 'scale': 'linear', 'src_nodata': None},

@@ -1701,6 +1701,7 @@ def s1_speckle(planes, starts, sizes, window: int = 7, method: str = "lee", look
     from . import s1_filter as F
 
     assert planes.dtype == torch.float32 and planes.dim() == 1, "the planes are one packed 1-D float32 buffer"
+    assert method != "refined_lee", "refined_lee has an entry point of its own: ops.s1_refined_lee"
     st, ss, h, code, lk, snd, to_db = F.check_speckle(int(planes.shape[0]), starts, sizes, window, method, looks, src_nodata, scale)
     N, dev, total = st.shape[0], planes.device, int(planes.shape[0])
     pixels = int((ss[:, 0].astype(np.int64) * ss[:, 1]).sum())
@@ -1716,6 +1717,32 @@ def s1_speckle(planes, starts, sizes, window: int = 7, method: str = "lee", look
         # HBM bytes: every value read once (the halo comes from the caches) and written once
         work = 8.0 * pixels
         _call("ig_s1_speckle", work, _p(planes), _p(tab[:N]), _p(sd), _p(tab[N:]), N, total, int(tp[-1]), h, code, float(lk), int(snd is not None),
+              float(snd) if snd is not None else 0.0, to_db, _p(out), _p(counts), _stream())
+    return out, counts
+
+
+def s1_refined_lee(planes, starts, sizes, looks: float = 4.4, src_nodata=None, scale: str = "linear", out=None):
+    """``ig_s1_refined_lee`` (include/instageo_hip.h): the refined Lee filter on the packed planes of :func:`s1_speckle`, with the same
+    host-side checks of ``starts`` and ``sizes``, the same tile table and the same outputs.  The window is 7 x 7."""
+    import numpy as np
+
+    from . import s1_filter as F
+
+    assert planes.dtype == torch.float32 and planes.dim() == 1, "the planes are one packed 1-D float32 buffer"
+    st, ss, _, _, lk, snd, to_db = F.check_speckle(int(planes.shape[0]), starts, sizes, F.REFINED_WINDOW, "refined_lee", looks, src_nodata, scale)
+    N, dev, total = st.shape[0], planes.device, int(planes.shape[0])
+    pixels = int((ss[:, 0].astype(np.int64) * ss[:, 1]).sum())
+    if out is None:
+        out = (torch.empty if pixels == total else torch.zeros)(total, dtype=torch.float32, device=dev)
+    assert out.dtype == torch.float32 and out.shape == planes.shape and out.device == dev, "out is a float32 tensor of the size of planes"
+    counts = torch.zeros((N, 2), dtype=torch.int32, device=dev)
+    if N:
+        tp = F.tile_table(ss)
+        # alive until the launch is queued; the copies are stream-ordered.  One upload of the int64 tables; both slices 8-byte aligned
+        tab = torch.from_numpy(np.concatenate([st, tp])).to(dev)
+        sd = torch.from_numpy(ss.reshape(-1)).to(dev)
+        work = 8.0 * pixels  # HBM bytes, as for ig_s1_speckle
+        _call("ig_s1_refined_lee", work, _p(planes), _p(tab[:N]), _p(sd), _p(tab[N:]), N, total, int(tp[-1]), float(lk), int(snd is not None),
               float(snd) if snd is not None else 0.0, to_db, _p(out), _p(counts), _stream())
     return out, counts
 

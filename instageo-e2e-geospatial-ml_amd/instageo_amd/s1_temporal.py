@@ -20,7 +20,7 @@ a GPU.  The linear scale uses correctly rounded operations only: both paths writ
 function, so dB values may differ in the last float32 bit.
 
 Not done: dates on different lattices or coordinate systems (warp them first: such files land in groups of their own and come back
-unfiltered, listed as ``alone``), a Lee or other estimator in place of the boxcar mean, the vv / vh ratio band, host tiling of a group
+unfiltered, listed as ``alone``), a Lee, refined Lee (``s1_filter``'s edge-aligned window) or other estimator in place of the boxcar mean, the vv / vh ratio band, host tiling of a group
 that exceeds ``max_bytes``.
 """
 from __future__ import annotations

@@ -1,9 +1,10 @@
-"""Speckle filtering: HIP-event time of ``ig_s1_speckle`` on one date of three synthetic Sentinel-1 RTC scenes of 11000 x 11000 pixels x 2
-bands (six float32 planes, 0.73 G values), windows 7 and 15, each method, linear and dB, next to a device copy of the same number of bytes
-(read plus written) and to the numpy host path on rows of one plane.  About 3 % of the values are NaN and a border of 200 pixels of every
-plane is the source's no-data value.
+"""Speckle filtering: HIP-event time of ``ig_s1_speckle`` and ``ig_s1_refined_lee`` on one date of three synthetic Sentinel-1 RTC scenes
+of 11000 x 11000 pixels x 2 bands (six float32 planes, 0.73 G values), windows 7 and 15 (``refined_lee``: 7 only), each method, linear
+and dB, next to a device copy of the same number of bytes (read plus written) and to the numpy host path on rows of one plane.  About
+3 % of the values are NaN and a border of 200 pixels of every plane is the source's no-data value.
 
-    python tools/s1_filter_bench.py [--reps 5] [--side 11000] [--host-rows 256] [--out profiles/s1_filter.txt]
+    python tools/s1_filter_bench.py [--reps 5] [--side 11000] [--host-rows 256] [--windows 7 15] [--methods lee refined_lee]
+                                    [--out profiles/s1_filter.txt]
 """
 import argparse
 import os
@@ -35,6 +36,8 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--side", type=int, default=11000)
     ap.add_argument("--host-rows", type=int, default=256, help="rows of one plane the numpy host path is timed on (scaled to all planes)")
+    ap.add_argument("--windows", type=int, nargs="+", default=[7, 15])
+    ap.add_argument("--methods", nargs="+", default=None, help="the methods to time (default: all; refined_lee runs at window 7 only)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     from instageo_amd import s1_filter as F
@@ -74,11 +77,15 @@ def main():
     emit(f"{moved / 1e6:7.1f} MB read + written; a device copy moving as many bytes: {copy_us:9.1f} us = {moved / copy_us / 1e6:5.2f} TB/s")
     rows = min(args.host_rows, side)
     host_plane = planes[:HW].view(side, side)[:rows].contiguous().view(-1).cpu().numpy()
-    for window in (7, 15):
+    for window in args.windows:
         h = window // 2
         for method, code in F.METHODS.items():
+            if args.methods and method not in args.methods or method == "refined_lee" and window != F.REFINED_WINDOW:
+                continue
             for scale, to_db in F.SCALES.items():
                 run = lambda: ns.s1_speckle(planes, starts, sizes, tile_ptr, N, N * HW, int(tp[-1]), h, code, F.LOOKS, 1, snd, to_db, out, counts)  # noqa: E731
+                if method == "refined_lee":  # an entry point of its own, without h and method
+                    run = lambda: ns.s1_refined_lee(planes, starts, sizes, tile_ptr, N, N * HW, int(tp[-1]), F.LOOKS, 1, snd, to_db, out, counts)  # noqa: E731
                 us = timed(run, args.reps)
                 counts.zero_()
                 run()
