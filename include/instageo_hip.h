@@ -446,6 +446,39 @@ int ig_zone_toggle(const int* edges, const unsigned char* bit, const long long* 
                    int W, void* stream);
 int ig_zone_tally(unsigned long long* canvas, const signed char* cls, unsigned long long* counts, int H, int W, int ncls, int fill,
                   int write_mask, void* stream);
+/* all_touched rasterisation (zonal.hip; not in the reference): a second rule on the grid, fixed point and limits of the block above
+ * (Q = 256, |X|, |Y| <= 2^29, H * W <= 2^31 - 1), for features that are small next to a pixel.  The default stays the centre rule.
+ * THE RULE.  Pixel (r, c) is the square 256 c <= X <= 256 c + 256, 256 r <= Y <= 256 r + 256.  An edge TOUCHES pixel (r, c) iff the closed
+ *   segment (x0, y0)-(x1, y1) meets the OPEN square (256 c, 256 c + 256) x (256 r, 256 r + 256).  Under all_touched a pixel belongs to a
+ *   zone or feature iff its centre is inside by the rule above OR one of the zone's edges touches it.  The square is open on purpose: an
+ *   edge that runs along a pixel border touches neither side, so a polygon whose vertices sit on the pixel lattice selects the same pixels
+ *   under both rules (a closed square would grow it by a ring).  This is not GDAL's line walker; for vertices in general position it is
+ *   expected to select the pixels of rasterio's all_touched=True, which has not been verified.
+ * ROWS.  With ymin = min(y0, y1), ymax = max(y0, y1) an edge touches exactly the rows floor(ymin / 256) <= r <= ceil(ymax / 256) - 1,
+ *   clamped to [0, H): none when ymin = ymax lies on a row border.
+ * COLUMNS of row r.  A non-horizontal edge: ya = max(ymin, 256 r), yb = min(ymax, 256 r + 256) and the abscissae x(ya), x(yb) as exact
+ *   rationals N / |y1 - y0|, N = x0 (y1 - y0) + (x1 - x0)(y - y0) negated when y1 < y0, |N| < 2^61 (int64).  A horizontal edge: its two x
+ *   coordinates.  With lo the smaller and hi the larger, the touched columns are exactly floor(lo / 256) <= c <= ceil(hi / 256) - 1,
+ *   clamped to [0, W): none for a vertical edge on a column border or a span outside the raster.  Nothing is clamped ONTO column 0,
+ *   unlike the toggle.  Floor and ceiling division on int64 with the denominator made positive; no floating point anywhere.
+ * ig_zone_touch_rows: edges (E, 4) int32, 16-byte aligned; rows[e] (E int32) = the number of rows in [0, H) edge e touches (ROWS).  The
+ *   exclusive scan is the caller's: first (E int64), total T <= 2^38.  An edge with a coordinate beyond 2^29 touches nothing.
+ * ig_zone_touch: one work item per (edge, touched row) pair 0..T-1, the edge found by binary search in first.  The item sets bit bit[e]
+ *   (E uint8, 0..63) of touch[r][c] for every column c of the span (COLUMNS) with 64-bit atomic ORs, which are order-independent: two
+ *   runs give the same bits.  touch is a (H, W) uint64 canvas the caller zeroes.  A lane writes a span of up to 4 columns itself; longer
+ *   spans (a near-horizontal edge can span the row) are written by the item's whole wave, one span after the other, 64 adjacent columns
+ *   per step.  Items that first places outside their edge's rows, and bits outside 0..63, are dropped.
+ * ig_zone_touch_merge: canvas (H, W) uint64 holds the toggles of the pass (ig_zone_toggle).  Per row m = (inclusive prefix XOR of the
+ *   toggles, by the device function ig_zone_tally scans with (one rule, one scan)) | touch, and canvas[r][c] = m[c] ^ m[c - 1] with m[-1] = 0 is
+ *   written back in place: the canvas is a toggle canvas again whose prefix XOR is the all_touched mask, and ig_zone_tally,
+ *   ig_zone_value_tally, ig_zone_quantile_hist and ig_burn_resolve take it as it is (the last feature that contains or touches a pixel
+ *   is the highest set bit).  touch is only read.  A workgroup owns whole rows and reads each chunk of 1024 columns before it writes it;
+ *   no kernel waits on another workgroup; every launch does a fixed amount of work.
+ * E = 0, T = 0 or H * W = 0 returns IG_OK without touching a pointer.  canvas, touch and first are 8-byte aligned. */
+int ig_zone_touch_rows(const int* edges, int* rows, long E, int H, void* stream);
+int ig_zone_touch(const int* edges, const unsigned char* bit, const long long* first, unsigned long long* touch, long E, long T, int H,
+                  int W, void* stream);
+int ig_zone_touch_merge(unsigned long long* canvas, const unsigned long long* touch, int H, int W, void* stream);
 /* Zonal statistics of float rasters (zonal.hip; not in the reference): per zone and band the count, mean, sum of squared deviations,
  * minimum and maximum of a band-major float32 raster (B, H, W) under the inside masks of the block above.  canvas (H, W) uint64 holds the
  * TOGGLES of one pass as ig_zone_toggle leaves them; it is read, never written, so one canvas serves any number of calls (band groups).

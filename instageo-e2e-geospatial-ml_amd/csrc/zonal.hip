@@ -18,6 +18,12 @@
 //                              the round's 8-bit digit: unsigned integer atomics, equal targets merged across the wave first
 //   7  zone_quantile_pick_kernel  per (band, zone bit, slot): the digit that holds the wanted rank; after the last round the values
 //   (6) and (7) count with integer atomics only and select members of the data: unique results as well.
+//   8  zone_touch_rows_kernel  all_touched (the rule: include/instageo_hip.h): per edge the number of raster rows whose open strip it meets
+//   9  zone_touch_kernel       per (edge, touched row) pair: the columns whose open square the edge meets in that row, exact rationals in
+//                              int64, and a 64-bit atomic OR of the zone's bit into each of them on a second canvas.  A lane writes a span of
+//                              up to ZT_SHORT columns itself; longer ones are taken by the whole wave, one after the other, 64 columns a step
+//   10 zone_touch_merge_kernel per row: m = (prefix XOR of the toggles, the scan of (3)) | touch, written back as toggles m[c] ^ m[c - 1]:
+//                              the canvas is a toggle canvas again and (3), (4), (6) and ig_burn_resolve work on it as they are
 //
 // Up to 64 zones share a pass: one bit of a uint64 canvas each.  A pass costs one sweep of the 8-byte canvas (read, optionally written)
 // and of the 1-byte class map, whatever the number of edges; the toggles are one atomic per crossing.
@@ -115,6 +121,137 @@ __device__ __forceinline__ void zone_scan_chunk(unsigned long long (&v)[ZVPT], u
     }
 #pragma unroll
     for (int j = 0; j < ZVPT; ++j) v[j] ^= pre;
+}
+
+// ---- all_touched: the pixels whose open square an edge meets --------------------------------------------------------------------------------
+constexpr int ZT_SHORT = 4;  // columns a lane writes on its own; a longer span is written by its wave
+
+// rows r whose open strip (256 r, 256 r + 256) the edge's y range meets: floor(ymin / 256) <= r <= ceil(ymax / 256) - 1, in [0, H).  Empty
+// for a horizontal edge on a row border; an edge with a coordinate beyond the limit touches nothing (as it crosses nothing).
+__device__ __forceinline__ RowSpan touch_rows_of(const int4 e, int H) {
+    const int lim = ZLIMIT;
+    if (e.x < -lim || e.x > lim || e.y < -lim || e.y > lim || e.z < -lim || e.z > lim || e.w < -lim || e.w > lim) return RowSpan{0, 0};
+    const int ylo = e.y < e.w ? e.y : e.w, yhi = e.y < e.w ? e.w : e.y;
+    int lo = ylo >> 8;              // floor: arithmetic shift
+    int hi = ((yhi + ZQ - 1) >> 8) - 1;  // ceil(yhi / 256) - 1
+    lo = lo < 0 ? 0 : lo;
+    hi = hi > H - 1 ? H - 1 : hi;
+    return RowSpan{lo, hi >= lo ? hi - lo + 1 : 0};
+}
+
+__device__ __forceinline__ long long floor_div(long long n, long long d) {  // d > 0
+    const long long q = n / d;
+    return n % d < 0 ? q - 1 : q;
+}
+__device__ __forceinline__ long long ceil_div(long long n, long long d) {  // d > 0
+    const long long q = n / d;
+    return n % d > 0 ? q + 1 : q;
+}
+
+struct ColSpan {
+    int lo, n;  // first touched column in [0, W) and their number
+};
+
+// The columns of row r (one of touch_rows_of) whose open square the edge meets.  The part of the edge inside the closed strip runs from
+// ya = max(ymin, 256 r) to yb = min(ymax, 256 r + 256), ya < yb for a non-horizontal edge; its abscissae there are N / D with
+// N = x0 (y1 - y0) + (x1 - x0)(y - y0), D = y1 - y0, both negated when y1 < y0: |N| < 2^61.  A horizontal edge has its own two ends.
+// With lo / hi the smaller / larger: floor(lo / 256) <= c <= ceil(hi / 256) - 1, clamped to [0, W) (nothing is moved onto column 0).
+__device__ __forceinline__ ColSpan touch_cols_of(const int4 e, int r, int W) {
+    long long den = (long long)e.w - e.y, a, b;
+    if (den == 0) {
+        den = 1;
+        a = e.x, b = e.z;
+    } else {
+        const long long ylo = e.y < e.w ? e.y : e.w, yhi = e.y < e.w ? e.w : e.y;
+        const long long top = (long long)ZQ * r, ya = ylo > top ? ylo : top, yb = yhi < top + ZQ ? yhi : top + ZQ;
+        a = (long long)e.x * den + ((long long)e.z - e.x) * (ya - e.y);
+        b = (long long)e.x * den + ((long long)e.z - e.x) * (yb - e.y);
+        if (den < 0) den = -den, a = -a, b = -b;
+    }
+    den *= ZQ;
+    long long lo = floor_div(a < b ? a : b, den), hi = ceil_div(a < b ? b : a, den) - 1;
+    lo = lo < 0 ? 0 : lo;
+    hi = hi > W - 1 ? W - 1 : hi;
+    return ColSpan{(int)lo, hi >= lo ? (int)(hi - lo + 1) : 0};
+}
+
+__global__ __launch_bounds__(ZTPB) void zone_touch_rows_kernel(const int4* __restrict__ edges, int* __restrict__ rows, long E, int H) {
+    const long e = blockIdx.x * (long)ZTPB + threadIdx.x;
+    if (e < E) rows[e] = touch_rows_of(edges[e], H).n;
+}
+
+// No lane leaves before the end: the long spans are written by all 64 lanes of the wave.  Every address is row r < H, column < W of the
+// (H, W) canvas: r and the span come clamped from touch_rows_of / touch_cols_of, and a lane without an item holds an empty span.
+__global__ __launch_bounds__(ZTPB) void zone_touch_kernel(const int4* __restrict__ edges, const unsigned char* __restrict__ bit,
+                                                          const long long* __restrict__ first, unsigned long long* __restrict__ touch,
+                                                          long E, long T, int H, int W) {
+    const long t = blockIdx.x * (long)ZTPB + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    long at = 0;  // canvas index of the span's first pixel
+    int n = 0;    // its columns
+    unsigned long long mask = 0;
+    if (t < T) {
+        long lo = 0, hi = E;  // the last e with first[e] <= t, as zone_toggle_kernel finds it
+        while (hi - lo > 1) {
+            const long mid = (lo + hi) >> 1;
+            if (first[mid] <= t) lo = mid;
+            else hi = mid;
+        }
+        const long long k = t - first[lo];
+        const int4 e = edges[lo];
+        const RowSpan rows = touch_rows_of(e, H);
+        const unsigned b = bit[lo];
+        if (k >= 0 && k < rows.n && b < (unsigned)ZBITS) {
+            const int r = rows.lo + (int)k;
+            const ColSpan cols = touch_cols_of(e, r, W);
+            at = (long)r * W + cols.lo;
+            n = cols.n;
+            mask = 1ull << b;
+        }
+    }
+    if (n <= ZT_SHORT)
+        for (int i = 0; i < n; ++i) atomicOr(touch + at + i, mask);
+    for (unsigned long long todo = __ballot(n > ZT_SHORT); todo; todo &= todo - 1) {  // the same in every lane
+        const int src = __ffsll((long long)todo) - 1;
+        const long s_at = __shfl(at, src, 64);
+        const int s_n = __shfl(n, src, 64);
+        const unsigned long long s_mask = __shfl(mask, src, 64);
+        for (int i = lane; i < s_n; i += 64) atomicOr(touch + s_at + i, s_mask);
+    }
+}
+
+// grid.x workgroups take rows blockIdx.x, blockIdx.x + gridDim.x, ...; a chunk is read (canvas and touch) before the scan's barrier and
+// written after it, each thread its own columns.  The mask left of a thread's run is the exclusive prefix XOR the scan gives it, OR the
+// touch bits of that column, which it reads itself: no further exchange between lanes.
+__global__ __launch_bounds__(ZTPB) void zone_touch_merge_kernel(unsigned long long* __restrict__ canvas,
+                                                                const unsigned long long* __restrict__ touch, int H, int W) {
+    __shared__ unsigned long long wtot[2][ZWAVES];
+    int par = 0;
+    for (int r = blockIdx.x; r < H; r += gridDim.x) {
+        unsigned long long* row = canvas + (long)r * W;
+        const unsigned long long* trow = touch + (long)r * W;
+        unsigned long long carry = 0;
+        for (long c0 = 0; c0 < W; c0 += ZCHUNK, par ^= 1) {
+            const long c = c0 + (long)threadIdx.x * ZVPT;
+            unsigned long long v[ZVPT], tb[ZVPT];
+#pragma unroll
+            for (int j = 0; j < ZVPT; ++j) {
+                const bool live = c + j < W;
+                v[j] = live ? row[c + j] : 0ull;
+                tb[j] = live ? trow[c + j] : 0ull;
+            }
+            const unsigned long long left_touch = c > 0 && c < W ? trow[c - 1] : 0ull;
+            const unsigned long long own = v[0];
+            zone_scan_chunk(v, carry, wtot[par]);
+            unsigned long long prev = c > 0 ? ((v[0] ^ own) | left_touch) : 0ull;  // m[c - 1]; XOR undoes itself: inclusive ^ own = exclusive
+#pragma unroll
+            for (int j = 0; j < ZVPT; ++j) {
+                const unsigned long long m = v[j] | tb[j];
+                if (c + j < W) row[c + j] = m ^ prev;
+                prev = m;
+            }
+        }
+    }
 }
 
 // cls = NULL: the masks only, nothing is counted.  grid.x workgroups take rows blockIdx.x, blockIdx.x + gridDim.x, ...  LDS: tab[64][ncls + 1]
@@ -563,6 +700,38 @@ int ig_zone_tally(unsigned long long* canvas, const signed char* cls, unsigned l
     IG_REQUIRE(((uintptr_t)canvas & 7) == 0 && ((uintptr_t)counts & 7) == 0, "ig_zone_tally: canvas and counts must be 8-byte aligned");
     return ig_launch<zone_tally_kernel>("ig_zone_tally", dim3((unsigned)(H < MAX_WG ? H : MAX_WG)), dim3(ZTPB), ZBITS * (ncls + 1) * 4,
                                         ST(stream), canvas, cls, counts, H, W, ncls, fill, write_mask);
+}
+
+int ig_zone_touch_rows(const int* edges, int* rows, long E, int H, void* stream) {
+    IG_REQUIRE(E >= 0 && E <= 0x7fffffffL, "ig_zone_touch_rows: need 0 <= E <= 2^31 - 1 (got %ld)", E);
+    IG_REQUIRE(H >= 0, "ig_zone_touch_rows: need H >= 0 (got %d)", H);
+    if (E == 0) return IG_OK;
+    IG_REQUIRE(edges && rows, "ig_zone_touch_rows: null pointer");
+    IG_REQUIRE(((uintptr_t)edges & 15) == 0, "ig_zone_touch_rows: edges must be 16-byte aligned");
+    return ig_launch<zone_touch_rows_kernel>("ig_zone_touch_rows", blocks_for(E), dim3(ZTPB), 0, ST(stream), (const int4*)edges, rows, E, H);
+}
+
+int ig_zone_touch(const int* edges, const unsigned char* bit, const long long* first, unsigned long long* touch, long E, long T, int H, int W,
+                  void* stream) {
+    IG_REQUIRE(E >= 0 && E <= 0x7fffffffL, "ig_zone_touch: need 0 <= E <= 2^31 - 1 (got %ld)", E);
+    IG_REQUIRE(T >= 0 && T <= (1L << 38), "ig_zone_touch: need 0 <= T <= 2^38 touched rows per call (got %ld)", T);
+    IG_REQUIRE_RASTER("ig_zone_touch");
+    if (E == 0 || T == 0 || (long)H * W == 0) return IG_OK;
+    IG_REQUIRE(edges && bit && first && touch, "ig_zone_touch: null pointer");
+    IG_REQUIRE(((uintptr_t)edges & 15) == 0, "ig_zone_touch: edges must be 16-byte aligned");
+    IG_REQUIRE(((uintptr_t)first & 7) == 0 && ((uintptr_t)touch & 7) == 0, "ig_zone_touch: first and touch must be 8-byte aligned");
+    return ig_launch<zone_touch_kernel>("ig_zone_touch", blocks_for(T), dim3(ZTPB), 0, ST(stream), (const int4*)edges, bit, first, touch, E, T,
+                                        H, W);
+}
+
+int ig_zone_touch_merge(unsigned long long* canvas, const unsigned long long* touch, int H, int W, void* stream) {
+    IG_REQUIRE_RASTER("ig_zone_touch_merge");
+    if ((long)H * W == 0) return IG_OK;
+    IG_REQUIRE(canvas && touch, "ig_zone_touch_merge: null pointer");
+    IG_REQUIRE(((uintptr_t)canvas & 7) == 0 && ((uintptr_t)touch & 7) == 0, "ig_zone_touch_merge: canvas and touch must be 8-byte aligned");
+    IG_REQUIRE(canvas != touch, "ig_zone_touch_merge: canvas and touch must be two canvases");
+    return ig_launch<zone_touch_merge_kernel>("ig_zone_touch_merge", dim3((unsigned)(H < MAX_WG ? H : MAX_WG)), dim3(ZTPB), 0, ST(stream), canvas,
+                                              touch, H, W);
 }
 
 int ig_zone_value_grid(int H) { return H < 0 ? 0 : H < ZV_MAX_WG ? H : ZV_MAX_WG; }

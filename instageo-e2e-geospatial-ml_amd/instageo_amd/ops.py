@@ -1053,6 +1053,42 @@ def zone_tally(canvas, classmap, counts, ncls: int = 2, fill: int = -1, write_ma
           int(ncls), int(fill), int(bool(write_mask)), _stream())
 
 
+def zone_touch_rows(edges, H: int):
+    """edges (E, 4) int32 {x0, y0, x1, y1} in Q = 256 fixed point -> (E,) int32: the rows in [0, H) each edge touches under the
+    all_touched rule (include/instageo_hip.h): the counterpart of :func:`zone_edge_rows`."""
+    assert edges.dtype == torch.int32 and edges.dim() == 2 and edges.shape[1] == 4
+    E = edges.shape[0]
+    rows = torch.zeros(E, dtype=torch.int32, device=edges.device)
+    if E:
+        _call("ig_zone_touch_rows", float(E) * 20, _p(edges), _p(rows), E, int(H), _stream())
+    return rows
+
+
+def zone_touch(edges, bit, first, touch, n_rows: int) -> None:
+    """Set, for each of the ``n_rows`` (edge, touched row) pairs, bit ``bit[e]`` of ``touch`` (H, W) int64 in every column whose open
+    square the edge meets in that row; ``first`` (E,) int64 = the exclusive scan of :func:`zone_touch_rows`.  The caller zeroes ``touch``."""
+    E = edges.shape[0]
+    assert edges.dtype == torch.int32 and edges.dim() == 2 and edges.shape[1] == 4 and bit.dtype == torch.uint8 and bit.numel() == E
+    assert first.dtype == torch.int64 and first.numel() == E and touch.dtype == torch.int64 and touch.dim() == 2 and touch.is_contiguous()
+    H, W = touch.shape
+    T = int(n_rows)
+    if E == 0 or T == 0 or H * W == 0:
+        return
+    # HBM bytes: at least one 8-byte atomic per item; how many more depends on the slopes of the edges
+    _call("ig_zone_touch", float(T) * 8, _p(edges), _p(bit), _p(first), _p(touch), E, T, H, W, _stream())
+
+
+def zone_touch_merge(canvas, touch) -> None:
+    """``canvas`` (H, W) int64, the toggles of a pass (:func:`zone_toggle`), becomes IN PLACE the toggles of (their prefix XOR | ``touch``):
+    every consumer of a toggle canvas then sees the all_touched masks.  ``touch`` (:func:`zone_touch`) is only read."""
+    assert canvas.dtype == torch.int64 and canvas.dim() == 2 and touch.dtype == torch.int64 and touch.shape == canvas.shape
+    assert canvas.is_contiguous() and touch.is_contiguous()
+    H, W = canvas.shape
+    if H * W == 0:
+        return
+    _call("ig_zone_touch_merge", float(H) * W * 24, _p(canvas), _p(touch), H, W, _stream())
+
+
 ZONE_VALUE_BANDS = 8  # bands per launch of ig_zone_value_tally (its LDS accumulators: 32 bytes per wave, zone bit and band)
 
 

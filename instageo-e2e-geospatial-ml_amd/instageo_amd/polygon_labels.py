@@ -21,8 +21,16 @@ Device tensors go through ``ig_zone_edge_rows`` / ``ig_zone_toggle`` (as they ar
 canvas that covers only the pass's bounding rectangle; the cells are tallied by ``ig_label_cells``.  Host arrays take the numpy twin, which
 scans feature by feature and row by row with int64 arithmetic, so the module works (and is tested) without a GPU.
 
-Out of scope: ``all_touched``, edge densification, an ignore band along boundaries, lines and points, GeoPackage / Shapefile input,
-rotated grids.
+``all_touched`` (default off; ``+polygon_labels.all_touched=true``): a pixel then belongs to a feature iff its centre is inside OR one of
+the feature's edges touches it: the closed edge meets the pixel's OPEN square (the rule and its integer span form:
+``include/instageo_hip.h``; the numpy twin: :func:`zonal.touch_spans`).  A field smaller than a pixel, which usually contains no centre,
+is then burned; "last feature wins" still holds, over the pixels a feature contains or touches; the labelled area follows the same rule.
+An edge along a pixel border touches neither side, so polygons on the pixel lattice burn the same pixels under both rules.  On the device
+the touched bits go onto a second canvas (``ig_zone_touch_rows``, ``ig_zone_touch``) and ``ig_zone_touch_merge`` folds them into the
+toggles; ``ig_burn_resolve`` runs as it is.
+
+Out of scope: edge densification, an ignore band along boundaries, lines and points (under the open-square rule a line along a pixel
+border burns nothing: they need a rule of their own), GeoPackage / Shapefile input, rotated grids.
 """
 from __future__ import annotations
 
@@ -119,10 +127,12 @@ def _check_grid(grid) -> Tuple[float, float, float, float]:
     return g
 
 
-def to_fixed(features: Sequence, shape: Tuple[int, int], grid, crs, src_crs=4326, stats: Optional[Dict[str, int]] = None):
+def to_fixed(features: Sequence, shape: Tuple[int, int], grid, crs, src_crs=4326, stats: Optional[Dict[str, int]] = None,
+             all_touched: bool = False):
     """``features`` (anything with ``.rings`` and ``.value``; map coordinates in ``src_crs``) on the grid ``grid`` = (X0, Y0, sx, sy) of
     ``crs`` with ``shape`` = (H, W) -> [(value, edges (E, 4) int32 {x0, y0, x1, y1})] in file order, in the fixed point of the rule.
-    A feature whose bounding box cannot hold a pixel centre of the raster is dropped (``stats["outside"]``), as is one with fewer than
+    A feature whose bounding box cannot hold a pixel centre of the raster (with ``all_touched``: cannot meet the inside of a pixel) is
+    dropped (``stats["outside"]``), as is one with fewer than
     three distinct vertices (``stats["degenerate"]``).  A vertex beyond the fixed-point limit, or outside the domain of the projection,
     raises the ValueError of :func:`zonal.quantise`, naming the feature."""
     H, W = int(shape[0]), int(shape[1])
@@ -147,7 +157,7 @@ def to_fixed(features: Sequence, shape: Tuple[int, int], grid, crs, src_crs=4326
             stats["degenerate"] += 1
             continue
         edges = np.concatenate([zonal.ring_edges(q) for q in parts])
-        if _rect(edges, H, W) is None:
+        if _rect(edges, H, W, all_touched) is None:
             stats["outside"] += 1
             continue
         items.append((feat.value, np.ascontiguousarray(edges, dtype=np.int32)))
@@ -158,16 +168,22 @@ def _ceil_px(v: int) -> int:
     return -((HALF - int(v)) // Q)  # ceil((v - 128) / 256)
 
 
-def _rect(edges: np.ndarray, H: int, W: int) -> Optional[Tuple[int, int, int, int]]:
+def _rect(edges: np.ndarray, H: int, W: int, all_touched: bool = False) -> Optional[Tuple[int, int, int, int]]:
     """The pixels that closed rings with these edges can contain, clipped to the raster -> (r0, c0, Hp, Wp), or None for none.  Row r is
     crossed only if ymin <= 256 r + 128 < ymax; a pixel in column c is inside only if xmin <= 256 c + 128 < xmax (a crossing lies at or
-    left of it and, the crossings of a row being even in number, another one right of it)."""
+    left of it and, the crossings of a row being even in number, another one right of it).  ``all_touched``: the pixels whose open
+    square the bounding box meets, rows floor(ymin / 256) .. ceil(ymax / 256) - 1 and the same for columns: they hold every touched
+    pixel and every centre above."""
     if len(edges) == 0:
         return None
     xmin, ymin = int(edges[:, 0].min()), int(edges[:, 1].min())
     xmax, ymax = int(edges[:, 0].max()), int(edges[:, 1].max())
-    r0, r1 = max(0, _ceil_px(ymin)), min(H - 1, (ymax - HALF - 1) // Q)
-    c0, c1 = max(0, _ceil_px(xmin)), min(W - 1, (xmax - HALF - 1) // Q)
+    if all_touched:
+        r0, r1 = max(0, ymin // Q), min(H - 1, -((-ymax) // Q) - 1)
+        c0, c1 = max(0, xmin // Q), min(W - 1, -((-xmax) // Q) - 1)
+    else:
+        r0, r1 = max(0, _ceil_px(ymin)), min(H - 1, (ymax - HALF - 1) // Q)
+        c0, c1 = max(0, _ceil_px(xmin)), min(W - 1, (xmax - HALF - 1) // Q)
     if r1 < r0 or c1 < c0:
         return None
     return r0, c0, r1 - r0 + 1, c1 - c0 + 1
@@ -183,22 +199,23 @@ def _check_items(items, dtype: str) -> None:
             raise ValueError(f"a seg burn value is an int in [-1, 127] (got {value!r})")
 
 
-def _passes(items, H: int, W: int):
+def _passes(items, H: int, W: int, all_touched: bool = False):
     """-> [(first item, items of the pass, rect)] for the passes of 64 features, in order, that can touch the raster."""
     out = []
     for first in range(0, len(items), PASS):
         part = items[first : first + PASS]
         edges = [e for _, e in part if len(e)]
-        rect = _rect(np.concatenate(edges), H, W) if edges else None
+        rect = _rect(np.concatenate(edges), H, W, all_touched) if edges else None
         if rect is not None:
             out.append((first, part, rect))
     return out
 
 
 # ---- the rule on host arrays ----------------------------------------------------------------------------------------------------------------
-def _inside_host(edges: np.ndarray, H: int, W: int):
-    """One feature's inside mask by the rule, in int64: -> (r0, c0, mask (Hp, Wp) bool) over its own rectangle, or None."""
-    rect = _rect(edges, H, W)
+def _inside_host(edges: np.ndarray, H: int, W: int, all_touched: bool = False):
+    """One feature's inside mask by the rule, in int64: -> (r0, c0, mask (Hp, Wp) bool) over its own rectangle, or None.
+    ``all_touched``: OR the pixels its edges touch (:func:`zonal.touch_spans`), over the rectangle that bounds those too."""
+    rect = _rect(edges, H, W, all_touched)
     if rect is None:
         return None
     r0, c0, Hp, Wp = rect
@@ -218,15 +235,18 @@ def _inside_host(edges: np.ndarray, H: int, W: int):
     keep = c < c0 + Wp
     toggles = np.zeros((Hp, Wp), dtype=np.uint8)
     np.bitwise_xor.at(toggles, (r[keep] - r0, c[keep] - c0), np.uint8(1))
-    return r0, c0, np.bitwise_xor.accumulate(toggles, axis=1).astype(bool)
+    mask = np.bitwise_xor.accumulate(toggles, axis=1).astype(bool)
+    if all_touched:
+        mask |= zonal.touched_mask(edges, H, W, rect)
+    return r0, c0, mask
 
 
-def _burn_host(raster: np.ndarray, items, stats: Dict[str, int]) -> None:
+def _burn_host(raster: np.ndarray, items, stats: Dict[str, int], all_touched: bool = False) -> None:
     H, W = raster.shape
-    for _, part, (r0, c0, Hp, Wp) in _passes(items, H, W):
+    for _, part, (r0, c0, Hp, Wp) in _passes(items, H, W, all_touched):
         touched = np.zeros((Hp, Wp), dtype=bool)  # the pixels the pass writes: what ig_burn_resolve counts
         for value, edges in part:
-            got = _inside_host(edges, H, W)
+            got = _inside_host(edges, H, W, all_touched)
             if got is None:
                 continue
             fr, fc, mask = got
@@ -237,13 +257,13 @@ def _burn_host(raster: np.ndarray, items, stats: Dict[str, int]) -> None:
         stats["pixels_written"] += int(touched.sum())
 
 
-def _burn_device(raster, items, stats: Dict[str, int]) -> None:
+def _burn_device(raster, items, stats: Dict[str, int], all_touched: bool = False) -> None:
     import torch
 
     from . import ops
 
     H, W = raster.shape
-    passes = _passes(items, H, W)
+    passes = _passes(items, H, W, all_touched)
     if not passes:
         return
     dev = raster.device
@@ -267,6 +287,7 @@ def _burn_device(raster, items, stats: Dict[str, int]) -> None:
     b_dev = torch.from_numpy(np.concatenate(bit_parts)).to(dev)
     t_dev = torch.from_numpy(tables).to(dev)
     scratch = torch.empty(max(r[2] * r[3] for _, _, r in passes), dtype=torch.int64, device=dev)  # one canvas, reused
+    scratch2 = torch.empty_like(scratch) if all_touched else None  # the canvas of touched bits
     written = torch.zeros(1, dtype=torch.int64, device=dev)
     for p, (_, _, (r0, c0, Hp, Wp)) in enumerate(passes):
         a, b = spans[p]
@@ -274,21 +295,31 @@ def _burn_device(raster, items, stats: Dict[str, int]) -> None:
         rows = ops.zone_edge_rows(e, Hp)
         first = torch.cumsum(rows, 0, dtype=torch.int64).sub_(rows)
         T = int(rows.sum(dtype=torch.int64).item())
+        TT = 0
+        if all_touched:
+            trows = ops.zone_touch_rows(e, Hp)
+            TT = int(trows.sum(dtype=torch.int64).item())
         stats["passes"] += 1
-        if T == 0:
+        if T == 0 and TT == 0:
             continue
         canvas = scratch[: Hp * Wp].view(Hp, Wp)
         canvas.zero_()
         ops.zone_toggle(e, b_dev[a:b], first, canvas, T)
+        if TT:
+            touch = scratch2[: Hp * Wp].view(Hp, Wp)
+            touch.zero_()
+            ops.zone_touch(e, b_dev[a:b], torch.cumsum(trows, 0, dtype=torch.int64).sub_(trows), touch, TT)
+            ops.zone_touch_merge(canvas, touch)
         ops.burn_resolve(canvas, t_dev[p], raster, r0, c0, written)
     stats["pixels_written"] += int(written.item())
 
 
-def burn_fixed(raster, items, stats: Optional[Dict[str, int]] = None):
+def burn_fixed(raster, items, stats: Optional[Dict[str, int]] = None, all_touched: bool = False):
     """Burn ``items`` = [(value, edges)] (:func:`to_fixed`: closed rings in the raster's fixed point), in order, into ``raster`` (H, W)
     int8 | float32 IN PLACE by the rule of the module docstring -> ``raster``.  A tensor on the device goes through the kernels (it may be
     a view with any row pitch), a numpy array through the twin.  ``stats`` gains ``passes`` (those that can touch the raster) and
-    ``pixels_written`` (per pass, the pixels inside at least one of its features, summed over the passes)."""
+    ``pixels_written`` (per pass, the pixels inside at least one of its features, summed over the passes).  ``all_touched``: a feature
+    also holds the pixels its edges touch (module docstring)."""
     stats = stats if stats is not None else {}
     stats.setdefault("passes", 0)
     stats.setdefault("pixels_written", 0)
@@ -299,9 +330,9 @@ def burn_fixed(raster, items, stats: Optional[Dict[str, int]] = None):
         raise ValueError(f"a raster of {raster.shape[0]} x {raster.shape[1]} pixels is beyond 2^31 - 1: burn it in row bands")
     _check_items(items, name)
     if isinstance(raster, np.ndarray):
-        _burn_host(raster, items, stats)
+        _burn_host(raster, items, stats, bool(all_touched))
     elif prep.is_device(raster):
-        _burn_device(raster, items, stats)
+        _burn_device(raster, items, stats, bool(all_touched))
     else:
         raise ValueError("burn_fixed takes a numpy array (host) or a tensor on the device")
     return raster
@@ -336,12 +367,13 @@ def _dtype(dtype) -> str:
 
 
 def burn(features: Sequence, shape: Tuple[int, int], grid, crs, *, src_crs=4326, dtype, background=None, labelled_area: Optional[Sequence] = None,
-         device: Optional[str] = None, stats: Optional[Dict[str, int]] = None):
+         device: Optional[str] = None, stats: Optional[Dict[str, int]] = None, all_touched: bool = False):
     """``features`` (:func:`read_features`; coordinates in EPSG:``src_crs``) burned onto the (H, W) = ``shape`` raster of ``grid`` =
     (X0, Y0, sx, sy) in ``crs`` (an EPSG code, ``"EPSG:n"`` or a :class:`crs.Crs`) -> the raster, ``dtype`` int8 | float32: a numpy
     array with ``device=None``, a tensor on ``device`` otherwise; the same bytes either way.  ``background``: what a pixel in no feature
     holds (default 0 / NaN); ``labelled_area``: features (only their rings count) outside which a pixel holds the ignore value instead.
-    ``stats`` gains ``outside``, ``degenerate`` (of ``features``), ``passes`` and ``pixels_written`` (:func:`burn_fixed`)."""
+    ``stats`` gains ``outside``, ``degenerate`` (of ``features``), ``passes`` and ``pixels_written`` (:func:`burn_fixed`).
+    ``all_touched``: features and labelled area alike also hold the pixels their edges touch."""
     prep.check_device(device)
     name = _dtype(dtype)
     H, W = int(shape[0]), int(shape[1])
@@ -349,12 +381,13 @@ def burn(features: Sequence, shape: Tuple[int, int], grid, crs, *, src_crs=4326,
         raise ValueError(f"a raster of {H} x {W} pixels is beyond 2^31 - 1: burn it in row bands")
     bg = _background(background, name)
     ignore = SEG_IGNORE if name == "int8" else float("nan")
-    items = to_fixed(features, (H, W), grid, crs, src_crs, stats)
+    at = bool(all_touched)
+    items = to_fixed(features, (H, W), grid, crs, src_crs, stats, at)
     area = None
     if labelled_area is not None:
-        area = [(bg, e) for _, e in to_fixed([Feature(i, bg, f.rings) for i, f in enumerate(labelled_area)], (H, W), grid, crs, src_crs, {})]
+        area = [(bg, e) for _, e in to_fixed([Feature(i, bg, f.rings) for i, f in enumerate(labelled_area)], (H, W), grid, crs, src_crs, {}, at)]
     raster = _new_raster((H, W), name, bg if area is None else ignore, device)
-    return burn_fixed(raster, (area or []) + items, stats)
+    return burn_fixed(raster, (area or []) + items, stats, at)
 
 
 # ---- cells -------------------------------------------------------------------------------------------------------------------------------------
@@ -434,15 +467,15 @@ def choose_grid(features: Sequence, chip_size: int, like: Optional[str] = None, 
 
 
 # ---- files ------------------------------------------------------------------------------------------------------------------------------------
-def _row_band(items, row0: int, rows: int, W: int):
+def _row_band(items, row0: int, rows: int, W: int, all_touched: bool = False):
     """The items that can touch rows [row0, row0 + rows) of the raster, their edges moved up by row0 whole pixels (exact)."""
     if row0 == 0:
-        return [(v, e) for v, e in items if _rect(e, rows, W) is not None]
+        return [(v, e) for v, e in items if _rect(e, rows, W, all_touched) is not None]
     shift = np.array([0, Q * row0, 0, Q * row0], dtype=np.int64)
     out = []
     for v, e in items:
         moved = e.astype(np.int64) - shift
-        if _rect(moved, rows, W) is None:
+        if _rect(moved, rows, W, all_touched) is None:
             continue
         if np.abs(moved).max() > zonal.COORD_LIMIT:
             raise ValueError(f"a vertex lies beyond 2^29 fixed-point units ({zonal.COORD_LIMIT // Q} pixels) of the row band at row {row0}")
@@ -459,7 +492,8 @@ def create_polygon_labels(features_file: str, output_directory: str, like: Optio
                           spatial_resolution: float = 30.0, chip_size: int = 256, task_type: str = "seg", value_property: Optional[str] = None,
                           burn_value=None, class_map: Optional[Dict[str, int]] = None, background=None, labelled_area: Optional[str] = None,
                           date: Optional[str] = None, date_property: Optional[str] = None, mgrs_tile_id: Optional[str] = None,
-                          min_foreground: int = 1, device: Optional[str] = None, max_pixels: int = MAX_PIXELS) -> List[str]:
+                          min_foreground: int = 1, device: Optional[str] = None, max_pixels: int = MAX_PIXELS,
+                          all_touched: bool = False) -> List[str]:
     """The polygons of ``features_file`` (GeoJSON, EPSG:``src_crs``) -> ``labels/label_x{x}_y{y}_{date}.tif`` (int8 for ``seg``, float32
     for ``reg``, each ``chip_size`` x ``chip_size`` with the GeoKeys ``create_raster_chips`` reads), ``records.csv`` (``label_filename,
     date[, mgrs_tile_id]``: the table ``create_raster_chips`` takes) and ``polygon_labels_stats.json`` under ``output_directory`` -> the
@@ -467,8 +501,12 @@ def create_polygon_labels(features_file: str, output_directory: str, like: Optio
     own rasters; otherwise ``date`` names them all.  ``labelled_area``: a GeoJSON of the ground that was labelled (module docstring).  A
     cell with fewer than ``min_foreground`` pixels that are neither the ignore value nor ``background`` is dropped; an existing file is
     not rewritten but still listed.  A raster of more than ``max_pixels`` (2^31 - 1) pixels is burned in row bands of whole cells.
-    ``device``: None = the numpy path, ``"cuda"`` / ``"cuda:n"`` = the kernels; both write the same bytes."""
+    ``device``: None = the numpy path, ``"cuda"`` / ``"cuda:n"`` = the kernels; both write the same bytes.  ``all_touched``: features and
+    labelled area also hold the pixels their edges touch (module docstring), so a field smaller than a pixel is still burned."""
     prep.check_device(device)
+    if not isinstance(all_touched, (bool, np.bool_)):
+        raise ValueError(f"all_touched must be true or false (got {all_touched!r})")
+    all_touched = bool(all_touched)
     if task_type not in TASKS:
         raise ValueError(f"task_type must be seg or reg (got {task_type!r})")
     name = TASKS[task_type]
@@ -504,15 +542,16 @@ def create_polygon_labels(features_file: str, output_directory: str, like: Optio
     rows_out: List[Tuple[str, str]] = []
     band_cells = max(1, int(max_pixels) // (S * W)) if ny and nx else 1
     for day, group in groups.items():
-        items = to_fixed(group, (H, W), grid, dst, src_crs, counts)
+        items = to_fixed(group, (H, W), grid, dst, src_crs, counts, all_touched)
         area_items = None
         if area is not None:
-            area_items = [(bg, e) for _, e in to_fixed([Feature(i, bg, z.rings) for i, z in enumerate(area)], (H, W), grid, dst, src_crs, {})]
+            area_items = [(bg, e) for _, e in to_fixed([Feature(i, bg, z.rings) for i, z in enumerate(area)], (H, W), grid, dst, src_crs, {},
+                                                       all_touched)]
         for cy0 in range(0, ny if nx else 0, band_cells):
             rows = min(band_cells, ny - cy0) * S
-            band = _row_band((area_items or []) + items, cy0 * S, rows, W)
+            band = _row_band((area_items or []) + items, cy0 * S, rows, W, all_touched)
             raster = _new_raster((rows, W), name, bg if area_items is None else ignore, device)
-            burn_fixed(raster, band, counts)
+            burn_fixed(raster, band, counts, all_touched)
             valid, hist = label_cells(raster, S, K)
             host = raster if isinstance(raster, np.ndarray) else raster.cpu().numpy()
             for by in range(rows // S):
@@ -556,13 +595,16 @@ def create_polygon_labels(features_file: str, output_directory: str, like: Optio
 # ---- mode=create_polygon_labels ---------------------------------------------------------------------------------------------------------------
 CONFIG_KEYS = ("features", "output_directory", "like", "crs", "src_crs", "spatial_resolution", "chip_size", "task_type", "value_property",
                "burn_value", "class_map", "background", "labelled_area", "date", "date_property", "mgrs_tile_id", "min_foreground", "device")
+# keys without a default: given as ``+polygon_labels.<key>=...`` on the command line, or in a YAML config.  all_touched: true | false
+# (unset = false): features and labelled area also hold the pixels their edges touch
+OPTIONAL_KEYS = ("all_touched",)
 
 
 def polygon_labels_options(cfg: Dict[str, Any]) -> Dict[str, Any]:
-    """The ``polygon_labels.*`` keys of ``mode=create_polygon_labels`` checked -> the keyword arguments of :func:`create_polygon_labels`.
-    An unknown key or a bad value raises ValueError; the files are required only in that mode.  ``device``: None = the device when there
-    is one, ``host`` = the numpy path, ``cuda`` / ``cuda:n``."""
-    c = prep.Section(cfg, "polygon_labels", CONFIG_KEYS)
+    """The ``polygon_labels.*`` keys of ``mode=create_polygon_labels`` checked -> the keyword arguments of :func:`create_polygon_labels`
+    (``all_touched`` only when it is on).  An unknown key or a bad value raises ValueError; the files are required only in that mode.
+    ``device``: None = the device when there is one, ``host`` = the numpy path, ``cuda`` / ``cuda:n``."""
+    c = prep.Section(cfg, "polygon_labels", CONFIG_KEYS + OPTIONAL_KEYS)
     size = c.integer("chip_size", 256, lo=1, hi=MAX_SIDE, what="must be an int in [1, 2^15]")
     task = c.choice("task_type", "seg", TASKS, "must be seg or reg")
     res = c.number("spatial_resolution", 30.0, lambda x: 0 < x < np.inf, "must be a positive number")
@@ -587,6 +629,8 @@ def polygon_labels_options(cfg: Dict[str, Any]) -> Dict[str, Any]:
                 src_crs=c.epsg("src_crs", 4326), spatial_resolution=res, chip_size=size, task_type=task,
                 value_property=c.text("value_property"), burn_value=bv, class_map=cmap, background=bg, labelled_area=c.text("labelled_area"),
                 date=c.text("date"), date_property=c.text("date_property"), mgrs_tile_id=c.text("mgrs_tile_id"), min_foreground=fgmin, device=dev)
+    if c.flag("all_touched"):
+        opts["all_touched"] = True
     if cfg.get("mode") == "create_polygon_labels":
         if opts["features_file"] is None or opts["output_directory"] is None:
             raise ValueError("mode=create_polygon_labels needs polygon_labels.features and polygon_labels.output_directory")

@@ -20,7 +20,15 @@ band and percentile, the two neighbouring order statistics by a radix selection 
 the same bits from run to run) and the host interpolates between them in float64 as numpy's default ``linear`` method does
 (``include/instageo_hip.h``).  :func:`zone_quantiles_host` is the numpy twin of the rule.  ``zonal_stats.percentiles`` adds them to the CSV.
 
-Out of scope: ``all_touched``, ``majority`` / ``minority`` / ``unique``, percentiles in ``test.zones`` of the inference modes, rotated or
+all_touched.  Every function that takes zones also takes ``all_touched`` (default off): a pixel then belongs to a zone iff its centre is
+inside OR one of the zone's edges touches it, i.e. the closed edge meets the pixel's OPEN square (``include/instageo_hip.h``).  A parcel
+smaller than a pixel then still has pixels.  The square is open so that an edge along a pixel border touches neither side: polygons on the
+pixel lattice (those of :mod:`instageo_amd.vectorize`) select the same pixels under both rules.  :func:`touch_spans` and
+:func:`touched_mask` are the numpy twin of the rule.  It is expected to match rasterio's ``all_touched=True`` for vertices in general
+position; that has not been verified.
+
+Out of scope: lines and points (under the open-square rule a line along a pixel border burns nothing: they need a rule of their own),
+``majority`` / ``minority`` / ``unique``, percentiles in ``test.zones`` of the inference modes, rotated or
 sheared geotransforms, one table merged across chips or tiles, zone rasters written as TIFF.
 """
 from __future__ import annotations
@@ -151,10 +159,59 @@ def _check_edges(edges: np.ndarray, edge_zone: np.ndarray, Z: int) -> Tuple[np.n
     return edges, edge_zone.astype(np.int64)
 
 
-def _passes(edges: np.ndarray, edge_zone: np.ndarray, Z: int, H: int, W: int, device):
+def touch_spans(edges: np.ndarray, H: int, W: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    """The numpy twin of the all_touched span rule (``include/instageo_hip.h``), in int64: ``edges`` (E, 4) {x0, y0, x1, y1} -> (edge,
+    row, first column, last column) of every (edge, touched row) pair whose span holds a column of the (H, W) raster.  Rows:
+    floor(ymin / 256) .. ceil(ymax / 256) - 1 in [0, H); columns: floor(lo / 256) .. ceil(hi / 256) - 1 in [0, W) with lo / hi the
+    abscissae at the two ends of the edge's part inside the row, exact rationals over abs(y1 - y0) (a horizontal edge: its own ends)."""
+    H, W = int(H), int(W)
+    x0, y0, x1, y1 = (np.asarray(edges)[:, k].astype(np.int64) for k in range(4))
+    ymin, ymax = np.minimum(y0, y1), np.maximum(y0, y1)
+    lo = np.maximum(ymin // Q, 0)
+    hi = np.minimum(-((-ymax) // Q) - 1, H - 1)
+    n = np.maximum(hi - lo + 1, 0)
+    first = np.cumsum(n) - n
+    e = np.repeat(np.arange(len(n)), n)
+    r = lo[e] + (np.arange(int(n.sum())) - first[e])
+    den = y1[e] - y0[e]
+    flat = den == 0
+    ya, yb = np.maximum(ymin[e], Q * r), np.minimum(ymax[e], Q * r + Q)
+    a = np.where(flat, x0[e], x0[e] * den + (x1[e] - x0[e]) * (ya - y0[e]))  # |a|, |b| < 2^61
+    b = np.where(flat, x1[e], x0[e] * den + (x1[e] - x0[e]) * (yb - y0[e]))
+    a, b = np.where(den < 0, -a, a), np.where(den < 0, -b, b)
+    den = np.where(flat, 1, np.abs(den)) * Q
+    c0 = np.maximum(np.minimum(a, b) // den, 0)
+    c1 = np.minimum(-((-np.maximum(a, b)) // den) - 1, W - 1)
+    keep = c1 >= c0
+    return e[keep], r[keep], c0[keep], c1[keep]
+
+
+def touch_rows(edges: np.ndarray, H: int) -> np.ndarray:
+    """-> (E,) int64: the rows in [0, H) each edge touches, what ``ig_zone_touch_rows`` counts (a row counts whatever its columns are)."""
+    y0, y1 = (np.asarray(edges)[:, k].astype(np.int64) for k in (1, 3))
+    lo = np.maximum(np.minimum(y0, y1) // Q, 0)
+    hi = np.minimum(-((-np.maximum(y0, y1)) // Q) - 1, int(H) - 1)
+    return np.maximum(hi - lo + 1, 0)
+
+
+def touched_mask(edges: np.ndarray, H: int, W: int, rect: Optional[Tuple[int, int, int, int]] = None) -> np.ndarray:
+    """-> (H, W) bool: the pixels of the (H, W) raster at least one of ``edges`` touches (:func:`touch_spans` painted: +1 at a span's
+    first column, -1 after its last, summed along the row).  ``rect`` = (r0, c0, Hp, Wp): only that rectangle of the raster, (Hp, Wp)."""
+    r0, c0, Hp, Wp = (0, 0, int(H), int(W)) if rect is None else rect
+    _, r, a, b = touch_spans(edges, H, W)
+    a, b = np.maximum(a, c0), np.minimum(b, c0 + Wp - 1)
+    keep = (r >= r0) & (r < r0 + Hp) & (b >= a)
+    steps = np.zeros((Hp, Wp + 1), dtype=np.int64)
+    np.add.at(steps, (r[keep] - r0, a[keep] - c0), 1)
+    np.add.at(steps, (r[keep] - r0, b[keep] - c0 + 1), -1)
+    return np.cumsum(steps, axis=1)[:, :Wp] > 0
+
+
+def _passes(edges: np.ndarray, edge_zone: np.ndarray, Z: int, H: int, W: int, device, all_touched: bool = False):
     """Yield (pass, canvas) for those of the ceil(Z / 64) passes whose zones cross a row of the raster at all: the (H, W) int64 canvas
     holds their toggles, bit ``zone % 64`` each (rows counted, scanned, toggled; not yet prefix-XORed).  A pass without a crossing
-    has no inside pixel and launches nothing."""
+    has no inside pixel and launches nothing.  ``all_touched``: the touched pixels go onto a second canvas and are merged into the
+    toggles (``ig_zone_touch_rows``, ``ig_zone_touch``, ``ig_zone_touch_merge``); a pass is then skipped only if it touches no row either."""
     edges, edge_zone = _check_edges(edges, edge_zone, Z)
     if len(edges) == 0 or H * W == 0:
         return
@@ -167,25 +224,35 @@ def _passes(edges: np.ndarray, edge_zone: np.ndarray, Z: int, H: int, W: int, de
         rows = ops.zone_edge_rows(e, H)
         first = torch.cumsum(rows, 0, dtype=torch.int64).sub_(rows)
         T = int(rows.sum(dtype=torch.int64).item())
-        if T == 0:
+        TT = 0
+        if all_touched:
+            touch_rows_ = ops.zone_touch_rows(e, H)
+            TT = int(touch_rows_.sum(dtype=torch.int64).item())
+        if T == 0 and TT == 0:
             continue
         canvas = torch.zeros((H, W), dtype=torch.int64, device=device)
         ops.zone_toggle(e, bit, first, canvas, T)
+        if TT:
+            touch = torch.zeros((H, W), dtype=torch.int64, device=device)
+            ops.zone_touch(e, bit, torch.cumsum(touch_rows_, 0, dtype=torch.int64).sub_(touch_rows_), touch, TT)
+            ops.zone_touch_merge(canvas, touch)
         yield p, canvas
 
 
-def zone_masks(edges: np.ndarray, edge_zone: np.ndarray, Z: int, H: int, W: int, device="cuda") -> torch.Tensor:
+def zone_masks(edges: np.ndarray, edge_zone: np.ndarray, Z: int, H: int, W: int, device="cuda", all_touched: bool = False) -> torch.Tensor:
     """-> (ceil(Z / 64), H, W) int64 bit planes on the device: bit ``z % 64`` of plane ``z // 64`` at (r, c) = pixel (r, c) is inside
-    zone z (bit 63 is the sign bit).  ``edges`` / ``edge_zone`` are those of :func:`zones_to_pixels`."""
+    zone z (bit 63 is the sign bit).  ``edges`` / ``edge_zone`` are those of :func:`zones_to_pixels`.  ``all_touched``: also the pixels
+    the zone's edges touch (module docstring); the same in every function below."""
     Z, H, W = int(Z), int(H), int(W)
     planes = torch.zeros(((Z + ops.ZONE_BITS - 1) // ops.ZONE_BITS, H, W), dtype=torch.int64, device=device)
-    for p, canvas in _passes(edges, edge_zone, Z, H, W, device):
+    for p, canvas in _passes(edges, edge_zone, Z, H, W, device, all_touched):
         ops.zone_tally(canvas, None, None, write_mask=True)
         planes[p] = canvas
     return planes
 
 
-def zone_counts(classmap: torch.Tensor, edges: np.ndarray, edge_zone: np.ndarray, Z: int, ncls: int, fill: int = -1) -> np.ndarray:
+def zone_counts(classmap: torch.Tensor, edges: np.ndarray, edge_zone: np.ndarray, Z: int, ncls: int, fill: int = -1,
+                all_touched: bool = False) -> np.ndarray:
     """Pixels per zone and class of one (H, W) int8 class map on the device -> (Z, ncls + 1) int64 numpy: ``[z][k]`` = the pixels of
     class k inside zone z for k < ncls, ``[z][ncls]`` = its pixels that are ``fill`` or lie outside [0, ncls).  2 <= ncls <= 127."""
     if classmap.dtype != torch.int8 or classmap.dim() != 2:
@@ -196,7 +263,7 @@ def zone_counts(classmap: torch.Tensor, edges: np.ndarray, edge_zone: np.ndarray
     H, W = classmap.shape
     cm = classmap.contiguous()
     out = np.zeros((Z, ncls + 1), dtype=np.int64)
-    for p, canvas in _passes(edges, edge_zone, Z, H, W, cm.device):
+    for p, canvas in _passes(edges, edge_zone, Z, H, W, cm.device, all_touched):
         counts = torch.zeros((ops.ZONE_BITS, ncls + 1), dtype=torch.int64, device=cm.device)
         ops.zone_tally(canvas, cm, counts, ncls, fill)
         lo = p * ops.ZONE_BITS
@@ -227,11 +294,11 @@ def write_zone_csv(path: str, ids: Sequence[Any], counts: np.ndarray, profile: O
 
 
 def zone_table(classmap: torch.Tensor, zones: Sequence[Zone], ncls: int, fill: int = -1,
-               profile: Optional[Dict[str, Any]] = None) -> Tuple[List[Any], np.ndarray]:
+               profile: Optional[Dict[str, Any]] = None, all_touched: bool = False) -> Tuple[List[Any], np.ndarray]:
     """What inference writes: ``zones`` (:func:`read_zones`; map coordinates when ``profile`` is georeferenced) on ``classmap`` ->
     (ids, counts) for :func:`write_zone_csv`."""
     edges, edge_zone = zones_to_pixels(zones, profile)
-    return [z.id for z in zones], zone_counts(classmap, edges, edge_zone, len(zones), ncls, fill)
+    return [z.id for z in zones], zone_counts(classmap, edges, edge_zone, len(zones), ncls, fill, all_touched)
 
 
 # ---- values: per-zone statistics of float rasters ---------------------------------------------------------------------------------------------
@@ -254,7 +321,8 @@ def _check_nodata(nodata) -> Optional[float]:
     return None if nd != nd else nd  # NaN is invalid anyway
 
 
-def zone_values(raster: torch.Tensor, edges: np.ndarray, edge_zone: np.ndarray, Z: int, nodata: Optional[float] = None) -> ZoneValues:
+def zone_values(raster: torch.Tensor, edges: np.ndarray, edge_zone: np.ndarray, Z: int, nodata: Optional[float] = None,
+                all_touched: bool = False) -> ZoneValues:
     """Per zone and band the count, sum, mean, population std, min and max of one (H, W) or (B, H, W) float32 raster on the device ->
     :class:`ZoneValues`.  A value is valid when it is finite and differs from ``nodata`` (compared as float32); where a zone has no valid
     value its statistics are NaN.  ``edges`` / ``edge_zone`` are those of :func:`zones_to_pixels`.  One canvas per pass of 64 zones serves
@@ -270,7 +338,7 @@ def zone_values(raster: torch.Tensor, edges: np.ndarray, edge_zone: np.ndarray, 
     pixels = np.zeros(Z, dtype=np.int64)
     valid = np.zeros((Z, B), dtype=np.int64)
     stats = np.zeros((Z, B, 4), dtype=np.float64)  # mean, M2, min, max
-    for p, canvas in _passes(edges, edge_zone, Z, H, W, r.device):
+    for p, canvas in _passes(edges, edge_zone, Z, H, W, r.device, all_touched):
         lo = p * ops.ZONE_BITS
         n = min(ops.ZONE_BITS, Z - lo)
         for b0 in range(0, B, ops.ZONE_VALUE_BANDS):
@@ -319,7 +387,7 @@ def quantile_lerp(a, b, g) -> np.ndarray:
 
 
 def zone_quantiles(raster: torch.Tensor, edges: np.ndarray, edge_zone: np.ndarray, Z: int, percentiles, nodata: Optional[float] = None,
-                   pairs: bool = False):
+                   pairs: bool = False, all_touched: bool = False):
     """Per zone and band the ``percentiles`` (numbers in [0, 100]; 50 is the median, 0 the minimum, 100 the maximum) of the valid values
     of one (H, W) or (B, H, W) float32 raster on the device -> (valid (Z, B) int64, values (Z, B, Q) float64), NaN where a zone has no
     valid value; with ``pairs`` also the order statistics themselves, (Z, B, Q, 2) float32 {v(lo), v(hi)}.  Validity, ``edges`` and
@@ -338,7 +406,7 @@ def zone_quantiles(raster: torch.Tensor, edges: np.ndarray, edge_zone: np.ndarra
     fr = [q / 100.0 for q in uniq]
     valid = np.zeros((Z, B), dtype=np.int64)
     order = np.full((Z, B, len(uniq), 2), np.nan, dtype=np.float32)
-    for p, canvas in _passes(edges, edge_zone, Z, H, W, r.device):
+    for p, canvas in _passes(edges, edge_zone, Z, H, W, r.device, all_touched):
         lo = p * ops.ZONE_BITS
         n = min(ops.ZONE_BITS, Z - lo)
         for b0 in range(0, B, ops.ZONE_VALUE_BANDS):
@@ -382,15 +450,15 @@ def zone_quantiles_host(mask: np.ndarray, raster: np.ndarray, percentiles, nodat
 
 
 def zone_value_table(raster: torch.Tensor, zones: Sequence[Zone], nodata: Optional[float] = None,
-                     profile: Optional[Dict[str, Any]] = None, percentiles=None):
+                     profile: Optional[Dict[str, Any]] = None, percentiles=None, all_touched: bool = False):
     """``zones`` (:func:`read_zones`; map coordinates when ``profile`` is georeferenced) on ``raster`` -> (ids, values) for
     :func:`write_zone_values_csv`: what :func:`zone_table` is to a class map.  With ``percentiles`` -> (ids, values, (Z, B, Q) float64 of
     :func:`zone_quantiles`)."""
     edges, edge_zone = zones_to_pixels(zones, profile)
-    ids, values = [z.id for z in zones], zone_values(raster, edges, edge_zone, len(zones), nodata)
+    ids, values = [z.id for z in zones], zone_values(raster, edges, edge_zone, len(zones), nodata, all_touched)
     if percentiles is None:
         return ids, values
-    return ids, values, zone_quantiles(raster, edges, edge_zone, len(zones), percentiles, nodata)[1]
+    return ids, values, zone_quantiles(raster, edges, edge_zone, len(zones), percentiles, nodata, all_touched=all_touched)[1]
 
 
 VALUE_COLUMNS = ("valid", "mean", "std", "min", "max", "sum")  # per band, in this order
@@ -437,14 +505,15 @@ def write_zone_values_csv(path: str, ids: Sequence[Any], values: ZoneValues, ban
 # ---- mode=zonal_stats -------------------------------------------------------------------------------------------------------------------------
 CONFIG_KEYS = ("raster", "zones", "zone_id_property", "output", "bands", "nodata", "zones_crs")
 # keys without a default: given as ``+zonal_stats.<key>=...`` on the command line, or in a YAML config.  percentiles: None, or a list of
-# 1..MAX_PERCENTILES distinct numbers in [0, 100] (50 = the median): the columns percentile_<q>_<b> of the CSV
-OPTIONAL_KEYS = ("percentiles",)
+# 1..MAX_PERCENTILES distinct numbers in [0, 100] (50 = the median): the columns percentile_<q>_<b> of the CSV.  all_touched: true | false
+# (unset = false): a zone also holds the pixels its edges touch
+OPTIONAL_KEYS = ("percentiles", "all_touched")
 MAX_PERCENTILES = 32
 
 
 def zonal_stats_options(cfg: Dict[str, Any]) -> Dict[str, Any]:
     """The ``zonal_stats.*`` keys checked -> {raster, zones (a list of :class:`Zone` in the raster's coordinate system), bands, nodata,
-    output, profile, percentiles}.  An unknown key, a bad value, a missing file, a band the file does not have, a feature that is no (Multi)Polygon,
+    output, profile, percentiles, all_touched}.  An unknown key, a bad value, a missing file, a band the file does not have, a feature that is no (Multi)Polygon,
     or ``zones_crs`` with a raster that carries no coordinate system raises ValueError naming the key.  Reads the raster's header and the
     GeoJSON; touches no device."""
     c = prep.Section(cfg, "zonal_stats", CONFIG_KEYS + OPTIONAL_KEYS)
@@ -456,6 +525,7 @@ def zonal_stats_options(cfg: Dict[str, Any]) -> Dict[str, Any]:
                 raise ValueError
         except ValueError:
             raise c.bad("percentiles", f"must be None or a list of 1..{MAX_PERCENTILES} distinct numbers in [0, 100]", c.get("percentiles")) from None
+    all_touched = c.flag("all_touched")
     raster, zfile = c.text("raster"), c.text("zones")
     for key, path in (("raster", raster), ("zones", zfile)):
         if path is None:
@@ -513,7 +583,7 @@ def zonal_stats_options(cfg: Dict[str, Any]) -> Dict[str, Any]:
     if output is None:
         output = os.path.join(os.path.dirname(raster), f"zonevalues_{os.path.splitext(os.path.basename(raster))[0]}.csv")
     return dict(raster=raster, zones=zones, bands=[int(b) for b in bands], nodata=nodata, output=output, profile=profile,
-                percentiles=percentiles)
+                percentiles=percentiles, all_touched=all_touched)
 
 
 def _to_float32(a: np.ndarray, device) -> torch.Tensor:
@@ -534,7 +604,7 @@ def run_from_config(cfg: Dict[str, Any], device: Optional[str] = None) -> int:
         raise RuntimeError("mode=zonal_stats runs on a HIP device and there is none (the tally has no host path)")
     a, profile = tiff.read(kw["raster"], kw["bands"])
     qs = kw["percentiles"]
-    ids, values, *rest = zone_value_table(_to_float32(a, device), kw["zones"], kw["nodata"], profile, qs)
+    ids, values, *rest = zone_value_table(_to_float32(a, device), kw["zones"], kw["nodata"], profile, qs, kw["all_touched"])
     write_zone_values_csv(kw["output"], ids, values, kw["bands"], profile, None if qs is None else (qs, rest[0]))
     print(json.dumps({"zonal_stats": {"zones": len(ids), "bands": len(kw["bands"]), "empty_zones": int((values.valid.sum(axis=1) == 0).sum()),
                                       "output": kw["output"]}}))
