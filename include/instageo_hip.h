@@ -652,7 +652,22 @@ int ig_mosaic_paste(const void* chips, const long long* starts, const int* rects
  * spherical web Mercator EPSG:3857 (R = 6378137; the other four ignored).  Transverse Mercator is the Krueger series in the third
  * flattening n to n^6, forward and inverse, in float64: xi + i eta = xi' + i eta' + sum_j alpha_j sin(2j (xi' + i eta')), j = 1..6, summed
  * by the angle-addition recurrence from one sincos and one sinh / cosh pair; the geographic latitude comes from the conformal one by
- * three Newton steps on tan(latitude) from tau'/(1 - e^2) (no data-dependent loop).  A GRID is four doubles (X0, Y0, sx, sy), the outer
+ * three Newton steps on tan(latitude) from tau'/(1 - e^2) (no data-dependent loop).
+ * ACCURACY of that rule, measured against a 50-digit reference that shares nothing with the series (tests/projection_truth.py: the
+ * conformal map from its definition, by complex Newton and quadrature; fixture tests/golden/projection_truth.npz), as |float64 evaluation
+ * of the rule (tests/warp_reference.py) - truth| on the ground.  Within 40 degrees of the central meridian, latitudes to 89.9: forward
+ * <= 3.8e-9 m, inverse (E - FE within 4800 km) <= 7.5e-8 m, and <= 4.1e-7 m within 0.6 degrees of a pole, which is the rounding of that
+ * evaluation (instageo_amd/crs.py stays within 2e-9 m there); web Mercator and the chains between systems <= 5.8e-8 m.  The device is
+ * held to 1e-6 m on all of these (tests/test_gpu_projection_truth.py).  BEYOND 40 degrees the truncated series itself is off, forward,
+ * worst per band of |longitude - lon0|:
+ *     latitude    (40, 50]    (50, 60]    (60, 70]    (70, 79.9]
+ *        0        1.3e-7 m    1.1e-5 m    4.8e-3 m    118 m      (4.7 m at 77.5 degrees)
+ *       20        3.8e-8 m    1.1e-6 m    3.9e-5 m    1.1e-3 m
+ *       45        2.1e-9 m    5.7e-9 m    1.3e-8 m    3.5e-8 m
+ * and <= 3.5e-8 m everywhere from 45 degrees of latitude up.  So the domain declared below (|longitude - lon0| < 80 degrees) reaches into
+ * a region where, near the equator, the coordinates are wrong by centimetres from 70 degrees on and by about 100 m at its edge; the
+ * kernels are exact evaluations of the series there (within twice its own error), not of the projection.  Sources that far from their
+ * meridian are off-raster in every caller.  A GRID is four doubles (X0, Y0, sx, sy), the outer
  * corner of the top-left pixel and the positive pixel sizes, with its size (h, w): the centre of pixel (r, c) lies at x = X0 + (c + 0.5) sx,
  * y = Y0 - (r + 0.5) sy, and the point (x, y) has the pixel coordinates u = (x - X0) / sx, v = (Y0 - y) / sy, so that pixel (r, c) covers
  * [c, c + 1) x [r, r + 1).
