@@ -2,8 +2,8 @@
 // gdal_rasterize.  The rule (the zonal block's grid and inside test, the last containing feature wins, untouched pixels keep what the
 // raster held) is stated in include/instageo_hip.h.  Everything is integer work or a copy of a caller-supplied value.
 //
-//   1  burn_resolve_kernel   per canvas row: inclusive prefix XOR of the toggles that ig_zone_toggle left on the pass canvas (the scan of
-//                            zone_tally_kernel: thread run of BVPT, wave scan, workgroup scan, carry over the chunks of BCHUNK columns) =
+//   1  burn_resolve_kernel   per canvas row: inclusive prefix XOR of the toggles that ig_zone_toggle left on the pass canvas (zone_scan_chunk
+//                            of zone_canvas.h, the scan of zonal.hip, with its geometry: chunks of ZCHUNK columns, ZVPT per thread) =
 //                            the inside mask of the pass's 64 features; the highest set bit is the last feature in file order; its value
 //                            comes from a 64-entry table in LDS and goes to the raster at (r0 + r, c0 + c).  Pixels with an empty mask
 //                            are not written.  The pixels written are counted per thread, wave and workgroup: one atomic per workgroup.
@@ -15,25 +15,33 @@
 // it shares, so any pitch and any c0 are safe.
 // Out-of-range writes are impossible: the entry point checks that the pass rectangle lies inside the raster, and the kernel writes only
 // columns c < Wp of rows r < Hp of that rectangle.
-#include "common.h"
+#include "zone_canvas.h"
 
 namespace {
 
-constexpr int BTPB = 256, BWAVES = BTPB / 64;
-constexpr int BVPT = 4, BCHUNK = BTPB * BVPT;  // columns a workgroup scans in one step
-constexpr int BBITS = 64, B_MAX_WG = 1024;
 constexpr int CELL_ROWS = 64, MAX_SIDE = 1 << 15, MAX_K = 128;
+
+// The workgroup's sum of `mine`, in thread 0 (the others get 0): wave sums, wcount[ZWAVES], one barrier.  Every thread calls it.
+__device__ __forceinline__ unsigned long long block_total(unsigned mine, unsigned* wcount) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o, 64);
+    if ((threadIdx.x & 63) == 0) wcount[threadIdx.x >> 6] = mine;
+    __syncthreads();
+    unsigned long long total = 0;
+    if (threadIdx.x == 0)
+        for (int w = 0; w < ZWAVES; ++w) total += wcount[w];
+    return total;
+}
 
 // T = signed char (int8 rasters) or unsigned (the bits of float32 rasters)
 template <typename T>
-__global__ __launch_bounds__(BTPB) void burn_resolve_kernel(const unsigned long long* __restrict__ canvas, const T* __restrict__ table,
+__global__ __launch_bounds__(ZTPB) void burn_resolve_kernel(const unsigned long long* __restrict__ canvas, const T* __restrict__ table,
                                                             T* __restrict__ out, unsigned long long* __restrict__ written, int Hp, int Wp,
                                                             long pitch, int r0, int c0) {
-    __shared__ T tab[BBITS];
-    __shared__ unsigned long long wtot[2][BWAVES];  // the wave totals of two consecutive chunks (one barrier per chunk)
-    __shared__ unsigned wcount[BWAVES];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (threadIdx.x < BBITS) tab[threadIdx.x] = table[threadIdx.x];
+    __shared__ T tab[ZBITS];
+    __shared__ unsigned long long wtot[2][ZWAVES];  // the wave totals of two consecutive chunks (one barrier per chunk)
+    __shared__ unsigned wcount[ZWAVES];
+    if (threadIdx.x < ZBITS) tab[threadIdx.x] = table[threadIdx.x];
     __syncthreads();
     unsigned mine = 0;  // pixels this thread stored: at most Hp * Wp <= 2^31 - 1
     int par = 0;
@@ -41,35 +49,17 @@ __global__ __launch_bounds__(BTPB) void burn_resolve_kernel(const unsigned long 
         const unsigned long long* row = canvas + (long)r * Wp;
         T* orow = out + ((long)r0 + r) * pitch + c0;
         unsigned long long carry = 0;  // the prefix XOR of the row's earlier chunks: the same in every thread
-        for (long cc = 0; cc < Wp; cc += BCHUNK, par ^= 1) {
-            const long c = cc + (long)threadIdx.x * BVPT;
-            unsigned long long v[BVPT];
-#pragma unroll
-            for (int j = 0; j < BVPT; ++j) {
-                v[j] = c + j < Wp ? row[c + j] : 0ull;
-                if (j) v[j] ^= v[j - 1];
-            }
-            unsigned long long t = v[BVPT - 1];  // inclusive scan of the thread totals over the wave
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const unsigned long long u = __shfl_up(t, o, 64);
-                if (lane >= o) t ^= u;
-            }
-            if (lane == 63) wtot[par][wave] = t;
-            __syncthreads();
-            unsigned long long pre = carry ^ t ^ v[BVPT - 1];  // XOR undoes itself: inclusive ^ own = exclusive
-#pragma unroll
-            for (int w = 0; w < BWAVES; ++w) {
-                const unsigned long long u = wtot[par][w];
-                if (w < wave) pre ^= u;
-                carry ^= u;
-            }
-            T val[BVPT];
-            bool hit[BVPT];
+        for (long cc = 0; cc < Wp; cc += ZCHUNK, par ^= 1) {
+            const long c = cc + (long)threadIdx.x * ZVPT;
+            unsigned long long v[ZVPT];
+            zone_load_toggles(v, row, c, Wp);
+            zone_scan_chunk(v, carry, wtot[par]);  // every thread of the workgroup, whatever its columns
+            T val[ZVPT];
+            bool hit[ZVPT];
             int hits = 0;
 #pragma unroll
-            for (int j = 0; j < BVPT; ++j) {
-                const unsigned long long m = c + j < Wp ? v[j] ^ pre : 0ull;
+            for (int j = 0; j < ZVPT; ++j) {
+                const unsigned long long m = c + j < Wp ? v[j] : 0ull;  // a dead column's mask is dropped
                 hit[j] = m != 0;
                 val[j] = tab[hit[j] ? 63 - __clzll((long long)m) : 0];
                 hits += hit[j];
@@ -77,7 +67,7 @@ __global__ __launch_bounds__(BTPB) void burn_resolve_kernel(const unsigned long 
             mine += (unsigned)hits;
             bool packed = false;
             if constexpr (sizeof(T) == 1) {
-                if (hits == BVPT && ((uintptr_t)(orow + c) & 3) == 0) {
+                if (hits == ZVPT && ((uintptr_t)(orow + c) & 3) == 0) {
                     // all four pixels of this thread, word aligned: the word is private to the thread
                     const unsigned word = (unsigned)(unsigned char)val[0] | (unsigned)(unsigned char)val[1] << 8 |
                                           (unsigned)(unsigned char)val[2] << 16 | (unsigned)(unsigned char)val[3] << 24;
@@ -87,33 +77,26 @@ __global__ __launch_bounds__(BTPB) void burn_resolve_kernel(const unsigned long 
             }
             if (!packed) {
 #pragma unroll
-                for (int j = 0; j < BVPT; ++j)
+                for (int j = 0; j < ZVPT; ++j)
                     if (hit[j]) orow[c + j] = val[j];
             }
         }
     }
     if (!written) return;  // uniform over the grid
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o, 64);
-    if (lane == 0) wcount[wave] = mine;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long total = 0;
-        for (int w = 0; w < BWAVES; ++w) total += wcount[w];
-        if (total) atomicAdd(written, total);
-    }
+    const unsigned long long total = block_total(mine, wcount);
+    if (total) atomicAdd(written, total);
 }
 
 // grid (cells, ceil(S / CELL_ROWS)).  LDS: tab[max(K, 1)] u32 (dynamic; a cell counts at most CELL_ROWS * S <= 2^21 pixels).
 template <bool F32>
-__global__ __launch_bounds__(BTPB) void label_cells_kernel(const void* __restrict__ raster, unsigned long long* __restrict__ valid,
+__global__ __launch_bounds__(ZTPB) void label_cells_kernel(const void* __restrict__ raster, unsigned long long* __restrict__ valid,
                                                            unsigned long long* __restrict__ hist, int nx, int S, int ignore, int K,
                                                            FDiv by_s) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned* tab = reinterpret_cast<unsigned*>(smem);
-    __shared__ unsigned wcount[BWAVES];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int i = threadIdx.x; i < K; i += BTPB) tab[i] = 0u;
+    __shared__ unsigned wcount[ZWAVES];
+    const int lane = threadIdx.x & 63;
+    for (int i = threadIdx.x; i < K; i += ZTPB) tab[i] = 0u;
     __syncthreads();
     const long cell = blockIdx.x;
     const long cy = cell / nx, cx = cell - cy * nx;
@@ -123,7 +106,7 @@ __global__ __launch_bounds__(BTPB) void label_cells_kernel(const void* __restric
     const long base = (cy * S + row0) * W + cx * S;
     const int n = rows * S;  // <= 2^21
     unsigned mine = 0;
-    for (int first = 0; first < n; first += BTPB) {  // uniform trip count: every lane takes part in the ballots below
+    for (int first = 0; first < n; first += ZTPB) {  // uniform trip count: every lane takes part in the ballots below
         const int idx = first + (int)threadIdx.x;
         int k = -1;  // the histogram cell, or none
         if (idx < n) {
@@ -148,16 +131,9 @@ __global__ __launch_bounds__(BTPB) void label_cells_kernel(const void* __restric
             todo &= ~same;
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o, 64);
-    if (lane == 0) wcount[wave] = mine;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long total = 0;
-        for (int w = 0; w < BWAVES; ++w) total += wcount[w];
-        if (total) atomicAdd(valid + cell, total);
-    }
-    for (int i = threadIdx.x; i < K; i += BTPB)
+    const unsigned long long total = block_total(mine, wcount);  // its barrier also ends the adds to tab
+    if (total) atomicAdd(valid + cell, total);
+    for (int i = threadIdx.x; i < K; i += ZTPB)
         if (tab[i]) atomicAdd(hist + cell * K + i, (unsigned long long)tab[i]);
 }
 
@@ -181,11 +157,11 @@ int ig_burn_resolve(const unsigned long long* canvas, int Hp, int Wp, const void
     IG_REQUIRE(((uintptr_t)canvas & 7) == 0 && ((uintptr_t)written & 7) == 0, "ig_burn_resolve: canvas and written must be 8-byte aligned");
     IG_REQUIRE(elem_size == 1 || (((uintptr_t)table & 3) == 0 && ((uintptr_t)out & 3) == 0),
                "ig_burn_resolve: a float32 table and raster must be 4-byte aligned");
-    const dim3 grid((unsigned)(Hp < B_MAX_WG ? Hp : B_MAX_WG));
+    const dim3 grid((unsigned)(Hp < MAX_WG ? Hp : MAX_WG));
     if (elem_size == 1)
-        return ig_launch<burn_resolve_kernel<signed char>>("ig_burn_resolve", grid, dim3(BTPB), 0, ST(stream), canvas, (const signed char*)table,
+        return ig_launch<burn_resolve_kernel<signed char>>("ig_burn_resolve", grid, dim3(ZTPB), 0, ST(stream), canvas, (const signed char*)table,
                                                           (signed char*)out, written, Hp, Wp, pitch, r0, c0);
-    return ig_launch<burn_resolve_kernel<unsigned>>("ig_burn_resolve", grid, dim3(BTPB), 0, ST(stream), canvas, (const unsigned*)table,
+    return ig_launch<burn_resolve_kernel<unsigned>>("ig_burn_resolve", grid, dim3(ZTPB), 0, ST(stream), canvas, (const unsigned*)table,
                                                    (unsigned*)out, written, Hp, Wp, pitch, r0, c0);
 }
 
@@ -207,9 +183,9 @@ int ig_label_cells(const void* raster, int ny, int nx, int S, int elem_size, int
     const dim3 grid((unsigned)((long)ny * nx), (unsigned)((S + CELL_ROWS - 1) / CELL_ROWS));
     const int smem = (K > 0 ? K : 1) * 4;
     if (elem_size == 4)
-        return ig_launch<label_cells_kernel<true>>("ig_label_cells", grid, dim3(BTPB), smem, ST(stream), raster, valid, hist, nx, S, ignore, K,
+        return ig_launch<label_cells_kernel<true>>("ig_label_cells", grid, dim3(ZTPB), smem, ST(stream), raster, valid, hist, nx, S, ignore, K,
                                                    make_fdiv(S));
-    return ig_launch<label_cells_kernel<false>>("ig_label_cells", grid, dim3(BTPB), smem, ST(stream), raster, valid, hist, nx, S, ignore, K,
+    return ig_launch<label_cells_kernel<false>>("ig_label_cells", grid, dim3(ZTPB), smem, ST(stream), raster, valid, hist, nx, S, ignore, K,
                                                 make_fdiv(S));
 }
 

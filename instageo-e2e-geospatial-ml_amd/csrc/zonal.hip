@@ -2,11 +2,12 @@
 // class.  Not in the reference.  The rule (Q = 256 fixed point, half-open crossing, even-odd on pixel centres) is stated in
 // include/instageo_hip.h.  Everything is integer arithmetic and every result is unique (independent of scheduling).
 //
-//   1  zone_edge_rows_kernel   per edge: the number of raster rows whose centre line it crosses
-//   2  zone_toggle_kernel      per (edge, crossed row) pair, found by binary search in the caller's exclusive scan of (1): the first column
-//                              whose centre lies at or right of the crossing, and one 64-bit atomic XOR of the zone's bit there
-//   3  zone_tally_kernel       per row: inclusive prefix XOR of the toggles (thread run of ZVPT, wave scan, workgroup scan, carry over the
-//                              chunks of ZCHUNK columns), which is the inside mask of 64 zones; every set bit is counted into an LDS table
+//   1  zone_rows_kernel<rows_of>  per edge: the number of raster rows whose centre line it crosses
+//   2  zone_toggle_kernel      per (edge, crossed row) pair, found by binary search in the caller's exclusive scan of (1) (edge_of_item): the
+//                              first column whose centre lies at or right of the crossing, and one 64-bit atomic XOR of the zone's bit there
+//   3  zone_tally_kernel       per row: inclusive prefix XOR of the toggles (zone_scan_chunk of zone_canvas.h, shared with burn.hip: thread run
+//                              of ZVPT, wave scan, workgroup scan, carry over the chunks of ZCHUNK columns), which is the inside mask of 64
+//                              zones; every set bit is counted into an LDS table
 //                              [64][ncls + 1] and the table reaches memory as one 64-bit add per non-empty cell and workgroup
 //   4  zone_value_tally_kernel the same rows and the same scan over a float32 raster of up to 8 bands: per zone bit and band the valid
 //                              values' (n, sum, M2, min, max), merged as triples (Chan, Golub, LeVeque) through the wave, the wave's LDS
@@ -18,7 +19,8 @@
 //                              the round's 8-bit digit: unsigned integer atomics, equal targets merged across the wave first
 //   7  zone_quantile_pick_kernel  per (band, zone bit, slot): the digit that holds the wanted rank; after the last round the values
 //   (6) and (7) count with integer atomics only and select members of the data: unique results as well.
-//   8  zone_touch_rows_kernel  all_touched (the rule: include/instageo_hip.h): per edge the number of raster rows whose open strip it meets
+//   8  zone_rows_kernel<touch_rows_of>  all_touched (the rule: include/instageo_hip.h): per edge the number of raster rows whose open strip
+//                              it meets; (1) over the other span
 //   9  zone_touch_kernel       per (edge, touched row) pair: the columns whose open square the edge meets in that row, exact rationals in
 //                              int64, and a 64-bit atomic OR of the zone's bit into each of them on a second canvas.  A lane writes a span of
 //                              up to ZT_SHORT columns itself; longer ones are taken by the whole wave, one after the other, 64 columns a step
@@ -32,36 +34,54 @@
 // Every launch does a fixed amount of work; no workgroup waits for another (a workgroup owns whole rows, so the carry between the chunks
 // of a long row stays in a register).  Out-of-range writes are impossible: a row or column outside the raster, an item past its edge's
 // rows (a scan that does not belong to the edges) and a bit outside 0..63 are dropped.
-#include "common.h"
+#include "zone_canvas.h"
 
 namespace {
 
-constexpr int ZTPB = 256, ZWAVES = ZTPB / 64;
-constexpr int ZVPT = 4, ZCHUNK = ZTPB * ZVPT;  // columns a workgroup scans in one step
-constexpr int ZQ = 256, ZHALF = 128;           // fixed-point units per pixel; the centre's offset
-constexpr int ZLIMIT = 1 << 29;                // |X|, |Y| <= 2^29
-constexpr int ZBITS = 64, MAX_NCLS = 127, MAX_WG = 1024;
+constexpr int ZQ = 256, ZHALF = 128;  // fixed-point units per pixel; the centre's offset
+constexpr int ZLIMIT = 1 << 29;       // |X|, |Y| <= 2^29
+constexpr int MAX_NCLS = 127;
 
 struct RowSpan {
-    int lo, n;  // first crossed row in [0, H) and their number
+    int lo, n;  // first row in [0, H) and their number
 };
 
-// rows r with (y0 <= Yc) != (y1 <= Yc), Yc = 256 r + 128: min(y0, y1) <= Yc < max(y0, y1).  An edge with a coordinate beyond the limit
-// crosses nothing (the host refuses such zones; this keeps every difference below 2^31 whatever arrives).
-__device__ __forceinline__ RowSpan rows_of(const int4 e, int H) {
+// The rows floor((ymin + below) / 256) .. floor((ymax + above) / 256) of an edge (arithmetic shift = floor), clamped to [0, H).  An edge
+// with a coordinate beyond the limit has none (the host refuses such zones; this keeps every difference below 2^31 whatever arrives).
+__device__ __forceinline__ RowSpan row_span(const int4 e, int H, int below, int above) {
     const int lim = ZLIMIT;
     if (e.x < -lim || e.x > lim || e.y < -lim || e.y > lim || e.z < -lim || e.z > lim || e.w < -lim || e.w > lim) return RowSpan{0, 0};
     const int ylo = e.y < e.w ? e.y : e.w, yhi = e.y < e.w ? e.w : e.y;
-    int lo = (ylo - ZHALF + ZQ - 1) >> 8;  // ceil((ylo - 128) / 256): arithmetic shift = floor
-    int hi = (yhi - ZHALF - 1) >> 8;       // floor((yhi - 129) / 256)
+    int lo = (ylo + below) >> 8, hi = (yhi + above) >> 8;
     lo = lo < 0 ? 0 : lo;
     hi = hi > H - 1 ? H - 1 : hi;
     return RowSpan{lo, hi >= lo ? hi - lo + 1 : 0};
 }
 
-__global__ __launch_bounds__(ZTPB) void zone_edge_rows_kernel(const int4* __restrict__ edges, int* __restrict__ rows, long E, int H) {
+// rows r with (y0 <= Yc) != (y1 <= Yc), Yc = 256 r + 128: min(y0, y1) <= Yc < max(y0, y1), i.e. ceil((ymin - 128) / 256) <= r <=
+// floor((ymax - 129) / 256)
+__device__ __forceinline__ RowSpan rows_of(const int4 e, int H) { return row_span(e, H, ZQ - 1 - ZHALF, -ZHALF - 1); }
+
+// all_touched: rows r whose open strip (256 r, 256 r + 256) the edge's y range meets: floor(ymin / 256) <= r <= ceil(ymax / 256) - 1.  Empty
+// for a horizontal edge on a row border.
+__device__ __forceinline__ RowSpan touch_rows_of(const int4 e, int H) { return row_span(e, H, 0, -1); }
+
+template <RowSpan (*Rows)(const int4, int)>
+__global__ __launch_bounds__(ZTPB) void zone_rows_kernel(const int4* __restrict__ edges, int* __restrict__ rows, long E, int H) {
     const long e = blockIdx.x * (long)ZTPB + threadIdx.x;
-    if (e < E) rows[e] = rows_of(edges[e], H).n;
+    if (e < E) rows[e] = Rows(edges[e], H).n;
+}
+
+// Item t of a launch over (edge, row) pairs belongs to the last edge e with first[e] <= t (first = the caller's exclusive scan of the
+// edges' row counts): its rows are items first[e] .. first[e + 1] - 1.
+__device__ __forceinline__ long edge_of_item(const long long* __restrict__ first, long E, long t) {
+    long lo = 0, hi = E;
+    while (hi - lo > 1) {
+        const long mid = (lo + hi) >> 1;
+        if (first[mid] <= t) lo = mid;
+        else hi = mid;
+    }
+    return lo;
 }
 
 __global__ __launch_bounds__(ZTPB) void zone_toggle_kernel(const int4* __restrict__ edges, const unsigned char* __restrict__ bit,
@@ -69,12 +89,7 @@ __global__ __launch_bounds__(ZTPB) void zone_toggle_kernel(const int4* __restric
                                                            long E, long T, int H, int W) {
     const long t = blockIdx.x * (long)ZTPB + threadIdx.x;
     if (t >= T) return;
-    long lo = 0, hi = E;  // the last e with first[e] <= t: its rows are first[e] .. first[e + 1] - 1
-    while (hi - lo > 1) {
-        const long mid = (lo + hi) >> 1;
-        if (first[mid] <= t) lo = mid;
-        else hi = mid;
-    }
+    const long lo = edge_of_item(first, E, t);
     const long long k = t - first[lo];
     const int4 e = edges[lo];
     const RowSpan span = rows_of(e, H);
@@ -94,50 +109,8 @@ __global__ __launch_bounds__(ZTPB) void zone_toggle_kernel(const int4* __restric
     if (c < W) atomicXor(canvas + (long)r * W + c, 1ull << b);
 }
 
-// The scan, once for every kernel that turns toggles into inside masks: the inclusive prefix XOR of one chunk of ZCHUNK columns of a
-// canvas row, continued from the row's earlier chunks.  v[j] = the toggles of this thread's columns c .. c + ZVPT - 1 (0 past the row's
-// end) become the inside masks of those columns (dead columns hold the mask of the last live one: the caller drops them).  Thread run,
-// wave scan, workgroup scan through wtot (the wave totals of this chunk: the caller alternates two of them, so one barrier per chunk is
-// enough), and carry = the prefix XOR of the row's earlier chunks, the same in every thread, updated for the next chunk.  Every thread of
-// the workgroup calls it (it holds a barrier).
-__device__ __forceinline__ void zone_scan_chunk(unsigned long long (&v)[ZVPT], unsigned long long& carry, unsigned long long* wtot) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int j = 1; j < ZVPT; ++j) v[j] ^= v[j - 1];
-    unsigned long long t = v[ZVPT - 1];  // inclusive scan of the thread totals over the wave
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned long long u = __shfl_up(t, o, 64);
-        if (lane >= o) t ^= u;
-    }
-    if (lane == 63) wtot[wave] = t;
-    __syncthreads();
-    unsigned long long pre = carry ^ t ^ v[ZVPT - 1];  // XOR undoes itself: inclusive ^ own = exclusive
-#pragma unroll
-    for (int w = 0; w < ZWAVES; ++w) {
-        const unsigned long long u = wtot[w];
-        if (w < wave) pre ^= u;
-        carry ^= u;
-    }
-#pragma unroll
-    for (int j = 0; j < ZVPT; ++j) v[j] ^= pre;
-}
-
 // ---- all_touched: the pixels whose open square an edge meets --------------------------------------------------------------------------------
 constexpr int ZT_SHORT = 4;  // columns a lane writes on its own; a longer span is written by its wave
-
-// rows r whose open strip (256 r, 256 r + 256) the edge's y range meets: floor(ymin / 256) <= r <= ceil(ymax / 256) - 1, in [0, H).  Empty
-// for a horizontal edge on a row border; an edge with a coordinate beyond the limit touches nothing (as it crosses nothing).
-__device__ __forceinline__ RowSpan touch_rows_of(const int4 e, int H) {
-    const int lim = ZLIMIT;
-    if (e.x < -lim || e.x > lim || e.y < -lim || e.y > lim || e.z < -lim || e.z > lim || e.w < -lim || e.w > lim) return RowSpan{0, 0};
-    const int ylo = e.y < e.w ? e.y : e.w, yhi = e.y < e.w ? e.w : e.y;
-    int lo = ylo >> 8;              // floor: arithmetic shift
-    int hi = ((yhi + ZQ - 1) >> 8) - 1;  // ceil(yhi / 256) - 1
-    lo = lo < 0 ? 0 : lo;
-    hi = hi > H - 1 ? H - 1 : hi;
-    return RowSpan{lo, hi >= lo ? hi - lo + 1 : 0};
-}
 
 __device__ __forceinline__ long long floor_div(long long n, long long d) {  // d > 0
     const long long q = n / d;
@@ -175,11 +148,6 @@ __device__ __forceinline__ ColSpan touch_cols_of(const int4 e, int r, int W) {
     return ColSpan{(int)lo, hi >= lo ? (int)(hi - lo + 1) : 0};
 }
 
-__global__ __launch_bounds__(ZTPB) void zone_touch_rows_kernel(const int4* __restrict__ edges, int* __restrict__ rows, long E, int H) {
-    const long e = blockIdx.x * (long)ZTPB + threadIdx.x;
-    if (e < E) rows[e] = touch_rows_of(edges[e], H).n;
-}
-
 // No lane leaves before the end: the long spans are written by all 64 lanes of the wave.  Every address is row r < H, column < W of the
 // (H, W) canvas: r and the span come clamped from touch_rows_of / touch_cols_of, and a lane without an item holds an empty span.
 __global__ __launch_bounds__(ZTPB) void zone_touch_kernel(const int4* __restrict__ edges, const unsigned char* __restrict__ bit,
@@ -191,12 +159,7 @@ __global__ __launch_bounds__(ZTPB) void zone_touch_kernel(const int4* __restrict
     int n = 0;    // its columns
     unsigned long long mask = 0;
     if (t < T) {
-        long lo = 0, hi = E;  // the last e with first[e] <= t, as zone_toggle_kernel finds it
-        while (hi - lo > 1) {
-            const long mid = (lo + hi) >> 1;
-            if (first[mid] <= t) lo = mid;
-            else hi = mid;
-        }
+        const long lo = edge_of_item(first, E, t);
         const long long k = t - first[lo];
         const int4 e = edges[lo];
         const RowSpan rows = touch_rows_of(e, H);
@@ -234,12 +197,8 @@ __global__ __launch_bounds__(ZTPB) void zone_touch_merge_kernel(unsigned long lo
         for (long c0 = 0; c0 < W; c0 += ZCHUNK, par ^= 1) {
             const long c = c0 + (long)threadIdx.x * ZVPT;
             unsigned long long v[ZVPT], tb[ZVPT];
-#pragma unroll
-            for (int j = 0; j < ZVPT; ++j) {
-                const bool live = c + j < W;
-                v[j] = live ? row[c + j] : 0ull;
-                tb[j] = live ? trow[c + j] : 0ull;
-            }
+            zone_load_toggles(v, row, c, W);
+            zone_load_toggles(tb, trow, c, W);
             const unsigned long long left_touch = c > 0 && c < W ? trow[c - 1] : 0ull;
             const unsigned long long own = v[0];
             zone_scan_chunk(v, carry, wtot[par]);
@@ -276,12 +235,11 @@ __global__ __launch_bounds__(ZTPB) void zone_tally_kernel(unsigned long long* __
             const long c = c0 + (long)threadIdx.x * ZVPT;
             unsigned long long v[ZVPT];
             int k[ZVPT];
+            zone_load_toggles(v, row, c, W);
 #pragma unroll
             for (int j = 0; j < ZVPT; ++j) {
-                v[j] = 0;
                 k[j] = ncls;
                 if (c + j < W) {
-                    v[j] = row[c + j];
                     const int s = cls ? crow[c + j] : fill;
                     if (s != fill && s >= 0 && s < ncls) k[j] = s;
                 }
@@ -375,8 +333,7 @@ __global__ __launch_bounds__(ZTPB) void zone_value_tally_kernel(const unsigned l
         for (long c0 = 0; c0 < W; c0 += ZCHUNK, par ^= 1) {
             const long c = c0 + (long)threadIdx.x * ZVPT;
             unsigned long long m[ZVPT];
-#pragma unroll
-            for (int j = 0; j < ZVPT; ++j) m[j] = c + j < W ? row[c + j] : 0ull;
+            zone_load_toggles(m, row, c, W);
             zone_scan_chunk(m, carry, wtot[par]);  // the workgroup's only barrier in this loop: what follows is per wave
             unsigned long long present = 0;
 #pragma unroll
@@ -546,8 +503,7 @@ __global__ __launch_bounds__(ZTPB) void zone_quantile_hist_kernel(const unsigned
         for (long c0 = 0; c0 < W; c0 += ZCHUNK, par ^= 1) {
             const long c = c0 + (long)threadIdx.x * ZVPT;
             unsigned long long m[ZVPT];
-#pragma unroll
-            for (int j = 0; j < ZVPT; ++j) m[j] = c + j < W ? row[c + j] : 0ull;
+            zone_load_toggles(m, row, c, W);
             zone_scan_chunk(m, carry, wtot[par]);  // the workgroup's only barrier in this loop: what follows is per wave
             unsigned long long present = 0;
 #pragma unroll
@@ -664,28 +620,35 @@ __global__ __launch_bounds__(ZQ_MAX_SLOTS) void zone_quantile_pick_kernel(unsign
     IG_REQUIRE(H >= 0 && W >= 0, name ": need H >= 0 and W >= 0 (H %d, W %d)", H, W);               \
     IG_REQUIRE((long)H * W <= 0x7fffffffL, name ": H * W = %ld exceeds 2^31 - 1", (long)H * W)
 
+// the checks of the two launches over edges (rows of `edges`, E, H) and of the two over (edge, row) items, whose T counts `items` and
+// which write the canvas `out`; an empty call returns before a pointer is looked at
+#define IG_REQUIRE_EDGE_ROWS(name)                                                           \
+    IG_REQUIRE(E >= 0 && E <= 0x7fffffffL, name ": need 0 <= E <= 2^31 - 1 (got %ld)", E);   \
+    IG_REQUIRE(H >= 0, name ": need H >= 0 (got %d)", H);                                    \
+    if (E == 0) return IG_OK;                                                                \
+    IG_REQUIRE(edges && rows, name ": null pointer");                                        \
+    IG_REQUIRE(((uintptr_t)edges & 15) == 0, name ": edges must be 16-byte aligned")
+#define IG_REQUIRE_EDGE_ITEMS(name, out, items)                                                              \
+    IG_REQUIRE(E >= 0 && E <= 0x7fffffffL, name ": need 0 <= E <= 2^31 - 1 (got %ld)", E);                   \
+    IG_REQUIRE(T >= 0 && T <= (1L << 38), name ": need 0 <= T <= 2^38 " items " per call (got %ld)", T);     \
+    IG_REQUIRE_RASTER(name);                                                                                 \
+    if (E == 0 || T == 0 || (long)H * W == 0) return IG_OK;                                                  \
+    IG_REQUIRE(edges && bit && first && out, name ": null pointer");                                         \
+    IG_REQUIRE(((uintptr_t)edges & 15) == 0, name ": edges must be 16-byte aligned");                        \
+    IG_REQUIRE(((uintptr_t)first & 7) == 0 && ((uintptr_t)out & 7) == 0, name ": first and " #out " must be 8-byte aligned")
+
 static inline dim3 blocks_for(long items) { return dim3((unsigned)((items + ZTPB - 1) / ZTPB)); }
 
 extern "C" {
 
 int ig_zone_edge_rows(const int* edges, int* rows, long E, int H, void* stream) {
-    IG_REQUIRE(E >= 0 && E <= 0x7fffffffL, "ig_zone_edge_rows: need 0 <= E <= 2^31 - 1 (got %ld)", E);
-    IG_REQUIRE(H >= 0, "ig_zone_edge_rows: need H >= 0 (got %d)", H);
-    if (E == 0) return IG_OK;
-    IG_REQUIRE(edges && rows, "ig_zone_edge_rows: null pointer");
-    IG_REQUIRE(((uintptr_t)edges & 15) == 0, "ig_zone_edge_rows: edges must be 16-byte aligned");
-    return ig_launch<zone_edge_rows_kernel>("ig_zone_edge_rows", blocks_for(E), dim3(ZTPB), 0, ST(stream), (const int4*)edges, rows, E, H);
+    IG_REQUIRE_EDGE_ROWS("ig_zone_edge_rows");
+    return ig_launch<zone_rows_kernel<rows_of>>("ig_zone_edge_rows", blocks_for(E), dim3(ZTPB), 0, ST(stream), (const int4*)edges, rows, E, H);
 }
 
 int ig_zone_toggle(const int* edges, const unsigned char* bit, const long long* first, unsigned long long* canvas, long E, long T, int H,
                    int W, void* stream) {
-    IG_REQUIRE(E >= 0 && E <= 0x7fffffffL, "ig_zone_toggle: need 0 <= E <= 2^31 - 1 (got %ld)", E);
-    IG_REQUIRE(T >= 0 && T <= (1L << 38), "ig_zone_toggle: need 0 <= T <= 2^38 crossings per call (got %ld)", T);
-    IG_REQUIRE_RASTER("ig_zone_toggle");
-    if (E == 0 || T == 0 || (long)H * W == 0) return IG_OK;
-    IG_REQUIRE(edges && bit && first && canvas, "ig_zone_toggle: null pointer");
-    IG_REQUIRE(((uintptr_t)edges & 15) == 0, "ig_zone_toggle: edges must be 16-byte aligned");
-    IG_REQUIRE(((uintptr_t)first & 7) == 0 && ((uintptr_t)canvas & 7) == 0, "ig_zone_toggle: first and canvas must be 8-byte aligned");
+    IG_REQUIRE_EDGE_ITEMS("ig_zone_toggle", canvas, "crossings");
     return ig_launch<zone_toggle_kernel>("ig_zone_toggle", blocks_for(T), dim3(ZTPB), 0, ST(stream), (const int4*)edges, bit, first, canvas, E,
                                          T, H, W);
 }
@@ -703,23 +666,14 @@ int ig_zone_tally(unsigned long long* canvas, const signed char* cls, unsigned l
 }
 
 int ig_zone_touch_rows(const int* edges, int* rows, long E, int H, void* stream) {
-    IG_REQUIRE(E >= 0 && E <= 0x7fffffffL, "ig_zone_touch_rows: need 0 <= E <= 2^31 - 1 (got %ld)", E);
-    IG_REQUIRE(H >= 0, "ig_zone_touch_rows: need H >= 0 (got %d)", H);
-    if (E == 0) return IG_OK;
-    IG_REQUIRE(edges && rows, "ig_zone_touch_rows: null pointer");
-    IG_REQUIRE(((uintptr_t)edges & 15) == 0, "ig_zone_touch_rows: edges must be 16-byte aligned");
-    return ig_launch<zone_touch_rows_kernel>("ig_zone_touch_rows", blocks_for(E), dim3(ZTPB), 0, ST(stream), (const int4*)edges, rows, E, H);
+    IG_REQUIRE_EDGE_ROWS("ig_zone_touch_rows");
+    return ig_launch<zone_rows_kernel<touch_rows_of>>("ig_zone_touch_rows", blocks_for(E), dim3(ZTPB), 0, ST(stream), (const int4*)edges, rows, E,
+                                                      H);
 }
 
 int ig_zone_touch(const int* edges, const unsigned char* bit, const long long* first, unsigned long long* touch, long E, long T, int H, int W,
                   void* stream) {
-    IG_REQUIRE(E >= 0 && E <= 0x7fffffffL, "ig_zone_touch: need 0 <= E <= 2^31 - 1 (got %ld)", E);
-    IG_REQUIRE(T >= 0 && T <= (1L << 38), "ig_zone_touch: need 0 <= T <= 2^38 touched rows per call (got %ld)", T);
-    IG_REQUIRE_RASTER("ig_zone_touch");
-    if (E == 0 || T == 0 || (long)H * W == 0) return IG_OK;
-    IG_REQUIRE(edges && bit && first && touch, "ig_zone_touch: null pointer");
-    IG_REQUIRE(((uintptr_t)edges & 15) == 0, "ig_zone_touch: edges must be 16-byte aligned");
-    IG_REQUIRE(((uintptr_t)first & 7) == 0 && ((uintptr_t)touch & 7) == 0, "ig_zone_touch: first and touch must be 8-byte aligned");
+    IG_REQUIRE_EDGE_ITEMS("ig_zone_touch", touch, "touched rows");
     return ig_launch<zone_touch_kernel>("ig_zone_touch", blocks_for(T), dim3(ZTPB), 0, ST(stream), (const int4*)edges, bit, first, touch, E, T,
                                         H, W);
 }

@@ -1008,30 +1008,40 @@ def ring_emit(root, ring_id, rank, tail, flag, first, n_vertices: int):
 ZONE_BITS = 64  # zones per pass: one bit of the uint64 canvas each
 
 
-def zone_edge_rows(edges, H: int):
-    """edges (E, 4) int32 {x0, y0, x1, y1} in Q = 256 fixed point -> (E,) int32: the rows in [0, H) whose centre line each edge crosses
-    (include/instageo_hip.h)."""
+def _zone_rows(entry: str, edges, H: int):
     assert edges.dtype == torch.int32 and edges.dim() == 2 and edges.shape[1] == 4
     E = edges.shape[0]
     rows = torch.zeros(E, dtype=torch.int32, device=edges.device)
     if E:
-        _call("ig_zone_edge_rows", float(E) * 20, _p(edges), _p(rows), E, int(H), _stream())
+        _call(entry, float(E) * 20, _p(edges), _p(rows), E, int(H), _stream())
     return rows
+
+
+def _zone_items(entry: str, edges, bit, first, out, n_items: int) -> None:
+    """One launch over ``n_items`` (edge, row) pairs that writes the (H, W) canvas ``out``."""
+    E = edges.shape[0]
+    assert edges.dtype == torch.int32 and edges.dim() == 2 and edges.shape[1] == 4 and bit.dtype == torch.uint8 and bit.numel() == E
+    assert first.dtype == torch.int64 and first.numel() == E and out.dtype == torch.int64 and out.dim() == 2
+    H, W = out.shape
+    T = int(n_items)
+    if E == 0 or T == 0 or H * W == 0:
+        return
+    # HBM bytes: per item one 8-byte atomic (ig_zone_touch: at least; how many more depends on the slopes of the edges); the edge and the
+    # steps of the search are cache hits
+    _call(entry, float(T) * 8, _p(edges), _p(bit), _p(first), _p(out), E, T, H, W, _stream())
+
+
+def zone_edge_rows(edges, H: int):
+    """edges (E, 4) int32 {x0, y0, x1, y1} in Q = 256 fixed point -> (E,) int32: the rows in [0, H) whose centre line each edge crosses
+    (include/instageo_hip.h)."""
+    return _zone_rows("ig_zone_edge_rows", edges, H)
 
 
 def zone_toggle(edges, bit, first, canvas, n_crossings: int) -> None:
     """Flip, for each of the ``n_crossings`` (edge, crossed row) pairs, bit ``bit[e]`` of ``canvas`` (H, W) int64 at the first column whose
     centre lies at or right of the crossing; ``first`` (E,) int64 = the exclusive scan of :func:`zone_edge_rows`, ``bit`` (E,) uint8 in
     0..63.  The caller zeroes the canvas."""
-    E = edges.shape[0]
-    assert edges.dtype == torch.int32 and edges.dim() == 2 and edges.shape[1] == 4 and bit.dtype == torch.uint8 and bit.numel() == E
-    assert first.dtype == torch.int64 and first.numel() == E and canvas.dtype == torch.int64 and canvas.dim() == 2
-    H, W = canvas.shape
-    T = int(n_crossings)
-    if E == 0 or T == 0 or H * W == 0:
-        return
-    # HBM bytes: per crossing one 8-byte atomic; the edge and the steps of the search are cache hits
-    _call("ig_zone_toggle", float(T) * 8, _p(edges), _p(bit), _p(first), _p(canvas), E, T, H, W, _stream())
+    _zone_items("ig_zone_toggle", edges, bit, first, canvas, n_crossings)
 
 
 def zone_tally(canvas, classmap, counts, ncls: int = 2, fill: int = -1, write_mask: bool = False) -> None:
@@ -1056,26 +1066,14 @@ def zone_tally(canvas, classmap, counts, ncls: int = 2, fill: int = -1, write_ma
 def zone_touch_rows(edges, H: int):
     """edges (E, 4) int32 {x0, y0, x1, y1} in Q = 256 fixed point -> (E,) int32: the rows in [0, H) each edge touches under the
     all_touched rule (include/instageo_hip.h): the counterpart of :func:`zone_edge_rows`."""
-    assert edges.dtype == torch.int32 and edges.dim() == 2 and edges.shape[1] == 4
-    E = edges.shape[0]
-    rows = torch.zeros(E, dtype=torch.int32, device=edges.device)
-    if E:
-        _call("ig_zone_touch_rows", float(E) * 20, _p(edges), _p(rows), E, int(H), _stream())
-    return rows
+    return _zone_rows("ig_zone_touch_rows", edges, H)
 
 
 def zone_touch(edges, bit, first, touch, n_rows: int) -> None:
     """Set, for each of the ``n_rows`` (edge, touched row) pairs, bit ``bit[e]`` of ``touch`` (H, W) int64 in every column whose open
     square the edge meets in that row; ``first`` (E,) int64 = the exclusive scan of :func:`zone_touch_rows`.  The caller zeroes ``touch``."""
-    E = edges.shape[0]
-    assert edges.dtype == torch.int32 and edges.dim() == 2 and edges.shape[1] == 4 and bit.dtype == torch.uint8 and bit.numel() == E
-    assert first.dtype == torch.int64 and first.numel() == E and touch.dtype == torch.int64 and touch.dim() == 2 and touch.is_contiguous()
-    H, W = touch.shape
-    T = int(n_rows)
-    if E == 0 or T == 0 or H * W == 0:
-        return
-    # HBM bytes: at least one 8-byte atomic per item; how many more depends on the slopes of the edges
-    _call("ig_zone_touch", float(T) * 8, _p(edges), _p(bit), _p(first), _p(touch), E, T, H, W, _stream())
+    assert touch.is_contiguous()
+    _zone_items("ig_zone_touch", edges, bit, first, touch, n_rows)
 
 
 def zone_touch_merge(canvas, touch) -> None:

@@ -291,26 +291,10 @@ def _burn_device(raster, items, stats: Dict[str, int], all_touched: bool = False
     written = torch.zeros(1, dtype=torch.int64, device=dev)
     for p, (_, _, (r0, c0, Hp, Wp)) in enumerate(passes):
         a, b = spans[p]
-        e = e_dev[a:b]
-        rows = ops.zone_edge_rows(e, Hp)
-        first = torch.cumsum(rows, 0, dtype=torch.int64).sub_(rows)
-        T = int(rows.sum(dtype=torch.int64).item())
-        TT = 0
-        if all_touched:
-            trows = ops.zone_touch_rows(e, Hp)
-            TT = int(trows.sum(dtype=torch.int64).item())
-        stats["passes"] += 1
-        if T == 0 and TT == 0:
-            continue
-        canvas = scratch[: Hp * Wp].view(Hp, Wp)
-        canvas.zero_()
-        ops.zone_toggle(e, b_dev[a:b], first, canvas, T)
-        if TT:
-            touch = scratch2[: Hp * Wp].view(Hp, Wp)
-            touch.zero_()
-            ops.zone_touch(e, b_dev[a:b], torch.cumsum(trows, 0, dtype=torch.int64).sub_(trows), touch, TT)
-            ops.zone_touch_merge(canvas, touch)
-        ops.burn_resolve(canvas, t_dev[p], raster, r0, c0, written)
+        canvas = zonal.toggle_canvas(e_dev[a:b], b_dev[a:b], Hp, Wp, all_touched, scratch, scratch2)
+        stats["passes"] += 1  # also a pass that crosses and touches no row
+        if canvas is not None:
+            ops.burn_resolve(canvas, t_dev[p], raster, r0, c0, written)
     stats["pixels_written"] += int(written.item())
 
 

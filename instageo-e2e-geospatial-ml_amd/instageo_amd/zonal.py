@@ -159,6 +159,14 @@ def _check_edges(edges: np.ndarray, edge_zone: np.ndarray, Z: int) -> Tuple[np.n
     return edges, edge_zone.astype(np.int64)
 
 
+def _touch_row_span(ymin: np.ndarray, ymax: np.ndarray, H: int) -> Tuple[np.ndarray, np.ndarray]:
+    """The all_touched rows of edges with ordinates ``ymin`` <= ``ymax`` (int64): floor(ymin / 256) .. ceil(ymax / 256) - 1 in [0, H) ->
+    (the first row, their number, 0 where there is none)."""
+    lo = np.maximum(ymin // Q, 0)
+    hi = np.minimum(-((-ymax) // Q) - 1, H - 1)
+    return lo, np.maximum(hi - lo + 1, 0)
+
+
 def touch_spans(edges: np.ndarray, H: int, W: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
     """The numpy twin of the all_touched span rule (``include/instageo_hip.h``), in int64: ``edges`` (E, 4) {x0, y0, x1, y1} -> (edge,
     row, first column, last column) of every (edge, touched row) pair whose span holds a column of the (H, W) raster.  Rows:
@@ -167,9 +175,7 @@ def touch_spans(edges: np.ndarray, H: int, W: int) -> Tuple[np.ndarray, np.ndarr
     H, W = int(H), int(W)
     x0, y0, x1, y1 = (np.asarray(edges)[:, k].astype(np.int64) for k in range(4))
     ymin, ymax = np.minimum(y0, y1), np.maximum(y0, y1)
-    lo = np.maximum(ymin // Q, 0)
-    hi = np.minimum(-((-ymax) // Q) - 1, H - 1)
-    n = np.maximum(hi - lo + 1, 0)
+    lo, n = _touch_row_span(ymin, ymax, H)
     first = np.cumsum(n) - n
     e = np.repeat(np.arange(len(n)), n)
     r = lo[e] + (np.arange(int(n.sum())) - first[e])
@@ -189,9 +195,7 @@ def touch_spans(edges: np.ndarray, H: int, W: int) -> Tuple[np.ndarray, np.ndarr
 def touch_rows(edges: np.ndarray, H: int) -> np.ndarray:
     """-> (E,) int64: the rows in [0, H) each edge touches, what ``ig_zone_touch_rows`` counts (a row counts whatever its columns are)."""
     y0, y1 = (np.asarray(edges)[:, k].astype(np.int64) for k in (1, 3))
-    lo = np.maximum(np.minimum(y0, y1) // Q, 0)
-    hi = np.minimum(-((-np.maximum(y0, y1)) // Q) - 1, int(H) - 1)
-    return np.maximum(hi - lo + 1, 0)
+    return _touch_row_span(np.minimum(y0, y1), np.maximum(y0, y1), int(H))[1]
 
 
 def touched_mask(edges: np.ndarray, H: int, W: int, rect: Optional[Tuple[int, int, int, int]] = None) -> np.ndarray:
@@ -207,11 +211,42 @@ def touched_mask(edges: np.ndarray, H: int, W: int, rect: Optional[Tuple[int, in
     return np.cumsum(steps, axis=1)[:, :Wp] > 0
 
 
+def toggle_canvas(e: torch.Tensor, bit: torch.Tensor, H: int, W: int, all_touched: bool = False, canvas: Optional[torch.Tensor] = None,
+                  touch: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+    """One pass, for zonal statistics and label burning alike: the edges ``e`` (E, 4) int32 of up to 64 zones on the device, bit ``bit``
+    (E,) uint8 each -> the (H, W) int64 canvas of their toggles (rows counted, scanned, toggled; not yet prefix-XORed), or None when no
+    edge crosses a row (a pass without a crossing has no inside pixel: nothing more is launched).  ``all_touched``: the touched pixels go
+    onto a second canvas and are merged into the toggles (``ig_zone_touch_rows``, ``ig_zone_touch``, ``ig_zone_touch_merge``); None then
+    only if no edge touches a row either.  ``canvas`` / ``touch``: flat int64 scratch of at least H * W elements to build them in (their
+    first H * W elements are zeroed and used); without them fresh memory.  Two host reads: the crossed and the touched rows."""
+    rows = ops.zone_edge_rows(e, H)
+    first = torch.cumsum(rows, 0, dtype=torch.int64).sub_(rows)
+    T = int(rows.sum(dtype=torch.int64).item())
+    TT = 0
+    if all_touched:
+        trows = ops.zone_touch_rows(e, H)
+        TT = int(trows.sum(dtype=torch.int64).item())
+    if T == 0 and TT == 0:
+        return None
+
+    def zeroed(scratch):
+        if scratch is None:
+            return torch.zeros((H, W), dtype=torch.int64, device=e.device)
+        return scratch[: H * W].view(H, W).zero_()
+
+    canvas = zeroed(canvas)
+    ops.zone_toggle(e, bit, first, canvas, T)
+    if TT:
+        touch = zeroed(touch)
+        ops.zone_touch(e, bit, torch.cumsum(trows, 0, dtype=torch.int64).sub_(trows), touch, TT)
+        ops.zone_touch_merge(canvas, touch)
+    return canvas
+
+
 def _passes(edges: np.ndarray, edge_zone: np.ndarray, Z: int, H: int, W: int, device, all_touched: bool = False):
     """Yield (pass, canvas) for those of the ceil(Z / 64) passes whose zones cross a row of the raster at all: the (H, W) int64 canvas
-    holds their toggles, bit ``zone % 64`` each (rows counted, scanned, toggled; not yet prefix-XORed).  A pass without a crossing
-    has no inside pixel and launches nothing.  ``all_touched``: the touched pixels go onto a second canvas and are merged into the
-    toggles (``ig_zone_touch_rows``, ``ig_zone_touch``, ``ig_zone_touch_merge``); a pass is then skipped only if it touches no row either."""
+    holds their toggles, bit ``zone % 64`` each (:func:`toggle_canvas`, which also says what ``all_touched`` adds and when a pass is
+    skipped)."""
     edges, edge_zone = _check_edges(edges, edge_zone, Z)
     if len(edges) == 0 or H * W == 0:
         return
@@ -221,22 +256,9 @@ def _passes(edges: np.ndarray, edge_zone: np.ndarray, Z: int, H: int, W: int, de
             continue
         e = torch.from_numpy(np.ascontiguousarray(edges[sel])).to(device)
         bit = torch.from_numpy((edge_zone[sel] % ops.ZONE_BITS).astype(np.uint8)).to(device)
-        rows = ops.zone_edge_rows(e, H)
-        first = torch.cumsum(rows, 0, dtype=torch.int64).sub_(rows)
-        T = int(rows.sum(dtype=torch.int64).item())
-        TT = 0
-        if all_touched:
-            touch_rows_ = ops.zone_touch_rows(e, H)
-            TT = int(touch_rows_.sum(dtype=torch.int64).item())
-        if T == 0 and TT == 0:
-            continue
-        canvas = torch.zeros((H, W), dtype=torch.int64, device=device)
-        ops.zone_toggle(e, bit, first, canvas, T)
-        if TT:
-            touch = torch.zeros((H, W), dtype=torch.int64, device=device)
-            ops.zone_touch(e, bit, torch.cumsum(touch_rows_, 0, dtype=torch.int64).sub_(touch_rows_), touch, TT)
-            ops.zone_touch_merge(canvas, touch)
-        yield p, canvas
+        canvas = toggle_canvas(e, bit, H, W, all_touched)
+        if canvas is not None:
+            yield p, canvas
 
 
 def zone_masks(edges: np.ndarray, edge_zone: np.ndarray, Z: int, H: int, W: int, device="cuda", all_touched: bool = False) -> torch.Tensor:

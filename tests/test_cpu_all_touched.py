@@ -62,6 +62,22 @@ def test_twin_equals_the_fraction_reference(name):
     assert np.array_equal(got, want.any(axis=0)[rect[0] : rect[0] + rect[2], rect[1] : rect[1] + rect[3]])
 
 
+@pytest.mark.parametrize("name", sorted(AR.cases()))
+def test_touch_rows_are_the_rows_of_the_spans(name):
+    """touch_rows and touch_spans share one row helper: on a raster wide enough for every abscissa (the edges moved right by whole pixels
+    until none lies left of column 0) an edge has exactly one span per touched row.  The exception follows from the rule: a vertical edge
+    on a column border touches rows (a row counts whatever its columns are) but no open square, so it has no span."""
+    H = AR.cases()[name][0]
+    edges = np.array(AR.reference(name)[0]).astype(np.int64)
+    edges[:, [0, 2]] -= int(edges[:, [0, 2]].min()) // zonal.Q * zonal.Q
+    W = int(edges[:, [0, 2]].max()) // zonal.Q + 1
+    on_border = (edges[:, 0] == edges[:, 2]) & (edges[:, 0] % zonal.Q == 0)
+    for h in (H, 1):
+        rows = zonal.touch_rows(edges, h)
+        per_edge = np.bincount(zonal.touch_spans(edges, h, W)[0], minlength=len(edges))
+        assert rows.sum() > 0 and np.array_equal(per_edge, np.where(on_border, 0, rows)), (name, h)
+
+
 def test_hand_built_zones_select_what_the_rule_says():
     H, W, zones = AR.cases()["hand_8x9"]
     edges, edge_zone, Z, touched = AR.reference("hand_8x9")

@@ -285,8 +285,11 @@ def test_header_states_the_rule_for_every_entry_point():
         assert "Q = 256" in part and "(y0 <= Yc) != (y1 <= Yc)" in part and (i == 1 or "xc <= Xc" in part), part[:40]
     for n in NAMES:
         assert re.search(r"\bint %s\(" % n, text)
-    src = open(os.path.join(PKG, "csrc", "zonal.hip")).read()
+    src = open(os.path.join(PKG, "csrc", "zone_canvas.h")).read()  # the geometry zonal.hip and burn.hip share
     assert "ZCHUNK = ZTPB * ZVPT" in src and "ZTPB = 256" in src and "ZVPT = 4" in src  # the 1024 columns the wide GPU case is built on
+    for user in ("zonal.hip", "burn.hip"):
+        text = open(os.path.join(PKG, "csrc", user)).read()
+        assert '#include "zone_canvas.h"' in text and not re.search(r"constexpr int \w*(TPB|VPT|CHUNK)\b", text), user  # no second geometry
     assert "zonal.hip" in open(os.path.join(PKG, "csrc", "Makefile")).read()
 
 

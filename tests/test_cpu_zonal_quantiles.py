@@ -198,7 +198,8 @@ def test_header_states_the_rule_and_the_kernels_use_integer_atomics_only():
         assert re.search(r"\bint %s\(" % n, text)
     src = open(os.path.join(PKG, "csrc", "zonal.hip")).read()
     new = src[src.index("ZQ_ROUNDS"):src.index("#define ST(s)")]
-    assert "zone_scan_chunk(m, carry, wtot[par])" in new and src.count("__shfl_up(t, o, 64)") == 1  # the one scan, shared
+    scan = "".join(open(os.path.join(PKG, "csrc", f)).read() for f in ("zonal.hip", "burn.hip", "zone_canvas.h"))
+    assert "zone_scan_chunk(m, carry, wtot[par])" in new and scan.count("__shfl_up(t, o, 64)") == 1  # the one scan, shared (zone_canvas.h)
     assert "#pragma clang fp contract(off)" in new and "atomicAdd" in new
     assert not re.search(r"atomic(Add|Max|Min|Exch|CAS)\s*\(\s*\(?\s*(float|double)", new) and "double*" not in new and "float* bins" not in new
     assert "while (" not in new  # no waiting on another workgroup, no unbounded loop

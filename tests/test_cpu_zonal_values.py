@@ -208,7 +208,8 @@ def test_header_declares_both_entry_points_and_states_the_rule():
     for n in NAMES + ("ig_zone_value_grid",):
         assert re.search(r"\bint %s\(" % n, text)
     src = open(os.path.join(PKG, "csrc", "zonal.hip")).read()
-    assert src.count("__shfl_up(t, o, 64)") == 1  # one scan, shared by the counting and the value tally
+    scan = src + open(os.path.join(PKG, "csrc", "burn.hip")).read() + open(os.path.join(PKG, "csrc", "zone_canvas.h")).read()
+    assert scan.count("__shfl_up(t, o, 64)") == 1  # one scan (zone_canvas.h), shared by the counting, the value tally and the burn
     assert "atomicAdd" not in src[src.index("zone_value_tally_kernel"):src.index("zone_value_reduce_kernel")]
 
 

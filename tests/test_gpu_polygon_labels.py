@@ -3,9 +3,10 @@ tests/polygon_labels_reference.py and numpy, every pixel of every buffer (row pa
 instageo_amd/polygon_labels.py against its host path byte for byte; the round trip with the vectoriser.
 
 Shapes are the smallest at which each launch can still go wrong: 5 x 1030 and 3 x 2051 (a workgroup scans 1024 columns in one step,
-burn.hip: the prefix carry crosses one and two chunk borders), pass rectangles at c0 = 0..3 under row pitches of 1030, 1031, 1033 and 1034
+ZCHUNK of zone_canvas.h: the prefix carry crosses one and two chunk borders, and a wave border every 256 columns inside a chunk), pass rectangles at c0 = 0..3 under row pitches of 1030, 1031, 1033 and 1034
 (every residue mod 4 of the row start and of the column offset: the packed 4-byte store of int8 pixels must stay inside words the thread
 owns), all 64 bits, bit 63 alone, bit 0 alone, three passes, an empty pass; cells of 16 x 16 on 3 x 5 cells, K = 0, 2, 127, and S = 1."""
+import json
 import os
 
 import numpy as np
@@ -14,9 +15,10 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import all_touched_reference as AR  # noqa: E402
 import polygon_labels_reference as PR  # noqa: E402
 import zonal_reference as ZR  # noqa: E402
-from instageo_amd import ops, vectorize, warp  # noqa: E402
+from instageo_amd import ops, vectorize, warp, zonal  # noqa: E402
 from instageo_amd import polygon_labels as P  # noqa: E402
 from instageo_amd import postprocess as PP  # noqa: E402
 
@@ -48,14 +50,12 @@ def wide_zones(Hp, Wp, seed, n=64):
 
 
 def resolve(zones, values, Hp, Wp, H, W, pitch, r0, c0, dtype):
-    """One pass through ig_zone_edge_rows / ig_zone_toggle on the pass canvas and ig_burn_resolve into a poisoned (H, pitch) buffer ->
-    (the whole buffer, the counter)."""
+    """One pass through ig_zone_edge_rows / ig_zone_toggle on the pass canvas (zonal.toggle_canvas; where nothing crosses, an empty
+    canvas) and ig_burn_resolve into a poisoned (H, pitch) buffer -> (the whole buffer, the counter)."""
     edges, owner = ZR.edges_of(zones)
-    e = torch.from_numpy(edges).to(DEV)
-    rows = ops.zone_edge_rows(e, Hp)
-    first = torch.cumsum(rows, 0, dtype=torch.int64).sub_(rows)
-    canvas = torch.zeros((Hp, Wp), dtype=torch.int64, device=DEV)
-    ops.zone_toggle(e, torch.from_numpy(owner.astype(np.uint8)).to(DEV), first, canvas, int(rows.sum().item()))
+    canvas = zonal.toggle_canvas(torch.from_numpy(edges).to(DEV), torch.from_numpy(owner.astype(np.uint8)).to(DEV), Hp, Wp)
+    if canvas is None:
+        canvas = torch.zeros((Hp, Wp), dtype=torch.int64, device=DEV)
     table = np.zeros(64, dtype=dtype)
     table[: len(values)] = values
     buf = torch.full((H, pitch), POISON[dtype], dtype=torch.int8 if dtype == np.int8 else torch.float32, device=DEV)
@@ -130,6 +130,86 @@ def test_every_bit_bit_63_alone_bit_0_alone_and_an_empty_canvas(dtype):
         assert n == count > 0 and set(np.unique(got).tolist()) == {POISON[dtype].item() if dtype == np.float32 else 77, vals[len(z) - 1]}
     got, n = resolve(outside, values, Hp, Wp, Hp, Wp, Wp, 0, 0, dtype)  # nothing crosses: nothing is written
     assert n == 0 and (got == POISON[dtype]).all()
+
+
+@pytest.fixture(scope="module")
+def scratch_case():
+    """The wide zones of a 5 x 2051 and of a 3 x 1030 pass, and the reference masks of the second under both rules (the centre rule of
+    polygon_labels_reference; all_touched: OR the pixels all_touched_reference finds touched, feature by feature), computed once."""
+    first, second = wide_zones(5, 2051, 2051), wide_zones(3, 1030, 1030)
+    centre = PR.masks_of([(0, z) for z in second], 3, 1030)
+    touched = np.stack([AR.touched(ZR.edges_of([z])[0], 3, 1030) for z in second])
+    return first, second, {False: centre, True: centre | touched}
+
+
+@pytest.mark.parametrize("all_touched", [False, True])
+def test_toggle_canvas_in_reused_scratch_equals_fresh_memory_and_the_reference(scratch_case, all_touched):
+    """A 5 x 2051 pass built in poisoned scratch, then a 3 x 1030 pass in the same scratch: what the first left behind (toggles across two
+    chunk borders, touch bits) must not reach the second, whose rows start at other offsets of the buffer."""
+    first, second, masks = scratch_case
+    scratch = torch.full((5 * 2051,), -1, dtype=torch.int64, device=DEV)
+    scratch2 = torch.full_like(scratch, -1)
+
+    def build(zones, Hp, Wp, *bufs):
+        edges, owner = ZR.edges_of(zones)
+        return zonal.toggle_canvas(torch.from_numpy(edges).to(DEV), torch.from_numpy(owner.astype(np.uint8)).to(DEV), Hp, Wp, all_touched, *bufs)
+
+    big = build(first, 5, 2051, scratch, scratch2)
+    assert big.data_ptr() == scratch.data_ptr() and tuple(big.shape) == (5, 2051) and bool(big.any())
+    got = build(second, 3, 1030, scratch, scratch2)
+    fresh = build(second, 3, 1030)
+    assert got.data_ptr() == scratch.data_ptr() and fresh.data_ptr() != scratch.data_ptr() and tuple(got.shape) == (3, 1030)
+    assert torch.equal(got, fresh)
+    assert bool((scratch[3 * 1030 :].view(-1) != 0).any())  # the rest of the first pass is still there: only the view was zeroed
+    m = masks[all_touched]
+    for dtype in (np.int8, np.float32):
+        values = values_of(64, dtype)
+        buf = torch.full((3, 1030), POISON[dtype], dtype=torch.int8 if dtype == np.int8 else torch.float32, device=DEV)
+        written = torch.zeros(1, dtype=torch.int64, device=DEV)
+        ops.burn_resolve(got, torch.from_numpy(np.asarray(values, dtype=dtype)).to(DEV), buf, 0, 0, written)
+        same(buf.cpu().numpy(), PR.burn(np.full((3, 1030), POISON[dtype], dtype=dtype), list(zip(values, second)), m))
+        assert int(written.item()) == int(m.any(axis=0).sum()) < 3 * 1030
+    assert int(masks[True].sum()) > int(masks[False].sum())  # the two rules differ on these zones
+
+
+# ---- the launches, as a contract ---------------------------------------------------------------------------------------------------------------
+def launch_sequences():
+    """The entry points launched, in order, by zone_counts, zone_values and burn_fixed with all_touched off and on, for 70 zones on a 5 x
+    1030 raster: a first pass of 64 wide zones and a second of five zones above the raster and one smaller than a pixel between four
+    centres, which crosses no centre line (off: the pass ends after ig_zone_edge_rows) and touches one pixel (on: it runs without
+    ig_zone_toggle) -> {"<function>/<off | on>": [names]}."""
+    H, W = 5, 1030
+    zones = wide_zones(H, W, W) + [[ZR.rect(3 + k, -9, 8 + k, -2)] for k in range(5)] + [[ZR.rect(10.625, 2.625, 10.875, 2.875)]]
+    edges, owner = ZR.edges_of(zones)
+    items = PR.items_of([(1 + k % 5, z) for k, z in enumerate(zones)])
+    cm = torch.from_numpy(ZR.class_map(7, H, W, 3)).to(DEV)
+    raster = torch.from_numpy(np.random.default_rng(7).random((H, W), dtype=np.float32)).to(DEV)
+    out, real = {}, ops._call
+    for flag in (False, True):
+        for name, run in (("zone_counts", lambda: zonal.zone_counts(cm, edges, owner, len(zones), 3, -1, all_touched=flag)),
+                          ("zone_values", lambda: zonal.zone_values(raster, edges, owner, len(zones), all_touched=flag)),
+                          ("burn_fixed", lambda: P.burn_fixed(torch.zeros((H, W), dtype=torch.int8, device=DEV), items, all_touched=flag))):
+            calls = []
+            ops._call = lambda entry, *a, **k: (calls.append(entry), real(entry, *a, **k))[1]
+            try:
+                run()
+            finally:
+                ops._call = real
+            out[f"{name}/{'on' if flag else 'off'}"] = calls
+    return out
+
+
+def test_the_launch_sequences_are_those_recorded_before_the_shared_canvas_builder():
+    """tests/golden/zone_launch_sequences.json holds what launch_sequences() returned on the commit before zonal.toggle_canvas existed (the
+    same function, run there on the device): the names and the order of the launches are part of the contract."""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "zone_launch_sequences.json")) as f:
+        want = json.load(f)
+    got = launch_sequences()
+    assert sorted(got) == sorted(want) and len(want) == 6
+    for key in sorted(want):
+        print(key, got[key])
+        assert got[key] == want[key], key
+    assert want["zone_counts/off"][-1] == "ig_zone_edge_rows" and "ig_zone_toggle" not in want["zone_counts/on"][-4:]  # the second pass
 
 
 # ---- ig_label_cells ----------------------------------------------------------------------------------------------------------------------------
