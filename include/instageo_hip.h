@@ -658,7 +658,10 @@ int ig_mosaic_paste(const void* chips, const long long* starts, const int* rects
  * of the rule (tests/warp_reference.py) - truth| on the ground.  Within 40 degrees of the central meridian, latitudes to 89.9: forward
  * <= 3.8e-9 m, inverse (E - FE within 4800 km) <= 7.5e-8 m, and <= 4.1e-7 m within 0.6 degrees of a pole, which is the rounding of that
  * evaluation (instageo_amd/crs.py stays within 2e-9 m there); web Mercator and the chains between systems <= 5.8e-8 m.  The device is
- * held to 1e-6 m on all of these (tests/test_gpu_projection_truth.py).  BEYOND 40 degrees the truncated series itself is off, forward,
+ * held to 1e-6 m on all of these (tests/test_gpu_projection_truth.py).  The PICKS of the value kernels (ig_warp, ig_chip_warp,
+ * ig_s1_chip_warp, ig_s2_chip_warp, ig_tile_render) are held to the same truth at 10 to 30 m pixels: outside 1e-6 m + 4 ulp of a pixel
+ * boundary the pixel read must equal the true pick (tests/test_cpu_warp_picks.py, tests/test_gpu_warp_picks.py, on
+ * tests/warp_pick_reference.py and tests/golden/warp_pick_truth.npz).  BEYOND 40 degrees the truncated series itself is off, forward,
  * worst per band of |longitude - lon0|:
  *     latitude    (40, 50]    (50, 60]    (60, 70]    (70, 79.9]
  *        0        1.3e-7 m    1.1e-5 m    4.8e-3 m    118 m      (4.7 m at 77.5 degrees)

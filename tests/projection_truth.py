@@ -315,5 +315,144 @@ def load(path=FIXTURE):
     return out
 
 
+# ---- truth at pixel scale: the picks of the value kernels ---------------------------------------------------------------------------------
+# The lattices above have pixels of 16 to 830 km and cross no 64 x 64 block seam: a raster under them would forgive kilometres.  The pick
+# cases have 10 to 30 m pixels (or that fraction of a degree) and a destination larger than one block; the truth is kept at a SAMPLE of
+# their pixels, as the source's own map coordinates (x', y'), so that tests/warp_pick_reference.py can lay any source grid under them.
+PICK_FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "warp_pick_truth.npz")
+PICK_POINTS = 250  # per case
+SEAM_LINES = (0, 63, 64, 127, 128)  # rows and columns on both sides of the 64 x 64 block seams, with the last one
+WM_ORIGIN = 6378137.0 * float(np.pi)  # the web Mercator square spans +-WM_ORIGIN
+
+
+def _px_around(crs, lon, lat, px, shape):
+    """The H x W grid of ``crs`` with square pixels ``px`` whose centre is the multiple of ``px`` nearest to the point (lon, lat)."""
+    H, W = shape
+    with mp.workdps(30):
+        x, y = (float(v) for v in from_lonlat(crs, mpf(lon), mpf(lat)))
+    return (round(x / px) * px - (W // 2) * px, round(y / px) * px + (H // 2) * px, px, px), (H, W)
+
+
+def _wm_tile_corner(lon, lat, z, tile, shape):
+    """The H x W grid on the pixel lattice of the XYZ tiles of zoom ``z`` (``tile`` pixels a side) from the north-west corner of the tile
+    that holds (lon, lat)."""
+    side = 2.0 * WM_ORIGIN / (1 << z)
+    with mp.workdps(30):
+        x, y = (float(v) for v in from_lonlat(WEB_MERCATOR, mpf(lon), mpf(lat)))
+    return (-WM_ORIGIN + np.floor((x + WM_ORIGIN) / side) * side, WM_ORIGIN - np.floor((WM_ORIGIN - y) / side) * side, side / tile, side / tile), shape
+
+
+def pick_lattices():
+    """name -> (dst_crs, dst_grid, (H, W), src_crs): core domain only, every point within 40 degrees of both central meridians."""
+    U36, U37, U36S, U21S, U1, U60, U32 = utm(36), utm(37), utm(36, True), utm(21, True), utm(1), utm(60), utm(32)
+    CUSTOM = (1.0, 9.5, 1.0, 1.5e6, -2e5)
+    G, WM = GEOGRAPHIC, WEB_MERCATOR
+    DEG = 2.0**-13  # 13.6 m of latitude
+    out = {}
+
+    def add(name, dst_crs, span, src_crs):
+        out[name] = (tuple(dst_crs), tuple(float(v) for v in span[0]), tuple(span[1]), tuple(src_crs))
+
+    add("utm37_to_utm36_lat40p6", U37, _px_around(U37, 36.0, 40.6, 10.0, (200, 150)), U36)
+    add("utm37_to_utm36_lat80", U37, _px_around(U37, 36.0, 80.0, 20.0, (130, 200)), U36)
+    add("utm36_north_to_south_equator", U36, ((618000.0, 1000.0, 10.0, 10.0), (200, 200)), U36S)
+    add("utm60_to_utm1_across_180", U60, _px_around(U60, 180.0, -35.0, 30.0, (129, 200)), U1)
+    add("wm_to_utm36", WM, _wm_tile_corner(34.0, 40.0, 13, 256, (192, 192)), U36)
+    add("utm36_to_wm", U36, _px_around(U36, 34.0, 40.0, 10.0, (150, 200)), WM)
+    add("geographic_to_utm36", G, ((34.5, 40.3125, DEG, DEG), (200, 200)), U36)
+    add("utm21s_to_geographic", U21S, _px_around(U21S, -56.2, -23.4, 10.0, (200, 160)), G)
+    add("custom_tm_to_utm32", CUSTOM, _px_around(CUSTOM, 10.7, 52.1, 15.0, (160, 200)), U32)
+    add("utm36_same_system", U36, ((512345.25, 4489012.5, 10.0, 10.0), (200, 200)), U36)
+    add("utm36_to_utm37_thin", U36, _px_around(U36, 36.0, 40.6, 20.0, (3, 200)), U37)
+    add("utm36_to_utm37_partly_outside", U36, _px_around(U36, 35.9, -12.3, 30.0, (150, 150)), U37)
+    return out
+
+
+def pick_sample(name, shape, n=PICK_POINTS):
+    """The sampled pixels of a pick case, (n, 2) int64 (row, col) in row-major order: every crossing of the rows and the columns 0, 63, 64,
+    127, 128 and the last that the grid has (the four corners among them), eight seeded pixels on each of those rows and columns, and a
+    seeded scatter up to ``n`` pixels in all."""
+    import zlib
+
+    H, W = shape
+    rng = np.random.default_rng(zlib.crc32(name.encode()))
+    rows = sorted({r for r in SEAM_LINES + (H - 1,) if r < H})
+    cols = sorted({c for c in SEAM_LINES + (W - 1,) if c < W})
+    pts = {(r, c) for r in rows for c in cols}
+    for r in rows:
+        pts |= {(r, int(c)) for c in rng.choice(W, min(8, W), replace=False)}
+    for c in cols:
+        pts |= {(int(r), c) for r in rng.choice(H, min(8, H), replace=False)}
+    while len(pts) < min(n, H * W):
+        pts.add((int(rng.integers(H)), int(rng.integers(W))))
+    return np.array(sorted(pts), dtype=np.int64)
+
+
+def _pick_point(args):
+    """One destination pixel centre (float64 x, y) -> the true float64 (x', y') of the source system."""
+    dst_crs, src_crs, x, y = args
+    if tuple(dst_crs) == tuple(src_crs):
+        return x, y  # the header's affine shortcut: the centre itself, no projection (the grid arithmetic is the reference module's)
+    with mp.workdps(DPS):
+        ll = to_lonlat(dst_crs, x, y)
+        xy = None if ll is None else from_lonlat(src_crs, *ll)
+        if xy is None:
+            raise ValueError(f"the centre ({x}, {y}) lies outside the domain: a pick case stays in the core")
+        if int(src_crs[0]) == 1 and not abs(wrap180(ll[0] - mpf(src_crs[1]))) < 40:
+            raise ValueError(f"the centre ({x}, {y}) lies in the outer band of the source: a pick case stays in the core")
+        return _f64(xy[0]), _f64(xy[1])
+
+
+def _exact_centres(grid, rc):
+    """The pixel centres X0 + (c + 1/2) sx, Y0 - (r + 1/2) sy of the float64 grid in rational arithmetic, rounded once."""
+    from fractions import Fraction as Fr
+
+    X0, Y0, sx, sy = (Fr(float(v)) for v in grid)
+    return [(float(X0 + (int(c) + Fr(1, 2)) * sx), float(Y0 - (int(r) + Fr(1, 2)) * sy)) for r, c in rc]
+
+
+def generate_picks(path=PICK_FIXTURE):
+    """Write the pick fixture: the table of the cases and per case ``<name>/rc`` (n, 2) int16 and ``<name>/xy`` (n, 2) float64.  Asserts,
+    case by case, that at most 1 % of the sample lies in the tie zone of the source grids that tests/warp_pick_reference.py lays under it."""
+    import multiprocessing
+
+    import warp_pick_reference as PR
+
+    table = pick_lattices()
+    data = {
+        "names": np.array(list(table)),
+        "dst_crs": np.array([t[0] for t in table.values()], dtype=np.float64),
+        "dst_grid": np.array([t[1] for t in table.values()], dtype=np.float64),
+        "shape": np.array([t[2] for t in table.values()], dtype=np.int64),
+        "src_crs": np.array([t[3] for t in table.values()], dtype=np.float64),
+    }
+    with multiprocessing.Pool(min(16, os.cpu_count() or 1)) as pool:
+        for name, (dst_crs, grid, shape, src_crs) in table.items():
+            rc = pick_sample(name, shape)
+            xy = np.array(pool.map(_pick_point, [(dst_crs, src_crs, x, y) for x, y in _exact_centres(grid, rc)], chunksize=4), dtype=np.float64)
+            assert np.isfinite(xy).all()
+            data[f"{name}/rc"], data[f"{name}/xy"] = rc.astype(np.int16), xy
+            case = dict(name=name, dst_crs=dst_crs, dst_grid=grid, shape=shape, src_crs=src_crs, rc=rc, xy=xy)
+            ties = [int(PR.picks(case, s)["tie"].sum()) for s in [PR.single(case)] + PR.pair(case) + PR.s2_classes(case)]
+            print(f"{name}: {shape[0]} x {shape[1]}, {len(rc)} points, in the tie zone of each source grid: {ties}", flush=True)
+            assert max(ties) <= 0.01 * len(rc), f"{name}: more than 1 % of the sample lies in a tie zone"
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    np.savez_compressed(path, **data)
+    return path
+
+
+def load_picks(path=PICK_FIXTURE):
+    """The pick fixture as a dict name -> dict(name, dst_crs, dst_grid, shape, src_crs, rc (n, 2) int64, xy (n, 2) float64).  numpy only."""
+    z = np.load(path)
+    out = {}
+    for i, name in enumerate(z["names"]):
+        name = str(name)
+        out[name] = dict(name=name, dst_crs=tuple(z["dst_crs"][i]), dst_grid=tuple(z["dst_grid"][i]), shape=tuple(int(v) for v in z["shape"][i]),
+                         src_crs=tuple(z["src_crs"][i]), rc=z[f"{name}/rc"].astype(np.int64), xy=z[f"{name}/xy"])
+    return out
+
+
 if __name__ == "__main__":
-    print(generate())
+    import sys
+
+    print(generate_picks() if sys.argv[1:] == ["picks"] else generate())
