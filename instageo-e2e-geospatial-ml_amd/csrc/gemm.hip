@@ -1255,6 +1255,7 @@ int launch_gemm(const AL& al, const BL& bl, const EP& ep_in, int M, int N, int K
                         ep.pairs = (int)grid.y;
                         grid.x = grid.x * grid.y, grid.y = 1;
                     }
+                    ig_note_grid((int)grid.x);
                     const int rc = ig_launch<gemm2_kernel<AL, BL, EP, A_TR, B_TR, 1, 2>>(what, grid, dim3(2 * NTHR2), 2 * G2::SMEM, st, al, bl, ep, M, N, K, tn,
                                                                                          ntiles, kchunk, zp);
                     if (rc != IG_OK) return rc;
@@ -1287,6 +1288,7 @@ int launch_gemm(const AL& al, const BL& bl, const EP& ep_in, int M, int N, int K
         constexpr int ring_ = 2 * (ta_ + tb_), stage_ = EP::kStagedAtomic ? bme_ * 512 : 0;                            \
         constexpr int lds_ = ring_ > stage_ ? ring_ : stage_;                                                          \
         ig_note_kernel("gemm_kernel<%s,%s,%s,%s,%s,%d,%d,%d,%d,%d>", AL::kName, BL::kName, EP::kName, A_TR ? "true" : "false", B_TR ? "true" : "false", NSEG_, MT_, NT_, WM_, BKT_); \
+        ig_note_grid((int)grid.x);                                                                                     \
         const int rc_ = ig_launch<gemm_kernel<AL, BL, EP, A_TR, B_TR, NSEG_, MT_, NT_, WM_, BKT_>>(what, grid, block, lds_, st, al, bl, ep, M, N, K, tn, kchunk); \
         if (rc_ != IG_OK) return rc_;                                                                                  \
     }

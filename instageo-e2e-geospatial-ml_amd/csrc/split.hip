@@ -172,6 +172,8 @@ extern "C" int ig_split_nearest(const int* a, int Na, const int* b, int Nb, unsi
         out_d2 = (u64*)buf, out_idx = (int*)(buf + cells * 8);
     }
     const dim3 grid((unsigned)((long)nblocks_a * ranges));
+    ig_note_kernel(ranges > 1 ? "split_nearest_kernel<%d>+split_merge_kernel" : "split_nearest_kernel<%d>", RA);
+    ig_note_grid((int)grid.x);
     const int rc = RA == 4 ? ig_launch<split_nearest_kernel<4>>("ig_split_nearest", grid, dim3(TPB), 0, st, a, Na, b, Nb, nblocks_a, per_range,
                                                                  out_d2, out_idx)
                            : ig_launch<split_nearest_kernel<1>>("ig_split_nearest", grid, dim3(TPB), 0, st, a, Na, b, Nb, nblocks_a, per_range,

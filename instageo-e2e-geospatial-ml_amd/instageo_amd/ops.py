@@ -197,6 +197,11 @@ def last_kernel() -> str:
     return (_lib.load().ig_last_kernel() or b"").decode()
 
 
+def last_grid() -> int:
+    """Workgroups of the launch :func:`last_kernel` names, where the entry point notes its grid (``ig_last_grid``)."""
+    return int(_lib.load().ig_last_grid())
+
+
 def deterministic() -> bool:
     return bool(_lib.load().ig_get_deterministic())
 
