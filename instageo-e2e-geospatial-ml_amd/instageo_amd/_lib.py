@@ -18,6 +18,9 @@ _REPO_ROOT = os.path.dirname(_PKG_ROOT)
 # is the in-tree library next to this file
 LIB_PATH = os.environ.get("IG_HIP_LIB") or os.path.join(_HERE, "libinstageo_hip.so")
 HEADER_PATH = os.path.join(_REPO_ROOT, "include", "instageo_hip.h")
+# companion headers of the same library: {path: the entry point that returns the stamp the library was built against}.  Their prototypes
+# are bound like the main header's; declared_symbols() stays the main header's list.
+COMPANION_HEADERS = {os.path.join(_REPO_ROOT, "include", "instageo_objects.h"): "ig_objects_header_stamp"}
 
 _SCALARS = {
     "int": ctypes.c_int,
@@ -77,11 +80,13 @@ def load():
 
     lib = ctypes.CDLL(LIB_PATH)
     protos = parse_header()
+    for path in COMPANION_HEADERS:
+        protos.update(parse_header(path))
     for name, (ret, types) in protos.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:  # pragma: no cover
-            raise HipLibraryError(f"symbol {name} declared in instageo_hip.h is missing from {LIB_PATH}") from e
+            raise HipLibraryError(f"symbol {name} declared in the headers under include/ is missing from {LIB_PATH}") from e
         fn.restype = ctypes.c_char_p if ret.startswith("const char") else ctypes.c_int
         fn.argtypes = [_ctype(t) for t in types]
     import hashlib
@@ -93,12 +98,23 @@ def load():
             f"{LIB_PATH} was built against another revision of {HEADER_PATH} (stamp {got:#x}, header {want:#x}): rebuild it "
             f"(`make -C {os.path.join(_PKG_ROOT, 'csrc')}`) -- calling it with this header's signatures would pass shifted arguments."
         )
+    for path, stamp in COMPANION_HEADERS.items():
+        want = int(hashlib.md5(open(path, "rb").read()).hexdigest()[:7], 16)
+        got = getattr(lib, stamp)()
+        if got != want:
+            raise HipLibraryError(f"{LIB_PATH} was built against another revision of {path} (stamp {got:#x}, header {want:#x}): rebuild it "
+                                  f"(`make -C {os.path.join(_PKG_ROOT, 'csrc')}`)")
     _lib, _protos = lib, protos
     return lib
 
 
 def declared_symbols() -> List[str]:
     return sorted(parse_header().keys())
+
+
+def companion_symbols() -> List[str]:
+    """The entry points the companion headers declare."""
+    return sorted(n for path in COMPANION_HEADERS for n in parse_header(path))
 
 
 def last_error() -> str:

@@ -23,7 +23,7 @@ import torch
 from . import ops
 from .metrics import metrics_from_matrix
 
-__all__ = ["check_boundary_options", "boundary_distance", "RunningBoundaryMetrics", "boundary_metrics_from_counts", "MAX_DISTANCES",
+__all__ = ["check_boundary_options", "boundary_distance", "class_maps", "RunningBoundaryMetrics", "boundary_metrics_from_counts", "MAX_DISTANCES",
            "MAX_RADIUS", "FILL"]
 
 MAX_DISTANCES = 8  # ig_boundary_update counts at most 8 distances per launch
@@ -83,6 +83,26 @@ def boundary_metrics_from_counts(band, trimap, distances: Sequence[float]) -> Li
     return out
 
 
+def class_maps(logits_or_preds: torch.Tensor, labels: torch.Tensor, num_classes: int, ignore_index: Optional[int] = None):
+    """-> (gt, pred) int8 maps of the labels' shape, on the device: gt = the label where it is valid (``ig_ce_loss``'s predicate:
+    label != ignore_index and 0 <= label < ncls), fill elsewhere; pred = ``ops.argmax_i8`` of logits (B, ncls, H, W), or the given
+    class map, with fill wherever gt is fill."""
+    lab = labels if labels.dtype in (torch.int64, torch.int32, torch.int16, torch.int8, torch.uint8) else labels.long()
+    valid = (lab >= 0) & (lab < num_classes)
+    if ignore_index is not None:
+        valid &= lab != int(ignore_index)
+    fill = torch.full((), FILL, dtype=torch.int8, device=lab.device)
+    gt = torch.where(valid, lab.to(torch.int8), fill)
+    p = logits_or_preds
+    if p.dim() == labels.dim() + 1:
+        p = ops.argmax_i8(p.contiguous())
+    elif p.dtype != torch.int8:
+        p = p.clamp(-1, 127).to(torch.int8)  # a class id beyond int8 is no class of this map: 127 >= ncls never counts
+    if p.shape != gt.shape:
+        raise ValueError(f"predictions {tuple(p.shape)} and labels {tuple(gt.shape)} differ in shape")
+    return gt.contiguous(), torch.where(valid, p, fill).contiguous()
+
+
 class RunningBoundaryMetrics:
     """Streaming Boundary IoU and trimap counts at a few distances, device resident (the pattern of :class:`metrics.RunningAUC`)."""
 
@@ -104,23 +124,8 @@ class RunningBoundaryMetrics:
         return self._band, self._trimap
 
     def class_maps(self, logits_or_preds: torch.Tensor, labels: torch.Tensor):
-        """-> (gt, pred) int8 maps of the labels' shape, on the device: gt = the label where it is valid (``ig_ce_loss``'s predicate:
-        label != ignore_index and 0 <= label < ncls), fill elsewhere; pred = ``ops.argmax_i8`` of logits (B, ncls, H, W), or the given
-        class map, with fill wherever gt is fill."""
-        lab = labels if labels.dtype in (torch.int64, torch.int32, torch.int16, torch.int8, torch.uint8) else labels.long()
-        valid = (lab >= 0) & (lab < self.num_classes)
-        if self.ignore_index is not None:
-            valid &= lab != int(self.ignore_index)
-        fill = torch.full((), FILL, dtype=torch.int8, device=lab.device)
-        gt = torch.where(valid, lab.to(torch.int8), fill)
-        p = logits_or_preds
-        if p.dim() == labels.dim() + 1:
-            p = ops.argmax_i8(p.contiguous())
-        elif p.dtype != torch.int8:
-            p = p.clamp(-1, 127).to(torch.int8)  # a class id beyond int8 is no class of this map: 127 >= ncls never counts
-        if p.shape != gt.shape:
-            raise ValueError(f"predictions {tuple(p.shape)} and labels {tuple(gt.shape)} differ in shape")
-        return gt.contiguous(), torch.where(valid, p, fill).contiguous()
+        """:func:`class_maps` with this instance's classes and ignore_index."""
+        return class_maps(logits_or_preds, labels, self.num_classes, self.ignore_index)
 
     def update(self, logits_or_preds: torch.Tensor, labels: torch.Tensor) -> None:
         """logits (B, ncls, H, W) f32 or predictions (B, H, W), labels (B, H, W), on the device; no host copy."""

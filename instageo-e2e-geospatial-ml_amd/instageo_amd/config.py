@@ -98,6 +98,12 @@ DEFAULTS: Dict[str, Any] = {'root_dir': None,
           # and test_trimap_IoU_d<d> over the pixels within d pixels of a class boundary, for each of up to 8 ascending distances in
           # [1, 32] (boundary.py)
           'boundary_metrics': False, 'boundary_distances': [1, 2, 4],
+          # object level (not in the reference): mode=eval also logs test_obj_F1_t<t> / test_obj_P_t<t> / test_obj_R_t<t> (detection of the
+          # connected regions at IoU > t; F1 with _<class>) and test_PQ_t<t> (with _<class>) / test_SQ_t<t> / test_RQ_t<t> (panoptic
+          # quality) for each of up to 10 ascending thresholds in [0.5, 0.999] of at most three decimals.  object_connectivity: 4 | 8;
+          # object_min_area: regions below it in pixels are neither objects nor matches; object_classes: the classes the means run over
+          # (None = all) (objects.py)
+          'object_metrics': False, 'object_iou_thresholds': [0.5], 'object_connectivity': 4, 'object_min_area': 1, 'object_classes': None,
           # Web Mercator map tiles (not in the reference's run.py; its backend serves them through TiTiler; maptiles.py): map_tiles writes
           # tiles_<name>/{z}/{x}/{y}.png + tilejson.json of the class map / prediction raster of mode=tile_inference, and tiles_merged/ of
           # the mosaic of mode=chip_inference (test.mosaic=true), rendered on the device.  map_tiles_minzoom / map_tiles_maxzoom: 'auto' or

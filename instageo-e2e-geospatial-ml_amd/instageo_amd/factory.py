@@ -7,8 +7,24 @@ import torch
 
 from .boundary import check_boundary_options
 from .calibration import check_calibrate_options, resolve_temperature
+from .objects import check_object_options
 from .regression import PrithviDistillationRegressionModule, PrithviRegressionModule
 from .segmentation import LOSS_CHOICES, PrithviDistillationSegmentationModule, PrithviSegmentationModule
+
+
+def object_options(cfg: Dict[str, Any]) -> Dict[str, Any]:
+    """The ``test.object_*`` keys (objects.py) as keyword arguments of ``set_object_metrics``, checked: a bad value raises ValueError.
+    With ``test.object_metrics`` off the thresholds are None and nothing is built."""
+    test_cfg = cfg.get("test", {})
+    if not test_cfg.get("object_metrics", False):
+        return dict(thresholds=None)
+    opts = dict(thresholds=test_cfg.get("object_iou_thresholds", [0.5]), connectivity=test_cfg.get("object_connectivity", 4),
+                min_area=test_cfg.get("object_min_area", 1), classes=test_cfg.get("object_classes"))
+    if opts["classes"] == "None":
+        opts["classes"] = None
+    opts["thresholds"] = check_object_options(opts["thresholds"], cfg["model"]["num_classes"], opts["connectivity"], opts["min_area"],
+                                              opts["classes"], bool(cfg.get("is_reg_task", False)))
+    return opts
 
 
 def create_model(cfg: Dict[str, Any], precision: str = "bf16", device=None) -> PrithviSegmentationModule:
@@ -43,6 +59,7 @@ def create_model(cfg: Dict[str, Any], precision: str = "bf16", device=None) -> P
     boundary = None
     if test_cfg.get("boundary_metrics", False):
         boundary = check_boundary_options(test_cfg.get("boundary_distances", [1, 2, 4]), m["num_classes"], bool(cfg.get("is_reg_task", False)))
+    objects = object_options(cfg)
     loss = t.get("loss", "ce")
     if loss not in LOSS_CHOICES:
         raise ValueError(f"train.loss={loss!r}: choose one of {', '.join(LOSS_CHOICES)}")
@@ -70,6 +87,7 @@ def create_model(cfg: Dict[str, Any], precision: str = "bf16", device=None) -> P
     if not cfg.get("is_reg_task", False):
         model.set_calibration(temperature, bool(test_cfg.get("calibration_metrics", False)), int(cal.get("nbins", 15)))
         model.set_boundary_metrics(boundary)
+        model.set_object_metrics(**objects)
     if not train_mode:
         ckpt = cfg.get("checkpoint_path")
         if not ckpt or str(ckpt) == "None":

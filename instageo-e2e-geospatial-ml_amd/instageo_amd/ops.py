@@ -937,6 +937,61 @@ def boundary_update(gt, pred, gt_d2, pred_d2, thresholds, band, trimap, ncls: in
           _p(band), _p(trimap), n, H * W, int(ncls), int(fill), _stream())
 
 
+OBJECT_EMPTY = -1  # the empty key of ig_object_pairs' table (all ones) as int64
+OBJECT_MAX_PIXELS = 2**31 - 1  # n * H * W per call of the object entry points
+
+
+def _object_table(keys, counts, capacity: int) -> None:
+    assert keys.dtype == torch.int64 and counts.dtype == torch.int32 and keys.dim() == 1 and counts.dim() == 1
+    assert keys.numel() == capacity and counts.numel() == capacity and keys.is_contiguous() and counts.is_contiguous()
+
+
+def object_pairs(gt_labels, pred_labels, keys, counts, status) -> None:
+    """The sparse overlap table of two label maps of :func:`ccl_label` (int32, the same shape (n, H, W) | (H, W)): ``keys`` int64 and
+    ``counts`` int32 of one length, a power of two in [1024, 2^30], are cleared and then hold one entry
+    ``((image * HW + gt label) << 32) | pred label`` -> shared pixels per pair of overlapping regions, ``OBJECT_EMPTY`` elsewhere, at
+    positions that mean nothing.  ``status`` (1,) int32 on the device: bit 0 is set when the table was too small (then it is not valid)
+    (include/instageo_objects.h)."""
+    assert gt_labels.dtype == torch.int32 and pred_labels.dtype == torch.int32 and gt_labels.dim() in (2, 3)
+    assert pred_labels.shape == gt_labels.shape and status.dtype == torch.int32 and status.numel() == 1
+    capacity = keys.numel()
+    _object_table(keys, counts, capacity)
+    n = gt_labels.shape[0] if gt_labels.dim() == 3 else 1
+    _call("ig_object_pairs", float(gt_labels.numel()) * 8 + capacity * 12.0, _p(gt_labels.contiguous()), _p(pred_labels.contiguous()), _p(keys),
+          _p(counts), capacity, _p(status), n, gt_labels.shape[-2] * gt_labels.shape[-1], _stream())
+
+
+def object_match(keys, counts, gt, pred, gt_area, pred_area, ratios, tp, iou_q, ncls: int, min_area: int = 1) -> None:
+    """Matches among the entries of an :func:`object_pairs` table: a pair of regions of one class (both of at least ``min_area`` pixels)
+    is a match at ``ratios[k] = (num, den)`` iff its IoU is strictly above num / den (1 to 10 host pairs in [1/2, 1)); ``tp`` int64
+    [K, ncls] += 1 and ``iou_q`` int64 [K, ncls] += the IoU in units of 2^-24 per match.  ``gt`` / ``pred`` int8 class maps with their
+    :func:`region_area` rasters.  Integer sums: order-independent."""
+    import ctypes
+
+    rs = [(int(a), int(b)) for a, b in ratios]
+    K = len(rs)
+    n, H, W = _class_maps(gt)
+    assert pred.shape == gt.shape and pred.dtype == torch.int8 and gt_area.shape == gt.shape and pred_area.shape == gt.shape
+    assert gt_area.dtype == torch.int32 and pred_area.dtype == torch.int32
+    assert tp.dtype == torch.int64 and tuple(tp.shape) == (K, ncls) and iou_q.dtype == torch.int64 and tuple(iou_q.shape) == (K, ncls)
+    capacity = keys.numel()
+    _object_table(keys, counts, capacity)
+    arr = ctypes.c_int * max(K, 1)
+    _call("ig_object_match", capacity * 12.0, _p(keys), _p(counts), capacity, _p(gt.contiguous()), _p(pred.contiguous()),
+          _p(gt_area.contiguous()), _p(pred_area.contiguous()), arr(*[a for a, _ in rs]), arr(*[b for _, b in rs]), K, _p(tp), _p(iou_q), n,
+          H * W, int(ncls), int(min_area), _stream())
+
+
+def object_count(classmap, labels, area, n_regions, ncls: int, min_area: int = 1) -> None:
+    """``n_regions`` int64 [ncls] += the regions of every class in (n, H, W) | (H, W) int8 class maps that have at least ``min_area``
+    pixels, given the maps' :func:`ccl_label` labels and :func:`region_area` areas."""
+    n, H, W = _class_maps(classmap)
+    assert labels.shape == classmap.shape and area.shape == classmap.shape and labels.dtype == torch.int32 and area.dtype == torch.int32
+    assert n_regions.dtype == torch.int64 and tuple(n_regions.shape) == (ncls,)
+    _call("ig_object_count", float(classmap.numel()) * 9, _p(classmap.contiguous()), _p(labels.contiguous()), _p(area.contiguous()),
+          _p(n_regions), n, H * W, int(ncls), int(min_area), _stream())
+
+
 MAX_EDGES = 2**31 - 1  # compact edge ids are int32
 
 

@@ -81,6 +81,10 @@ class PrithviRegressionModule(PrithviSegmentationModule):
         if distances is not None:
             raise ValueError("test.boundary_metrics needs class maps: a regression module has none")
 
+    def set_object_metrics(self, thresholds=None, **_options) -> None:
+        if thresholds is not None:
+            raise ValueError("test.object_metrics needs class maps: a regression module has none")
+
     def _fused_loss(self, logits, labels, stats, dlogits, step_type: str) -> None:
         """outputs.squeeze(1)[mask] vs labels[mask] (log1p-scaled when use_log_scale): MSE mean, metrics on the de-scaled
         values (regression.py:153-174) -- one kernel; ``stats`` = (sum of squared errors, #valid)."""

@@ -50,7 +50,7 @@ from . import prep
 from .config import check_required_flags, load_config
 from .dataloader import (ArrayChipDataset, InstaGeoDataset, SyntheticChipDataset, eval_collate_fn, infer_collate_fn, normalize_batch,
                          process_and_augment, process_and_augment_batch, process_test)
-from .factory import create_model
+from .factory import create_model, object_options
 from .infer_utils import chip_inference
 from .pipeline_utils import compute_stats
 
@@ -166,6 +166,9 @@ def _reduce_metrics(metrics, dev, model=None, step_type: Optional[str] = None) -
             D.reduce_confusion(model.test_reliability.device_hist(dev))
         if getattr(model, "test_boundary", None) is not None:  # test.boundary_metrics
             for counts in model.test_boundary.device_counts(dev):
+                D.reduce_confusion(counts)
+        if getattr(model, "test_objects", None) is not None:  # test.object_metrics: tp, iou_q, n_gt, n_pred
+            for counts in model.test_objects.device_counts(dev):
                 D.reduce_confusion(counts)
 
 
@@ -496,6 +499,7 @@ def main(argv: Optional[List[str]] = None) -> int:
     mosaic = mosaic_options(cfg)  # likewise a bad mosaic key, or test.mosaic outside mode=chip_inference
     reproject = warp_options(cfg)  # likewise the keys of the reprojected mosaic
     tiles = map_tiles_options(cfg)  # likewise the keys of the map tiles
+    object_options(cfg)  # likewise the keys of the object metrics (create_model reads them again)
     if cfg["mode"] == "map_tiles":  # no model: an existing GeoTIFF -> tiles_<name>/{z}/{x}/{y}.png + tilejson.json (maptiles.py)
         inp = str(cfg["test"]["input"])
         root = cfg.get("root_dir")

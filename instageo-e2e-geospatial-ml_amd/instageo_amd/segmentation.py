@@ -23,6 +23,7 @@ from .boundary import RunningBoundaryMetrics
 from .calibration import RunningNLL, RunningReliability, check_temperature
 from .metrics import RunningAUC, RunningConfusionMatrix
 from .model import PrithviSeg
+from .objects import RunningObjectMetrics, check_object_options
 
 try:  # the module must still work as a LightningModule when Lightning is installed
     import pytorch_lightning as pl  # type: ignore
@@ -374,6 +375,8 @@ class PrithviSegmentationModule(_Base):
         self.test_nll: Optional[RunningNLL] = None  # test.calibration_metrics: test_nll / test_ece / test_mce at that temperature
         self.test_reliability: Optional[RunningReliability] = None
         self.test_boundary: Optional[RunningBoundaryMetrics] = None  # test.boundary_metrics: test_bIoU_d* / test_trimap_* (boundary.py)
+        self.test_objects: Optional[RunningObjectMetrics] = None  # test.object_metrics: test_obj_* / test_PQ_* (objects.py)
+        self.object_classes: Optional[Sequence[int]] = None  # test.object_classes: the classes their means run over
         self.logged: Dict[str, Any] = {}
         self._loss_sums: Dict[str, torch.Tensor] = {}
         self._optimizer: Optional[FusedAdamW] = None
@@ -423,6 +426,16 @@ class PrithviSegmentationModule(_Base):
         given distances in pixels; None switches them off."""
         self.test_boundary = None if distances is None else RunningBoundaryMetrics(self._num_classes, distances, self.ignore_index)
 
+    def set_object_metrics(self, thresholds: Optional[Sequence[float]] = None, connectivity: int = 4, min_area: int = 1,
+                           classes: Optional[Sequence[int]] = None) -> None:
+        """``test.object_metrics`` / ``test.object_*`` (objects.py): object F1 and panoptic quality of the test epoch's connected regions
+        at the given IoU thresholds; None switches them off."""
+        if thresholds is not None:
+            check_object_options(list(thresholds), self._num_classes, connectivity, min_area, classes)
+        self.object_classes = None if thresholds is None or classes is None else list(classes)
+        self.test_objects = None if thresholds is None else RunningObjectMetrics(self._num_classes, thresholds, self.ignore_index,
+                                                                                 connectivity, min_area)
+
     def scale_logits_(self, logits: torch.Tensor) -> torch.Tensor:
         """logits / temperature IN PLACE; at temperature 1 nothing runs, so every uncalibrated output keeps its bits."""
         if self.temperature != 1.0:
@@ -431,10 +444,12 @@ class PrithviSegmentationModule(_Base):
 
     def _test_probability_metrics(self, logits: torch.Tensor, labels: torch.Tensor) -> None:
         """The test epoch's consumers of the logits beside the loss and the confusion matrix, which have seen the raw logits: with
-        ``test.boundary_metrics`` the boundary counts of the raw logits' argmax, then the softmax consumers -- ROC-AUC histograms and, with
+        ``test.boundary_metrics`` / ``test.object_metrics`` the boundary / object counts of the raw logits' argmax, then the softmax consumers -- ROC-AUC histograms and, with
         ``test.calibration_metrics``, the cross-entropy sum and the reliability histograms.  Scales ``logits``."""
         if self.test_boundary is not None:
             self.test_boundary.update(logits, labels)
+        if self.test_objects is not None:
+            self.test_objects.update(logits, labels)
         logits = self.scale_logits_(logits)
         self.test_auc.update_from_logits(logits, labels)
         if self.test_nll is not None:
@@ -528,6 +543,14 @@ class PrithviSegmentationModule(_Base):
                         self.log(f"test_bIoU_d{d}_{idx}", value)
                     self.log(f"test_trimap_Acc_d{d}", r["trimap_acc"])
                     self.log(f"test_trimap_IoU_d{d}", r["trimap_iou"])
+            if self.test_objects is not None:
+                for r in self.test_objects.compute(self.object_classes):
+                    t = "%g" % r["threshold"]
+                    for key, name in (("obj_F1", "f1"), ("obj_P", "precision"), ("obj_R", "recall"), ("PQ", "pq"), ("SQ", "sq"), ("RQ", "rq")):
+                        self.log(f"test_{key}_t{t}", r[name])
+                    for idx, (f1, pq) in enumerate(zip(r["f1_per_class"], r["pq_per_class"])):
+                        self.log(f"test_obj_F1_t{t}_{idx}", f1)
+                        self.log(f"test_PQ_t{t}_{idx}", pq)
         for idx, value in enumerate(m["f1_per_class"]):
             self.log(f"{step_type}_F1_{idx}", value)
         metrics.reset()
@@ -538,6 +561,8 @@ class PrithviSegmentationModule(_Base):
                 self.test_reliability.reset()
             if self.test_boundary is not None:
                 self.test_boundary.reset()
+            if self.test_objects is not None:
+                self.test_objects.reset()
 
     def on_train_epoch_end(self) -> None:
         self._shared_epoch_end("train")

@@ -32,12 +32,12 @@ NAMESPACE = "instageo_mi355x"
 _SCALAR_SCHEMA = {"int": "int", "long": "int", "unsigned": "int", "float": "float", "double": "float"}
 _SKIP = {"ig_last_error", "ig_last_kernel", "ig_note_reset", "ig_last_grid", "ig_version", "ig_header_stamp", "ig_device_info",
          "ig_set_reserved_cus", "ig_get_reserved_cus", "ig_set_deterministic", "ig_get_deterministic", "ig_det_fold", "ig_det_fold_ranges",
-         "ig_linear_wgrad_group", "ig_conv3x3_fwd_stats", "ig_conv3x3_cls_fwd", "ig_d4_apply", "ig_calib_nll_grid", "ig_boundary_update", "ig_zone_quantile_pick"}  # host-side queries: no tensors; the grouped launch takes
+         "ig_linear_wgrad_group", "ig_conv3x3_fwd_stats", "ig_conv3x3_cls_fwd", "ig_d4_apply", "ig_calib_nll_grid", "ig_boundary_update", "ig_zone_quantile_pick", "ig_object_match"}  # host-side queries: no tensors; the grouped launch takes
 # HOST arrays of device pointers; ig_conv3x3_fwd_stats / ig_conv3x3_cls_fwd report through a HOST int (ig_conv3x3_fwd + ig_bn_relu_fwd /
 # ig_classifier_fwd are the op-level equivalents); ig_d4_apply takes its transform codes as a HOST int array (ops.d4_apply);
 # ig_calib_nll_grid takes its inverse temperatures as a HOST float array (ops.calib_nll_grid); ig_boundary_update takes its squared
 # distances as a HOST int array (ops.boundary_update); ig_zone_quantile_pick takes its fractions as a HOST double array
-# (ops.zone_value_quantiles)
+# (ops.zone_value_quantiles); ig_object_match takes its IoU thresholds as two HOST int arrays (ops.object_match)
 
 
 def parse_prototypes(path: str = _lib.HEADER_PATH) -> Dict[str, List[Tuple[str, str]]]:
@@ -76,6 +76,7 @@ def schema_of(name: str, params: List[Tuple[str, str]]) -> Tuple[str, List[Tuple
 
 _LIBRARY: Optional[torch.library.Library] = None
 RAW_OPS: Dict[str, str] = {}  # op name -> schema
+COMPANION_OPS: Dict[str, str] = {}  # the same for the entry points of _lib.COMPANION_HEADERS
 
 
 def _make_impl(entry: str, kinds):
@@ -103,15 +104,16 @@ def register() -> Dict[str, str]:
     if _LIBRARY is not None:
         return RAW_OPS
     lib = torch.library.Library(NAMESPACE, "DEF")
-    for entry, params in parse_prototypes().items():
-        if entry in _SKIP or not any("*" in t for t, n in params if n != "stream"):
-            continue
-        schema, kinds = schema_of(entry, params)
-        op = entry[3:]
-        lib.define(op + schema)
-        lib.impl(op, _make_impl(entry, kinds), "CUDA")
-        torch.library.register_fake(f"{NAMESPACE}::{op}", lambda *a, **k: None, lib=lib)
-        RAW_OPS[op] = schema
+    for path, table in [(_lib.HEADER_PATH, RAW_OPS)] + [(p, COMPANION_OPS) for p in _lib.COMPANION_HEADERS]:
+        for entry, params in parse_prototypes(path).items():
+            if entry in _SKIP or not any("*" in t for t, n in params if n != "stream"):
+                continue
+            schema, kinds = schema_of(entry, params)
+            op = entry[3:]
+            lib.define(op + schema)
+            lib.impl(op, _make_impl(entry, kinds), "CUDA")
+            torch.library.register_fake(f"{NAMESPACE}::{op}", lambda *a, **k: None, lib=lib)
+            table[op] = schema
     _register_functional(lib)
     _register_network(lib)
     _LIBRARY = lib
