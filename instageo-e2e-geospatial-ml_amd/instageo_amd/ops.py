@@ -8,6 +8,7 @@ from __future__ import annotations
 
 from typing import Optional, Tuple
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1330,6 +1331,63 @@ def cog_tiles(raster, tile: int, pad: int = 0, predictor: int = 1):
     return out
 
 
+# ---- the marshalling layer of the raster wrappers below (mosaic_paste .. label_limit) -------------------------------------------------------
+def _upload(dev, *arrays):
+    """Host arrays of ONE dtype -> one tensor on ``dev`` per array, of the array's shape: views of a single transfer, in the order given, so
+    no caller computes an offset and every view starts on a multiple of its element size.  An empty array still gets a valid pointer (one
+    zero of its own): a kernel that is handed a list of length 0 never sees null.  The caller's names keep the views alive until the
+    launch is queued; the copy is stream-ordered."""
+    arrays = [a if a.size else np.zeros(1, dtype=a.dtype) for a in arrays]
+    assert all(a.dtype == arrays[0].dtype for a in arrays), "one upload holds one dtype"
+    buf = torch.from_numpy(arrays[0] if len(arrays) == 1 else np.concatenate(arrays, axis=None)).to(dev)
+    assert buf.data_ptr() % buf.element_size() == 0, "the upload starts off its element size"  # every view a whole number of elements further
+    if len(arrays) == 1:
+        return [buf]
+    return [v if a.ndim == 1 else v.view(a.shape) for v, a in zip(buf.split([a.size for a in arrays]), arrays)]
+
+
+def _labels_on(labels, dev):
+    """The labels of a warped cut (None, a tensor or a host array) -> (the labels on ``dev`` or None, their element size or 1)."""
+    if labels is None:
+        return None, 1
+    if not torch.is_tensor(labels):
+        labels = torch.from_numpy(np.ascontiguousarray(labels))
+    return labels.to(dev), labels.element_size()
+
+
+def _label_tail(labels, es: int, valid_bit: int, K: int, outs):
+    """The arguments the three label-taking warps end on; ``outs`` as :func:`_chip_outputs` returns them."""
+    return (_p(labels), es, int(valid_bit), int(K), *(_p(t) for t in outs), _stream())
+
+
+# an optional (lo, hi) pair and an optional scalar as the kernels take them: a flag, then the values as ``cast`` makes them (0 without)
+def _opt_pair(v, cast):
+    return (1, cast(v[0]), cast(v[1])) if v is not None else (0, cast(0), cast(0))
+
+
+def _opt_value(v, cast=float):
+    return (1, cast(v)) if v is not None else (0, cast(0))
+
+
+def _plane_outputs(planes, sizes, out, columns: int):
+    """The outputs of the speckle family over the packed ``planes`` of ``sizes`` (N, 2) -> (out, counts (N, columns) int32 zeros, the
+    pixels of all planes).  A new ``out`` is zeroed only where the planes leave elements of the buffer out: theirs are all written."""
+    total, dev = int(planes.shape[0]), planes.device
+    pixels = int((sizes[:, 0].astype(np.int64) * sizes[:, 1]).sum())
+    if out is None:
+        out = (torch.empty if pixels == total else torch.zeros)(total, dtype=torch.float32, device=dev)
+    assert out.dtype == torch.float32 and out.shape == planes.shape and out.device == dev, "out is a float32 tensor of the size of planes"
+    return out, torch.zeros((sizes.shape[0], columns), dtype=torch.int32, device=dev), pixels
+
+
+def _check_bins(bin_ptr, bin_idx, blocks: int, n: int, what: str) -> None:
+    """ValueError unless ``bin_ptr`` / ``bin_idx`` are the CSR lists of ``blocks`` canvas blocks over ``n`` chips or sources (``what``)."""
+    if bin_ptr.shape[0] != blocks + 1 or bin_ptr[0] != 0 or (np.diff(bin_ptr) < 0).any() or bin_ptr[-1] != bin_idx.shape[0]:
+        raise ValueError(f"bin_ptr must hold {blocks} + 1 ascending offsets into bin_idx, from 0 to its length")
+    if bin_idx.size and (bin_idx.min() < 0 or bin_idx.max() >= n):
+        raise ValueError(f"bin_idx holds a {what}")
+
+
 MOSAIC_RULES = {"last": 0, "first": 1, "mode": 2, "mean": 3}  # include/instageo_hip.h
 MOSAIC_BLOCK = 64  # side of the canvas block one workgroup owns, and of a bin of the chip lists
 MOSAIC_LIMIT = 1 << 30  # |row0|, |col0|, h, w of a chip rectangle
@@ -1342,8 +1400,6 @@ def mosaic_paste(chips, starts, rects, bin_ptr, bin_idx, shape: Tuple[int, int],
     64 x 64 canvas blocks (:func:`instageo_amd.mosaic.bins`) as host arrays: they are checked here, so that no chip read can leave
     ``chips``, and uploaded.  -> the (H, W) canvas of ``chips``' dtype, or (canvas, cover (H, W) uint8) with ``cover``.  ``out`` /
     ``cover_out``: write into these contiguous (H, W) tensors instead of new ones (every pixel is written)."""
-    import numpy as np
-
     assert chips.dim() == 1 and chips.dtype in (torch.int8, torch.float32), "chips is the packed 1-D int8 or float32 buffer"
     es = chips.element_size()
     code = MOSAIC_RULES.get(rule)
@@ -1364,21 +1420,18 @@ def mosaic_paste(chips, starts, rects, bin_ptr, bin_idx, shape: Tuple[int, int],
             raise ValueError("a chip rectangle needs h, w >= 1 and |row0|, |col0|, h, w <= 2^30")
         if (starts < 0).any() or (starts + h * w > chips.numel()).any():
             raise ValueError(f"a chip's pixels lie outside the packed buffer of {chips.numel()} elements")
-        if bin_ptr.shape[0] != blocks + 1 or bin_ptr[0] != 0 or (np.diff(bin_ptr) < 0).any() or bin_ptr[-1] != bin_idx.shape[0]:
-            raise ValueError(f"bin_ptr must hold {blocks} + 1 ascending offsets into bin_idx, from 0 to its length")
-        if bin_idx.size and (bin_idx.min() < 0 or bin_idx.max() >= n):
-            raise ValueError("bin_idx holds a chip index outside the rectangles")
+        _check_bins(bin_ptr, bin_idx, blocks, n, "chip index outside the rectangles")
     dev = chips.device
     dst = out if out is not None else torch.empty((H, W), dtype=chips.dtype, device=dev)
     cover = cover or cover_out is not None
     cov = cover_out if cover_out is not None else torch.empty((H, W), dtype=torch.uint8, device=dev) if cover else None
     assert dst.dtype == chips.dtype and tuple(dst.shape) == (H, W) and (cov is None or (cov.dtype == torch.uint8 and tuple(cov.shape) == (H, W)))
     if H * W:
-        up = lambda a: torch.from_numpy(a).to(dev) if n else None  # noqa: E731
-        meta = [up(starts), up(rects), up(bin_ptr), up(bin_idx)]  # alive until the launch is queued; the copies are stream-ordered
+        # without chips the kernel takes null for them and their lists
+        st, rc, bp, bi = (*_upload(dev, starts), *_upload(dev, rects, bin_ptr, bin_idx)) if n else (None,) * 4
         # HBM bytes: the chips read once (an upper bound where they overhang or a rule stops early) + the canvas (+ cover) written
-        _call("ig_mosaic_paste", float(es) * (chips.numel() + H * W) + (H * W if cover else 0), _p(chips) if n else None, _p(meta[0]),
-              _p(meta[1]), n, _p(meta[2]), _p(meta[3]), H, W, es, code, int(fill), _p(dst), _p(cov), _stream())
+        _call("ig_mosaic_paste", float(es) * (chips.numel() + H * W) + (H * W if cover else 0), _p(chips) if n else None, _p(st), _p(rc), n,
+              _p(bp), _p(bi), H, W, es, code, int(fill), _p(dst), _p(cov), _stream())
     return (dst, cov) if cover else dst
 
 
@@ -1388,8 +1441,6 @@ WARP_MAX_SOURCES = 8
 
 
 def _warp_doubles(values, n: int, what: str):
-    import numpy as np
-
     a = np.ascontiguousarray(values, dtype=np.float64).reshape(-1)
     if a.shape[0] != n:
         raise ValueError(f"{what} holds {n} doubles (got {a.shape[0]})")
@@ -1397,8 +1448,6 @@ def _warp_doubles(values, n: int, what: str):
 
 
 def _warp_grid(grid, what: str):
-    import numpy as np
-
     g = _warp_doubles(grid, 4, what)
     if not (np.isfinite(g).all() and g[2] > 0 and g[3] > 0):
         raise ValueError(f"{what} = (X0, Y0, sx, sy) needs finite values and positive pixel sizes (got {tuple(g)})")
@@ -1409,17 +1458,15 @@ def warp_coords(dst_crs, dst_grid, shape: Tuple[int, int], src_crs, src_grid, de
     """``ig_warp_coords`` (include/instageo_hip.h): the source pixel coordinates of every pixel centre of the ``shape`` = (H, W)
     destination grid -> a (2, H, W) float64 tensor (u, v), NaN outside the domain.  ``dst_crs`` / ``src_crs``: five doubles (kind, lon0,
     k0, FE, FN); ``dst_grid`` / ``src_grid``: (X0, Y0, sx, sy); host values, uploaded here."""
-    import numpy as np
-
     H, W = int(shape[0]), int(shape[1])
     if H < 0 or W < 0 or H * W > 2**31 - 1 or -(-H // 4) > 65535:
         raise ValueError(f"a destination of {H} x {W} pixels is beyond the kernel's limits (H * W <= 2^31 - 1, H <= 262140)")
-    meta = np.concatenate([_warp_doubles(dst_crs, 5, "dst_crs"), _warp_grid(dst_grid, "dst_grid"), _warp_doubles(src_crs, 5, "src_crs"),
-                           _warp_grid(src_grid, "src_grid")])
+    meta = [_warp_doubles(dst_crs, 5, "dst_crs"), _warp_grid(dst_grid, "dst_grid"), _warp_doubles(src_crs, 5, "src_crs"),
+            _warp_grid(src_grid, "src_grid")]
     uv = torch.empty((2, H, W), dtype=torch.float64, device=device)
     if H * W:
-        m = torch.from_numpy(meta).to(uv.device)  # alive until the launch is queued; the copy is stream-ordered
-        _call("ig_warp_coords", 16.0 * H * W, _p(m[0:5]), _p(m[5:9]), H, W, _p(m[9:14]), _p(m[14:18]), _p(uv), _stream())
+        dc, dg, sc, sg = _upload(uv.device, *meta)
+        _call("ig_warp_coords", 16.0 * H * W, _p(dc), _p(dg), H, W, _p(sc), _p(sg), _p(uv), _stream())
     return uv
 
 
@@ -1431,8 +1478,6 @@ def warp(src, starts, src_crs, src_grid, src_size, bin_ptr, bin_idx, dst_crs, ds
     ``dst_grid`` (4,) as host arrays: they are checked here, so that no source read can leave ``src``, and uploaded.  -> the (H, W)
     raster of ``src``'s dtype, or (raster, src_id (H, W) uint8) with ``src_id``.  ``out`` / ``src_id_out``: write into these contiguous
     (H, W) tensors instead of new ones (every pixel is written)."""
-    import numpy as np
-
     assert src.dim() == 1 and src.dtype in (torch.int8, torch.float32), "src is the packed 1-D int8 or float32 buffer"
     es = src.element_size()
     mode, code = WARP_RESAMPLING.get(resampling), WARP_RULES.get(rule)
@@ -1466,33 +1511,27 @@ def warp(src, starts, src_crs, src_grid, src_size, bin_ptr, bin_idx, dst_crs, ds
             raise ValueError("a source needs 1 <= h, w <= 2^30")
         if (starts < 0).any() or (starts + h * w > src.numel()).any():
             raise ValueError(f"a source's pixels lie outside the packed buffer of {src.numel()} elements")
-        if bin_ptr.shape[0] != blocks + 1 or bin_ptr[0] != 0 or (np.diff(bin_ptr) < 0).any() or bin_ptr[-1] != bin_idx.shape[0]:
-            raise ValueError(f"bin_ptr must hold {blocks} + 1 ascending offsets into bin_idx, from 0 to its length")
-        if bin_idx.size and (bin_idx.min() < 0 or bin_idx.max() >= n):
-            raise ValueError("bin_idx holds a source index outside the sources")
+        _check_bins(bin_ptr, bin_idx, blocks, n, "source index outside the sources")
     dev = src.device
     dst = out if out is not None else torch.empty((H, W), dtype=src.dtype, device=dev)
     src_id = src_id or src_id_out is not None
     sid = src_id_out if src_id_out is not None else torch.empty((H, W), dtype=torch.uint8, device=dev) if src_id else None
     assert dst.dtype == src.dtype and tuple(dst.shape) == (H, W) and (sid is None or (sid.dtype == torch.uint8 and tuple(sid.shape) == (H, W)))
     if H * W:
-        # one upload for the float64 descriptions (8-byte aligned slices), one per integer array
-        dbl = torch.from_numpy(np.concatenate([dst_crs, dst_grid, src_crs, src_grid])).to(dev)
-        up = lambda a: torch.from_numpy(a).to(dev) if n else None  # noqa: E731
-        # alive until the launch is queued; an empty list still needs a pointer
-        meta = [up(starts), up(src_size.reshape(-1)), up(bin_ptr), up(bin_idx if bin_idx.size else np.zeros(1, dtype=np.int32))]
+        dc, dg, sc, sg = _upload(dev, dst_crs, dst_grid, src_crs, src_grid)
+        # without sources the kernel takes null for them, their descriptions and their lists
+        st, sz, bp, bi = (*_upload(dev, starts), *_upload(dev, src_size.reshape(-1), bin_ptr, bin_idx)) if n else (None,) * 4
         # HBM bytes: the destination (+ src_id) written, and as many source pixels gathered
-        _call("ig_warp", 2.0 * es * H * W + (H * W if src_id else 0), _p(src) if n else None, _p(meta[0]), _p(dbl[9 : 9 + 5 * n]) if n else None,
-              _p(dbl[9 + 5 * n :]) if n else None, _p(meta[1]), n, _p(meta[2]), _p(meta[3]), _p(dbl[0:5]), _p(dbl[5:9]), H, W, es, mode, code,
-              int(fill), _p(dst), _p(sid), _stream())
+        _call("ig_warp", 2.0 * es * H * W + (H * W if src_id else 0), _p(src) if n else None, _p(st), _p(sc) if n else None,
+              _p(sg) if n else None, _p(sz), n, _p(bp), _p(bi), _p(dc), _p(dg), H, W, es, mode, code, int(fill), _p(dst), _p(sid), _stream())
     return (dst, sid) if src_id else dst
 
 
 def _chip_outputs(out, dev, shape, dtype, labels=None, K: int = 0):
     """The output tensors of a chip launch, checked.  ``out``: None, or a dict with any of ``chips``, ``validity`` and (with ``labels``, on
     the device) ``maps``: contiguous tensors to write into instead of new ones.  -> (chips ``shape`` = (n, T * C, S, S) of ``dtype``,
-    validity (n, S, S) uint8, valid_values (n,) int32 zeros, maps like ``labels``, valid_labels (n,) int32 zeros, hist (n, K) int32 zeros):
-    the last three None without labels, hist None with K = 0."""
+    valid_values (n,) int32 zeros, validity (n, S, S) uint8, maps like ``labels``, valid_labels (n,) int32 zeros, hist (n, K) int32 zeros),
+    the order the wrappers return them in and the kernels take them in: the last three None without labels, hist None with K = 0."""
     n, S = shape[0], shape[-1]
     out = dict(out or {})
     chips = out.pop("chips", None)
@@ -1509,7 +1548,7 @@ def _chip_outputs(out, dev, shape, dtype, labels=None, K: int = 0):
         assert maps.dtype == labels.dtype and tuple(maps.shape) == (n, S, S)
         valid_labels = torch.zeros((n,), dtype=torch.int32, device=dev)
         hist = torch.zeros((n, K), dtype=torch.int32, device=dev) if K else None
-    return chips, plane, valid, maps, valid_labels, hist
+    return chips, valid, plane, maps, valid_labels, hist
 
 
 def chip_cut(tile, fmask, origins, S: int, T: int, mask_bits: int = 0, strategy: str = "each", no_data_value: int = 0, clip=None):
@@ -1523,14 +1562,13 @@ def chip_cut(tile, fmask, origins, S: int, T: int, mask_bits: int = 0, strategy:
     o = C.check_cut(tuple(tile.shape), None if fmask is None else tuple(fmask.shape), origins, S, T, mask_bits, strategy, no_data_value, clip)
     n, (TC, H, W) = o.shape[0], tile.shape
     dev = tile.device
-    chips, plane, valid = _chip_outputs(None, dev, (n, TC, S, S), torch.int16)[:3]
+    chips, valid, plane = _chip_outputs(None, dev, (n, TC, S, S), torch.int16)[:3]
     if n:
-        od = torch.from_numpy(o).to(dev)  # alive until the launch is queued; the copy is stream-ordered
-        lo, hi = (int(clip[0]), int(clip[1])) if clip is not None else (0, 0)
+        (od,) = _upload(dev, o)
         # HBM bytes: the chips' windows of the tile and the Fmask read, the chips and the validity plane written
         _call("ig_chip_cut", float(n) * S * S * (4 * TC + (T if fmask is not None else 0) + 1), _p(tile), _p(fmask), _p(od), n, int(T), TC // int(T),
-              H, W, int(S), int(mask_bits), C.STRATEGIES[strategy], int(no_data_value), int(clip is not None), lo, hi, _p(chips), _p(valid),
-              _p(plane), _stream())
+              H, W, int(S), int(mask_bits), C.STRATEGIES[strategy], int(no_data_value), *_opt_pair(clip, int), _p(chips), _p(valid), _p(plane),
+              _stream())
     return chips, valid, plane
 
 
@@ -1541,8 +1579,6 @@ def s2_chip_cut(bands, starts, geom, scl, scl_starts, scl_geom, origins, S: int,
     ``scl_geom`` (T of each) and ``origins`` (n, 2) as host arrays: they are checked here (every plane inside its buffer, every chip
     wholly inside the output grid ``out_grid`` = (H_o, W_o, p_o)) and uploaded.
     -> (chips (n, T * C, S, S) uint16, valid_values (n,) int32, validity (n, S, S) uint8)."""
-    import numpy as np
-
     from . import s2_chips as S2
 
     assert bands.dtype == torch.uint16 and bands.dim() == 1, "the band planes are one packed 1-D uint16 buffer"
@@ -1552,18 +1588,14 @@ def s2_chip_cut(bands, starts, geom, scl, scl_starts, scl_geom, origins, S: int,
     n, TC, S = o.shape[0], g.shape[0], int(S)
     Ho, Wo, po = (int(v) for v in out_grid)
     dev = bands.device
-    chips, plane, valid = _chip_outputs(None, dev, (n, TC, S, S), torch.uint16)[:3]
+    chips, valid, plane = _chip_outputs(None, dev, (n, TC, S, S), torch.uint16)[:3]
     if n:
-        # alive until the launch is queued; the copies are stream-ordered
-        od = torch.from_numpy(o).to(dev)
-        gd = torch.from_numpy(np.ascontiguousarray(np.concatenate([g, sg]) if scl is not None else g)).to(dev)
-        sd = torch.from_numpy(st).to(dev)
-        ssd = torch.from_numpy(sst).to(dev) if scl is not None else None
-        lo, hi = (int(valid_range[0]), int(valid_range[1])) if valid_range is not None else (0, 0)
+        od, gd = _upload(dev, o, np.concatenate([g, sg]) if scl is not None else g)  # one geometry table: the bands' rows, then the SCL planes'
+        sd, ssd = _upload(dev, st, sst) if scl is not None else (*_upload(dev, st), None)
         # HBM bytes: the chips and the validity plane written, the bands read at their own resolution (at most the bytes written)
         _call("ig_s2_chip_cut", float(n) * S * S * (4 * TC + (T if scl is not None else 0) + 1), _p(bands), _p(sd), _p(scl), _p(ssd), _p(gd),
               _p(od), n, int(T), TC // int(T), Ho, Wo, po, S, int(class_bits), S2.STRATEGIES[strategy], int(no_data_value), int(boa_offset),
-              int(valid_range is not None), lo, hi, _p(chips), _p(valid), _p(plane), _stream())
+              *_opt_pair(valid_range, int), _p(chips), _p(valid), _p(plane), _stream())
     return chips, valid, plane
 
 
@@ -1572,8 +1604,6 @@ def chip_labels(origins, S: int, ptr, pts, labels, w: int, validity, valid_bit: 
     ``labels`` (P,) int16 | float32 as host arrays: they are checked here (ptr monotone, every point inside its chip, every index inside
     the labels) and uploaded; ``validity`` the (n, S, S) uint8 plane of :func:`chip_cut` on the device, or None with ``valid_bit`` 0.
     -> (maps (n, S, S) of the labels' dtype, valid_labels (n,) int32, hist (n, K) int32 or None)."""
-    import numpy as np
-
     from . import chips as C
 
     labels = np.ascontiguousarray(labels)
@@ -1589,10 +1619,9 @@ def chip_labels(origins, S: int, ptr, pts, labels, w: int, validity, valid_bit: 
     valid = torch.zeros((n,), dtype=torch.int32, device=dev)
     hist = torch.zeros((n, K), dtype=torch.int32, device=dev) if K else None
     if n:
-        up = lambda a: torch.from_numpy(a if a.size else np.zeros(4, dtype=a.dtype)).to(dev)  # noqa: E731  an empty list still needs a pointer
-        meta = [up(o), up(p), up(q.reshape(-1)), up(labels)]  # alive until the launch is queued; the copies are stream-ordered
-        _call("ig_chip_labels", float(n) * S * S * (labels.itemsize + (validity is not None)), _p(meta[0]), n, int(S), _p(meta[1]), _p(meta[2]),
-              _p(meta[3]), labels.shape[0], labels.itemsize, int(w), _p(validity), int(valid_bit), int(K), _p(maps), _p(valid), _p(hist), _stream())
+        (od, pd, qd), (ld,) = _upload(dev, o, p, q.reshape(-1)), _upload(dev, labels)
+        _call("ig_chip_labels", float(n) * S * S * (labels.itemsize + (validity is not None)), _p(od), n, int(S), _p(pd), _p(qd), _p(ld),
+              labels.shape[0], labels.itemsize, int(w), _p(validity), int(valid_bit), int(K), _p(maps), _p(valid), _p(hist), _stream())
     return maps, valid, hist
 
 
@@ -1604,8 +1633,6 @@ def chip_warp(tile, fmask, src_crs, src_grid, dst_crs, dst_grids, S: int, T: int
     int16, valid_values (n,) int32, validity (n, S, S) uint8, maps, valid_labels, hist): the last three None without labels, hist None
     with K = 0.  ``out``: a dict with any of ``chips``, ``validity``, ``maps``: contiguous tensors to write into instead of new ones
     (every element is written)."""
-    import numpy as np
-
     from . import raster_chips as R
 
     assert tile.dtype == torch.int16 and tile.dim() == 3, "a tile is (T * C, H, W) int16"
@@ -1616,21 +1643,15 @@ def chip_warp(tile, fmask, src_crs, src_grid, dst_crs, dst_grids, S: int, T: int
                                   valid_bit, K)
     n, (TC, H, W), S = dg.shape[0], tile.shape, int(S)
     dev = tile.device
-    if labels is not None and not torch.is_tensor(labels):
-        labels = torch.from_numpy(np.ascontiguousarray(labels))
-    if labels is not None:
-        labels = labels.to(dev)
-    chips, plane, valid, maps, valid_labels, hist = _chip_outputs(out, dev, (n, TC, S, S), torch.int16, labels, K)
+    labels, es = _labels_on(labels, dev)
+    outs = _chip_outputs(out, dev, (n, TC, S, S), torch.int16, labels, K)
     if n:
-        dbl = torch.from_numpy(np.concatenate([sc, sg, dc, dg.reshape(-1)])).to(dev)  # one upload; every slice 8-byte aligned
-        lo, hi = (int(clip[0]), int(clip[1])) if clip is not None else (0, 0)
-        es = labels.element_size() if labels is not None else 1
+        scd, sgd, dcd, dgd = _upload(dev, sc, sg, dc, dg.reshape(-1))
         # HBM bytes: as many tile values and Fmask bytes gathered as chip values written, the validity plane, the labels in and out
         work = float(n) * S * S * (4 * TC + (T if fmask is not None else 0) + 1 + (2 * es if labels is not None else 0))
-        _call("ig_chip_warp", work, _p(tile), _p(fmask), _p(dbl[0:5]), _p(dbl[5:9]), _p(dbl[9:14]), _p(dbl[14:]), n, int(T), TC // int(T), H, W, S,
-              int(mask_bits), R.STRATEGIES[strategy], int(no_data_value), int(clip is not None), lo, hi, _p(labels), es, int(valid_bit), int(K),
-              _p(chips), _p(valid), _p(plane), _p(maps), _p(valid_labels), _p(hist), _stream())
-    return chips, valid, plane, maps, valid_labels, hist
+        _call("ig_chip_warp", work, _p(tile), _p(fmask), _p(scd), _p(sgd), _p(dcd), _p(dgd), n, int(T), TC // int(T), H, W, S, int(mask_bits),
+              R.STRATEGIES[strategy], int(no_data_value), *_opt_pair(clip, int), *_label_tail(labels, es, valid_bit, K, outs))
+    return outs
 
 
 def s2_chip_warp(bands, starts, plane_class, class_grid, class_size, scl, scl_starts, src_crs, dst_crs, dst_grids, S: int, T: int,
@@ -1644,8 +1665,6 @@ def s2_chip_warp(bands, starts, plane_class, class_grid, class_size, scl, scl_st
     valid_values (n,) int32, validity (n, S, S) uint8, maps, valid_labels, hist): the last three None without labels, hist None with
     K = 0.  ``out``: a dict with any of ``chips``, ``validity``, ``maps``: contiguous tensors to write into instead of new ones (every
     element is written)."""
-    import numpy as np
-
     from . import s2_raster_chips as R
 
     assert bands.dtype == torch.uint16 and bands.dim() == 1, "the band planes are one packed 1-D uint16 buffer"
@@ -1657,26 +1676,18 @@ def s2_chip_warp(bands, starts, plane_class, class_grid, class_size, scl, scl_st
                                                    None if labels is None else tuple(labels.shape), lab_dtype, valid_bit, K)
     n, TC, G, S, T = dg.shape[0], st.shape[0], cg.shape[0], int(S), int(T)
     dev = bands.device
-    if labels is not None and not torch.is_tensor(labels):
-        labels = torch.from_numpy(np.ascontiguousarray(labels))
-    if labels is not None:
-        labels = labels.to(dev)
-    chips, plane, valid, maps, valid_labels, hist = _chip_outputs(out, dev, (n, TC, S, S), torch.uint16, labels, K)
+    labels, es = _labels_on(labels, dev)
+    outs = _chip_outputs(out, dev, (n, TC, S, S), torch.uint16, labels, K)
     if n:
-        # alive until the launch is queued; the copies are stream-ordered.  One upload of the doubles; every slice 8-byte aligned
-        dbl = torch.from_numpy(np.concatenate([sc, dc, cg.reshape(-1), dg.reshape(-1)])).to(dev)
-        ints = torch.from_numpy(np.concatenate([pc, cs.reshape(-1)])).to(dev)
-        sd = torch.from_numpy(st).to(dev)
-        ssd = torch.from_numpy(sst).to(dev) if scl is not None else None
-        lo, hi = (int(valid_range[0]), int(valid_range[1])) if valid_range is not None else (0, 0)
-        es = labels.element_size() if labels is not None else 1
+        scd, dcd, cgd, dgd = _upload(dev, sc, dc, cg.reshape(-1), dg.reshape(-1))
+        pcd, csd = _upload(dev, pc, cs.reshape(-1))
+        sd, ssd = _upload(dev, st, sst) if scl is not None else (*_upload(dev, st), None)
         # HBM bytes: the chips and the validity plane written, at most as many band values and SCL bytes gathered, the labels in and out
         work = float(n) * S * S * (4 * TC + (T if scl is not None else 0) + 1 + (2 * es if labels is not None else 0))
-        _call("ig_s2_chip_warp", work, _p(bands), _p(sd), _p(scl), _p(ssd), _p(ints[: pc.shape[0]]), _p(dbl[10 : 10 + 4 * G]),
-              _p(ints[pc.shape[0] :]), G, _p(dbl[0:5]), _p(dbl[5:10]), _p(dbl[10 + 4 * G :]), n, T, TC // T, S, int(class_bits),
-              R.STRATEGIES[strategy], int(no_data_value), int(boa_offset), int(valid_range is not None), lo, hi, _p(labels), es, int(valid_bit),
-              int(K), _p(chips), _p(valid), _p(plane), _p(maps), _p(valid_labels), _p(hist), _stream())
-    return chips, valid, plane, maps, valid_labels, hist
+        _call("ig_s2_chip_warp", work, _p(bands), _p(sd), _p(scl), _p(ssd), _p(pcd), _p(cgd), _p(csd), G, _p(scd), _p(dcd), _p(dgd), n, T, TC // T, S,
+              int(class_bits), R.STRATEGIES[strategy], int(no_data_value), int(boa_offset), *_opt_pair(valid_range, int),
+              *_label_tail(labels, es, valid_bit, K, outs))
+    return outs
 
 
 def s1_chip_cut(planes, starts, scene_crs, scene_grid, scene_size, date_scenes, dst_crs, dst_grid, origins, S: int, no_data_value: float = -1.0,
@@ -1686,8 +1697,6 @@ def s1_chip_cut(planes, starts, scene_crs, scene_grid, scene_size, date_scenes, 
     (N, 2) = (H, W), ``dst_crs``, ``dst_grid`` (4,) and ``origins`` (n, 2) as host values: they are checked here (every plane inside the
     buffer) and uploaded.  -> (chips (n, T * C, S, S) float32, valid_values (n,) int32, validity (n, S, S) uint8).  ``out``: a dict with
     any of ``chips``, ``validity``: contiguous tensors to write into instead of new ones (every element is written)."""
-    import numpy as np
-
     from . import s1_chips as V
 
     assert planes.dtype == torch.float32 and planes.dim() == 1, "the planes are one packed 1-D float32 buffer"
@@ -1696,18 +1705,15 @@ def s1_chip_cut(planes, starts, scene_crs, scene_grid, scene_size, date_scenes, 
                                                                             src_nodata, clip)
     n, N, S = o.shape[0], sg.shape[0], int(S)
     dev = planes.device
-    chips, plane, valid = _chip_outputs(out, dev, (n, T * C, S, S), torch.float32)[:3]
+    chips, valid, plane = _chip_outputs(out, dev, (n, T * C, S, S), torch.float32)[:3]
     if n:
-        # alive until the launch is queued; the copies are stream-ordered.  One upload of the doubles; every slice 8-byte aligned
-        dbl = torch.from_numpy(np.concatenate([dc, dg, sc.reshape(-1), sg.reshape(-1)])).to(dev)
-        ints = torch.from_numpy(np.concatenate([ss.reshape(-1), o.reshape(-1)])).to(dev)
-        sd = torch.from_numpy(st).to(dev)
-        lo, hi = (float(clip[0]), float(clip[1])) if clip is not None else (0.0, 0.0)
+        dcd, dgd, scd, sgd = _upload(dev, dc, dg, sc.reshape(-1), sg.reshape(-1))
+        ssd, od = _upload(dev, ss.reshape(-1), o.reshape(-1))
+        (sd,) = _upload(dev, st)
         # HBM bytes: the chips and the validity plane written, at least as many values gathered
         work = float(n) * S * S * (8 * T * C + 1)
-        _call("ig_s1_chip_cut", work, _p(planes), _p(sd), _p(dbl[9 : 9 + 5 * N]), _p(dbl[9 + 5 * N :]), _p(ints[: 2 * N]), N, int(first_bits),
-              _p(dbl[0:5]), _p(dbl[5:9]), _p(ints[2 * N :]), n, T, C, S, float(nd), int(snd is not None), float(snd) if snd is not None else 0.0,
-              int(clip is not None), lo, hi, _p(chips), _p(valid), _p(plane), _stream())
+        _call("ig_s1_chip_cut", work, _p(planes), _p(sd), _p(scd), _p(sgd), _p(ssd), N, int(first_bits), _p(dcd), _p(dgd), _p(od), n, T, C, S,
+              float(nd), *_opt_value(snd), *_opt_pair(clip, float), _p(chips), _p(valid), _p(plane), _stream())
     return chips, valid, plane
 
 
@@ -1719,8 +1725,6 @@ def s1_chip_warp(planes, starts, scene_crs, scene_grid, scene_size, date_scenes,
     (n, S, S) int8 | float32 as a device tensor or a host array.  -> (chips (n, T * C, S, S) float32, valid_values (n,) int32, validity
     (n, S, S) uint8, maps, valid_labels, hist): the last three None without labels, hist None with K = 0.  ``out``: a dict with any of
     ``chips``, ``validity``, ``maps``: contiguous tensors to write into instead of new ones (every element is written)."""
-    import numpy as np
-
     from . import s1_raster_chips as R
 
     assert planes.dtype == torch.float32 and planes.dim() == 1, "the planes are one packed 1-D float32 buffer"
@@ -1731,25 +1735,16 @@ def s1_chip_warp(planes, starts, scene_crs, scene_grid, scene_size, date_scenes,
                                                                           valid_bit, K)
     n, N, S = dg.shape[0], sg.shape[0], int(S)
     dev = planes.device
-    if labels is not None and not torch.is_tensor(labels):
-        labels = torch.from_numpy(np.ascontiguousarray(labels))
-    if labels is not None:
-        labels = labels.to(dev)
-    chips, plane, valid, maps, valid_labels, hist = _chip_outputs(out, dev, (n, T * C, S, S), torch.float32, labels, K)
+    labels, es = _labels_on(labels, dev)
+    outs = _chip_outputs(out, dev, (n, T * C, S, S), torch.float32, labels, K)
     if n:
-        # alive until the launch is queued; the copies are stream-ordered.  One upload of the doubles; every slice 8-byte aligned
-        dbl = torch.from_numpy(np.concatenate([dc, sc.reshape(-1), sg.reshape(-1), dg.reshape(-1)])).to(dev)
-        ints = torch.from_numpy(np.ascontiguousarray(ss.reshape(-1))).to(dev)
-        sd = torch.from_numpy(st).to(dev)
-        lo, hi = (float(clip[0]), float(clip[1])) if clip is not None else (0.0, 0.0)
-        es = labels.element_size() if labels is not None else 1
+        dcd, scd, sgd, dgd = _upload(dev, dc, sc.reshape(-1), sg.reshape(-1), dg.reshape(-1))
+        (ssd,), (sd,) = _upload(dev, ss.reshape(-1)), _upload(dev, st)
         # HBM bytes: the chips and the validity plane written, at least as many values gathered, the labels in and out
         work = float(n) * S * S * (8 * T * C + 1 + (2 * es if labels is not None else 0))
-        _call("ig_s1_chip_warp", work, _p(planes), _p(sd), _p(dbl[5 : 5 + 5 * N]), _p(dbl[5 + 5 * N : 5 + 9 * N]), _p(ints), N, int(first_bits),
-              _p(dbl[0:5]), _p(dbl[5 + 9 * N :]), n, T, C, S, float(nd), int(snd is not None), float(snd) if snd is not None else 0.0,
-              int(clip is not None), lo, hi, _p(labels), es, int(valid_bit), int(K), _p(chips), _p(valid), _p(plane), _p(maps),
-              _p(valid_labels), _p(hist), _stream())
-    return chips, valid, plane, maps, valid_labels, hist
+        _call("ig_s1_chip_warp", work, _p(planes), _p(sd), _p(scd), _p(sgd), _p(ssd), N, int(first_bits), _p(dcd), _p(dgd), n, T, C, S, float(nd),
+              *_opt_value(snd), *_opt_pair(clip, float), *_label_tail(labels, es, valid_bit, K, outs))
+    return outs
 
 
 def composite(bands, starts, fmasks, fmask_starts, step_ptr, C: int, shape: Tuple[int, int], mask_bits: int = 0, no_data_value: int = -9999,
@@ -1758,8 +1753,6 @@ def composite(bands, starts, fmasks, fmask_starts, step_ptr, C: int, shape: Tupl
     as 1-D tensors on the device; ``starts`` (N * C,), ``fmask_starts`` (N,) and ``step_ptr`` (T + 1,) as host arrays: they are checked
     here (every plane of ``shape`` = (H, W) inside its buffer, step_ptr ascending from 0, at most 16 candidates per step) and uploaded.
     -> (composite (T, C, H, W) int16, count (T, H, W) uint8, source (T, H, W) uint8, hist (T, 17) int32)."""
-    import numpy as np
-
     from . import composite as K
 
     assert bands.dtype == torch.int16 and bands.dim() == 1, "the band planes are one packed 1-D int16 buffer"
@@ -1772,15 +1765,34 @@ def composite(bands, starts, fmasks, fmask_starts, step_ptr, C: int, shape: Tupl
     source = torch.empty((T, H, W), dtype=torch.uint8, device=dev)
     hist = torch.zeros((T, K.CELLS), dtype=torch.int32, device=dev)
     if T and H * W:
-        # alive until the launch is queued; the copies are stream-ordered.  One upload of the offsets; both slices 8-byte aligned
-        tab = torch.from_numpy(np.concatenate([st, fst] if fst is not None else [st])).to(dev)
-        pd = torch.from_numpy(ptr).to(dev)
+        sd, fd = _upload(dev, st, fst) if fst is not None else (*_upload(dev, st), None)
+        (pd,) = _upload(dev, ptr)
         # HBM bytes: every value and Fmask byte of every candidate read once, the composites, counts and sources written
         work = float(H * W) * (N * (2 * C + 1 if fst is not None else 2 * C) + T * (2 * C + 2))
-        _call("ig_composite", work, _p(bands) if N else None, _p(tab[: N * C]) if N else None, _p(fmasks) if fst is not None and N else None,
-              _p(tab[N * C :]) if fst is not None and N else None, _p(pd), T, N, max_m, C, H, W, int(mask_bits), int(no_data_value), int(min_clear),
-              K.METHODS[method], _p(comp), _p(count), _p(source), _p(hist), _stream())
+        # without scenes the kernel takes null for them and their offsets
+        _call("ig_composite", work, _p(bands) if N else None, _p(sd) if N else None, _p(fmasks) if fst is not None and N else None,
+              _p(fd) if N else None, _p(pd), T, N, max_m, C, H, W, int(mask_bits), int(no_data_value), int(min_clear), K.METHODS[method], _p(comp),
+              _p(count), _p(source), _p(hist), _stream())
     return comp, count, source, hist
+
+
+def _s1_filter(entry: str, planes, starts, sizes, window, method, looks, src_nodata, scale, out):
+    """``s1_speckle`` and ``s1_refined_lee``: the same checks, tables and outputs; ``ig_s1_speckle`` also takes the half window and the
+    method's code."""
+    from . import s1_filter as F
+
+    assert planes.dtype == torch.float32 and planes.dim() == 1, "the planes are one packed 1-D float32 buffer"
+    assert (method == "refined_lee") == (entry == "ig_s1_refined_lee"), "refined_lee has an entry point of its own: ops.s1_refined_lee"
+    st, ss, h, code, lk, snd, to_db = F.check_speckle(int(planes.shape[0]), starts, sizes, window, method, looks, src_nodata, scale)
+    N, total = st.shape[0], int(planes.shape[0])
+    out, counts, pixels = _plane_outputs(planes, ss, out, 2)
+    if N:
+        tp = F.tile_table(ss)
+        (sd, td), (zd,) = _upload(planes.device, st, tp), _upload(planes.device, ss.reshape(-1))
+        # HBM bytes: every value read once (the halo comes from the caches) and written once
+        _call(entry, 8.0 * pixels, _p(planes), _p(sd), _p(zd), _p(td), N, total, int(tp[-1]), *((h, code) if entry == "ig_s1_speckle" else ()),
+              float(lk), *_opt_value(snd), to_db, _p(out), _p(counts), _stream())
+    return out, counts
 
 
 def s1_speckle(planes, starts, sizes, window: int = 7, method: str = "lee", looks: float = 4.4, src_nodata=None, scale: str = "linear",
@@ -1790,55 +1802,15 @@ def s1_speckle(planes, starts, sizes, window: int = 7, method: str = "lee", look
     the prefix table of tiles.  -> (out: float32 with the layout of ``planes``, elements outside every plane 0; counts (N, 2) int32: the
     present outputs and the pixels the dB step dropped).  ``out``: a contiguous float32 tensor of the size of ``planes`` to write into
     instead of a new one (only the elements of the planes are written)."""
-    import numpy as np
-
-    from . import s1_filter as F
-
-    assert planes.dtype == torch.float32 and planes.dim() == 1, "the planes are one packed 1-D float32 buffer"
-    assert method != "refined_lee", "refined_lee has an entry point of its own: ops.s1_refined_lee"
-    st, ss, h, code, lk, snd, to_db = F.check_speckle(int(planes.shape[0]), starts, sizes, window, method, looks, src_nodata, scale)
-    N, dev, total = st.shape[0], planes.device, int(planes.shape[0])
-    pixels = int((ss[:, 0].astype(np.int64) * ss[:, 1]).sum())
-    if out is None:
-        out = (torch.empty if pixels == total else torch.zeros)(total, dtype=torch.float32, device=dev)
-    assert out.dtype == torch.float32 and out.shape == planes.shape and out.device == dev, "out is a float32 tensor of the size of planes"
-    counts = torch.zeros((N, 2), dtype=torch.int32, device=dev)
-    if N:
-        tp = F.tile_table(ss)
-        # alive until the launch is queued; the copies are stream-ordered.  One upload of the int64 tables; both slices 8-byte aligned
-        tab = torch.from_numpy(np.concatenate([st, tp])).to(dev)
-        sd = torch.from_numpy(ss.reshape(-1)).to(dev)
-        # HBM bytes: every value read once (the halo comes from the caches) and written once
-        work = 8.0 * pixels
-        _call("ig_s1_speckle", work, _p(planes), _p(tab[:N]), _p(sd), _p(tab[N:]), N, total, int(tp[-1]), h, code, float(lk), int(snd is not None),
-              float(snd) if snd is not None else 0.0, to_db, _p(out), _p(counts), _stream())
-    return out, counts
+    return _s1_filter("ig_s1_speckle", planes, starts, sizes, window, method, looks, src_nodata, scale, out)
 
 
 def s1_refined_lee(planes, starts, sizes, looks: float = 4.4, src_nodata=None, scale: str = "linear", out=None):
     """``ig_s1_refined_lee`` (include/instageo_hip.h): the refined Lee filter on the packed planes of :func:`s1_speckle`, with the same
     host-side checks of ``starts`` and ``sizes``, the same tile table and the same outputs.  The window is 7 x 7."""
-    import numpy as np
+    from .s1_filter import REFINED_WINDOW
 
-    from . import s1_filter as F
-
-    assert planes.dtype == torch.float32 and planes.dim() == 1, "the planes are one packed 1-D float32 buffer"
-    st, ss, _, _, lk, snd, to_db = F.check_speckle(int(planes.shape[0]), starts, sizes, F.REFINED_WINDOW, "refined_lee", looks, src_nodata, scale)
-    N, dev, total = st.shape[0], planes.device, int(planes.shape[0])
-    pixels = int((ss[:, 0].astype(np.int64) * ss[:, 1]).sum())
-    if out is None:
-        out = (torch.empty if pixels == total else torch.zeros)(total, dtype=torch.float32, device=dev)
-    assert out.dtype == torch.float32 and out.shape == planes.shape and out.device == dev, "out is a float32 tensor of the size of planes"
-    counts = torch.zeros((N, 2), dtype=torch.int32, device=dev)
-    if N:
-        tp = F.tile_table(ss)
-        # alive until the launch is queued; the copies are stream-ordered.  One upload of the int64 tables; both slices 8-byte aligned
-        tab = torch.from_numpy(np.concatenate([st, tp])).to(dev)
-        sd = torch.from_numpy(ss.reshape(-1)).to(dev)
-        work = 8.0 * pixels  # HBM bytes, as for ig_s1_speckle
-        _call("ig_s1_refined_lee", work, _p(planes), _p(tab[:N]), _p(sd), _p(tab[N:]), N, total, int(tp[-1]), float(lk), int(snd is not None),
-              float(snd) if snd is not None else 0.0, to_db, _p(out), _p(counts), _stream())
-    return out, counts
+    return _s1_filter("ig_s1_refined_lee", planes, starts, sizes, REFINED_WINDOW, "refined_lee", looks, src_nodata, scale, out)
 
 
 def s1_temporal(planes, starts, sizes, group, date, offsets, window: int = 7, src_nodata=None, scale: str = "linear", out=None):
@@ -1849,32 +1821,23 @@ def s1_temporal(planes, starts, sizes, group, date, offsets, window: int = 7, sr
     counts (N, 4) int32: the present outputs, the pixels the dB step dropped, the pixels passed through and the present outputs where one
     date contributed).  ``out``: a contiguous float32 tensor of the size of ``planes`` to write into instead of a new one (only the
     elements of the planes are written)."""
-    import numpy as np
-
     from . import s1_temporal as Q
 
     assert planes.dtype == torch.float32 and planes.dim() == 1, "the planes are one packed 1-D float32 buffer"
     st, ss, h, snd, to_db, T = Q.check_temporal(int(planes.shape[0]), starts, sizes, group, date, offsets, window, src_nodata, scale)
     N, dev, total = st.shape[0], planes.device, int(planes.shape[0])
-    pixels = int((ss[:, 0].astype(np.int64) * ss[:, 1]).sum())
-    if out is None:
-        out = (torch.empty if pixels == total else torch.zeros)(total, dtype=torch.float32, device=dev)
-    assert out.dtype == torch.float32 and out.shape == planes.shape and out.device == dev, "out is a float32 tensor of the size of planes"
-    counts = torch.zeros((N, 4), dtype=torch.int32, device=dev)
+    out, counts, pixels = _plane_outputs(planes, ss, out, 4)
     if N:
         G = T.lattice.shape[0]
-        # alive until the launch is queued; the copies are stream-ordered.  One upload per element width; every int64 slice 8-byte aligned
-        tab = torch.from_numpy(np.concatenate([st, T.tile_ptr])).to(dev)
-        ints = torch.from_numpy(np.concatenate([ss.reshape(-1), T.place.reshape(-1), T.lattice.reshape(-1), T.member_ptr, T.members])).to(dev)
-        sd, pl, la, mp, mm = ints[: 2 * N], ints[2 * N : 5 * N], ints[5 * N : 5 * N + 2 * G], ints[5 * N + 2 * G : 5 * N + 3 * G + 1], ints[5 * N + 3 * G + 1 :]
+        sd, td = _upload(dev, st, T.tile_ptr)
+        zd, pl, la, mp, mm = _upload(dev, ss.reshape(-1), T.place.reshape(-1), T.lattice.reshape(-1), T.member_ptr, T.members)
         # HBM bytes: every value read once (the second sweep and the halo come from the caches) and written once
-        work = 8.0 * pixels
-        _call("ig_s1_temporal", work, _p(planes), _p(tab[:N]), _p(sd), _p(pl), _p(la), _p(mp), _p(mm), _p(tab[N:]), N, G, N, total,
-              int(T.tile_ptr[-1]), h, int(snd is not None), float(snd) if snd is not None else 0.0, to_db, _p(out), _p(counts), _stream())
+        _call("ig_s1_temporal", 8.0 * pixels, _p(planes), _p(sd), _p(zd), _p(pl), _p(la), _p(mp), _p(mm), _p(td), N, G, N, total,
+              int(T.tile_ptr[-1]), h, *_opt_value(snd), to_db, _p(out), _p(counts), _stream())
     return out, counts
 
 
-TILE_STYLES ={"palette": 0, "ramp": 1, "rgb": 2}  # include/instageo_hip.h
+TILE_STYLES = {"palette": 0, "ramp": 1, "rgb": 2}  # include/instageo_hip.h
 TILE_MAX_LEVELS = 13
 
 
@@ -1886,8 +1849,6 @@ def tile_render(levels, src_crs, src_grid, tile_grids, tile_level, tile: int, st
     and ``tile_level`` (n,) int32 as host values; ``lut`` (256, 4) uint8 (host array or device tensor); ``rescale`` = (lo, hi).  The level
     shapes are checked here, so that no read can leave a level.  -> (rgba (n, tile, tile, 4) uint8, opaque (n,) int32).  ``out``: a
     contiguous (n, tile, tile, 4) uint8 tensor to write into instead of a new one (every pixel is written)."""
-    import numpy as np
-
     code = TILE_STYLES.get(style)
     if code is None:
         raise ValueError(f"style must be one of {tuple(TILE_STYLES)} (got {style!r})")
@@ -1941,14 +1902,12 @@ def tile_render(levels, src_crs, src_grid, tile_grids, tile_level, tile: int, st
     opaque = torch.zeros((n,), dtype=torch.int32, device=dev)
     if n:
         sc, sg = _warp_doubles(src_crs, 5, "src_crs"), _warp_doubles(src_grid, 4, "src_grid")
-        # alive until the launch is queued; the copies are stream-ordered
-        dbl = torch.from_numpy(np.concatenate([sc, sg, grids.reshape(-1)])).to(dev)
-        table = torch.tensor([_p(lv) for lv in levels], dtype=torch.int64).to(dev)
-        lv_d = torch.from_numpy(lvl).to(dev)
+        (scd, sgd, gd), (lv_d,) = _upload(dev, sc, sg, grids.reshape(-1)), _upload(dev, lvl)
+        table = torch.tensor([_p(lv) for lv in levels], dtype=torch.int64).to(dev)  # alive until the launch is queued, as the uploads are
         # HBM bytes: the tiles written and as many source values gathered
         _call("ig_tile_render", float(n) * tile * tile * (4 + first.element_size() * bands), _p(table), len(levels), first.element_size(), bands, H, W,
-              _p(dbl[0:5]), _p(dbl[5:9]), _p(dbl[9:]), _p(lv_d), n, tile, code, _p(lut), int(ncolors), int(fill), lo, hi - lo, order[0], order[1],
-              order[2], _p(rgba), _p(opaque), _stream())
+              _p(scd), _p(sgd), _p(gd), _p(lv_d), n, tile, code, _p(lut), int(ncolors), int(fill), lo, hi - lo, order[0], order[1], order[2],
+              _p(rgba), _p(opaque), _stream())
     return rgba, opaque
 
 
@@ -1997,8 +1956,6 @@ def label_limit(labels, ptr, pts, ignore_index: int, K: int = 0):
     """``ig_label_limit`` (include/instageo_hip.h): ``labels`` (n, H, W) int16 | float32 on the device, ``ptr`` (n + 1,) and ``pts``
     (P, 2) = (row, col) as host arrays: ptr is checked here and the points outside their map are dropped, then both are uploaded.
     -> (out like labels, valid_labels (n,) int32, hist (n, K) int32 or None)."""
-    import numpy as np
-
     from . import clean as C
 
     out, valid, hist = _label_outputs(labels, K)
@@ -2006,11 +1963,10 @@ def label_limit(labels, ptr, pts, ignore_index: int, K: int = 0):
     C.check_label_args((n, H, W), "int16" if labels.dtype == torch.int16 else "float32", ignore_index, K)
     p, q = C.check_points(n, H, W, ptr, pts)
     if n and H and W:
-        up = lambda a: torch.from_numpy(a if a.size else np.zeros(4, dtype=a.dtype)).to(labels.device)  # noqa: E731  an empty list still needs a pointer
-        meta = [up(p), up(q.reshape(-1))]  # alive until the launch is queued; the copies are stream-ordered
+        pd, qd = _upload(labels.device, p, q.reshape(-1))
         es = labels.element_size()
-        _call("ig_label_limit", float(n) * H * W * 2 * es, _p(labels), n, H, W, es, _p(meta[0]), _p(meta[1]), q.shape[0], int(ignore_index),
-              int(K), _p(out), _p(valid), _p(hist), _stream())
+        _call("ig_label_limit", float(n) * H * W * 2 * es, _p(labels), n, H, W, es, _p(pd), _p(qd), q.shape[0], int(ignore_index), int(K), _p(out),
+              _p(valid), _p(hist), _stream())
     return out, valid, hist
 
 
@@ -2023,8 +1979,6 @@ def split_assign(pts, centres, assign, check_range: bool = True):
     (``assign`` is read and overwritten), ``centres`` (K, 3) int32 as a host array or a tensor -> (sums (K, 4) int64: sum x, sum y, sum z,
     count per centre; changed (1,) int32), both on the device.  ``check_range=False`` skips the device reduction that checks
     |coordinate| <= 2^29 of ``pts`` (a caller that quantised them itself)."""
-    import numpy as np
-
     from . import split as S
 
     cen = np.ascontiguousarray(centres.cpu().numpy() if torch.is_tensor(centres) else centres)

@@ -97,6 +97,16 @@ def test_chip_labels_equal_the_twin(S, w, counts, dtype):
         assert all(torch.equal(x, y) for x, y in zip(a[:2], b[:2])) and (a[2] is None or torch.equal(a[2], b[2]))
 
 
+def test_chip_labels_without_points_are_all_no_data():
+    """No point in any chip: the kernel is handed the lists' stand-in pointers and a count of 0."""
+    v = torch.full((1, 8, 8), 3, dtype=torch.uint8, device="cuda")
+    none = np.zeros((0, 3), dtype=np.int32)
+    for labels in (np.zeros(0, dtype=np.int16), np.array([1, 2], dtype=np.int16)):
+        got = chips.label_maps([(0, 0)], 8, [0, 0], none, labels, 1, v, "any", "seg", 8)
+        _same(got, CR.label_maps([(0, 0)], 8, [0, 0], none, labels, 1, v.cpu().numpy(), 1, 8, np.int16))
+        assert (got[0] == -1).all() and not got[1].any() and not got[2].any()
+
+
 def test_both_kernels_are_deterministic():
     k, tile, fmask = cut_case("t3c2_70x75_s32")
     t, f = torch.from_numpy(tile).cuda(), torch.from_numpy(fmask).cuda()

@@ -134,6 +134,15 @@ def test_label_limit_equals_the_twin():
     _same(clean.limit_labels(_dev(f), ptr, pts, -1), R.limit(f, ptr, pts, -1))
 
 
+def test_label_limit_without_points_keeps_nothing():
+    """No point in any map: the kernel is handed the list's stand-in pointer and a count of 0."""
+    labels = R.make_labels(1, 8, 8, 0.5, seed=6)
+    none = np.zeros((0, 2), dtype=np.int32)
+    got = clean.limit_labels(_dev(labels), [0, 0], none, -1, 7)
+    _same(got, R.limit(labels, [0, 0], none, -1, 7))
+    assert (got[0] == -1).all() and not got[1].any() and not got[2].any()
+
+
 def test_label_limit_kernel_ignores_points_outside_the_map():
     """Points outside the map handed straight to the entry point (the host wrapper would drop them): they paint nothing."""
     labels, ptr, pts = _limit_case()
